@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — particle-steps/s of the PCISPH step path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one rank per GPU over RCCL. Either the driver starts the ranks (`python -m torch.distributed.run ... bench.py
 --gpus N`: WORLD_SIZE is set, this file is a rank) or this file does: called from a plain shell with --gpus N > 1 and no
@@ -13,7 +13,10 @@ loop + integration) of BASELINE config #4, the 16M-particle pure-liquid box of S
 the boundary shell, box 78h x 50h x 470h, wide cell ids) — the configuration the metric and both north_star targets are
 quoted on — through the C ABI of libsphmi.so with all state resident in HBM. The same box is used for every --gpus N
 (N > 1: cut into N z-slabs, 4-layer halo exchanged once per step over RCCL), so the series is STRONG scaling.
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step = wall time of one timed step, ...), the workload's config and the library that ran.
+--dump-outputs DIR (N = 1) then also writes what the last timed step left a caller (dump_outputs below). With --full the line
+also carries
   roofline      the density pass (pcisph_computeDensity): algorithmic bytes = 132 B/particle (32 distances + 1 write,
                 SURVEY §8d) / its mean launch duration, measured with HIP events on the solver's stream inside real steps
                 (2.18 GB per launch: 8x the Infinity Cache, i.e. an HBM figure)
@@ -25,6 +28,7 @@ Rank 0 prints ONE JSON line. Besides the contract fields it carries
                 the worm scene of config #3 (elastic matter, membranes, muscles on); a 0.77 M-particle liquid column after
                 1,500 steps of collapse (disordered state: the exact-walk counters of findNeighbors are reported)
   rccl_ranks, devices, halo   (N > 1) world size as the process group reports it, each rank's device, per-rank exchange figures
+                (every run); the check that the owned sets still partition the particles (--full)
 """
 import argparse
 import hashlib
@@ -54,6 +58,10 @@ WORKLOADS = {
 DAM_BREAK = ((120.0, 50.0, 50.0), (80, 90, 100), 0xffffffff)  # extra block: 0.72 M liquid particles in a column at low x
 
 DEFAULT_WORKLOAD = "config4_16M_box"
+
+# --dump-outputs: above this many particles a fixed, seeded sample of particle ids is written (44 MB of .npy files at most)
+DUMP_SAMPLE_ROWS = 1000000
+DUMP_SAMPLE_SEED = 20261016
 
 # Algorithmic bytes per particle of every launch of a stage in one step (pure liquid, 3 predict-correct iterations), for the
 # layout the kernels actually use: neighbour ids as 16-bit offsets (64 B per row + a 4-byte base), distances 128 B per row.
@@ -213,19 +221,29 @@ def parse_args(argv):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS) + ["weak"],
                     help="default: config #4 for every --gpus N (strong scaling); 'weak': 1M-particle column per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (positions, velocities, densities) as DIR/<name>.npy (--gpus 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-stage pass and roofline, read-back loops and p50, "
+                         "CPU baseline, extra blocks, multi-GPU partition check")
     ap.add_argument("--cpu-steps", type=int, default=-1,
-                    help="steps of the CPU baseline (default: ~10 s of work on 16 cores, e.g. 4 at 16.5 M; 0 = skip)")
-    ap.add_argument("--no-stage-pass", action="store_true", help="skip the second, per-stage-timed pass")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra blocks (config #2, config #3, evolved dam break)")
+                    help="--full: steps of the CPU baseline (default: ~10 s of work on 16 cores, e.g. 4 at 16.5 M; 0 = skip)")
+    ap.add_argument("--no-stage-pass", action="store_true", help="--full: skip the second, per-stage-timed pass")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra blocks (config #2, config #3, evolved dam break)")
     ap.add_argument("--allow-diagnostic-lib", action="store_true", help="run although SPHMI_LIB names a timing-only (invalid-results) build")
     ap.add_argument("--dry-run", action="store_true",
                     help="N > 1 only: launcher, rendezvous, cuts and per-rank scene slices, no solver (needs no GPU; tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
     argv = sys.argv[1:]
     args = parse_args(argv)
+    if args.dump_outputs is not None and args.gpus > 1:
+        sys.exit("bench.py: --dump-outputs is for --gpus 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, argv))
     rank_main(args)
@@ -363,10 +381,14 @@ def rank_main(args):
         wall = float(t.item())
     ms_per_step = wall * 1e3 / args.steps
     value = N * args.steps / wall  # N = particles of the whole job (all ranks)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, solver, np, N)
+        beat("outputs written")
 
+    # everything below up to the result line runs with --full only
     # second pass: the same steps with a HIP event pair around every stage (kept out of `value`)
     stages_ms, stages_frac, roofline, sort_passes = {}, {}, None, None
-    if not args.no_stage_pass:
+    if args.full and not args.no_stage_pass:
         solver.set_stage_timing(True)
         solver.reset_stage_times()
         k2 = max(5, min(args.steps, 20))
@@ -428,7 +450,7 @@ def rank_main(args):
     #                                             16.5 M that nothing can hide, i.e. +0.13 ms per step over 50 steps)
     #   ms_per_step_same_pass_without_readback    the interleaved plain loop, same method as the steady-state figure
     p50_ms, readback_ms, readback_blocking_ms, readback_plain_ms, readback_wall_ms = None, None, None, None, None
-    if world == 1:
+    if args.full and world == 1:
         host_pos = np.empty((N, 4), np.float32)
         solver.read_position_buffer_async(host_pos)  # (page-locks host_pos once, outside the timed loops)
         solver.wait_position_buffer()
@@ -479,6 +501,7 @@ def rank_main(args):
     partition_ok = None
     if decomposition is not None:
         decomposition.finish()
+    if args.full and decomposition is not None:
         pos_l, vel_l, gid_l, owned_l = solver.slab_read()
         m = owned_l.astype(bool)
         stats = torch.tensor([float(m.sum()), float(np.isfinite(pos_l[m]).all() and np.isfinite(vel_l[m]).all()),
@@ -501,7 +524,7 @@ def rank_main(args):
     cpu_steps = args.cpu_steps
     if cpu_steps < 0:  # ~10 s on 16 cores at the 6.9e6 particle-steps/s of round 1: 4 steps at 16.5 M, 80 at 1 M
         cpu_steps = int(max(2, min(80, round(6.9e7 / N))))
-    if rank == 0 and cpu_steps > 0 and world == 1:
+    if args.full and rank == 0 and cpu_steps > 0 and world == 1:
         cores = host_cores()
         ora = scenes.oracle_for(sc, threads=cores)
         ora.step()  # warm-up (page faults, first-touch)
@@ -530,7 +553,7 @@ def rank_main(args):
 
     # extra blocks, GPU only, N = 1 only, outside `value`
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         solver.close()
         sc = None
         if workload_name != "config2_1M_cube":
@@ -549,15 +572,18 @@ def rank_main(args):
                        "pcisph_iterations": cfg.maxIteration,
                        "parallelism": "1 GPU" if world == 1 else
                        "%d z-slabs, 4-layer halo, one RCCL send + recv per neighbour per step" % world},
-            "device_ms_per_step": round(dev_ms / args.steps, 4),
-            "ms_per_step_p50": None if p50_ms is None else round(p50_ms, 4),
-            "ms_per_step_with_position_readback": None if readback_ms is None else round(readback_ms, 4),
-            "ms_per_step_with_blocking_position_readback": None if readback_blocking_ms is None else round(readback_blocking_ms, 4),
-            "ms_per_step_with_position_readback_incl_final_copy": None if readback_wall_ms is None else round(readback_wall_ms, 4),
-            "ms_per_step_same_pass_without_readback": None if readback_plain_ms is None else round(readback_plain_ms, 4),
-            "roofline": roofline, "cpu_baseline": cpu, "stages_ms": stages_ms, "stages_frac": stages_frac,
-            "radix_sort_passes": sort_passes, "lib": lib,
+            "device_ms_per_step": round(dev_ms / args.steps, 4), "lib": lib,
         }
+        if args.full:
+            out.update({
+                "ms_per_step_p50": None if p50_ms is None else round(p50_ms, 4),
+                "ms_per_step_with_position_readback": None if readback_ms is None else round(readback_ms, 4),
+                "ms_per_step_with_blocking_position_readback": None if readback_blocking_ms is None else round(readback_blocking_ms, 4),
+                "ms_per_step_with_position_readback_incl_final_copy": None if readback_wall_ms is None else round(readback_wall_ms, 4),
+                "ms_per_step_same_pass_without_readback": None if readback_plain_ms is None else round(readback_plain_ms, 4),
+                "roofline": roofline, "cpu_baseline": cpu, "stages_ms": stages_ms, "stages_frac": stages_frac,
+                "radix_sort_passes": sort_passes,
+            })
         out.update(extra)
         if cpu:
             out["gpu_over_cpu"] = round(value / cpu["value"], 1)
@@ -577,6 +603,26 @@ def rank_main(args):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, solver, np, N):
+    """--dump-outputs DIR: what the last timed step left a caller of the step path, as float32 .npy files — position.npy and
+    velocity.npy (x, y, z, w per particle, particle order: sph_read_position / sph_read_velocity) and density.npy (sph_read_density,
+    moved from sorted to particle order through the sort's particle ids) — and particle_ids.npy (float64): the rows written.
+    Above DUMP_SAMPLE_ROWS particles the rows are a fixed, seeded sample of the particle ids, the same in every run."""
+    os.makedirs(directory, exist_ok=True)
+    pos = solver.read_position_buffer()
+    vel = solver.read_velocity_buffer()
+    rho_sorted = solver.read_density_buffer()
+    rho = np.full(N, np.nan, np.float32)
+    rho[solver.read_particleIndex_buffer()[:, 1]] = rho_sorted  # (cell id, particle id) per sorted slot
+    if N > DUMP_SAMPLE_ROWS:
+        ids = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(N, DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        ids = np.arange(N)
+    for name, a in (("position", pos[ids]), ("velocity", vel[ids]), ("density", rho[ids]),
+                    ("particle_ids", ids.astype(np.float64))):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def density_sources_sha():

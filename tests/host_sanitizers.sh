@@ -20,7 +20,7 @@ from oracle import oraclebind as O
 O.LIB_PATH = "$OUT/libsphoracle.so"
 import scenes
 sc = sphmi.generate_worm(sphmi.default_config())
-z = np.load(scenes.worm_scene_path())
+z = scenes.worm_input()
 assert (sc["position"].view(np.uint32) == z["position"].view(np.uint32)).all() and (sc["elastic"].view(np.uint32) == z["elastic"].view(np.uint32)).all()
 b = scenes.liquid_box((8.0, 8.0, 8.0), (12, 10, 12), jitter_in_r0=0.03)
 d = tempfile.mkdtemp()

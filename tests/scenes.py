@@ -148,14 +148,29 @@ def config1():
                 particle_membranes=None)
 
 
-def worm_scene_path():
-    return os.path.join(GOLDEN, "worm_input.npz")
+# the reference generator's worm scene, split in two so that neither fixture file exceeds 1 MiB
+WORM_INPUT_FILES = {"worm_input.npz": ("position", "velocity", "membranes", "particle_membranes"),
+                    "worm_input_elastic.npz": ("elastic",)}
+
+
+def worm_input():
+    """The arrays of the worm scene fixture (tests/golden/worm_input*.npz) as one dict."""
+    out = {}
+    for f, names in WORM_INPUT_FILES.items():
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            out.update({k: z[k] for k in names})
+    return out
+
+
+def save_worm_input(arrays):
+    for f, names in WORM_INPUT_FILES.items():
+        np.savez_compressed(os.path.join(GOLDEN, f), **{k: arrays[k] for k in names})
 
 
 def worm_scene():
     """BASELINE config #3: the output of the reference's own generator (owHelper::generateConfiguration), committed as
-    the fixture tests/golden/worm_input.npz by tests/golden/make_golden.py."""
-    z = np.load(worm_scene_path())
+    the fixture tests/golden/worm_input*.npz by tests/golden/make_golden.py."""
+    z = worm_input()
     cfg = sphmi.default_config()
     cfg.particleCount = int(z["position"].shape[0])
     cfg.numOfElasticP = int(z["elastic"].shape[0] // 32)

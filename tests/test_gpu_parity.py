@@ -672,7 +672,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                        "--cpu-steps", "2", "--no-extra"], capture_output=True, text=True, timeout=600)
+                        "--full", "--cpu-steps", "2", "--no-extra"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -687,6 +687,44 @@ def test_bench_line_contract():
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert "traffic" in rf and rf["bytes_per_launch"] == d["config"]["particles"] * 132
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb and cb["unit"] == "particle-steps/s"
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the contract fields and none of the --full measurements; --dump-outputs writes what
+    its last timed step computed, bit-identical to the oracle after warm-up + timed steps on the same scene."""
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "stages_ms", "stages_frac", "ms_per_step_p50", "config3_worm"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["particles"] * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-2
+    box, lattice, mask = bench.WORKLOADS["tiny"]
+    sc = scenes.liquid_box(box, lattice, mask=mask)
+    N = sc["cfg"].particleCount
+    assert N == d["config"]["particles"] and N <= bench.DUMP_SAMPLE_ROWS
+    ora = scenes.oracle_for(sc)
+    for _ in range(2 + 3):
+        ora.step()
+    rho = np.empty(N, np.float32)
+    rho[ora.buffer("particleIndex").reshape(-1, 2)[:N, 1]] = ora.buffer("rho")[:N]
+    want = {"position": ora.buffer("position").reshape(-1, 4)[:N], "velocity": ora.buffer("velocity").reshape(-1, 4)[:N],
+            "density": rho, "particle_ids": np.arange(N, dtype=np.float64)}
+    ora.close()
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in want)
+    for k, w in want.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype in (np.float32, np.float64)
+        assert scenes.bits_equal(got, w), (k, scenes.diff_report(got, w))
 
 
 # ---------------------------------------------------------------------------------------------- round 3

@@ -45,8 +45,8 @@ def test_surface_tension_coefficient_matches_oracle():
 
 def test_box_generator_reproduces_reference_boundary_shell():
     """The boundary part of sphmi_generate_box == the last numOfBoundaryP particles of the reference generator's
-    output (tests/golden/worm_input.npz), bit for bit: positions, normals stored in velocity, type 3 in both .w."""
-    w = np.load(os.path.join(GOLDEN, "worm_input.npz"))
+    output (tests/golden/worm_input*.npz), bit for bit: positions, normals stored in velocity, type 3 in both .w."""
+    w = scenes.worm_input()
     cfg = sphmi.default_config()
     pos, vel, cnt = sphmi.generate_box(cfg, 0, 0, 0)
     nb = cnt["numOfBoundaryP"]
@@ -264,10 +264,10 @@ def test_frame_feed_inversion_and_writers(tmp_path):
 
 def test_worm_generator_matches_reference_fixture():
     """SURVEY 8 f1: sphmi_generate_worm restates owHelper::generateConfiguration (owHelper.cpp:104-1429). Pinned against the
-    output of the compiled reference generator (tests/golden/worm_input.npz, made by tests/golden/make_golden.py): particle
+    output of the compiled reference generator (tests/golden/worm_input*.npz, made by tests/golden/make_golden.py): particle
     counts, every position / velocity bit, all 137,804 springs with their rest lengths and muscle colours, the 11,386
     membrane triangles and the per-particle triangle lists."""
-    z = np.load(scenes.worm_scene_path())
+    z = scenes.worm_input()
     cfg = sphmi.default_config()
     sc = sphmi.generate_worm(cfg)
     assert (sc["numOfElasticP"], sc["numOfLiquidP"], sc["numOfBoundaryP"]) == (10143, 120336, 102408)

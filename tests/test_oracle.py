@@ -1,6 +1,7 @@
 """CPU tests that pin the oracle (oracle/sph_oracle.c):
   * against the committed fixtures that the reference's own kernels produced (tests/golden/*.npz), and
-  * where oracle/_ref/libsphref.so exists (the build container), live against those kernels, buffer by buffer.
+  * where oracle/_ref/libsphref.so exists (the build container), live against those kernels, buffer by buffer (elsewhere
+    against the digests of those kernels' buffers, tests/golden/ref_live_digests.json).
 The reference ships no tests or golden vectors of its own."""
 import json
 import os
@@ -141,29 +142,59 @@ def _ref_available():
     return refbind.available()
 
 
-@pytest.mark.skipif(not _ref_available(), reason="oracle/_ref/libsphref.so only exists in the build container")
-@pytest.mark.parametrize("name", ["tiny_jitter", "tiny_elastic", "elastic_offset"])
-def test_oracle_live_against_reference_kernels(name):
-    from oracle import refbind as R
+LIVE_SCENES = ["tiny_jitter", "tiny_elastic", "elastic_offset"]
+LIVE_BUFFERS = ["position", "velocity", "sortedPosition", "sortedVelocity", "acceleration", "neighborMap", "particleIndex",
+                "particleIndexBack", "gridCellIndex", "gridCellIndexFixedUp", "pressure", "rho"]
+LIVE_DIGESTS = os.path.join(scenes.GOLDEN, "ref_live_digests.json")
+
+
+def live_scene(name):
     sc = scenes.elastic_offset_box() if name == "elastic_offset" else scenes.SCENES[name]()
-    c = sc["cfg"]
-    N = c.particleCount
-    S = R.RefSolver(sc["position"], sc["velocity"], (c.xmax, c.ymax, c.zmax), (c.gridCellsX, c.gridCellsY, c.gridCellsZ),
-                    elastic=sc["elastic"], membranes=sc["membranes"], particle_membranes=sc["particle_membranes"],
-                    elastic_offset=c.elasticOffset, threads=4)
-    T = scenes.oracle_for(sc)
-    names = ["position", "velocity", "sortedPosition", "sortedVelocity", "acceleration", "neighborMap", "particleIndex",
-             "particleIndexBack", "gridCellIndex", "gridCellIndexFixedUp", "pressure", "rho"]
     stages = list(scenes.STAGE_SEQUENCE)
     if sc["particle_membranes"] is None and sc["elastic"] is not None:
         # elastic matter without membrane lists: the reference creates no membrane buffers (owOpenCLSolver.cpp:68-81) and
         # its kernel would dereference them; the membrane stage is left out on both sides
         stages.remove("computeInteractionWithMembranes")
+    return sc, stages
+
+
+def ref_solver(sc, threads=4):
+    from oracle import refbind as R
+    c = sc["cfg"]
+    return R.RefSolver(sc["position"], sc["velocity"], (c.xmax, c.ymax, c.zmax), (c.gridCellsX, c.gridCellsY, c.gridCellsZ),
+                       elastic=sc["elastic"], membranes=sc["membranes"], particle_membranes=sc["particle_membranes"],
+                       elastic_offset=c.elasticOffset, threads=threads)
+
+
+def buffer_digest(a):
+    """sha256 of a buffer's bytes (every word, the dead .w lanes included), first 16 hex digits."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+
+
+@pytest.mark.parametrize("name", LIVE_SCENES)
+def test_oracle_live_against_reference_kernels(name):
+    """Three steps stage by stage, every buffer after every stage: against the reference's own kernels where oracle/_ref has been
+    built, and always against the digests of their buffers recorded by tests/golden/make_ref_digests.py."""
+    sc, stages = live_scene(name)
+    recorded = json.load(open(LIVE_DIGESTS))[name]
+    S = ref_solver(sc) if _ref_available() else None
+    T = scenes.oracle_for(sc)
+    k = 0
     for it in range(3):
         for st in stages:
-            S.run(st, it); T.run(st)
-            for b in names:  # every word of every buffer, including the dead .w lanes
-                assert scenes.bits_equal(S.buffer(b), T.buffer(b)), (it, st, b, scenes.diff_report(S.buffer(b), T.buffer(b)))
+            T.run(st)
+            if S is not None:
+                S.run(st, it)
+            assert recorded[k]["stage"] == st, (k, recorded[k]["stage"], st)
+            for b in LIVE_BUFFERS:  # every word of every buffer, including the dead .w lanes
+                assert buffer_digest(T.buffer(b)) == recorded[k]["digests"][b], (it, st, b)
+                if S is not None:
+                    assert scenes.bits_equal(S.buffer(b), T.buffer(b)), (it, st, b, scenes.diff_report(S.buffer(b), T.buffer(b)))
+            k += 1
         if sc["elastic"] is not None:
             sig = sphmi.muscle_signal(it)
-            S.update_muscles(sig); T.update_muscles(sig)
+            T.update_muscles(sig)
+            if S is not None:
+                S.update_muscles(sig)
+    assert k == len(recorded)

@@ -403,7 +403,7 @@ def test_bench_self_launch_two_ranks_on_one_card():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SPHMI_DIST_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(scenes.ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny_long", "--steps", "4",
-                        "--warmup", "2"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "2", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout

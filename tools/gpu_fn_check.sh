@@ -10,7 +10,7 @@ tail -2 $OUT/gpu_tests.log
 timeout -k 10 120 python tools/time_find_neighbors.py 20 | tee $OUT/fn_time.txt
 timeout -k 10 120 python tools/time_find_neighbors.py 20 0.3 | tee -a $OUT/fn_time.txt
 if [ -f smoothed-particle-hydrodynamics_amd/libsphmi_stamps.so ]; then timeout -k 10 120 python tools/fn_phase_shares.py 5 | tee $OUT/fn_phases.txt; fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-steps 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --cpu-steps 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python - <<P
 import json
 d=json.load(open("$OUT/bench.json"))
