@@ -140,6 +140,32 @@ int sph_read_buffer(sph_solver* s, const char* name, void* out, size_t bytes, si
  * (neighborMap[].y: distance * simulationScale, -1 = empty). Either pointer may be NULL. Blocking. */
 int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t count, int32_t* ids, float* dist);
 
+/* ---- Field sampling (SPH interpolation; no reference counterpart) ---------------------------------------------------------
+ * Reads the SORTED STATE OF THE LAST COMPLETED STEP: the arrays that step's neighbour search, density and pressure loop ran on
+ * (sortedPos / sortedVel as gathered by the sort, before integration; rho from computeDensity; pressure after the last
+ * predict-correct iteration; the cell table). This is the state sph_read_density describes, ONE INTEGRATION STEP BEHIND
+ * sph_read_position. Read-only on every solver array; not a stage (no stage timing).
+ *
+ * For a query point p and a type mask m, particle j (sorted index) is selected when all of:
+ *   (1 << (int)position.w) & m != 0        (bit 1 = liquid, 2 = elastic, 3 = boundary; the worm's elastic types are 2.x)
+ *   dx*dx + dy*dy + dz*dz < h*h            (d = p - x_j in scene units, float, products and sums in that order, h*h one float)
+ *   j's cell key is in the step's cell table (key < gridCellCount)
+ * For the selected j in ASCENDING SORTED INDEX, in float throughout: a = hs2 - r2*ss2 (ss2 = simScale*simScale as a float,
+ * hs2 = (h*simScale)^2 as the step computes it), w = a*a*a, v_j = w * (1.0f/rho_j); W += w, S += v_j, U += v_j*vel_j.xyz,
+ * P += v_j*p_j as sequential float sums. Record (SPH_SAMPLE_WORDS floats):
+ *   { rho = (float)massWpoly6 * W, shepard = (float)massWpoly6 * S, vx, vy, vz = U/S, p = P/S, n = count, 0 }
+ * with zeros in place of the quotients when S == 0; a non-finite query point gives an all-zero record.
+ * Allowed once the density and pressure-force stages of a step have run (sph_step or the sph_run_* path), SPH_ERR_ORDER before;
+ * SPH_ERR_INVALID for a slab solver, a typeMask of 0 or with bits outside 1..3, dims <= 0, count < 0, or null pointers
+ * (count == 0 is a no-op). Blocking, on the solver's stream; device scratch is grown on demand (bounded: large grids go in
+ * z-chunks) and freed by sph_destroy. */
+#define SPH_SAMPLE_WORDS 8
+int sph_sample_points(sph_solver* s, const float* points4 /* host, count x (x,y,z,unused) */, int32_t count,
+                      uint32_t typeMask, float* out /* host, count x 8 */);
+/* Grid point (i, j, k) = origin + (float)i * spacing per axis (one float multiply, one float add). */
+int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                    uint32_t typeMask, float* out /* host, dims[2] x dims[1] x dims[0] x 8, x fastest */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

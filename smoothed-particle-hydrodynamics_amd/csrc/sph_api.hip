@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -228,7 +229,7 @@ static void free_all(sph_solver* s) {
   void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
                   d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist};
+                  s->blockHist, s->sampleBuf};
   for (void* p : ptrs) if (p) hipFree(p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
@@ -958,6 +959,79 @@ extern "C" int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t coun
       }
       if (dist) dist[(size_t)i * 32 + k] = td[src];
     }
+  return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- field sampling
+// Reads the sorted state the last step's density and pressure loop ran on (sph_sample.hip); enqueued on s->stream and waited
+// for, like the sph_read_* family. Large requests go through the device scratch in pieces (z-chunks of a grid, runs of points)
+// so that the scratch stays bounded whatever the request.
+static const size_t kSampleScratchBytes = (size_t)64 << 20;
+
+static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleParams* p) {
+  if (s->hasSlab) { sph_set_error("%s: sampling a slab solver is not supported", what); return SPH_ERR_INVALID; }
+  if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("%s: typeMask must be a non-empty set of bits 1..3", what); return SPH_ERR_INVALID; }
+  NEED(s, P_DENSITY | P_PRESSUREFORCE, what);
+  volatile float hh = s->cfg.h * s->cfg.h;
+  volatile float ss2 = s->cfg.simulationScale * s->cfg.simulationScale;
+  p->typeMask = typeMask; p->hh = hh; p->ss2 = ss2; p->mwp = (float)s->d.massWpoly6;
+  return SPH_OK;
+}
+
+static int sample_scratch(sph_solver* s, size_t bytes) {
+  if (s->sampleBytes >= bytes) return SPH_OK;
+  if (s->sampleBuf) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(s->sampleBuf); }
+  s->sampleBuf = nullptr; s->sampleBytes = 0;
+  SPH_HIP(hipMalloc(&s->sampleBuf, bytes));
+  s->sampleBytes = bytes;
+  return SPH_OK;
+}
+
+extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_points: bad count or null pointer"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_sample_points", &p);
+  if (rc != SPH_OK || count == 0) return rc;
+  const size_t rec = sizeof(float) * SPH_SAMPLE_WORDS, perPoint = sizeof(float4) + rec;
+  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
+  rc = sample_scratch(s, (size_t)piece * perPoint);
+  if (rc != SPH_OK) return rc;
+  float* dOut = (float*)s->sampleBuf;
+  float* dPts = (float*)((char*)s->sampleBuf + (size_t)piece * rec);
+  for (int first = 0; first < count; first += piece) {
+    const int n = std::min(piece, count - first);
+    SPH_HIP(hipMemcpyAsync(dPts, points4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    rc = sphk_sample_points(s, p, dPts, n, dOut);
+    if (rc != SPH_OK) return rc;
+    rc = d2h(s, out + (size_t)first * SPH_SAMPLE_WORDS, dOut, rec * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                               uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
+    sph_set_error("sph_sample_grid: null pointer or dims <= 0");
+    return SPH_ERR_INVALID;
+  }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_sample_grid", &p);
+  if (rc != SPH_OK) return rc;
+  const size_t rec = sizeof(float) * SPH_SAMPLE_WORDS, planeBytes = rec * (size_t)dims[0] * (size_t)dims[1];
+  // z-chunks of whole bricks (4 planes) that fit the scratch; at least one brick layer however large a plane is
+  int planes = (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
+  rc = sample_scratch(s, planeBytes * (size_t)planes);
+  if (rc != SPH_OK) return rc;
+  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
+    const int nz = std::min(planes, dims[2] - k0);
+    rc = sphk_sample_grid(s, p, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
+    if (rc != SPH_OK) return rc;
+    rc = d2h(s, (char*)out + planeBytes * (size_t)k0, s->sampleBuf, planeBytes * (size_t)nz);
+    if (rc != SPH_OK) return rc;
+  }
   return SPH_OK;
 }
 

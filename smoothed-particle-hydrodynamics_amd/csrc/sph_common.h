@@ -123,6 +123,8 @@ struct sph_solver {
   HostReg hostRegs[8]; int numHostRegs;    // caller buffers page-locked in place by hipHostRegister (released by sph_destroy)
   uint32_t* pinnedFlags;               // pinned: [0] copy of dbg[6] taken with the last asynchronous read-back
   uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (check_finite_state)
+  // field sampling (sph_sample_points / sph_sample_grid): device scratch for query points and records, grown on demand
+  void* sampleBuf; size_t sampleBytes;
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -226,6 +228,17 @@ int sphk_slab_rebuild(sph_solver* s, const uint32_t* recvDown, int nDown, const 
 int sphk_slab_rebuild_framed(sph_solver* s, const uint32_t* frameDown, int capDown, const uint32_t* frameUp, int capUp,
                              const uint32_t* keptPtr, uint32_t* totals);  // every length read on the device; d.N is left alone
 int sphk_slab_sort_rebuild(sph_solver* s, int total);  // staging area in any order -> local set sorted by global id
+// sph_sample.hip (read-only on every solver array; the constants of the sampling contract, include/sphmi.h)
+struct SampleParams {
+  uint32_t typeMask;  // bits 1..3: liquid, elastic, boundary
+  float hh;           // h*h rounded to float once
+  float ss2;          // simScale*simScale
+  float mwp;          // (float)massWpoly6
+};
+int sphk_sample_points(sph_solver* s, const SampleParams& p, const float* pts4, int count, float* out);  // device pointers
+// grid z-planes [kBase, kBase + nz) of the lattice origin + (float)i * spacing; out = nz x ny x nx records (device)
+int sphk_sample_grid(sph_solver* s, const SampleParams& p, const float origin[3], const float spacing[3], int nx, int ny,
+                     int kBase, int nz, float* out);
 // sph_elastic.hip
 int sphk_elastic(sph_solver* s);
 int sphk_clear_membranes(sph_solver* s);

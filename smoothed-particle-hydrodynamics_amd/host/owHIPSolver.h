@@ -64,6 +64,15 @@ class owHIPSolver {
     check(sph_read_particle_index(s_, particleIndexBuffer), "read_particleIndex_buffer");
   }
 
+  // beyond the reference: SPH interpolation over the sorted state of the last completed step (include/sphmi.h, sph_sample_*);
+  // out holds count x SPH_SAMPLE_WORDS / dims[2] x dims[1] x dims[0] x SPH_SAMPLE_WORDS floats. typeMask bits: 1 liquid, 2 elastic, 3 boundary
+  void samplePoints(const float* points4, int count, unsigned int typeMask, float* out) {
+    check(sph_sample_points(s_, points4, count, typeMask, out), "samplePoints");
+  }
+  void sampleGrid(const float origin[3], const float spacing[3], const int dims[3], unsigned int typeMask, float* out) {
+    check(sph_sample_grid(s_, origin, spacing, dims, typeMask, out), "sampleGrid");
+  }
+
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }
   sph_solver* handle() { return s_; }

@@ -5,11 +5,16 @@
 //   sphmi_run --position P.txt --velocity V.txt [--steps N] [--staged] [--out positions.bin] [--quiet] [--blocking-readback]
 //   sphmi_run --box 50 50 50 --lattice 100 100 100 [--wide] ...
 //   sphmi_run --worm [--muscles] ...      the generated worm scene of the reference's default start-up (owHelper.cpp:709)
+//   ... --sample-grid NX NY NZ --sample-every K --sample-out DIR
+//        after every K-th step, sample the fields of all particle types on an NX x NY x NZ lattice spanning the scene's box
+//        ([xmin, xmax] x [ymin, ymax] x [zmin, zmax], spacing (max - min) / (N - 1) in float) and write DIR/fields_<steps done>.bin:
+//        raw float32 records in sph_sample_grid's layout (NZ x NY x NX x 8, x fastest; sphmi.frames.read_fields)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <string>
 #include <vector>
 
 #include "owHIPSolver.h"
@@ -32,6 +37,7 @@ int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
   double box[3] = {0, 0, 0}; int lat[3] = {0, 0, 0};
+  int sampleDims[3] = {0, 0, 0}, sampleEvery = 0; const char* sampleDir = nullptr;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--velocity") && i + 1 < argc) velFile = argv[++i];
@@ -45,7 +51,15 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--muscles")) muscles = true;
     else if (!strcmp(argv[i], "--worm")) worm = true;
     else if (!strcmp(argv[i], "--blocking-readback")) blockingRead = true;  // the reference's blocking read_position_buffer
+    else if (!strcmp(argv[i], "--sample-grid") && i + 3 < argc) { for (int k = 0; k < 3; k++) sampleDims[k] = atoi(argv[++i]); }
+    else if (!strcmp(argv[i], "--sample-every") && i + 1 < argc) sampleEvery = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--sample-out") && i + 1 < argc) sampleDir = argv[++i];
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+  }
+  const bool sampling = sampleDims[0] > 0 || sampleEvery > 0 || sampleDir;
+  if (sampling && (sampleDims[0] <= 0 || sampleDims[1] <= 0 || sampleDims[2] <= 0 || sampleEvery <= 0 || !sampleDir)) {
+    fprintf(stderr, "--sample-grid NX NY NZ (all > 0), --sample-every K (> 0) and --sample-out DIR go together\n");
+    return 2;
   }
   try {
     sph_config cfg;
@@ -92,6 +106,10 @@ int main(int argc, char** argv) {
                                                     membraneData_cpp.empty() ? nullptr : membraneData_cpp.data(),
                                                     particleMembranesList_cpp.empty() ? nullptr : particleMembranesList_cpp.data());
     std::vector<float> muscle_activation_signal_cpp(cfg.muscleCount, 0.f);
+    float sampleOrigin[3] = {cfg.xmin, cfg.ymin, cfg.zmin}, sampleSpacing[3];
+    const float boxMax[3] = {cfg.xmax, cfg.ymax, cfg.zmax};
+    for (int k = 0; k < 3; k++) sampleSpacing[k] = sampleDims[k] > 1 ? (boxMax[k] - sampleOrigin[k]) / (float)(sampleDims[k] - 1) : 0.f;
+    std::vector<float> fields(sampling ? (size_t)sampleDims[0] * sampleDims[1] * sampleDims[2] * SPH_SAMPLE_WORDS : 0);
     Watch helper; helper.quiet = quiet;
     double total = 0;
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
@@ -132,6 +150,15 @@ int main(int argc, char** argv) {
       helper.report("_readBuffer: \t\t%9.3f ms\n");
       if (!quiet) printf("------------------------------------\n_Total_step_time:\t%9.3f ms\n------------------------------------\n", helper.elapsed());
       total += helper.elapsed();
+      if (sampling && (iterationCount + 1) % sampleEvery == 0) {
+        ocl_solver->sampleGrid(sampleOrigin, sampleSpacing, sampleDims, (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE) |
+                               (1u << SPH_BOUNDARY_PARTICLE), fields.data());
+        const std::string path = std::string(sampleDir) + "/fields_" + std::to_string(iterationCount + 1) + ".bin";
+        FILE* f = fopen(path.c_str(), "wb");
+        if (!f || fwrite(fields.data(), sizeof(float), fields.size(), f) != fields.size()) throw std::runtime_error("cannot write " + path);
+        fclose(f);
+        helper.report("_sampleGrid: \t\t%9.3f ms\n");
+      }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);
         ocl_solver->updateMuscleActivityData(muscle_activation_signal_cpp.data());

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SPHMI_LIB", os.path.join(_PKG, "libsphmi.so"))  # SPH
 HOST_LIB_PATH = os.path.join(_PKG, "libsphmi_host.so")
 
 ABI_VERSION = 2
+SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -98,7 +99,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_buffer", "sph_read_neighbor_rows", "sph_synchronize", "sph_set_stage_timing", "sph_get_stage_times",
                     "sph_reset_stage_times", "sph_step_sort_passes", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
-                    "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event"] + _STAGE_FUNCS
+                    "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
+                    "sph_sample_grid"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -175,6 +177,8 @@ def device_lib():
         L.sph_stream_wait_event.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_particle_count.argtypes = [C.c_void_p]
         L.sph_slab_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_sample_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        L.sph_sample_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         _dev = L
     return _dev
 
@@ -364,6 +368,15 @@ _BUF_DTYPE = {"position": np.float32, "velocity": np.float32, "sortedPosition": 
               "rho": np.float32, "debugCounters": np.uint32, "diagnosticTrace": np.uint32}
 
 
+def type_mask(types):
+    """Particle types (1 liquid, 2 elastic, 3 boundary) -> the typeMask bit set of sph_sample_*; other values are passed on
+    as bits for the library to reject."""
+    m = 0
+    for t in types:
+        m |= 1 << int(t)
+    return m & 0xffffffff
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -462,6 +475,31 @@ class owHIPSolver:
     def read_particleIndex_buffer(self, out=None):
         out = np.empty((self.N, 2), np.uint32) if out is None else out
         self._chk(self._L.sph_read_particle_index(self._h, _ptr(out)))
+        return out
+
+    # --- field sampling (sph_sample_points / sph_sample_grid): the sorted state of the last completed step ---
+    def sample_points(self, points, types=(1, 2, 3)):
+        """SPH interpolation at `points` ([Q, 3] or [Q, 4], scene units) over the particles of the given types:
+        float32[Q, 8] records (density, shepard, vx, vy, vz, pressure, count, 0), include/sphmi.h."""
+        pts = np.asarray(points, np.float32)
+        pts = pts.reshape(-1, pts.shape[-1]) if pts.ndim else pts.reshape(-1, 1)
+        if pts.shape[1] not in (3, 4):
+            raise SphError("sample_points: points must be [Q, 3] or [Q, 4]")
+        p4 = np.zeros((pts.shape[0], 4), np.float32)
+        p4[:, :3] = pts[:, :3]
+        out = np.empty((p4.shape[0], SAMPLE_WORDS), np.float32)
+        self._chk(self._L.sph_sample_points(self._h, _ptr(p4), p4.shape[0], type_mask(types), _ptr(out)))
+        return out
+
+    def sample_grid(self, origin, spacing, dims, types=(1, 2, 3)):
+        """The same on the lattice origin + (float)i * spacing, i < dims = (nx, ny, nz): float32[nz, ny, nx, 8]."""
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        size = int(dm[0]) * int(dm[1]) * int(dm[2]) if (dm > 0).all() else 0
+        out = np.empty((max(int(dm[2]), 0), max(int(dm[1]), 0), max(int(dm[0]), 0), SAMPLE_WORDS) if size else (1, SAMPLE_WORDS),
+                       np.float32)
+        self._chk(self._L.sph_sample_grid(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), _ptr(out)))
         return out
 
     # --- extras ---

@@ -6,6 +6,10 @@ sorted order), inverts the permutation itself (`p_indexb[2*p_indexb[2*i+1]] = i`
 `density[p_indexb[2*i]]`. `frame()` does the same inversion and returns per-particle arrays in orig order; `density_colour()`
 is the viewer's blue -> cyan -> green -> yellow -> red ramp over 0..5 % compression; `write_vtk` / `write_npz` replace the GL
 window with files ParaView or numpy can open.
+
+Field grids (owHIPSolver.sample_grid, float32[nz, ny, nx, 8] records: density, shepard, vx, vy, vz, pressure, count, 0):
+`write_vtk_grid` writes one as a legacy-VTK volume beside the point cloud, `free_surface_height` turns one into a water-height
+map (the dam-break gauge) and `read_fields` loads the raw files `sphmi_run --sample-grid` writes.
 """
 import numpy as np
 
@@ -72,3 +76,63 @@ def write_vtk(path, position, density, include_boundary=False):
         f.write(pos[:, 3].astype(">f4").tobytes())
         f.write(b"\n")
     return n
+
+
+GRID_FIELDS = ("density", "shepard", "vx", "vy", "vz", "pressure", "count")
+
+
+def write_vtk_grid(path, origin, spacing, fields):
+    """Legacy-VTK STRUCTURED_POINTS (binary, big-endian like write_vtk) of a sample_grid result `fields` [nz, ny, nx, 8]:
+    point data `density`, `shepard`, `pressure` (scalars) and `velocity` (vectors)."""
+    g = np.asarray(fields, np.float32)
+    if g.ndim != 4 or g.shape[3] < 6:
+        raise ValueError("fields must be [nz, ny, nx, 8] records")
+    nz, ny, nx = g.shape[:3]
+    n = nx * ny * nz
+    o = [float(np.float32(v)) for v in origin]
+    sp = [float(np.float32(v)) for v in spacing]
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi fields\nBINARY\nDATASET STRUCTURED_POINTS\n")
+        f.write(("DIMENSIONS %d %d %d\n" % (nx, ny, nz)).encode())
+        f.write(("ORIGIN %.9g %.9g %.9g\n" % tuple(o)).encode())
+        f.write(("SPACING %.9g %.9g %.9g\n" % tuple(sp)).encode())
+        f.write(("POINT_DATA %d\n" % n).encode())
+        for name, col in (("density", 0), ("shepard", 1), ("pressure", 5)):
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(g[..., col]).astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(b"VECTORS velocity float\n")
+        f.write(np.ascontiguousarray(g[..., 2:5]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return n
+
+
+def free_surface_height(grid, origin, spacing, threshold=0.5):
+    """Water height per (y, x) column of a sample_grid result [nz, ny, nx, 8]: the highest z at which `shepard` (the fraction of
+    space the fluid fills, ~1 inside) falls from >= threshold to < threshold between two grid planes, interpolated linearly
+    between them. A column whose top plane is still >= threshold gives the top plane's z; one that never reaches the
+    threshold gives NaN. float64 [ny, nx]."""
+    g = np.asarray(grid, np.float32)
+    s = g[..., 1].astype(np.float64)  # [nz, ny, nx]
+    nz = s.shape[0]
+    z = float(np.float32(origin[2])) + np.arange(nz, dtype=np.float64) * float(np.float32(spacing[2]))
+    thr = float(threshold)
+    above = s >= thr
+    out = np.full(s.shape[1:], np.nan)
+    top = above[-1]
+    out[top] = z[-1]
+    if nz > 1:
+        cross = above[:-1] & ~above[1:]  # plane k >= thr, plane k+1 below
+        has = cross.any(axis=0) & ~top
+        k = (nz - 2) - np.argmax(cross[::-1], axis=0)  # highest crossing per column
+        yy, xx = np.nonzero(has)
+        kk = k[yy, xx]
+        s0, s1 = s[kk, yy, xx], s[kk + 1, yy, xx]
+        out[yy, xx] = z[kk] + (s0 - thr) / (s0 - s1) * (z[kk + 1] - z[kk])
+    return out
+
+
+def read_fields(path, dims):
+    """A `sphmi_run --sample-grid NX NY NZ` output file (raw float32 records in sph_sample_grid's layout) as [NZ, NY, NX, 8]."""
+    nx, ny, nz = (int(v) for v in dims)
+    return np.fromfile(path, np.float32).reshape(nz, ny, nx, 8)
