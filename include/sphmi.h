@@ -166,6 +166,42 @@ int sph_sample_points(sph_solver* s, const float* points4 /* host, count x (x,y,
 int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
                     uint32_t typeMask, float* out /* host, dims[2] x dims[1] x dims[0] x 8, x fastest */);
 
+/* ---- Isosurface extraction (marching cubes over a sampled field; no reference counterpart) --------------------------------
+ * Field: f(i,j,k) is word `field` (0 density, 1 shepard, 2 vx, 3 vy, 4 vz, 5 pressure) of the record that
+ * sph_sample_grid(s, origin, spacing, dims, typeMask, ...) would return at lattice point (i,j,k), bit for bit: the same state
+ * (the last completed step, one integration step behind sph_read_position). Inside: f >= iso (float compare; NaN is outside).
+ * Cells: cell (i,j,k), i < nx-1, j < ny-1, k < nz-1, has corner c (0..7) at lattice point (i + (c&1), j + ((c>>1)&1), k + (c>>2));
+ * its case is sum of inside(c) << c.
+ * Edges: cube edges 0..3 run along x between corners (0,1) (2,3) (4,5) (6,7); 4..7 along y between (0,2) (1,3) (4,6) (5,7);
+ * 8..11 along z between (0,4) (1,5) (2,6) (3,7). Cube edge e is the lattice edge that starts at its first corner, axis e/4.
+ * Vertices: one per lattice edge whose two ends differ in inside-ness, numbered by the edge's lower lattice point in x-fastest
+ * order (k, then j, then i) and within a point in the order +x, +y, +z. Its position is the lower point's coordinates with the
+ * edge's axis changed to x0 + t*(x1 - x0), t = (iso - f0)/(f1 - f0), where f0, f1 are the field at the lower and upper point and
+ * x0, x1 their coordinates on that axis, each origin + (float)i*spacing; all float, in that order, no contraction, IEEE division.
+ * t may be 0: coincident vertices and zero-area triangles are allowed.
+ * Triangles: cells in x-fastest order; within a cell, the triangles of the case table, three vertex ids each, oriented so that
+ * (v1-v0)x(v2-v0) points from inside toward outside (toward lower f). The table (csrc/sph_mc_table.h, tools/gen_mc_table.py):
+ *   1. on each cube face, a face with 2 crossed edges gets one segment between them; a face with 4 has two inside corners on
+ *      a diagonal, and each is cut off on its own by a segment joining the two crossed edges next to it;
+ *   2. each segment is directed so that, seen from outside the cube, the face's inside corner(s) it cuts off lie to its right;
+ *   3. the directed segments form disjoint cycles; each starts at its smallest edge number, cycles in ascending order of it;
+ *   4. a cycle c0..c(L-1) becomes the fan (c0, cq, c(q+1)), q = 1..L-2, of its first rotation whose chords (c0, cq),
+ *      q = 2..L-2, never join two edges that lie on a common cube face.
+ * The mesh is closed wherever the lattice's border points are outside.
+ * Lifetime: the mesh stays in device memory owned by the solver until the next sph_extract_surface or sph_destroy; steps do
+ * not change it. counts = {vertices, triangles}. sph_read_surface copies it to the host, blocking; either pointer may be NULL;
+ * SPH_ERR_ORDER before any successful extraction.
+ * Errors: SPH_ERR_ORDER before a step's density and pressure-force stages have run; SPH_ERR_INVALID for a slab solver, a bad
+ * typeMask (as sampling), field outside 0..5, a non-finite iso, any dims < 2, a lattice of more than 2^31-1 points, or null
+ * pointers; SPH_ERR_SIZE if the vertex count exceeds 2^31-1 (vertex ids are int32). A failed call leaves no mesh behind.
+ * Read-only on every solver array; on the solver's stream, blocking only to return the counts. Device memory beyond the
+ * sampling scratch: about 10 bytes per lattice point plus 12 bytes per vertex and per triangle, grown on demand, freed by
+ * sph_destroy. */
+#define SPH_SURFACE_FIELDS 6 /* record words 0..5 of sph_sample_*: density, shepard, vx, vy, vz, pressure */
+int sph_extract_surface(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3], uint32_t typeMask,
+                        int32_t field, float iso, int64_t counts[2] /* out: vertices, triangles */);
+int sph_read_surface(sph_solver* s, float* vertices /* host, counts[0] x 3 */, int32_t* triangles /* host, counts[1] x 3 */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

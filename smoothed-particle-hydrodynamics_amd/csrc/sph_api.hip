@@ -229,7 +229,7 @@ static void free_all(sph_solver* s) {
   void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
                   d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist, s->sampleBuf};
+                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf};
   for (void* p : ptrs) if (p) hipFree(p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
@@ -978,14 +978,17 @@ static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, Samp
   return SPH_OK;
 }
 
-static int sample_scratch(sph_solver* s, size_t bytes) {
-  if (s->sampleBytes >= bytes) return SPH_OK;
-  if (s->sampleBuf) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(s->sampleBuf); }
-  s->sampleBuf = nullptr; s->sampleBytes = 0;
-  SPH_HIP(hipMalloc(&s->sampleBuf, bytes));
-  s->sampleBytes = bytes;
+// device buffer *buf of *have bytes grown to at least `bytes` (the old one is freed once the stream has finished with it)
+static int grow_scratch(sph_solver* s, void** buf, size_t* have, size_t bytes) {
+  if (*have >= bytes) return SPH_OK;
+  if (*buf) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(*buf); }
+  *buf = nullptr; *have = 0;
+  SPH_HIP(hipMalloc(buf, bytes));
+  *have = bytes;
   return SPH_OK;
 }
+
+static int sample_scratch(sph_solver* s, size_t bytes) { return grow_scratch(s, &s->sampleBuf, &s->sampleBytes, bytes); }
 
 extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
   ENTER(s);
@@ -1010,6 +1013,12 @@ extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t co
   return SPH_OK;
 }
 
+// z-chunks of whole bricks (4 planes) that fit the scratch; at least one brick layer however large a plane is
+static int sample_grid_planes(const int32_t dims[3]) {
+  const size_t planeBytes = sizeof(float) * SPH_SAMPLE_WORDS * (size_t)dims[0] * (size_t)dims[1];
+  return (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
+}
+
 extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
                                uint32_t typeMask, float* out) {
   ENTER(s);
@@ -1020,9 +1029,8 @@ extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float
   SampleParams p;
   int rc = sample_check(s, typeMask, "sph_sample_grid", &p);
   if (rc != SPH_OK) return rc;
-  const size_t rec = sizeof(float) * SPH_SAMPLE_WORDS, planeBytes = rec * (size_t)dims[0] * (size_t)dims[1];
-  // z-chunks of whole bricks (4 planes) that fit the scratch; at least one brick layer however large a plane is
-  int planes = (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
+  const size_t planeBytes = sizeof(float) * SPH_SAMPLE_WORDS * (size_t)dims[0] * (size_t)dims[1];
+  const int planes = sample_grid_planes(dims);
   rc = sample_scratch(s, planeBytes * (size_t)planes);
   if (rc != SPH_OK) return rc;
   for (int k0 = 0; k0 < dims[2]; k0 += planes) {
@@ -1033,6 +1041,72 @@ extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float
     if (rc != SPH_OK) return rc;
   }
   return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- isosurface extraction
+// The scalar lattice comes from the sampling kernels (z-chunks through the sampling scratch, one word kept per record), then
+// marching cubes runs on it (sph_surface.hip). Blocks once, for the counts; the emitting kernels stay queued on s->stream.
+static size_t surf_bytes_align(size_t b) { return (b + 255) & ~(size_t)255; }  // triangles start at a 256-B boundary
+
+extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                                   uint32_t typeMask, int32_t field, float iso, int64_t counts[2]) {
+  ENTER(s);
+  s->meshValid = false;  // a failed call leaves no mesh behind
+  s->meshCounts[0] = s->meshCounts[1] = 0;
+  if (counts) counts[0] = counts[1] = 0;
+  if (!origin || !spacing || !dims || !counts) { sph_set_error("sph_extract_surface: null pointer"); return SPH_ERR_INVALID; }
+  if (field < 0 || field >= SPH_SURFACE_FIELDS) { sph_set_error("sph_extract_surface: field %d is not in 0..5", field); return SPH_ERR_INVALID; }
+  if (!std::isfinite(iso)) { sph_set_error("sph_extract_surface: iso is not finite"); return SPH_ERR_INVALID; }
+  if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) { sph_set_error("sph_extract_surface: dims must all be >= 2"); return SPH_ERR_INVALID; }
+  const long long P = (long long)dims[0] * (long long)dims[1] * (long long)dims[2];
+  if (P > 0x7fffffffLL) { sph_set_error("sph_extract_surface: the lattice has more than 2^31-1 points"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_extract_surface", &p);
+  if (rc != SPH_OK) return rc;
+  rc = grow_scratch(s, &s->surfBuf, &s->surfBytes, sphk_surface_scratch_bytes(P));
+  if (rc != SPH_OK) return rc;
+  const size_t plane = (size_t)dims[0] * (size_t)dims[1];
+  const int planes = sample_grid_planes(dims);
+  rc = sample_scratch(s, sizeof(float) * SPH_SAMPLE_WORDS * plane * (size_t)planes);
+  if (rc != SPH_OK) return rc;
+  float* lattice = (float*)s->surfBuf;  // the scratch's first P floats
+  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
+    const int nz = std::min(planes, dims[2] - k0);
+    rc = sphk_sample_grid(s, p, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
+    if (rc != SPH_OK) return rc;
+    rc = sphk_surface_field(s, (const float*)s->sampleBuf, field, (int)(plane * (size_t)nz), lattice + plane * (size_t)k0);
+    if (rc != SPH_OK) return rc;
+  }
+  unsigned long long totals[2] = {0, 0};
+  rc = sphk_surface_count(s, s->surfBuf, dims, iso, totals);
+  if (rc != SPH_OK) return rc;
+  if (totals[0] > 0x7fffffffULL) {
+    sph_set_error("sph_extract_surface: %llu vertices exceed the int32 vertex ids", totals[0]);
+    return SPH_ERR_SIZE;
+  }
+  const size_t vBytes = surf_bytes_align(sizeof(float) * 3 * (size_t)totals[0]);
+  rc = grow_scratch(s, &s->meshBuf, &s->meshBytes, std::max<size_t>(vBytes + sizeof(int32_t) * 3 * (size_t)totals[1], 1));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_surface_emit(s, s->surfBuf, dims, iso, origin, spacing, (float*)s->meshBuf, (int32_t*)((char*)s->meshBuf + vBytes));
+  if (rc != SPH_OK) return rc;
+  s->meshCounts[0] = (int64_t)totals[0];
+  s->meshCounts[1] = (int64_t)totals[1];
+  s->meshValid = true;
+  counts[0] = s->meshCounts[0];
+  counts[1] = s->meshCounts[1];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangles) {
+  ENTER(s);
+  if (!s->meshValid) { sph_set_error("sph_read_surface: no surface has been extracted"); return SPH_ERR_ORDER; }
+  const size_t vBytes = sizeof(float) * 3 * (size_t)s->meshCounts[0];
+  int rc = SPH_OK;
+  if (vertices && vBytes) rc = d2h(s, vertices, s->meshBuf, vBytes);
+  if (rc != SPH_OK) return rc;
+  const size_t tBytes = sizeof(int32_t) * 3 * (size_t)s->meshCounts[1];
+  if (triangles && tBytes) rc = d2h(s, triangles, (char*)s->meshBuf + surf_bytes_align(vBytes), tBytes);
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------- slab decomposition

@@ -125,6 +125,10 @@ struct sph_solver {
   uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (check_finite_state)
   // field sampling (sph_sample_points / sph_sample_grid): device scratch for query points and records, grown on demand
   void* sampleBuf; size_t sampleBytes;
+  // isosurface extraction (sph_extract_surface / sph_read_surface): lattice scratch and the last mesh, grown on demand
+  void* surfBuf; size_t surfBytes;
+  void* meshBuf; size_t meshBytes;
+  int64_t meshCounts[2]; bool meshValid;  // vertices, triangles of the last successful extraction
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -239,6 +243,13 @@ int sphk_sample_points(sph_solver* s, const SampleParams& p, const float* pts4, 
 // grid z-planes [kBase, kBase + nz) of the lattice origin + (float)i * spacing; out = nz x ny x nx records (device)
 int sphk_sample_grid(sph_solver* s, const SampleParams& p, const float origin[3], const float spacing[3], int nx, int ny,
                      int kBase, int nz, float* out);
+// sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
+size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
+int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records
+// classify + scan; blocks until totals (vertices, triangles) are on the host
+int sphk_surface_count(sph_solver* s, void* scratch, const int dims[3], float iso, unsigned long long* totals);
+int sphk_surface_emit(sph_solver* s, void* scratch, const int dims[3], float iso, const float origin[3], const float spacing[3],
+                      float* verts, int32_t* tris);  // after sphk_surface_count, on the same scratch
 // sph_elastic.hip
 int sphk_elastic(sph_solver* s);
 int sphk_clear_membranes(sph_solver* s);

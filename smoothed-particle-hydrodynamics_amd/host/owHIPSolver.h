@@ -72,6 +72,13 @@ class owHIPSolver {
   void sampleGrid(const float origin[3], const float spacing[3], const int dims[3], unsigned int typeMask, float* out) {
     check(sph_sample_grid(s_, origin, spacing, dims, typeMask, out), "sampleGrid");
   }
+  // beyond the reference: marching-cubes isosurface of word `field` (0..5) of sampleGrid's records (include/sphmi.h,
+  // sph_extract_surface); counts = {vertices, triangles}; readSurface copies the mesh (vertices x 3 floats, triangles x 3 ints)
+  void extractSurface(const float origin[3], const float spacing[3], const int dims[3], unsigned int typeMask, int field, float iso,
+                      int64_t counts[2]) {
+    check(sph_extract_surface(s_, origin, spacing, dims, typeMask, field, iso, counts), "extractSurface");
+  }
+  void readSurface(float* vertices, int32_t* triangles) { check(sph_read_surface(s_, vertices, triangles), "readSurface"); }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

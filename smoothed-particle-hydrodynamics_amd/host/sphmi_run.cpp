@@ -9,6 +9,10 @@
 //        after every K-th step, sample the fields of all particle types on an NX x NY x NZ lattice spanning the scene's box
 //        ([xmin, xmax] x [ymin, ymax] x [zmin, zmax], spacing (max - min) / (N - 1) in float) and write DIR/fields_<steps done>.bin:
 //        raw float32 records in sph_sample_grid's layout (NZ x NY x NX x 8, x fastest; sphmi.frames.read_fields)
+//   ... --surface-grid NX NY NZ --surface-every K --surface-out DIR [--surface-iso X]
+//        after every K-th step, extract the isosurface shepard = X (default 0.5) of the liquid and elastic particles on the same
+//        box-spanning lattice (sph_extract_surface) and write DIR/surface_<steps done>.ply (binary little-endian PLY;
+//        sphmi.frames.read_ply)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,11 +37,29 @@ struct Watch {  // owHelper::refreshTime / watch_report (owHelper.cpp:44-57,1806
   double elapsed() const { return t1 - t0; }
 };
 
+// binary little-endian PLY: float x y z per vertex, list uchar int vertex_indices per face (sphmi.frames.write_ply)
+static void write_ply(const std::string& path, const std::vector<float>& verts, const std::vector<int32_t>& tris) {
+  const size_t nv = verts.size() / 3, nt = tris.size() / 3;
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot write " + path);
+  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+             "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", nv, nt);
+  bool ok = fwrite(verts.data(), sizeof(float), verts.size(), f) == verts.size();
+  std::vector<unsigned char> faces(nt * 13);
+  for (size_t t = 0; t < nt; t++) {
+    faces[t * 13] = 3;
+    memcpy(&faces[t * 13 + 1], &tris[t * 3], 12);  // little-endian host
+  }
+  ok = ok && fwrite(faces.data(), 1, faces.size(), f) == faces.size();
+  if (fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
+}
+
 int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
   double box[3] = {0, 0, 0}; int lat[3] = {0, 0, 0};
   int sampleDims[3] = {0, 0, 0}, sampleEvery = 0; const char* sampleDir = nullptr;
+  int surfDims[3] = {0, 0, 0}, surfEvery = 0; const char* surfDir = nullptr; float surfIso = 0.5f;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--velocity") && i + 1 < argc) velFile = argv[++i];
@@ -54,11 +76,20 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--sample-grid") && i + 3 < argc) { for (int k = 0; k < 3; k++) sampleDims[k] = atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--sample-every") && i + 1 < argc) sampleEvery = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--sample-out") && i + 1 < argc) sampleDir = argv[++i];
+    else if (!strcmp(argv[i], "--surface-grid") && i + 3 < argc) { for (int k = 0; k < 3; k++) surfDims[k] = atoi(argv[++i]); }
+    else if (!strcmp(argv[i], "--surface-every") && i + 1 < argc) surfEvery = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--surface-out") && i + 1 < argc) surfDir = argv[++i];
+    else if (!strcmp(argv[i], "--surface-iso") && i + 1 < argc) surfIso = (float)atof(argv[++i]);
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool sampling = sampleDims[0] > 0 || sampleEvery > 0 || sampleDir;
   if (sampling && (sampleDims[0] <= 0 || sampleDims[1] <= 0 || sampleDims[2] <= 0 || sampleEvery <= 0 || !sampleDir)) {
     fprintf(stderr, "--sample-grid NX NY NZ (all > 0), --sample-every K (> 0) and --sample-out DIR go together\n");
+    return 2;
+  }
+  const bool surfacing = surfDims[0] > 0 || surfEvery > 0 || surfDir;
+  if (surfacing && (surfDims[0] < 2 || surfDims[1] < 2 || surfDims[2] < 2 || surfEvery <= 0 || !surfDir)) {
+    fprintf(stderr, "--surface-grid NX NY NZ (all >= 2), --surface-every K (> 0) and --surface-out DIR go together\n");
     return 2;
   }
   try {
@@ -110,6 +141,10 @@ int main(int argc, char** argv) {
     const float boxMax[3] = {cfg.xmax, cfg.ymax, cfg.zmax};
     for (int k = 0; k < 3; k++) sampleSpacing[k] = sampleDims[k] > 1 ? (boxMax[k] - sampleOrigin[k]) / (float)(sampleDims[k] - 1) : 0.f;
     std::vector<float> fields(sampling ? (size_t)sampleDims[0] * sampleDims[1] * sampleDims[2] * SPH_SAMPLE_WORDS : 0);
+    float surfSpacing[3];
+    for (int k = 0; k < 3; k++) surfSpacing[k] = surfDims[k] > 1 ? (boxMax[k] - sampleOrigin[k]) / (float)(surfDims[k] - 1) : 0.f;
+    std::vector<float> meshVerts;
+    std::vector<int32_t> meshTris;
     Watch helper; helper.quiet = quiet;
     double total = 0;
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
@@ -158,6 +193,16 @@ int main(int argc, char** argv) {
         if (!f || fwrite(fields.data(), sizeof(float), fields.size(), f) != fields.size()) throw std::runtime_error("cannot write " + path);
         fclose(f);
         helper.report("_sampleGrid: \t\t%9.3f ms\n");
+      }
+      if (surfacing && (iterationCount + 1) % surfEvery == 0) {
+        int64_t counts[2];
+        ocl_solver->extractSurface(sampleOrigin, surfSpacing, surfDims, (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE),
+                                   1 /* shepard */, surfIso, counts);
+        meshVerts.resize((size_t)counts[0] * 3);
+        meshTris.resize((size_t)counts[1] * 3);
+        ocl_solver->readSurface(meshVerts.data(), meshTris.data());
+        write_ply(std::string(surfDir) + "/surface_" + std::to_string(iterationCount + 1) + ".ply", meshVerts, meshTris);
+        helper.report("_extractSurface: \t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

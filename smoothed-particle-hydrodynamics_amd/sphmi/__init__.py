@@ -16,6 +16,7 @@ HOST_LIB_PATH = os.path.join(_PKG, "libsphmi_host.so")
 
 ABI_VERSION = 2
 SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
+SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -100,7 +101,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_reset_stage_times", "sph_step_sort_passes", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
-                    "sph_sample_grid"] + _STAGE_FUNCS
+                    "sph_sample_grid", "sph_extract_surface", "sph_read_surface"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -179,6 +180,9 @@ def device_lib():
         L.sph_slab_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sph_sample_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_sample_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sph_extract_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_float,
+                                          C.c_void_p]
+        L.sph_read_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -501,6 +505,27 @@ class owHIPSolver:
                        np.float32)
         self._chk(self._L.sph_sample_grid(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), _ptr(out)))
         return out
+
+    # --- isosurface extraction (sph_extract_surface / sph_read_surface): marching cubes over a sampled field ---
+    def extract_surface(self, origin, spacing, dims, iso=0.5, field="shepard", types=(1,)):
+        """Triangle mesh of {f >= iso} for word `field` (a name from frames.GRID_FIELDS[:6] or 0..5) of sample_grid(origin,
+        spacing, dims, types), extracted on the device: (vertices float32[V, 3], triangles int32[T, 3]), triangles wound with
+        normals toward lower f (include/sphmi.h)."""
+        from . import frames
+        if isinstance(field, str):
+            if field not in frames.GRID_FIELDS[:SURFACE_FIELDS]:
+                raise SphError("extract_surface: field must be one of %s" % (frames.GRID_FIELDS[:SURFACE_FIELDS],))
+            field = frames.GRID_FIELDS.index(field)
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        counts = np.zeros(2, np.int64)
+        self._chk(self._L.sph_extract_surface(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), int(field), float(iso),
+                                              _ptr(counts)))
+        verts = np.empty((int(counts[0]), 3), np.float32)
+        tris = np.empty((int(counts[1]), 3), np.int32)
+        self._chk(self._L.sph_read_surface(self._h, _ptr(verts) if verts.size else None, _ptr(tris) if tris.size else None))
+        return verts, tris
 
     # --- extras ---
     def step(self, iterationCount=0):

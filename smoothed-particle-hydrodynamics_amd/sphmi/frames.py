@@ -10,6 +10,9 @@ window with files ParaView or numpy can open.
 Field grids (owHIPSolver.sample_grid, float32[nz, ny, nx, 8] records: density, shepard, vx, vy, vz, pressure, count, 0):
 `write_vtk_grid` writes one as a legacy-VTK volume beside the point cloud, `free_surface_height` turns one into a water-height
 map (the dam-break gauge) and `read_fields` loads the raw files `sphmi_run --sample-grid` writes.
+
+Surface meshes (owHIPSolver.extract_surface): `write_ply` / `read_ply` write and read binary little-endian PLY triangle meshes,
+the format `sphmi_run --surface-out` writes.
 """
 import numpy as np
 
@@ -136,3 +139,53 @@ def read_fields(path, dims):
     """A `sphmi_run --sample-grid NX NY NZ` output file (raw float32 records in sph_sample_grid's layout) as [NZ, NY, NX, 8]."""
     nx, ny, nz = (int(v) for v in dims)
     return np.fromfile(path, np.float32).reshape(nz, ny, nx, 8)
+
+
+def write_ply(path, vertices, triangles):
+    """Binary little-endian PLY of a triangle mesh (extract_surface): `float x y z` per vertex, `list uchar int vertex_indices`
+    per face. ParaView, Blender and MeshLab read it."""
+    v = np.ascontiguousarray(vertices, "<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, "<i4").reshape(-1, 3)
+    faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    faces["n"] = 3
+    faces["i"] = t
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (v.shape[0], t.shape[0])).encode())
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+    return v.shape[0], t.shape[0]
+
+
+def read_ply(path):
+    """(vertices float32[V, 3], triangles int32[T, 3]) of a binary little-endian triangle PLY as write_ply (and sphmi_run
+    --surface-out) write it."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    header = data[:end].decode("ascii").split("\n")
+    if header[0] != "ply" or header[1] != "format binary_little_endian 1.0":
+        raise ValueError("%s: not a binary little-endian PLY" % path)
+    counts, vprops, face_prop = {}, [], None
+    element = None
+    for line in header[2:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info", "end_header"):
+            continue
+        if w[0] == "element":
+            element = w[1]
+            counts[element] = int(w[2])
+        elif w[0] == "property" and element == "vertex":
+            if w[1] not in ("float", "float32"):
+                raise ValueError("%s: vertex property %s is not float" % (path, w[2]))
+            vprops.append(w[2])
+        elif w[0] == "property" and element == "face":
+            face_prop = w[1:]
+    if vprops[:3] != ["x", "y", "z"] or face_prop is None or face_prop[:3] not in (["list", "uchar", "int"], ["list", "uint8", "int32"]):
+        raise ValueError("%s: expected float x y z vertices and list uchar int faces" % path)
+    nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+    vert = np.frombuffer(data, "<f4", nv * len(vprops), end).reshape(nv, len(vprops))[:, :3]
+    faces = np.frombuffer(data, [("n", "u1"), ("i", "<i4", (3,))], nf, end + 4 * nv * len(vprops))
+    if nf and (faces["n"] != 3).any():
+        raise ValueError("%s: faces must be triangles" % path)
+    return np.array(vert, np.float32), np.array(faces["i"], np.int32).reshape(nf, 3)
