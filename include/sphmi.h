@@ -202,6 +202,45 @@ int sph_extract_surface(sph_solver* s, const float origin[3], const float spacin
                         int32_t field, float iso, int64_t counts[2] /* out: vertices, triangles */);
 int sph_read_surface(sph_solver* s, float* vertices /* host, counts[0] x 3 */, int32_t* triangles /* host, counts[1] x 3 */);
 
+/* ---- Gradient sampling and surface normals (SPH gradients of the sampled fields; no reference counterpart) -----------------
+ * State, selected set, order (ascending sorted index), lattice point formula, argument rules and errors are exactly those of
+ * sph_sample_points / sph_sample_grid (SPH_ERR_ORDER before a step's density and pressure-force stages; SPH_ERR_INVALID for a
+ * slab solver, a bad typeMask, dims <= 0, count < 0 or null pointers; count == 0 is a no-op). Read-only, blocking.
+ * For each selected particle j in ascending sorted index, with dx, dy, dz, r2, t = hs2 - r2*ss2, w = t*t*t and
+ * invRho = 1.0f/rho_j those of the sampling contract (d = p - x_j in scene units), all in float, in this order, no contraction:
+ *   g = t*t (the value inside w);  q = g*invRho
+ *   Bx += g*dx, By += g*dy, Bz += g*dz
+ *   Cx += q*dx, Cy += q*dy, Cz += q*dz
+ *   for A in (vx_j, vy_j, vz_j, p_j):  a = q*A;  E_A.x += a*dx, E_A.y += a*dy, E_A.z += a*dz
+ * 18 sequential float sums starting at 0, beside sampling's W, S, U, P, n. K = (float)(-6.0 * massWpoly6 * (double)simScale),
+ * computed in double and rounded once (massWpoly6 as in the sampling contract): gradients are taken with respect to
+ * simulation-scaled (physical) coordinates, so vorticity is in 1/s. Record (SPH_GRADIENT_WORDS floats):
+ *   0..7    the sph_sample_* record at the same point, bit for bit (U_x, U_y, U_z, P below are its words 2..5)
+ *   8..10   grad rho      = K*Bx, K*By, K*Bz
+ *   11..13  grad shepard  = K*Cx, K*Cy, K*Cz
+ *   14..22  grad u, row-major G[i][c] = K*(E_ui.c - U_i*C.c) for i = x, y, z and c = x, y, z (u_i = vx, vy, vz)
+ *   23..25  grad p        = K*(E_p.c - P*C.c)
+ *   26..28  vorticity     = (G[2][1] - G[1][2], G[0][2] - G[2][0], G[1][0] - G[0][1])
+ *   29      divergence    = (G[0][0] + G[1][1]) + G[2][2]
+ *   30      Q-criterion   = -0.5f * s, s = 0, then s += G[i][j]*G[j][i] for (i, j) in row-major order (9 terms)
+ *   31      0
+ * When S == 0, words 14..30 are 0 (as sampling's quotients); a non-finite query point gives an all-zero record (+0 bits), while
+ * a finite point that selects nothing has -0 in words 8..13 (K*0 with K < 0). */
+#define SPH_GRADIENT_WORDS 32
+int sph_sample_gradient_points(sph_solver* s, const float* points4 /* host, count x (x,y,z,unused) */, int32_t count,
+                               uint32_t typeMask, float* out /* host, count x 32 */);
+int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                             uint32_t typeMask, float* out /* host, dims[2] x dims[1] x dims[0] x 32, x fastest */);
+/* One normal per vertex of the mesh of the last successful sph_extract_surface, computed on the device from the mesh's
+ * vertices (no host round trip). The gradient used for a vertex is the record sph_sample_gradient_points would return at the
+ * vertex's float coordinates with the extraction's typeMask; its words are chosen by the extraction's field: 0 -> 8..10,
+ * 1 -> 11..13, 2, 3, 4 -> 14..16, 17..19, 20..22, 5 -> 23..25. len = sqrtf((gx*gx + gy*gy) + gz*gz) and
+ * n = (-(gx/len), -(gy/len), -(gz/len)) (toward lower f: the side the triangles' winding faces), or (0, 0, 0) where len is 0
+ * or not finite. Blocking. SPH_ERR_ORDER before any successful extraction, and once any stage, step or slab call has run since
+ * that extraction (the sampled state has changed; sph_read_surface keeps working); SPH_ERR_INVALID for a null pointer with
+ * counts[0] > 0. */
+int sph_surface_normals(sph_solver* s, float* normals /* host, counts[0] x 3 */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

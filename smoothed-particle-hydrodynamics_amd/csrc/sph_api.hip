@@ -449,11 +449,13 @@ static int slab_finish(sph_solver* s, int32_t counts[4]);
 
 extern "C" int sph_run_clear_buffers(sph_solver* s) {
   ENTER(s);
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_FIND_NEIGHBORS);
   return sphk_clear_neighbors(s);
 }
 extern "C" int sph_run_hash_particles(sph_solver* s) {
   ENTER(s);
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_HASH);
   int rc = sphk_hash(s);
   if (rc == SPH_OK) s->progress = P_HASH;  // a new step starts here
@@ -461,6 +463,7 @@ extern "C" int sph_run_hash_particles(sph_solver* s) {
 }
 extern "C" int sph_run_sort(sph_solver* s) {
   ENTER(s); NEED(s, P_HASH, "sph_run_sort");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_SORT);
   int rc = sphk_sort(s);
   if (rc == SPH_OK) s->progress |= P_SORT;
@@ -468,6 +471,7 @@ extern "C" int sph_run_sort(sph_solver* s) {
 }
 extern "C" int sph_run_sort_post_pass(sph_solver* s) {
   ENTER(s); NEED(s, P_SORT, "sph_run_sort_post_pass");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_SORT_POST);
   int rc = sphk_sort_post(s);
   if (rc == SPH_OK) s->progress |= P_SORTPOST;
@@ -475,6 +479,7 @@ extern "C" int sph_run_sort_post_pass(sph_solver* s) {
 }
 extern "C" int sph_run_indexx(sph_solver* s) {
   ENTER(s); NEED(s, P_SORT, "sph_run_indexx");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_INDEX);
   int rc = sphk_index_raw(s);
   if (rc == SPH_OK) s->progress |= P_INDEXX;
@@ -482,6 +487,7 @@ extern "C" int sph_run_indexx(sph_solver* s) {
 }
 extern "C" int sph_run_index_post_pass(sph_solver* s) {
   ENTER(s); NEED(s, P_INDEXX, "sph_run_index_post_pass");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_INDEX);
   int rc = sphk_index_fixed(s);
   if (rc == SPH_OK) s->progress |= P_INDEXPOST;
@@ -489,6 +495,7 @@ extern "C" int sph_run_index_post_pass(sph_solver* s) {
 }
 extern "C" int sph_run_find_neighbors(sph_solver* s) {
   ENTER(s); NEED(s, P_SORTPOST | P_INDEXPOST, "sph_run_find_neighbors");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_FIND_NEIGHBORS);
   int rc = sphk_find_neighbors(s);
   if (rc == SPH_OK) s->progress |= P_FIND;
@@ -496,6 +503,7 @@ extern "C" int sph_run_find_neighbors(sph_solver* s) {
 }
 extern "C" int sph_run_pcisph_compute_density(sph_solver* s) {
   ENTER(s); NEED(s, P_FIND, "sph_run_pcisph_compute_density");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_DENSITY);
   int rc = sphk_density(s);
   if (rc == SPH_OK) s->progress |= P_DENSITY;
@@ -503,6 +511,7 @@ extern "C" int sph_run_pcisph_compute_density(sph_solver* s) {
 }
 extern "C" int sph_run_pcisph_compute_forces_and_init_pressure(sph_solver* s) {
   ENTER(s); NEED(s, P_DENSITY, "sph_run_pcisph_compute_forces_and_init_pressure");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_FORCES);
   int rc = sphk_forces(s, false);
   if (rc == SPH_OK) s->progress |= P_FORCES;
@@ -510,11 +519,13 @@ extern "C" int sph_run_pcisph_compute_forces_and_init_pressure(sph_solver* s) {
 }
 extern "C" int sph_run_pcisph_compute_elastic_forces(sph_solver* s) {
   ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_compute_elastic_forces");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_ELASTIC);
   return sphk_elastic(s);
 }
 extern "C" int sph_run_pcisph_predict_positions(sph_solver* s) {
   ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_predict_positions");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_PRESSURE_FORCE);
   int rc = sphk_predict_positions(s);
   if (rc == SPH_OK) s->progress |= P_PREDICTPOS;
@@ -522,6 +533,7 @@ extern "C" int sph_run_pcisph_predict_positions(sph_solver* s) {
 }
 extern "C" int sph_run_pcisph_predict_density(sph_solver* s) {
   ENTER(s); NEED(s, P_PREDICTPOS, "sph_run_pcisph_predict_density");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_PREDICT_DENSITY);
   int rc = sphk_predict_density(s, false);
   if (rc == SPH_OK) s->progress |= P_PREDICTDENS;
@@ -529,11 +541,13 @@ extern "C" int sph_run_pcisph_predict_density(sph_solver* s) {
 }
 extern "C" int sph_run_pcisph_correct_pressure(sph_solver* s) {
   ENTER(s); NEED(s, P_PREDICTDENS, "sph_run_pcisph_correct_pressure");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_PREDICT_DENSITY);
   return sphk_correct_pressure(s);
 }
 extern "C" int sph_run_pcisph_compute_pressure_force_acceleration(sph_solver* s) {
   ENTER(s); NEED(s, P_PREDICTDENS, "sph_run_pcisph_compute_pressure_force_acceleration");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_PRESSURE_FORCE);
   int rc = sphk_pressure_force(s, 0);
   if (rc == SPH_OK) s->progress |= P_PRESSUREFORCE;
@@ -542,22 +556,26 @@ extern "C" int sph_run_pcisph_compute_pressure_force_acceleration(sph_solver* s)
 extern "C" int sph_run_pcisph_integrate(sph_solver* s, int iterationCount) {
   (void)iterationCount;  // only used by commented-out debug prints in the reference (sphFluid.cl:1784-1805)
   ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_integrate");
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_INTEGRATE);
   return sphk_integrate(s);
 }
 extern "C" int sph_run_clear_membrane_buffers(sph_solver* s) {
   ENTER(s);
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_MEMBRANES);
   return sphk_clear_membranes(s);
 }
 extern "C" int sph_run_compute_interaction_with_membranes(sph_solver* s) {
   ENTER(s); NEED(s, P_FIND, "sph_run_compute_interaction_with_membranes");
   if (!s->d.pml) return SPH_OK;  // no membrane lists were supplied
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_MEMBRANES);
   return sphk_membranes(s);
 }
 extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s) {
   ENTER(s);
+  s->stateEpoch++;
   StageTimer t(s, SPH_ST_MEMBRANES);
   return sphk_membranes_finalize(s);
 }
@@ -578,6 +596,7 @@ struct StepTail {
 
 static int enqueue_step(sph_solver* s, const StepTail* tail) {
   int rc;
+  s->stateEpoch++;
 #define RUN(stage, call) do { StageTimer t_(s, stage); rc = (call); if (rc != SPH_OK) return rc; } while (0)
   if (s->hasSlab) {
     RUN(SPH_ST_SORT, sphk_hash_sort_post_slab(s));
@@ -1014,8 +1033,8 @@ extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t co
 }
 
 // z-chunks of whole bricks (4 planes) that fit the scratch; at least one brick layer however large a plane is
-static int sample_grid_planes(const int32_t dims[3]) {
-  const size_t planeBytes = sizeof(float) * SPH_SAMPLE_WORDS * (size_t)dims[0] * (size_t)dims[1];
+static int sample_grid_planes(const int32_t dims[3], int words = SPH_SAMPLE_WORDS) {
+  const size_t planeBytes = sizeof(float) * words * (size_t)dims[0] * (size_t)dims[1];
   return (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
 }
 
@@ -1092,6 +1111,9 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
   s->meshCounts[0] = (int64_t)totals[0];
   s->meshCounts[1] = (int64_t)totals[1];
   s->meshValid = true;
+  s->meshTypeMask = typeMask;
+  s->meshField = field;
+  s->meshEpoch = s->stateEpoch;
   counts[0] = s->meshCounts[0];
   counts[1] = s->meshCounts[1];
   return SPH_OK;
@@ -1109,6 +1131,87 @@ extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangl
   return rc;
 }
 
+// ---------------------------------------------------------------------------------------------- gradient sampling
+// The same state, selection, argument rules and scratch as field sampling, with 32-word records (sph_gradient.hip).
+static float gradient_scale(const sph_solver* s) { return (float)(-6.0 * s->d.massWpoly6 * (double)s->cfg.simulationScale); }
+
+extern "C" int sph_sample_gradient_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_gradient_points: bad count or null pointer"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_sample_gradient_points", &p);
+  if (rc != SPH_OK || count == 0) return rc;
+  const size_t rec = sizeof(float) * SPH_GRADIENT_WORDS, perPoint = sizeof(float4) + rec;
+  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
+  rc = sample_scratch(s, (size_t)piece * perPoint);
+  if (rc != SPH_OK) return rc;
+  float* dOut = (float*)s->sampleBuf;
+  float* dPts = (float*)((char*)s->sampleBuf + (size_t)piece * rec);
+  const float K = gradient_scale(s);
+  for (int first = 0; first < count; first += piece) {
+    const int n = std::min(piece, count - first);
+    SPH_HIP(hipMemcpyAsync(dPts, points4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    rc = sphk_gradient_points(s, p, K, dPts, n, dOut);
+    if (rc != SPH_OK) return rc;
+    rc = d2h(s, out + (size_t)first * SPH_GRADIENT_WORDS, dOut, rec * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+extern "C" int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                                        uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
+    sph_set_error("sph_sample_gradient_grid: null pointer or dims <= 0");
+    return SPH_ERR_INVALID;
+  }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_sample_gradient_grid", &p);
+  if (rc != SPH_OK) return rc;
+  const size_t planeBytes = sizeof(float) * SPH_GRADIENT_WORDS * (size_t)dims[0] * (size_t)dims[1];
+  const int planes = sample_grid_planes(dims, SPH_GRADIENT_WORDS);
+  rc = sample_scratch(s, planeBytes * (size_t)planes);
+  if (rc != SPH_OK) return rc;
+  const float K = gradient_scale(s);
+  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
+    const int nz = std::min(planes, dims[2] - k0);
+    rc = sphk_gradient_grid(s, p, K, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
+    if (rc != SPH_OK) return rc;
+    rc = d2h(s, (char*)out + planeBytes * (size_t)k0, s->sampleBuf, planeBytes * (size_t)nz);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+// Normals of the mesh in meshBuf, computed from its vertices where they lie; runs of vertices through the sampling scratch.
+extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
+  ENTER(s);
+  if (!s->meshValid) { sph_set_error("sph_surface_normals: no surface has been extracted"); return SPH_ERR_ORDER; }
+  if (s->meshEpoch != s->stateEpoch) {
+    sph_set_error("sph_surface_normals: the solver's state has changed since the surface was extracted");
+    return SPH_ERR_ORDER;
+  }
+  const int64_t V = s->meshCounts[0];
+  if (V > 0 && !normals) { sph_set_error("sph_surface_normals: null pointer"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &p);
+  if (rc != SPH_OK || V == 0) return rc;
+  const size_t rec = sizeof(float) * 3;
+  const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
+  rc = sample_scratch(s, (size_t)piece * rec);
+  if (rc != SPH_OK) return rc;
+  const float K = gradient_scale(s);
+  for (int64_t first = 0; first < V; first += piece) {
+    const int n = (int)std::min<int64_t>(piece, V - first);
+    rc = sphk_surface_normals(s, p, K, s->meshField, (const float*)s->meshBuf + 3 * (size_t)first, n, (float*)s->sampleBuf);
+    if (rc != SPH_OK) return rc;
+    rc = d2h(s, normals + 3 * (size_t)first, s->sampleBuf, rec * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- slab decomposition
 extern "C" int sph_particle_count(sph_solver* s) {
   ENTER(s);
@@ -1117,6 +1220,7 @@ extern "C" int sph_particle_count(sph_solver* s) {
 
 extern "C" int sph_slab_init(sph_solver* s, const sph_slab* slab, const uint32_t* globalIds) {
   ENTER(s);
+  s->stateEpoch++;
   if (!slab || !globalIds) { sph_set_error("sph_slab_init: null argument"); return SPH_ERR_INVALID; }
   if (s->cfg.cellIdMask != 0xffffffffu) { sph_set_error("slab decomposition needs wide cell ids (cellIdMask = 0xffffffff)"); return SPH_ERR_INVALID; }
   if (s->d.hasElastic) { sph_set_error("slab decomposition supports pure-liquid scenes only"); return SPH_ERR_INVALID; }
@@ -1215,6 +1319,7 @@ extern "C" int sph_slab_step_messages(sph_solver* s, int32_t counts[2]) {
 
 extern "C" int sph_slab_rebuild(sph_solver* s, const void* recvDown, int32_t nDown, const void* recvUp, int32_t nUp) {
   ENTER(s);
+  s->stateEpoch++;
   if (!s->hasSlab || nDown < 0 || nUp < 0 || (nDown && !recvDown) || (nUp && !recvUp)) { sph_set_error("sph_slab_rebuild: bad arguments"); return SPH_ERR_INVALID; }
   if (s->slabStepPending) {  // overlapped step: the kept count arrives with the end of the step
     SPH_HIP(hipStreamSynchronize(s->stream));
@@ -1241,6 +1346,7 @@ extern "C" int sph_slab_rebuild(sph_solver* s, const void* recvDown, int32_t nDo
 extern "C" int sph_slab_rebuild_framed(sph_solver* s, const void* frameDown, int32_t capDownRecords, const void* frameUp,
                                        int32_t capUpRecords) {
   ENTER(s);
+  s->stateEpoch++;
   if (!s->hasSlab || capDownRecords < 0 || capUpRecords < 0 || (s->slab.hasLower && !frameDown) || (s->slab.hasUpper && !frameUp)) {
     sph_set_error("sph_slab_rebuild_framed: slab not initialised, negative capacity, or no frame from a neighbour that exists");
     return SPH_ERR_INVALID;

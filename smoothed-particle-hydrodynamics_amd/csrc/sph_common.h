@@ -129,6 +129,11 @@ struct sph_solver {
   void* surfBuf; size_t surfBytes;
   void* meshBuf; size_t meshBytes;
   int64_t meshCounts[2]; bool meshValid;  // vertices, triangles of the last successful extraction
+  uint32_t meshTypeMask; int meshField;   // ... and its arguments (sph_surface_normals)
+  uint64_t meshEpoch;                     // stateEpoch when it was extracted
+  // bumped by every call that rewrites the sorted state sampling reads (stages, steps, slab calls): sph_surface_normals is
+  // only allowed while it still equals meshEpoch
+  uint64_t stateEpoch;
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -243,6 +248,12 @@ int sphk_sample_points(sph_solver* s, const SampleParams& p, const float* pts4, 
 // grid z-planes [kBase, kBase + nz) of the lattice origin + (float)i * spacing; out = nz x ny x nx records (device)
 int sphk_sample_grid(sph_solver* s, const SampleParams& p, const float origin[3], const float spacing[3], int nx, int ny,
                      int kBase, int nz, float* out);
+// sph_gradient.hip (the gradient records of include/sphmi.h; K = (float)(-6 * massWpoly6 * simScale)); device pointers
+int sphk_gradient_points(sph_solver* s, const SampleParams& p, float K, const float* pts4, int count, float* out);
+int sphk_gradient_grid(sph_solver* s, const SampleParams& p, float K, const float origin[3], const float spacing[3], int nx, int ny,
+                       int kBase, int nz, float* out);  // as sphk_sample_grid, 32-word records
+// normals[3*i..] of the `count` packed (x, y, z) vertices at verts, from the gradient of record word `field` (0..5)
+int sphk_surface_normals(sph_solver* s, const SampleParams& p, float K, int field, const float* verts, int count, float* normals);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

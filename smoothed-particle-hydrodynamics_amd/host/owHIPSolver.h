@@ -79,6 +79,16 @@ class owHIPSolver {
     check(sph_extract_surface(s_, origin, spacing, dims, typeMask, field, iso, counts), "extractSurface");
   }
   void readSurface(float* vertices, int32_t* triangles) { check(sph_read_surface(s_, vertices, triangles), "readSurface"); }
+  // beyond the reference: SPH gradients, vorticity, divergence and Q at points / on sampleGrid's lattice (include/sphmi.h,
+  // sph_sample_gradient_*; SPH_GRADIENT_WORDS floats per record), and unit vertex normals of the last extractSurface mesh
+  // (counts[0] x 3 floats; refused once the solver has stepped since the extraction)
+  void sampleGradientPoints(const float* points4, int count, unsigned int typeMask, float* out) {
+    check(sph_sample_gradient_points(s_, points4, count, typeMask, out), "sampleGradientPoints");
+  }
+  void sampleGradientGrid(const float origin[3], const float spacing[3], const int dims[3], unsigned int typeMask, float* out) {
+    check(sph_sample_gradient_grid(s_, origin, spacing, dims, typeMask, out), "sampleGradientGrid");
+  }
+  void surfaceNormals(float* normals) { check(sph_surface_normals(s_, normals), "surfaceNormals"); }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

@@ -13,6 +13,9 @@
 //        after every K-th step, extract the isosurface shepard = X (default 0.5) of the liquid and elastic particles on the same
 //        box-spanning lattice (sph_extract_surface) and write DIR/surface_<steps done>.ply (binary little-endian PLY;
 //        sphmi.frames.read_ply)
+//   ... --sample-gradients      with --sample-grid: also write DIR/gradients_<steps done>.bin, sph_sample_gradient_grid's
+//        32-word records on the same lattice (NZ x NY x NX x 32; sphmi.frames.read_gradients)
+//   ... --surface-normals       with --surface-grid: the PLY files carry unit vertex normals (sph_surface_normals) as nx ny nz
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -37,14 +40,27 @@ struct Watch {  // owHelper::refreshTime / watch_report (owHelper.cpp:44-57,1806
   double elapsed() const { return t1 - t0; }
 };
 
-// binary little-endian PLY: float x y z per vertex, list uchar int vertex_indices per face (sphmi.frames.write_ply)
-static void write_ply(const std::string& path, const std::vector<float>& verts, const std::vector<int32_t>& tris) {
+// binary little-endian PLY: float x y z (and nx ny nz when normals are given) per vertex, list uchar int vertex_indices per
+// face (sphmi.frames.write_ply)
+static void write_ply(const std::string& path, const std::vector<float>& verts, const std::vector<int32_t>& tris,
+                      const std::vector<float>* normals = nullptr) {
   const size_t nv = verts.size() / 3, nt = tris.size() / 3;
   FILE* f = fopen(path.c_str(), "wb");
   if (!f) throw std::runtime_error("cannot write " + path);
-  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
-             "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", nv, nt);
-  bool ok = fwrite(verts.data(), sizeof(float), verts.size(), f) == verts.size();
+  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+             "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", nv,
+          normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", nt);
+  bool ok;
+  if (normals) {
+    std::vector<float> vn(nv * 6);
+    for (size_t v = 0; v < nv; v++) {
+      memcpy(&vn[v * 6], &verts[v * 3], 12);
+      memcpy(&vn[v * 6 + 3], &(*normals)[v * 3], 12);
+    }
+    ok = fwrite(vn.data(), sizeof(float), vn.size(), f) == vn.size();
+  } else {
+    ok = fwrite(verts.data(), sizeof(float), verts.size(), f) == verts.size();
+  }
   std::vector<unsigned char> faces(nt * 13);
   for (size_t t = 0; t < nt; t++) {
     faces[t * 13] = 3;
@@ -60,6 +76,7 @@ int main(int argc, char** argv) {
   double box[3] = {0, 0, 0}; int lat[3] = {0, 0, 0};
   int sampleDims[3] = {0, 0, 0}, sampleEvery = 0; const char* sampleDir = nullptr;
   int surfDims[3] = {0, 0, 0}, surfEvery = 0; const char* surfDir = nullptr; float surfIso = 0.5f;
+  bool sampleGradients = false, surfNormals = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--velocity") && i + 1 < argc) velFile = argv[++i];
@@ -80,6 +97,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--surface-every") && i + 1 < argc) surfEvery = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--surface-out") && i + 1 < argc) surfDir = argv[++i];
     else if (!strcmp(argv[i], "--surface-iso") && i + 1 < argc) surfIso = (float)atof(argv[++i]);
+    else if (!strcmp(argv[i], "--sample-gradients")) sampleGradients = true;
+    else if (!strcmp(argv[i], "--surface-normals")) surfNormals = true;
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool sampling = sampleDims[0] > 0 || sampleEvery > 0 || sampleDir;
@@ -92,6 +111,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--surface-grid NX NY NZ (all >= 2), --surface-every K (> 0) and --surface-out DIR go together\n");
     return 2;
   }
+  if (sampleGradients && !sampling) { fprintf(stderr, "--sample-gradients needs --sample-grid\n"); return 2; }
+  if (surfNormals && !surfacing) { fprintf(stderr, "--surface-normals needs --surface-grid\n"); return 2; }
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -143,7 +164,8 @@ int main(int argc, char** argv) {
     std::vector<float> fields(sampling ? (size_t)sampleDims[0] * sampleDims[1] * sampleDims[2] * SPH_SAMPLE_WORDS : 0);
     float surfSpacing[3];
     for (int k = 0; k < 3; k++) surfSpacing[k] = surfDims[k] > 1 ? (boxMax[k] - sampleOrigin[k]) / (float)(surfDims[k] - 1) : 0.f;
-    std::vector<float> meshVerts;
+    std::vector<float> gradients(sampleGradients ? (size_t)sampleDims[0] * sampleDims[1] * sampleDims[2] * SPH_GRADIENT_WORDS : 0);
+    std::vector<float> meshVerts, meshNormals;
     std::vector<int32_t> meshTris;
     Watch helper; helper.quiet = quiet;
     double total = 0;
@@ -193,6 +215,15 @@ int main(int argc, char** argv) {
         if (!f || fwrite(fields.data(), sizeof(float), fields.size(), f) != fields.size()) throw std::runtime_error("cannot write " + path);
         fclose(f);
         helper.report("_sampleGrid: \t\t%9.3f ms\n");
+        if (sampleGradients) {
+          ocl_solver->sampleGradientGrid(sampleOrigin, sampleSpacing, sampleDims, (1u << SPH_LIQUID_PARTICLE) |
+                                         (1u << SPH_ELASTIC_PARTICLE) | (1u << SPH_BOUNDARY_PARTICLE), gradients.data());
+          const std::string gpath = std::string(sampleDir) + "/gradients_" + std::to_string(iterationCount + 1) + ".bin";
+          FILE* g = fopen(gpath.c_str(), "wb");
+          if (!g || fwrite(gradients.data(), sizeof(float), gradients.size(), g) != gradients.size()) throw std::runtime_error("cannot write " + gpath);
+          fclose(g);
+          helper.report("_sampleGradientGrid: \t%9.3f ms\n");
+        }
       }
       if (surfacing && (iterationCount + 1) % surfEvery == 0) {
         int64_t counts[2];
@@ -201,7 +232,12 @@ int main(int argc, char** argv) {
         meshVerts.resize((size_t)counts[0] * 3);
         meshTris.resize((size_t)counts[1] * 3);
         ocl_solver->readSurface(meshVerts.data(), meshTris.data());
-        write_ply(std::string(surfDir) + "/surface_" + std::to_string(iterationCount + 1) + ".ply", meshVerts, meshTris);
+        if (surfNormals) {
+          meshNormals.resize(meshVerts.size());
+          ocl_solver->surfaceNormals(meshNormals.data());
+        }
+        write_ply(std::string(surfDir) + "/surface_" + std::to_string(iterationCount + 1) + ".ply", meshVerts, meshTris,
+                  surfNormals ? &meshNormals : nullptr);
         helper.report("_extractSurface: \t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)

@@ -17,6 +17,7 @@ HOST_LIB_PATH = os.path.join(_PKG, "libsphmi_host.so")
 ABI_VERSION = 2
 SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
 SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
+GRADIENT_WORDS = 32  # sph_sample_gradient_* record: the sample record, then gradients, vorticity, divergence, Q (frames.GRADIENT_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -101,7 +102,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_reset_stage_times", "sph_step_sort_passes", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
-                    "sph_sample_grid", "sph_extract_surface", "sph_read_surface"] + _STAGE_FUNCS
+                    "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
+                    "sph_sample_gradient_grid", "sph_surface_normals"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -183,6 +185,9 @@ def device_lib():
         L.sph_extract_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_float,
                                           C.c_void_p]
         L.sph_read_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_sample_gradient_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        L.sph_sample_gradient_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sph_surface_normals.argtypes = [C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -520,12 +525,47 @@ class owHIPSolver:
         sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
         dm = np.ascontiguousarray(dims, np.int32).reshape(3)
         counts = np.zeros(2, np.int64)
+        self._mesh_vertices = 0  # (a failed extraction leaves no mesh behind)
         self._chk(self._L.sph_extract_surface(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), int(field), float(iso),
                                               _ptr(counts)))
+        self._mesh_vertices = int(counts[0])
         verts = np.empty((int(counts[0]), 3), np.float32)
         tris = np.empty((int(counts[1]), 3), np.int32)
         self._chk(self._L.sph_read_surface(self._h, _ptr(verts) if verts.size else None, _ptr(tris) if tris.size else None))
         return verts, tris
+
+    # --- gradient sampling (sph_sample_gradient_points / sph_sample_gradient_grid) and surface normals ---
+    def sample_gradient_points(self, points, types=(1, 2, 3)):
+        """sample_points with the SPH gradients: float32[Q, 32] records (the 8 sample words, grad rho, grad shepard, grad u
+        row-major, grad p, vorticity, divergence, Q, 0; frames.GRADIENT_FIELDS, include/sphmi.h). Gradients are per metre of
+        simulation-scaled space."""
+        pts = np.asarray(points, np.float32)
+        pts = pts.reshape(-1, pts.shape[-1]) if pts.ndim else pts.reshape(-1, 1)
+        if pts.shape[1] not in (3, 4):
+            raise SphError("sample_gradient_points: points must be [Q, 3] or [Q, 4]")
+        p4 = np.zeros((pts.shape[0], 4), np.float32)
+        p4[:, :3] = pts[:, :3]
+        out = np.empty((p4.shape[0], GRADIENT_WORDS), np.float32)
+        self._chk(self._L.sph_sample_gradient_points(self._h, _ptr(p4), p4.shape[0], type_mask(types), _ptr(out)))
+        return out
+
+    def sample_gradient_grid(self, origin, spacing, dims, types=(1, 2, 3)):
+        """The same on sample_grid's lattice: float32[nz, ny, nx, 32]."""
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        size = int(dm[0]) * int(dm[1]) * int(dm[2]) if (dm > 0).all() else 0
+        out = np.empty((int(dm[2]), int(dm[1]), int(dm[0]), GRADIENT_WORDS) if size else (1, GRADIENT_WORDS), np.float32)
+        self._chk(self._L.sph_sample_gradient_grid(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), _ptr(out)))
+        return out
+
+    def surface_normals(self):
+        """float32[V, 3] unit normals (toward lower f) of the vertices of the last extract_surface, from the gradient of the
+        contoured field at each vertex; (0, 0, 0) where that gradient vanishes. Refused once the solver has stepped since."""
+        n = getattr(self, "_mesh_vertices", 0)  # 0 without a mesh: the library reports SPH_ERR_ORDER
+        out = np.empty((n, 3), np.float32)
+        self._chk(self._L.sph_surface_normals(self._h, _ptr(out) if out.size else None))
+        return out
 
     # --- extras ---
     def step(self, iterationCount=0):

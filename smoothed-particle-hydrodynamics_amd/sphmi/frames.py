@@ -12,7 +12,11 @@ Field grids (owHIPSolver.sample_grid, float32[nz, ny, nx, 8] records: density, s
 map (the dam-break gauge) and `read_fields` loads the raw files `sphmi_run --sample-grid` writes.
 
 Surface meshes (owHIPSolver.extract_surface): `write_ply` / `read_ply` write and read binary little-endian PLY triangle meshes,
-the format `sphmi_run --surface-out` writes.
+the format `sphmi_run --surface-out` writes, with vertex normals (owHIPSolver.surface_normals) when given.
+
+Gradient grids (owHIPSolver.sample_gradient_grid, float32[nz, ny, nx, 32] records named by GRADIENT_FIELDS):
+`write_vtk_gradients` writes vorticity, density gradient, divergence and Q as a legacy-VTK volume, and `read_gradients` loads
+the raw files `sphmi_run --sample-gradients` writes.
 """
 import numpy as np
 
@@ -82,6 +86,10 @@ def write_vtk(path, position, density, include_boundary=False):
 
 
 GRID_FIELDS = ("density", "shepard", "vx", "vy", "vz", "pressure", "count")
+# the 32 words of a sph_sample_gradient_* record (include/sphmi.h); gradients are per metre of simulation-scaled space
+GRADIENT_FIELDS = GRID_FIELDS + ("unused7",) + \
+    tuple("d%s_d%s" % (f, c) for f in ("rho", "shepard", "vx", "vy", "vz", "p") for c in "xyz") + \
+    ("vorticity_x", "vorticity_y", "vorticity_z", "divergence", "q_criterion", "unused31")
 
 
 def write_vtk_grid(path, origin, spacing, fields):
@@ -141,25 +149,34 @@ def read_fields(path, dims):
     return np.fromfile(path, np.float32).reshape(nz, ny, nx, 8)
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY of a triangle mesh (extract_surface): `float x y z` per vertex, `list uchar int vertex_indices`
-    per face. ParaView, Blender and MeshLab read it."""
+def write_ply(path, vertices, triangles, normals=None):
+    """Binary little-endian PLY of a triangle mesh (extract_surface): `float x y z` per vertex (then `float nx ny nz` when
+    `normals` [V, 3] is given, e.g. surface_normals()), `list uchar int vertex_indices` per face. ParaView, Blender and
+    MeshLab read it."""
     v = np.ascontiguousarray(vertices, "<f4").reshape(-1, 3)
     t = np.ascontiguousarray(triangles, "<i4").reshape(-1, 3)
+    nprops = ""
+    if normals is not None:
+        n = np.asarray(normals, "<f4").reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError("normals must be [V, 3] like the vertices")
+        v = np.ascontiguousarray(np.concatenate([v, n], axis=1))
+        nprops = "property float nx\nproperty float ny\nproperty float nz\n"
     faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     faces["n"] = 3
     faces["i"] = t
     with open(path, "wb") as f:
-        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (v.shape[0], t.shape[0])).encode())
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (v.shape[0], nprops, t.shape[0])).encode())
         f.write(v.tobytes())
         f.write(faces.tobytes())
     return v.shape[0], t.shape[0]
 
 
-def read_ply(path):
+def read_ply(path, with_normals=False):
     """(vertices float32[V, 3], triangles int32[T, 3]) of a binary little-endian triangle PLY as write_ply (and sphmi_run
-    --surface-out) write it."""
+    --surface-out) write it. with_normals=True adds a third item: the `nx ny nz` vertex properties as float32[V, 3], or
+    None when the file has none."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -188,4 +205,46 @@ def read_ply(path):
     faces = np.frombuffer(data, [("n", "u1"), ("i", "<i4", (3,))], nf, end + 4 * nv * len(vprops))
     if nf and (faces["n"] != 3).any():
         raise ValueError("%s: faces must be triangles" % path)
-    return np.array(vert, np.float32), np.array(faces["i"], np.int32).reshape(nf, 3)
+    v, t = np.array(vert, np.float32), np.array(faces["i"], np.int32).reshape(nf, 3)
+    if not with_normals:
+        return v, t
+    normals = None
+    if all(c in vprops for c in ("nx", "ny", "nz")):
+        allv = np.frombuffer(data, "<f4", nv * len(vprops), end).reshape(nv, len(vprops))
+        normals = np.array(allv[:, [vprops.index(c) for c in ("nx", "ny", "nz")]], np.float32)
+    return v, t, normals
+
+
+def write_vtk_gradients(path, origin, spacing, records):
+    """Legacy-VTK STRUCTURED_POINTS (binary, big-endian like write_vtk_grid) of a sample_gradient_grid result `records`
+    [nz, ny, nx, 32]: point data `vorticity` and `density_gradient` (vectors), `divergence` and `q_criterion` (scalars)."""
+    g = np.asarray(records, np.float32)
+    if g.ndim != 4 or g.shape[3] != len(GRADIENT_FIELDS):
+        raise ValueError("records must be [nz, ny, nx, 32]")
+    nz, ny, nx = g.shape[:3]
+    n = nx * ny * nz
+    o = [float(np.float32(v)) for v in origin]
+    sp = [float(np.float32(v)) for v in spacing]
+    w = GRADIENT_FIELDS.index
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi gradients\nBINARY\nDATASET STRUCTURED_POINTS\n")
+        f.write(("DIMENSIONS %d %d %d\n" % (nx, ny, nz)).encode())
+        f.write(("ORIGIN %.9g %.9g %.9g\n" % tuple(o)).encode())
+        f.write(("SPACING %.9g %.9g %.9g\n" % tuple(sp)).encode())
+        f.write(("POINT_DATA %d\n" % n).encode())
+        for name, first in (("vorticity", w("vorticity_x")), ("density_gradient", w("drho_dx"))):
+            f.write(("VECTORS %s float\n" % name).encode())
+            f.write(np.ascontiguousarray(g[..., first:first + 3]).astype(">f4").tobytes())
+            f.write(b"\n")
+        for name in ("divergence", "q_criterion"):
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(g[..., w(name)]).astype(">f4").tobytes())
+            f.write(b"\n")
+    return n
+
+
+def read_gradients(path, dims):
+    """A `sphmi_run --sample-gradients` output file (raw float32 records in sph_sample_gradient_grid's layout) as
+    [NZ, NY, NX, 32]."""
+    nx, ny, nz = (int(v) for v in dims)
+    return np.fromfile(path, np.float32).reshape(nz, ny, nx, len(GRADIENT_FIELDS))
