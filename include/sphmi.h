@@ -241,6 +241,52 @@ int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float s
  * counts[0] > 0. */
 int sph_surface_normals(sph_solver* s, float* normals /* host, counts[0] x 3 */);
 
+/* ---- Flow diagnostics (reductions and histograms over the particles; no reference counterpart) ------------------------------
+ * State: the sorted state of the last completed step, exactly the one sph_sample_* describes (one integration step behind
+ * sph_read_position). Sorted particle j is SELECTED for the region (x0,y0,z0,x1,y1,z1) when its type t = (int)position.w is
+ * 1..3 with (1 << t) & typeMask, its cell key is in the step's cell table (key < gridCellCount, as sampling), and
+ * x0 <= x && x < x1, y0 <= y && y < y1, z0 <= z && z < z1 (float compares; a bound may be +-infinity, so (-inf, +inf) on every
+ * axis is "everything"; a region with x0 >= x1 is empty).
+ * Per-particle terms, IN FLOAT, in the written order, no contraction, then widened to double (exact):
+ *   v2 = vx*vx + vy*vy + vz*vz;  Lx = y*vz - z*vy, Ly = z*vx - x*vz, Lz = x*vy - y*vx;  e = rho - rho0 (cfg.rho0), e2 = e*e.
+ * An unselected particle contributes +0.0 to every sum. Record, SPH_DIAG_WORDS doubles per region:
+ *   0        n, the number of selected particles
+ *   1..3     sum x, y, z            4..6   sum vx, vy, vz          7..9   sum Lx, Ly, Lz (about the origin, per unit mass)
+ *   10       sum v2                 11     sum rho                 12     sum e2
+ *   13       sum p (pressure after the last predict-correct iteration)
+ *   16, 17   min rho, max rho       18, 19 min p, max p
+ *   20..22   max v2; the lowest sorted index that attains it; that particle's original id (its particleIndex value)
+ *   23..25   min x, y, z            26..28 max x, y, z             14, 15, 29..31   0 (reserved)
+ * Minima and maxima are float compares; the result is canonicalised by + 0.0f (-0 is reported as +0) and widened. With n = 0
+ * words 16..20 and 23..28 are 0 and words 21, 22 are -1.
+ * THE SUMS ARE DOUBLES ADDED IN A FIXED SHAPE, so that a result depends on nothing but the state and the region: not on the
+ * launch geometry, the device, or the other regions of the call. With the terms t[0..N) in ascending sorted index:
+ *   reduce(a): pad a with +0.0 to a whole number (at least one) of chunks of 1024
+ *              in each chunk, for stride = 512, 256, ..., 1:  a[i] = a[i] + a[i + stride]  for every i < stride
+ *              c = the chunks' a[0], in chunk order;  return c[0] if there is one chunk, else reduce(c)
+ * (at most three levels for SPH_MAX_PARTICLES; trailing zero terms never change a result). No atomics on floating-point values.
+ * A float widened to double has 29 spare mantissa bits, so unless the terms span more than ~2^29 in magnitude these sums equal
+ * the exactly rounded sum of the terms.
+ * Boundary particles (type 3) keep the wall normal in `velocity`: sums over them are legal but are not momenta.
+ * Errors (both functions): SPH_ERR_ORDER before a step's density and pressure-force stages have run; SPH_ERR_INVALID for a slab
+ * solver, a typeMask of 0 or with bits outside 1..3, null pointers (region6 of sph_histogram may be NULL = everything), count
+ * outside 1..SPH_DIAG_MAX_REGIONS, a NaN region bound, bins outside 1..SPH_HIST_MAX_BINS, field outside 0..6, non-finite lo or
+ * hi, lo >= hi; a blown-up state is reported as by every blocking call. Blocking, on the solver's stream, read-only on every
+ * solver array (a mesh stays valid for sph_surface_normals), not a stage (no stage timing). Device scratch (256 bytes per region
+ * and 1024 particles, or the bins) is grown on demand and freed by sph_destroy. */
+#define SPH_DIAG_WORDS 32
+#define SPH_DIAG_MAX_REGIONS 16
+int sph_diagnostics(sph_solver* s, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
+                    uint32_t typeMask, double* out /* host, count x 32 */);
+/* Distribution of one per-particle quantity q over the selected particles (same state and selection). field: 0 density,
+ * 1 speed sqrtf(v2) (correctly rounded), 2 pressure, 3 the number of valid entries of the particle's neighbour row as a float
+ * (the ids >= 0 of sph_read_neighbor_rows), 4, 5, 6 x, y, z. All in float: q < lo counts in out[0]; q >= hi in out[bins + 1];
+ * otherwise in bin min((int)((q - lo) * scale), bins - 1), scale = (float)bins / (hi - lo) computed once on the host in float.
+ * field 3, lo 0, hi 33, bins 33 is the exact neighbour-count distribution: bin 32 counts the particles at the cap. */
+#define SPH_HIST_MAX_BINS 4096
+int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6 /* host or NULL */,
+                  uint32_t typeMask, uint32_t* out /* host, bins + 2: below, bin 0 .. bins-1, at-or-above */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

@@ -229,7 +229,7 @@ static void free_all(sph_solver* s) {
   void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
                   d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf};
+                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf, s->diagBuf};
   for (void* p : ptrs) if (p) hipFree(p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
@@ -1210,6 +1210,66 @@ extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
     if (rc != SPH_OK) return rc;
   }
   return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- flow diagnostics
+// Reductions and histograms over the same state as sampling (sph_diag.hip); blocking, read-only, no stage timing.
+static int diag_region_ok(const float* b, const char* what) {
+  for (int k = 0; k < 6; k++)
+    if (std::isnan(b[k])) { sph_set_error("%s: a region bound is NaN", what); return SPH_ERR_INVALID; }
+  return SPH_OK;
+}
+
+extern "C" int sph_diagnostics(sph_solver* s, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
+  ENTER(s);
+  if (!regions6 || !out) { sph_set_error("sph_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_diagnostics", &p);
+  if (rc != SPH_OK) return rc;
+  DiagArgs a = {};
+  for (int r = 0; r < count; r++) {
+    rc = diag_region_ok(regions6 + 6 * r, "sph_diagnostics");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
+  }
+  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
+  rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, count));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_diagnostics(s, a, (double*)s->diagBuf, &records);
+  if (rc != SPH_OK) return rc;
+  rc = d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)count);
+  return rc != SPH_OK ? rc : check_finite_state(s);
+}
+
+extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6, uint32_t typeMask,
+                             uint32_t* out) {
+  ENTER(s);
+  if (!out) { sph_set_error("sph_histogram: null pointer"); return SPH_ERR_INVALID; }
+  if (field < 0 || field > 6) { sph_set_error("sph_histogram: field %d is not in 0..6", field); return SPH_ERR_INVALID; }
+  if (bins < 1 || bins > SPH_HIST_MAX_BINS) { sph_set_error("sph_histogram: bins %d is not in 1..%d", bins, SPH_HIST_MAX_BINS); return SPH_ERR_INVALID; }
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) { sph_set_error("sph_histogram: lo and hi must be finite with lo < hi"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_histogram", &p);
+  if (rc != SPH_OK) return rc;
+  HistArgs a = {};
+  if (region6) {
+    rc = diag_region_ok(region6, "sph_histogram");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
+  } else {
+    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
+  }
+  volatile float width = hi - lo;
+  volatile float scale = (float)bins / width;
+  a.typeMask = typeMask; a.field = field; a.bins = bins; a.lo = lo; a.hi = hi; a.scale = scale;
+  rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(uint32_t) * (size_t)(bins + 2));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_histogram(s, a, (uint32_t*)s->diagBuf);
+  if (rc != SPH_OK) return rc;
+  rc = d2h(s, out, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
+  return rc != SPH_OK ? rc : check_finite_state(s);
 }
 
 // ---------------------------------------------------------------------------------------------- slab decomposition

@@ -125,6 +125,8 @@ struct sph_solver {
   uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (check_finite_state)
   // field sampling (sph_sample_points / sph_sample_grid): device scratch for query points and records, grown on demand
   void* sampleBuf; size_t sampleBytes;
+  // diagnostics (sph_diagnostics / sph_histogram): device scratch for the reduction tree's partials and the bins, grown on demand
+  void* diagBuf; size_t diagBytes;
   // isosurface extraction (sph_extract_surface / sph_read_surface): lattice scratch and the last mesh, grown on demand
   void* surfBuf; size_t surfBytes;
   void* meshBuf; size_t meshBytes;
@@ -254,6 +256,22 @@ int sphk_gradient_grid(sph_solver* s, const SampleParams& p, float K, const floa
                        int kBase, int nz, float* out);  // as sphk_sample_grid, 32-word records
 // normals[3*i..] of the `count` packed (x, y, z) vertices at verts, from the gradient of record word `field` (0..5)
 int sphk_surface_normals(sph_solver* s, const SampleParams& p, float K, int field, const float* verts, int count, float* normals);
+// sph_diag.hip (the records and histograms of include/sphmi.h; read-only on every solver array)
+struct DiagArgs {
+  float box[SPH_DIAG_MAX_REGIONS][6];  // x0, y0, z0, x1, y1, z1 per region
+  int count;
+  uint32_t typeMask;
+  float rho0;
+};
+struct HistArgs {
+  float box[6];
+  uint32_t typeMask;
+  int field, bins;
+  float lo, hi, scale;  // scale = (float)bins / (hi - lo)
+};
+size_t sphk_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_DIAG_WORDS records
+int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records);  // *records: where the records land
+int sphk_histogram(sph_solver* s, const HistArgs& a, uint32_t* out);  // out: bins + 2 device words
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

@@ -1,0 +1,347 @@
+// Flow diagnostics: reductions over the selected particles of up to 16 axis-aligned regions, and histograms of one per-particle
+// quantity, read from the sorted state of the last completed step (include/sphmi.h: sph_diagnostics / sph_histogram, DESIGN.md
+// §15). Read-only on every solver array.
+//
+// The sums are doubles reduced in the FIXED TREE of the contract: the terms in ascending sorted index, padded with +0.0 to whole
+// chunks of 1024; in a chunk, a[i] += a[i + stride] for stride = 512 ... 1; the chunks' results are the terms of the next
+// level, until one chunk is left. One 256-thread block owns one chunk, so the shape depends on nothing but N:
+//   stride 512, 256   thread t holds elements t, t+256, t+512, t+768:  (e0 + e2) + (e1 + e3) in registers
+//   stride 128, 64    across the four waves, through LDS (every thread parks its 14 values there: 28 KB per block)
+//   stride 32 ... 1   inside one wave, __shfl_down
+// No floating-point atomics anywhere. Extremes are order-independent (float compares; the max-v2 particle by the pair
+// (larger v2, then lower index)) and travel through the levels as exactly widened doubles.
+#include "sph_common.h"
+
+#include <algorithm>
+
+#define DIAG_CHUNK 1024
+#define DIAG_SUMS 14  // record words 0..13
+
+// Partials of a level: part[(region * SPH_DIAG_WORDS + word) * chunks + chunk], so that the next level reads them coalesced.
+__device__ __forceinline__ size_t diag_at(int region, int word, int chunks, int chunk) {
+  return ((size_t)(region * SPH_DIAG_WORDS + word)) * (size_t)chunks + (size_t)chunk;
+}
+
+__device__ __forceinline__ double diag_wave_sum(double x) {  // strides 32 ... 1 of the tree; lane 0 holds the result
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) x = x + __shfl_down(x, s, 64);
+  return x;
+}
+
+// the 10 plain extremes of a record, in this order: words 16, 18, 23, 24, 25 (minima), then 17, 19, 26, 27, 28 (maxima)
+__device__ static const int kDiagMinWord[5] = {16, 18, 23, 24, 25};
+__device__ static const int kDiagMaxWord[5] = {17, 19, 26, 27, 28};
+
+// ---- level 0: particles -> one partial per chunk, word and region ---------------------------------------------------------
+// Every array is read once, whatever the number of regions: the per-particle terms stay in registers and the region loop only
+// selects among them.
+__global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, double* __restrict__ part, int chunks) {
+  __shared__ double sh[DIAG_SUMS][SPH_BLOCK];
+  __shared__ float shx[4][10];
+  __shared__ float shv[4];
+  __shared__ int shi[4];
+  const int t = threadIdx.x, chunk = blockIdx.x, lane = t & 63, wave = t >> 6;
+  float f[4][13];  // x y z, vx vy vz, Lx Ly Lz, v2, rho, e2, p: record words 1..13
+  bool ok[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int j = chunk * DIAG_CHUNK + e * SPH_BLOCK + t;
+    ok[e] = false;
+#pragma unroll
+    for (int w = 0; w < 13; w++) f[e][w] = 0.f;
+    if (j < d.N) {
+      const float4 p = d.sortedPos[j];
+      const float4 v = d.sortedVel[j];
+      const float rho = d.rho[j];
+      const float pr = d.rp[j].y;
+      const uint32_t key = d.keys[j];
+      const int type = (int)p.w;
+      ok[e] = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && key < (uint32_t)d.G;
+      f[e][0] = p.x; f[e][1] = p.y; f[e][2] = p.z;
+      f[e][3] = v.x; f[e][4] = v.y; f[e][5] = v.z;
+      f[e][6] = p.y * v.z - p.z * v.y;
+      f[e][7] = p.z * v.x - p.x * v.z;
+      f[e][8] = p.x * v.y - p.y * v.x;
+      f[e][9] = v.x * v.x + v.y * v.y + v.z * v.z;
+      f[e][10] = rho;
+      const float er = rho - a.rho0;
+      f[e][11] = er * er;
+      f[e][12] = pr;
+    }
+  }
+  for (int r = 0; r < a.count; r++) {
+    const float x0 = a.box[r][0], y0 = a.box[r][1], z0 = a.box[r][2], x1 = a.box[r][3], y1 = a.box[r][4], z1 = a.box[r][5];
+    bool sel[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      sel[e] = ok[e] && x0 <= f[e][0] && f[e][0] < x1 && y0 <= f[e][1] && f[e][1] < y1 && z0 <= f[e][2] && f[e][2] < z1;
+    // No particle of this chunk in the region (the sorted order is spatial, so that is the common case for a small region): every
+    // sum of +0.0 terms is +0.0 and every extreme keeps its identity, which is what the tree below would produce.
+    if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
+      if (t < SPH_DIAG_WORDS) {
+        double x = 0.0;
+        bool used = t < DIAG_SUMS || t == 20 || t == 21;
+        if (t == 20) x = -(double)INFINITY;
+        if (t == 21) x = 2147483647.0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+          if (t == kDiagMinWord[k]) { x = (double)INFINITY; used = true; }
+          if (t == kDiagMaxWord[k]) { x = -(double)INFINITY; used = true; }
+        }
+        if (used) part[diag_at(r, t, chunks, chunk)] = x;
+      }
+      continue;
+    }
+    // sums: strides 512 and 256 in registers, one word at a time (the 14 doubles are never live together)
+#pragma unroll
+    for (int w = 0; w < DIAG_SUMS; w++) {
+      double q[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float x = w == 0 ? 1.0f : f[e][w == 0 ? 0 : w - 1];
+        asm volatile("" : "+v"(x));  // widen here, per region: hoisted out of the loop, the 52 doubles cost 104 VGPRs
+        q[e] = sel[e] ? (double)x : 0.0;
+      }
+      sh[w][t] = (q[0] + q[2]) + (q[1] + q[3]);
+    }
+    // extremes of this thread's four elements, then of its wave
+    float mn[5], mx[5], bestV = -INFINITY;
+    int bestI = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 5; k++) { mn[k] = INFINITY; mx[k] = -INFINITY; }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      if (!sel[e]) continue;
+      const float q[5] = {f[e][10], f[e][12], f[e][0], f[e][1], f[e][2]};
+#pragma unroll
+      for (int k = 0; k < 5; k++) { mn[k] = q[k] < mn[k] ? q[k] : mn[k]; mx[k] = q[k] > mx[k] ? q[k] : mx[k]; }
+      if (f[e][9] > bestV) { bestV = f[e][9]; bestI = chunk * DIAG_CHUNK + e * SPH_BLOCK + t; }  // ascending index: the first wins
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) {
+        const float om = __shfl_down(mn[k], s, 64), ox = __shfl_down(mx[k], s, 64);
+        mn[k] = om < mn[k] ? om : mn[k];
+        mx[k] = ox > mx[k] ? ox : mx[k];
+      }
+      const float ov = __shfl_down(bestV, s, 64);
+      const int oi = __shfl_down(bestI, s, 64);
+      if (ov > bestV || (ov == bestV && oi < bestI)) { bestV = ov; bestI = oi; }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) { shx[wave][k] = mn[k]; shx[wave][5 + k] = mx[k]; }
+      shv[wave] = bestV; shi[wave] = bestI;
+    }
+    __syncthreads();
+    // stride 128
+    if (t < 128) {
+#pragma unroll
+      for (int w = 0; w < DIAG_SUMS; w++) sh[w][t] = sh[w][t] + sh[w][t + 128];
+    }
+    __syncthreads();
+    // stride 64 and the in-wave strides: the 14 words are shared out among the four waves
+    for (int w = wave; w < DIAG_SUMS; w += 4) {
+      const double x = diag_wave_sum(sh[w][lane] + sh[w][lane + 64]);
+      if (lane == 0) part[diag_at(r, w, chunks, chunk)] = x;
+    }
+    if (t < 10) {
+      float x = shx[0][t];
+      for (int q = 1; q < 4; q++) { const float o = shx[q][t]; x = t < 5 ? (o < x ? o : x) : (o > x ? o : x); }
+      part[diag_at(r, t < 5 ? kDiagMinWord[t] : kDiagMaxWord[t - 5], chunks, chunk)] = (double)x;
+    } else if (t == 10) {
+      float bv = shv[0]; int bi = shi[0];
+      for (int q = 1; q < 4; q++) if (shv[q] > bv || (shv[q] == bv && shi[q] < bi)) { bv = shv[q]; bi = shi[q]; }
+      part[diag_at(r, 20, chunks, chunk)] = (double)bv;
+      part[diag_at(r, 21, chunks, chunk)] = (double)bi;
+    }
+    __syncthreads();  // sh / shx are reused by the next region
+  }
+}
+
+// ---- upper levels: `nIn` partials per word and region -> ceil(nIn / 1024); the same tree (tiny launches) ------------------------
+enum { DIAG_OP_SUM = 0, DIAG_OP_MIN = 1, DIAG_OP_MAX = 2 };
+
+template <int OP>
+__device__ __forceinline__ double diag_combine(double a, double b) {
+  if (OP == DIAG_OP_SUM) return a + b;
+  if (OP == DIAG_OP_MIN) return b < a ? b : a;
+  return b > a ? b : a;
+}
+
+template <int OP>
+__device__ double diag_block_reduce(const double* __restrict__ in, int nIn, int chunk, double pad, double* sh) {
+  const int t = threadIdx.x;
+  double e[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int i = chunk * DIAG_CHUNK + k * SPH_BLOCK + t;
+    e[k] = i < nIn ? in[i] : pad;
+  }
+  sh[t] = diag_combine<OP>(diag_combine<OP>(e[0], e[2]), diag_combine<OP>(e[1], e[3]));
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (t < s) sh[t] = diag_combine<OP>(sh[t], sh[t + s]);
+    __syncthreads();
+  }
+  const double x = sh[0];
+  __syncthreads();
+  return x;
+}
+
+// One block per output chunk, region and job: jobs 0..13 the sums, 14..18 the minima, 19..23 the maxima, 24 the pair.
+#define DIAG_UPPER_JOBS 25
+__global__ __launch_bounds__(SPH_BLOCK) void k_diag_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {
+  __shared__ double sh[SPH_BLOCK];
+  __shared__ double shI[SPH_BLOCK];
+  const int t = threadIdx.x, chunk = blockIdx.x, r = blockIdx.y, job = blockIdx.z;
+  if (job < DIAG_SUMS) {
+    const double x = diag_block_reduce<DIAG_OP_SUM>(in + diag_at(r, job, nIn, 0), nIn, chunk, 0.0, sh);
+    if (t == 0) out[diag_at(r, job, nOut, chunk)] = x;
+  } else if (job < DIAG_SUMS + 5) {
+    const int w = kDiagMinWord[job - DIAG_SUMS];
+    const double x = diag_block_reduce<DIAG_OP_MIN>(in + diag_at(r, w, nIn, 0), nIn, chunk, (double)INFINITY, sh);
+    if (t == 0) out[diag_at(r, w, nOut, chunk)] = x;
+  } else if (job < DIAG_SUMS + 10) {
+    const int w = kDiagMaxWord[job - DIAG_SUMS - 5];
+    const double x = diag_block_reduce<DIAG_OP_MAX>(in + diag_at(r, w, nIn, 0), nIn, chunk, -(double)INFINITY, sh);
+    if (t == 0) out[diag_at(r, w, nOut, chunk)] = x;
+  } else {  // the pair (max v2, lowest index that attains it)
+    double bv = -(double)INFINITY, bi = 2147483647.0;
+    for (int k = 0; k < 4; k++) {
+      const int i = chunk * DIAG_CHUNK + k * SPH_BLOCK + t;
+      if (i >= nIn) continue;
+      const double ov = in[diag_at(r, 20, nIn, i)], oi = in[diag_at(r, 21, nIn, i)];
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    sh[t] = bv; shI[t] = bi;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+      if (t < s && (sh[t + s] > sh[t] || (sh[t + s] == sh[t] && shI[t + s] < shI[t]))) { sh[t] = sh[t + s]; shI[t] = shI[t + s]; }
+      __syncthreads();
+    }
+    if (t == 0) { out[diag_at(r, 20, nOut, chunk)] = sh[0]; out[diag_at(r, 21, nOut, chunk)] = shI[0]; }
+  }
+}
+
+// ---- the records: canonical extremes (+ 0.0f), the empty-selection rule, the original id of the fastest particle ------------
+__global__ void k_diag_final(SphDev d, const double* __restrict__ top /* one chunk per word */, double* __restrict__ out) {
+  const int r = blockIdx.x, w = threadIdx.x;  // SPH_DIAG_WORDS threads
+  const double n = top[diag_at(r, 0, 1, 0)];
+  double x = 0.0;
+  if (w < DIAG_SUMS) x = top[diag_at(r, w, 1, 0)];
+  else if (w == 21 || w == 22) {
+    x = -1.0;
+    if (n > 0.0) {
+      const int idx = (int)top[diag_at(r, 21, 1, 0)];
+      if (idx < d.N) x = w == 21 ? (double)idx : (double)d.vals[idx];  // (no index when every selected v2 is NaN)
+    }
+  } else if ((w >= 16 && w <= 20) || (w >= 23 && w <= 28)) {
+    if (n > 0.0) x = (double)((float)top[diag_at(r, w, 1, 0)] + 0.0f);
+  }
+  out[r * SPH_DIAG_WORDS + w] = x;
+}
+
+size_t sphk_diag_scratch_doubles(int N, int regions) {
+  size_t total = 0;
+  for (int n = N;;) {
+    const int c = n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1;
+    total += (size_t)c;
+    if (c == 1) break;
+    n = c;
+  }
+  return (total + 1) * (size_t)regions * SPH_DIAG_WORDS;  // the levels' partials, then the records
+}
+
+int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records) {
+  const int R = a.count;
+  int n = s->d.N;
+  int chunks = n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1;
+  double* cur = scratch;
+  hipLaunchKernelGGL(k_diag_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
+  SPH_HIP(hipGetLastError());
+  while (chunks > 1) {
+    const int nOut = (chunks + DIAG_CHUNK - 1) / DIAG_CHUNK;
+    double* next = cur + (size_t)R * SPH_DIAG_WORDS * (size_t)chunks;
+    hipLaunchKernelGGL(k_diag_upper, dim3(nOut, R, DIAG_UPPER_JOBS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut);
+    SPH_HIP(hipGetLastError());
+    cur = next; chunks = nOut;
+  }
+  double* out = cur + (size_t)R * SPH_DIAG_WORDS;
+  hipLaunchKernelGGL(k_diag_final, dim3(R), dim3(SPH_DIAG_WORDS), 0, s->stream, s->d, (const double*)cur, out);
+  SPH_HIP(hipGetLastError());
+  *records = out;
+  return SPH_OK;
+}
+
+// ---- histogram ---------------------------------------------------------------------------------------------------------------
+// Counts are integers, so any order gives the same result: a histogram per block in LDS (integer atomics), then one integer
+// atomicAdd per non-empty bin and block.
+__device__ __forceinline__ float hist_neighbor_count(const SphDev& d, int id) {
+  int n = 0;
+  const bool wide = d.nbr16[nbr_index(id, 0)] == SPH_N16_WIDE;
+  if (wide) {
+#pragma unroll
+    for (int g = 0; g < 8; g++) {
+      const int4 q = *(const int4*)(d.nbrId + nbr_index(id, 4 * g));
+      n += (q.x >= 0) + (q.y >= 0) + (q.z >= 0) + (q.w >= 0);
+    }
+  } else {
+    const int base = d.nbrBase[id];
+#pragma unroll
+    for (int g = 0; g < 8; g++) {
+      const uint2 q = *(const uint2*)(d.nbr16 + nbr_index(id, 4 * g));
+      const uint32_t e[4] = {q.x & 0xffffu, q.x >> 16, q.y & 0xffffu, q.y >> 16};
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (e[k] != SPH_N16_EMPTY) n += (((e[k] & 0x8000u) ? base : id) + (int)(e[k] & 0x7fffu) - SPH_N16_BIAS) >= 0;
+    }
+  }
+  return (float)n;
+}
+
+__global__ __launch_bounds__(SPH_BLOCK) void k_histogram(SphDev d, HistArgs a, uint32_t* __restrict__ out) {
+  __shared__ uint32_t hist[SPH_HIST_MAX_BINS + 2];
+  const int slots = a.bins + 2;
+  for (int b = threadIdx.x; b < slots; b += SPH_BLOCK) hist[b] = 0u;
+  __syncthreads();
+  for (int j = blockIdx.x * SPH_BLOCK + threadIdx.x; j < d.N; j += gridDim.x * SPH_BLOCK) {
+    const float4 p = d.sortedPos[j];
+    const int type = (int)p.w;
+    if (!(type >= 1 && type <= 3 && ((1u << type) & a.typeMask))) continue;
+    if (!(d.keys[j] < (uint32_t)d.G)) continue;
+    if (!(a.box[0] <= p.x && p.x < a.box[3] && a.box[1] <= p.y && p.y < a.box[4] && a.box[2] <= p.z && p.z < a.box[5])) continue;
+    float q;
+    switch (a.field) {
+      case 0: q = d.rho[j]; break;
+      case 1: { const float4 v = d.sortedVel[j]; q = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); } break;
+      case 2: q = d.rp[j].y; break;
+      case 3: q = hist_neighbor_count(d, j); break;
+      case 4: q = p.x; break;
+      case 5: q = p.y; break;
+      default: q = p.z; break;
+    }
+    int slot;
+    if (q < a.lo) slot = 0;
+    else if (q >= a.hi) slot = a.bins + 1;
+    else {
+      const int b = (int)((q - a.lo) * a.scale);
+      slot = 1 + (b < a.bins - 1 ? b : a.bins - 1);
+      if (slot < 1) slot = 1;  // (a NaN value; the state has blown up)
+    }
+    atomicAdd(&hist[slot], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < slots; b += SPH_BLOCK)
+    if (hist[b]) atomicAdd(&out[b], hist[b]);
+}
+
+int sphk_histogram(sph_solver* s, const HistArgs& a, uint32_t* out) {
+  SPH_HIP(hipMemsetAsync(out, 0, sizeof(uint32_t) * (size_t)(a.bins + 2), s->stream));
+  if (s->d.N <= 0) return SPH_OK;
+  const int blocks = std::min(sph_blocks(s->d.N), 4096);
+  hipLaunchKernelGGL(k_histogram, dim3(blocks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, out);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}

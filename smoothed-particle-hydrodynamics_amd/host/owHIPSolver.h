@@ -89,6 +89,14 @@ class owHIPSolver {
     check(sph_sample_gradient_grid(s_, origin, spacing, dims, typeMask, out), "sampleGradientGrid");
   }
   void surfaceNormals(float* normals) { check(sph_surface_normals(s_, normals), "surfaceNormals"); }
+  // beyond the reference: reductions over the particles inside `count` (1..16) regions (x0,y0,z0,x1,y1,z1), SPH_DIAG_WORDS doubles
+  // each, and the distribution of one per-particle quantity in bins + 2 counters (include/sphmi.h, sph_diagnostics / sph_histogram)
+  void diagnostics(const float* regions6, int count, unsigned int typeMask, double* out) {
+    check(sph_diagnostics(s_, regions6, count, typeMask, out), "diagnostics");
+  }
+  void histogram(int field, float lo, float hi, int bins, const float* region6, unsigned int typeMask, uint32_t* out) {
+    check(sph_histogram(s_, field, lo, hi, bins, region6, typeMask, out), "histogram");
+  }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

@@ -16,7 +16,12 @@
 //   ... --sample-gradients      with --sample-grid: also write DIR/gradients_<steps done>.bin, sph_sample_gradient_grid's
 //        32-word records on the same lattice (NZ x NY x NX x 32; sphmi.frames.read_gradients)
 //   ... --surface-normals       with --surface-grid: the PLY files carry unit vertex normals (sph_surface_normals) as nx ny nz
+//   ... --diagnostics-every K --diagnostics-out FILE.csv [--diagnostics-region X0 Y0 Z0 X1 Y1 Z1]...
+//        after every K-th step, sph_diagnostics of the liquid and elastic particles over the whole scene (region 0) and up to 15
+//        further regions ("inf" / "-inf" are accepted as bounds): one CSV row per report and region (step, region, the 32 record
+//        words as %.17g; sphmi.frames.read_diagnostics_csv) and, unless --quiet, one summary line per report
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -77,6 +82,8 @@ int main(int argc, char** argv) {
   int sampleDims[3] = {0, 0, 0}, sampleEvery = 0; const char* sampleDir = nullptr;
   int surfDims[3] = {0, 0, 0}, surfEvery = 0; const char* surfDir = nullptr; float surfIso = 0.5f;
   bool sampleGradients = false, surfNormals = false;
+  int diagEvery = 0; bool diagEverySeen = false; const char* diagFile = nullptr;
+  std::vector<float> diagRegions = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};  // region 0: everything
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--velocity") && i + 1 < argc) velFile = argv[++i];
@@ -98,6 +105,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--surface-out") && i + 1 < argc) surfDir = argv[++i];
     else if (!strcmp(argv[i], "--surface-iso") && i + 1 < argc) surfIso = (float)atof(argv[++i]);
     else if (!strcmp(argv[i], "--sample-gradients")) sampleGradients = true;
+    else if (!strcmp(argv[i], "--diagnostics-every") && i + 1 < argc) { diagEvery = atoi(argv[++i]); diagEverySeen = true; }
+    else if (!strcmp(argv[i], "--diagnostics-out") && i + 1 < argc) diagFile = argv[++i];
+    else if (!strcmp(argv[i], "--diagnostics-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) diagRegions.push_back((float)atof(argv[++i])); }
     else if (!strcmp(argv[i], "--surface-normals")) surfNormals = true;
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
@@ -113,6 +123,18 @@ int main(int argc, char** argv) {
   }
   if (sampleGradients && !sampling) { fprintf(stderr, "--sample-gradients needs --sample-grid\n"); return 2; }
   if (surfNormals && !surfacing) { fprintf(stderr, "--surface-normals needs --surface-grid\n"); return 2; }
+  const int diagCount = (int)(diagRegions.size() / 6);
+  const bool diagnosing = diagEverySeen || diagFile || diagCount > 1;
+  if (diagnosing && (diagEvery <= 0 || !diagFile)) {
+    fprintf(stderr, "--diagnostics-every K (> 0) and --diagnostics-out FILE.csv go together (--diagnostics-region needs both)\n");
+    return 2;
+  }
+  if (diagCount > SPH_DIAG_MAX_REGIONS) {
+    fprintf(stderr, "at most %d --diagnostics-region (the whole scene is always region 0)\n", SPH_DIAG_MAX_REGIONS - 1);
+    return 2;
+  }
+  for (float b : diagRegions)
+    if (std::isnan(b)) { fprintf(stderr, "--diagnostics-region: a bound is not a number\n"); return 2; }
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -167,6 +189,15 @@ int main(int argc, char** argv) {
     std::vector<float> gradients(sampleGradients ? (size_t)sampleDims[0] * sampleDims[1] * sampleDims[2] * SPH_GRADIENT_WORDS : 0);
     std::vector<float> meshVerts, meshNormals;
     std::vector<int32_t> meshTris;
+    std::vector<double> diagRecords((size_t)diagCount * SPH_DIAG_WORDS);
+    FILE* diagCsv = nullptr;
+    if (diagnosing) {
+      diagCsv = fopen(diagFile, "w");
+      if (!diagCsv) throw std::runtime_error(std::string("cannot write ") + diagFile);
+      fputs("step,region,n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
+            "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
+            "reserved31\n", diagCsv);
+    }
     Watch helper; helper.quiet = quiet;
     double total = 0;
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
@@ -240,6 +271,22 @@ int main(int argc, char** argv) {
                   surfNormals ? &meshNormals : nullptr);
         helper.report("_extractSurface: \t%9.3f ms\n");
       }
+      if (diagnosing && (iterationCount + 1) % diagEvery == 0) {
+        ocl_solver->diagnostics(diagRegions.data(), diagCount, (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE), diagRecords.data());
+        for (int r = 0; r < diagCount; r++) {
+          fprintf(diagCsv, "%d,%d", iterationCount + 1, r);
+          for (int w = 0; w < SPH_DIAG_WORDS; w++) fprintf(diagCsv, ",%.17g", diagRecords[(size_t)r * SPH_DIAG_WORDS + w]);
+          fputc('\n', diagCsv);
+        }
+        if (fflush(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
+        if (!quiet) {
+          const double* d = diagRecords.data();  // the whole scene
+          const double n = d[0], inv = n > 0 ? 1.0 / n : 0.0;
+          printf("_diagnostics: n %.0f  Ekin %.6e  max|v| %.6e  rho mean %.4f min %.4f max %.4f  rms(rho-rho0)/rho0 %.3e\n", n,
+                 0.5 * (double)cfg.mass * d[10], std::sqrt(d[20]), d[11] * inv, d[16], d[17], std::sqrt(d[12] * inv) / (double)cfg.rho0);
+        }
+        helper.report("_diagnostics: \t\t%9.3f ms\n");
+      }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);
         ocl_solver->updateMuscleActivityData(muscle_activation_signal_cpp.data());
@@ -258,6 +305,7 @@ int main(int argc, char** argv) {
       if (!f || fwrite(position_cpp.data(), sizeof(float), position_cpp.size(), f) != position_cpp.size()) throw std::runtime_error("cannot write --out file");
       fclose(f);
     }
+    if (diagCsv && fclose(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
     delete ocl_solver;
   } catch (std::exception& e) {  // owPhysicsFluidSimulator.cpp:73-76,144-148
     std::cout << "ERROR: " << e.what() << std::endl;

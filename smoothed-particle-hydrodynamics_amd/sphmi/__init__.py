@@ -17,6 +17,10 @@ HOST_LIB_PATH = os.path.join(_PKG, "libsphmi_host.so")
 ABI_VERSION = 2
 SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
 SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
+DIAG_WORDS = 32  # sph_diagnostics record (frames.DIAG_FIELDS)
+DIAG_MAX_REGIONS = 16
+HIST_MAX_BINS = 4096
+HIST_FIELDS = ("density", "speed", "pressure", "neighbors", "x", "y", "z")  # sph_histogram field numbers 0..6
 GRADIENT_WORDS = 32  # sph_sample_gradient_* record: the sample record, then gradients, vorticity, divergence, Q (frames.GRADIENT_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
@@ -103,7 +107,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
-                    "sph_sample_gradient_grid", "sph_surface_normals"] + _STAGE_FUNCS
+                    "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -188,6 +192,8 @@ def device_lib():
         L.sph_sample_gradient_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_sample_gradient_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.sph_surface_normals.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        L.sph_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p]
         _dev = L
     return _dev
 
@@ -565,6 +571,42 @@ class owHIPSolver:
         n = getattr(self, "_mesh_vertices", 0)  # 0 without a mesh: the library reports SPH_ERR_ORDER
         out = np.empty((n, 3), np.float32)
         self._chk(self._L.sph_surface_normals(self._h, _ptr(out) if out.size else None))
+        return out
+
+    # --- flow diagnostics (sph_diagnostics / sph_histogram): the sorted state of the last completed step ---
+    def diagnostics(self, regions=None, types=(1, 2)):
+        """Reductions over the particles of the given types inside each region (x0, y0, z0, x1, y1, z1; lower bounds
+        inclusive, upper exclusive, +-inf allowed; None = one region holding everything): float64[R, 32] records named by
+        frames.DIAG_FIELDS (count, sums of position, velocity, angular momentum, v2, density, squared density error and
+        pressure, then extremes; include/sphmi.h). The sums are added in a fixed tree, so a record depends on the state and
+        its region alone. The default types are the moving matter: a boundary particle's `velocity` holds the wall normal,
+        so sums over type 3 are legal but are not momenta. frames.diagnostics_summary turns a record into physical numbers."""
+        if regions is None:
+            regions = [(-np.inf,) * 3 + (np.inf,) * 3]
+        rg = np.ascontiguousarray(regions, np.float32)
+        if rg.size % 6:
+            raise SphError("diagnostics: regions must be [R, 6]")
+        rg = rg.reshape(-1, 6)
+        out = np.zeros((max(rg.shape[0], 1), DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_diagnostics(self._h, _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
+        return out
+
+    def histogram(self, field, lo, hi, bins, region=None, types=(1, 2)):
+        """Distribution of one per-particle quantity (a name from HIST_FIELDS or 0..6) over the same selection as
+        diagnostics(): uint32[bins + 2] = values below lo, `bins` equal bins of [lo, hi), values at or above hi.
+        histogram("neighbors", 0, 33, 33)[1:-1] is the exact neighbour-count distribution."""
+        if isinstance(field, str):
+            if field not in HIST_FIELDS:
+                raise SphError("histogram: field must be one of %s" % (HIST_FIELDS,))
+            field = HIST_FIELDS.index(field)
+        rg = None
+        if region is not None:
+            rg = np.ascontiguousarray(region, np.float32)
+            if rg.size != 6:
+                raise SphError("histogram: region must be (x0, y0, z0, x1, y1, z1)")
+        out = np.zeros(max(int(bins), 0) + 2, np.uint32)
+        self._chk(self._L.sph_histogram(self._h, int(field), float(np.float32(lo)), float(np.float32(hi)), int(bins), _ptr(rg),
+                                        type_mask(types), _ptr(out)))
         return out
 
     # --- extras ---

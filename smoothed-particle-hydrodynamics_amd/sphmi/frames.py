@@ -17,6 +17,10 @@ the format `sphmi_run --surface-out` writes, with vertex normals (owHIPSolver.su
 Gradient grids (owHIPSolver.sample_gradient_grid, float32[nz, ny, nx, 32] records named by GRADIENT_FIELDS):
 `write_vtk_gradients` writes vorticity, density gradient, divergence and Q as a legacy-VTK volume, and `read_gradients` loads
 the raw files `sphmi_run --sample-gradients` writes.
+
+Diagnostics (owHIPSolver.diagnostics, float64[R, 32] records named by DIAG_FIELDS): `diagnostics_summary` derives mass, centre
+of mass, kinetic energy, density error and the like from one record, `write_diagnostics_csv` / `read_diagnostics_csv` write and
+read the per-step table `sphmi_run --diagnostics-out` writes (every word as %.17g: a round trip keeps every bit).
 """
 import numpy as np
 
@@ -248,3 +252,69 @@ def read_gradients(path, dims):
     [NZ, NY, NX, 32]."""
     nx, ny, nz = (int(v) for v in dims)
     return np.fromfile(path, np.float32).reshape(nz, ny, nx, len(GRADIENT_FIELDS))
+
+
+# ---- flow diagnostics (owHIPSolver.diagnostics; include/sphmi.h, sph_diagnostics) ----
+DIAG_FIELDS = ("n", "sum_x", "sum_y", "sum_z", "sum_vx", "sum_vy", "sum_vz", "sum_lx", "sum_ly", "sum_lz", "sum_v2", "sum_rho",
+               "sum_e2", "sum_p", "reserved14", "reserved15", "min_rho", "max_rho", "min_p", "max_p", "max_v2", "max_v2_index",
+               "max_v2_id", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "reserved29", "reserved30", "reserved31")
+
+
+def diagnostics_summary(record, cfg):
+    """Physical numbers (Python floats, computed in double) from one 32-word diagnostics record: mass = n * cfg.mass, centre of
+    mass and mean velocity (scene units, as positions and velocities are stored), kinetic energy 0.5 * mass-per-particle * sum v2,
+    linear and angular momentum, max speed, mean / min / max density, rms and max relative density error against cfg.rho0, mean
+    pressure and the bounding box. With n = 0 the means are 0."""
+    r = np.asarray(record, np.float64).reshape(-1)
+    if r.size != len(DIAG_FIELDS):
+        raise ValueError("diagnostics_summary: a record has %d words" % len(DIAG_FIELDS))
+    n = float(r[0])
+    m = float(cfg.mass)
+    rho0 = float(cfg.rho0)
+    def mean(x):
+        return float(x) / n if n > 0 else 0.0
+    return dict(
+        n=int(n), mass=n * m,
+        centre_of_mass=tuple(mean(x) for x in r[1:4]),
+        mean_velocity=tuple(mean(x) for x in r[4:7]),
+        momentum=tuple(m * float(x) for x in r[4:7]),
+        angular_momentum=tuple(m * float(x) for x in r[7:10]),
+        kinetic_energy=0.5 * m * float(r[10]),
+        max_speed=float(np.sqrt(r[20])), max_speed_index=int(r[21]), max_speed_id=int(r[22]),
+        mean_density=mean(r[11]), min_density=float(r[16]), max_density=float(r[17]),
+        rms_density_error=float(np.sqrt(mean(r[12]))) / rho0,
+        max_density_error=(max(abs(float(r[16]) - rho0), abs(float(r[17]) - rho0)) / rho0) if n > 0 else 0.0,
+        mean_pressure=mean(r[13]), min_pressure=float(r[18]), max_pressure=float(r[19]),
+        bbox_min=tuple(float(x) for x in r[23:26]), bbox_max=tuple(float(x) for x in r[26:29]))
+
+
+def write_diagnostics_csv(path, steps, records):
+    """One row per step and region: `step,region,` then the 32 record words as %.17g, under a header naming them. `steps`: S step
+    numbers; `records`: float64[S, R, 32] (or [S, 32] for one region)."""
+    rec = np.asarray(records, np.float64)
+    if rec.ndim == 2:
+        rec = rec[:, None, :]
+    if rec.ndim != 3 or rec.shape[2] != len(DIAG_FIELDS) or rec.shape[0] != len(steps):
+        raise ValueError("write_diagnostics_csv: records must be [len(steps), R, %d]" % len(DIAG_FIELDS))
+    with open(path, "w") as f:
+        f.write("step,region," + ",".join(DIAG_FIELDS) + "\n")
+        for s, block in zip(steps, rec):
+            for r, row in enumerate(block):
+                f.write("%d,%d," % (int(s), r) + ",".join("%.17g" % float(x) for x in row) + "\n")
+
+
+def read_diagnostics_csv(path):
+    """(steps int64[S], records float64[S, R, 32]) of a file written by write_diagnostics_csv or `sphmi_run --diagnostics-out`."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        if header != ["step", "region"] + list(DIAG_FIELDS):
+            raise ValueError("%s: not a diagnostics table" % path)
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    if not rows:
+        return np.zeros(0, np.int64), np.zeros((0, 0, len(DIAG_FIELDS)), np.float64)
+    steps, regions = [int(r[0]) for r in rows], [int(r[1]) for r in rows]
+    R = max(regions) + 1
+    if len(rows) % R or regions != list(range(R)) * (len(rows) // R):
+        raise ValueError("%s: rows are not grouped as one block of regions per step" % path)
+    rec = np.array([[float(x) for x in r[2:]] for r in rows], np.float64).reshape(-1, R, len(DIAG_FIELDS))
+    return np.array(steps[::R], np.int64), rec
