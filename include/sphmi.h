@@ -287,6 +287,49 @@ int sph_diagnostics(sph_solver* s, const float* regions6 /* host, count x (x0,y0
 int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6 /* host or NULL */,
                   uint32_t typeMask, uint32_t* out /* host, bins + 2: below, bin 0 .. bins-1, at-or-above */);
 
+/* ---- Connected components (the pieces the matter is in: droplets, fragments, bodies; no reference counterpart) ---------------
+ * State: the sorted state of the last completed step, as sampling and diagnostics (one integration step behind
+ * sph_read_position), and that step's neighbour rows: row(i) = the ids >= 0 that sph_read_neighbor_rows returns for sorted
+ * particle i.
+ * Nodes: sorted particle j is SELECTED exactly as for sph_diagnostics with the region "everything": type t = (int)position.w in
+ * 1..3 with (1 << t) & typeMask, and its cell key < gridCellCount.
+ * Edges: {i, j}, i != j, both selected, j in row(i) OR i in row(j) (a row holds at most 32 entries, chosen through a per-particle
+ * threshold radius, so the rows are not symmetric; the graph is their symmetric closure), and r2 < link2, where d = x_i - x_j per
+ * coordinate in float, r2 = dx*dx + dy*dy + dz*dz (float, that order, no contraction, scene units: the sampling contract's
+ * expression) and link2 = linkRadius * linkRadius as one float. Float negation is exact, so r2 is the same from either end.
+ * linkRadius = +infinity keeps every row entry ("the pairs that exchanged forces in this step") and reads no neighbour position.
+ * Two particles within h that are absent from each other's capped rows are linked only through third particles.
+ * Components: the connected components of that graph; an isolated selected particle is a component of one. A component's ROOT
+ * is its lowest sorted index. Components are numbered 0 .. C-1 in ascending order of their roots. labels[j] is j's component
+ * number, or -1 if j is not selected. The result is integers and float minima / maxima only and does not depend on the order of
+ * execution: it is a function of the state and the arguments.
+ * Table, one row per component: root, n (members), and the bounding box min x, y, z, max x, y, z of the members' sorted
+ * positions (float compares, canonicalised by + 0.0f as the diagnostics' extremes).
+ * sph_component_diagnostics: record r is the sph_diagnostics record, word for word (same per-particle float terms, same widening,
+ * the same fixed tree over all N terms in ascending sorted index with non-members contributing +0.0, same rules for the extremes,
+ * the same "lowest sorted index that attains max v2" and its original id), where "selected" means labels[j] == components[r].
+ * Ids may repeat; a record does not depend on the other ids of the call. Hence word 0 equals the table's n, words 23..28 equal
+ * the table's bounding box, and when a labelling has a single component its record equals sph_diagnostics(everything, typeMask)
+ * bit for bit.
+ * Lifetime: the labelling lives in device memory owned by the solver until the next sph_label_components or sph_destroy;
+ * sph_read_components keeps working after further steps. sph_component_diagnostics reads the live state, so it returns
+ * SPH_ERR_ORDER once any stage, step or slab call has run since the labelling. The three calls are read-only on every solver
+ * array (a mesh stays valid for sph_surface_normals; a labelling stays valid across sph_diagnostics, sampling and extraction
+ * calls), blocking, on the solver's stream, and not stages (no stage timing).
+ * Errors: SPH_ERR_ORDER before a step's neighbour, density and pressure-force stages have run, and for the two readers before
+ * any successful labelling; SPH_ERR_INVALID for a slab solver, a typeMask of 0 or with bits outside 1..3, a linkRadius that is NaN
+ * or <= 0, null counts / components / out, count outside 1..SPH_DIAG_MAX_REGIONS, a component id outside 0..C-1. A failed
+ * sph_label_components leaves no labelling behind. Zero selected particles is legal: counts = {0, 0}, all labels -1. A pointer
+ * walk that exceeds its bound of N steps (never, unless memory is corrupted) is reported as SPH_ERR_HIP rather than followed.
+ * Device memory: 8 bytes per particle (the union-find parents and the labels), 32 bytes per component for the table, 12 bytes
+ * per 256 particles for the scan; grown on demand and freed by sph_destroy. */
+int sph_label_components(sph_solver* s, float linkRadius, uint32_t typeMask, int64_t counts[2] /* selected particles, components */);
+/* Any pointer may be NULL. */
+int sph_read_components(sph_solver* s, int32_t* labels /* host, N, sorted order */, int32_t* rootCount /* host, C x (root, n) */,
+                        float* bbox /* host, C x 6 */);
+int sph_component_diagnostics(sph_solver* s, const int32_t* components /* host, count ids */, int32_t count,
+                              double* out /* host, count x SPH_DIAG_WORDS */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

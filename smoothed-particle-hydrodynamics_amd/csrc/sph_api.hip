@@ -229,7 +229,7 @@ static void free_all(sph_solver* s) {
   void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
                   d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf, s->diagBuf};
+                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf, s->diagBuf, s->ccBuf, s->ccTable};
   for (void* p : ptrs) if (p) hipFree(p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
@@ -1269,6 +1269,98 @@ extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, i
   rc = sphk_histogram(s, a, (uint32_t*)s->diagBuf);
   if (rc != SPH_OK) return rc;
   rc = d2h(s, out, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
+  return rc != SPH_OK ? rc : check_finite_state(s);
+}
+
+// ---------------------------------------------------------------------------------------------- connected components
+// The pieces the matter is in: components of the graph of the last step's neighbour rows (sph_components.hip). The labelling
+// lives in ccBuf / ccTable until the next one; the per-component records reuse the diagnostics tree with the labels as selection.
+extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t typeMask, int64_t counts[2]) {
+  ENTER(s);
+  s->ccValid = false;  // a failed call leaves no labelling behind
+  s->ccCounts[0] = s->ccCounts[1] = 0;
+  if (counts) counts[0] = counts[1] = 0;
+  if (!counts) { sph_set_error("sph_label_components: null pointer"); return SPH_ERR_INVALID; }
+  if (std::isnan(linkRadius) || !(linkRadius > 0.f)) { sph_set_error("sph_label_components: linkRadius must be > 0"); return SPH_ERR_INVALID; }
+  SampleParams p;
+  int rc = sample_check(s, typeMask, "sph_label_components", &p);
+  if (rc != SPH_OK) return rc;
+  NEED(s, P_FIND, "sph_label_components");
+  const bool finite = !std::isinf(linkRadius);
+  volatile float link2 = linkRadius * linkRadius;
+  rc = grow_scratch(s, &s->ccBuf, &s->ccBytes, sphk_components_scratch_bytes(s->d.N));
+  if (rc != SPH_OK) return rc;
+  uint32_t* dTotals = nullptr;
+  rc = sphk_components_link(s, typeMask, finite, link2, s->ccBuf, &dTotals);
+  if (rc != SPH_OK) return rc;
+  uint32_t totals[3] = {0, 0, 0};
+  rc = d2h(s, totals, dTotals, sizeof(totals));  // the call's one wait for a result
+  if (rc != SPH_OK) return rc;
+  if (totals[2]) {
+    sph_set_error("sph_label_components: a parent walk or hook retry ran past its bound of N steps (flags 0x%x)", totals[2]);
+    return SPH_ERR_HIP;
+  }
+  const int C = (int)totals[1];
+  rc = grow_scratch(s, &s->ccTable, &s->ccTableBytes, sizeof(int32_t) * 8 * (size_t)std::max(C, 1));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_components_number(s, s->ccBuf, C, (int32_t*)s->ccTable);
+  if (rc != SPH_OK) return rc;
+  rc = check_finite_state(s);  // (synchronises the stream)
+  if (rc != SPH_OK) return rc;
+  s->ccCounts[0] = (int64_t)totals[0];
+  s->ccCounts[1] = (int64_t)C;
+  s->ccN = s->d.N;
+  s->ccEpoch = s->stateEpoch;
+  s->ccValid = true;
+  counts[0] = s->ccCounts[0];
+  counts[1] = s->ccCounts[1];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_components(sph_solver* s, int32_t* labels, int32_t* rootCount, float* bbox) {
+  ENTER(s);
+  if (!s->ccValid) { sph_set_error("sph_read_components: no labelling has been made"); return SPH_ERR_ORDER; }
+  int rc = SPH_OK;
+  if (labels && s->ccN > 0) rc = d2h(s, labels, sphk_components_labels(s->ccBuf, s->ccN), sizeof(int32_t) * (size_t)s->ccN);
+  if (rc != SPH_OK) return rc;
+  const size_t C = (size_t)s->ccCounts[1];
+  if ((rootCount || bbox) && C > 0) {
+    std::vector<int32_t> rows(C * 8);
+    rc = d2h(s, rows.data(), s->ccTable, sizeof(int32_t) * 8 * C);
+    if (rc != SPH_OK) return rc;
+    for (size_t c = 0; c < C; c++) {
+      if (rootCount) { rootCount[2 * c] = rows[8 * c]; rootCount[2 * c + 1] = rows[8 * c + 1]; }
+      if (bbox) memcpy(bbox + 6 * c, &rows[8 * c + 2], sizeof(float) * 6);
+    }
+  }
+  return SPH_OK;
+}
+
+extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* components, int32_t count, double* out) {
+  ENTER(s);
+  if (!components || !out) { sph_set_error("sph_component_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_component_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  if (!s->ccValid) { sph_set_error("sph_component_diagnostics: no labelling has been made"); return SPH_ERR_ORDER; }
+  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
+    sph_set_error("sph_component_diagnostics: the solver's state has changed since the labelling");
+    return SPH_ERR_ORDER;
+  }
+  DiagArgs a = {};
+  for (int r = 0; r < count; r++) {
+    if (components[r] < 0 || (int64_t)components[r] >= s->ccCounts[1]) {
+      sph_set_error("sph_component_diagnostics: component %d is not in 0..%lld", components[r], (long long)s->ccCounts[1] - 1);
+      return SPH_ERR_INVALID;
+    }
+    a.comp[r] = components[r];
+  }
+  a.count = count; a.typeMask = 0xEu; a.rho0 = s->d.rho0;
+  a.labels = sphk_components_labels(s->ccBuf, s->ccN);
+  int rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, count));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_diagnostics(s, a, (double*)s->diagBuf, &records);
+  if (rc != SPH_OK) return rc;
+  rc = d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)count);
   return rc != SPH_OK ? rc : check_finite_state(s);
 }
 

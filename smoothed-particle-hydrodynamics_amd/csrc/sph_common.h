@@ -136,6 +136,12 @@ struct sph_solver {
   // bumped by every call that rewrites the sorted state sampling reads (stages, steps, slab calls): sph_surface_normals is
   // only allowed while it still equals meshEpoch
   uint64_t stateEpoch;
+  // connected components (sph_label_components / sph_read_components): the labelling's scratch and table, grown on demand
+  void* ccBuf; size_t ccBytes;
+  void* ccTable; size_t ccTableBytes;
+  int64_t ccCounts[2]; bool ccValid;  // selected particles, components of the last successful labelling
+  int ccN;                            // ... the particle count it was made for
+  uint64_t ccEpoch;                   // ... and stateEpoch at that time (sph_component_diagnostics)
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -262,6 +268,9 @@ struct DiagArgs {
   int count;
   uint32_t typeMask;
   float rho0;
+  // component mode (sph_component_diagnostics): record r selects the particles with labels[j] == comp[r] instead of the box test
+  const int32_t* labels;  // nullptr: box mode
+  int32_t comp[SPH_DIAG_MAX_REGIONS];
 };
 struct HistArgs {
   float box[6];
@@ -272,6 +281,13 @@ struct HistArgs {
 size_t sphk_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_DIAG_WORDS records
 int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records);  // *records: where the records land
 int sphk_histogram(sph_solver* s, const HistArgs& a, uint32_t* out);  // out: bins + 2 device words
+// sph_components.hip (connected components of the neighbour graph; read-only on every solver array)
+size_t sphk_components_scratch_bytes(int N);             // parent and labels (4 B per particle each), the scan's block totals
+int32_t* sphk_components_labels(void* scratch, int N);   // where the N labels lie in that scratch
+// init, hook, flatten, count: *totals = 3 device words {selected particles, components, error flags of the bounded walks}
+int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float link2, void* scratch, uint32_t** totals);
+// after sphk_components_link on the same scratch: labels, and the table of C rows of 8 words (root, n, bbox as floats)
+int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

@@ -35,6 +35,9 @@ __device__ static const int kDiagMaxWord[5] = {17, 19, 26, 27, 28};
 // ---- level 0: particles -> one partial per chunk, word and region ---------------------------------------------------------
 // Every array is read once, whatever the number of regions: the per-particle terms stay in registers and the region loop only
 // selects among them.
+// COMP: the selection of record r is labels[j] == comp[r] (sph_component_diagnostics) instead of type, key and box; everything
+// after the selection is the same code.
+template <bool COMP>
 __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, double* __restrict__ part, int chunks) {
   __shared__ double sh[DIAG_SUMS][SPH_BLOCK];
   __shared__ float shx[4][10];
@@ -43,10 +46,12 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
   const int t = threadIdx.x, chunk = blockIdx.x, lane = t & 63, wave = t >> 6;
   float f[4][13];  // x y z, vx vy vz, Lx Ly Lz, v2, rho, e2, p: record words 1..13
   bool ok[4];
+  int lab[4];
 #pragma unroll
   for (int e = 0; e < 4; e++) {
     const int j = chunk * DIAG_CHUNK + e * SPH_BLOCK + t;
     ok[e] = false;
+    lab[e] = -1;
 #pragma unroll
     for (int w = 0; w < 13; w++) f[e][w] = 0.f;
     if (j < d.N) {
@@ -56,7 +61,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
       const float pr = d.rp[j].y;
       const uint32_t key = d.keys[j];
       const int type = (int)p.w;
-      ok[e] = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && key < (uint32_t)d.G;
+      if (COMP) { lab[e] = a.labels[j]; ok[e] = lab[e] >= 0; }
+      else ok[e] = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && key < (uint32_t)d.G;
       f[e][0] = p.x; f[e][1] = p.y; f[e][2] = p.z;
       f[e][3] = v.x; f[e][4] = v.y; f[e][5] = v.z;
       f[e][6] = p.y * v.z - p.z * v.y;
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
     bool sel[4];
 #pragma unroll
     for (int e = 0; e < 4; e++)
-      sel[e] = ok[e] && x0 <= f[e][0] && f[e][0] < x1 && y0 <= f[e][1] && f[e][1] < y1 && z0 <= f[e][2] && f[e][2] < z1;
+      sel[e] = COMP ? (ok[e] && lab[e] == a.comp[r]) : ok[e] && x0 <= f[e][0] && f[e][0] < x1 && y0 <= f[e][1] && f[e][1] < y1 && z0 <= f[e][2] && f[e][2] < z1;
     // No particle of this chunk in the region (the sorted order is spatial, so that is the common case for a small region): every
     // sum of +0.0 terms is +0.0 and every extreme keeps its identity, which is what the tree below would produce.
     if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
@@ -259,7 +265,8 @@ int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double**
   int n = s->d.N;
   int chunks = n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1;
   double* cur = scratch;
-  hipLaunchKernelGGL(k_diag_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
+  if (a.labels) hipLaunchKernelGGL(k_diag_leaf<true>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
+  else hipLaunchKernelGGL(k_diag_leaf<false>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
   SPH_HIP(hipGetLastError());
   while (chunks > 1) {
     const int nOut = (chunks + DIAG_CHUNK - 1) / DIAG_CHUNK;

@@ -97,6 +97,18 @@ class owHIPSolver {
   void histogram(int field, float lo, float hi, int bins, const float* region6, unsigned int typeMask, uint32_t* out) {
     check(sph_histogram(s_, field, lo, hi, bins, region6, typeMask, out), "histogram");
   }
+  // beyond the reference: the connected components of the particles of `typeMask` in the graph of the last step's neighbour rows
+  // (pairs closer than linkRadius; INFINITY = every row entry): counts = {selected particles, components}; components() copies
+  // the labels (particleCount ints in sorted order, -1 = not selected) and the table (C x (root, n), C x 6 bbox floats; any
+  // pointer may be null); componentDiagnostics gives the diagnostics() record of each of `count` (1..16) component ids
+  // (include/sphmi.h, sph_label_components / sph_read_components / sph_component_diagnostics)
+  void labelComponents(float linkRadius, unsigned int typeMask, int64_t counts[2]) {
+    check(sph_label_components(s_, linkRadius, typeMask, counts), "labelComponents");
+  }
+  void components(int32_t* labels, int32_t* rootCount, float* bbox) { check(sph_read_components(s_, labels, rootCount, bbox), "components"); }
+  void componentDiagnostics(const int32_t* ids, int count, double* out) {
+    check(sph_component_diagnostics(s_, ids, count, out), "componentDiagnostics");
+  }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

@@ -20,6 +20,13 @@
 //        after every K-th step, sph_diagnostics of the liquid and elastic particles over the whole scene (region 0) and up to 15
 //        further regions ("inf" / "-inf" are accepted as bounds): one CSV row per report and region (step, region, the 32 record
 //        words as %.17g; sphmi.frames.read_diagnostics_csv) and, unless --quiet, one summary line per report
+//   ... --components-every K --components-out FILE.csv [--components-link R] [--components-types T...] [--components-top M]
+//        after every K-th step, label the connected components (sph_label_components) of the particles of the given types
+//        (1 liquid, 2 elastic, 3 boundary; default 1 2) with link radius R (scene units; default inf = every neighbour-row entry)
+//        and write one CSV row per report and component for the M largest components (default 16, at most 16), ordered by
+//        descending n, then ascending root: step, component id, root, n, bounding box (%.9g) and the 32 words of its
+//        sph_component_diagnostics record (%.17g; sphmi.frames.read_components_csv); unless --quiet, one summary line per report
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -84,8 +91,22 @@ int main(int argc, char** argv) {
   bool sampleGradients = false, surfNormals = false;
   int diagEvery = 0; bool diagEverySeen = false; const char* diagFile = nullptr;
   std::vector<float> diagRegions = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};  // region 0: everything
+  int compEvery = 0, compTop = SPH_DIAG_MAX_REGIONS; bool compSeen = false, compTypesSeen = false; const char* compFile = nullptr;
+  float compLink = INFINITY; unsigned compMask = 0;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
+    else if (!strcmp(argv[i], "--components-every") && i + 1 < argc) { compEvery = atoi(argv[++i]); compSeen = true; }
+    else if (!strcmp(argv[i], "--components-out") && i + 1 < argc) { compFile = argv[++i]; compSeen = true; }
+    else if (!strcmp(argv[i], "--components-link") && i + 1 < argc) { compLink = (float)atof(argv[++i]); compSeen = true; }
+    else if (!strcmp(argv[i], "--components-top") && i + 1 < argc) { compTop = atoi(argv[++i]); compSeen = true; }
+    else if (!strcmp(argv[i], "--components-types")) {
+      compSeen = compTypesSeen = true;
+      while (i + 1 < argc && argv[i + 1][0] != '-') {
+        const int t = atoi(argv[++i]);
+        if (t < 1 || t > 3) { fprintf(stderr, "--components-types: a type is 1 (liquid), 2 (elastic) or 3 (boundary)\n"); return 2; }
+        compMask |= 1u << t;
+      }
+    }
     else if (!strcmp(argv[i], "--velocity") && i + 1 < argc) velFile = argv[++i];
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) outFile = argv[++i];
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) steps = atoi(argv[++i]);
@@ -135,6 +156,15 @@ int main(int argc, char** argv) {
   }
   for (float b : diagRegions)
     if (std::isnan(b)) { fprintf(stderr, "--diagnostics-region: a bound is not a number\n"); return 2; }
+  if (compSeen && (compEvery <= 0 || !compFile)) {
+    fprintf(stderr, "--components-every K (> 0) and --components-out FILE.csv go together (the other --components options need both)\n");
+    return 2;
+  }
+  if (compTypesSeen && !compMask) { fprintf(stderr, "--components-types needs at least one type\n"); return 2; }
+  if (!compMask) compMask = (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE);
+  if (std::isnan(compLink) || !(compLink > 0.f)) { fprintf(stderr, "--components-link R: R must be > 0\n"); return 2; }
+  if (compTop < 1 || compTop > SPH_DIAG_MAX_REGIONS) { fprintf(stderr, "--components-top M: M must be in 1..%d\n", SPH_DIAG_MAX_REGIONS); return 2; }
+  const bool labelling = compSeen;
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -197,6 +227,18 @@ int main(int argc, char** argv) {
       fputs("step,region,n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
             "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
             "reserved31\n", diagCsv);
+    }
+    FILE* compCsv = nullptr;
+    std::vector<int32_t> compRootCount, compIds;
+    std::vector<float> compBbox;
+    std::vector<double> compRecords;
+    if (labelling) {
+      compCsv = fopen(compFile, "w");
+      if (!compCsv) throw std::runtime_error(std::string("cannot write ") + compFile);
+      fputs("step,component,root,n,min_x,min_y,min_z,max_x,max_y,max_z,"
+            "n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
+            "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
+            "reserved31\n", compCsv);
     }
     Watch helper; helper.quiet = quiet;
     double total = 0;
@@ -287,6 +329,38 @@ int main(int argc, char** argv) {
         }
         helper.report("_diagnostics: \t\t%9.3f ms\n");
       }
+      if (labelling && (iterationCount + 1) % compEvery == 0) {
+        int64_t counts[2];
+        ocl_solver->labelComponents(compLink, compMask, counts);
+        const size_t C = (size_t)counts[1];
+        compRootCount.resize(2 * C);
+        compBbox.resize(6 * C);
+        ocl_solver->components(nullptr, compRootCount.data(), compBbox.data());
+        compIds.resize(C);
+        for (size_t c = 0; c < C; c++) compIds[c] = (int32_t)c;
+        const size_t top = std::min(C, (size_t)compTop);
+        // descending n, then ascending root (= ascending id)
+        std::partial_sort(compIds.begin(), compIds.begin() + top, compIds.end(), [&](int32_t a, int32_t b) {
+          const int32_t na = compRootCount[2 * (size_t)a + 1], nb = compRootCount[2 * (size_t)b + 1];
+          return na != nb ? na > nb : a < b;
+        });
+        compRecords.assign(top * SPH_DIAG_WORDS, 0.0);
+        if (top) ocl_solver->componentDiagnostics(compIds.data(), (int)top, compRecords.data());
+        for (size_t r = 0; r < top; r++) {
+          const size_t c = (size_t)compIds[r];
+          fprintf(compCsv, "%d,%d,%d,%d", iterationCount + 1, compIds[r], compRootCount[2 * c], compRootCount[2 * c + 1]);
+          for (int k = 0; k < 6; k++) fprintf(compCsv, ",%.9g", compBbox[6 * c + k]);
+          for (int w = 0; w < SPH_DIAG_WORDS; w++) fprintf(compCsv, ",%.17g", compRecords[r * SPH_DIAG_WORDS + w]);
+          fputc('\n', compCsv);
+        }
+        if (fflush(compCsv) != 0) throw std::runtime_error(std::string("cannot write ") + compFile);
+        if (!quiet) {
+          const long long largest = top ? compRootCount[2 * (size_t)compIds[0] + 1] : 0;
+          printf("_components: selected %lld  components %lld  largest %lld  outside it %lld\n", (long long)counts[0], (long long)counts[1],
+                 largest, (long long)counts[0] - largest);
+        }
+        helper.report("_components: \t\t%9.3f ms\n");
+      }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);
         ocl_solver->updateMuscleActivityData(muscle_activation_signal_cpp.data());
@@ -306,6 +380,7 @@ int main(int argc, char** argv) {
       fclose(f);
     }
     if (diagCsv && fclose(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
+    if (compCsv && fclose(compCsv) != 0) throw std::runtime_error(std::string("cannot write ") + compFile);
     delete ocl_solver;
   } catch (std::exception& e) {  // owPhysicsFluidSimulator.cpp:73-76,144-148
     std::cout << "ERROR: " << e.what() << std::endl;

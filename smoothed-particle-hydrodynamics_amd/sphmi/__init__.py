@@ -107,7 +107,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
-                    "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram"] + _STAGE_FUNCS
+                    "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
+                    "sph_read_components", "sph_component_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -194,6 +195,9 @@ def device_lib():
         L.sph_surface_normals.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sph_label_components.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
+        L.sph_read_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_component_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         _dev = L
     return _dev
 
@@ -608,6 +612,37 @@ class owHIPSolver:
         self._chk(self._L.sph_histogram(self._h, int(field), float(np.float32(lo)), float(np.float32(hi)), int(bins), _ptr(rg),
                                         type_mask(types), _ptr(out)))
         return out
+
+    # --- connected components (sph_label_components / sph_read_components / sph_component_diagnostics) ---
+    def label_components(self, link_radius=np.inf, types=(1, 2)):
+        """Label the connected components of the graph of the last step's neighbour rows over the particles of the given types:
+        two selected particles are linked when either has the other in its row and (for a finite `link_radius`, scene units)
+        they are closer than it. Returns (n_selected, n_components); the labelling stays on the device until the next call
+        (components(), component_diagnostics()). Components are numbered by ascending lowest sorted index (include/sphmi.h)."""
+        counts = np.zeros(2, np.int64)
+        self._components = 0  # (a failed labelling leaves none behind)
+        self._chk(self._L.sph_label_components(self._h, float(np.float32(link_radius)), type_mask(types), _ptr(counts)))
+        self._components = int(counts[1])
+        return int(counts[0]), int(counts[1])
+
+    def components(self):
+        """The last labelling: labels int32[N] in sorted order (-1 = not selected), root_count int32[C, 2] (lowest sorted
+        index, members), bbox float32[C, 6] (min x, y, z, max x, y, z). frames.labels_in_original_order maps the labels to
+        the original particle order."""
+        c = getattr(self, "_components", 0)  # 0 without a labelling: the library reports SPH_ERR_ORDER
+        labels = np.empty(self.N, np.int32)
+        rc = np.empty((c, 2), np.int32)
+        bb = np.empty((c, 6), np.float32)
+        self._chk(self._L.sph_read_components(self._h, _ptr(labels), _ptr(rc) if c else None, _ptr(bb) if c else None))
+        return labels, rc, bb
+
+    def component_diagnostics(self, ids):
+        """float64[R, 32]: the diagnostics() record of the particles of each listed component (1..16 ids of the last labelling;
+        ids may repeat). Refused once the solver has stepped since the labelling."""
+        comp = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.zeros((max(comp.size, 1), DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_component_diagnostics(self._h, _ptr(comp) if comp.size else None, comp.size, _ptr(out)))
+        return out[:comp.size]
 
     # --- extras ---
     def step(self, iterationCount=0):

@@ -21,6 +21,11 @@ the raw files `sphmi_run --sample-gradients` writes.
 Diagnostics (owHIPSolver.diagnostics, float64[R, 32] records named by DIAG_FIELDS): `diagnostics_summary` derives mass, centre
 of mass, kinetic energy, density error and the like from one record, `write_diagnostics_csv` / `read_diagnostics_csv` write and
 read the per-step table `sphmi_run --diagnostics-out` writes (every word as %.17g: a round trip keeps every bit).
+
+Connected components (owHIPSolver.label_components / components / component_diagnostics): `component_summary` turns the table
+into sizes and masses, `labels_in_original_order` maps the sorted-order labels to the particles' original order so that
+`write_vtk` / `write_npz` can store a label beside each particle (`labels=`), and `write_components_csv` /
+`read_components_csv` write and read the table `sphmi_run --components-out` writes.
 """
 import numpy as np
 
@@ -59,18 +64,25 @@ def density_colour(rho, rho0):
     return rgb  # like glColor4f, components outside [0,1] are left to the consumer to clamp
 
 
-def write_npz(path, position, density, step=None):
+def write_npz(path, position, density, step=None, labels=None):
+    """`labels`: optional component label per particle in orig order (labels_in_original_order), stored as int32 `component`."""
+    extra = {} if labels is None else {"component": np.asarray(labels, np.int32)}
     np.savez_compressed(path, position=np.asarray(position, np.float32), density=np.asarray(density, np.float32),
-                        step=np.int64(-1 if step is None else step))
+                        step=np.int64(-1 if step is None else step), **extra)
 
 
-def write_vtk(path, position, density, include_boundary=False):
-    """Legacy-VTK polydata (binary, big-endian): points + `density` and `type` point scalars."""
+def write_vtk(path, position, density, include_boundary=False, labels=None):
+    """Legacy-VTK polydata (binary, big-endian): points + `density` and `type` point scalars, and `component` (int) when
+    `labels` (one per particle, orig order: labels_in_original_order) is given."""
     pos = np.asarray(position, np.float32).reshape(-1, 4)
     rho = np.asarray(density, np.float32)
+    lab = None if labels is None else np.asarray(labels, np.int32).reshape(-1)
+    if lab is not None and lab.shape[0] != pos.shape[0]:
+        raise ValueError("labels must hold one entry per particle")
     if not include_boundary:
         keep = pos[:, 3].astype(np.int32) != 3  # BOUNDARY_PARTICLE (owOpenCLConstant.h:12)
         pos, rho = pos[keep], rho[keep]
+        lab = None if lab is None else lab[keep]
     n = pos.shape[0]
     with open(path, "wb") as f:
         f.write(b"# vtk DataFile Version 3.0\nsphmi frame\nBINARY\nDATASET POLYDATA\n")
@@ -86,6 +98,10 @@ def write_vtk(path, position, density, include_boundary=False):
         f.write(b"\nSCALARS type float 1\nLOOKUP_TABLE default\n")
         f.write(pos[:, 3].astype(">f4").tobytes())
         f.write(b"\n")
+        if lab is not None:
+            f.write(b"SCALARS component int 1\nLOOKUP_TABLE default\n")
+            f.write(lab.astype(">i4").tobytes())
+            f.write(b"\n")
     return n
 
 
@@ -318,3 +334,68 @@ def read_diagnostics_csv(path):
         raise ValueError("%s: rows are not grouped as one block of regions per step" % path)
     rec = np.array([[float(x) for x in r[2:]] for r in rows], np.float64).reshape(-1, R, len(DIAG_FIELDS))
     return np.array(steps[::R], np.int64), rec
+
+
+# ---- connected components (owHIPSolver.label_components / components / component_diagnostics; include/sphmi.h) ----
+COMPONENT_FIELDS = ("root", "n", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z")
+
+
+def component_summary(root_count, bbox, mass):
+    """Sizes of a labelling from its table: number of components, the largest one (lowest id among equals) and its size, the
+    component ids by descending size (then ascending id), the sizes in that order, the particles outside the largest one and
+    the mass per component id (n * mass, float64)."""
+    rc = np.asarray(root_count, np.int64).reshape(-1, 2)
+    bb = np.asarray(bbox, np.float32).reshape(-1, 6)
+    if bb.shape[0] != rc.shape[0]:
+        raise ValueError("component_summary: root_count and bbox must have one row per component")
+    n = rc[:, 1]
+    order = np.lexsort((np.arange(n.size), -n))
+    largest = int(order[0]) if n.size else -1
+    return dict(components=int(n.size), largest=largest, largest_n=int(n[largest]) if n.size else 0, order=order,
+                sizes=n[order], outside_largest=int(n.sum() - (n[largest] if n.size else 0)), mass=n.astype(np.float64) * float(mass),
+                largest_bbox=tuple(float(x) for x in bb[largest]) if n.size else None)
+
+
+def labels_in_original_order(labels, particle_index):
+    """Component label per particle in ORIG order from the sorted-order labels and the (cell, orig id) pairs of
+    read_particleIndex_buffer taken in the same step: out[orig id] = labels[sorted position] (invert_particle_index)."""
+    lab = np.asarray(labels, np.int32).reshape(-1)
+    back = invert_particle_index(particle_index)
+    if back.shape[0] != lab.shape[0]:
+        raise ValueError("labels_in_original_order: one label per particle expected")
+    return lab[back]
+
+
+def write_components_csv(path, steps, ids, root_count, bbox, records):
+    """One row per report and component: `step,component,root,n,` the bounding box as %.9g (float32 round trip) and the 32 words
+    of the component's diagnostics record as %.17g. steps[k] goes with ids[k] (component ids), root_count[k] [R, 2], bbox[k]
+    [R, 6] and records[k] [R, 32]; R may differ from report to report."""
+    with open(path, "w") as f:
+        f.write("step,component," + ",".join(COMPONENT_FIELDS) + "," + ",".join(DIAG_FIELDS) + "\n")
+        for k, step in enumerate(steps):
+            rc = np.asarray(root_count[k], np.int64).reshape(-1, 2)
+            bb = np.asarray(bbox[k], np.float32).reshape(-1, 6)
+            rec = np.asarray(records[k], np.float64).reshape(-1, len(DIAG_FIELDS))
+            cid = np.asarray(ids[k], np.int64).reshape(-1)
+            if not (rc.shape[0] == bb.shape[0] == rec.shape[0] == cid.shape[0]):
+                raise ValueError("write_components_csv: report %d has rows of different lengths" % k)
+            for r in range(cid.shape[0]):
+                f.write("%d,%d,%d,%d," % (int(step), cid[r], rc[r, 0], rc[r, 1]) + ",".join("%.9g" % float(x) for x in bb[r]) + "," +
+                        ",".join("%.17g" % float(x) for x in rec[r]) + "\n")
+
+
+def read_components_csv(path):
+    """The rows of a file written by write_components_csv or `sphmi_run --components-out`, in file order:
+    (steps int64[K], ids int64[K], root_count int32[K, 2], bbox float32[K, 6], records float64[K, 32])."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        if header != ["step", "component"] + list(COMPONENT_FIELDS) + list(DIAG_FIELDS):
+            raise ValueError("%s: not a components table" % path)
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    K = len(rows)
+    steps = np.array([int(r[0]) for r in rows], np.int64)
+    ids = np.array([int(r[1]) for r in rows], np.int64)
+    rc = np.array([[int(r[2]), int(r[3])] for r in rows], np.int32).reshape(K, 2)
+    bb = np.array([[float(x) for x in r[4:10]] for r in rows], np.float64).astype(np.float32).reshape(K, 6)
+    rec = np.array([[float(x) for x in r[10:]] for r in rows], np.float64).reshape(K, len(DIAG_FIELDS))
+    return steps, ids, rc, bb, rec
