@@ -1,5 +1,6 @@
 // C ABI of libsphmi.so (include/sphmi.h): solver lifetime, the 18 stage entry points that mirror
-// owOpenCLSolver::_run* (owOpenCLSolver.cpp:213-687), the fused step, read-back and reference-layout export.
+// owOpenCLSolver::_run* (owOpenCLSolver.cpp:213-687), the fused step, read-back, reference-layout export and the slab
+// protocol. The analysis calls (sampling, surfaces, diagnostics, components) are in sph_api_analysis.hip.
 // There is no CPU path in this library: every entry point needs a HIP device and fails with SPH_ERR_HIP otherwise.
 #include <stdarg.h>
 #include <string.h>
@@ -8,7 +9,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sph_common.h"
+#include "sph_api_internal.h"
 #include "sph_fastmath.h"
 
 #define SPH_STR_(x) #x
@@ -51,20 +52,6 @@ extern "C" const char* sph_build_info(void) {
 #endif
       ;
 }
-
-// stage progress bits for the order contract of simulationStep()
-enum { P_HASH = 1, P_SORT = 2, P_SORTPOST = 4, P_INDEXX = 8, P_INDEXPOST = 16, P_FIND = 32, P_DENSITY = 64, P_FORCES = 128,
-       P_PREDICTPOS = 256, P_PREDICTDENS = 512, P_PRESSUREFORCE = 1024 };
-
-#define NEED(s, bits, what)                                                              \
-  do {                                                                                   \
-    if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; }                  \
-    if (((s)->progress & (bits)) != (bits)) {                                            \
-      sph_set_error("%s called before the stage(s) it depends on (simulationStep order, " \
-                    "owPhysicsFluidSimulator.cpp:88-113)", what);                        \
-      return SPH_ERR_ORDER;                                                              \
-    }                                                                                    \
-  } while (0)
 
 template <typename T>
 static int dev_alloc(T** p, size_t count) {
@@ -186,7 +173,7 @@ extern "C" int sph_set_stage_timing(sph_solver* s, int enable) {
 extern "C" int sph_reset_stage_times(sph_solver* s) {
   if (!s) return SPH_ERR_INVALID;
   int rc = resolve_pending(s);
-  // (every diagnostic counter except dbg[6], the non-finite-coordinate count that check_finite_state reports)
+  // (every diagnostic counter except dbg[6], the non-finite-coordinate count that sph_check_finite_state reports)
   hipMemsetAsync(s->d.dbg, 0, sizeof(uint32_t) * 6, s->stream);
   hipMemsetAsync(s->d.dbg + 7, 0, sizeof(uint32_t) * (SPH_DBG_WORDS - 7), s->stream);
   memset(s->stageMs, 0, sizeof(s->stageMs));
@@ -229,8 +216,9 @@ static void free_all(sph_solver* s) {
   void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
                   d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist, s->sampleBuf, s->surfBuf, s->meshBuf, s->diagBuf, s->ccBuf, s->ccTable};
+                  s->blockHist};
   for (void* p : ptrs) if (p) hipFree(p);
+  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable}) if (b->p) hipFree(b->p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
   s->numHostRegs = 0;
@@ -291,7 +279,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   // search); in wide mode a coordinate outside the box gives a cell id outside [0, gridCellCount), and the radix sort only
   // orders the bits a valid id can have. (Reference mode keeps the reference's behaviour for out-of-box input: ids alias.)
   // Creation is the only way in for such coordinates: integrate clamps every new position into the box (sphFluid.cl:1750-1755,
-  // integrate_particle), and a NaN — which no clamp catches — is counted by the hash kernel (dbg[6], check_finite_state).
+  // integrate_particle), and a NaN — which no clamp catches — is counted by the hash kernel (dbg[6], sph_check_finite_state).
   {
     const bool wide = cfg->cellIdMask == 0xffffffffu;
     for (int i = 0; i < N; i++) {
@@ -442,11 +430,6 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
 }
 
 // ---------------------------------------------------------------------------------------------- stages
-static int slab_finish(sph_solver* s, int32_t counts[4]);
-// (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
-#define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)
-#define ENTER(s) do { ENTER_RAW(s); if ((s)->slabRebuildPending) { const int rcf_ = slab_finish((s), nullptr); if (rcf_ != SPH_OK) return rcf_; } } while (0)
-
 extern "C" int sph_run_clear_buffers(sph_solver* s) {
   ENTER(s);
   s->stateEpoch++;
@@ -682,8 +665,6 @@ extern "C" int sph_update_muscles(sph_solver* s, const float* signal, int n) {
   return SPH_OK;
 }
 
-static int check_finite_state(sph_solver* s);
-
 extern "C" int sph_step_sort_passes(sph_solver* s) {
   ENTER(s);
   bool compact;
@@ -692,11 +673,11 @@ extern "C" int sph_step_sort_passes(sph_solver* s) {
 
 extern "C" int sph_synchronize(sph_solver* s) {
   ENTER(s);
-  return check_finite_state(s);  // (synchronises the stream)
+  return sph_check_finite_state(s);  // (synchronises the stream)
 }
 
 // ---------------------------------------------------------------------------------------------- read-back
-static int d2h(sph_solver* s, void* dst, const void* src, size_t bytes) {
+int sph_d2h(sph_solver* s, void* dst, const void* src, size_t bytes) {
   SPH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream));
   SPH_HIP(hipStreamSynchronize(s->stream));
   return SPH_OK;
@@ -709,7 +690,7 @@ static int report_blown_up(sph_solver* s) {
   sph_set_error("%llu particle coordinate(s) were not finite: the simulation state has blown up", (unsigned long long)s->blownUp);
   return SPH_ERR_INVALID;
 }
-static int check_finite_state(sph_solver* s) {
+int sph_check_finite_state(sph_solver* s) {
   uint32_t bad = 0;
   SPH_HIP(hipMemcpyAsync(&bad, s->d.dbg + 6, sizeof(bad), hipMemcpyDeviceToHost, s->stream));
   SPH_HIP(hipStreamSynchronize(s->stream));
@@ -722,8 +703,8 @@ static int check_finite_state(sph_solver* s) {
 
 extern "C" int sph_read_position(sph_solver* s, float* out) {
   ENTER(s); if (!out) return SPH_ERR_INVALID;
-  const int rc = d2h(s, out, s->d.posOrig, sizeof(float4) * (size_t)s->d.N);
-  return rc != SPH_OK ? rc : check_finite_state(s);
+  const int rc = sph_d2h(s, out, s->d.posOrig, sizeof(float4) * (size_t)s->d.N);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
 }
 // ---- asynchronous read_position_buffer. The reference's step always ends with a blocking 16N-byte read
 // (owPhysicsFluidSimulator.cpp:115; 264 MB at 16.5 M particles: +45 % on the step when it is waited for). posOrig is written by
@@ -817,18 +798,18 @@ int sph_guard_position_write(sph_solver* s) {
 
 extern "C" int sph_read_velocity(sph_solver* s, float* out) {
   ENTER(s); if (!out) return SPH_ERR_INVALID;
-  return d2h(s, out, s->d.velOrig, sizeof(float4) * (size_t)s->d.N);
+  return sph_d2h(s, out, s->d.velOrig, sizeof(float4) * (size_t)s->d.N);
 }
 extern "C" int sph_read_density(sph_solver* s, float* out) {
   ENTER(s); if (!out) return SPH_ERR_INVALID;
-  return d2h(s, out, s->d.rho, sizeof(float) * (size_t)s->d.N);
+  return sph_d2h(s, out, s->d.rho, sizeof(float) * (size_t)s->d.N);
 }
 extern "C" int sph_read_particle_index(sph_solver* s, uint32_t* out) {
   ENTER(s); if (!out) return SPH_ERR_INVALID;
   const size_t n = (size_t)s->d.N;
   std::vector<uint32_t> k(n), v(n);
-  int rc = d2h(s, k.data(), s->d.keys, sizeof(uint32_t) * n);
-  if (rc == SPH_OK) rc = d2h(s, v.data(), s->d.vals, sizeof(uint32_t) * n);
+  int rc = sph_d2h(s, k.data(), s->d.keys, sizeof(uint32_t) * n);
+  if (rc == SPH_OK) rc = sph_d2h(s, v.data(), s->d.vals, sizeof(uint32_t) * n);
   if (rc != SPH_OK) return rc;
   for (size_t i = 0; i < n; i++) { out[2 * i] = k[i]; out[2 * i + 1] = v[i]; }
   return SPH_OK;
@@ -866,25 +847,25 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   char* o = (char*)out;
   switch (which) {
     case B_POS:
-      rc = d2h(s, o, d.posOrig, sizeof(float4) * n);
-      if (rc == SPH_OK) { if (d.membDelta) rc = d2h(s, o + sizeof(float4) * n, d.membDelta, sizeof(float4) * n); else memset(o + sizeof(float4) * n, 0, sizeof(float4) * n); }
+      rc = sph_d2h(s, o, d.posOrig, sizeof(float4) * n);
+      if (rc == SPH_OK) { if (d.membDelta) rc = sph_d2h(s, o + sizeof(float4) * n, d.membDelta, sizeof(float4) * n); else memset(o + sizeof(float4) * n, 0, sizeof(float4) * n); }
       break;
     case B_VEL:
-      rc = d2h(s, o, d.velOrig, sizeof(float4) * n);
+      rc = sph_d2h(s, o, d.velOrig, sizeof(float4) * n);
       memset(o + sizeof(float4) * n, 0, sizeof(float4) * n);  // the scratch half is only ever zeroed (App. B #16)
       break;
     case B_SPOS: {
       std::vector<uint32_t> k(n);
       std::vector<float4> sv(n);
-      rc = d2h(s, o, d.sortedPos, sizeof(float4) * n);
+      rc = sph_d2h(s, o, d.sortedPos, sizeof(float4) * n);
       if (rc == SPH_OK) {  // the predicted half: packed (x, y, z) on the device; .w is dead data in the reference
         std::vector<float> p3(3 * n);
-        rc = d2h(s, p3.data(), d.predPos, sizeof(float) * 3 * n);
+        rc = sph_d2h(s, p3.data(), d.predPos, sizeof(float) * 3 * n);
         float4* half = (float4*)(o + sizeof(float4) * n);
         if (rc == SPH_OK) for (size_t i = 0; i < n; i++) half[i] = make_float4(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], 0.f);
       }
-      if (rc == SPH_OK) rc = d2h(s, k.data(), d.keys, sizeof(uint32_t) * n);
-      if (rc == SPH_OK) rc = d2h(s, sv.data(), d.sortedVel, sizeof(float4) * n);
+      if (rc == SPH_OK) rc = sph_d2h(s, k.data(), d.keys, sizeof(uint32_t) * n);
+      if (rc == SPH_OK) rc = sph_d2h(s, sv.data(), d.sortedVel, sizeof(float4) * n);
       if (rc != SPH_OK) break;
       float4* a = (float4*)o;
       for (size_t i = 0; i < n; i++) {
@@ -896,10 +877,10 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
         a[n + i].w = (type == SPH_BOUNDARY_PARTICLE) ? cellf : cellf + d.posTimeStep * (sv[i].w + d.dt * 0.f);
       }
     } break;
-    case B_SVEL: rc = d2h(s, o, d.sortedVel, sizeof(float4) * n); break;
+    case B_SVEL: rc = sph_d2h(s, o, d.sortedVel, sizeof(float4) * n); break;
     case B_ACC:
-      rc = d2h(s, o, d.acc, sizeof(float4) * n);
-      if (rc == SPH_OK) rc = d2h(s, o + sizeof(float4) * n, d.accP, sizeof(float4) * n);
+      rc = sph_d2h(s, o, d.acc, sizeof(float4) * n);
+      if (rc == SPH_OK) rc = sph_d2h(s, o + sizeof(float4) * n, d.accP, sizeof(float4) * n);
       break;
     case B_NMAP:
     case B_NIDS: {
@@ -908,10 +889,10 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
       std::vector<float> dist(mapN);
       std::vector<uint16_t> n16(mapN);
       std::vector<int32_t> nbase((size_t)numTiles * 64);
-      rc = d2h(s, ids.data(), d.nbrId, sizeof(int32_t) * mapN);
-      if (rc == SPH_OK) rc = d2h(s, n16.data(), d.nbr16, sizeof(uint16_t) * mapN);
-      if (rc == SPH_OK) rc = d2h(s, nbase.data(), d.nbrBase, sizeof(int32_t) * nbase.size());
-      if (rc == SPH_OK) rc = d2h(s, dist.data(), d.nbrDist, sizeof(float) * mapN);
+      rc = sph_d2h(s, ids.data(), d.nbrId, sizeof(int32_t) * mapN);
+      if (rc == SPH_OK) rc = sph_d2h(s, n16.data(), d.nbr16, sizeof(uint16_t) * mapN);
+      if (rc == SPH_OK) rc = sph_d2h(s, nbase.data(), d.nbrBase, sizeof(int32_t) * nbase.size());
+      if (rc == SPH_OK) rc = sph_d2h(s, dist.data(), d.nbrDist, sizeof(float) * mapN);
       if (rc == SPH_OK)  // the ids live in the 16-bit map (sph_common.h); the 32-bit rows only where that could not be written
         for (size_t id = 0; id < n; id++)
           for (int k = 0; k < 32; k++) ids[nbr_index((int)id, k)] = nbr_decode(n16.data(), nbase.data(), ids.data(), (int)id, k);
@@ -924,21 +905,21 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
         }
     } break;
     case B_PI: rc = sph_read_particle_index(s, (uint32_t*)o); break;
-    case B_PIB: rc = d2h(s, o, d.backIndex, sizeof(uint32_t) * n); break;
-    case B_GCI: rc = d2h(s, o, d.cellStartRaw, sizeof(uint32_t) * G1); break;
-    case B_GCIF: rc = d2h(s, o, d.cellStart, sizeof(uint32_t) * G1); break;
+    case B_PIB: rc = sph_d2h(s, o, d.backIndex, sizeof(uint32_t) * n); break;
+    case B_GCI: rc = sph_d2h(s, o, d.cellStartRaw, sizeof(uint32_t) * G1); break;
+    case B_GCIF: rc = sph_d2h(s, o, d.cellStart, sizeof(uint32_t) * G1); break;
     case B_P: {
       std::vector<float2> rp(n);
-      rc = d2h(s, rp.data(), d.rp, sizeof(float2) * n);
+      rc = sph_d2h(s, rp.data(), d.rp, sizeof(float2) * n);
       if (rc == SPH_OK) for (size_t i = 0; i < n; i++) ((float*)o)[i] = rp[i].y;
     } break;
-    case B_TRACE: rc = d2h(s, o, d.valsAlt, sizeof(uint32_t) * n); break;
-    case B_DBG: rc = d2h(s, o, d.dbg, sizeof(uint32_t) * SPH_DBG_WORDS); break;
+    case B_TRACE: rc = sph_d2h(s, o, d.valsAlt, sizeof(uint32_t) * n); break;
+    case B_DBG: rc = sph_d2h(s, o, d.dbg, sizeof(uint32_t) * SPH_DBG_WORDS); break;
     case B_RHO:
-      rc = d2h(s, o, d.rho, sizeof(float) * n);
+      rc = sph_d2h(s, o, d.rho, sizeof(float) * n);
       if (rc == SPH_OK) {
         std::vector<float2> rp(n);
-        rc = d2h(s, rp.data(), d.rp, sizeof(float2) * n);
+        rc = sph_d2h(s, rp.data(), d.rp, sizeof(float2) * n);
         if (rc == SPH_OK) for (size_t i = 0; i < n; i++) ((float*)o)[n + i] = rp[i].x;
       }
       break;
@@ -959,11 +940,11 @@ extern "C" int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t coun
   std::vector<int32_t> tb;
   if (ids) {
     ti.resize(words); t16.resize(words); tb.resize((t1 - t0) * 64);
-    rc = d2h(s, ti.data(), s->d.nbrId + base, sizeof(int32_t) * words);
-    if (rc == SPH_OK) rc = d2h(s, t16.data(), s->d.nbr16 + base, sizeof(uint16_t) * words);
-    if (rc == SPH_OK) rc = d2h(s, tb.data(), s->d.nbrBase + t0 * 64, sizeof(int32_t) * tb.size());
+    rc = sph_d2h(s, ti.data(), s->d.nbrId + base, sizeof(int32_t) * words);
+    if (rc == SPH_OK) rc = sph_d2h(s, t16.data(), s->d.nbr16 + base, sizeof(uint16_t) * words);
+    if (rc == SPH_OK) rc = sph_d2h(s, tb.data(), s->d.nbrBase + t0 * 64, sizeof(int32_t) * tb.size());
   }
-  if (rc == SPH_OK && dist) { td.resize(words); rc = d2h(s, td.data(), s->d.nbrDist + base, sizeof(float) * words); }
+  if (rc == SPH_OK && dist) { td.resize(words); rc = sph_d2h(s, td.data(), s->d.nbrDist + base, sizeof(float) * words); }
   if (rc != SPH_OK) return rc;
   const int shift = (int)(t0 * 64);  // the copies start at tile t0: decode with tile-relative particle numbers
   for (int32_t i = 0; i < count; i++)
@@ -979,389 +960,6 @@ extern "C" int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t coun
       if (dist) dist[(size_t)i * 32 + k] = td[src];
     }
   return SPH_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- field sampling
-// Reads the sorted state the last step's density and pressure loop ran on (sph_sample.hip); enqueued on s->stream and waited
-// for, like the sph_read_* family. Large requests go through the device scratch in pieces (z-chunks of a grid, runs of points)
-// so that the scratch stays bounded whatever the request.
-static const size_t kSampleScratchBytes = (size_t)64 << 20;
-
-static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleParams* p) {
-  if (s->hasSlab) { sph_set_error("%s: sampling a slab solver is not supported", what); return SPH_ERR_INVALID; }
-  if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("%s: typeMask must be a non-empty set of bits 1..3", what); return SPH_ERR_INVALID; }
-  NEED(s, P_DENSITY | P_PRESSUREFORCE, what);
-  volatile float hh = s->cfg.h * s->cfg.h;
-  volatile float ss2 = s->cfg.simulationScale * s->cfg.simulationScale;
-  p->typeMask = typeMask; p->hh = hh; p->ss2 = ss2; p->mwp = (float)s->d.massWpoly6;
-  return SPH_OK;
-}
-
-// device buffer *buf of *have bytes grown to at least `bytes` (the old one is freed once the stream has finished with it)
-static int grow_scratch(sph_solver* s, void** buf, size_t* have, size_t bytes) {
-  if (*have >= bytes) return SPH_OK;
-  if (*buf) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(*buf); }
-  *buf = nullptr; *have = 0;
-  SPH_HIP(hipMalloc(buf, bytes));
-  *have = bytes;
-  return SPH_OK;
-}
-
-static int sample_scratch(sph_solver* s, size_t bytes) { return grow_scratch(s, &s->sampleBuf, &s->sampleBytes, bytes); }
-
-extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
-  ENTER(s);
-  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_points: bad count or null pointer"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_sample_points", &p);
-  if (rc != SPH_OK || count == 0) return rc;
-  const size_t rec = sizeof(float) * SPH_SAMPLE_WORDS, perPoint = sizeof(float4) + rec;
-  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
-  rc = sample_scratch(s, (size_t)piece * perPoint);
-  if (rc != SPH_OK) return rc;
-  float* dOut = (float*)s->sampleBuf;
-  float* dPts = (float*)((char*)s->sampleBuf + (size_t)piece * rec);
-  for (int first = 0; first < count; first += piece) {
-    const int n = std::min(piece, count - first);
-    SPH_HIP(hipMemcpyAsync(dPts, points4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
-    rc = sphk_sample_points(s, p, dPts, n, dOut);
-    if (rc != SPH_OK) return rc;
-    rc = d2h(s, out + (size_t)first * SPH_SAMPLE_WORDS, dOut, rec * (size_t)n);
-    if (rc != SPH_OK) return rc;
-  }
-  return SPH_OK;
-}
-
-// z-chunks of whole bricks (4 planes) that fit the scratch; at least one brick layer however large a plane is
-static int sample_grid_planes(const int32_t dims[3], int words = SPH_SAMPLE_WORDS) {
-  const size_t planeBytes = sizeof(float) * words * (size_t)dims[0] * (size_t)dims[1];
-  return (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
-}
-
-extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
-                               uint32_t typeMask, float* out) {
-  ENTER(s);
-  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
-    sph_set_error("sph_sample_grid: null pointer or dims <= 0");
-    return SPH_ERR_INVALID;
-  }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_sample_grid", &p);
-  if (rc != SPH_OK) return rc;
-  const size_t planeBytes = sizeof(float) * SPH_SAMPLE_WORDS * (size_t)dims[0] * (size_t)dims[1];
-  const int planes = sample_grid_planes(dims);
-  rc = sample_scratch(s, planeBytes * (size_t)planes);
-  if (rc != SPH_OK) return rc;
-  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
-    const int nz = std::min(planes, dims[2] - k0);
-    rc = sphk_sample_grid(s, p, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
-    if (rc != SPH_OK) return rc;
-    rc = d2h(s, (char*)out + planeBytes * (size_t)k0, s->sampleBuf, planeBytes * (size_t)nz);
-    if (rc != SPH_OK) return rc;
-  }
-  return SPH_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- isosurface extraction
-// The scalar lattice comes from the sampling kernels (z-chunks through the sampling scratch, one word kept per record), then
-// marching cubes runs on it (sph_surface.hip). Blocks once, for the counts; the emitting kernels stay queued on s->stream.
-static size_t surf_bytes_align(size_t b) { return (b + 255) & ~(size_t)255; }  // triangles start at a 256-B boundary
-
-extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
-                                   uint32_t typeMask, int32_t field, float iso, int64_t counts[2]) {
-  ENTER(s);
-  s->meshValid = false;  // a failed call leaves no mesh behind
-  s->meshCounts[0] = s->meshCounts[1] = 0;
-  if (counts) counts[0] = counts[1] = 0;
-  if (!origin || !spacing || !dims || !counts) { sph_set_error("sph_extract_surface: null pointer"); return SPH_ERR_INVALID; }
-  if (field < 0 || field >= SPH_SURFACE_FIELDS) { sph_set_error("sph_extract_surface: field %d is not in 0..5", field); return SPH_ERR_INVALID; }
-  if (!std::isfinite(iso)) { sph_set_error("sph_extract_surface: iso is not finite"); return SPH_ERR_INVALID; }
-  if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) { sph_set_error("sph_extract_surface: dims must all be >= 2"); return SPH_ERR_INVALID; }
-  const long long P = (long long)dims[0] * (long long)dims[1] * (long long)dims[2];
-  if (P > 0x7fffffffLL) { sph_set_error("sph_extract_surface: the lattice has more than 2^31-1 points"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_extract_surface", &p);
-  if (rc != SPH_OK) return rc;
-  rc = grow_scratch(s, &s->surfBuf, &s->surfBytes, sphk_surface_scratch_bytes(P));
-  if (rc != SPH_OK) return rc;
-  const size_t plane = (size_t)dims[0] * (size_t)dims[1];
-  const int planes = sample_grid_planes(dims);
-  rc = sample_scratch(s, sizeof(float) * SPH_SAMPLE_WORDS * plane * (size_t)planes);
-  if (rc != SPH_OK) return rc;
-  float* lattice = (float*)s->surfBuf;  // the scratch's first P floats
-  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
-    const int nz = std::min(planes, dims[2] - k0);
-    rc = sphk_sample_grid(s, p, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
-    if (rc != SPH_OK) return rc;
-    rc = sphk_surface_field(s, (const float*)s->sampleBuf, field, (int)(plane * (size_t)nz), lattice + plane * (size_t)k0);
-    if (rc != SPH_OK) return rc;
-  }
-  unsigned long long totals[2] = {0, 0};
-  rc = sphk_surface_count(s, s->surfBuf, dims, iso, totals);
-  if (rc != SPH_OK) return rc;
-  if (totals[0] > 0x7fffffffULL) {
-    sph_set_error("sph_extract_surface: %llu vertices exceed the int32 vertex ids", totals[0]);
-    return SPH_ERR_SIZE;
-  }
-  const size_t vBytes = surf_bytes_align(sizeof(float) * 3 * (size_t)totals[0]);
-  rc = grow_scratch(s, &s->meshBuf, &s->meshBytes, std::max<size_t>(vBytes + sizeof(int32_t) * 3 * (size_t)totals[1], 1));
-  if (rc != SPH_OK) return rc;
-  rc = sphk_surface_emit(s, s->surfBuf, dims, iso, origin, spacing, (float*)s->meshBuf, (int32_t*)((char*)s->meshBuf + vBytes));
-  if (rc != SPH_OK) return rc;
-  s->meshCounts[0] = (int64_t)totals[0];
-  s->meshCounts[1] = (int64_t)totals[1];
-  s->meshValid = true;
-  s->meshTypeMask = typeMask;
-  s->meshField = field;
-  s->meshEpoch = s->stateEpoch;
-  counts[0] = s->meshCounts[0];
-  counts[1] = s->meshCounts[1];
-  return SPH_OK;
-}
-
-extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangles) {
-  ENTER(s);
-  if (!s->meshValid) { sph_set_error("sph_read_surface: no surface has been extracted"); return SPH_ERR_ORDER; }
-  const size_t vBytes = sizeof(float) * 3 * (size_t)s->meshCounts[0];
-  int rc = SPH_OK;
-  if (vertices && vBytes) rc = d2h(s, vertices, s->meshBuf, vBytes);
-  if (rc != SPH_OK) return rc;
-  const size_t tBytes = sizeof(int32_t) * 3 * (size_t)s->meshCounts[1];
-  if (triangles && tBytes) rc = d2h(s, triangles, (char*)s->meshBuf + surf_bytes_align(vBytes), tBytes);
-  return rc;
-}
-
-// ---------------------------------------------------------------------------------------------- gradient sampling
-// The same state, selection, argument rules and scratch as field sampling, with 32-word records (sph_gradient.hip).
-static float gradient_scale(const sph_solver* s) { return (float)(-6.0 * s->d.massWpoly6 * (double)s->cfg.simulationScale); }
-
-extern "C" int sph_sample_gradient_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
-  ENTER(s);
-  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_gradient_points: bad count or null pointer"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_sample_gradient_points", &p);
-  if (rc != SPH_OK || count == 0) return rc;
-  const size_t rec = sizeof(float) * SPH_GRADIENT_WORDS, perPoint = sizeof(float4) + rec;
-  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
-  rc = sample_scratch(s, (size_t)piece * perPoint);
-  if (rc != SPH_OK) return rc;
-  float* dOut = (float*)s->sampleBuf;
-  float* dPts = (float*)((char*)s->sampleBuf + (size_t)piece * rec);
-  const float K = gradient_scale(s);
-  for (int first = 0; first < count; first += piece) {
-    const int n = std::min(piece, count - first);
-    SPH_HIP(hipMemcpyAsync(dPts, points4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
-    rc = sphk_gradient_points(s, p, K, dPts, n, dOut);
-    if (rc != SPH_OK) return rc;
-    rc = d2h(s, out + (size_t)first * SPH_GRADIENT_WORDS, dOut, rec * (size_t)n);
-    if (rc != SPH_OK) return rc;
-  }
-  return SPH_OK;
-}
-
-extern "C" int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
-                                        uint32_t typeMask, float* out) {
-  ENTER(s);
-  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
-    sph_set_error("sph_sample_gradient_grid: null pointer or dims <= 0");
-    return SPH_ERR_INVALID;
-  }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_sample_gradient_grid", &p);
-  if (rc != SPH_OK) return rc;
-  const size_t planeBytes = sizeof(float) * SPH_GRADIENT_WORDS * (size_t)dims[0] * (size_t)dims[1];
-  const int planes = sample_grid_planes(dims, SPH_GRADIENT_WORDS);
-  rc = sample_scratch(s, planeBytes * (size_t)planes);
-  if (rc != SPH_OK) return rc;
-  const float K = gradient_scale(s);
-  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
-    const int nz = std::min(planes, dims[2] - k0);
-    rc = sphk_gradient_grid(s, p, K, origin, spacing, dims[0], dims[1], k0, nz, (float*)s->sampleBuf);
-    if (rc != SPH_OK) return rc;
-    rc = d2h(s, (char*)out + planeBytes * (size_t)k0, s->sampleBuf, planeBytes * (size_t)nz);
-    if (rc != SPH_OK) return rc;
-  }
-  return SPH_OK;
-}
-
-// Normals of the mesh in meshBuf, computed from its vertices where they lie; runs of vertices through the sampling scratch.
-extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
-  ENTER(s);
-  if (!s->meshValid) { sph_set_error("sph_surface_normals: no surface has been extracted"); return SPH_ERR_ORDER; }
-  if (s->meshEpoch != s->stateEpoch) {
-    sph_set_error("sph_surface_normals: the solver's state has changed since the surface was extracted");
-    return SPH_ERR_ORDER;
-  }
-  const int64_t V = s->meshCounts[0];
-  if (V > 0 && !normals) { sph_set_error("sph_surface_normals: null pointer"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &p);
-  if (rc != SPH_OK || V == 0) return rc;
-  const size_t rec = sizeof(float) * 3;
-  const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
-  rc = sample_scratch(s, (size_t)piece * rec);
-  if (rc != SPH_OK) return rc;
-  const float K = gradient_scale(s);
-  for (int64_t first = 0; first < V; first += piece) {
-    const int n = (int)std::min<int64_t>(piece, V - first);
-    rc = sphk_surface_normals(s, p, K, s->meshField, (const float*)s->meshBuf + 3 * (size_t)first, n, (float*)s->sampleBuf);
-    if (rc != SPH_OK) return rc;
-    rc = d2h(s, normals + 3 * (size_t)first, s->sampleBuf, rec * (size_t)n);
-    if (rc != SPH_OK) return rc;
-  }
-  return SPH_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- flow diagnostics
-// Reductions and histograms over the same state as sampling (sph_diag.hip); blocking, read-only, no stage timing.
-static int diag_region_ok(const float* b, const char* what) {
-  for (int k = 0; k < 6; k++)
-    if (std::isnan(b[k])) { sph_set_error("%s: a region bound is NaN", what); return SPH_ERR_INVALID; }
-  return SPH_OK;
-}
-
-extern "C" int sph_diagnostics(sph_solver* s, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
-  ENTER(s);
-  if (!regions6 || !out) { sph_set_error("sph_diagnostics: null pointer"); return SPH_ERR_INVALID; }
-  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_diagnostics", &p);
-  if (rc != SPH_OK) return rc;
-  DiagArgs a = {};
-  for (int r = 0; r < count; r++) {
-    rc = diag_region_ok(regions6 + 6 * r, "sph_diagnostics");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
-  }
-  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
-  rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, count));
-  if (rc != SPH_OK) return rc;
-  double* records = nullptr;
-  rc = sphk_diagnostics(s, a, (double*)s->diagBuf, &records);
-  if (rc != SPH_OK) return rc;
-  rc = d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)count);
-  return rc != SPH_OK ? rc : check_finite_state(s);
-}
-
-extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6, uint32_t typeMask,
-                             uint32_t* out) {
-  ENTER(s);
-  if (!out) { sph_set_error("sph_histogram: null pointer"); return SPH_ERR_INVALID; }
-  if (field < 0 || field > 6) { sph_set_error("sph_histogram: field %d is not in 0..6", field); return SPH_ERR_INVALID; }
-  if (bins < 1 || bins > SPH_HIST_MAX_BINS) { sph_set_error("sph_histogram: bins %d is not in 1..%d", bins, SPH_HIST_MAX_BINS); return SPH_ERR_INVALID; }
-  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) { sph_set_error("sph_histogram: lo and hi must be finite with lo < hi"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_histogram", &p);
-  if (rc != SPH_OK) return rc;
-  HistArgs a = {};
-  if (region6) {
-    rc = diag_region_ok(region6, "sph_histogram");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
-  } else {
-    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
-  }
-  volatile float width = hi - lo;
-  volatile float scale = (float)bins / width;
-  a.typeMask = typeMask; a.field = field; a.bins = bins; a.lo = lo; a.hi = hi; a.scale = scale;
-  rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(uint32_t) * (size_t)(bins + 2));
-  if (rc != SPH_OK) return rc;
-  rc = sphk_histogram(s, a, (uint32_t*)s->diagBuf);
-  if (rc != SPH_OK) return rc;
-  rc = d2h(s, out, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
-  return rc != SPH_OK ? rc : check_finite_state(s);
-}
-
-// ---------------------------------------------------------------------------------------------- connected components
-// The pieces the matter is in: components of the graph of the last step's neighbour rows (sph_components.hip). The labelling
-// lives in ccBuf / ccTable until the next one; the per-component records reuse the diagnostics tree with the labels as selection.
-extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t typeMask, int64_t counts[2]) {
-  ENTER(s);
-  s->ccValid = false;  // a failed call leaves no labelling behind
-  s->ccCounts[0] = s->ccCounts[1] = 0;
-  if (counts) counts[0] = counts[1] = 0;
-  if (!counts) { sph_set_error("sph_label_components: null pointer"); return SPH_ERR_INVALID; }
-  if (std::isnan(linkRadius) || !(linkRadius > 0.f)) { sph_set_error("sph_label_components: linkRadius must be > 0"); return SPH_ERR_INVALID; }
-  SampleParams p;
-  int rc = sample_check(s, typeMask, "sph_label_components", &p);
-  if (rc != SPH_OK) return rc;
-  NEED(s, P_FIND, "sph_label_components");
-  const bool finite = !std::isinf(linkRadius);
-  volatile float link2 = linkRadius * linkRadius;
-  rc = grow_scratch(s, &s->ccBuf, &s->ccBytes, sphk_components_scratch_bytes(s->d.N));
-  if (rc != SPH_OK) return rc;
-  uint32_t* dTotals = nullptr;
-  rc = sphk_components_link(s, typeMask, finite, link2, s->ccBuf, &dTotals);
-  if (rc != SPH_OK) return rc;
-  uint32_t totals[3] = {0, 0, 0};
-  rc = d2h(s, totals, dTotals, sizeof(totals));  // the call's one wait for a result
-  if (rc != SPH_OK) return rc;
-  if (totals[2]) {
-    sph_set_error("sph_label_components: a parent walk or hook retry ran past its bound of N steps (flags 0x%x)", totals[2]);
-    return SPH_ERR_HIP;
-  }
-  const int C = (int)totals[1];
-  rc = grow_scratch(s, &s->ccTable, &s->ccTableBytes, sizeof(int32_t) * 8 * (size_t)std::max(C, 1));
-  if (rc != SPH_OK) return rc;
-  rc = sphk_components_number(s, s->ccBuf, C, (int32_t*)s->ccTable);
-  if (rc != SPH_OK) return rc;
-  rc = check_finite_state(s);  // (synchronises the stream)
-  if (rc != SPH_OK) return rc;
-  s->ccCounts[0] = (int64_t)totals[0];
-  s->ccCounts[1] = (int64_t)C;
-  s->ccN = s->d.N;
-  s->ccEpoch = s->stateEpoch;
-  s->ccValid = true;
-  counts[0] = s->ccCounts[0];
-  counts[1] = s->ccCounts[1];
-  return SPH_OK;
-}
-
-extern "C" int sph_read_components(sph_solver* s, int32_t* labels, int32_t* rootCount, float* bbox) {
-  ENTER(s);
-  if (!s->ccValid) { sph_set_error("sph_read_components: no labelling has been made"); return SPH_ERR_ORDER; }
-  int rc = SPH_OK;
-  if (labels && s->ccN > 0) rc = d2h(s, labels, sphk_components_labels(s->ccBuf, s->ccN), sizeof(int32_t) * (size_t)s->ccN);
-  if (rc != SPH_OK) return rc;
-  const size_t C = (size_t)s->ccCounts[1];
-  if ((rootCount || bbox) && C > 0) {
-    std::vector<int32_t> rows(C * 8);
-    rc = d2h(s, rows.data(), s->ccTable, sizeof(int32_t) * 8 * C);
-    if (rc != SPH_OK) return rc;
-    for (size_t c = 0; c < C; c++) {
-      if (rootCount) { rootCount[2 * c] = rows[8 * c]; rootCount[2 * c + 1] = rows[8 * c + 1]; }
-      if (bbox) memcpy(bbox + 6 * c, &rows[8 * c + 2], sizeof(float) * 6);
-    }
-  }
-  return SPH_OK;
-}
-
-extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* components, int32_t count, double* out) {
-  ENTER(s);
-  if (!components || !out) { sph_set_error("sph_component_diagnostics: null pointer"); return SPH_ERR_INVALID; }
-  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_component_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
-  if (!s->ccValid) { sph_set_error("sph_component_diagnostics: no labelling has been made"); return SPH_ERR_ORDER; }
-  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
-    sph_set_error("sph_component_diagnostics: the solver's state has changed since the labelling");
-    return SPH_ERR_ORDER;
-  }
-  DiagArgs a = {};
-  for (int r = 0; r < count; r++) {
-    if (components[r] < 0 || (int64_t)components[r] >= s->ccCounts[1]) {
-      sph_set_error("sph_component_diagnostics: component %d is not in 0..%lld", components[r], (long long)s->ccCounts[1] - 1);
-      return SPH_ERR_INVALID;
-    }
-    a.comp[r] = components[r];
-  }
-  a.count = count; a.typeMask = 0xEu; a.rho0 = s->d.rho0;
-  a.labels = sphk_components_labels(s->ccBuf, s->ccN);
-  int rc = grow_scratch(s, &s->diagBuf, &s->diagBytes, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, count));
-  if (rc != SPH_OK) return rc;
-  double* records = nullptr;
-  rc = sphk_diagnostics(s, a, (double*)s->diagBuf, &records);
-  if (rc != SPH_OK) return rc;
-  rc = d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)count);
-  return rc != SPH_OK ? rc : check_finite_state(s);
 }
 
 // ---------------------------------------------------------------------------------------------- slab decomposition
@@ -1494,7 +1092,7 @@ extern "C" int sph_slab_rebuild(sph_solver* s, const void* recvDown, int32_t nDo
 
 // ---- the rebuild without a host round trip. The frames are what RCCL delivered: [payload words | payload]; the kept count is
 // where the pack left it on the device. Everything is enqueued at once; the totals come back through pinned memory and
-// slab_finish (called by sph_slab_rebuild_finish, or implicitly by the next entry point) sets the new particle count.
+// sph_slab_finish (called by sph_slab_rebuild_finish, or implicitly by the next entry point) sets the new particle count.
 extern "C" int sph_slab_rebuild_framed(sph_solver* s, const void* frameDown, int32_t capDownRecords, const void* frameUp,
                                        int32_t capUpRecords) {
   ENTER(s);
@@ -1518,7 +1116,7 @@ extern "C" int sph_slab_rebuild_framed(sph_solver* s, const void* frameDown, int
 
 // counts: kept, records from below, records from above, and 1 if NOTHING was merged because a frame announced more records than
 // its buffer had room for (the caller fetches the missing part and rebuilds with sph_slab_rebuild; the state is untouched).
-static int slab_finish(sph_solver* s, int32_t counts[4]) {
+int sph_slab_finish(sph_solver* s, int32_t counts[4]) {
   SPH_HIP(hipEventSynchronize(s->slabRebuildEvent));
   s->slabRebuildPending = false;
   if (s->slabStepPending) {  // the flags that came back with the end of the overlapped step
@@ -1552,7 +1150,7 @@ extern "C" int sph_slab_rebuild_finish(sph_solver* s, int32_t counts[4]) {
   ENTER_RAW(s);
   if (!counts) { sph_set_error("sph_slab_rebuild_finish: null argument"); return SPH_ERR_INVALID; }
   if (!s->slabRebuildPending) { sph_set_error("sph_slab_rebuild_finish without sph_slab_rebuild_framed"); return SPH_ERR_ORDER; }
-  return slab_finish(s, counts);
+  return sph_slab_finish(s, counts);
 }
 
 extern "C" int sph_slab_liquid_signature(sph_solver* s, uint32_t* typeBits) {
@@ -1585,9 +1183,9 @@ extern "C" int sph_slab_read(sph_solver* s, float* position4, float* velocity4, 
   if (!s->hasSlab) { sph_set_error("slab not initialised"); return SPH_ERR_INVALID; }
   const size_t n = (size_t)s->d.N;
   int rc = SPH_OK;
-  if (position4) rc = d2h(s, position4, s->d.posOrig, sizeof(float4) * n);
-  if (rc == SPH_OK && velocity4) rc = d2h(s, velocity4, s->d.velOrig, sizeof(float4) * n);
-  if (rc == SPH_OK && globalIds) rc = d2h(s, globalIds, s->d.gid, sizeof(uint32_t) * n);
-  if (rc == SPH_OK && owned) rc = d2h(s, owned, s->d.owned, sizeof(uint32_t) * n);
+  if (position4) rc = sph_d2h(s, position4, s->d.posOrig, sizeof(float4) * n);
+  if (rc == SPH_OK && velocity4) rc = sph_d2h(s, velocity4, s->d.velOrig, sizeof(float4) * n);
+  if (rc == SPH_OK && globalIds) rc = sph_d2h(s, globalIds, s->d.gid, sizeof(uint32_t) * n);
+  if (rc == SPH_OK && owned) rc = sph_d2h(s, owned, s->d.owned, sizeof(uint32_t) * n);
   return rc;
 }

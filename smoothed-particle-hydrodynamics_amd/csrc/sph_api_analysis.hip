@@ -1,0 +1,383 @@
+// C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
+// diagnostics and histograms, connected components. All of them read the sorted state of the last completed step and write
+// nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "sph_api_internal.h"
+
+// ---------------------------------------------------------------------------------------------- field sampling
+// Reads the sorted state the last step's density and pressure loop ran on (sph_sample.hip); enqueued on s->stream and waited
+// for, like the sph_read_* family. Large requests go through the device scratch in pieces (z-chunks of a grid, runs of points)
+// so that the scratch stays bounded whatever the request.
+static const size_t kSampleScratchBytes = (size_t)64 << 20;
+
+// The argument and order rules every analysis call shares; a != nullptr: the constants of the sampling contract too.
+static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleArgs* a = nullptr) {
+  if (s->hasSlab) { sph_set_error("%s: sampling a slab solver is not supported", what); return SPH_ERR_INVALID; }
+  if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("%s: typeMask must be a non-empty set of bits 1..3", what); return SPH_ERR_INVALID; }
+  NEED(s, P_DENSITY | P_PRESSUREFORCE, what);
+  if (!a) return SPH_OK;
+  volatile float hh = s->cfg.h * s->cfg.h;
+  volatile float ss2 = s->cfg.simulationScale * s->cfg.simulationScale;
+  *a = SampleArgs{};
+  a->typeMask = typeMask; a->hh = hh; a->ss2 = ss2; a->mwp = (float)s->d.massWpoly6;
+  return SPH_OK;
+}
+
+// device buffer b grown to at least `bytes` (the old one is freed once the stream has finished with it)
+static int grow_scratch(sph_solver* s, SphScratch& b, size_t bytes) {
+  if (b.bytes >= bytes) return SPH_OK;
+  if (b.p) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(b.p); }
+  b.p = nullptr; b.bytes = 0;
+  SPH_HIP(hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return SPH_OK;
+}
+
+// Runs of `count` host query points (x, y, z, unused) through the sampling scratch: a piece's points are uploaded behind the
+// room for its records of `words` floats, launch(points, n, records) enqueues the kernel on them (device pointers), and the
+// records are copied out.
+template <typename Launch>
+static int sample_point_runs(sph_solver* s, const float* points4, int count, int words, float* out, Launch launch) {
+  const size_t rec = sizeof(float) * words, perPoint = sizeof(float4) + rec;
+  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
+  int rc = grow_scratch(s, s->sampleBuf, (size_t)piece * perPoint);
+  if (rc != SPH_OK) return rc;
+  float* dOut = (float*)s->sampleBuf.p;
+  float* dPts = (float*)((char*)s->sampleBuf.p + (size_t)piece * rec);
+  for (int first = 0; first < count; first += piece) {
+    const int n = std::min(piece, count - first);
+    SPH_HIP(hipMemcpyAsync(dPts, points4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    rc = launch(dPts, n, dOut);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, out + (size_t)first * words, dOut, rec * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+// A lattice in z-chunks of whole bricks (4 planes) that fit the sampling scratch, at least one brick layer however large a
+// plane is: launch(k0, nz, records) enqueues the kernel that fills the records (`words` floats each) of planes [k0, k0 + nz),
+// consume(first, n, records) takes those n records, the lattice's records first .. first + n, from the scratch.
+template <typename Launch, typename Consume>
+static int sample_grid_chunks(sph_solver* s, const int32_t dims[3], int words, Launch launch, Consume consume) {
+  const size_t plane = (size_t)dims[0] * (size_t)dims[1], planeBytes = sizeof(float) * words * plane;
+  const int planes = (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
+  int rc = grow_scratch(s, s->sampleBuf, planeBytes * (size_t)planes);
+  if (rc != SPH_OK) return rc;
+  float* records = (float*)s->sampleBuf.p;
+  for (int k0 = 0; k0 < dims[2]; k0 += planes) {
+    const int nz = std::min(planes, dims[2] - k0);
+    rc = launch(k0, nz, records);
+    if (rc != SPH_OK) return rc;
+    rc = consume(plane * (size_t)k0, plane * (size_t)nz, records);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_points: bad count or null pointer"); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  const int rc = sample_check(s, typeMask, "sph_sample_points", &a);
+  if (rc != SPH_OK || count == 0) return rc;
+  return sample_point_runs(s, points4, count, SPH_SAMPLE_WORDS, out,
+                           [&](const float* pts, int n, float* records) { return sphk_sample_points(s, a, pts, n, records); });
+}
+
+extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                               uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
+    sph_set_error("sph_sample_grid: null pointer or dims <= 0");
+    return SPH_ERR_INVALID;
+  }
+  SampleArgs a;
+  const int rc = sample_check(s, typeMask, "sph_sample_grid", &a);
+  if (rc != SPH_OK) return rc;
+  return sample_grid_chunks(
+      s, dims, SPH_SAMPLE_WORDS,
+      [&](int k0, int nz, float* records) { return sphk_sample_grid(s, a, origin, spacing, dims[0], dims[1], k0, nz, records); },
+      [&](size_t first, size_t n, const float* records) {
+        return sph_d2h(s, out + first * SPH_SAMPLE_WORDS, records, sizeof(float) * SPH_SAMPLE_WORDS * n);
+      });
+}
+
+// ---------------------------------------------------------------------------------------------- isosurface extraction
+// The scalar lattice comes from the sampling kernels (z-chunks through the sampling scratch, one word kept per record), then
+// marching cubes runs on it (sph_surface.hip). Blocks once, for the counts; the emitting kernels stay queued on s->stream.
+static size_t surf_bytes_align(size_t b) { return (b + 255) & ~(size_t)255; }  // triangles start at a 256-B boundary
+
+extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                                   uint32_t typeMask, int32_t field, float iso, int64_t counts[2]) {
+  ENTER(s);
+  s->meshValid = false;  // a failed call leaves no mesh behind
+  s->meshCounts[0] = s->meshCounts[1] = 0;
+  if (counts) counts[0] = counts[1] = 0;
+  if (!origin || !spacing || !dims || !counts) { sph_set_error("sph_extract_surface: null pointer"); return SPH_ERR_INVALID; }
+  if (field < 0 || field >= SPH_SURFACE_FIELDS) { sph_set_error("sph_extract_surface: field %d is not in 0..5", field); return SPH_ERR_INVALID; }
+  if (!std::isfinite(iso)) { sph_set_error("sph_extract_surface: iso is not finite"); return SPH_ERR_INVALID; }
+  if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) { sph_set_error("sph_extract_surface: dims must all be >= 2"); return SPH_ERR_INVALID; }
+  const long long P = (long long)dims[0] * (long long)dims[1] * (long long)dims[2];
+  if (P > 0x7fffffffLL) { sph_set_error("sph_extract_surface: the lattice has more than 2^31-1 points"); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  int rc = sample_check(s, typeMask, "sph_extract_surface", &a);
+  if (rc != SPH_OK) return rc;
+  rc = grow_scratch(s, s->surfBuf, sphk_surface_scratch_bytes(P));
+  if (rc != SPH_OK) return rc;
+  float* lattice = (float*)s->surfBuf.p;  // the scratch's first P floats
+  rc = sample_grid_chunks(
+      s, dims, SPH_SAMPLE_WORDS,
+      [&](int k0, int nz, float* records) { return sphk_sample_grid(s, a, origin, spacing, dims[0], dims[1], k0, nz, records); },
+      [&](size_t first, size_t n, const float* records) { return sphk_surface_field(s, records, field, (int)n, lattice + first); });
+  if (rc != SPH_OK) return rc;
+  unsigned long long totals[2] = {0, 0};
+  rc = sphk_surface_count(s, s->surfBuf.p, dims, iso, totals);
+  if (rc != SPH_OK) return rc;
+  if (totals[0] > 0x7fffffffULL) {
+    sph_set_error("sph_extract_surface: %llu vertices exceed the int32 vertex ids", totals[0]);
+    return SPH_ERR_SIZE;
+  }
+  const size_t vBytes = surf_bytes_align(sizeof(float) * 3 * (size_t)totals[0]);
+  rc = grow_scratch(s, s->meshBuf, std::max<size_t>(vBytes + sizeof(int32_t) * 3 * (size_t)totals[1], 1));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_surface_emit(s, s->surfBuf.p, dims, iso, origin, spacing, (float*)s->meshBuf.p, (int32_t*)((char*)s->meshBuf.p + vBytes));
+  if (rc != SPH_OK) return rc;
+  s->meshCounts[0] = (int64_t)totals[0];
+  s->meshCounts[1] = (int64_t)totals[1];
+  s->meshValid = true;
+  s->meshTypeMask = typeMask;
+  s->meshField = field;
+  s->meshEpoch = s->stateEpoch;
+  counts[0] = s->meshCounts[0];
+  counts[1] = s->meshCounts[1];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangles) {
+  ENTER(s);
+  if (!s->meshValid) { sph_set_error("sph_read_surface: no surface has been extracted"); return SPH_ERR_ORDER; }
+  const size_t vBytes = sizeof(float) * 3 * (size_t)s->meshCounts[0];
+  int rc = SPH_OK;
+  if (vertices && vBytes) rc = sph_d2h(s, vertices, s->meshBuf.p, vBytes);
+  if (rc != SPH_OK) return rc;
+  const size_t tBytes = sizeof(int32_t) * 3 * (size_t)s->meshCounts[1];
+  if (triangles && tBytes) rc = sph_d2h(s, triangles, (char*)s->meshBuf.p + surf_bytes_align(vBytes), tBytes);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- gradient sampling
+// The same state, selection, argument rules and scratch as field sampling, with 32-word records (sph_gradient.hip).
+static float gradient_scale(const sph_solver* s) { return (float)(-6.0 * s->d.massWpoly6 * (double)s->cfg.simulationScale); }
+
+extern "C" int sph_sample_gradient_points(sph_solver* s, const float* points4, int32_t count, uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_gradient_points: bad count or null pointer"); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  const int rc = sample_check(s, typeMask, "sph_sample_gradient_points", &a);
+  if (rc != SPH_OK || count == 0) return rc;
+  const float K = gradient_scale(s);
+  return sample_point_runs(s, points4, count, SPH_GRADIENT_WORDS, out,
+                           [&](const float* pts, int n, float* records) { return sphk_gradient_points(s, a, K, pts, n, records); });
+}
+
+extern "C" int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
+                                        uint32_t typeMask, float* out) {
+  ENTER(s);
+  if (!origin || !spacing || !dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
+    sph_set_error("sph_sample_gradient_grid: null pointer or dims <= 0");
+    return SPH_ERR_INVALID;
+  }
+  SampleArgs a;
+  const int rc = sample_check(s, typeMask, "sph_sample_gradient_grid", &a);
+  if (rc != SPH_OK) return rc;
+  const float K = gradient_scale(s);
+  return sample_grid_chunks(
+      s, dims, SPH_GRADIENT_WORDS,
+      [&](int k0, int nz, float* records) { return sphk_gradient_grid(s, a, K, origin, spacing, dims[0], dims[1], k0, nz, records); },
+      [&](size_t first, size_t n, const float* records) {
+        return sph_d2h(s, out + first * SPH_GRADIENT_WORDS, records, sizeof(float) * SPH_GRADIENT_WORDS * n);
+      });
+}
+
+// Normals of the mesh in meshBuf, computed from its vertices where they lie; runs of vertices through the sampling scratch.
+extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
+  ENTER(s);
+  if (!s->meshValid) { sph_set_error("sph_surface_normals: no surface has been extracted"); return SPH_ERR_ORDER; }
+  if (s->meshEpoch != s->stateEpoch) {
+    sph_set_error("sph_surface_normals: the solver's state has changed since the surface was extracted");
+    return SPH_ERR_ORDER;
+  }
+  const int64_t V = s->meshCounts[0];
+  if (V > 0 && !normals) { sph_set_error("sph_surface_normals: null pointer"); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  int rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &a);
+  if (rc != SPH_OK || V == 0) return rc;
+  const size_t rec = sizeof(float) * 3;
+  const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
+  rc = grow_scratch(s, s->sampleBuf, (size_t)piece * rec);
+  if (rc != SPH_OK) return rc;
+  const float K = gradient_scale(s);
+  for (int64_t first = 0; first < V; first += piece) {
+    const int n = (int)std::min<int64_t>(piece, V - first);
+    rc = sphk_surface_normals(s, a, K, s->meshField, (const float*)s->meshBuf.p + 3 * (size_t)first, n, (float*)s->sampleBuf.p);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, normals + 3 * (size_t)first, s->sampleBuf.p, rec * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- flow diagnostics
+// Reductions and histograms over the same state as sampling (sph_diag.hip); blocking, read-only, no stage timing.
+static int diag_region_ok(const float* b, const char* what) {
+  for (int k = 0; k < 6; k++)
+    if (std::isnan(b[k])) { sph_set_error("%s: a region bound is NaN", what); return SPH_ERR_INVALID; }
+  return SPH_OK;
+}
+
+// the records of a.count selections: through the diagnostics scratch to `out`, then the check every blocking call ends with
+static int diag_records(sph_solver* s, const DiagArgs& a, double* out) {
+  int rc = grow_scratch(s, s->diagBuf, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, a.count));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_diagnostics(s, a, (double*)s->diagBuf.p, &records);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)a.count);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+extern "C" int sph_diagnostics(sph_solver* s, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
+  ENTER(s);
+  if (!regions6 || !out) { sph_set_error("sph_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  int rc = sample_check(s, typeMask, "sph_diagnostics");
+  if (rc != SPH_OK) return rc;
+  DiagArgs a = {};
+  for (int r = 0; r < count; r++) {
+    rc = diag_region_ok(regions6 + 6 * r, "sph_diagnostics");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
+  }
+  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
+  return diag_records(s, a, out);
+}
+
+extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6, uint32_t typeMask,
+                             uint32_t* out) {
+  ENTER(s);
+  if (!out) { sph_set_error("sph_histogram: null pointer"); return SPH_ERR_INVALID; }
+  if (field < 0 || field > 6) { sph_set_error("sph_histogram: field %d is not in 0..6", field); return SPH_ERR_INVALID; }
+  if (bins < 1 || bins > SPH_HIST_MAX_BINS) { sph_set_error("sph_histogram: bins %d is not in 1..%d", bins, SPH_HIST_MAX_BINS); return SPH_ERR_INVALID; }
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) { sph_set_error("sph_histogram: lo and hi must be finite with lo < hi"); return SPH_ERR_INVALID; }
+  int rc = sample_check(s, typeMask, "sph_histogram");
+  if (rc != SPH_OK) return rc;
+  HistArgs a = {};
+  if (region6) {
+    rc = diag_region_ok(region6, "sph_histogram");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
+  } else {
+    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
+  }
+  volatile float width = hi - lo;
+  volatile float scale = (float)bins / width;
+  a.typeMask = typeMask; a.field = field; a.bins = bins; a.lo = lo; a.hi = hi; a.scale = scale;
+  rc = grow_scratch(s, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_histogram(s, a, (uint32_t*)s->diagBuf.p);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, s->diagBuf.p, sizeof(uint32_t) * (size_t)(bins + 2));
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+// ---------------------------------------------------------------------------------------------- connected components
+// The pieces the matter is in: components of the graph of the last step's neighbour rows (sph_components.hip). The labelling
+// lives in ccBuf / ccTable until the next one; the per-component records reuse the diagnostics tree with the labels as selection.
+extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t typeMask, int64_t counts[2]) {
+  ENTER(s);
+  s->ccValid = false;  // a failed call leaves no labelling behind
+  s->ccCounts[0] = s->ccCounts[1] = 0;
+  if (counts) counts[0] = counts[1] = 0;
+  if (!counts) { sph_set_error("sph_label_components: null pointer"); return SPH_ERR_INVALID; }
+  if (std::isnan(linkRadius) || !(linkRadius > 0.f)) { sph_set_error("sph_label_components: linkRadius must be > 0"); return SPH_ERR_INVALID; }
+  int rc = sample_check(s, typeMask, "sph_label_components");
+  if (rc != SPH_OK) return rc;
+  NEED(s, P_FIND, "sph_label_components");
+  const bool finite = !std::isinf(linkRadius);
+  volatile float link2 = linkRadius * linkRadius;
+  rc = grow_scratch(s, s->ccBuf, sphk_components_scratch_bytes(s->d.N));
+  if (rc != SPH_OK) return rc;
+  uint32_t* dTotals = nullptr;
+  rc = sphk_components_link(s, typeMask, finite, link2, s->ccBuf.p, &dTotals);
+  if (rc != SPH_OK) return rc;
+  uint32_t totals[3] = {0, 0, 0};
+  rc = sph_d2h(s, totals, dTotals, sizeof(totals));  // the call's one wait for a result
+  if (rc != SPH_OK) return rc;
+  if (totals[2]) {
+    sph_set_error("sph_label_components: a parent walk or hook retry ran past its bound of N steps (flags 0x%x)", totals[2]);
+    return SPH_ERR_HIP;
+  }
+  const int C = (int)totals[1];
+  rc = grow_scratch(s, s->ccTable, sizeof(int32_t) * 8 * (size_t)std::max(C, 1));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_components_number(s, s->ccBuf.p, C, (int32_t*)s->ccTable.p);
+  if (rc != SPH_OK) return rc;
+  rc = sph_check_finite_state(s);  // (synchronises the stream)
+  if (rc != SPH_OK) return rc;
+  s->ccCounts[0] = (int64_t)totals[0];
+  s->ccCounts[1] = (int64_t)C;
+  s->ccN = s->d.N;
+  s->ccEpoch = s->stateEpoch;
+  s->ccValid = true;
+  counts[0] = s->ccCounts[0];
+  counts[1] = s->ccCounts[1];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_components(sph_solver* s, int32_t* labels, int32_t* rootCount, float* bbox) {
+  ENTER(s);
+  if (!s->ccValid) { sph_set_error("sph_read_components: no labelling has been made"); return SPH_ERR_ORDER; }
+  int rc = SPH_OK;
+  if (labels && s->ccN > 0) rc = sph_d2h(s, labels, sphk_components_labels(s->ccBuf.p, s->ccN), sizeof(int32_t) * (size_t)s->ccN);
+  if (rc != SPH_OK) return rc;
+  const size_t C = (size_t)s->ccCounts[1];
+  if ((rootCount || bbox) && C > 0) {
+    std::vector<int32_t> rows(C * 8);
+    rc = sph_d2h(s, rows.data(), s->ccTable.p, sizeof(int32_t) * 8 * C);
+    if (rc != SPH_OK) return rc;
+    for (size_t c = 0; c < C; c++) {
+      if (rootCount) { rootCount[2 * c] = rows[8 * c]; rootCount[2 * c + 1] = rows[8 * c + 1]; }
+      if (bbox) memcpy(bbox + 6 * c, &rows[8 * c + 2], sizeof(float) * 6);
+    }
+  }
+  return SPH_OK;
+}
+
+extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* components, int32_t count, double* out) {
+  ENTER(s);
+  if (!components || !out) { sph_set_error("sph_component_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_component_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  if (!s->ccValid) { sph_set_error("sph_component_diagnostics: no labelling has been made"); return SPH_ERR_ORDER; }
+  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
+    sph_set_error("sph_component_diagnostics: the solver's state has changed since the labelling");
+    return SPH_ERR_ORDER;
+  }
+  DiagArgs a = {};
+  for (int r = 0; r < count; r++) {
+    if (components[r] < 0 || (int64_t)components[r] >= s->ccCounts[1]) {
+      sph_set_error("sph_component_diagnostics: component %d is not in 0..%lld", components[r], (long long)s->ccCounts[1] - 1);
+      return SPH_ERR_INVALID;
+    }
+    a.comp[r] = components[r];
+  }
+  a.count = count; a.typeMask = 0xEu; a.rho0 = s->d.rho0;
+  a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
+  return diag_records(s, a, out);
+}
+

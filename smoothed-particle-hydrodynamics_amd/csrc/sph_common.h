@@ -73,6 +73,8 @@ struct SphDev {  // what the kernels see; passed by value
   uint32_t* dbg;  // SPH_DBG_WORDS diagnostic counters (neighbour-search fallbacks etc.), zeroed by sph_reset_stage_times
 };
 
+struct SphScratch { void* p; size_t bytes; };  // a device buffer that only grows
+
 struct sph_solver {
   sph_config cfg;
   SphDev d;
@@ -122,14 +124,10 @@ struct sph_solver {
   struct HostReg { void* p; size_t bytes; };
   HostReg hostRegs[8]; int numHostRegs;    // caller buffers page-locked in place by hipHostRegister (released by sph_destroy)
   uint32_t* pinnedFlags;               // pinned: [0] copy of dbg[6] taken with the last asynchronous read-back
-  uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (check_finite_state)
-  // field sampling (sph_sample_points / sph_sample_grid): device scratch for query points and records, grown on demand
-  void* sampleBuf; size_t sampleBytes;
-  // diagnostics (sph_diagnostics / sph_histogram): device scratch for the reduction tree's partials and the bins, grown on demand
-  void* diagBuf; size_t diagBytes;
-  // isosurface extraction (sph_extract_surface / sph_read_surface): lattice scratch and the last mesh, grown on demand
-  void* surfBuf; size_t surfBytes;
-  void* meshBuf; size_t meshBytes;
+  uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (sph_check_finite_state)
+  // device scratch of the analysis calls (sph_api_analysis.hip), each grown on demand and kept: query points and records of
+  // field / gradient sampling; the diagnostics tree's partials and the histogram bins; the isosurface lattice; the last mesh
+  SphScratch sampleBuf, diagBuf, surfBuf, meshBuf;
   int64_t meshCounts[2]; bool meshValid;  // vertices, triangles of the last successful extraction
   uint32_t meshTypeMask; int meshField;   // ... and its arguments (sph_surface_normals)
   uint64_t meshEpoch;                     // stateEpoch when it was extracted
@@ -137,8 +135,7 @@ struct sph_solver {
   // only allowed while it still equals meshEpoch
   uint64_t stateEpoch;
   // connected components (sph_label_components / sph_read_components): the labelling's scratch and table, grown on demand
-  void* ccBuf; size_t ccBytes;
-  void* ccTable; size_t ccTableBytes;
+  SphScratch ccBuf, ccTable;
   int64_t ccCounts[2]; bool ccValid;  // selected particles, components of the last successful labelling
   int ccN;                            // ... the particle count it was made for
   uint64_t ccEpoch;                   // ... and stateEpoch at that time (sph_component_diagnostics)
@@ -245,23 +242,27 @@ int sphk_slab_rebuild(sph_solver* s, const uint32_t* recvDown, int nDown, const 
 int sphk_slab_rebuild_framed(sph_solver* s, const uint32_t* frameDown, int capDown, const uint32_t* frameUp, int capUp,
                              const uint32_t* keptPtr, uint32_t* totals);  // every length read on the device; d.N is left alone
 int sphk_slab_sort_rebuild(sph_solver* s, int total);  // staging area in any order -> local set sorted by global id
-// sph_sample.hip (read-only on every solver array; the constants of the sampling contract, include/sphmi.h)
-struct SampleParams {
+// sph_sample.hip (read-only on every solver array). The kernels' arguments: the constants of the sampling contract
+// (include/sphmi.h), which the entry points fill, and the lattice of a grid launch, which the grid launchers fill.
+struct SampleArgs {
   uint32_t typeMask;  // bits 1..3: liquid, elastic, boundary
-  float hh;           // h*h rounded to float once
+  float hh;           // h*h, rounded to float once: the selection test r2 < hh
   float ss2;          // simScale*simScale
   float mwp;          // (float)massWpoly6
+  // grid: point (i, j, k) = origin + (float)i * spacing per axis; k counts from kBase (the chunk's first z plane)
+  float ox, oy, oz, sx, sy, sz;
+  int nx, ny, nz, kBase;
 };
-int sphk_sample_points(sph_solver* s, const SampleParams& p, const float* pts4, int count, float* out);  // device pointers
+int sphk_sample_points(sph_solver* s, const SampleArgs& a, const float* pts4, int count, float* out);  // device pointers
 // grid z-planes [kBase, kBase + nz) of the lattice origin + (float)i * spacing; out = nz x ny x nx records (device)
-int sphk_sample_grid(sph_solver* s, const SampleParams& p, const float origin[3], const float spacing[3], int nx, int ny,
+int sphk_sample_grid(sph_solver* s, const SampleArgs& a, const float origin[3], const float spacing[3], int nx, int ny,
                      int kBase, int nz, float* out);
 // sph_gradient.hip (the gradient records of include/sphmi.h; K = (float)(-6 * massWpoly6 * simScale)); device pointers
-int sphk_gradient_points(sph_solver* s, const SampleParams& p, float K, const float* pts4, int count, float* out);
-int sphk_gradient_grid(sph_solver* s, const SampleParams& p, float K, const float origin[3], const float spacing[3], int nx, int ny,
+int sphk_gradient_points(sph_solver* s, const SampleArgs& a, float K, const float* pts4, int count, float* out);
+int sphk_gradient_grid(sph_solver* s, const SampleArgs& a, float K, const float origin[3], const float spacing[3], int nx, int ny,
                        int kBase, int nz, float* out);  // as sphk_sample_grid, 32-word records
 // normals[3*i..] of the `count` packed (x, y, z) vertices at verts, from the gradient of record word `field` (0..5)
-int sphk_surface_normals(sph_solver* s, const SampleParams& p, float K, int field, const float* verts, int count, float* normals);
+int sphk_surface_normals(sph_solver* s, const SampleArgs& a, float K, int field, const float* verts, int count, float* normals);
 // sph_diag.hip (the records and histograms of include/sphmi.h; read-only on every solver array)
 struct DiagArgs {
   float box[SPH_DIAG_MAX_REGIONS][6];  // x0, y0, z0, x1, y1, z1 per region

@@ -93,33 +93,12 @@ __device__ __forceinline__ void grad_store(const SampleArgs& a, float K, const G
   for (int k = 0; k < SPH_GRADIENT_WORDS / 4; k++) o[k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
 }
 
-// One point, one lane, direct loads: sample_one's walk with the gradient sums. Returns whether the point is finite.
+// One point through the point walk (sph_sample_walk.h) with the gradient sums. Returns whether the point is finite.
 __device__ bool grad_one(const SphDev& d, const SampleArgs& a, float px, float py, float pz, GradAcc& g) {
   grad_zero(g);
-  if (!sample_finite(px, py, pz)) return false;
-  int x0, x1, y0, y1, z0, z1;
-  sample_axis_range(px, d, x0, x1); sample_axis_range(py, d, y0, y1); sample_axis_range(pz, d, z0, z1);
-  uint64_t last = 0;  // 0 = none yet; otherwise key + 1
-  for (;;) {
-    uint32_t best = 0xffffffffu;
-    for (int cz = z0; cz <= z1; cz++)
-      for (int cy = y0; cy <= y1; cy++)
-        for (int cx = x0; cx <= x1; cx++) {
-          const uint32_t k = sample_key(d, cx, cy, cz);
-          if (k < (uint32_t)d.G && (uint64_t)k + 1 > last && k < best) best = k;
-        }
-    if (best == 0xffffffffu) break;
-    last = (uint64_t)best + 1;
-    uint32_t start, end;
-    sample_run(d, best, start, end);
-    for (uint32_t j = start; j < end; j++) {
-      const float4 xj = d.sortedPos[j];
-      if (!sample_type_ok(a, xj.w)) continue;
-      const float4 v = d.sortedVel[j];
-      grad_hit(d, a, g, px, py, pz, xj, make_float4(v.x, v.y, v.z, d.rp[j].y), 1.0f / d.rho[j]);
-    }
-  }
-  return true;
+  return sample_point_walk(d, a, px, py, pz, [&](float x, float y, float z, float4 xj, float4 vj, float invRho) {
+    grad_hit(d, a, g, x, y, z, xj, vj, invRho);
+  });
 }
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_gradient_points(SphDev d, SampleArgs a, float K, const float4* __restrict__ pts,
@@ -135,85 +114,23 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_gradient_points(SphDev d, SampleA
 // Grid points whose bricks would span too many cells for the wave-uniform walk (spacing > 2h/3): one lane per point.
 __global__ __launch_bounds__(SPH_BLOCK) void k_gradient_grid_points(SphDev d, SampleArgs a, float K, float* __restrict__ out) {
   const long long i = (long long)blockIdx.x * SPH_BLOCK + threadIdx.x;
-  const long long plane = (long long)a.nx * a.ny;
-  if (i >= plane * a.nz) return;
-  const int k = (int)(i / plane), rem = (int)(i - (long long)k * plane), j = rem / a.nx, ii = rem - j * a.nx;
-  const float px = a.ox + (float)ii * a.sx, py = a.oy + (float)j * a.sy, pz = a.oz + (float)(a.kBase + k) * a.sz;
+  float px, py, pz;
+  if (!sample_grid_point(a, i, px, py, pz)) return;
   GradAcc g;
   const bool finite = grad_one(d, a, px, py, pz, g);
   grad_store(a, K, g, finite, out + (size_t)i * SPH_GRADIENT_WORDS);
 }
 
-// The hot path: k_sample_grid's brick walk (one wave per 4x4x4 brick, the brick box's distinct keys ascending and made scalar,
-// runs staged through LDS 64 candidates at a time with the type folded into a NaN x) with the gradient sums per hit. The LDS
-// bytes per candidate are sampling's; only the work per hit and the accumulators grow.
-// Bricks whose box would exceed SPH_SAMPLE_BOX_MAX cells (points far apart: huge coordinates) walk each lane's own box in turn
-// (at most 4x4x4 cells, sample_axis_range) with the other lanes' query points made NaN: the same ascending walk as grad_one,
-// without inlining a second walk, which would double the kernel's registers.
+// The hot path: the brick walk (sph_sample_walk.h) with the gradient sums per hit. The LDS bytes per candidate are sampling's;
+// only the work per hit and the accumulators grow.
 __global__ __launch_bounds__(SPH_SAMPLE_WAVE) void k_gradient_grid(SphDev d, SampleArgs a, float K, int nbx, int nby, int nblocks,
                                                                    float* __restrict__ out) {
-  __shared__ float4 sPos[SPH_SAMPLE_WAVE];
-  __shared__ float4 sVel[SPH_SAMPLE_WAVE];
-  __shared__ float sInv[SPH_SAMPLE_WAVE];
-  const int b = sample_xcd_block(nblocks);
-  const int lane = threadIdx.x;
-  const int bx = b % nbx, by = (b / nbx) % nby, bz = b / (nbx * nby);
-  const int i = bx * 4 + (lane & 3), j = by * 4 + ((lane >> 2) & 3), k = bz * 4 + (lane >> 4);
-  const bool valid = i < a.nx && j < a.ny && k < a.nz;
-  float px = a.ox + (float)i * a.sx, py = a.oy + (float)j * a.sy, pz = a.oz + (float)(a.kBase + k) * a.sz;
-  const bool active = valid && sample_finite(px, py, pz);
-  float* o = out + (((size_t)k * a.ny + j) * a.nx + i) * SPH_GRADIENT_WORDS;
-  int x0 = 0x7fffffff, x1 = -0x7fffffff - 1, y0 = x0, y1 = x1, z0 = x0, z1 = x1;
-  if (active) { sample_axis_range(px, d, x0, x1); sample_axis_range(py, d, y0, y1); sample_axis_range(pz, d, z0, z1); }
-  else px = py = pz = __builtin_nanf("");  // never selects anything
-  int bx0 = wave_min_i(x0), bx1 = wave_max_i(x1), by0 = wave_min_i(y0), by1 = wave_max_i(y1);
-  int bz0 = wave_min_i(z0), bz1 = wave_max_i(z1);
   GradAcc g;
   grad_zero(g);
-  const bool perLane = bx0 <= bx1 && (long long)(bx1 - bx0 + 1) * (by1 - by0 + 1) * (bz1 - bz0 + 1) > SPH_SAMPLE_BOX_MAX;
-  // walks: 1 over the brick's box (none if no lane is active), or one per lane's box
-  for (int w = 0; w < (perLane ? SPH_SAMPLE_WAVE : 1); w++) {
-    float qx = px, qy = py, qz = pz;
-    if (perLane) {
-      bx0 = __shfl(x0, w, SPH_SAMPLE_WAVE); bx1 = __shfl(x1, w, SPH_SAMPLE_WAVE);
-      by0 = __shfl(y0, w, SPH_SAMPLE_WAVE); by1 = __shfl(y1, w, SPH_SAMPLE_WAVE);
-      bz0 = __shfl(z0, w, SPH_SAMPLE_WAVE); bz1 = __shfl(z1, w, SPH_SAMPLE_WAVE);
-      if (lane != w) qx = qy = qz = __builtin_nanf("");
-    }
-    if (bx0 > bx1) continue;  // no active lane (in this walk)
-    const int nbox = (bx1 - bx0 + 1) * (by1 - by0 + 1) * (bz1 - bz0 + 1);
-    // lane l holds the key of box cell l (0xffffffff: none, or outside the table)
-    const int wx = bx1 - bx0 + 1, wy = by1 - by0 + 1;
-    uint32_t myKey = 0xffffffffu;
-    if (lane < nbox) {
-      const int cx = bx0 + lane % wx, cy = by0 + (lane / wx) % wy, cz = bz0 + lane / (wx * wy);
-      const uint32_t key = sample_key(d, cx, cy, cz);
-      if (key < (uint32_t)d.G) myKey = key;
-    }
-    for (;;) {
-      const uint32_t key = __builtin_amdgcn_readfirstlane(wave_min_u(myKey));
-      if (key == 0xffffffffu) break;
-      if (myKey == key) myKey = 0xffffffffu;  // dedupe: every lane holding this key drops it
-      uint32_t start, end;
-      sample_run(d, key, start, end);
-      for (uint32_t base = start; base < end; base += SPH_SAMPLE_WAVE) {
-        const uint32_t c = base + (uint32_t)lane;
-        if (c < end) {
-          float4 xj = d.sortedPos[c];
-          const float4 v = d.sortedVel[c];
-          if (!sample_type_ok(a, xj.w)) xj.x = __builtin_nanf("");
-          sPos[lane] = xj;
-          sVel[lane] = make_float4(v.x, v.y, v.z, d.rp[c].y);
-          sInv[lane] = 1.0f / d.rho[c];
-        }
-        __syncthreads();
-        const int cnt = (int)min(end - base, (uint32_t)SPH_SAMPLE_WAVE);
-        for (int q = 0; q < cnt; q++) grad_hit(d, a, g, qx, qy, qz, sPos[q], sVel[q], sInv[q]);
-        __syncthreads();
-      }
-    }
-  }
-  if (valid) grad_store(a, K, g, active, o);
+  const SampleBrickLane l = sample_brick_walk(d, a, nbx, nby, nblocks, [&](float x, float y, float z, float4 xj, float4 vj, float invRho) {
+    grad_hit(d, a, g, x, y, z, xj, vj, invRho);
+  });
+  if (l.valid) grad_store(a, K, g, l.finite, out + l.index * SPH_GRADIENT_WORDS);
 }
 
 // One normal per mesh vertex: the gradient record at the vertex's coordinates (the points path, bit for bit), then
@@ -243,47 +160,30 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_surface_normals(SphDev d, SampleA
   normals[3 * (size_t)i + 2] = nz;
 }
 
-static SampleArgs grad_args(const SampleParams& p) {
-  SampleArgs a = {};
-  a.typeMask = p.typeMask; a.hh = p.hh; a.ss2 = p.ss2; a.mwp = p.mwp;
-  return a;
-}
-
-int sphk_gradient_points(sph_solver* s, const SampleParams& p, float K, const float* pts4, int count, float* out) {
+int sphk_gradient_points(sph_solver* s, const SampleArgs& a, float K, const float* pts4, int count, float* out) {
   if (count <= 0) return SPH_OK;
-  hipLaunchKernelGGL(k_gradient_points, dim3(sph_blocks(count)), dim3(SPH_BLOCK), 0, s->stream, s->d, grad_args(p), K,
-                     (const float4*)pts4, count, out);
+  hipLaunchKernelGGL(k_gradient_points, dim3(sph_blocks(count)), dim3(SPH_BLOCK), 0, s->stream, s->d, a, K, (const float4*)pts4, count,
+                     out);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
 
-int sphk_gradient_grid(sph_solver* s, const SampleParams& p, float K, const float origin[3], const float spacing[3], int nx, int ny,
+int sphk_gradient_grid(sph_solver* s, const SampleArgs& a, float K, const float origin[3], const float spacing[3], int nx, int ny,
                        int kBase, int nz, float* out) {
-  SampleArgs a = grad_args(p);
-  a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-  a.sx = spacing[0]; a.sy = spacing[1]; a.sz = spacing[2];
-  a.nx = nx; a.ny = ny; a.nz = nz; a.kBase = kBase;
-  // the brick / per-lane split of sphk_sample_grid
-  const float lim = 2.0f * s->d.h / 3.0f;
-  const bool bricks = fabsf(a.sx) <= lim && fabsf(a.sy) <= lim && fabsf(a.sz) <= lim;
-  if (bricks) {
-    const int nbx = (nx + 3) / 4, nby = (ny + 3) / 4, nbz = (nz + 3) / 4;
-    const long long nb = (long long)nbx * nby * nbz;
-    if (nb > 0x7fffffffLL) { sph_set_error("sph_sample_gradient_grid: chunk too large"); return SPH_ERR_INVALID; }
-    hipLaunchKernelGGL(k_gradient_grid, dim3((unsigned)nb), dim3(SPH_SAMPLE_WAVE), 0, s->stream, s->d, a, K, nbx, nby, (int)nb, out);
-  } else {
-    const long long n = (long long)nx * ny * nz;
-    hipLaunchKernelGGL(k_gradient_grid_points, dim3((unsigned)((n + SPH_BLOCK - 1) / SPH_BLOCK)), dim3(SPH_BLOCK), 0, s->stream,
-                       s->d, a, K, out);
-  }
-  SPH_HIP(hipGetLastError());
-  return SPH_OK;
+  return sample_launch_grid(
+      s, a, origin, spacing, nx, ny, kBase, nz, "sph_sample_gradient_grid",
+      [&](const SampleArgs& g, int nbx, int nby, int nb) {
+        hipLaunchKernelGGL(k_gradient_grid, dim3((unsigned)nb), dim3(SPH_SAMPLE_WAVE), 0, s->stream, s->d, g, K, nbx, nby, nb, out);
+      },
+      [&](const SampleArgs& g, unsigned blocks) {
+        hipLaunchKernelGGL(k_gradient_grid_points, dim3(blocks), dim3(SPH_BLOCK), 0, s->stream, s->d, g, K, out);
+      });
 }
 
-int sphk_surface_normals(sph_solver* s, const SampleParams& p, float K, int field, const float* verts, int count, float* normals) {
+int sphk_surface_normals(sph_solver* s, const SampleArgs& a, float K, int field, const float* verts, int count, float* normals) {
   if (count <= 0) return SPH_OK;
-  hipLaunchKernelGGL(k_surface_normals, dim3(sph_blocks(count)), dim3(SPH_BLOCK), 0, s->stream, s->d, grad_args(p), K, field, verts,
-                     count, normals);
+  hipLaunchKernelGGL(k_surface_normals, dim3(sph_blocks(count)), dim3(SPH_BLOCK), 0, s->stream, s->d, a, K, field, verts, count,
+                     normals);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }

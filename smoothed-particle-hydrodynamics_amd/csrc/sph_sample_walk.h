@@ -1,21 +1,12 @@
-// Shared by the sampling kernels (sph_sample.hip) and the gradient kernels (sph_gradient.hip): the launch arguments, the
-// cell walk of one query point (axis ranges, masked keys, runs of the cell table), the sampling record and the wave-wide
-// reductions of the brick walk. See sph_sample.hip for the contract these serve.
+// Shared by the sampling kernels (sph_sample.hip) and the gradient kernels (sph_gradient.hip): the two cell walks (one query
+// point per lane; one 4x4x4 brick of grid points per wave) as templates over what is done per selected particle, the pieces
+// they are made of (axis ranges, masked keys, runs of the cell table), the sampling record and the split of a grid launch
+// between the two walks. See sph_sample.hip for the contract these serve.
 #pragma once
 #include "sph_common.h"
 
 #define SPH_SAMPLE_WAVE 64
 #define SPH_SAMPLE_BOX_MAX 64  // cells a brick box may hold for the wave-uniform walk (3x3x3 = 27 while spacing <= 2h/3)
-
-struct SampleArgs {
-  uint32_t typeMask;  // bits 1..3
-  float hh;           // h*h, rounded to float once: the selection test r2 < hh
-  float ss2;          // simScale*simScale
-  float mwp;          // (float)massWpoly6
-  // grid: point (i, j, k) = origin + (float)i * spacing per axis; k counts from kBase (the chunk's first z plane)
-  float ox, oy, oz, sx, sy, sz;
-  int nx, ny, nz, kBase;
-};
 
 // Cell range of one axis that holds every particle a query coordinate c can select. The hash truncates x * cellSizeInv and
 // is monotone, so [(int)((c-h)*inv), (int)((c+h)*inv)] holds them up to rounding; the range is widened by a margin far
@@ -94,3 +85,147 @@ __device__ __forceinline__ uint32_t wave_min_u(uint32_t v) {
   return v;
 }
 
+// The point walk. One point, one lane, direct loads: the distinct keys of the point's cell box in ascending order (each step
+// finds the smallest key above the last one, so equal masked keys — aliased cells in reference mode — are visited once), and
+// hit(px, py, pz, xj, (vel.xyz, pressure), 1/rho_j) for every particle of a selected type in those runs, in ascending
+// sorted index. Returns whether the point is finite (a non-finite point selects nothing).
+template <typename Hit>
+__device__ __forceinline__ bool sample_point_walk(const SphDev& d, const SampleArgs& a, float px, float py, float pz, Hit hit) {
+  if (!sample_finite(px, py, pz)) return false;
+  int x0, x1, y0, y1, z0, z1;
+  sample_axis_range(px, d, x0, x1); sample_axis_range(py, d, y0, y1); sample_axis_range(pz, d, z0, z1);
+  uint64_t last = 0;  // 0 = none yet; otherwise key + 1
+  for (;;) {
+    uint32_t best = 0xffffffffu;
+    for (int cz = z0; cz <= z1; cz++)
+      for (int cy = y0; cy <= y1; cy++)
+        for (int cx = x0; cx <= x1; cx++) {
+          const uint32_t k = sample_key(d, cx, cy, cz);
+          if (k < (uint32_t)d.G && (uint64_t)k + 1 > last && k < best) best = k;
+        }
+    if (best == 0xffffffffu) break;
+    last = (uint64_t)best + 1;
+    uint32_t start, end;
+    sample_run(d, best, start, end);
+    for (uint32_t j = start; j < end; j++) {
+      const float4 xj = d.sortedPos[j];
+      if (!sample_type_ok(a, xj.w)) continue;
+      const float4 v = d.sortedVel[j];
+      hit(px, py, pz, xj, make_float4(v.x, v.y, v.z, d.rp[j].y), 1.0f / d.rho[j]);
+    }
+  }
+  return true;
+}
+
+// Point i of a grid chunk in the order of its records (x fastest); false past the chunk's end.
+__device__ __forceinline__ bool sample_grid_point(const SampleArgs& a, long long i, float& px, float& py, float& pz) {
+  const long long plane = (long long)a.nx * a.ny;
+  if (i >= plane * a.nz) return false;
+  const int k = (int)(i / plane), rem = (int)(i - (long long)k * plane), j = rem / a.nx, ii = rem - j * a.nx;
+  px = a.ox + (float)ii * a.sx; py = a.oy + (float)j * a.sy; pz = a.oz + (float)(a.kBase + k) * a.sz;
+  return true;
+}
+
+struct SampleBrickLane {
+  bool valid;    // the lane's point lies inside the chunk: it has a record
+  bool finite;   // ... and its coordinates are finite
+  size_t index;  // of that record in the chunk
+};
+
+// The brick walk, the hot path: one wave (one block) per 4x4x4 brick of grid points, lane = x + 4y + 16z. The brick's cell box
+// is the union of its points' boxes; its distinct keys are taken in ascending order (wave-wide minimum above the last one, made
+// scalar), and each run is streamed through LDS in chunks of 64 candidates: one coalesced load per candidate (position,
+// velocity, pressure, 1/rho once per candidate; particles of unselected types get a NaN x so that every lane's distance test
+// rejects them), then every lane loops over the chunk with broadcast LDS reads and calls hit as the point walk does. A candidate
+// from a cell outside a lane's own box fails that lane's distance test (monotone hash), so each lane's hits come in ascending
+// sorted index with no per-lane cell logic; hit has to make that distance test, with r2 < a.hh false for a NaN.
+// (Broadcasting each candidate with v_readlane instead of LDS was measured 2x slower: DESIGN.md §12.)
+// Bricks whose box would exceed SPH_SAMPLE_BOX_MAX cells (points far apart: huge coordinates) walk each lane's own box in turn
+// (at most 4x4x4 cells, sample_axis_range) with the other lanes' query points made NaN: the same ascending walk as the point
+// walk's, without inlining a second walk, which would cost the kernels registers.
+template <typename Hit>
+__device__ __forceinline__ SampleBrickLane sample_brick_walk(const SphDev& d, const SampleArgs& a, int nbx, int nby, int nblocks,
+                                                             Hit hit) {
+  __shared__ float4 sPos[SPH_SAMPLE_WAVE];
+  __shared__ float4 sVel[SPH_SAMPLE_WAVE];
+  __shared__ float sInv[SPH_SAMPLE_WAVE];
+  const int b = sample_xcd_block(nblocks);
+  const int lane = threadIdx.x;
+  const int bx = b % nbx, by = (b / nbx) % nby, bz = b / (nbx * nby);
+  const int i = bx * 4 + (lane & 3), j = by * 4 + ((lane >> 2) & 3), k = bz * 4 + (lane >> 4);
+  const bool valid = i < a.nx && j < a.ny && k < a.nz;
+  float px = a.ox + (float)i * a.sx, py = a.oy + (float)j * a.sy, pz = a.oz + (float)(a.kBase + k) * a.sz;
+  const bool active = valid && sample_finite(px, py, pz);
+  int x0 = 0x7fffffff, x1 = -0x7fffffff - 1, y0 = x0, y1 = x1, z0 = x0, z1 = x1;
+  if (active) { sample_axis_range(px, d, x0, x1); sample_axis_range(py, d, y0, y1); sample_axis_range(pz, d, z0, z1); }
+  else px = py = pz = __builtin_nanf("");  // never selects anything
+  int bx0 = wave_min_i(x0), bx1 = wave_max_i(x1), by0 = wave_min_i(y0), by1 = wave_max_i(y1);
+  int bz0 = wave_min_i(z0), bz1 = wave_max_i(z1);
+  const bool perLane = bx0 <= bx1 && (long long)(bx1 - bx0 + 1) * (by1 - by0 + 1) * (bz1 - bz0 + 1) > SPH_SAMPLE_BOX_MAX;
+  // walks: 1 over the brick's box (none if no lane is active), or one per lane's box
+  for (int w = 0; w < (perLane ? SPH_SAMPLE_WAVE : 1); w++) {
+    float qx = px, qy = py, qz = pz;
+    if (perLane) {
+      bx0 = __shfl(x0, w, SPH_SAMPLE_WAVE); bx1 = __shfl(x1, w, SPH_SAMPLE_WAVE);
+      by0 = __shfl(y0, w, SPH_SAMPLE_WAVE); by1 = __shfl(y1, w, SPH_SAMPLE_WAVE);
+      bz0 = __shfl(z0, w, SPH_SAMPLE_WAVE); bz1 = __shfl(z1, w, SPH_SAMPLE_WAVE);
+      if (lane != w) qx = qy = qz = __builtin_nanf("");
+    }
+    if (bx0 > bx1) continue;  // no active lane (in this walk)
+    const int nbox = (bx1 - bx0 + 1) * (by1 - by0 + 1) * (bz1 - bz0 + 1);
+    // lane l holds the key of box cell l (0xffffffff: none, or outside the table)
+    const int wx = bx1 - bx0 + 1, wy = by1 - by0 + 1;
+    uint32_t myKey = 0xffffffffu;
+    if (lane < nbox) {
+      const int cx = bx0 + lane % wx, cy = by0 + (lane / wx) % wy, cz = bz0 + lane / (wx * wy);
+      const uint32_t key = sample_key(d, cx, cy, cz);
+      if (key < (uint32_t)d.G) myKey = key;
+    }
+    for (;;) {
+      const uint32_t key = __builtin_amdgcn_readfirstlane(wave_min_u(myKey));
+      if (key == 0xffffffffu) break;
+      if (myKey == key) myKey = 0xffffffffu;  // dedupe: every lane holding this key drops it
+      uint32_t start, end;
+      sample_run(d, key, start, end);
+      for (uint32_t base = start; base < end; base += SPH_SAMPLE_WAVE) {
+        const uint32_t c = base + (uint32_t)lane;
+        if (c < end) {
+          float4 xj = d.sortedPos[c];
+          const float4 v = d.sortedVel[c];
+          if (!sample_type_ok(a, xj.w)) xj.x = __builtin_nanf("");
+          sPos[lane] = xj;
+          sVel[lane] = make_float4(v.x, v.y, v.z, d.rp[c].y);
+          sInv[lane] = 1.0f / d.rho[c];
+        }
+        __syncthreads();
+        const int cnt = (int)min(end - base, (uint32_t)SPH_SAMPLE_WAVE);
+        for (int q = 0; q < cnt; q++) hit(qx, qy, qz, sPos[q], sVel[q], sInv[q]);
+        __syncthreads();
+      }
+    }
+  }
+  return SampleBrickLane{valid, active, ((size_t)k * a.ny + j) * a.nx + i};
+}
+
+// One chunk of a grid (z-planes [kBase, kBase + nz)): fills the lattice part of the arguments and launches the brick walk,
+// bricks(args, nbx, nby, blocks), or one lane per point, points(args, blocks). `what` names the entry point in the error.
+template <typename Bricks, typename Points>
+static int sample_launch_grid(const sph_solver* s, SampleArgs a, const float origin[3], const float spacing[3], int nx, int ny,
+                              int kBase, int nz, const char* what, Bricks bricks, Points points) {
+  a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
+  a.sx = spacing[0]; a.sy = spacing[1]; a.sz = spacing[2];
+  a.nx = nx; a.ny = ny; a.nz = nz; a.kBase = kBase;
+  // A 4-point brick spans 3 spacings; with spacing <= 2h/3 its box is at most 3 cells (of 2h) per axis: the wave-uniform walk.
+  const float lim = 2.0f * s->d.h / 3.0f;
+  if (fabsf(a.sx) <= lim && fabsf(a.sy) <= lim && fabsf(a.sz) <= lim) {
+    const int nbx = (nx + 3) / 4, nby = (ny + 3) / 4, nbz = (nz + 3) / 4;
+    const long long nb = (long long)nbx * nby * nbz;
+    if (nb > 0x7fffffffLL) { sph_set_error("%s: chunk too large", what); return SPH_ERR_INVALID; }
+    bricks(a, nbx, nby, (int)nb);
+  } else {
+    const long long n = (long long)nx * ny * nz;
+    points(a, (unsigned)((n + SPH_BLOCK - 1) / SPH_BLOCK));
+  }
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}

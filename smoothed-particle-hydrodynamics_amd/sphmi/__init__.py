@@ -400,6 +400,23 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _points4(points, what):
+    """Query points ([Q, 3] or [Q, 4]) as the float32[Q, 4] array the sph_sample_*_points calls read."""
+    pts = np.asarray(points, np.float32)
+    pts = pts.reshape(-1, pts.shape[-1]) if pts.ndim else pts.reshape(-1, 1)
+    if pts.shape[1] not in (3, 4):
+        raise SphError("%s: points must be [Q, 3] or [Q, 4]" % what)
+    p4 = np.zeros((pts.shape[0], 4), np.float32)
+    p4[:, :3] = pts[:, :3]
+    return p4
+
+
+def _lattice(origin, spacing, dims):
+    """A lattice's (origin, spacing, dims) as the three arrays the grid calls read."""
+    return (np.ascontiguousarray(origin, np.float32).reshape(3), np.ascontiguousarray(spacing, np.float32).reshape(3),
+            np.ascontiguousarray(dims, np.int32).reshape(3))
+
+
 def build_info():
     """sph_build_info() of the loaded libsphmi.so ("DIAG" in it: a timing-only variant with invalid results)."""
     return device_lib().sph_build_info().decode()
@@ -500,21 +517,14 @@ class owHIPSolver:
     def sample_points(self, points, types=(1, 2, 3)):
         """SPH interpolation at `points` ([Q, 3] or [Q, 4], scene units) over the particles of the given types:
         float32[Q, 8] records (density, shepard, vx, vy, vz, pressure, count, 0), include/sphmi.h."""
-        pts = np.asarray(points, np.float32)
-        pts = pts.reshape(-1, pts.shape[-1]) if pts.ndim else pts.reshape(-1, 1)
-        if pts.shape[1] not in (3, 4):
-            raise SphError("sample_points: points must be [Q, 3] or [Q, 4]")
-        p4 = np.zeros((pts.shape[0], 4), np.float32)
-        p4[:, :3] = pts[:, :3]
+        p4 = _points4(points, "sample_points")
         out = np.empty((p4.shape[0], SAMPLE_WORDS), np.float32)
         self._chk(self._L.sph_sample_points(self._h, _ptr(p4), p4.shape[0], type_mask(types), _ptr(out)))
         return out
 
     def sample_grid(self, origin, spacing, dims, types=(1, 2, 3)):
         """The same on the lattice origin + (float)i * spacing, i < dims = (nx, ny, nz): float32[nz, ny, nx, 8]."""
-        o = np.ascontiguousarray(origin, np.float32).reshape(3)
-        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
-        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        o, sp, dm = _lattice(origin, spacing, dims)
         size = int(dm[0]) * int(dm[1]) * int(dm[2]) if (dm > 0).all() else 0
         out = np.empty((max(int(dm[2]), 0), max(int(dm[1]), 0), max(int(dm[0]), 0), SAMPLE_WORDS) if size else (1, SAMPLE_WORDS),
                        np.float32)
@@ -531,9 +541,7 @@ class owHIPSolver:
             if field not in frames.GRID_FIELDS[:SURFACE_FIELDS]:
                 raise SphError("extract_surface: field must be one of %s" % (frames.GRID_FIELDS[:SURFACE_FIELDS],))
             field = frames.GRID_FIELDS.index(field)
-        o = np.ascontiguousarray(origin, np.float32).reshape(3)
-        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
-        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        o, sp, dm = _lattice(origin, spacing, dims)
         counts = np.zeros(2, np.int64)
         self._mesh_vertices = 0  # (a failed extraction leaves no mesh behind)
         self._chk(self._L.sph_extract_surface(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), int(field), float(iso),
@@ -549,21 +557,14 @@ class owHIPSolver:
         """sample_points with the SPH gradients: float32[Q, 32] records (the 8 sample words, grad rho, grad shepard, grad u
         row-major, grad p, vorticity, divergence, Q, 0; frames.GRADIENT_FIELDS, include/sphmi.h). Gradients are per metre of
         simulation-scaled space."""
-        pts = np.asarray(points, np.float32)
-        pts = pts.reshape(-1, pts.shape[-1]) if pts.ndim else pts.reshape(-1, 1)
-        if pts.shape[1] not in (3, 4):
-            raise SphError("sample_gradient_points: points must be [Q, 3] or [Q, 4]")
-        p4 = np.zeros((pts.shape[0], 4), np.float32)
-        p4[:, :3] = pts[:, :3]
+        p4 = _points4(points, "sample_gradient_points")
         out = np.empty((p4.shape[0], GRADIENT_WORDS), np.float32)
         self._chk(self._L.sph_sample_gradient_points(self._h, _ptr(p4), p4.shape[0], type_mask(types), _ptr(out)))
         return out
 
     def sample_gradient_grid(self, origin, spacing, dims, types=(1, 2, 3)):
         """The same on sample_grid's lattice: float32[nz, ny, nx, 32]."""
-        o = np.ascontiguousarray(origin, np.float32).reshape(3)
-        sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
-        dm = np.ascontiguousarray(dims, np.int32).reshape(3)
+        o, sp, dm = _lattice(origin, spacing, dims)
         size = int(dm[0]) * int(dm[1]) * int(dm[2]) if (dm > 0).all() else 0
         out = np.empty((int(dm[2]), int(dm[1]), int(dm[0]), GRADIENT_WORDS) if size else (1, GRADIENT_WORDS), np.float32)
         self._chk(self._L.sph_sample_gradient_grid(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), _ptr(out)))

@@ -158,6 +158,30 @@ def grid_points(origin, spacing, dims):
     return g
 
 
+def axis_cell_range(c, h, cell_size_inv):
+    """float32 restatement of the kernels' sample_axis_range (sph_sample_walk.h): the cell range [lo, hi] of one axis that
+    holds every particle the coordinates `c` can select."""
+    c = np.asarray(c, np.float32)
+    h, inv = f32(h), f32(cell_size_inv)
+    ul, uh = (c - h) * inv, (c + h) * inv
+    ul = ul - np.minimum(np.abs(ul) * f32(2.0 ** -21) + f32(2.0 ** -10), f32(0.5))
+    uh = uh + np.minimum(np.abs(uh) * f32(2.0 ** -21) + f32(2.0 ** -10), f32(0.5))
+    lo = np.trunc(np.clip(ul, f32(-2.0 ** 30), f32(2.0 ** 30))).astype(np.int64)
+    hi = np.trunc(np.clip(uh, f32(-2.0 ** 30), f32(2.0 ** 30))).astype(np.int64)
+    return lo, np.minimum(hi, lo + 3)
+
+
+def brick_box_cells(origin, spacing, dims, h, cell_size_inv):
+    """Cells in the box of every 4x4x4 brick of the lattice (finite points only), as the brick walk forms it: the union of
+    its points' axis_cell_range per axis. int64[nbz, nby, nbx]; a box above 64 cells takes the walk's per-lane form."""
+    g = grid_points(origin, spacing, dims)
+    widths = []
+    for axis, coords in enumerate((g[0, 0, :, 0], g[0, :, 0, 1], g[:, 0, 0, 2])):
+        lo, hi = axis_cell_range(coords, h, cell_size_inv)
+        widths.append(np.array([hi[b:b + 4].max() - lo[b:b + 4].min() + 1 for b in range(0, len(coords), 4)], np.int64))
+    return widths[2][:, None, None] * widths[1][None, :, None] * widths[0][None, None, :]
+
+
 def brute_force_f64(pos, vel, rho, p, types, points, h, sim_scale, mass_wpoly6, types_sel=(1, 2, 3)):
     """The same interpolation in float64 with a plain all-pairs loop over points (for small clouds): density, shepard,
     velocity, pressure, count."""

@@ -129,6 +129,13 @@ def test_gradient_grid_equals_points_config1():
     # a lattice with non-finite points: all-zero records
     g = hip.sample_gradient_grid((np.inf, 0.0, 0.0), (h / 2, h / 2, h / 2), (5, 6, 7))
     assert not bits(g).any()
+    # brick path so far out that float coordinates no longer resolve h: bricks whose cell box exceeds the 64 cells of the
+    # wave-uniform walk go lane by lane; nothing is within h, so n is 0 and every word is zero (words 8..13 are K * 0 = -0,
+    # as on the points path)
+    far = ((2e7, 2e7, 2e7), (0.66 * h, 0.66 * h, 0.66 * h), (12, 12, 12))
+    assert (sample_ref.brick_box_cells(*far, cfg.h, cfg.hashGridCellSizeInv) > 64).any()
+    g, _ = grid_vs_points(hip, *far)
+    assert not g.any() and not bits(g[..., 6]).any()
     hip.close()
 
 

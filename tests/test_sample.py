@@ -180,6 +180,12 @@ def test_sample_grid_equals_points_config1():
     # spacing > 2h/3: one lane per point
     g, _ = grid_vs_points(hip, (0.0, 0.0, 0.0), (1.5 * h, 1.5 * h, 2 * h), (21, 15, 40))
     assert g[..., 6].max() > 5
+    # brick path so far out that float coordinates no longer resolve h: bricks whose cell box exceeds the 64 cells of the
+    # wave-uniform walk go lane by lane; nothing is within h, so every record is all +0
+    far = ((2e7, 2e7, 2e7), (0.66 * h, 0.66 * h, 0.66 * h), (12, 12, 12))
+    assert (sample_ref.brick_box_cells(*far, cfg.h, cfg.hashGridCellSizeInv) > 64).any()
+    g, _ = grid_vs_points(hip, *far)
+    assert not bits(g).any()
     hip.close()
 
 
