@@ -330,6 +330,62 @@ int sph_read_components(sph_solver* s, int32_t* labels /* host, N, sorted order 
 int sph_component_diagnostics(sph_solver* s, const int32_t* components /* host, count ids */, int32_t count,
                               double* out /* host, count x SPH_DIAG_WORDS */);
 
+/* ---- Particle selection, free-surface measure and compact read-back (no reference counterpart) --------------------------------
+ * State: the sorted state of the last completed step and that step's neighbour rows, exactly as sph_label_components describes
+ * them (one integration step behind sph_read_position). row(i) = the 32 slots of sorted particle i as sph_read_neighbor_rows
+ * returns them (-1 = empty).
+ * SURFACE MEASURE m_i of sorted particle i, all float, in the written order, no contraction, IEEE division and square root:
+ *   W = Bx = By = Bz = 0
+ *   for slot k = 0 .. 31 in ascending order, j = row(i)[k], skipped when j < 0 or j == i:
+ *     dx = x_j - x_i, dy = y_j - y_i, dz = z_j - z_i           (sorted positions, scene units)
+ *     r2 = dx*dx + dy*dy + dz*dz                                (the sampling contract's expression and order)
+ *     t  = hs2 - r2*ss2                                         (hs2, ss2 as in the sampling contract)
+ *     skipped when !(t > 0)                                     (the rows hold entries at or beyond h: the search admits 31h/30)
+ *     w  = (t*t)*t;  W += w;  Bx += w*dx;  By += w*dy;  Bz += w*dz
+ *   if W == 0:  m = 1.0f
+ *   else:       cx = Bx/W, cy = By/W, cz = Bz/W;  m = sqrtf((cx*cx + cy*cy) + cz*cz) / h
+ * i.e. the distance from the particle to the kernel-weighted centroid of the neighbours the step used, in units of h: 0 in a
+ * symmetric neighbourhood, 1 by definition for a particle without neighbours, never above 1 up to rounding. Neighbours of every
+ * type count (liquid at a wall or at an elastic shell is not "surface"), selected or not. The quotients are taken BEFORE the
+ * squares: w is about 1e-31 with the usual simulationScale, and Bx*Bx would underflow float to 0.
+ * sph_particle_measure writes m for every sorted particle.
+ * SELECTION: sorted particle j is selected when all of these hold:
+ *   - sph_diagnostics selects it for region6 with typeMask (type, cell key < gridCellCount, half-open float box; region6 == NULL
+ *     is "everything");
+ *   - for each of the termCount (0 .. SPH_SELECT_MAX_TERMS) terms {field, lo, hi}: q >= lo && q < hi in float, where q for field
+ *     0..6 is bit for bit the q of sph_histogram for that field (density, speed, pressure, neighbour count as a float, x, y, z)
+ *     and field 7 (SPH_SELECT_FIELD_SURFACE) is m_j. lo may be -infinity and hi +infinity; a NaN q fails the term;
+ *   - if component >= 0: labels[j] == component in the solver's current labelling (sph_label_components).
+ * The selection is the list of the selected sorted indices IN ASCENDING ORDER; every entry is a function of the state and the
+ * arguments, and nothing in it depends on launch geometry or execution order. *count receives its length. It lives in device
+ * memory owned by the solver until the next sph_select_particles or sph_destroy.
+ * READ-BACK: sph_read_selection(s, sortedIndex, origId, records); any pointer may be NULL. Entry r describes selected particle
+ * j = sortedIndex[r]: origId[r] is its particleIndex value (the mapping of word 22 of the diagnostics record), records[r] is
+ * SPH_SELECT_WORDS floats { x, y, z, type, vx, vy, vz, rho, p, neighbour count, m, 0 }, each word bit-identical to what the
+ * existing exports give for particle j (sortedPosition xyz, sortedVelocity, rho, pressure, the histogram's field 3) and to
+ * sph_particle_measure. type is the particle's position.w bit pattern (1, 2.x, 3: sph_read_position's .w of particle origId[r]),
+ * not the .w of the exported sortedPosition, which carries the cell id in the reference's layout.
+ * Rules: blocking, on the solver's stream, read-only on every solver array (a mesh stays valid for sph_surface_normals, a
+ * labelling for sph_component_diagnostics), not stages (no stage timing). SPH_ERR_ORDER before a step's neighbour, density and
+ * pressure-force stages have run; for sph_read_selection before any successful selection and, because it gathers from the live
+ * state, once any stage, step or slab call has run since the selection; for component >= 0 without a labelling of the current
+ * state. SPH_ERR_INVALID for a slab solver, a typeMask of 0 or with bits outside 1..3, a NaN region bound, termCount outside
+ * 0..SPH_SELECT_MAX_TERMS or null terms with termCount > 0, a field outside 0..7, a NaN bound or lo >= hi, component < -1 or
+ * >= the labelling's component count, a null count or out. Zero selected particles is legal. A failed selection leaves none
+ * behind. Device memory: 4 bytes per SELECTED particle for the list (sized from a counting pass), 40 bytes per 256 particles for
+ * the scan (a 1-bit-per-particle mask of the counting pass, block counts and offsets), and the sampling scratch (at most 64 MiB)
+ * as staging for the records and the measure, which go to the host in pieces; grown on demand, freed by sph_destroy. */
+#define SPH_SELECT_WORDS 12
+#define SPH_SELECT_MAX_TERMS 4
+#define SPH_SELECT_FIELD_SURFACE 7
+typedef struct sph_select_term { int32_t field; float lo, hi; } sph_select_term;
+int sph_particle_measure(sph_solver* s, float* out /* host, N floats, sorted order */);
+int sph_select_particles(sph_solver* s, const float* region6 /* host or NULL */, uint32_t typeMask,
+                         const sph_select_term* terms /* host, termCount */, int32_t termCount, int32_t component /* -1 = any */,
+                         int64_t* count);
+int sph_read_selection(sph_solver* s, int32_t* sortedIndex /* host, count */, uint32_t* origId /* host, count */,
+                       float* records /* host, count x 12 */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

@@ -1,5 +1,5 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components. All of them read the sorted state of the last completed step and write
+// diagnostics and histograms, connected components, particle selection. All of them read the sorted state of the last completed step and write
 // nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
 #include <string.h>
 
@@ -381,3 +381,138 @@ extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* component
   return diag_records(s, a, out);
 }
 
+
+// ---------------------------------------------------------------------------------------------- particle selection
+// Which particles, not what about them (sph_select.hip): a counting pass sizes the list, the list is written in ascending
+// sorted index, and the records are gathered from the live state when they are asked for (the meshEpoch / ccEpoch pattern).
+static int select_check(sph_solver* s, uint32_t typeMask, const char* what, float* ss2) {
+  SampleArgs a;
+  const int rc = sample_check(s, typeMask, what, &a);
+  if (rc != SPH_OK) return rc;
+  NEED(s, P_FIND, what);
+  *ss2 = a.ss2;
+  return SPH_OK;
+}
+
+extern "C" int sph_particle_measure(sph_solver* s, float* out) {
+  ENTER(s);
+  if (!out) { sph_set_error("sph_particle_measure: null pointer"); return SPH_ERR_INVALID; }
+  float ss2 = 0.f;
+  int rc = select_check(s, 0xEu, "sph_particle_measure", &ss2);
+  if (rc != SPH_OK) return rc;
+  const int N = s->d.N;
+  if (N <= 0) return SPH_OK;
+  const int piece = (int)std::min<size_t>(((size_t)N + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / sizeof(float));
+  rc = grow_scratch(s, s->sampleBuf, sizeof(float) * (size_t)piece);
+  if (rc != SPH_OK) return rc;
+  for (int first = 0; first < N; first += piece) {
+    const int n = std::min(piece, N - first);
+    rc = sphk_particle_measure(s, ss2, first, n, (float*)s->sampleBuf.p);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, out + first, s->sampleBuf.p, sizeof(float) * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return sph_check_finite_state(s);
+}
+
+extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_t typeMask, const sph_select_term* terms,
+                                    int32_t termCount, int32_t component, int64_t* count) {
+  ENTER(s);
+  s->selValid = false;  // a failed call leaves no selection behind
+  s->selCount = 0;
+  if (count) *count = 0;
+  if (!count) { sph_set_error("sph_select_particles: null count"); return SPH_ERR_INVALID; }
+  SelectArgs a = {};
+  int rc = select_check(s, typeMask, "sph_select_particles", &a.ss2);
+  if (rc != SPH_OK) return rc;
+  a.typeMask = typeMask;
+  if (region6) {
+    rc = diag_region_ok(region6, "sph_select_particles");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
+  } else {
+    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
+  }
+  if (termCount < 0 || termCount > SPH_SELECT_MAX_TERMS) {
+    sph_set_error("sph_select_particles: termCount %d is not in 0..%d", termCount, SPH_SELECT_MAX_TERMS);
+    return SPH_ERR_INVALID;
+  }
+  if (termCount > 0 && !terms) { sph_set_error("sph_select_particles: null terms"); return SPH_ERR_INVALID; }
+  a.termCount = termCount;
+  for (int k = 0; k < termCount; k++) {
+    const sph_select_term& t = terms[k];
+    if (t.field < 0 || t.field > SPH_SELECT_FIELD_SURFACE) { sph_set_error("sph_select_particles: field %d is not in 0..7", t.field); return SPH_ERR_INVALID; }
+    if (std::isnan(t.lo) || std::isnan(t.hi) || !(t.lo < t.hi)) { sph_set_error("sph_select_particles: a term needs lo < hi, neither NaN"); return SPH_ERR_INVALID; }
+    a.field[k] = t.field; a.lo[k] = t.lo; a.hi[k] = t.hi;
+    if (t.field == 3 || t.field == SPH_SELECT_FIELD_SURFACE) a.needRow = 1;
+    if (t.field == SPH_SELECT_FIELD_SURFACE) a.needMeasure = 1;
+  }
+  a.component = -1;
+  if (component < -1) { sph_set_error("sph_select_particles: component %d is below -1", component); return SPH_ERR_INVALID; }
+  if (component >= 0) {
+    if (!s->ccValid || s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
+      sph_set_error("sph_select_particles: no labelling of the current state (sph_label_components)");
+      return SPH_ERR_ORDER;
+    }
+    if ((int64_t)component >= s->ccCounts[1]) {
+      sph_set_error("sph_select_particles: component %d is not in 0..%lld", component, (long long)s->ccCounts[1] - 1);
+      return SPH_ERR_INVALID;
+    }
+    a.component = component;
+    a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
+  }
+  rc = grow_scratch(s, s->selBuf, sphk_select_scratch_bytes(s->d.N));
+  if (rc != SPH_OK) return rc;
+  uint32_t* dTotals = nullptr;
+  rc = sphk_select_count(s, a, s->selBuf.p, &dTotals);
+  if (rc != SPH_OK) return rc;
+  uint32_t totals[2] = {0, 0};
+  rc = sph_d2h(s, totals, dTotals, sizeof(totals));  // the call's one wait for a result
+  if (rc != SPH_OK) return rc;
+  if (totals[0] > (uint32_t)std::max(s->d.N, 0)) { sph_set_error("sph_select_particles: the count %u exceeds N", totals[0]); return SPH_ERR_HIP; }
+  rc = grow_scratch(s, s->selList, sizeof(int32_t) * (size_t)std::max<uint32_t>(totals[0], 1u));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_select_scatter(s, s->selBuf.p, totals[0], (int32_t*)s->selList.p);
+  if (rc != SPH_OK) return rc;
+  rc = sph_check_finite_state(s);  // (synchronises the stream)
+  if (rc != SPH_OK) return rc;
+  s->selCount = (int64_t)totals[0];
+  s->selN = s->d.N;
+  s->selEpoch = s->stateEpoch;
+  s->selValid = true;
+  *count = s->selCount;
+  return SPH_OK;
+}
+
+extern "C" int sph_read_selection(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records) {
+  ENTER(s);
+  if (!s->selValid) { sph_set_error("sph_read_selection: no selection has been made"); return SPH_ERR_ORDER; }
+  if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
+    sph_set_error("sph_read_selection: the solver's state has changed since the selection");
+    return SPH_ERR_ORDER;
+  }
+  const size_t n = (size_t)s->selCount;
+  if (n == 0) return SPH_OK;
+  int rc = SPH_OK;
+  const int32_t* list = (const int32_t*)s->selList.p;
+  if (sortedIndex) rc = sph_d2h(s, sortedIndex, list, sizeof(int32_t) * n);
+  if (rc != SPH_OK || (!origId && !records)) return rc;
+  float ss2 = 0.f;
+  rc = select_check(s, 0xEu, "sph_read_selection", &ss2);
+  if (rc != SPH_OK) return rc;
+  const size_t rec = sizeof(float) * SPH_SELECT_WORDS, per = rec + sizeof(uint32_t);
+  const size_t piece = std::min<size_t>(n, kSampleScratchBytes / per);
+  rc = grow_scratch(s, s->sampleBuf, piece * per);
+  if (rc != SPH_OK) return rc;
+  float* dRec = (float*)s->sampleBuf.p;
+  uint32_t* dIds = (uint32_t*)((char*)s->sampleBuf.p + piece * rec);
+  for (size_t first = 0; first < n; first += piece) {
+    const size_t m = std::min(piece, n - first);
+    rc = sphk_select_gather(s, ss2, list + first, (int)m, dRec, dIds);
+    if (rc != SPH_OK) return rc;
+    if (records) rc = sph_d2h(s, records + first * SPH_SELECT_WORDS, dRec, rec * m);
+    if (rc == SPH_OK && origId) rc = sph_d2h(s, origId + first, dIds, sizeof(uint32_t) * m);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}

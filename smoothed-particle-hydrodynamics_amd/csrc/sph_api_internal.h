@@ -1,5 +1,5 @@
 // What the two translation units of the C ABI share (sph_api.hip: solver lifetime, stages, step, read-back, slab;
-// sph_api_analysis.hip: sampling, surfaces, gradients, diagnostics, components): the order contract and the entry checks.
+// sph_api_analysis.hip: sampling, surfaces, gradients, diagnostics, components, selection): the order contract and the entry checks.
 #pragma once
 #include "sph_common.h"
 

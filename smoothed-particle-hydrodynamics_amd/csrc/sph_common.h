@@ -139,6 +139,12 @@ struct sph_solver {
   int64_t ccCounts[2]; bool ccValid;  // selected particles, components of the last successful labelling
   int ccN;                            // ... the particle count it was made for
   uint64_t ccEpoch;                   // ... and stateEpoch at that time (sph_component_diagnostics)
+  // particle selection (sph_select_particles / sph_read_selection): the scan's scratch (mask, block counts) and the list of
+  // selected sorted indices, grown on demand; the records go through sampleBuf in pieces
+  SphScratch selBuf, selList;
+  int64_t selCount; bool selValid;    // length of the last successful selection
+  int selN;                           // ... the particle count it was made for
+  uint64_t selEpoch;                  // ... and stateEpoch at that time (sph_read_selection gathers from the live state)
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -289,6 +295,25 @@ int32_t* sphk_components_labels(void* scratch, int N);   // where the N labels l
 int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float link2, void* scratch, uint32_t** totals);
 // after sphk_components_link on the same scratch: labels, and the table of C rows of 8 words (root, n, bbox as floats)
 int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table);
+// sph_select.hip (particle selection, surface measure and compact read-back; read-only on every solver array)
+struct SelectArgs {
+  float box[6];
+  uint32_t typeMask;
+  int termCount;
+  int field[SPH_SELECT_MAX_TERMS];
+  float lo[SPH_SELECT_MAX_TERMS], hi[SPH_SELECT_MAX_TERMS];
+  int component;          // -1: any
+  const int32_t* labels;  // the current labelling (component >= 0)
+  float ss2;              // simScale*simScale, one float (the sampling contract's)
+  int needRow, needMeasure;  // a term on field 3 or 7 / on field 7: the surviving lanes walk their row
+};
+size_t sphk_select_scratch_bytes(int N);  // the 1-bit mask (8 B per 64 particles), block counts and offsets (8 B per 256), totals
+// flags + scan: *totals = 2 device words, the number of selected particles
+int sphk_select_count(sph_solver* s, const SelectArgs& a, void* scratch, uint32_t** totals);
+int sphk_select_scatter(sph_solver* s, void* scratch, uint32_t total, int32_t* list);  // after sphk_select_count, same scratch
+// records (SPH_SELECT_WORDS floats each, 16-byte aligned) and original ids of list[0..n); device pointers
+int sphk_select_gather(sph_solver* s, float ss2, const int32_t* list, int n, float* records, uint32_t* origId);
+int sphk_particle_measure(sph_solver* s, float ss2, int first, int n, float* out);  // out[r] = m of sorted particle first + r
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

@@ -109,6 +109,20 @@ class owHIPSolver {
   void componentDiagnostics(const int32_t* ids, int count, double* out) {
     check(sph_component_diagnostics(s_, ids, count, out), "componentDiagnostics");
   }
+  // beyond the reference: the particles themselves. particleMeasure writes the surface measure of every sorted particle
+  // (particleCount floats); selectParticles selects on the device by type, region (x0,y0,z0,x1,y1,z1 or null), up to
+  // SPH_SELECT_MAX_TERMS range terms and a component of the last labelling (-1 = any) and returns the number selected;
+  // readSelection copies the ascending sorted indices, the original ids and the SPH_SELECT_WORDS-float records (any pointer may
+  // be null) (include/sphmi.h, sph_particle_measure / sph_select_particles / sph_read_selection)
+  void particleMeasure(float* out) { check(sph_particle_measure(s_, out), "particleMeasure"); }
+  int64_t selectParticles(const float* region6, unsigned int typeMask, const sph_select_term* terms, int termCount, int component = -1) {
+    int64_t count = 0;
+    check(sph_select_particles(s_, region6, typeMask, terms, termCount, component, &count), "selectParticles");
+    return count;
+  }
+  void readSelection(int32_t* sortedIndex, uint32_t* origId, float* records) {
+    check(sph_read_selection(s_, sortedIndex, origId, records), "readSelection");
+  }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

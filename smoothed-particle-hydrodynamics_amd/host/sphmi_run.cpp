@@ -26,6 +26,12 @@
 //        and write one CSV row per report and component for the M largest components (default 16, at most 16), ordered by
 //        descending n, then ascending root: step, component id, root, n, bounding box (%.9g) and the 32 words of its
 //        sph_component_diagnostics record (%.17g; sphmi.frames.read_components_csv); unless --quiet, one summary line per report
+//   ... --select-every K --select-out DIR [--select-surface T] [--select-region X0 Y0 Z0 X1 Y1 Z1] [--select-types T...]
+//       [--select-term FIELD LO HI]...
+//        after every K-th step, select particles on the device (sph_select_particles) and write DIR/selection_<steps done>.bin:
+//        the count as int64, then the sorted indices (int32), the original ids (uint32) and the 12-float records
+//        (sphmi.frames.read_selection). Types default to 1 (liquid); FIELD is density, speed, pressure, neighbors, x, y, z,
+//        surface or 0..7, "inf" / "-inf" are accepted as bounds, up to 4 terms; --select-surface T is the term surface T inf
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -82,6 +88,14 @@ static void write_ply(const std::string& path, const std::vector<float>& verts, 
   if (fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
 }
 
+static int select_field(const char* name) {
+  static const char* names[] = {"density", "speed", "pressure", "neighbors", "x", "y", "z", "surface"};
+  for (int f = 0; f < 8; f++)
+    if (!strcmp(name, names[f])) return f;
+  if (name[0] >= '0' && name[0] <= '7' && !name[1]) return name[0] - '0';
+  return -1;
+}
+
 int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
@@ -93,8 +107,30 @@ int main(int argc, char** argv) {
   std::vector<float> diagRegions = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};  // region 0: everything
   int compEvery = 0, compTop = SPH_DIAG_MAX_REGIONS; bool compSeen = false, compTypesSeen = false; const char* compFile = nullptr;
   float compLink = INFINITY; unsigned compMask = 0;
+  int selEvery = 0; bool selSeen = false, selTypesSeen = false, selRegionSeen = false; const char* selDir = nullptr;
+  unsigned selMask = 0; float selRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+  std::vector<sph_select_term> selTerms;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
+    else if (!strcmp(argv[i], "--select-every") && i + 1 < argc) { selEvery = atoi(argv[++i]); selSeen = true; }
+    else if (!strcmp(argv[i], "--select-out") && i + 1 < argc) { selDir = argv[++i]; selSeen = true; }
+    else if (!strcmp(argv[i], "--select-surface") && i + 1 < argc) { selTerms.push_back(sph_select_term{SPH_SELECT_FIELD_SURFACE, (float)atof(argv[++i]), INFINITY}); selSeen = true; }
+    else if (!strcmp(argv[i], "--select-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) selRegion[k] = (float)atof(argv[++i]); selSeen = selRegionSeen = true; }
+    else if (!strcmp(argv[i], "--select-term") && i + 3 < argc) {
+      const int f = select_field(argv[++i]);
+      if (f < 0) { fprintf(stderr, "--select-term FIELD LO HI: FIELD is density, speed, pressure, neighbors, x, y, z, surface or 0..7\n"); return 2; }
+      const float lo = (float)atof(argv[++i]), hi = (float)atof(argv[++i]);
+      selTerms.push_back(sph_select_term{f, lo, hi});
+      selSeen = true;
+    }
+    else if (!strcmp(argv[i], "--select-types")) {
+      selSeen = selTypesSeen = true;
+      while (i + 1 < argc && argv[i + 1][0] != '-') {
+        const int t = atoi(argv[++i]);
+        if (t < 1 || t > 3) { fprintf(stderr, "--select-types: a type is 1 (liquid), 2 (elastic) or 3 (boundary)\n"); return 2; }
+        selMask |= 1u << t;
+      }
+    }
     else if (!strcmp(argv[i], "--components-every") && i + 1 < argc) { compEvery = atoi(argv[++i]); compSeen = true; }
     else if (!strcmp(argv[i], "--components-out") && i + 1 < argc) { compFile = argv[++i]; compSeen = true; }
     else if (!strcmp(argv[i], "--components-link") && i + 1 < argc) { compLink = (float)atof(argv[++i]); compSeen = true; }
@@ -165,6 +201,18 @@ int main(int argc, char** argv) {
   if (std::isnan(compLink) || !(compLink > 0.f)) { fprintf(stderr, "--components-link R: R must be > 0\n"); return 2; }
   if (compTop < 1 || compTop > SPH_DIAG_MAX_REGIONS) { fprintf(stderr, "--components-top M: M must be in 1..%d\n", SPH_DIAG_MAX_REGIONS); return 2; }
   const bool labelling = compSeen;
+  if (selSeen && (selEvery <= 0 || !selDir)) {
+    fprintf(stderr, "--select-every K (> 0) and --select-out DIR go together (the other --select options need both)\n");
+    return 2;
+  }
+  if (selTypesSeen && !selMask) { fprintf(stderr, "--select-types needs at least one type\n"); return 2; }
+  if (!selMask) selMask = 1u << SPH_LIQUID_PARTICLE;
+  if (selTerms.size() > SPH_SELECT_MAX_TERMS) { fprintf(stderr, "at most %d terms (--select-term, --select-surface)\n", SPH_SELECT_MAX_TERMS); return 2; }
+  for (const sph_select_term& t : selTerms)
+    if (std::isnan(t.lo) || std::isnan(t.hi) || !(t.lo < t.hi)) { fprintf(stderr, "a selection term needs LO < HI, both numbers\n"); return 2; }
+  for (float b : selRegion)
+    if (std::isnan(b)) { fprintf(stderr, "--select-region: a bound is not a number\n"); return 2; }
+  const bool selecting = selSeen;
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -232,6 +280,7 @@ int main(int argc, char** argv) {
     std::vector<int32_t> compRootCount, compIds;
     std::vector<float> compBbox;
     std::vector<double> compRecords;
+    std::vector<int32_t> selIndex; std::vector<uint32_t> selIds; std::vector<float> selRecords;
     if (labelling) {
       compCsv = fopen(compFile, "w");
       if (!compCsv) throw std::runtime_error(std::string("cannot write ") + compFile);
@@ -360,6 +409,20 @@ int main(int argc, char** argv) {
                  largest, (long long)counts[0] - largest);
         }
         helper.report("_components: \t\t%9.3f ms\n");
+      }
+      if (selecting && (iterationCount + 1) % selEvery == 0) {
+        const int64_t n = ocl_solver->selectParticles(selRegionSeen ? selRegion : nullptr, selMask, selTerms.data(), (int)selTerms.size());
+        selIndex.resize((size_t)n); selIds.resize((size_t)n); selRecords.resize((size_t)n * SPH_SELECT_WORDS);
+        ocl_solver->readSelection(selIndex.data(), selIds.data(), selRecords.data());
+        const std::string path = std::string(selDir) + "/selection_" + std::to_string(iterationCount + 1) + ".bin";
+        FILE* f = fopen(path.c_str(), "wb");  // little-endian host
+        bool ok = f && fwrite(&n, sizeof(n), 1, f) == 1 && fwrite(selIndex.data(), sizeof(int32_t), selIndex.size(), f) == selIndex.size() &&
+                  fwrite(selIds.data(), sizeof(uint32_t), selIds.size(), f) == selIds.size() &&
+                  fwrite(selRecords.data(), sizeof(float), selRecords.size(), f) == selRecords.size();
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) throw std::runtime_error("cannot write " + path);
+        if (!quiet) printf("_select: selected %lld of %d\n", (long long)n, cfg.particleCount);
+        helper.report("_select: \t\t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

@@ -21,6 +21,9 @@ DIAG_WORDS = 32  # sph_diagnostics record (frames.DIAG_FIELDS)
 DIAG_MAX_REGIONS = 16
 HIST_MAX_BINS = 4096
 HIST_FIELDS = ("density", "speed", "pressure", "neighbors", "x", "y", "z")  # sph_histogram field numbers 0..6
+SELECT_WORDS = 12  # sph_read_selection record: x, y, z, type, vx, vy, vz, rho, p, neighbour count, surface measure, 0 (frames.SELECT_FIELDS)
+SELECT_MAX_TERMS = 4
+SELECT_FIELDS = HIST_FIELDS + ("surface",)  # sph_select_particles term fields 0..7
 GRADIENT_WORDS = 32  # sph_sample_gradient_* record: the sample record, then gradients, vorticity, divergence, Q (frames.GRADIENT_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
@@ -49,6 +52,10 @@ class SphSlab(C.Structure):
 
 SLAB_RECORD_WORDS = 9
 SLAB_COMPACT_WORDS = 7  # x, y, z, vx, vy, vz, global id (sph_slab_set_record_format)
+
+
+class SphSelectTerm(C.Structure):
+    _fields_ = [("field", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
 
 
 class SphError(RuntimeError):
@@ -108,7 +115,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
-                    "sph_read_components", "sph_component_diagnostics"] + _STAGE_FUNCS
+                    "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
+                    "sph_read_selection"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -198,6 +206,9 @@ def device_lib():
         L.sph_label_components.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
         L.sph_read_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sph_component_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.sph_particle_measure.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_select_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.sph_read_selection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -644,6 +655,55 @@ class owHIPSolver:
         out = np.zeros((max(comp.size, 1), DIAG_WORDS), np.float64)
         self._chk(self._L.sph_component_diagnostics(self._h, _ptr(comp) if comp.size else None, comp.size, _ptr(out)))
         return out[:comp.size]
+
+    # --- particle selection (sph_particle_measure / sph_select_particles / sph_read_selection) ---
+    def particle_measure(self):
+        """float32[N], sorted order: the surface measure of every particle, the distance to the kernel-weighted centroid of the
+        neighbours the last step used, in units of h (0 in a symmetric neighbourhood, 1 without neighbours; include/sphmi.h)."""
+        out = np.empty(self.N, np.float32)
+        self._chk(self._L.sph_particle_measure(self._h, _ptr(out)))
+        return out
+
+    def select(self, region=None, types=(1, 2), terms=(), component=None):
+        """Select particles on the device: those diagnostics() selects for `region` and `types` that also satisfy every term
+        (field, lo, hi) -- lo <= q < hi in float32, field a name from SELECT_FIELDS (HIST_FIELDS plus "surface", the
+        particle_measure() value) or 0..7, +-inf allowed -- and, if `component` is given, belong to that component of the last
+        label_components(). Returns the number selected; selection() reads them back. Up to 4 terms."""
+        rg = None
+        if region is not None:
+            rg = np.ascontiguousarray(region, np.float32)
+            if rg.size != 6:
+                raise SphError("select: region must be (x0, y0, z0, x1, y1, z1)")
+        terms = list(terms)
+        arr = (SphSelectTerm * max(len(terms), 1))()
+        for k, (field, lo, hi) in enumerate(terms):
+            if isinstance(field, str):
+                if field not in SELECT_FIELDS:
+                    raise SphError("select: field must be one of %s" % (SELECT_FIELDS,))
+                field = SELECT_FIELDS.index(field)
+            arr[k].field, arr[k].lo, arr[k].hi = int(field), float(np.float32(lo)), float(np.float32(hi))
+        count = np.zeros(1, np.int64)
+        self._selected = 0  # (a failed selection leaves none behind)
+        self._chk(self._L.sph_select_particles(self._h, _ptr(rg), type_mask(types), C.cast(arr, C.c_void_p) if terms else None,
+                                               len(terms), -1 if component is None else int(component), _ptr(count)))
+        self._selected = int(count[0])
+        return self._selected
+
+    def select_surface(self, threshold=0.10, types=(1,)):
+        """select() of the particles of `types` whose surface measure is at least `threshold` (the free surface of the liquid
+        by default). 0.10 separates the outermost layer of a resting lattice from its interior; it is not calibrated for
+        disordered flows -- look at particle_measure() first."""
+        return self.select(types=types, terms=(("surface", threshold, np.inf),))
+
+    def selection(self):
+        """The last select(): (sorted_index int32[n] ascending, orig_id uint32[n], records float32[n, 12] named by
+        frames.SELECT_FIELDS). Refused once the solver has stepped since the selection."""
+        n = getattr(self, "_selected", 0)  # 0 without a selection: the library reports SPH_ERR_ORDER
+        idx = np.empty(n, np.int32)
+        ids = np.empty(n, np.uint32)
+        rec = np.empty((n, SELECT_WORDS), np.float32)
+        self._chk(self._L.sph_read_selection(self._h, _ptr(idx) if n else None, _ptr(ids) if n else None, _ptr(rec) if n else None))
+        return idx, ids, rec
 
     # --- extras ---
     def step(self, iterationCount=0):

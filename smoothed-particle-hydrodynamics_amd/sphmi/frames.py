@@ -26,6 +26,10 @@ Connected components (owHIPSolver.label_components / components / component_diag
 into sizes and masses, `labels_in_original_order` maps the sorted-order labels to the particles' original order so that
 `write_vtk` / `write_npz` can store a label beside each particle (`labels=`), and `write_components_csv` /
 `read_components_csv` write and read the table `sphmi_run --components-out` writes.
+
+Selections (owHIPSolver.select / selection, float32[n, 12] records named by SELECT_FIELDS): `write_vtk_selection` writes the
+selected particles as a point cloud with everything a record holds as point data, `write_npz(selection=...)` stores one beside a
+frame, and `write_selection` / `read_selection` write and read the files `sphmi_run --select-out` writes.
 """
 import numpy as np
 
@@ -64,9 +68,15 @@ def density_colour(rho, rho0):
     return rgb  # like glColor4f, components outside [0,1] are left to the consumer to clamp
 
 
-def write_npz(path, position, density, step=None, labels=None):
-    """`labels`: optional component label per particle in orig order (labels_in_original_order), stored as int32 `component`."""
+def write_npz(path, position, density, step=None, labels=None, selection=None):
+    """`labels`: optional component label per particle in orig order (labels_in_original_order), stored as int32 `component`.
+    `selection`: optional (sorted_index, orig_id, records) of owHIPSolver.selection(), stored as `selection_index`,
+    `selection_id` and `selection_records`."""
     extra = {} if labels is None else {"component": np.asarray(labels, np.int32)}
+    if selection is not None:
+        idx, ids, rec = selection
+        extra.update(selection_index=np.asarray(idx, np.int32), selection_id=np.asarray(ids, np.uint32),
+                     selection_records=np.asarray(rec, np.float32).reshape(-1, len(SELECT_FIELDS)))
     np.savez_compressed(path, position=np.asarray(position, np.float32), density=np.asarray(density, np.float32),
                         step=np.int64(-1 if step is None else step), **extra)
 
@@ -399,3 +409,71 @@ def read_components_csv(path):
     bb = np.array([[float(x) for x in r[4:10]] for r in rows], np.float64).astype(np.float32).reshape(K, 6)
     rec = np.array([[float(x) for x in r[10:]] for r in rows], np.float64).reshape(K, len(DIAG_FIELDS))
     return steps, ids, rc, bb, rec
+
+
+# ---- particle selection (owHIPSolver.select / selection; include/sphmi.h, sph_select_particles) ----
+SELECT_FIELDS = ("x", "y", "z", "type", "vx", "vy", "vz", "density", "pressure", "neighbors", "surface", "unused11")
+
+
+def write_vtk_selection(path, records, orig_id):
+    """Legacy-VTK polydata (binary, big-endian like write_vtk) of a selection: one point per record with `type`, `density`,
+    `pressure`, `neighbors`, `surface` (float scalars), `id` (int, the original particle id) and `velocity` (vectors)."""
+    rec = np.asarray(records, np.float32).reshape(-1, len(SELECT_FIELDS))
+    ids = np.asarray(orig_id, np.uint32).reshape(-1)
+    if ids.shape[0] != rec.shape[0]:
+        raise ValueError("write_vtk_selection: one id per record expected")
+    n = rec.shape[0]
+    w = SELECT_FIELDS.index
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi selection\nBINARY\nDATASET POLYDATA\n")
+        f.write(("POINTS %d float\n" % n).encode())
+        f.write(rec[:, :3].astype(">f4").tobytes())
+        f.write(("\nVERTICES %d %d\n" % (n, 2 * n)).encode())
+        cells = np.empty((n, 2), ">i4")
+        cells[:, 0] = 1
+        cells[:, 1] = np.arange(n)
+        f.write(cells.tobytes())
+        f.write(("\nPOINT_DATA %d\n" % n).encode())
+        for name in ("type", "density", "pressure", "neighbors", "surface"):
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(rec[:, w(name)]).astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(b"SCALARS id int 1\nLOOKUP_TABLE default\n")
+        f.write(ids.astype(">i4").tobytes())
+        f.write(b"\nVECTORS velocity float\n")
+        f.write(np.ascontiguousarray(rec[:, w("vx"):w("vz") + 1]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return n
+
+
+def write_selection(path, sorted_index, orig_id, records):
+    """The file `sphmi_run --select-out` writes, little-endian: the count n as int64, then n int32 sorted indices, n uint32
+    original ids and n x 12 float32 records."""
+    idx = np.ascontiguousarray(sorted_index, "<i4").reshape(-1)
+    ids = np.ascontiguousarray(orig_id, "<u4").reshape(-1)
+    rec = np.ascontiguousarray(records, "<f4").reshape(-1, len(SELECT_FIELDS))
+    if not (idx.shape[0] == ids.shape[0] == rec.shape[0]):
+        raise ValueError("write_selection: the three arrays must have one entry per selected particle")
+    with open(path, "wb") as f:
+        f.write(np.array([idx.shape[0]], "<i8").tobytes())
+        f.write(idx.tobytes())
+        f.write(ids.tobytes())
+        f.write(rec.tobytes())
+    return idx.shape[0]
+
+
+def read_selection(path):
+    """(sorted_index int32[n], orig_id uint32[n], records float32[n, 12]) of a file written by write_selection or
+    `sphmi_run --select-out`."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 8:
+        raise ValueError("%s: not a selection file" % path)
+    n = int(np.frombuffer(data, "<i8", 1, 0)[0])
+    W = len(SELECT_FIELDS)
+    if n < 0 or len(data) != 8 + n * (8 + 4 * W):
+        raise ValueError("%s: %d bytes do not hold %d selected particles" % (path, len(data), n))
+    idx = np.frombuffer(data, "<i4", n, 8).astype(np.int32)
+    ids = np.frombuffer(data, "<u4", n, 8 + 4 * n).astype(np.uint32)
+    rec = np.frombuffer(data, "<f4", n * W, 8 + 8 * n).astype(np.float32).reshape(n, W)
+    return idx, ids, rec
