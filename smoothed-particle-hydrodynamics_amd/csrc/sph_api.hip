@@ -25,27 +25,11 @@ void sph_set_error(const char* fmt, ...) {
 extern "C" const char* sph_last_error(void) { return g_err; }
 extern "C" int sph_abi_version(void) { return SPHMI_ABI_VERSION; }
 
-// What this binary was built as. Diagnostic / timing-only variants (make variant EXTRA=-D...) compute INVALID results; a
-// benchmark must not load one unnoticed (bench.py prints this string and refuses a build whose info contains "DIAG").
+// What this binary was built as: the product, or a variant of it (make variant NAME=... EXTRA=-D...); bench.py prints this string.
 extern "C" const char* sph_build_info(void) {
   return "libsphmi gfx950 abi " SPH_STR(SPHMI_ABI_VERSION)
-#ifdef DIAG_OWN_GATHER
-         " DIAG_OWN_GATHER(invalid results)"
-#endif
-#ifdef DIAG_NO_WALK
-         " DIAG_NO_WALK(invalid results)"
-#endif
-#ifdef DIAG_DENSITY_INTO_REC
-         " DIAG_DENSITY_INTO_REC(invalid results)"
-#endif
-#ifdef DIAG_NO_REPLAY
-         " DIAG_NO_REPLAY(invalid results)"
-#endif
 #ifdef FN_STAMPS
          " FN_STAMPS"
-#endif
-#ifdef NO_XCD_REMAP
-         " NO_XCD_REMAP"
 #endif
 #ifdef SPH_VARIANT
          " variant:" SPH_STR(SPH_VARIANT)

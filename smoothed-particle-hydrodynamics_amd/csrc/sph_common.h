@@ -175,6 +175,16 @@ __device__ __forceinline__ bool sph_range_id(const SphDev& d, int linear, int& i
   id = begin + linear;
   return id < end;
 }
+
+// XCD-aware block order: the hardware deals consecutive workgroups round-robin over the 8 XCDs; remapped, each XCD works on
+// one contiguous eighth of the blocks (of the sorted particle range), and its L2 holds only that slab's neighbourhood.
+__device__ __forceinline__ int xcd_block(int nblocks) {
+  const int b = blockIdx.x;
+  const int per = nblocks >> 3;  // blocks per XCD in the evenly divisible part
+  const int even = per << 3;
+  if (b >= even) return b;       // tail blocks keep their index
+  return (b & 7) * per + (b >> 3);
+}
 #endif
 
 

@@ -21,6 +21,7 @@
 // parent[r] == r, so it fails, and is retried from the value it returns, if r has stopped being a root.
 // Every pointer walk and every retry loop is bounded by N + 1 steps; an overrun sets err[0] instead of spinning.
 #include "sph_common.h"
+#include "sph_row_walk.h"
 
 #include <algorithm>
 
@@ -42,16 +43,6 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_init(SphDev d, uint32_t typeMa
   parent[j] = cc_selected(d, typeMask, j, d.sortedPos[j]) ? j : -1;
 }
 
-#ifndef CC_HALVE
-#define CC_HALVE 2  // path halving in find: 2 = atomic minimum, 1 = atomic store, 0 = none
-#endif
-#ifndef CC_PRELINK
-#define CC_PRELINK 1  // 1: before hooking, every particle points at the smallest linked neighbour below it
-#endif
-#ifndef CC_COMPRESS
-#define CC_COMPRESS 1  // 1: ... and the chains that makes are shortened by pointer jumping
-#endif
-
 // Root of x's tree as far as this lane can see it (a value that was a root when it was read). Path halving: parent[x] moves to
 // its grandparent by an atomic minimum, so that a slower lane's older value never moves it back up.
 __device__ __forceinline__ int cc_find(int32_t* parent, int x, int limit, uint32_t* err) {
@@ -59,11 +50,7 @@ __device__ __forceinline__ int cc_find(int32_t* parent, int x, int limit, uint32
   int p = cc_load(parent + x);
   while (p != x) {
     const int g = cc_load(parent + p);
-#if CC_HALVE == 2
     if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#elif CC_HALVE == 1
-    if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     x = p;
     p = g;
     if (++steps > limit) { atomicOr(err, 1u); break; }
@@ -87,61 +74,31 @@ __device__ __forceinline__ int cc_union(int32_t* parent, int i, int j, int limit
   return a;
 }
 
-// XCD-aware block order (as the gather kernels): each XCD works on one contiguous eighth of the sorted range, so that the parent
-// lines its finds walk stay in that XCD's L2.
-__device__ __forceinline__ int cc_block(int nblocks) {
-  const int b = blockIdx.x;
-  const int per = nblocks >> 3, even = per << 3;
-  if (b >= even) return b;
-  return (b & 7) * per + (b >> 3);
-}
-
 // fn(j) for every entry j of selected particle i's row that is an edge of the contract (j selected, j != i, r2 < link2 if FINITE)
 template <bool FINITE, typename F>
 __device__ __forceinline__ void cc_for_each_edge(const SphDev& d, float link2, const int32_t* parent, int i, F fn) {
   float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
   if (FINITE) pi = d.sortedPos[i];
-  const size_t base = ((size_t)(i >> 6) * 8) * 64 + (size_t)(i & 63);
-  typedef unsigned int nt2 __attribute__((ext_vector_type(2)));
-  typedef int nt4 __attribute__((ext_vector_type(4)));
-  const nt2* v16 = reinterpret_cast<const nt2*>(d.nbr16) + base;
-  const nt4* v32 = reinterpret_cast<const nt4*>(d.nbrId) + base;
-  const nt2 first = __builtin_nontemporal_load(v16);  // the rows are streamed once
-  const bool wide = (first.x & 0xffffu) == SPH_N16_WIDE;
-  const int zBase = wide ? 0 : d.nbrBase[i];
-#pragma unroll 2
-  for (int g = 0; g < 8; g++) {
-    int nb[4];
-    if (wide) {
-      const nt4 q = __builtin_nontemporal_load(v32 + (size_t)g * 64);
-      nb[0] = q.x; nb[1] = q.y; nb[2] = q.z; nb[3] = q.w;
-    } else {
-      const nt2 q = g == 0 ? first : __builtin_nontemporal_load(v16 + (size_t)g * 64);
-      const uint32_t e[4] = {q.x & 0xffffu, q.x >> 16, q.y & 0xffffu, q.y >> 16};
-#pragma unroll
-      for (int k = 0; k < 4; k++) nb[k] = e[k] == SPH_N16_EMPTY ? -1 : ((e[k] & 0x8000u) ? zBase : i) + (int)(e[k] & 0x7fffu) - SPH_N16_BIAS;
+  sph_row_for_each_slot(d, i, [&](int j) {
+    if (j < 0 || j >= d.N || j == i) return;
+    if (cc_load(parent + j) < 0) return;  // not selected (-1 never changes)
+    if (FINITE) {
+      const float4 pj = d.sortedPos[j];
+      const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+      const float r2 = dx * dx + dy * dy + dz * dz;
+      if (!(r2 < link2)) return;
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int j = nb[k];
-      if (j < 0 || j >= d.N || j == i) continue;
-      if (cc_load(parent + j) < 0) continue;  // not selected (-1 never changes)
-      if (FINITE) {
-        const float4 pj = d.sortedPos[j];
-        const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-        const float r2 = dx * dx + dy * dy + dz * dz;
-        if (!(r2 < link2)) continue;
-      }
-      fn(j);
-    }
-  }
+    fn(j);
+  });
 }
 
+// (The kernels that walk `parent` take their blocks in XCD order — xcd_block, sph_common.h — so that the parent lines their finds
+// walk stay in one XCD's L2.)
 // Before any hook: parent[i] = the smallest particle below i that i's own row links it to (or i). A forest already (parent[i] <= i,
 // same set), written without atomics: only lane i writes entry i here, and other lanes only test the sign of what they read.
 template <bool FINITE>
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_prelink(SphDev d, float link2, int32_t* parent) {
-  const int i = cc_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
+  const int i = xcd_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
   if (i >= d.N) return;
   if (cc_load(parent + i) < 0) return;
   int m = i;
@@ -154,7 +111,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_prelink(SphDev d, float link2,
 // chain of length L is gone after about log2(L) rounds (the sorted order follows the cells, so the chains of a long box run
 // hundreds of cell layers deep).
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_compress(int N, int32_t* parent, uint32_t* err) {
-  const int i = cc_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
+  const int i = xcd_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
   if (i >= N) return;
   int p = cc_load(parent + i);
   if (p < 0) return;
@@ -169,7 +126,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_compress(int N, int32_t* paren
 
 template <bool FINITE>
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_hook(SphDev d, float link2, int32_t* parent, uint32_t* err) {
-  const int i = cc_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
+  const int i = xcd_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
   if (i >= d.N) return;
   if (cc_load(parent + i) < 0) return;
   int mine = i;  // a member of i's set, as close to its root as this lane has seen: where the next find for i starts
@@ -179,7 +136,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_hook(SphDev d, float link2, in
 // Read-only walk to the root, then one store to the particle's own entry. Another lane that passes through this entry meanwhile
 // reads either the old value or the root: both are members of the set that are not larger than the entry's index.
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_flatten(int N, int32_t* parent, uint32_t* err) {
-  const int j = cc_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
+  const int j = xcd_block(gridDim.x) * SPH_BLOCK + threadIdx.x;
   if (j >= N) return;
   int x = cc_load(parent + j);
   if (x < 0) return;
@@ -421,15 +378,11 @@ int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float li
   if (N > 0) {
     hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, typeMask, parent);
     SPH_HIP(hipGetLastError());
-#if CC_PRELINK
     if (finite) hipLaunchKernelGGL(k_cc_prelink<true>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent);
     else hipLaunchKernelGGL(k_cc_prelink<false>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent);
     SPH_HIP(hipGetLastError());
-#if CC_COMPRESS
     hipLaunchKernelGGL(k_cc_compress, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, err);
     SPH_HIP(hipGetLastError());
-#endif
-#endif
     if (finite) hipLaunchKernelGGL(k_cc_hook<true>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent, err);
     else hipLaunchKernelGGL(k_cc_hook<false>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent, err);
     SPH_HIP(hipGetLastError());

@@ -7,9 +7,9 @@
 //
 // MI355X design. The reference walks ~640 candidates twice per particle and does the expensive part
 // (sqrt, IEEE divide, histogram / store) under a branch that ~7 % of the lanes take but ~99 % of the waves execute.
-// Here a 256-thread workgroup owns 128 consecutive sorted particles, TWO lanes per particle (FN_LANES; four were measured:
-// slower), stages the <= 9 contiguous runs of sorted particles that can contain their candidates (cells are contiguous along x
-// in the sorted order) into LDS once as SoA x/y/z, and each lane
+// Here a 256-thread workgroup owns 128 consecutive sorted particles, TWO lanes per particle (four were measured: slower),
+// stages the <= 9 contiguous runs of sorted particles that can contain their candidates (cells are contiguous along x in the
+// sorted order) into LDS once as SoA x/y/z, and each lane
 //   1. walks four of the particle's 8 cells ONCE (~280 candidates), four candidates per trip (16-byte aligned LDS reads,
 //      packed-f32 math, next quad prefetched), with the cheap filter d^2 <= max(h, 31h/30)^2 — a superset of both reference
 //      passes — and appends the LDS slot of every hit to a private u16 list in LDS (~20 of ~280 survive),
@@ -27,7 +27,6 @@
 #include <string.h>
 
 #include <mutex>
-#include <type_traits>
 
 #include "sph_common.h"
 
@@ -68,31 +67,17 @@ __device__ __forceinline__ int wrap_cell(int c, int G) {  // searchCell, sphFlui
   return c;
 }
 
-#ifndef FN_PART
-#define FN_PART 128               // particles per workgroup (A/B: 256 particles / 512 threads / one workgroup per CU)
-#endif
-#ifndef FN_LANES
-#define FN_LANES 2                // lanes per particle: 2 (a pair; whole cells) or 4 (a DPP quad: pairs x cell halves). A/B on MI355X,
-#endif                            // config #2: 2 lanes 0.44 ms, 4 lanes 0.58 ms (more waves per SIMD, but 30 % more instructions)
-#define FN_LOG_LANES (FN_LANES == 4 ? 2 : 1)
-#define FN_THREADS (FN_LANES * FN_PART)
-#define FN_PER_WAVE (64 / FN_LANES)  // particles per wave
+#define FN_PART 128               // particles per workgroup: two workgroups of 256 threads per CU (one of 512 is slower)
+#define FN_THREADS (2 * FN_PART)  // two lanes per particle
+#define FN_PER_WAVE 32            // particles per wave
 #define FN_WAVES (FN_THREADS / 64)
-#ifndef FN_CAND_CAP
 #define FN_CAND_CAP 4096          // staged candidates per workgroup (SoA x/y/z: 48 KB; + lists 24 KB -> two workgroups per CU)
-#endif
-#ifndef FN_STAGE_PER
-#define FN_STAGE_PER 8           // candidate records per thread and staging round, all loads of a round in flight (A/B: 8 0.429, 12 0.440, 16 0.436 ms)
-#endif
+#define FN_STAGE_PER 8            // candidate records per thread and staging round, all loads of a round in flight together
 #define FN_WIN 16                 // cell-table window per row: covers batches that span up to 13 cells (else: direct table reads)
 #define FN_CAND_PAD 16            // the aligned, prefetching 4-wide walk reads (never uses) up to 15 slots past a piece
-#ifndef FN_LIST_CAP
-#define FN_LIST_CAP (96 / FN_LANES)  // compaction list entries per lane (u16 [entry][lane]); 96 per particle
-#endif
-#ifndef FN_CHUNK
-#define FN_CHUNK 8                 // list entries per wave-uniform skip test in the replay loops (A/B: 8 0.419 ms, 4 0.445 ms)
-#endif
-#define FN_SLOTS_PER_LANE (SPH_MAXN / FN_LANES)  // map slots every lane of a particle finishes (square root + store)
+#define FN_LIST_CAP 48            // compaction list entries per lane (u16 [entry][lane]); 96 per particle
+#define FN_CHUNK 8                // list entries per wave-uniform skip test in the replay loops
+#define FN_SLOTS_PER_LANE (SPH_MAXN / 2)  // map slots every lane of a particle finishes (square root + store)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -116,17 +101,11 @@ struct FnShared {
 #endif
 };
 static_assert(FN_LIST_ROWS >= FN_LIST_CAP, "the wave's list area holds the lists first, the staging of the store phase afterwards");
-static_assert(FN_LANES == 2 || FN_LANES == 4, "two or four lanes per particle");
 
-// DPP moves inside a quad (4 consecutive lanes = the lanes of one particle): value of lane (l ^ 1), (l ^ 2)
-__device__ __forceinline__ int quad_xor1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true); }  // quad_perm [1,0,3,2]
-__device__ __forceinline__ int quad_xor2(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true); }  // quad_perm [2,3,0,1]
-// the lanes of one particle: value held by the lane of the OTHER PAIR (same half) / by the lane of the other HALF (same pair; none with two lanes)
-__device__ __forceinline__ int grp_other_pair(int v) { return FN_LANES == 4 ? quad_xor2(v) : quad_xor1(v); }
-__device__ __forceinline__ int grp_other_half(int v) { return FN_LANES == 4 ? quad_xor1(v) : 0; }
-typedef typename std::conditional<(FN_LIST_CAP > 32), unsigned long long, uint32_t>::type fn_mask_t;  // one bit per list entry
-__device__ __forceinline__ int fn_popc(uint32_t v) { return __popc(v); }
-__device__ __forceinline__ int fn_popc(unsigned long long v) { return __popcll(v); }
+// DPP move inside the pair of lanes that serves one particle: the value held by the other lane (l ^ 1)
+__device__ __forceinline__ int pair_other(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true); }  // quad_perm [1,0,3,2]
+typedef unsigned long long fn_mask_t;  // one bit per list entry
+static_assert(FN_LIST_CAP <= 64, "one bit per list entry");
 
 // d.dbg layout: [0] particles handed to the exact wave-per-particle walk because a cell was not staged, [1] because a list
 // overflowed, [2] rows without a 16-bit copy because an offset was out of range, [3] candidate runs dropped for LDS capacity;
@@ -173,9 +152,7 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
       hi[k] = (int)g.cellStart[c + 1];
       if (hi[k] - lo[k] > (1 << 20)) hi[k] = lo[k];  // a million particles in one cell: a blown-up state (counted by k_hash); do not walk it
       ldsBase[k] = -1;
-#ifndef FN_EXACT_GLOBAL
       if (r >= 0 && hi[k] > lo[k] && lo[k] >= sh.rowLo[r] && hi[k] <= sh.rowHi[r]) ldsBase[k] = sh.rowBase[r] + (lo[k] - sh.rowLo[r]);
-#endif
     }
   }
   if (lane < 32) sh.hist[wave][lane] = 0u;
@@ -241,17 +218,16 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
   if (lane == 0) g.nbr16[nbr_index(id, 0)] = (uint16_t)SPH_N16_WIDE;  // no 16-bit copy of this row: readers take the 32-bit ids
 }
 
-// Quad (4p .. 4p+3) serves particle p. Lanes 0,1 (pair A) walk the cells k = 0,5,6,7 of the reference's order and lanes 2,3
-// (pair B) the cells 1,2,3,4; inside a pair, lane `sub` = 0 takes the first half of every cell (in sorted-index order) and
-// lane 1 the second half. The merged traversal order is therefore
-//   A0.0 A0.1 | B1.0 B1.1 B2.0 B2.1 B3.0 B3.1 B4.0 B4.1 | A5.0 A5.1 A6.0 A6.1 A7.0 A7.1
-// and four per-piece hit counts per lane (one packed word, two DPP moves) place every neighbour in the reference's slot.
-// Pair A gets 54 % of the hits (own cell ~42 %, edges 5 % each, corner 2 %), pair B 46 % (faces ~14 % each, one edge).
+// The lane pair (2p, 2p+1) serves particle p. Lane A (even) walks the cells k = 0,5,6,7 of the reference's order and lane B (odd)
+// the cells 1,2,3,4, each cell whole, in sorted-index order. The merged traversal order is therefore
+//   A0 | B1 B2 B3 B4 | A5 A6 A7
+// and four per-cell hit counts per lane (one packed word, one DPP move) place every neighbour in the reference's slot.
+// Lane A gets 54 % of the hits (own cell ~42 %, edges 5 % each, corner 2 %), lane B 46 % (faces ~14 % each, one edge).
 //
 // Synchronisation: ONE workgroup barrier per batch, between the staging of the candidates and their use. Everything before it
 // (batch bounds, the 9 candidate runs, their LDS layout) is computed redundantly by every wave from loads with workgroup-uniform
 // addresses, everything after it is private to a wave (its lists, its d^2 staging area, the exact walks of its own particles).
-__global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1 : 2))) void k_find_neighbors(FnParams d, const float4* __restrict__ sortedPos,
+__global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, const float4* __restrict__ sortedPos,
                                                                    const uint32_t* __restrict__ keys,
                                                                    const uint32_t* __restrict__ cellStart,
                                                                    const float* __restrict__ binU, int32_t* __restrict__ nbrId,
@@ -261,8 +237,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   extern __shared__ __align__(16) unsigned char fn_smem[];
   FnShared& sh = *reinterpret_cast<FnShared*>(fn_smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = tid >> FN_LOG_LANES, quadLane = tid & (FN_LANES - 1);  // quadLane: lane inside the particle's group
-  const int pairB = FN_LANES == 4 ? quadLane >> 1 : quadLane, sub = FN_LANES == 4 ? (quadLane & 1) : 0;
+  const int p = tid >> 1, laneB = tid & 1;  // the particle; 0: its lane A, 1: its lane B
   const int rangeBegin = (int)cellStart[d.rangeLo], rangeEnd = (int)cellStart[d.rangeHi];  // all particles, or fewer ghost layers
   // (an XCD-aware tile order — each XCD one contiguous eighth of the tiles — was measured: 0.441 vs 0.430 ms on config #2, no change at 16.5 M)
   const int p0 = rangeBegin + blockIdx.x * FN_PART;
@@ -355,7 +330,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   if (tid >= 192 && tid < 256) sh.binU[tid - 192] = binU[tid - 192];
   FN_STAMP(0)
   {
-    constexpr int PER = FN_LANES == 4 ? 6 : FN_STAGE_PER;  // records per thread and round, all loads of a round in flight together
+    constexpr int PER = FN_STAGE_PER;
 #pragma unroll 1
     for (int f0 = 0; f0 < total; f0 += PER * FN_THREADS) {
       float4 rec[PER];
@@ -379,7 +354,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   const bool mine_now = alive && id >= batchLo && id < batchHi;  // this lane's particle belongs to the current batch
   bool slow = false;
 
-  if (mine_now) {  // (whole quads: the four lanes of a particle agree)
+  if (mine_now) {  // (whole pairs: the two lanes of a particle agree)
   // (opaque to the optimiser: everything derived from the particle's record is otherwise hoisted out of the batch loop,
   // which runs once for almost every workgroup, and then spilled)
   float4 me = myPos;
@@ -387,7 +362,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   asm volatile("" : "+v"(me.x), "+v"(me.y), "+v"(me.z), "+v"(myCellNow), "+v"(idNow));
   int pLo[4], pHi[4], absDelta[4];  // this lane's four pieces as LDS slot ranges; sorted index = LDS slot + absDelta
   int selfSlot = -1;
-  int zLoMine = 0;  // pair B: first sorted index of cell 3, the z neighbour (base of the flagged 16-bit offsets)
+  int zLoMine = 0;  // lane B: first sorted index of cell 3, the z neighbour (base of the flagged 16-bit offsets)
   {  // the lane's four cells (sphFluid.cl:253-308) with the cell table read from the LDS window where possible
     const float px = me.x - d.xmin, py = me.y - d.ymin, pz = me.z - d.zmin;
     const float cfx = (float)(int)(me.x * d.cellSizeInv) * d.cellSize;
@@ -398,10 +373,10 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
     const int dz = ((pz - cfz) < d.h) ? -1 : 1;
     const int sy = dy * d.gx, sz = dz * d.gx * d.gy;
     const int ry = dy + 1, rz = dz + 1;  // staged-row ids: row = (y step + 1) + 3 * (z step + 1)
-    // pair A: cells 0 (own), 5 (xz), 6 (yz), 7 (xyz); pair B: cells 1 (x), 2 (y), 3 (z), 4 (xy)
-    const bool stepX[4] = {pairB != 0, pairB == 0, false, true};
-    const bool stepY[4] = {false, pairB != 0, pairB == 0, true};
-    const bool stepZ[4] = {false, pairB == 0, true, pairB == 0};
+    // lane A: cells 0 (own), 5 (xz), 6 (yz), 7 (xyz); lane B: cells 1 (x), 2 (y), 3 (z), 4 (xy)
+    const bool stepX[4] = {laneB != 0, laneB == 0, false, true};
+    const bool stepY[4] = {false, laneB != 0, laneB == 0, true};
+    const bool stepZ[4] = {false, laneB == 0, true, laneB == 0};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int xs = stepX[i] ? dx : 0;
@@ -425,30 +400,23 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
         if (staged && lo >= sh.rowLo[row] && hi <= sh.rowHi[row]) base = sh.rowBase[row] + (lo - sh.rowLo[row]);
         else slow = true;  // a non-empty cell of this particle is not in LDS
       }
-      // halves (four lanes per particle): the split point is rounded to a 16-byte boundary of the SoA arrays so the second
-      // half starts aligned; with two lanes per particle a lane walks whole cells
-      const int mid = FN_LANES == 4 ? min(base + n, max(base, (base + (n >> 1) + 2) & ~3)) : base + n;
-      pLo[i] = sub ? mid : base;
-      pHi[i] = sub ? base + n : mid;
+      pLo[i] = base;
+      pHi[i] = base + n;
       absDelta[i] = lo - base;
       if (i == 2) zLoMine = lo;
-      if (i == 0 && pairB == 0) selfSlot = base + (idNow - lo);  // the particle itself sits in its own cell
+      if (i == 0 && laneB == 0) selfSlot = base + (idNow - lo);  // the particle itself sits in its own cell
     }
   }
-  {  // both pairs must agree (inside a pair the lanes see the same cells). The DPP move is executed by ALL four lanes — under a
-     // short-circuit `||` the lanes that are already slow would sit it out and their partners would read 0 from them.
-    const int otherPair = grp_other_pair((int)slow);
-    slow = slow || (otherPair != 0);
+  {  // both lanes must agree. The DPP move is executed by BOTH lanes — under a short-circuit `||` a lane that is already slow
+     // would sit it out and its partner would read 0 from it.
+    const int other = pair_other((int)slow);
+    slow = slow || (other != 0);
   }
   if (slow) {
 #pragma unroll
     for (int i = 0; i < 4; i++) pHi[i] = pLo[i];
-    if (quadLane == 0) atomicAdd(&dbg[0], 1u);
+    if (laneB == 0) atomicAdd(&dbg[0], 1u);
   }
-#ifdef DIAG_NO_WALK  // timing only: nothing is walked (every list stays empty)
-#pragma unroll
-  for (int i = 0; i < 4; i++) pHi[i] = pLo[i];
-#endif
   FN_STAMP(4)
 
   // ---- 1. single walk with the cheap filter; r_max covers pass 0 (h) and every possible pass-1 radius (<= 31h/30).
@@ -473,11 +441,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   asm volatile("" : "+s"(neg1s));  // (a scalar pair; held in a vector pair instead: the same time)
   const f32x2 neg1 = {neg1s, neg1s};
   uint16_t (*const myList)[64] = sh.list[wave];
-#ifdef FN_SUB_BY_ADD  // A/B: the differences as v_pk_add_f32 with negated operands (6.7 cycles each against 5.5 for v_pk_fma_f32)
-#define FN_DIFF(m, c) ((m) - (c))
-#else
 #define FN_DIFF(m, c) __builtin_elementwise_fma((c), neg1, (m))
-#endif
 #define FN_TEST(X, Y, Z)                                                                        \
   {                                                                                             \
     const f32x2 ex0 = FN_DIFF(mx, X.xy), ex1 = FN_DIFF(mx, X.zw), ey0 = FN_DIFF(my, Y.xy), ey1 = FN_DIFF(my, Y.zw); \
@@ -548,16 +512,10 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
 #undef FN_TEST
 #undef FN_FLUSH
   FN_STAMP(5)
-#ifdef DIAG_NO_REPLAY  // timing only: the lists are walked and then dropped (a 1-entry list per lane keeps the walk alive)
-  { const int keep = min(cnt, 1); cnt = keep;
-#pragma unroll
-    for (int i = 0; i < 4; i++) segEnd[i] = min(segEnd[i], keep); }
-#endif
   int over = cnt > FN_LIST_CAP ? 1 : 0;
-  over |= grp_other_half(over);  // all lanes of the particle take part
-  over |= grp_other_pair(over);
+  over |= pair_other(over);  // both lanes of the particle take part
   if (over) {
-    if (quadLane == 0 && !slow) atomicAdd(&dbg[1], 1u);
+    if (laneB == 0 && !slow) atomicAdd(&dbg[1], 1u);
     slow = true;
 #pragma unroll
     for (int i = 0; i < 4; i++) segEnd[i] = 0;
@@ -611,8 +569,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
         for (int u = 0; u < FN_CHUNK; u++) c += (d2v[c0 + u] < U) ? 1 : 0;
       }
     }
-    c += grp_other_half(c);
-    c += grp_other_pair(c);
+    c += pair_other(c);
     if (lo < hi) {
       if (c >= SPH_MAXN) { hi = mid; cAtHi = c; } else lo = mid + 1;
     }
@@ -621,7 +578,7 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
   const float r2 = sh.binU[32 + jb];  // r_thr^2 with r_thr = (float)(jb + 1) * h / 30 (sphFluid.cl:313-321), from the host
   FN_STAMP(7)
 
-  // ---- 2b. pass 1: hits with d^2 <= r_thr^2 as a bit mask; per-piece counts by popcount, exchanged inside the quad as one
+  // ---- 2b. pass 1: hits with d^2 <= r_thr^2 as a bit mask; per-piece counts by popcount, exchanged inside the pair as one
   // packed word; every hit goes to (hits in earlier pieces of the merged order) + (rank inside its piece). Slots >= 32
   // are dropped, which is what the reference's `break` / `spaceLeft` logic amounts to (sphFluid.cl:145,168-169).
   fn_mask_t acc = 0;
@@ -636,40 +593,38 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
 #pragma unroll
   for (int i = 0; i < 4; i++) below[i] = (segEnd[i] >= (int)(8 * sizeof(fn_mask_t))) ? ~(fn_mask_t)0 : (((fn_mask_t)1 << segEnd[i]) - 1);
   int mine[4];
-  mine[0] = fn_popc(acc & below[0]);
+  mine[0] = __popcll(acc & below[0]);
 #pragma unroll
-  for (int i = 1; i < 4; i++) mine[i] = fn_popc(acc & below[i] & ~below[i - 1]);
-  const int packed = mine[0] | (mine[1] << 8) | (mine[2] << 16) | (mine[3] << 24);  // each <= 48
-  const int partner = grp_other_half(packed);   // the other half of the same four cells (none with two lanes per particle)
-  const int cellTot = packed + partner;         // whole-cell counts of this pair (bytes <= 48: no carry)
-  const int otherTot = grp_other_pair(cellTot); // whole-cell counts of the other pair
-  const int zLoOther = grp_other_pair(zLoMine);  // (a DPP move: executed by all lanes of the particle)
+  for (int i = 1; i < 4; i++) mine[i] = __popcll(acc & below[i] & ~below[i - 1]);
+  const int cellTot = mine[0] | (mine[1] << 8) | (mine[2] << 16) | (mine[3] << 24);  // this lane's per-cell counts, each <= 48
+  const int otherTot = pair_other(cellTot);  // the other lane's
+  const int zLoOther = pair_other(zLoMine);  // (a DPP move: executed by both lanes of the particle)
   // (the wave's list area is free from here on: every lane has its slots in slotPk, and LDS operations of a wave retire in order)
   if (!slow) {
     const int c0b = cellTot & 255, c1b = (cellTot >> 8) & 255, c2b = (cellTot >> 16) & 255, c3b = (cellTot >> 24) & 255;
     const int o0b = otherTot & 255;
     const int sumOther = o0b + ((otherTot >> 8) & 255) + ((otherTot >> 16) & 255) + ((otherTot >> 24) & 255);
     const int run = min(c0b + c1b + c2b + c3b + sumOther, SPH_MAXN);
-    // pair A (cells 0 | 5 6 7): cell 0 starts at 0, cells 5.. after cell 0 and all of pair B;
-    // pair B (cells 1 2 3 4): starts after cell 0 (= pair A's first cell)
-    const int first = pairB ? o0b : 0, afterFirst = pairB ? 0 : sumOther;
+    // lane A (cells 0 | 5 6 7): cell 0 starts at 0, cells 5.. after cell 0 and all of lane B's;
+    // lane B (cells 1 2 3 4): starts after cell 0 (= lane A's first cell)
+    const int first = laneB ? o0b : 0, afterFirst = laneB ? 0 : sumOther;
     int start[4];
-    start[0] = first + (sub ? (partner & 255) : 0);
-    start[1] = first + c0b + afterFirst + (sub ? ((partner >> 8) & 255) : 0);
-    start[2] = first + c0b + afterFirst + c1b + (sub ? ((partner >> 16) & 255) : 0);
-    start[3] = first + c0b + afterFirst + c1b + c2b + (sub ? ((partner >> 24) & 255) : 0);
+    start[0] = first;
+    start[1] = first + c0b + afterFirst;
+    start[2] = first + c0b + afterFirst + c1b;
+    start[3] = first + c0b + afterFirst + c1b + c2b;
     // Ids go straight to the tiled map (4-byte stores); the d^2 of the accepted neighbours go to the wave's staging area
-    // [particle][slot], from which every lane of the quad then takes 8 consecutive slots: 8 square roots per lane instead of
-    // one per list entry, and the distances leave as two 16-byte stores per lane (which also write the -1 of the unused slots).
-    // The 16-bit copy of the row (sph_common.h, SPH_N16_*): offsets from the particle itself, or — cells one z layer away: pair A's
-    // 5 6 7, pair B's 3 — from the first particle of the z-neighbour cell. A piece's entries are its LDS slots + one constant, so
+    // [particle][slot], from which each lane of the pair then takes 16 consecutive slots: 16 square roots per lane instead of
+    // one per list entry, and the distances leave as four 16-byte stores per lane (which also write the -1 of the unused slots).
+    // The 16-bit copy of the row (sph_common.h, SPH_N16_*): offsets from the particle itself, or — cells one z layer away: lane A's
+    // 5 6 7, lane B's 3 — from the first particle of the z-neighbour cell. A piece's entries are its LDS slots + one constant, so
     // the range check is two comparisons per piece, not one per entry.
-    const int zBase = pairB ? zLoMine : zLoOther;
+    const int zBase = laneB ? zLoMine : zLoOther;
     int rel16[4];
     int wide = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const bool zf = pairB ? (i == 2) : (i != 0);
+      const bool zf = laneB ? (i == 2) : (i != 0);
       rel16[i] = absDelta[i] - (zf ? zBase : idNow) + SPH_N16_BIAS;
       if (pHi[i] > pLo[i] && (pLo[i] + rel16[i] < 0 || pHi[i] - 1 + rel16[i] > SPH_N16_MAX)) wide = 1;
     }
@@ -677,17 +632,16 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
     // passed; the reader only follows the flag, so no per-piece bookkeeping is needed)
     int own16 = SPH_N16_BIAS - idNow, far16 = SPH_N16_BIAS + 0x8000 - zBase;
     asm volatile("" : "+v"(own16), "+v"(far16));  // (kept in registers: rematerialised per entry they cost two more instructions each)
-    wide |= grp_other_half(wide);  // (both lanes are in this branch: `slow` is agreed inside the particle)
-    wide |= grp_other_pair(wide);
+    wide |= pair_other(wide);  // (both lanes are in this branch: `slow` is agreed inside the particle)
     int tidNow = tid;  // (opaque: keeps the address below from being hoisted to the kernel's prologue and spilled)
     asm volatile("" : "+v"(tidNow));
     float* const waveArea = reinterpret_cast<float*>(&sh.list[0][0][0]) + (tidNow >> 6) * (FN_LIST_ROWS * 64 / 2);
-    float* const dstRow = waveArea + ((tidNow & 63) >> FN_LOG_LANES) * FN_DST_STRIDE;
+    float* const dstRow = waveArea + ((tidNow & 63) >> 1) * FN_DST_STRIDE;
     // the row's 16-bit entries, [particle of the wave][slot], behind the d^2 area; pre-filled with "empty" by the lane that will store them
-    uint16_t* const idRow = reinterpret_cast<uint16_t*>(waveArea + FN_PER_WAVE * FN_DST_STRIDE) + ((tidNow & 63) >> FN_LOG_LANES) * SPH_MAXN;
+    uint16_t* const idRow = reinterpret_cast<uint16_t*>(waveArea + FN_PER_WAVE * FN_DST_STRIDE) + ((tidNow & 63) >> 1) * SPH_MAXN;
 #pragma unroll
     for (int v = 0; v < FN_SLOTS_PER_LANE / 8; v++)
-      *reinterpret_cast<uint4*>(idRow + FN_SLOTS_PER_LANE * quadLane + 8 * v) = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+      *reinterpret_cast<uint4*>(idRow + FN_SLOTS_PER_LANE * laneB + 8 * v) = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
     const uint32_t mapBase = ((uint32_t)(idNow >> 6) * (8u * 64u) + (uint32_t)(idNow & 63)) << 2;  // element index of slot 0 (< 2^32: N <= 2^27)
     // walk the entries in list order with a running (piece start, index delta, rank inside the piece)
     int curStart = start[0], curDelta = absDelta[0], rank = 0;
@@ -736,28 +690,28 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
     }
     }
     if (wide) {  // K1 folded in: unused slots of the 32-bit row (the 16-bit ones are pre-filled)
-      for (int k = run + quadLane; k < SPH_MAXN; k += FN_LANES) nbrId[mapBase + (uint32_t)(((k >> 2) << 8) + (k & 3))] = -1;
+      for (int k = run + laneB; k < SPH_MAXN; k += 2) nbrId[mapBase + (uint32_t)(((k >> 2) << 8) + (k & 3))] = -1;
     }
-    if (quadLane == 0) nbrBase[idNow] = zBase;
-    const uint32_t mapMine = mapBase + (uint32_t)((FN_SLOTS_PER_LANE / 4) * quadLane) * 256u;  // this lane's first group of 4 slots
+    if (laneB == 0) nbrBase[idNow] = zBase;
+    const uint32_t mapMine = mapBase + (uint32_t)((FN_SLOTS_PER_LANE / 4) * laneB) * 256u;  // this lane's first group of 4 slots
     // the 16-bit ids: every lane takes FN_SLOTS_PER_LANE consecutive slots of the particle from the staging area, 8 bytes per group of 4
 #pragma unroll
     for (int v = 0; v < FN_SLOTS_PER_LANE / 8; v++) {
-      const uint4 q = *reinterpret_cast<const uint4*>(idRow + FN_SLOTS_PER_LANE * quadLane + 8 * v);
+      const uint4 q = *reinterpret_cast<const uint4*>(idRow + FN_SLOTS_PER_LANE * laneB + 8 * v);
       *reinterpret_cast<uint2*>(nbr16 + (size_t)(mapMine + (uint32_t)(2 * v) * 256u)) = make_uint2(q.x, q.y);
       *reinterpret_cast<uint2*>(nbr16 + (size_t)(mapMine + (uint32_t)(2 * v + 1) * 256u)) = make_uint2(q.z, q.w);
     }
-    if (wide && quadLane == 0) {  // (after the entries: stores of one wave to one address keep their order)
+    if (wide && laneB == 0) {  // (after the entries: stores of one wave to one address keep their order)
       nbr16[mapBase] = (uint16_t)SPH_N16_WIDE;
       atomicAdd(&dbg[2], 1u);
     }
 #pragma unroll
     for (int gq = 0; gq < FN_SLOTS_PER_LANE / 4; gq++) {
-      const f32x4 dq = *reinterpret_cast<const f32x4*>(dstRow + FN_SLOTS_PER_LANE * quadLane + 4 * gq);
+      const f32x4 dq = *reinterpret_cast<const f32x4*>(dstRow + FN_SLOTS_PER_LANE * laneB + 4 * gq);
       const float dv[4] = {dq.x, dq.y, dq.z, dq.w};
       float out[4];
 #pragma unroll
-      for (int j = 0; j < 4; j++) out[j] = (FN_SLOTS_PER_LANE * quadLane + 4 * gq + j < run) ? sqrtf(dv[j]) * d.simScale : -1.f;
+      for (int j = 0; j < 4; j++) out[j] = (FN_SLOTS_PER_LANE * laneB + 4 * gq + j < run) ? sqrtf(dv[j]) * d.simScale : -1.f;
       *reinterpret_cast<f32x4*>(nbrDist + (size_t)(mapMine + (uint32_t)gq * 256u)) = f32x4{out[0], out[1], out[2], out[3]};
     }
   }
@@ -766,11 +720,11 @@ __global__ __launch_bounds__(FN_THREADS, (FN_LANES == 4 ? 4 : (FN_PART > 128 ? 1
 
   // ---- the rare particles the fast path cannot serve: the exact walk, by the wave that owns them (uniform control flow)
   {
-    unsigned long long todo = __ballot(mine_now && slow && quadLane == 0);
+    unsigned long long todo = __ballot(mine_now && slow && laneB == 0);
     while (todo != 0ull) {
       const int b = __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
-      fn_exact_walk(d, g, sh, p0 + wave * FN_PER_WAVE + (b >> FN_LOG_LANES), wave, lane);
+      fn_exact_walk(d, g, sh, p0 + wave * FN_PER_WAVE + (b >> 1), wave, lane);
     }
   }
   FN_STAMP(9)

@@ -23,26 +23,14 @@ __device__ __forceinline__ void store_pred(const SphDev& d, int id, const float4
   const f32x3a v = {p.x, p.y, p.z};
   *reinterpret_cast<f32x3a*>(d.predPos + 3 * (size_t)id) = v;
 }
-// DIAGNOSTIC build only (timings, results invalid): DIAG_OWN_GATHER reads the lane's own record instead of the neighbour's, so
-// every gather becomes a coalesced load. A/B on MI355X, config #2: forces 0.148 -> 0.061 ms, predictDensity x3 0.115 -> 0.083,
-// pressure force x3 0.284 -> 0.199: the 16-byte neighbour gathers (64 different cache lines per wave instruction) cost about
-// a fifth of the step; the kernels take the same time per particle at 1 M (cache resident) and at 16.5 M particles.
-#ifdef DIAG_OWN_GATHER
-#define NBR_INDEX(j) (id)
-#else
+// The always-valid gather index of the branch-free kernels: an empty slot (-1) reads record 0 and is masked out of the sum.
+// (The 16-byte neighbour gathers — 64 different cache lines per wave instruction — cost about a fifth of the step: DESIGN.md 4.1.)
 #define NBR_INDEX(j) (max((j), 0))
-#endif
 
-// neighbour gathers kept in flight per lane by the branch-free kernels (A/B on MI355X, config #2)
-#ifndef FC_BATCH
+// neighbour gathers kept in flight per lane by the branch-free kernels: as many as the kernel's register budget leaves room for
 #define FC_BATCH 8   // forces: two 16-B gathers per neighbour
-#endif
-#ifndef PF_BATCH
 #define PF_BATCH 8   // pressure force: 16 B + 4 B per neighbour
-#endif
-#ifndef PD_BATCH
 #define PD_BATCH 16  // predicted density: 16 B per neighbour
-#endif
 
 // index into SphDev::gatherRec: groups of four particles, [4 x part 0][4 x part 1] (one 128-byte line; see k_pack_gather_records)
 __device__ __forceinline__ size_t rec_index(int j, int part) { return ((size_t)(j >> 2) << 3) + (size_t)(part << 2) + (size_t)(j & 3); }
@@ -88,9 +76,7 @@ struct NbrTile {
   }
 };
 
-// XCD-aware block order: the hardware deals consecutive workgroups round-robin over the 8 XCDs; remap so that each
-// XCD works on one contiguous eighth of the sorted particle range and its L2 holds only that slab's neighbourhood.
-// Range-aware form for launches restricted to a cell range (slab mode): the remap must run over the blocks that HAVE work.
+// XCD-aware block order (xcd_block, sph_common.h) in its range-aware form, for launches restricted to a cell range (slab mode): the remap must run over the blocks that HAVE work.
 // Remapping over the whole grid would hand the first eighth of the logical blocks — for a short range, all of the work — to
 // one XCD (a 5-layer launch then took as long as the full one: 120 us instead of 17).
 __device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) {
@@ -98,7 +84,6 @@ __device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) {
   const int active = (end - begin + SPH_BLOCK - 1) / SPH_BLOCK;
   int b = blockIdx.x;
   if (b >= active) return false;
-#ifndef NO_XCD_REMAP
   const int per = active >> 3, even = per << 3;
   if (b < even) {
     const int x = b & 7;
@@ -107,20 +92,8 @@ __device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) {
     // measured: 0-7 % slower on all three gather kernels)
     b = x * per + k;
   }
-#endif
   id = begin + b * SPH_BLOCK + threadIdx.x;
   return id < end;
-}
-
-__device__ __forceinline__ int xcd_block(int nblocks) {
-#ifdef NO_XCD_REMAP
-  return blockIdx.x;
-#endif
-  const int b = blockIdx.x;
-  const int per = nblocks >> 3;  // blocks per XCD in the evenly divisible part
-  const int even = per << 3;
-  if (b >= even) return b;       // tail blocks keep their index
-  return (b & 7) * per + (b >> 3);
 }
 
 // ------------------------------------------------------------------ K6 pcisph_computeDensity (sphFluid.cl:472-518)
@@ -129,9 +102,10 @@ __device__ __forceinline__ int xcd_block(int nblocks) {
 // A/B on MI355X (bench.py roofline, 16.5 M particles): XCD-remapped blocks + plain loads 0.66 of 8 TB/s, plain block
 // order 0.67-0.69, plain order + non-temporal loads 0.75 (6.0 TB/s = 96 % of this part's 6.29 TB/s copy rate). The pass has
 // no reuse, so neither an XCD-local L2 nor keeping the stream in cache helps.
-#ifndef DENSITY_ITEMS
-#define DENSITY_ITEMS 1   // particles per thread, all of their 8 x 16-B loads in flight together (A/B in profiles/README.md)
-#endif
+// Particles per thread, all of their 8 x 16-B loads in flight together. One: the pass runs at 91 % of the part's copy rate, eight
+// loads per lane cover HBM. The loops over it stay: written out for one particle the same arithmetic compiles to a different load
+// and wait order (profiles/r10/README.md), which would have to be timed on the graded kernel.
+constexpr int DENSITY_ITEMS = 1;
 __global__ __launch_bounds__(SPH_BLOCK) void k_density(SphDev d, int nblocks) {
   typedef float nt4 __attribute__((ext_vector_type(4)));
   const int begin = (int)d.cellStart[d.rangeLo], end = (int)d.cellStart[d.rangeHi];
@@ -168,11 +142,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_density(SphDev d, int nblocks) {
     }
     if (density < (double)d.hs6) density = (double)d.hs6;
     density *= d.massWpoly6;
-#ifdef DIAG_DENSITY_INTO_REC  // timing experiment (results invalid): the density as a 4-byte store into the gather record's half-line
-    reinterpret_cast<float*>(&d.gatherRec[rec_index(id, 1)])[3] = (float)density;
-#else
     d.rho[id] = (float)density;
-#endif
   }
 }
 
@@ -513,11 +483,7 @@ __device__ __forceinline__ bool pf_batch(const SphDev& d, const float4 xi, const
     // the numerator is selected first, so only one IEEE division is spent
     float num = -(d.hs - r) * (d.hs - r) * half * (pi_ + rpj[k].y);
     if (__any(r < d.closeRf)) num = (r < d.closeRf) ? -(hq - r) * (hq - r) * half * d.rho0delta : num;  // (pairs closer than h/4: rare, so wave-uniformly skipped)
-#ifdef PF_IEEE_VALUE  // A/B: the compiler's division for value (13-15 instructions instead of 8)
-    const float value = num / rpj[k].x;
-#else
-    const float value = FAST ? sph_div1_by(num, rpj[k].x) : num / rpj[k].x;
-#endif
+    const float value = FAST ? sph_div1_by(num, rpj[k].x) : num / rpj[k].x;  // (8 instructions against the 13-15 of the compiler's division)
     const float vx = (xi.x - xj[k].x) * d.simScale, vy = (xi.y - xj[k].y) * d.simScale, vz = (xi.z - xj[k].z) * d.simScale;
     const bool use = jj[k] != -1 && r < d.hs;
     const float ax_ = value * vx, ay_ = value * vy, az_ = value * vz;

@@ -1,5 +1,5 @@
 // The slot loop over one sorted particle's neighbour row, shared by the analysis kernels that read the rows after a step
-// (sph_select.hip; the same walk, decode and non-temporal loads as cc_for_each_edge in sph_components.hip).
+// (sph_select.hip, sph_components.hip).
 #pragma once
 #include "sph_common.h"
 

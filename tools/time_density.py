@@ -8,7 +8,7 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 box, lat, mask = WORK[name]
 sc = scenes.liquid_box(box, lat, mask=mask)
 h = scenes.hip_for(sc)
-if not os.environ.get("SPHMI_NO_STEPS"):  # (diagnostic builds with invalid results must not integrate)
+if not os.environ.get("SPHMI_NO_STEPS"):  # (skipped under counter collection: tools/gpu_density_traffic_quick.sh)
     for it in range(3): h.step(it)
 h._runClearBuffers(); h._runHashParticles(); h._runSort(); h._runSortPostPass(); h._runIndexx(); h._runIndexPostPass(); h._runFindNeighbors()
 for _ in range(3): h._run_pcisph_computeDensity()

@@ -1,5 +1,5 @@
 """Time findNeighbors alone (staged API) on the config #2 cube: hash/sort/index once, then the search `reps` times.
-Used for A/B builds (SPHMI_LIB=...), including ablations whose neighbour maps are not valid and must not be consumed."""
+Used for A/B builds (SPHMI_LIB=...): tools/time_find_neighbors.py [reps] [jitter] [16M]."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import scenes
