@@ -386,6 +386,63 @@ int sph_select_particles(sph_solver* s, const float* region6 /* host or NULL */,
 int sph_read_selection(sph_solver* s, int32_t* sortedIndex /* host, count */, uint32_t* origId /* host, count */,
                        float* records /* host, count x 12 */);
 
+/* ---- Elastic-matter diagnostics (spring strain, muscle groups, membranes; no reference counterpart) ----------------------------
+ * State: the sorted state of the last completed step, as sampling and diagnostics (one integration step behind
+ * sph_read_position): positions are the sorted positions the step's stages ran on, the sorted index of original id o is
+ * particleIndexBack[o], the tables are the connection table, the membrane table and elasticOffset given to sph_create, and the
+ * muscle signal is the one sph_update_muscles stored last. Hence r and dr below are the values the step's elastic-force stage
+ * used, provided the signal has not been changed since that step.
+ * CONNECTION: row index in 0..numOfElasticP-1, slot nc in 0..31 of the connection table; conn = (x, y, z, w) of that slot. A
+ * row ends at the first slot with (int)conn.x == -1, as in the elastic-force stage; the slots before it are LIVE, the others
+ * dead. Connections are DIRECTED: a spring that is listed from both of its ends is two connections, one owned by each end, and
+ * every count and sum below counts it twice. Per live connection, in float, in the written order, no contraction, IEEE division
+ * and square root:
+ *   i = particleIndexBack[index + elasticOffset] (the owning end), j = particleIndexBack[(int)conn.x]
+ *   v = (x_i - x_j) * simulationScale per coordinate;  r = sqrtf(((vx*vx + vy*vy) + vz*vz) + 0.f*0.f)
+ *   L0 = conn.y;  dr = r - L0;  e = dr / L0, or e = 0 when !(L0 > 0)
+ *   group m = (int)conn.z if 1 <= m <= muscleCount, else 0 (no muscle);  sig = signal[m - 1] for m > 0
+ *   only when r != 0:  spring term s = -(v / r) * dr * 600000000.f per coordinate, and, only when m > 0 && sig > 0,
+ *                      contraction term c = -(v / r) * sig * 800.f per coordinate       (both exactly as the stage adds them)
+ * sph_elastic_measure: one row per elastic particle in connection-table order; any pointer may be NULL. sortedIndex = i,
+ * origId = index + elasticOffset (the particleIndex value of sorted particle i). records: SPH_ELASTIC_WORDS floats
+ *   { n, nMuscle, eMin, eMax, eSum, sum dr*dr, sx, sy, sz, cx, cy, cz }
+ * n = live slots, nMuscle = live slots with m > 0; eMin / eMax are float compares canonicalised by + 0.0f, 0 when n == 0; the
+ * four scalar and vector sums start from +0.0f and are added in ascending slot order (s only for the slots with r != 0, c only
+ * for those that have a contraction term), so s and c are the spring and contraction accelerations the step applied to the
+ * particle, each as a sum of its own. connections: (r, dr) per slot, (-1, 0) for a dead slot.
+ * sph_muscle_diagnostics: record 0 holds the live connections of no muscle group (m == 0), record m those of muscle m;
+ * SPH_MUSCLE_WORDS doubles each:
+ *   0 n                      1 signal (float widened; 0 for record 0)
+ *   2 sum L0                 3 sum r                   4 sum dr             5 sum (dr*dr as float)
+ *   6 sum e                  7 min e                   8 max e              9 sum (dr * 600000000.f as float)
+ *   10 sum (sig * 800.f as float) over the connections with r != 0 && sig > 0
+ *   11..13 sum x_i, y_i, z_i of the owning end (scene units)                14 connections with r == 0          15 0
+ * Every spring of the reference's generator is listed from both ends, so words 11..13 divided by n are the centroid of the
+ * group's spring midpoints. Each term is a float widened to double; the sums use the fixed tree reduce(a) of sph_diagnostics
+ * above over the numOfElasticP * 32 slot terms in table order (row-major, slot fastest), where a slot that is dead or belongs
+ * to another group contributes +0.0: a record depends on nothing but the state, the tables and the signal, and not on
+ * muscleCount's other groups. Extremes as in sph_diagnostics: float compares, + 0.0f, widened, 0 when n == 0.
+ * sph_membrane_measure: per triangle (a, b, c) of original ids, positions p = sortedPosition[particleIndexBack[.]], in float and
+ * scene units: e1 = b - a, e2 = c - a, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),
+ * len = sqrtf((nx*nx + ny*ny) + nz*nz), area = 0.5f * len, unit normal n / len (0 when len == 0), centroid ((a + b) + c) / 3.0f;
+ * record { area, nx, ny, nz, cx, cy, cz, 0 }. totals = { count, sum area (the same fixed tree over the triangles in table order,
+ * areas widened), min area, max area (as the extremes above) }. out may be NULL. There is no signed volume: the reference
+ * generator's worm mesh is closed but not consistently oriented, so a divergence-theorem volume would mean nothing.
+ * Rules: blocking, on the solver's stream, read-only on every solver array (meshes, labellings and selections stay valid), not
+ * stages (no stage timing). SPH_ERR_ORDER before a step's density and pressure-force stages have run. SPH_ERR_INVALID for a slab
+ * solver, a solver without elastic matter (numOfElasticP == 0), sph_membrane_measure with numOfMembranes == 0, a null out of
+ * sph_muscle_diagnostics or null totals, and a connection or membrane id outside 0..N-1 met on the device (reported, never
+ * followed; the outputs are then unspecified). A blown-up state is reported as by every blocking call. Device scratch, grown on
+ * demand and freed by sph_destroy: 312 bytes per elastic particle for sph_elastic_measure; (muscleCount + 1) x 128 bytes per
+ * 1024 slots (32 elastic particles) for sph_muscle_diagnostics; 32 bytes per triangle for sph_membrane_measure. */
+#define SPH_ELASTIC_WORDS 12
+#define SPH_MUSCLE_WORDS 16
+#define SPH_MEMBRANE_WORDS 8
+int sph_elastic_measure(sph_solver* s, int32_t* sortedIndex /* host, numOfElasticP */, uint32_t* origId /* host, numOfElasticP */,
+                        float* records /* host, numOfElasticP x 12 */, float* connections /* host, numOfElasticP x 32 x 2 */);
+int sph_muscle_diagnostics(sph_solver* s, double* out /* host, (muscleCount + 1) x SPH_MUSCLE_WORDS */);
+int sph_membrane_measure(sph_solver* s, float* out /* host, numOfMembranes x 8, or NULL */, double totals[4]);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

@@ -1,5 +1,5 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components, particle selection. All of them read the sorted state of the last completed step and write
+// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics. All of them read the sorted state of the last completed step and write
 // nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
 #include <string.h>
 
@@ -515,4 +515,100 @@ extern "C" int sph_read_selection(sph_solver* s, int32_t* sortedIndex, uint32_t*
     if (rc != SPH_OK) return rc;
   }
   return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- elastic-matter diagnostics
+// Spring strain per elastic particle, reductions per muscle group and membrane triangle areas (sph_elastic_measure.hip): the
+// tables given to sph_create, evaluated on the sorted state of the last completed step. Blocking, read-only, no stage timing.
+static int elastic_check(sph_solver* s, const char* what) {
+  if (s->hasSlab) { sph_set_error("%s: a slab solver is not supported", what); return SPH_ERR_INVALID; }
+  if (s->d.numElastic <= 0 || !s->d.elastic) { sph_set_error("%s: the solver holds no elastic matter", what); return SPH_ERR_INVALID; }
+  NEED(s, P_DENSITY | P_PRESSUREFORCE, what);
+  return SPH_OK;
+}
+
+static int elastic_bad_ids(uint32_t flags, const char* what) {
+  if (!flags) return SPH_OK;
+  sph_set_error("%s: a connection or membrane id lies outside 0..N-1 (flags 0x%x); it was not followed", what, flags);
+  return SPH_ERR_INVALID;
+}
+
+extern "C" int sph_elastic_measure(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records, float* connections) {
+  ENTER(s);
+  int rc = elastic_check(s, "sph_elastic_measure");
+  if (rc != SPH_OK) return rc;
+  // [flags, 256 bytes][records][connections][sorted indices][original ids]; an output that is not asked for is not written
+  const size_t E = (size_t)s->d.numElastic, head = 256;
+  const size_t recBytes = sizeof(float) * SPH_ELASTIC_WORDS * E, conBytes = sizeof(float) * 2 * SPH_MAX_NEIGHBOR_COUNT * E;
+  rc = grow_scratch(s, s->elasticBuf, head + recBytes + conBytes + 2 * sizeof(uint32_t) * E);
+  if (rc != SPH_OK) return rc;
+  char* base = (char*)s->elasticBuf.p;
+  uint32_t* dBad = (uint32_t*)base;
+  float* dRec = (float*)(base + head);
+  float* dCon = (float*)(base + head + recBytes);
+  int32_t* dIdx = (int32_t*)(base + head + recBytes + conBytes);
+  uint32_t* dIds = (uint32_t*)(dIdx + E);
+  rc = sphk_elastic_measure(s, sortedIndex ? dIdx : nullptr, origId ? dIds : nullptr, records ? dRec : nullptr,
+                            connections ? dCon : nullptr, dBad);
+  if (rc != SPH_OK) return rc;
+  // enqueued together, waited for once
+  if (records) SPH_HIP(hipMemcpyAsync(records, dRec, recBytes, hipMemcpyDeviceToHost, s->stream));
+  if (connections) SPH_HIP(hipMemcpyAsync(connections, dCon, conBytes, hipMemcpyDeviceToHost, s->stream));
+  if (sortedIndex) SPH_HIP(hipMemcpyAsync(sortedIndex, dIdx, sizeof(int32_t) * E, hipMemcpyDeviceToHost, s->stream));
+  if (origId) SPH_HIP(hipMemcpyAsync(origId, dIds, sizeof(uint32_t) * E, hipMemcpyDeviceToHost, s->stream));
+  uint32_t flags = 0;
+  rc = sph_d2h(s, &flags, dBad, sizeof(flags));
+  if (rc != SPH_OK) return rc;
+  rc = elastic_bad_ids(flags, "sph_elastic_measure");
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+extern "C" int sph_muscle_diagnostics(sph_solver* s, double* out) {
+  ENTER(s);
+  if (!out) { sph_set_error("sph_muscle_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  int rc = elastic_check(s, "sph_muscle_diagnostics");
+  if (rc != SPH_OK) return rc;
+  const int groups = s->d.muscleCount + 1;
+  rc = grow_scratch(s, s->elasticBuf, sizeof(double) * sphk_group_tree_doubles((long long)s->d.numElastic * SPH_MAX_NEIGHBOR_COUNT, groups));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_muscle_diagnostics(s, (double*)s->elasticBuf.p, &records);
+  if (rc != SPH_OK) return rc;
+  const size_t words = (size_t)groups * SPH_MUSCLE_WORDS;
+  SPH_HIP(hipMemcpyAsync(out, records, sizeof(double) * words, hipMemcpyDeviceToHost, s->stream));
+  double flags = 0.0;
+  rc = sph_d2h(s, &flags, records + words, sizeof(flags));
+  if (rc != SPH_OK) return rc;
+  rc = elastic_bad_ids((uint32_t)flags, "sph_muscle_diagnostics");
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+extern "C" int sph_membrane_measure(sph_solver* s, float* out, double totals[4]) {
+  ENTER(s);
+  if (!totals) { sph_set_error("sph_membrane_measure: null totals"); return SPH_ERR_INVALID; }
+  int rc = elastic_check(s, "sph_membrane_measure");
+  if (rc != SPH_OK) return rc;
+  const size_t M = (size_t)std::max(s->d.numMembranes, 0);
+  if (M == 0 || !s->d.membraneData) { sph_set_error("sph_membrane_measure: the solver holds no membranes"); return SPH_ERR_INVALID; }
+  // [records, 32 bytes per triangle][the tree's levels and flags]
+  const size_t recBytes = sizeof(float) * SPH_MEMBRANE_WORDS * M;
+  rc = grow_scratch(s, s->elasticBuf, recBytes + sizeof(double) * sphk_group_tree_doubles((long long)M, 1));
+  if (rc != SPH_OK) return rc;
+  float* dRec = (float*)s->elasticBuf.p;
+  double* top = nullptr;
+  rc = sphk_membrane_measure(s, out ? dRec : nullptr, (double*)((char*)s->elasticBuf.p + recBytes), &top);
+  if (rc != SPH_OK) return rc;
+  if (out) SPH_HIP(hipMemcpyAsync(out, dRec, recBytes, hipMemcpyDeviceToHost, s->stream));
+  double t[SPH_MUSCLE_WORDS + 1];
+  rc = sph_d2h(s, t, top, sizeof(t));
+  if (rc != SPH_OK) return rc;
+  uint32_t flags = 0;
+  memcpy(&flags, &t[SPH_MUSCLE_WORDS], sizeof(flags));
+  rc = elastic_bad_ids(flags, "sph_membrane_measure");
+  if (rc != SPH_OK) return rc;
+  volatile float mn = (float)t[7] + 0.0f, mx = (float)t[8] + 0.0f;  // the extremes' canonical form, as the diagnostics'
+  totals[0] = t[0]; totals[1] = t[2];
+  totals[2] = t[0] > 0.0 ? (double)mn : 0.0;
+  totals[3] = t[0] > 0.0 ? (double)mx : 0.0;
+  return sph_check_finite_state(s);
 }

@@ -145,6 +145,9 @@ struct sph_solver {
   int64_t selCount; bool selValid;    // length of the last successful selection
   int selN;                           // ... the particle count it was made for
   uint64_t selEpoch;                  // ... and stateEpoch at that time (sph_read_selection gathers from the live state)
+  // elastic-matter diagnostics (sph_elastic_measure / sph_muscle_diagnostics / sph_membrane_measure): records on their way to
+  // the host and the group tree's partials, grown on demand
+  SphScratch elasticBuf;
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -324,6 +327,15 @@ int sphk_select_scatter(sph_solver* s, void* scratch, uint32_t total, int32_t* l
 // records (SPH_SELECT_WORDS floats each, 16-byte aligned) and original ids of list[0..n); device pointers
 int sphk_select_gather(sph_solver* s, float ss2, const int32_t* list, int n, float* records, uint32_t* origId);
 int sphk_particle_measure(sph_solver* s, float ss2, int first, int n, float* out);  // out[r] = m of sorted particle first + r
+// sph_elastic_measure.hip (spring strain, muscle groups, membrane areas; read-only on every solver array)
+// per elastic particle, device pointers, any of the four may be null; *bad: one device word of error flags (ids out of range)
+int sphk_elastic_measure(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records, float* connections, uint32_t* bad);
+size_t sphk_group_tree_doubles(long long terms, int groups);  // scratch of the two calls below for `terms` slots / triangles
+// *records: (muscleCount + 1) x SPH_MUSCLE_WORDS doubles, directly followed by the error flags as one double
+int sphk_muscle_diagnostics(sph_solver* s, double* scratch, double** records);
+// out: numMembranes x 8 floats (device) or null; *top: 16 doubles (word 0 count, 2 area sum, 7 min, 8 max), directly followed by
+// an 8-byte cell whose low word holds the error flags
+int sphk_membrane_measure(sph_solver* s, float* out, double* scratch, double** top);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

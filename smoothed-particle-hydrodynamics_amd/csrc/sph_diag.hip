@@ -11,21 +11,15 @@
 // No floating-point atomics anywhere. Extremes are order-independent (float compares; the max-v2 particle by the pair
 // (larger v2, then lower index)) and travel through the levels as exactly widened doubles.
 #include "sph_common.h"
+#include "sph_tree.h"  // DIAG_CHUNK, diag_wave_sum, diag_block_reduce: shared with the elastic-matter reductions
 
 #include <algorithm>
 
-#define DIAG_CHUNK 1024
 #define DIAG_SUMS 14  // record words 0..13
 
 // Partials of a level: part[(region * SPH_DIAG_WORDS + word) * chunks + chunk], so that the next level reads them coalesced.
 __device__ __forceinline__ size_t diag_at(int region, int word, int chunks, int chunk) {
   return ((size_t)(region * SPH_DIAG_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
-
-__device__ __forceinline__ double diag_wave_sum(double x) {  // strides 32 ... 1 of the tree; lane 0 holds the result
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) x = x + __shfl_down(x, s, 64);
-  return x;
 }
 
 // the 10 plain extremes of a record, in this order: words 16, 18, 23, 24, 25 (minima), then 17, 19, 26, 27, 28 (maxima)
@@ -167,35 +161,6 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
 }
 
 // ---- upper levels: `nIn` partials per word and region -> ceil(nIn / 1024); the same tree (tiny launches) ------------------------
-enum { DIAG_OP_SUM = 0, DIAG_OP_MIN = 1, DIAG_OP_MAX = 2 };
-
-template <int OP>
-__device__ __forceinline__ double diag_combine(double a, double b) {
-  if (OP == DIAG_OP_SUM) return a + b;
-  if (OP == DIAG_OP_MIN) return b < a ? b : a;
-  return b > a ? b : a;
-}
-
-template <int OP>
-__device__ double diag_block_reduce(const double* __restrict__ in, int nIn, int chunk, double pad, double* sh) {
-  const int t = threadIdx.x;
-  double e[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int i = chunk * DIAG_CHUNK + k * SPH_BLOCK + t;
-    e[k] = i < nIn ? in[i] : pad;
-  }
-  sh[t] = diag_combine<OP>(diag_combine<OP>(e[0], e[2]), diag_combine<OP>(e[1], e[3]));
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (t < s) sh[t] = diag_combine<OP>(sh[t], sh[t + s]);
-    __syncthreads();
-  }
-  const double x = sh[0];
-  __syncthreads();
-  return x;
-}
-
 // One block per output chunk, region and job: jobs 0..13 the sums, 14..18 the minima, 19..23 the maxima, 24 the pair.
 #define DIAG_UPPER_JOBS 25
 __global__ __launch_bounds__(SPH_BLOCK) void k_diag_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {

@@ -124,6 +124,18 @@ class owHIPSolver {
     check(sph_read_selection(s_, sortedIndex, origId, records), "readSelection");
   }
 
+  // beyond the reference: the elastic matter. elasticMeasure writes one row per elastic particle in connection-table order (sorted
+  // index, original id, SPH_ELASTIC_WORDS floats of strain and spring / contraction acceleration, and (r, r - L0) for each of the
+  // 32 slots; any pointer may be null); muscleDiagnostics writes (muscleCount + 1) x SPH_MUSCLE_WORDS doubles, record 0 the
+  // connections of no muscle group; membraneMeasure writes numOfMembranes x SPH_MEMBRANE_WORDS floats (or nothing for null) and
+  // totals = {count, total area, min area, max area} (include/sphmi.h, sph_elastic_measure / sph_muscle_diagnostics /
+  // sph_membrane_measure)
+  void elasticMeasure(int32_t* sortedIndex, uint32_t* origId, float* records, float* connections) {
+    check(sph_elastic_measure(s_, sortedIndex, origId, records, connections), "elasticMeasure");
+  }
+  void muscleDiagnostics(double* out) { check(sph_muscle_diagnostics(s_, out), "muscleDiagnostics"); }
+  void membraneMeasure(float* out, double totals[4]) { check(sph_membrane_measure(s_, out, totals), "membraneMeasure"); }
+
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }
   sph_solver* handle() { return s_; }

@@ -32,6 +32,11 @@
 //        the count as int64, then the sorted indices (int32), the original ids (uint32) and the 12-float records
 //        (sphmi.frames.read_selection). Types default to 1 (liquid); FIELD is density, speed, pressure, neighbors, x, y, z,
 //        surface or 0..7, "inf" / "-inf" are accepted as bounds, up to 4 terms; --select-surface T is the term surface T inf
+//   ... --elastic-every K --elastic-out DIR
+//        after every K-th step of a scene with elastic matter (--worm), sph_muscle_diagnostics into DIR/muscles_<steps done>.csv:
+//        one row per group (0 = the connections of no muscle): group, n, signal, mean length, mean rest length, mean strain, min
+//        and max strain as %.17g (sphmi.frames.read_muscles_csv); unless --quiet, one line per report with the total membrane area
+//        (sph_membrane_measure) and the global min, mean and max strain over all connections
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -110,8 +115,11 @@ int main(int argc, char** argv) {
   int selEvery = 0; bool selSeen = false, selTypesSeen = false, selRegionSeen = false; const char* selDir = nullptr;
   unsigned selMask = 0; float selRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   std::vector<sph_select_term> selTerms;
+  int elaEvery = 0; bool elaSeen = false; const char* elaDir = nullptr;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
+    else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
+    else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
     else if (!strcmp(argv[i], "--select-every") && i + 1 < argc) { selEvery = atoi(argv[++i]); selSeen = true; }
     else if (!strcmp(argv[i], "--select-out") && i + 1 < argc) { selDir = argv[++i]; selSeen = true; }
     else if (!strcmp(argv[i], "--select-surface") && i + 1 < argc) { selTerms.push_back(sph_select_term{SPH_SELECT_FIELD_SURFACE, (float)atof(argv[++i]), INFINITY}); selSeen = true; }
@@ -213,6 +221,8 @@ int main(int argc, char** argv) {
   for (float b : selRegion)
     if (std::isnan(b)) { fprintf(stderr, "--select-region: a bound is not a number\n"); return 2; }
   const bool selecting = selSeen;
+  if (elaSeen && (elaEvery <= 0 || !elaDir)) { fprintf(stderr, "--elastic-every K (> 0) and --elastic-out DIR go together\n"); return 2; }
+  const bool measuringElastic = elaSeen;
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -251,6 +261,7 @@ int main(int argc, char** argv) {
       fprintf(stderr, "usage: sphmi_run (--position P --velocity V | --box X Y Z --lattice A B C | --worm [--muscles]) [--steps N] [--staged] [--wide] [--out F]\n");
       return 2;
     }
+    if (measuringElastic && numOfElasticP == 0) { fprintf(stderr, "--elastic-every needs a scene with elastic matter (--worm)\n"); return 2; }
     printf("particles: %d (liquid %d, elastic %d, boundary %d), grid %d x %d x %d\n", cfg.particleCount, numOfLiquidP,
            numOfElasticP, numOfBoundaryP, cfg.gridCellsX, cfg.gridCellsY, cfg.gridCellsZ);
     owOpenCLSolver* ocl_solver = new owOpenCLSolver(cfg, position_cpp.data(), velocity_cpp.data(),
@@ -258,6 +269,7 @@ int main(int argc, char** argv) {
                                                     membraneData_cpp.empty() ? nullptr : membraneData_cpp.data(),
                                                     particleMembranesList_cpp.empty() ? nullptr : particleMembranesList_cpp.data());
     std::vector<float> muscle_activation_signal_cpp(cfg.muscleCount, 0.f);
+    std::vector<double> muscleRecords(measuringElastic ? ((size_t)cfg.muscleCount + 1) * SPH_MUSCLE_WORDS : 0);
     float sampleOrigin[3] = {cfg.xmin, cfg.ymin, cfg.zmin}, sampleSpacing[3];
     const float boxMax[3] = {cfg.xmax, cfg.ymax, cfg.zmax};
     for (int k = 0; k < 3; k++) sampleSpacing[k] = sampleDims[k] > 1 ? (boxMax[k] - sampleOrigin[k]) / (float)(sampleDims[k] - 1) : 0.f;
@@ -423,6 +435,29 @@ int main(int argc, char** argv) {
         if (!ok) throw std::runtime_error("cannot write " + path);
         if (!quiet) printf("_select: selected %lld of %d\n", (long long)n, cfg.particleCount);
         helper.report("_select: \t\t%9.3f ms\n");
+      }
+      if (measuringElastic && (iterationCount + 1) % elaEvery == 0) {
+        ocl_solver->muscleDiagnostics(muscleRecords.data());
+        const std::string path = std::string(elaDir) + "/muscles_" + std::to_string(iterationCount + 1) + ".csv";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + path);
+        fputs("group,n,signal,mean_length,mean_rest_length,mean_strain,min_strain,max_strain\n", f);
+        double nAll = 0, eAll = 0, eMin = INFINITY, eMax = -INFINITY;
+        for (int g = 0; g <= cfg.muscleCount; g++) {
+          const double* r = &muscleRecords[(size_t)g * SPH_MUSCLE_WORDS];
+          const double n = r[0];
+          fprintf(f, "%d,%.0f,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", g, n, r[1], n > 0 ? r[3] / n : 0.0, n > 0 ? r[2] / n : 0.0,
+                  n > 0 ? r[6] / n : 0.0, r[7], r[8]);
+          if (n > 0) { nAll += n; eAll += r[6]; eMin = std::min(eMin, r[7]); eMax = std::max(eMax, r[8]); }
+        }
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + path);
+        if (!quiet) {
+          double totals[4] = {0, 0, 0, 0};
+          if (cfg.numOfMembranes > 0) ocl_solver->membraneMeasure(nullptr, totals);
+          printf("_elastic: connections %.0f  strain min %.6e mean %.6e max %.6e  membrane area %.9e over %.0f triangles\n", nAll,
+                 nAll > 0 ? eMin : 0.0, nAll > 0 ? eAll / nAll : 0.0, nAll > 0 ? eMax : 0.0, totals[1], totals[0]);
+        }
+        helper.report("_elastic: \t\t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

@@ -25,6 +25,9 @@ SELECT_WORDS = 12  # sph_read_selection record: x, y, z, type, vx, vy, vz, rho, 
 SELECT_MAX_TERMS = 4
 SELECT_FIELDS = HIST_FIELDS + ("surface",)  # sph_select_particles term fields 0..7
 GRADIENT_WORDS = 32  # sph_sample_gradient_* record: the sample record, then gradients, vorticity, divergence, Q (frames.GRADIENT_FIELDS)
+ELASTIC_WORDS = 12  # sph_elastic_measure record (frames.ELASTIC_FIELDS)
+MUSCLE_WORDS = 16  # sph_muscle_diagnostics record (frames.MUSCLE_FIELDS)
+MEMBRANE_WORDS = 8  # sph_membrane_measure record: area, unit normal, centroid, 0 (frames.MEMBRANE_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -116,7 +119,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
-                    "sph_read_selection"] + _STAGE_FUNCS
+                    "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -209,6 +212,9 @@ def device_lib():
         L.sph_particle_measure.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_select_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.sph_read_selection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_elastic_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_muscle_diagnostics.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_membrane_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -704,6 +710,41 @@ class owHIPSolver:
         rec = np.empty((n, SELECT_WORDS), np.float32)
         self._chk(self._L.sph_read_selection(self._h, _ptr(idx) if n else None, _ptr(ids) if n else None, _ptr(rec) if n else None))
         return idx, ids, rec
+
+    # --- elastic-matter diagnostics (sph_elastic_measure / sph_muscle_diagnostics / sph_membrane_measure) ---
+    def elastic_measure(self, connections=True):
+        """Spring strain of every elastic particle in the state of the last completed step, rows in connection-table order:
+        (sorted_index int32[E], orig_id uint32[E], records float32[E, 12] named by frames.ELASTIC_FIELDS -- live connections,
+        those in a muscle group, min / max / sum of the strain (r - L0) / L0, sum of (r - L0)^2 and the spring and contraction
+        accelerations the step applied -- and, unless connections=False, float32[E, 32, 2] holding (r, r - L0) per slot, (-1, 0)
+        for an empty slot; None otherwise). Connections are directed: a spring listed from both ends counts twice
+        (include/sphmi.h)."""
+        E = int(self.cfg.numOfElasticP)
+        idx = np.empty(E, np.int32)
+        ids = np.empty(E, np.uint32)
+        rec = np.empty((E, ELASTIC_WORDS), np.float32)
+        con = np.empty((E, MAX_NEIGHBOR_COUNT, 2), np.float32) if connections else None
+        self._chk(self._L.sph_elastic_measure(self._h, _ptr(idx) if E else None, _ptr(ids) if E else None, _ptr(rec) if E else None,
+                                              _ptr(con) if (connections and E) else None))
+        return idx, ids, rec, con
+
+    def muscle_diagnostics(self):
+        """float64[muscleCount + 1, 16] records named by frames.MUSCLE_FIELDS: record 0 the connections of no muscle group, record
+        m those of muscle m (count, signal, sums of rest length, length, elongation, strain and forces, strain extremes, position
+        sums of the owning ends). The sums are added in the fixed tree of diagnostics(), so a record depends on the state, the
+        tables and the signal alone. frames.muscle_summary turns the records into per-group means."""
+        out = np.zeros((int(self.cfg.muscleCount) + 1, MUSCLE_WORDS), np.float64)
+        self._chk(self._L.sph_muscle_diagnostics(self._h, _ptr(out)))
+        return out
+
+    def membrane_measure(self, records=True):
+        """(records float32[M, 8] -- area, unit normal, centroid, 0 per membrane triangle; None with records=False --,
+        totals float64[4] = count, total area (fixed tree), min area, max area)."""
+        M = int(self.cfg.numOfMembranes)
+        rec = np.empty((M, MEMBRANE_WORDS), np.float32) if records else None
+        totals = np.zeros(4, np.float64)
+        self._chk(self._L.sph_membrane_measure(self._h, _ptr(rec) if (records and M) else None, _ptr(totals)))
+        return rec, totals
 
     # --- extras ---
     def step(self, iterationCount=0):

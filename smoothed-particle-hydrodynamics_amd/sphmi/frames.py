@@ -30,6 +30,11 @@ into sizes and masses, `labels_in_original_order` maps the sorted-order labels t
 Selections (owHIPSolver.select / selection, float32[n, 12] records named by SELECT_FIELDS): `write_vtk_selection` writes the
 selected particles as a point cloud with everything a record holds as point data, `write_npz(selection=...)` stores one beside a
 frame, and `write_selection` / `read_selection` write and read the files `sphmi_run --select-out` writes.
+
+Elastic matter (owHIPSolver.elastic_measure / muscle_diagnostics / membrane_measure): `muscle_summary` turns the per-group records
+(float64[G + 1, 16] named by MUSCLE_FIELDS) into mean length, rest length and strain per group, `write_muscles_csv` /
+`read_muscles_csv` write and read the table `sphmi_run --elastic-out` writes, and `write_vtk_elastic` writes the elastic particles
+as a point cloud with their strain record (ELASTIC_FIELDS) as point data.
 """
 import numpy as np
 
@@ -477,3 +482,87 @@ def read_selection(path):
     ids = np.frombuffer(data, "<u4", n, 8 + 4 * n).astype(np.uint32)
     rec = np.frombuffer(data, "<f4", n * W, 8 + 8 * n).astype(np.float32).reshape(n, W)
     return idx, ids, rec
+
+
+# ---- elastic-matter diagnostics (owHIPSolver.elastic_measure / muscle_diagnostics / membrane_measure; include/sphmi.h) ----
+ELASTIC_FIELDS = ("n", "n_muscle", "min_strain", "max_strain", "sum_strain", "sum_dr2", "spring_x", "spring_y", "spring_z",
+                  "contraction_x", "contraction_y", "contraction_z")
+MUSCLE_FIELDS = ("n", "signal", "sum_rest_length", "sum_length", "sum_dr", "sum_dr2", "sum_strain", "min_strain", "max_strain",
+                 "sum_spring", "sum_contraction", "sum_x", "sum_y", "sum_z", "n_zero_length", "reserved15")
+MEMBRANE_FIELDS = ("area", "normal_x", "normal_y", "normal_z", "centroid_x", "centroid_y", "centroid_z", "unused7")
+MUSCLE_SUMMARY_FIELDS = ("group", "n", "signal", "mean_length", "mean_rest_length", "mean_strain", "min_strain", "max_strain")
+
+
+def muscle_summary(records):
+    """float64[G + 1, 8] from muscle_diagnostics() records, one row per group named by MUSCLE_SUMMARY_FIELDS: group (0 = the
+    connections of no muscle), n, signal, mean length sum_length / n, mean rest length, mean strain, min and max strain. Lengths
+    are simulation-scaled (the units of the connection table's rest lengths). The quotients are IEEE double divisions of the
+    record's words; with n = 0 they are 0."""
+    r = np.asarray(records, np.float64).reshape(-1, len(MUSCLE_FIELDS))
+    out = np.zeros((r.shape[0], len(MUSCLE_SUMMARY_FIELDS)), np.float64)
+    n = r[:, 0]
+    has = n > 0
+    out[:, 0] = np.arange(r.shape[0])
+    out[:, 1], out[:, 2] = n, r[:, 1]
+    for col, word in ((3, 3), (4, 2), (5, 6)):
+        out[has, col] = r[has, word] / n[has]
+    out[:, 6], out[:, 7] = r[:, 7], r[:, 8]
+    return out
+
+
+def write_muscles_csv(path, records):
+    """The table `sphmi_run --elastic-out` writes: one row per group, muscle_summary's columns, every number as %.17g."""
+    rows = muscle_summary(records)
+    with open(path, "w") as f:
+        f.write(",".join(MUSCLE_SUMMARY_FIELDS) + "\n")
+        for row in rows:
+            f.write("%d,%d," % (int(row[0]), int(row[1])) + ",".join("%.17g" % float(x) for x in row[2:]) + "\n")
+    return rows.shape[0]
+
+
+def read_muscles_csv(path):
+    """float64[G + 1, 8] of a file written by write_muscles_csv or `sphmi_run --elastic-out`."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        if header != list(MUSCLE_SUMMARY_FIELDS):
+            raise ValueError("%s: not a muscle table" % path)
+        rows = [[float(x) for x in line.strip().split(",")] for line in f if line.strip()]
+    return np.array(rows, np.float64).reshape(-1, len(MUSCLE_SUMMARY_FIELDS))
+
+
+def write_vtk_elastic(path, position, orig_id, records):
+    """Legacy-VTK polydata (binary, big-endian like write_vtk) of the elastic particles: one point per row of
+    owHIPSolver.elastic_measure() at position[orig_id] (`position`: [N, 4] in orig order, e.g. read_position_buffer()), with
+    `connections`, `muscle_connections`, `min_strain`, `max_strain`, `mean_strain` (float scalars), `id` (int) and
+    `spring_acceleration`, `contraction_acceleration` (vectors) as point data."""
+    rec = np.asarray(records, np.float32).reshape(-1, len(ELASTIC_FIELDS))
+    ids = np.asarray(orig_id, np.uint32).reshape(-1)
+    if ids.shape[0] != rec.shape[0]:
+        raise ValueError("write_vtk_elastic: one id per record expected")
+    pos = np.asarray(position, np.float32).reshape(-1, 4)[ids.astype(np.int64), :3]
+    n = rec.shape[0]
+    w = ELASTIC_FIELDS.index
+    live = np.maximum(rec[:, w("n")], np.float32(1))
+    scalars = (("connections", rec[:, w("n")]), ("muscle_connections", rec[:, w("n_muscle")]), ("min_strain", rec[:, w("min_strain")]),
+               ("max_strain", rec[:, w("max_strain")]), ("mean_strain", rec[:, w("sum_strain")] / live))
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi elastic matter\nBINARY\nDATASET POLYDATA\n")
+        f.write(("POINTS %d float\n" % n).encode())
+        f.write(pos.astype(">f4").tobytes())
+        f.write(("\nVERTICES %d %d\n" % (n, 2 * n)).encode())
+        cells = np.empty((n, 2), ">i4")
+        cells[:, 0] = 1
+        cells[:, 1] = np.arange(n)
+        f.write(cells.tobytes())
+        f.write(("\nPOINT_DATA %d\n" % n).encode())
+        for name, col in scalars:
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(col).astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(b"SCALARS id int 1\nLOOKUP_TABLE default\n")
+        f.write(ids.astype(">i4").tobytes())
+        for name, first in (("spring_acceleration", w("spring_x")), ("contraction_acceleration", w("contraction_x"))):
+            f.write(("\nVECTORS %s float\n" % name).encode())
+            f.write(np.ascontiguousarray(rec[:, first:first + 3]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return n
