@@ -443,6 +443,79 @@ int sph_elastic_measure(sph_solver* s, int32_t* sortedIndex /* host, numOfElasti
 int sph_muscle_diagnostics(sph_solver* s, double* out /* host, (muscleCount + 1) x SPH_MUSCLE_WORDS */);
 int sph_membrane_measure(sph_solver* s, float* out /* host, numOfMembranes x 8, or NULL */, double totals[4]);
 
+/* ---- Particle rendering: depth, id, colour and thickness images (no reference counterpart in the solver: the
+ * reference's viewer, owWorldSimulation.cpp, draws every particle each frame) ---------------------------------------------------
+ * sph_render_particles draws the selected particles of the sorted state of the last completed step (the state sph_sample_*
+ * describes: one integration step behind sph_read_position) as shaded spheres into images that stay on the device;
+ * sph_read_render copies them out. Everything is a function of the state and the arguments alone: the only cross-lane operations
+ * are 64-bit integer min and add atomics, ballots and popcounts; no floating-point atomics; no dependence on launch geometry.
+ * SELECTION: sorted particle j is a candidate when sph_diagnostics would select it for region6 (NULL = everything) and typeMask
+ * (type bit, cell key < number of cells, half-open box); the box doubles as a cut-away.
+ * PROJECTION, all in float, in the written order, no contraction, IEEE division and square root:
+ *   d = x_j - eye per coordinate;  cx = (d.x*right.x + d.y*right.y) + d.z*right.z;  cy likewise with up, cz with forward
+ *   k = scale / cz (perspective) or k = scale (orthographic);  u = cx*k + centre[0];  v = centre[1] - cy*k  (row 0 is the top)
+ *   R = radius*k;  R2 = R*R
+ * The particle is DRAWN when cz > nearPlane, R > 0, R <= maxRadiusPx, fabsf(u) < 1048576.f and fabsf(v) < 1048576.f (NaN fails
+ * every test). right / up / forward are used as given (the caller's orthonormal frame; frames.look_at makes one).
+ * FRAGMENTS: pixel (px, py) has its centre at ((float)px + 0.5f, (float)py + 0.5f); dx = centre.x - u, dy = centre.y - v,
+ * d2 = dx*dx + dy*dy; the pixel is covered when d2 <= R2; nz = sqrtf(1.0f - d2/R2); depth = cz - radius*nz; the fragment exists
+ * when depth > nearPlane. The pixel set is that test over the whole image (the kernels search floor(u-R)-1 .. floor(u+R)+1 and
+ * likewise in y, which contains it). Under perspective this is a sphere IMPOSTOR: a disc of the projected radius at the centre's
+ * depth, shaded and offset in depth like a sphere seen along the view axis, not the true perspective outline of a sphere.
+ * WINNER: key = ((uint64)bits(depth) << 32) | j; depth is positive, so its bit pattern orders as the float does. A pixel holds
+ * the minimum key over its fragments: the nearest fragment, and on equal depth bits the lower sorted index. Images, row-major
+ * [height][width]: depth (float; +inf where uncovered), sortedIndex (int32; -1), origId (uint32, the winner's particleIndex value;
+ * 0xFFFFFFFF), rgba (4 bytes; background).
+ * COLOUR of a covered pixel: the winner's u, v, R2 and nz are recomputed by the same expressions; base colour c per channel:
+ *   mode 0  typeColour[t - 1], t = (int)position.w
+ *   mode 1  the reference viewer's density ramp (owWorldSimulation.cpp:127-141, frames.density_colour) of rho_j against rho0, for
+ *           every type: rho clipped to [0, 2.0f*rho0]; c = (0, 0, 1); then for f in 1.00f, 1.01f, 1.02f, 1.03f, 1.04f in this
+ *           order dc = (100.0f*(rho - rho0*f))/rho0 and, when dc > 0, c = (0, dc, 1), (0, 1, 1 - dc), (dc, 1, 0), (1, 1 - dc, 0),
+ *           (1, 0, 0) respectively (later ramps win)
+ *   mode 2  q = sph_histogram's quantity for `field`; s = fminf(fmaxf((q - lo)*inv, 0.f), 1.f) with inv = 1.0f/(hi - lo) computed
+ *           once on the host; a = s*4.0f; i = min((int)a, 3); f = a - (float)i; c = stop[i] + f*(stop[i+1] - stop[i]) over
+ *           SPH_RENDER_FIELD_RAMP (a NaN q gives s = 0)
+ *   mode 3  SPH_RENDER_LABEL_PALETTE[label % 12] of the current sph_label_components labelling; (0.5, 0.5, 0.5) for a label < 0
+ * then shade = ambient + (1.0f - ambient)*nz, byte = (uint8)(int)(fminf(fmaxf(c*shade, 0.f), 1.f)*255.0f + 0.5f), A = 255.
+ * THICKNESS (wantThickness != 0): every fragment, not only the winner, adds (uint32)(int)(nz*256.0f + 0.5f) to its pixel: the
+ * chord 2*radius*nz in units of radius/128, an X-ray column of the selected matter. The sum is a 64-bit integer (integer adds
+ * commute), returned saturated to uint32; 0 where uncovered.
+ * counts = { particles drawn (candidates that pass the five tests above, whether or not a fragment lands in the image), covered
+ * pixels }. The images live in device memory owned by the solver until the next render or sph_destroy; they are self-contained:
+ * sph_read_render returns the same bytes after further steps. Any pointer of sph_read_render may be NULL.
+ * Rules: blocking, on the solver's stream, read-only on every solver array (meshes, labellings and selections stay valid), not a
+ * stage (no stage timing). SPH_ERR_ORDER before a step's density and pressure-force stages have run (mode 2 with field 3: the
+ * neighbour stage too), for mode 3 without a labelling of the current state, and for sph_read_render before any successful render.
+ * SPH_ERR_INVALID for a slab solver, a bad typeMask, a NaN region bound, a null view or counts, any field of the view outside the
+ * ranges below or not finite, and thickness != NULL after a render made without it. A failed render leaves no image behind.
+ * Device memory, grown on demand: 24 bytes per pixel (36 with thickness) and 4 bytes per particle. */
+typedef struct sph_render_view {
+  int32_t width, height;        /* 1..8192 each, width*height <= 1<<24 */
+  int32_t projection;           /* 0 orthographic, 1 perspective */
+  float eye[3], right[3], up[3], forward[3];   /* the caller's orthonormal frame; used as given, only checked finite */
+  float scale;                  /* orthographic: pixels per scene unit; perspective: focal length in pixels; > 0 */
+  float centre[2];              /* principal point in pixels */
+  float nearPlane;              /* >= 0, finite */
+  float radius;                 /* sphere radius in scene units, > 0 */
+  float maxRadiusPx;            /* 0 < . <= 4096 */
+  int32_t colourMode;           /* 0 type, 1 density (the viewer's ramp), 2 field, 3 component label */
+  int32_t field; float lo, hi;  /* mode 2: sph_histogram's field 0..6, lo < hi, finite */
+  float typeColour[3][3];       /* mode 0: rgb for liquid, elastic, boundary */
+  float ambient;                /* 0..1 */
+  uint8_t background[4];        /* RGBA of an uncovered pixel */
+} sph_render_view;
+/* the five stops of mode 2: blue, cyan, green, yellow, red */
+#define SPH_RENDER_FIELD_RAMP { {0.f, 0.f, 1.f}, {0.f, 1.f, 1.f}, {0.f, 1.f, 0.f}, {1.f, 1.f, 0.f}, {1.f, 0.f, 0.f} }
+/* the twelve colours of mode 3, label % 12 */
+#define SPH_RENDER_LABEL_COLOURS 12
+#define SPH_RENDER_LABEL_PALETTE { {0.90f, 0.10f, 0.10f}, {0.10f, 0.50f, 0.90f}, {0.20f, 0.70f, 0.20f}, {0.95f, 0.60f, 0.10f}, \
+                                   {0.60f, 0.30f, 0.80f}, {0.10f, 0.75f, 0.75f}, {0.95f, 0.90f, 0.20f}, {0.85f, 0.35f, 0.65f}, \
+                                   {0.55f, 0.35f, 0.15f}, {0.40f, 0.85f, 0.55f}, {0.30f, 0.30f, 0.65f}, {0.75f, 0.75f, 0.75f} }
+int sph_render_particles(sph_solver* s, const sph_render_view* view, const float* region6 /* or NULL */, uint32_t typeMask,
+                         int32_t wantThickness, int64_t counts[2] /* particles drawn, covered pixels */);
+int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba /* 4 per pixel */,
+                    uint32_t* thickness);  /* host, width x height each; any may be NULL */
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

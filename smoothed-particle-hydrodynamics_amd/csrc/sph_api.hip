@@ -202,7 +202,7 @@ static void free_all(sph_solver* s) {
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
                   s->blockHist};
   for (void* p : ptrs) if (p) hipFree(p);
-  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable, &s->selBuf, &s->selList, &s->elasticBuf}) if (b->p) hipFree(b->p);
+  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable, &s->selBuf, &s->selList, &s->elasticBuf, &s->renderBuf}) if (b->p) hipFree(b->p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
   s->numHostRegs = 0;

@@ -1,5 +1,5 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics. All of them read the sorted state of the last completed step and write
+// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, particle rendering. All of them read the sorted state of the last completed step and write
 // nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
 #include <string.h>
 
@@ -611,4 +611,103 @@ extern "C" int sph_membrane_measure(sph_solver* s, float* out, double totals[4])
   totals[2] = t[0] > 0.0 ? (double)mn : 0.0;
   totals[3] = t[0] > 0.0 ? (double)mx : 0.0;
   return sph_check_finite_state(s);
+}
+
+// ---------------------------------------------------------------------------------------------- particle rendering
+// Images of the particles (sph_render.hip): clear, splat, drain and resolve are enqueued together and waited for once, for the
+// two counts. The images stay in renderBuf and hold everything sph_read_render returns, so they outlive the state they show.
+static bool render_view_ok(const sph_render_view& v) {
+  const float* f[] = {v.eye, v.right, v.up, v.forward};
+  for (const float* a : f)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(a[k])) { sph_set_error("sph_render_particles: eye, right, up and forward must be finite"); return false; }
+  if (v.width < 1 || v.width > 8192 || v.height < 1 || v.height > 8192 || (int64_t)v.width * v.height > ((int64_t)1 << 24)) {
+    sph_set_error("sph_render_particles: width and height must be in 1..8192 with width*height <= 1<<24"); return false;
+  }
+  if (v.projection != 0 && v.projection != 1) { sph_set_error("sph_render_particles: projection %d is not 0 or 1", v.projection); return false; }
+  if (!std::isfinite(v.scale) || !(v.scale > 0.f)) { sph_set_error("sph_render_particles: scale must be finite and > 0"); return false; }
+  if (!std::isfinite(v.centre[0]) || !std::isfinite(v.centre[1])) { sph_set_error("sph_render_particles: centre must be finite"); return false; }
+  if (!std::isfinite(v.nearPlane) || !(v.nearPlane >= 0.f)) { sph_set_error("sph_render_particles: nearPlane must be finite and >= 0"); return false; }
+  if (!std::isfinite(v.radius) || !(v.radius > 0.f)) { sph_set_error("sph_render_particles: radius must be finite and > 0"); return false; }
+  if (!(v.maxRadiusPx > 0.f && v.maxRadiusPx <= 4096.f)) { sph_set_error("sph_render_particles: maxRadiusPx must be in (0, 4096]"); return false; }
+  if (v.colourMode < 0 || v.colourMode > 3) { sph_set_error("sph_render_particles: colourMode %d is not in 0..3", v.colourMode); return false; }
+  if (v.colourMode == 2) {
+    if (v.field < 0 || v.field > 6) { sph_set_error("sph_render_particles: field %d is not in 0..6", v.field); return false; }
+    if (!std::isfinite(v.lo) || !std::isfinite(v.hi) || !(v.lo < v.hi)) { sph_set_error("sph_render_particles: lo and hi must be finite with lo < hi"); return false; }
+  }
+  if (v.colourMode == 0)
+    for (int t = 0; t < 3; t++)
+      for (int k = 0; k < 3; k++)
+        if (!std::isfinite(v.typeColour[t][k])) { sph_set_error("sph_render_particles: typeColour must be finite"); return false; }
+  if (!(v.ambient >= 0.f && v.ambient <= 1.f)) { sph_set_error("sph_render_particles: ambient must be in 0..1"); return false; }
+  return true;
+}
+
+extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, const float* region6, uint32_t typeMask,
+                                    int32_t wantThickness, int64_t counts[2]) {
+  ENTER(s);
+  s->renderValid = false;  // a failed render leaves no image behind
+  if (counts) counts[0] = counts[1] = 0;
+  if (!view || !counts) { sph_set_error("sph_render_particles: null pointer"); return SPH_ERR_INVALID; }
+  int rc = sample_check(s, typeMask, "sph_render_particles");
+  if (rc != SPH_OK) return rc;
+  if (!render_view_ok(*view)) return SPH_ERR_INVALID;
+  RenderArgs a = {};
+  a.view = *view;
+  a.typeMask = typeMask;
+  if (region6) {
+    rc = diag_region_ok(region6, "sph_render_particles");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
+  } else {
+    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
+  }
+  if (view->colourMode == 2) {
+    if (view->field == 3) NEED(s, P_FIND, "sph_render_particles (field 3)");
+    volatile float width = view->hi - view->lo;
+    volatile float inv = 1.0f / width;
+    a.inv = inv;
+  }
+  if (view->colourMode == 3) {
+    if (!s->ccValid || s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
+      sph_set_error("sph_render_particles: no labelling of the current state (sph_label_components)");
+      return SPH_ERR_ORDER;
+    }
+    a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
+  }
+  const bool thickness = wantThickness != 0;
+  const RenderLayout L = sphk_render_layout(view->width, view->height, thickness, s->d.N);
+  rc = grow_scratch(s, s->renderBuf, L.bytes);
+  if (rc != SPH_OK) return rc;
+  rc = sphk_render(s, a, thickness, s->renderBuf.p);
+  if (rc != SPH_OK) return rc;
+  uint32_t head[2] = {0, 0};
+  rc = sph_d2h(s, head, (char*)s->renderBuf.p + L.head, sizeof(head));  // the call's one wait for a result
+  if (rc != SPH_OK) return rc;
+  rc = sph_check_finite_state(s);
+  if (rc != SPH_OK) return rc;
+  s->renderW = view->width; s->renderH = view->height;
+  s->renderThickness = thickness;
+  s->renderN = s->d.N;
+  s->renderValid = true;
+  counts[0] = (int64_t)head[0];
+  counts[1] = (int64_t)head[1];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba, uint32_t* thickness) {
+  ENTER(s);
+  if (!s->renderValid) { sph_set_error("sph_read_render: nothing has been rendered"); return SPH_ERR_ORDER; }
+  if (thickness && !s->renderThickness) { sph_set_error("sph_read_render: the last render accumulated no thickness"); return SPH_ERR_INVALID; }
+  const RenderLayout L = sphk_render_layout(s->renderW, s->renderH, s->renderThickness, s->renderN);
+  const size_t words = sizeof(uint32_t) * (size_t)s->renderW * (size_t)s->renderH;
+  const char* base = (const char*)s->renderBuf.p;
+  // enqueued together, waited for once
+  if (depth) SPH_HIP(hipMemcpyAsync(depth, base + L.depth, words, hipMemcpyDeviceToHost, s->stream));
+  if (sortedIndex) SPH_HIP(hipMemcpyAsync(sortedIndex, base + L.index, words, hipMemcpyDeviceToHost, s->stream));
+  if (origId) SPH_HIP(hipMemcpyAsync(origId, base + L.origId, words, hipMemcpyDeviceToHost, s->stream));
+  if (rgba) SPH_HIP(hipMemcpyAsync(rgba, base + L.rgba, words, hipMemcpyDeviceToHost, s->stream));
+  if (thickness) SPH_HIP(hipMemcpyAsync(thickness, base + L.thickOut, words, hipMemcpyDeviceToHost, s->stream));
+  SPH_HIP(hipStreamSynchronize(s->stream));
+  return SPH_OK;
 }

@@ -148,6 +148,11 @@ struct sph_solver {
   // elastic-matter diagnostics (sph_elastic_measure / sph_muscle_diagnostics / sph_membrane_measure): records on their way to
   // the host and the group tree's partials, grown on demand
   SphScratch elasticBuf;
+  // particle rendering (sph_render_particles / sph_read_render): keys, thickness sums, the resolved images and the queue of large
+  // splats in one buffer, grown on demand; the images are self-contained, so there is no epoch
+  SphScratch renderBuf;
+  bool renderValid; bool renderThickness;  // a successful render exists / it accumulated thickness
+  int renderW, renderH, renderN;           // ... its size and the particle count its buffer was laid out for
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -336,6 +341,19 @@ int sphk_muscle_diagnostics(sph_solver* s, double* scratch, double** records);
 // out: numMembranes x 8 floats (device) or null; *top: 16 doubles (word 0 count, 2 area sum, 7 min, 8 max), directly followed by
 // an 8-byte cell whose low word holds the error flags
 int sphk_membrane_measure(sph_solver* s, float* out, double* scratch, double** top);
+// sph_render.hip (depth, id, colour and thickness images of the particles; read-only on every solver array)
+struct RenderArgs {
+  sph_render_view view;
+  float box[6];
+  uint32_t typeMask;
+  float inv;              // 1.0f / (hi - lo), one float (colour mode 2)
+  const int32_t* labels;  // the current labelling (colour mode 3)
+};
+// where the pieces of a render lie in its buffer (bytes from its start); thick / thickOut are 0 without thickness
+struct RenderLayout { size_t head, keys, thick, depth, index, origId, rgba, thickOut, queue, bytes; };
+RenderLayout sphk_render_layout(int width, int height, bool thickness, int N);
+// clear, splat, drain the queue of large splats, resolve; head words afterwards: [0] particles drawn, [1] covered pixels
+int sphk_render(sph_solver* s, const RenderArgs& a, bool thickness, void* buf);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

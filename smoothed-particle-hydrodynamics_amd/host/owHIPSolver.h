@@ -136,6 +136,17 @@ class owHIPSolver {
   void muscleDiagnostics(double* out) { check(sph_muscle_diagnostics(s_, out), "muscleDiagnostics"); }
   void membraneMeasure(float* out, double totals[4]) { check(sph_membrane_measure(s_, out, totals), "membraneMeasure"); }
 
+  // beyond the reference: a picture. renderParticles draws the particles of typeMask inside region6 (or null) as shaded spheres
+  // through `view` into depth, sorted-index, original-id, rgba and (wantThickness) thickness images kept on the device and fills
+  // counts = {particles drawn, covered pixels}; readRender copies the images out, width x height words each (any pointer may be
+  // null) (include/sphmi.h, sph_render_particles / sph_read_render)
+  void renderParticles(const sph_render_view& view, const float* region6, unsigned int typeMask, bool wantThickness, int64_t counts[2]) {
+    check(sph_render_particles(s_, &view, region6, typeMask, wantThickness ? 1 : 0, counts), "renderParticles");
+  }
+  void readRender(float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba, uint32_t* thickness) {
+    check(sph_read_render(s_, depth, sortedIndex, origId, rgba, thickness), "readRender");
+  }
+
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }
   sph_solver* handle() { return s_; }

@@ -37,6 +37,17 @@
 //        one row per group (0 = the connections of no muscle): group, n, signal, mean length, mean rest length, mean strain, min
 //        and max strain as %.17g (sphmi.frames.read_muscles_csv); unless --quiet, one line per report with the total membrane area
 //        (sph_membrane_measure) and the global min, mean and max strain over all connections
+//   ... --render-every K --render-out DIR [--render-size W H] [--render-eye X Y Z] [--render-target X Y Z] [--render-up X Y Z]
+//       [--render-ortho S | --render-focal F] [--render-radius R] [--render-colour type|density|field:N:LO:HI|label]
+//       [--render-thickness]
+//        after every K-th step, draw the liquid and elastic particles on the device (sph_render_particles) and write
+//        DIR/frame_<steps done>.ppm (binary P6; sphmi.frames.read_ppm), DIR/frame_<steps done>.depth.f32 (raw float32, H x W, +inf
+//        where nothing was drawn) and, with --render-thickness, DIR/frame_<steps done>.thickness.u32. The camera is at --render-eye
+//        looking at --render-target (defaults: the centre of the scene's box, seen from two box diagonals away towards
+//        (0.6, 0.5, 1)) with --render-up (default 0 1 0), the frame computed in double and narrowed once (sphmi.frames.look_at);
+//        --render-ortho S: orthographic, S pixels per scene unit; --render-focal F: perspective, focal length F pixels (default:
+//        perspective with F = W); the principal point is the image centre, the sphere radius defaults to r0 / 2, N is a field
+//        number 0..6 of sph_histogram; label colours need no other option (the components of the drawn types are labelled first)
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -101,6 +112,28 @@ static int select_field(const char* name) {
   return -1;
 }
 
+// the camera frame of sphmi.frames.look_at: double arithmetic in this order, narrowed once; false when it is degenerate
+static bool look_at(const double eye[3], const double target[3], const double up[3], sph_render_view* v) {
+  double f[3] = {target[0] - eye[0], target[1] - eye[1], target[2] - eye[2]};
+  double n = std::sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+  if (!(n > 0)) return false;
+  for (int k = 0; k < 3; k++) f[k] /= n;
+  double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+  n = std::sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+  if (!(n > 1e-12)) return false;
+  for (int k = 0; k < 3; k++) r[k] /= n;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  for (int k = 0; k < 3; k++) { v->eye[k] = (float)eye[k]; v->right[k] = (float)r[k]; v->up[k] = (float)u[k]; v->forward[k] = (float)f[k]; }
+  return true;
+}
+
+static bool write_file(const std::string& path, const void* header, size_t headerBytes, const void* body, size_t bodyBytes) {
+  FILE* f = fopen(path.c_str(), "wb");
+  bool ok = f && fwrite(header, 1, headerBytes, f) == headerBytes && fwrite(body, 1, bodyBytes, f) == bodyBytes;
+  if (f && fclose(f) != 0) ok = false;
+  return ok;
+}
+
 int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
@@ -116,10 +149,25 @@ int main(int argc, char** argv) {
   unsigned selMask = 0; float selRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   std::vector<sph_select_term> selTerms;
   int elaEvery = 0; bool elaSeen = false; const char* elaDir = nullptr;
+  int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
+  const char* renDir = nullptr; const char* renColour = "density";
+  double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
+  float renOrtho = 0.f, renFocal = 0.f, renRadius = 0.f; bool renOrthoSeen = false, renFocalSeen = false, renRadiusSeen = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
+    else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
+    else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
+    else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
+    else if (!strcmp(argv[i], "--render-eye") && i + 3 < argc) { for (int k = 0; k < 3; k++) renEye[k] = atof(argv[++i]); renSeen = renEyeSeen = true; }
+    else if (!strcmp(argv[i], "--render-target") && i + 3 < argc) { for (int k = 0; k < 3; k++) renTarget[k] = atof(argv[++i]); renSeen = renTargetSeen = true; }
+    else if (!strcmp(argv[i], "--render-up") && i + 3 < argc) { for (int k = 0; k < 3; k++) renUp[k] = atof(argv[++i]); renSeen = true; }
+    else if (!strcmp(argv[i], "--render-ortho") && i + 1 < argc) { renOrtho = (float)atof(argv[++i]); renSeen = renOrthoSeen = true; }
+    else if (!strcmp(argv[i], "--render-focal") && i + 1 < argc) { renFocal = (float)atof(argv[++i]); renSeen = renFocalSeen = true; }
+    else if (!strcmp(argv[i], "--render-radius") && i + 1 < argc) { renRadius = (float)atof(argv[++i]); renSeen = renRadiusSeen = true; }
+    else if (!strcmp(argv[i], "--render-colour") && i + 1 < argc) { renColour = argv[++i]; renSeen = true; }
+    else if (!strcmp(argv[i], "--render-thickness")) { renThickness = renSeen = true; }
     else if (!strcmp(argv[i], "--select-every") && i + 1 < argc) { selEvery = atoi(argv[++i]); selSeen = true; }
     else if (!strcmp(argv[i], "--select-out") && i + 1 < argc) { selDir = argv[++i]; selSeen = true; }
     else if (!strcmp(argv[i], "--select-surface") && i + 1 < argc) { selTerms.push_back(sph_select_term{SPH_SELECT_FIELD_SURFACE, (float)atof(argv[++i]), INFINITY}); selSeen = true; }
@@ -223,6 +271,34 @@ int main(int argc, char** argv) {
   const bool selecting = selSeen;
   if (elaSeen && (elaEvery <= 0 || !elaDir)) { fprintf(stderr, "--elastic-every K (> 0) and --elastic-out DIR go together\n"); return 2; }
   const bool measuringElastic = elaSeen;
+  if (renSeen && (renEvery <= 0 || !renDir)) {
+    fprintf(stderr, "--render-every K (> 0) and --render-out DIR go together (the other --render options need both)\n");
+    return 2;
+  }
+  const bool rendering = renSeen;
+  sph_render_view renView;
+  memset(&renView, 0, sizeof(renView));
+  if (rendering) {
+    if (renSize[0] < 1 || renSize[0] > 8192 || renSize[1] < 1 || renSize[1] > 8192 || (long long)renSize[0] * renSize[1] > (1LL << 24)) {
+      fprintf(stderr, "--render-size W H: 1..8192 each and W*H <= 16777216\n"); return 2;
+    }
+    if (renOrthoSeen && renFocalSeen) { fprintf(stderr, "--render-ortho and --render-focal exclude each other\n"); return 2; }
+    if ((renOrthoSeen && !(renOrtho > 0.f && std::isfinite(renOrtho))) || (renFocalSeen && !(renFocal > 0.f && std::isfinite(renFocal)))) {
+      fprintf(stderr, "--render-ortho S / --render-focal F: a finite number > 0\n"); return 2;
+    }
+    if (renRadiusSeen && !(renRadius > 0.f && std::isfinite(renRadius))) { fprintf(stderr, "--render-radius R: a finite number > 0\n"); return 2; }
+    if (!strcmp(renColour, "type")) renView.colourMode = 0;
+    else if (!strcmp(renColour, "density")) renView.colourMode = 1;
+    else if (!strcmp(renColour, "label")) renView.colourMode = 3;
+    else {
+      int n = 0;
+      if (sscanf(renColour, "field:%d:%f:%f%n", &renView.field, &renView.lo, &renView.hi, &n) != 3 || renColour[n] || renView.field < 0 ||
+          renView.field > 6 || !std::isfinite(renView.lo) || !std::isfinite(renView.hi) || !(renView.lo < renView.hi)) {
+        fprintf(stderr, "--render-colour: type, density, label or field:N:LO:HI with N in 0..6 and LO < HI, both finite\n"); return 2;
+      }
+      renView.colourMode = 2;
+    }
+  }
   try {
     sph_config cfg;
     sphmi_default_config(&cfg);
@@ -293,6 +369,28 @@ int main(int argc, char** argv) {
     std::vector<float> compBbox;
     std::vector<double> compRecords;
     std::vector<int32_t> selIndex; std::vector<uint32_t> selIds; std::vector<float> selRecords;
+    std::vector<uint8_t> renRgba; std::vector<float> renDepth; std::vector<uint32_t> renThick;
+    if (rendering) {  // the defaults of sphmi.frames.render_view
+      const double lo[3] = {cfg.xmin, cfg.ymin, cfg.zmin}, hi[3] = {cfg.xmax, cfg.ymax, cfg.zmax};
+      const double diag = std::sqrt(((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1])) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+      const double dir[3] = {0.6, 0.5, 1.0}, dirLen = std::sqrt((0.6 * 0.6 + 0.5 * 0.5) + 1.0);
+      for (int k = 0; k < 3; k++) {
+        if (!renTargetSeen) renTarget[k] = 0.5 * (lo[k] + hi[k]);
+        if (!renEyeSeen) renEye[k] = renTarget[k] + 2.0 * diag * dir[k] / dirLen;
+      }
+      if (!look_at(renEye, renTarget, renUp, &renView)) throw std::runtime_error("--render-eye / --render-target / --render-up: the eye is at the target, or up is parallel to the view direction");
+      renView.width = renSize[0]; renView.height = renSize[1];
+      renView.projection = renOrthoSeen ? 0 : 1;
+      renView.scale = renOrthoSeen ? renOrtho : (renFocalSeen ? renFocal : (float)renSize[0]);
+      renView.centre[0] = 0.5f * (float)renSize[0]; renView.centre[1] = 0.5f * (float)renSize[1];
+      renView.nearPlane = 0.f;
+      renView.radius = renRadiusSeen ? renRadius : 0.5f * cfg.r0;
+      renView.maxRadiusPx = 256.f;
+      const float typeColour[3][3] = {{0.2f, 0.45f, 0.9f}, {0.9f, 0.55f, 0.2f}, {0.6f, 0.6f, 0.6f}};
+      memcpy(renView.typeColour, typeColour, sizeof(typeColour));
+      renView.ambient = 0.25f;
+      renView.background[0] = renView.background[1] = renView.background[2] = 0; renView.background[3] = 255;
+    }
     if (labelling) {
       compCsv = fopen(compFile, "w");
       if (!compCsv) throw std::runtime_error(std::string("cannot write ") + compFile);
@@ -421,6 +519,25 @@ int main(int argc, char** argv) {
                  largest, (long long)counts[0] - largest);
         }
         helper.report("_components: \t\t%9.3f ms\n");
+      }
+      if (rendering && (iterationCount + 1) % renEvery == 0) {
+        const unsigned renMask = (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE);
+        int64_t counts[2] = {0, 0};
+        if (renView.colourMode == 3) ocl_solver->labelComponents(INFINITY, renMask, counts);
+        ocl_solver->renderParticles(renView, nullptr, renMask, renThickness, counts);
+        const size_t pixels = (size_t)renView.width * (size_t)renView.height;
+        renRgba.resize(4 * pixels); renDepth.resize(pixels); renThick.resize(renThickness ? pixels : 0);
+        ocl_solver->readRender(renDepth.data(), nullptr, nullptr, renRgba.data(), renThickness ? renThick.data() : nullptr);
+        for (size_t p = 0; p < pixels; p++) memmove(&renRgba[3 * p], &renRgba[4 * p], 3);  // RGBA -> RGB in place
+        const std::string base = std::string(renDir) + "/frame_" + std::to_string(iterationCount + 1);
+        char header[64];
+        const int hn = snprintf(header, sizeof(header), "P6\n%d %d\n255\n", renView.width, renView.height);
+        if (!write_file(base + ".ppm", header, (size_t)hn, renRgba.data(), 3 * pixels)) throw std::runtime_error("cannot write " + base + ".ppm");
+        if (!write_file(base + ".depth.f32", header, 0, renDepth.data(), sizeof(float) * pixels)) throw std::runtime_error("cannot write " + base + ".depth.f32");
+        if (renThickness && !write_file(base + ".thickness.u32", header, 0, renThick.data(), sizeof(uint32_t) * pixels))
+          throw std::runtime_error("cannot write " + base + ".thickness.u32");
+        if (!quiet) printf("_render: drew %lld particles, covered %lld of %zu pixels -> %s.ppm\n", (long long)counts[0], (long long)counts[1], pixels, base.c_str());
+        helper.report("_render: \t\t%9.3f ms\n");
       }
       if (selecting && (iterationCount + 1) % selEvery == 0) {
         const int64_t n = ocl_solver->selectParticles(selRegionSeen ? selRegion : nullptr, selMask, selTerms.data(), (int)selTerms.size());

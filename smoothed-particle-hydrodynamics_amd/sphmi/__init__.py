@@ -61,6 +61,18 @@ class SphSelectTerm(C.Structure):
     _fields_ = [("field", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
 
 
+class SphRenderView(C.Structure):
+    """sph_render_view of include/sphmi.h (frames.render_view fills one)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("projection", C.c_int32),
+                ("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3),
+                ("scale", C.c_float), ("centre", C.c_float * 2), ("nearPlane", C.c_float), ("radius", C.c_float),
+                ("maxRadiusPx", C.c_float), ("colourMode", C.c_int32), ("field", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("typeColour", (C.c_float * 3) * 3), ("ambient", C.c_float), ("background", C.c_uint8 * 4)]
+
+
+RENDER_COLOUR_MODES = ("type", "density", "field", "label")  # sph_render_view.colourMode 0..3
+
+
 class SphError(RuntimeError):
     pass
 
@@ -119,7 +131,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
-                    "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure"] + _STAGE_FUNCS
+                    "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
+                    "sph_render_particles", "sph_read_render"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -215,6 +228,8 @@ def device_lib():
         L.sph_elastic_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sph_muscle_diagnostics.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_membrane_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_render_particles.argtypes = [C.c_void_p, C.POINTER(SphRenderView), C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.sph_read_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -745,6 +760,40 @@ class owHIPSolver:
         totals = np.zeros(4, np.float64)
         self._chk(self._L.sph_membrane_measure(self._h, _ptr(rec) if (records and M) else None, _ptr(totals)))
         return rec, totals
+
+    # --- particle rendering (sph_render_particles / sph_read_render) ---
+    def render(self, view, region=None, types=(1, 2), thickness=False):
+        """Draw the particles of `types` inside `region` (as diagnostics(); the box doubles as a cut-away) as shaded spheres
+        through `view` (an SphRenderView; frames.render_view makes one) into images kept on the device: nearest fragment per
+        pixel, ties to the lower sorted index, and with thickness=True the summed chord of every fragment. Returns (particles
+        drawn, covered pixels); rendered() reads the images. The state is the sorted state of the last completed step
+        (include/sphmi.h)."""
+        rg = None
+        if region is not None:
+            rg = np.ascontiguousarray(region, np.float32)
+            if rg.size != 6:
+                raise SphError("render: region must be (x0, y0, z0, x1, y1, z1)")
+        counts = np.zeros(2, np.int64)
+        self._render_shape = None  # (a failed render leaves no image behind)
+        self._chk(self._L.sph_render_particles(self._h, C.byref(view) if view is not None else None, _ptr(rg), type_mask(types),
+                                               1 if thickness else 0, _ptr(counts)))
+        self._render_shape = (int(view.height), int(view.width))
+        return int(counts[0]), int(counts[1])
+
+    def rendered(self, depth=True, index=True, orig_id=True, rgba=True, thickness=False):
+        """The images of the last render() as a dict of the ones asked for: depth float32[H, W] (+inf where uncovered), index
+        int32[H, W] (the winner's sorted index, -1), orig_id uint32[H, W] (0xFFFFFFFF), rgba uint8[H, W, 4] (the view's
+        background) and thickness uint32[H, W] (units of radius / 128; frames.thickness_in_scene_units). They stay readable
+        after further steps."""
+        shape = getattr(self, "_render_shape", None) or (1, 1)  # without a render the library reports SPH_ERR_ORDER
+        out = {}
+        if depth: out["depth"] = np.empty(shape, np.float32)
+        if index: out["index"] = np.empty(shape, np.int32)
+        if orig_id: out["orig_id"] = np.empty(shape, np.uint32)
+        if rgba: out["rgba"] = np.empty(shape + (4,), np.uint8)
+        if thickness: out["thickness"] = np.empty(shape, np.uint32)
+        self._chk(self._L.sph_read_render(self._h, *[_ptr(out.get(k)) for k in ("depth", "index", "orig_id", "rgba", "thickness")]))
+        return out
 
     # --- extras ---
     def step(self, iterationCount=0):

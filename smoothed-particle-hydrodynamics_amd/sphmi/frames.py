@@ -35,7 +35,15 @@ Elastic matter (owHIPSolver.elastic_measure / muscle_diagnostics / membrane_meas
 (float64[G + 1, 16] named by MUSCLE_FIELDS) into mean length, rest length and strain per group, `write_muscles_csv` /
 `read_muscles_csv` write and read the table `sphmi_run --elastic-out` writes, and `write_vtk_elastic` writes the elastic particles
 as a point cloud with their strain record (ELASTIC_FIELDS) as point data.
+
+Pictures (owHIPSolver.render / rendered): `look_at` makes the camera frame, `render_view` fills an SphRenderView that frames a
+bounding box, `write_ppm` / `read_ppm` (binary P6) and `write_png` / `read_png` (8-bit RGBA, zlib from the standard library) store
+the colour image, `thickness_in_scene_units` scales the thickness image; FIELD_RAMP and LABEL_PALETTE are the header's tables.
 """
+import math
+import struct
+import zlib
+
 import numpy as np
 
 
@@ -566,3 +574,193 @@ def write_vtk_elastic(path, position, orig_id, records):
             f.write(np.ascontiguousarray(rec[:, first:first + 3]).astype(">f4").tobytes())
         f.write(b"\n")
     return n
+
+
+# ---- particle rendering (owHIPSolver.render / rendered; include/sphmi.h, sph_render_particles) ----
+# SPH_RENDER_FIELD_RAMP: the five stops of colour mode 2 (blue, cyan, green, yellow, red)
+FIELD_RAMP = np.array([(0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 1, 0), (1, 0, 0)], np.float32)
+# SPH_RENDER_LABEL_PALETTE: the twelve colours of colour mode 3 (label % 12)
+LABEL_PALETTE = np.array([(0.90, 0.10, 0.10), (0.10, 0.50, 0.90), (0.20, 0.70, 0.20), (0.95, 0.60, 0.10), (0.60, 0.30, 0.80),
+                          (0.10, 0.75, 0.75), (0.95, 0.90, 0.20), (0.85, 0.35, 0.65), (0.55, 0.35, 0.15), (0.40, 0.85, 0.55),
+                          (0.30, 0.30, 0.65), (0.75, 0.75, 0.75)], np.float32)
+TYPE_COLOURS = ((0.2, 0.45, 0.9), (0.9, 0.55, 0.2), (0.6, 0.6, 0.6))  # render_view's default for liquid, elastic, boundary
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0)):
+    """(eye, right, up, forward) as float32[3] each, the orthonormal frame of a camera at `eye` looking at `target`:
+    forward = (target - eye) normalised, right = forward x up normalised, up = right x forward. Computed in float64 and narrowed
+    once. Raises when eye == target or `up` is parallel to the view direction."""
+    e = [float(x) for x in np.asarray(eye, np.float64).reshape(3)]
+    t = [float(x) for x in np.asarray(target, np.float64).reshape(3)]
+    up = [float(x) for x in np.asarray(up, np.float64).reshape(3)]
+    # plain double arithmetic in a fixed order, so that the C++ driver's frame has the same bits
+    f = [t[0] - e[0], t[1] - e[1], t[2] - e[2]]
+    n = math.sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2])
+    if not n > 0:
+        raise ValueError("look_at: eye and target coincide")
+    f = [x / n for x in f]
+    r = [f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]]
+    n = math.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
+    if not n > 1e-12:
+        raise ValueError("look_at: up is parallel to the view direction")
+    r = [x / n for x in r]
+    u = [r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]]
+    e, r, u, f = (np.array(x, np.float64) for x in (e, r, u, f))
+    return e.astype(np.float32), r.astype(np.float32), u.astype(np.float32), f.astype(np.float32)
+
+
+def render_view(bbox_min, bbox_max, width=640, height=480, eye=None, target=None, up=(0.0, 1.0, 0.0), perspective=True, scale=None,
+                radius=None, colour="density", field="speed", lo=0.0, hi=1.0, type_colours=TYPE_COLOURS, ambient=0.25,
+                background=(0, 0, 0, 255), near=0.0, max_radius_px=256.0, margin=0.95):
+    """An SphRenderView whose camera frames the box [bbox_min, bbox_max]: `target` defaults to the box centre, `eye` to a point
+    two box diagonals away from it towards (+x, +y, +z) weighted (0.6, 0.5, 1); the principal point is the image centre; `scale`
+    (pixels per scene unit, or the focal length in pixels with perspective=True) defaults to the largest value at which the eight
+    corners in front of the camera stay inside `margin` of the half image. `radius` (scene units) defaults to 1/60 of the box
+    diagonal. colour: "type", "density", "field" (with `field` a name of HIST_FIELDS or 0..6 and lo < hi) or "label"."""
+    import sphmi
+    lo3, hi3 = np.asarray(bbox_min, np.float64).reshape(3), np.asarray(bbox_max, np.float64).reshape(3)
+    centre, diag = 0.5 * (lo3 + hi3), float(np.linalg.norm(hi3 - lo3))
+    target = centre if target is None else np.asarray(target, np.float64).reshape(3)
+    if eye is None:
+        d = np.array([0.6, 0.5, 1.0])
+        eye = target + 2.0 * diag * d / np.linalg.norm(d)
+    e, r, u, f = look_at(eye, target, up)
+    if scale is None:
+        corners = np.array([[x, y, z] for x in (lo3[0], hi3[0]) for y in (lo3[1], hi3[1]) for z in (lo3[2], hi3[2])]) - e.astype(np.float64)
+        cx, cy, cz = corners @ r.astype(np.float64), corners @ u.astype(np.float64), corners @ f.astype(np.float64)
+        if perspective:
+            front = cz > 1e-9 * max(diag, 1.0)
+            cx, cy = np.abs(cx[front]) / cz[front], np.abs(cy[front]) / cz[front]
+        ex = max(float(np.max(np.abs(cx), initial=0.0)), 1e-30)
+        ey = max(float(np.max(np.abs(cy), initial=0.0)), 1e-30)
+        scale = margin * min(0.5 * width / ex, 0.5 * height / ey)
+    v = sphmi.SphRenderView()
+    v.width, v.height, v.projection = int(width), int(height), 1 if perspective else 0
+    for k in range(3):
+        v.eye[k], v.right[k], v.up[k], v.forward[k] = float(e[k]), float(r[k]), float(u[k]), float(f[k])
+    v.scale = float(scale)
+    v.centre[0], v.centre[1] = 0.5 * width, 0.5 * height
+    v.nearPlane, v.radius, v.maxRadiusPx = float(near), float(diag / 60.0 if radius is None else radius), float(max_radius_px)
+    if isinstance(colour, str):
+        if colour not in sphmi.RENDER_COLOUR_MODES:
+            raise ValueError("render_view: colour must be one of %s" % (sphmi.RENDER_COLOUR_MODES,))
+        colour = sphmi.RENDER_COLOUR_MODES.index(colour)
+    if isinstance(field, str):
+        if field not in sphmi.HIST_FIELDS:
+            raise ValueError("render_view: field must be one of %s" % (sphmi.HIST_FIELDS,))
+        field = sphmi.HIST_FIELDS.index(field)
+    v.colourMode, v.field, v.lo, v.hi = int(colour), int(field), float(lo), float(hi)
+    for t in range(3):
+        for k in range(3):
+            v.typeColour[t][k] = float(type_colours[t][k])
+    v.ambient = float(ambient)
+    for k in range(4):
+        v.background[k] = int(background[k])
+    return v
+
+
+def thickness_in_scene_units(thickness, radius):
+    """float64 image of the summed chord lengths in scene units: a thickness word counts radius / 128 (a fragment through the
+    middle of a sphere adds 256 = the diameter 2 * radius)."""
+    return np.asarray(thickness, np.float64) * (float(np.float32(radius)) / 128.0)
+
+
+def _rgb_image(image, channels):
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("an image must be uint8[H, W, 3] or uint8[H, W, 4]")
+    if a.shape[2] == channels:
+        return np.ascontiguousarray(a)
+    if channels == 3:
+        return np.ascontiguousarray(a[:, :, :3])
+    return np.ascontiguousarray(np.concatenate([a, np.full(a.shape[:2] + (1,), 255, np.uint8)], axis=2))
+
+
+def write_ppm(path, image):
+    """Binary PPM (P6, maxval 255) of uint8[H, W, 3] or the RGB of uint8[H, W, 4] (rendered()["rgba"]): the file
+    `sphmi_run --render-out` writes."""
+    a = _rgb_image(image, 3)
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(a.tobytes())
+    return a.shape[0], a.shape[1]
+
+
+def read_ppm(path):
+    """uint8[H, W, 3] of a binary P6 file with maxval 255 (comments in the header are skipped)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    tokens, at = [], 0
+    while len(tokens) < 4:
+        while at < len(data) and data[at:at + 1].isspace():
+            at += 1
+        if data[at:at + 1] == b"#":
+            while at < len(data) and data[at:at + 1] != b"\n":
+                at += 1
+            continue
+        start = at
+        while at < len(data) and not data[at:at + 1].isspace():
+            at += 1
+        if start == at:
+            raise ValueError("%s: truncated PPM header" % path)
+        tokens.append(data[start:at])
+    at += 1  # the single whitespace byte after maxval
+    if tokens[0] != b"P6" or int(tokens[3]) != 255:
+        raise ValueError("%s: not a binary P6 file with maxval 255" % path)
+    w, h = int(tokens[1]), int(tokens[2])
+    if len(data) - at != 3 * w * h:
+        raise ValueError("%s: %d bytes of pixels, %d expected" % (path, len(data) - at, 3 * w * h))
+    return np.frombuffer(data, np.uint8, 3 * w * h, at).reshape(h, w, 3).copy()
+
+
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def write_png(path, image, level=6):
+    """PNG of uint8[H, W, 4] (or [H, W, 3], made opaque): 8-bit RGBA, non-interlaced, every row with filter 0."""
+    a = _rgb_image(image, 4)
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 4 * w), np.uint8)  # the leading 0 of a row is its filter type
+    rows[:, 1:] = a.reshape(h, 4 * w)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+    with open(path, "wb") as f:
+        f.write(_PNG_MAGIC)
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(rows.tobytes(), level)))
+        f.write(chunk(b"IEND", b""))
+    return h, w
+
+
+def read_png(path):
+    """uint8[H, W, 4] of a PNG as write_png writes it (8-bit RGBA, non-interlaced, filter 0 on every row); anything else is
+    refused."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError("%s: not a PNG" % path)
+    at, header, body = 8, None, b""
+    while at + 12 <= len(data):
+        n, kind = struct.unpack(">I4s", data[at:at + 8])
+        chunk = data[at + 8:at + 8 + n]
+        crc, = struct.unpack(">I", data[at + 8 + n:at + 12 + n])
+        if len(chunk) != n or (zlib.crc32(kind + chunk) & 0xffffffff) != crc:
+            raise ValueError("%s: damaged %s chunk" % (path, kind.decode("latin-1")))
+        if kind == b"IHDR":
+            header = struct.unpack(">IIBBBBB", chunk)
+        elif kind == b"IDAT":
+            body += chunk
+        elif kind == b"IEND":
+            break
+        at += 12 + n
+    if header is None or header[2:] != (8, 6, 0, 0, 0):
+        raise ValueError("%s: only 8-bit non-interlaced RGBA is read" % path)
+    w, h = header[:2]
+    raw = np.frombuffer(zlib.decompress(body), np.uint8)
+    if raw.size != h * (1 + 4 * w):
+        raise ValueError("%s: %d bytes of rows, %d expected" % (path, raw.size, h * (1 + 4 * w)))
+    rows = raw.reshape(h, 1 + 4 * w)
+    if rows[:, 0].any():
+        raise ValueError("%s: a row uses a filter other than 0" % path)
+    return rows[:, 1:].reshape(h, w, 4).copy()
