@@ -443,6 +443,68 @@ int sph_elastic_measure(sph_solver* s, int32_t* sortedIndex /* host, numOfElasti
 int sph_muscle_diagnostics(sph_solver* s, double* out /* host, (muscleCount + 1) x SPH_MUSCLE_WORDS */);
 int sph_membrane_measure(sph_solver* s, float* out /* host, numOfMembranes x 8, or NULL */, double totals[4]);
 
+/* ---- Force decomposition (which matter pushes on which; no reference counterpart) ------------------------------
+ * The viscous, surface-tension and pressure accelerations of the step's kernels K7 (computeForcesAndInitPressure) and K12
+ * (computePressureForceAcceleration), recomputed once and kept apart by the class of the neighbour that exerted them.
+ * State: the sorted state of the last completed step and that step's neighbour rows, as sph_select_particles describes them:
+ * x, v, rho, rhoStar (the predicted density, second half of buffer "rho") and p of the last predict-correct iteration;
+ * row(i)[k] and dist(i)[k] are what sph_read_neighbor_rows returns for sorted particle i. hs = h * simulationScale,
+ * simScale = simulationScale, and massMu, closeRf, rho0delta, del2W, massGradW are the step's own constants: (float)(mass *
+ * viscosity); the smallest float >= 0.5 * (double)(float)(hs / 2); (float)(rho0 * delta); del2WviscosityCoefficient;
+ * (double)mass * gradWspikyCoefficient.
+ * CLASS of a neighbour j: c = (int)sortedPosition[j].w: 1 liquid, 2 elastic, 3 boundary.
+ * For a sorted particle i that is not a boundary particle, the slots k = 0..31 in ascending order, j = row(i)[k]; all
+ * arithmetic in float in the written order, no contraction, IEEE division and square root:
+ *   K7 terms, used when j != -1 && dist(i)[k] < hs, with rk = dist(i)[k] the STORED distance:
+ *     tv = ((v_j - v_i) * (hs - rk)) / rho_j  per component; v_j of a BOUNDARY neighbour is its wall normal, which the
+ *          boundary keeps in its velocity slot: the reference adds it as if it were a velocity (sphFluid.cl:653), and so does
+ *          this decomposition, because it reports what the step computed
+ *     tt = surfTensCoeff * (x_i - x_j)        per component (scene units, as the reference)
+ *   K12 terms, used when j != -1 && r < hs:
+ *     e = x_i - x_j;  r = sqrtf(ex*ex + ey*ey + ez*ez) * simScale
+ *     num = -(hs - r) * (hs - r) * 0.5f * (p_i + p_j);  when r < closeRf: num = -(hq - r) * (hq - r) * 0.5f * rho0delta,
+ *     hq = hs * 0.25f;  value = num / rhoStar_j;  tq = (value * (e * simScale)) / r  per component
+ * SUMS, sequential float sums that start at +0 and run in slot order (a slot that is not used leaves a sum untouched):
+ *   V, T, P over all used slots (the step's own sums); V_c, T_c, P_c over the used slots of class c; n_c = K7-used slots of class c.
+ * SCALES, the step's own: sF = massMu * (float)(del2W / (double)rho_i);  sP = (float)(massGradW / (double)rhoStar_i).
+ * RECORD, SPH_FORCE_WORDS floats per particle:
+ *   0..8     class 1 (what the liquid exerts): V_1*sF (xyz), T_1 (xyz), P_1*sP (xyz)
+ *   9..17    class 2 (elastic matter), 18..26 class 3 (boundary): the same nine words
+ *   27..29   n_1, n_2, n_3 as floats
+ *   30..32   aF = V*sF + g + T per component, exactly as K7 writes the acceleration (sx*scale + gravity_x + tx)
+ *   33..35   aP = P*sP, the pressure acceleration of the last K12          36..39   0
+ * A boundary particle's record is all zero. Values are ACCELERATIONS of particle i; the force is cfg.mass times them.
+ * Words 30..32 equal buffer "acceleration"[i] wherever the elastic-force stage added nothing (every liquid particle); words
+ * 33..35 equal its second half for every non-boundary particle.
+ * sph_force_measure: fromSelection = 0 writes one record for each of the N sorted particles, in sorted order; fromSelection = 1
+ * writes the records of the particles of the current selection (sph_select_particles), in its order, sph_read_selection's
+ * count of them, under sph_read_selection's SPH_ERR_ORDER rules (no selection, or the state has changed since). The records
+ * travel to the host in pieces through the sampling scratch.
+ * sph_force_diagnostics: selection, region rules, count limit and errors exactly as sph_diagnostics. Per-particle terms, floats
+ * widened to double, an unselected particle contributing +0.0, summed by the fixed tree reduce(a) of sph_diagnostics over all N
+ * terms in ascending sorted index. With visc_c, tens_c, pres_c the record's words of class c, per component and in float:
+ *   h_c = (visc_c + pres_c) + tens_c;  tau_c = x_i x h_c = (y*hz - z*hy, z*hx - x*hz, x*hy - y*hx);
+ *   w_c = (h_c.x*v_x + h_c.y*v_y) + h_c.z*v_z
+ * Record, SPH_FORCE_DIAG_WORDS doubles per region:
+ *   0        n, the number of selected particles       1..27    sum of record words 0..26
+ *   28..30   sum aF          31..33   sum aP           34..42   sum tau_c for c = 1, 2, 3 (torque about the origin per unit mass)
+ *   43..45   sum w_c (power per unit mass)             46..48   sum n_c             49..63   0
+ * SCOPE. Only K7 and K12 are decomposed. The spring and muscle accelerations are sph_elastic_measure's. The boundary hand-off
+ * inside integrate and the membrane interaction are position corrections, not forces, and are not reported. The reference's
+ * pressure term divides by rhoStar_j, so it is not antisymmetric: the reaction on class c is only approximately minus what
+ * class c exerts, and no word here pretends otherwise.
+ * Rules: blocking, on the solver's stream, read-only on every solver array (a mesh, a labelling, a selection and a render stay
+ * valid), not stages (no stage timing). SPH_ERR_ORDER before a step's neighbour, density, force and pressure-force stages have
+ * run. SPH_ERR_INVALID for a slab solver, null pointers, fromSelection outside 0..1, a typeMask of 0 or with bits outside 1..3,
+ * count outside 1..SPH_DIAG_MAX_REGIONS, a NaN region bound. A blown-up state is reported as by every blocking call. Device
+ * scratch, grown on demand and freed by sph_destroy: the sampling scratch (at most 64 MiB) and 512 bytes per region and 1024
+ * particles for the totals. */
+#define SPH_FORCE_WORDS 40
+#define SPH_FORCE_DIAG_WORDS 64
+int sph_force_measure(sph_solver* s, int32_t fromSelection, float* out /* host, N (or the selection's count) x 40 */);
+int sph_force_diagnostics(sph_solver* s, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
+                          uint32_t typeMask, double* out /* host, count x 64 */);
+
 /* ---- Particle rendering: depth, id, colour and thickness images (no reference counterpart in the solver: the
  * reference's viewer, owWorldSimulation.cpp, draws every particle each frame) ---------------------------------------------------
  * sph_render_particles draws the selected particles of the sorted state of the last completed step (the state sph_sample_*

@@ -1,5 +1,5 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, particle rendering. All of them read the sorted state of the last completed step and write
+// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, particle rendering. All of them read the sorted state of the last completed step and write
 // nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
 #include <string.h>
 
@@ -611,6 +611,75 @@ extern "C" int sph_membrane_measure(sph_solver* s, float* out, double totals[4])
   totals[2] = t[0] > 0.0 ? (double)mn : 0.0;
   totals[3] = t[0] > 0.0 ? (double)mx : 0.0;
   return sph_check_finite_state(s);
+}
+
+// ---------------------------------------------------------------------------------------------- force decomposition
+// The K7 and K12 accelerations by the class of the neighbour that exerted them (sph_forces.hip): per particle in pieces through
+// the sampling scratch, and as region totals through the diagnostics scratch. Blocking, read-only, no stage timing.
+static int force_check(sph_solver* s, uint32_t typeMask, const char* what) {
+  const int rc = sample_check(s, typeMask, what);
+  if (rc != SPH_OK) return rc;
+  NEED(s, P_FIND | P_FORCES, what);  // the rows, and the gather records K7 packs
+  return SPH_OK;
+}
+
+extern "C" int sph_force_measure(sph_solver* s, int32_t fromSelection, float* out) {
+  ENTER(s);
+  if (fromSelection != 0 && fromSelection != 1) { sph_set_error("sph_force_measure: fromSelection %d is not 0 or 1", fromSelection); return SPH_ERR_INVALID; }
+  size_t n = (size_t)std::max(s->d.N, 0);
+  const int32_t* list = nullptr;
+  if (fromSelection) {
+    if (!s->selValid) { sph_set_error("sph_force_measure: no selection has been made"); return SPH_ERR_ORDER; }
+    if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
+      sph_set_error("sph_force_measure: the solver's state has changed since the selection");
+      return SPH_ERR_ORDER;
+    }
+    n = (size_t)s->selCount;
+    list = (const int32_t*)s->selList.p;
+  }
+  int rc = force_check(s, 0xEu, "sph_force_measure");
+  if (rc != SPH_OK) return rc;
+  if (n == 0) return sph_check_finite_state(s);
+  if (!out) { sph_set_error("sph_force_measure: null pointer"); return SPH_ERR_INVALID; }
+  const size_t rec = sizeof(float) * SPH_FORCE_WORDS;
+  const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
+  rc = grow_scratch(s, s->sampleBuf, piece * rec);
+  if (rc != SPH_OK) return rc;
+  for (size_t first = 0; first < n; first += piece) {
+    const size_t m = std::min(piece, n - first);
+    rc = sphk_force_records(s, (int)first, (int)m, list ? list + first : nullptr, (float*)s->sampleBuf.p);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, out + first * SPH_FORCE_WORDS, s->sampleBuf.p, rec * m);
+    if (rc != SPH_OK) return rc;
+  }
+  return sph_check_finite_state(s);
+}
+
+extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
+  ENTER(s);
+  if (!regions6 || !out) { sph_set_error("sph_force_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_force_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  int rc = force_check(s, typeMask, "sph_force_diagnostics");
+  if (rc != SPH_OK) return rc;
+  DiagArgs a = {};
+  for (int r = 0; r < count; r++) {
+    rc = diag_region_ok(regions6 + 6 * r, "sph_force_diagnostics");
+    if (rc != SPH_OK) return rc;
+    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
+  }
+  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
+  // the per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the diagnostics scratch
+  const int chunks = s->d.N > 0 ? (s->d.N + 1023) / 1024 : 1;
+  const int pieceChunks = (int)std::min<size_t>((size_t)chunks, kSampleScratchBytes / sphk_force_terms_bytes(1));
+  rc = grow_scratch(s, s->sampleBuf, sphk_force_terms_bytes(pieceChunks));
+  if (rc != SPH_OK) return rc;
+  rc = grow_scratch(s, s->diagBuf, sizeof(double) * sphk_force_diag_scratch_doubles(s->d.N, count));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_force_diagnostics(s, a, (float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, records, sizeof(double) * SPH_FORCE_DIAG_WORDS * (size_t)count);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
 }
 
 // ---------------------------------------------------------------------------------------------- particle rendering

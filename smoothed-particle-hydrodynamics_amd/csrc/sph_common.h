@@ -354,6 +354,14 @@ struct RenderLayout { size_t head, keys, thick, depth, index, origId, rgba, thic
 RenderLayout sphk_render_layout(int width, int height, bool thickness, int N);
 // clear, splat, drain the queue of large splats, resolve; head words afterwards: [0] particles drawn, [1] covered pixels
 int sphk_render(sph_solver* s, const RenderArgs& a, bool thickness, void* buf);
+// sph_forces.hip (the K7 / K12 accelerations by the class of the neighbour that exerted them; read-only on every
+// solver array). Device pointers.
+// records (SPH_FORCE_WORDS floats each, 16-byte aligned) of the sorted particles first .. first + n, or of list[0..n) if given
+int sphk_force_records(sph_solver* s, int first, int n, const int32_t* list, float* out);
+size_t sphk_force_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_FORCE_DIAG_WORDS records
+size_t sphk_force_terms_bytes(int chunks);                   // the staged per-particle terms of `chunks` chunks of 1024 particles
+// the particles go through `terms` in pieces of pieceChunks chunks; *records: where the records land (in scratch)
+int sphk_force_diagnostics(sph_solver* s, const DiagArgs& a, float* terms, int pieceChunks, double* scratch, double** records);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

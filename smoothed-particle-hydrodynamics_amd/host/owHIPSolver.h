@@ -136,6 +136,16 @@ class owHIPSolver {
   void muscleDiagnostics(double* out) { check(sph_muscle_diagnostics(s_, out), "muscleDiagnostics"); }
   void membraneMeasure(float* out, double totals[4]) { check(sph_membrane_measure(s_, out, totals), "membraneMeasure"); }
 
+  // beyond the reference: who pushes on whom. forceMeasure writes SPH_FORCE_WORDS floats per sorted particle (fromSelection =
+  // false: particleCount records) or per particle of the current selection, in its order (fromSelection = true): the viscous,
+  // tension and pressure accelerations of the last step by the class of the neighbour that exerted them; forceDiagnostics writes
+  // their totals over `count` (1..16) regions, SPH_FORCE_DIAG_WORDS doubles each. Accelerations: times cfg.mass they are forces
+  // (include/sphmi.h, sph_force_measure / sph_force_diagnostics)
+  void forceMeasure(bool fromSelection, float* out) { check(sph_force_measure(s_, fromSelection ? 1 : 0, out), "forceMeasure"); }
+  void forceDiagnostics(const float* regions6, int count, unsigned int typeMask, double* out) {
+    check(sph_force_diagnostics(s_, regions6, count, typeMask, out), "forceDiagnostics");
+  }
+
   // beyond the reference: a picture. renderParticles draws the particles of typeMask inside region6 (or null) as shaded spheres
   // through `view` into depth, sorted-index, original-id, rgba and (wantThickness) thickness images kept on the device and fills
   // counts = {particles drawn, covered pixels}; readRender copies the images out, width x height words each (any pointer may be

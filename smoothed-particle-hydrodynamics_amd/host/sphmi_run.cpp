@@ -37,6 +37,10 @@
 //        one row per group (0 = the connections of no muscle): group, n, signal, mean length, mean rest length, mean strain, min
 //        and max strain as %.17g (sphmi.frames.read_muscles_csv); unless --quiet, one line per report with the total membrane area
 //        (sph_membrane_measure) and the global min, mean and max strain over all connections
+//   ... --forces-every K
+//        after every K-th step, sph_force_diagnostics over the whole scene: one line per call with the load in newtons (cfg.mass
+//        times the summed accelerations; viscous + pressure + tension). On --worm the liquid's load on the elastic matter (type 2)
+//        with its torque about the origin and its power; otherwise the boundary's and the liquid's load on the liquid (type 1)
 //   ... --render-every K --render-out DIR [--render-size W H] [--render-eye X Y Z] [--render-target X Y Z] [--render-up X Y Z]
 //       [--render-ortho S | --render-focal F] [--render-radius R] [--render-colour type|density|field:N:LO:HI|label]
 //       [--render-thickness]
@@ -149,6 +153,7 @@ int main(int argc, char** argv) {
   unsigned selMask = 0; float selRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   std::vector<sph_select_term> selTerms;
   int elaEvery = 0; bool elaSeen = false; const char* elaDir = nullptr;
+  int forEvery = 0; bool forSeen = false;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -157,6 +162,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
+    else if (!strcmp(argv[i], "--forces-every") && i + 1 < argc) { forEvery = atoi(argv[++i]); forSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -271,6 +277,8 @@ int main(int argc, char** argv) {
   const bool selecting = selSeen;
   if (elaSeen && (elaEvery <= 0 || !elaDir)) { fprintf(stderr, "--elastic-every K (> 0) and --elastic-out DIR go together\n"); return 2; }
   const bool measuringElastic = elaSeen;
+  if (forSeen && forEvery <= 0) { fprintf(stderr, "--forces-every K needs K > 0\n"); return 2; }
+  const bool measuringForces = forSeen;
   if (renSeen && (renEvery <= 0 || !renDir)) {
     fprintf(stderr, "--render-every K (> 0) and --render-out DIR go together (the other --render options need both)\n");
     return 2;
@@ -575,6 +583,23 @@ int main(int argc, char** argv) {
                  nAll > 0 ? eMin : 0.0, nAll > 0 ? eAll / nAll : 0.0, nAll > 0 ? eMax : 0.0, totals[1], totals[0]);
         }
         helper.report("_elastic: \t\t%9.3f ms\n");
+      }
+      if (measuringForces && (iterationCount + 1) % forEvery == 0) {
+        const float everything[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+        double r[SPH_FORCE_DIAG_WORDS];
+        const bool worm = numOfElasticP > 0;
+        ocl_solver->forceDiagnostics(everything, 1, worm ? (1u << SPH_ELASTIC_PARTICLE) : (1u << SPH_LIQUID_PARTICLE), r);
+        const double m = (double)cfg.mass;
+        // load of class c (1 liquid, 2 elastic, 3 boundary) on the selected particles: (viscous + pressure) + tension
+        auto load = [&](int c, int axis) { const double* q = r + 1 + 9 * (c - 1); return (m * q[axis] + m * q[6 + axis]) + m * q[3 + axis]; };
+        if (worm)
+          printf("_forces: step %d  liquid on elastic (n %.0f): load %.9e %.9e %.9e N  torque %.9e %.9e %.9e  power %.9e W  "
+                 "(pressure part %.9e %.9e %.9e N)\n", iterationCount + 1, r[0], load(1, 0), load(1, 1), load(1, 2), m * r[34], m * r[35],
+                 m * r[36], m * r[43], m * r[7], m * r[8], m * r[9]);
+        else
+          printf("_forces: step %d  on liquid (n %.0f): boundary load %.9e %.9e %.9e N  liquid load %.9e %.9e %.9e N\n", iterationCount + 1,
+                 r[0], load(3, 0), load(3, 1), load(3, 2), load(1, 0), load(1, 1), load(1, 2));
+        helper.report("_forces: \t\t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

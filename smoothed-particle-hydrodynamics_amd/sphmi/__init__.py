@@ -28,6 +28,8 @@ GRADIENT_WORDS = 32  # sph_sample_gradient_* record: the sample record, then gra
 ELASTIC_WORDS = 12  # sph_elastic_measure record (frames.ELASTIC_FIELDS)
 MUSCLE_WORDS = 16  # sph_muscle_diagnostics record (frames.MUSCLE_FIELDS)
 MEMBRANE_WORDS = 8  # sph_membrane_measure record: area, unit normal, centroid, 0 (frames.MEMBRANE_FIELDS)
+FORCE_WORDS = 40  # sph_force_measure record (frames.FORCE_FIELDS)
+FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -132,7 +134,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
                     "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
-                    "sph_render_particles", "sph_read_render"] + _STAGE_FUNCS
+                    "sph_render_particles", "sph_read_render", "sph_force_measure", "sph_force_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -228,6 +230,8 @@ def device_lib():
         L.sph_elastic_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sph_muscle_diagnostics.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_membrane_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_force_measure.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.sph_force_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_render_particles.argtypes = [C.c_void_p, C.POINTER(SphRenderView), C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
         L.sph_read_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
@@ -760,6 +764,34 @@ class owHIPSolver:
         totals = np.zeros(4, np.float64)
         self._chk(self._L.sph_membrane_measure(self._h, _ptr(rec) if (records and M) else None, _ptr(totals)))
         return rec, totals
+
+    # --- force decomposition (sph_force_measure / sph_force_diagnostics) ---
+    def force_measure(self, selection=False):
+        """The viscous, surface-tension and pressure accelerations the last completed step computed for every sorted particle
+        (selection=False: float32[N, 40]) or for the particles of the last select(), in its order (selection=True), kept apart
+        by the class of the neighbour that exerted them: records named by frames.FORCE_FIELDS -- nine words per class (liquid,
+        elastic, boundary), the three neighbour counts, the step's own viscous + gravity + tension acceleration and its
+        pressure acceleration. Accelerations of the particle; times cfg.mass they are forces (include/sphmi.h).
+        select(types=(2,)) then force_measure(selection=True) is the load on a body without exporting the liquid."""
+        n = getattr(self, "_selected", 0) if selection else self.N  # without a selection the library reports SPH_ERR_ORDER
+        out = np.zeros((n, FORCE_WORDS), np.float32)
+        self._chk(self._L.sph_force_measure(self._h, 1 if selection else 0, _ptr(out) if n else None))
+        return out
+
+    def force_diagnostics(self, regions=None, types=(1, 2)):
+        """Totals of force_measure() over the particles diagnostics() selects for each region: float64[R, 64] records named by
+        frames.FORCE_DIAG_FIELDS (count, the 27 per-class sums, the step's two accelerations, torque about the origin and power
+        per class, neighbour counts), added in the fixed tree of diagnostics(). frames.force_summary turns a record into
+        newtons, newton metres and watts."""
+        if regions is None:
+            regions = [(-np.inf,) * 3 + (np.inf,) * 3]
+        rg = np.ascontiguousarray(regions, np.float32)
+        if rg.size % 6:
+            raise SphError("force_diagnostics: regions must be [R, 6]")
+        rg = rg.reshape(-1, 6)
+        out = np.zeros((max(rg.shape[0], 1), FORCE_DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_force_diagnostics(self._h, _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
+        return out
 
     # --- particle rendering (sph_render_particles / sph_read_render) ---
     def render(self, view, region=None, types=(1, 2), thickness=False):

@@ -576,6 +576,75 @@ def write_vtk_elastic(path, position, orig_id, records):
     return n
 
 
+# ---- force decomposition (owHIPSolver.force_measure / force_diagnostics; include/sphmi.h, sph_force_measure) ----
+FORCE_CLASSES = ("liquid", "elastic", "boundary")  # class 1, 2, 3 of the neighbour that exerts the term
+_FORCE_KINDS = ("viscous", "tension", "pressure")
+FORCE_FIELDS = tuple("%s_%s_%s" % (c, k, a) for c in FORCE_CLASSES for k in _FORCE_KINDS for a in "xyz") + \
+    tuple("n_" + c for c in FORCE_CLASSES) + ("step_x", "step_y", "step_z", "step_pressure_x", "step_pressure_y", "step_pressure_z") + \
+    ("unused36", "unused37", "unused38", "unused39")
+FORCE_DIAG_FIELDS = ("n",) + tuple("sum_" + f for f in FORCE_FIELDS[:27]) + tuple("sum_" + f for f in FORCE_FIELDS[30:36]) + \
+    tuple("sum_torque_%s_%s" % (c, a) for c in FORCE_CLASSES for a in "xyz") + tuple("sum_power_" + c for c in FORCE_CLASSES) + \
+    tuple("sum_n_" + c for c in FORCE_CLASSES) + tuple("reserved%d" % w for w in range(49, 64))
+
+
+def force_summary(record, mass):
+    """A force_diagnostics() record as physical numbers, a dict of float64 values: the record's sums are accelerations, `mass`
+    (cfg.mass, kg per particle) times them are newtons. n; viscous, tension, pressure and load = (viscous + pressure) + tension
+    per class as [3, 3] arrays (rows liquid, elastic, boundary: what that class exerts on the selected particles); hydrodynamic =
+    the liquid's row of load (thrust and drag on a selected body); torque [3, 3] about the origin in newton x scene unit; power
+    [3] in watts; neighbors [3], the summed neighbour counts; step = mass x (sum of the step's own viscous + gravity + tension
+    acceleration + sum of its pressure acceleration)."""
+    r = np.asarray(record, np.float64).reshape(len(FORCE_DIAG_FIELDS))
+    m = float(mass)
+    per = r[1:28].reshape(3, 3, 3)  # class, kind, axis
+    out = {"n": r[0], "viscous": m * per[:, 0], "tension": m * per[:, 1], "pressure": m * per[:, 2]}
+    out["load"] = (out["viscous"] + out["pressure"]) + out["tension"]
+    out["hydrodynamic"] = out["load"][0].copy()
+    out["torque"] = m * r[34:43].reshape(3, 3)
+    out["power"] = m * r[43:46]
+    out["neighbors"] = r[46:49].copy()
+    out["step"] = m * (r[28:31] + r[31:34])
+    return out
+
+
+def write_vtk_forces(path, position, orig_id, records, mass=1.0):
+    """Legacy-VTK polydata (binary, big-endian like write_vtk) of the particles of force_measure(selection=True): one point per
+    record at position[orig_id] (`position`: [N, 4] in orig order; orig_id from selection()), with `id` (int), the three
+    neighbour counts (float scalars) and the vectors load_liquid, load_elastic, load_boundary = mass x ((viscous + pressure) +
+    tension) of that class, pressure_liquid = mass x the liquid's pressure term, and step = mass x (words 30..32 + words 33..35)."""
+    rec = np.asarray(records, np.float32).reshape(-1, len(FORCE_FIELDS))
+    ids = np.asarray(orig_id, np.uint32).reshape(-1)
+    if ids.shape[0] != rec.shape[0]:
+        raise ValueError("write_vtk_forces: one id per record expected")
+    pos = np.asarray(position, np.float32).reshape(-1, 4)[ids.astype(np.int64), :3]
+    n = rec.shape[0]
+    m = np.float32(mass)
+    per = rec[:, :27].reshape(n, 3, 3, 3)
+    load = m * ((per[:, :, 0] + per[:, :, 2]) + per[:, :, 1])
+    vectors = [("load_" + c, load[:, k]) for k, c in enumerate(FORCE_CLASSES)]
+    vectors += [("pressure_liquid", m * per[:, 0, 2]), ("step", m * (rec[:, 30:33] + rec[:, 33:36]))]
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi force decomposition\nBINARY\nDATASET POLYDATA\n")
+        f.write(("POINTS %d float\n" % n).encode())
+        f.write(pos.astype(">f4").tobytes())
+        f.write(("\nVERTICES %d %d\n" % (n, 2 * n)).encode())
+        cells = np.empty((n, 2), ">i4")
+        cells[:, 0] = 1
+        cells[:, 1] = np.arange(n)
+        f.write(cells.tobytes())
+        f.write(("\nPOINT_DATA %d\n" % n).encode())
+        f.write(b"SCALARS id int 1\nLOOKUP_TABLE default\n")
+        f.write(ids.astype(">i4").tobytes())
+        for k, c in enumerate(FORCE_CLASSES):
+            f.write(("\nSCALARS neighbors_%s float 1\nLOOKUP_TABLE default\n" % c).encode())
+            f.write(np.ascontiguousarray(rec[:, 27 + k]).astype(">f4").tobytes())
+        for name, v in vectors:
+            f.write(("\nVECTORS %s float\n" % name).encode())
+            f.write(np.ascontiguousarray(v).astype(">f4").tobytes())
+        f.write(b"\n")
+    return n
+
+
 # ---- particle rendering (owHIPSolver.render / rendered; include/sphmi.h, sph_render_particles) ----
 # SPH_RENDER_FIELD_RAMP: the five stops of colour mode 2 (blue, cyan, green, yellow, red)
 FIELD_RAMP = np.array([(0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 1, 0), (1, 0, 0)], np.float32)
