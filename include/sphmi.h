@@ -578,6 +578,59 @@ int sph_render_particles(sph_solver* s, const sph_render_view* view, const float
 int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba /* 4 per pixel */,
                     uint32_t* thickness);  /* host, width x height each; any may be NULL */
 
+/* ---- Particle editing: emitters, drains, gates (no reference counterpart: the reference fixes the particle set
+ * when the solver is made) -----------------------------------------------------------------------------------------------------
+ * Particles are removed from and appended to a live solver between two steps, within the capacity given to sph_create.
+ * STATE: the edits act on the CURRENT state, the one sph_read_position and sph_read_velocity return in original-id order, not on
+ * the sorted state one step behind it that the analysis calls read. Between two steps that pair of arrays IS the solver's state
+ * (the step rewrites every other array before it reads it), so an edited solver continues bit for bit like a solver newly
+ * created from the edited arrays.
+ * MARKING. sph_remove_region marks particle o when (int)position[o].w is 1, 2 or 3 with that bit set in typeMask and its float
+ * position lies in the half-open box x0 <= x < x1, y0 <= y < y1, z0 <= z < z1, compared as sph_diagnostics compares (bounds of
+ * +-infinity allowed, region6 == NULL is "everywhere"). There is no cell-key condition: the keys are stale at this point. With
+ * countOnly != 0 it only writes *removed, the number of marked particles: no solver array is touched, the analysis state and the
+ * edit map stay as they were ("is the inlet clear?"). sph_remove_selection marks origId[r] of every entry of the live selection
+ * of sph_select_particles, under the epoch rule of sph_read_selection. sph_remove_ids marks the listed original ids; duplicates
+ * are allowed; an id >= N is SPH_ERR_INVALID and nothing changes.
+ * REMOVAL is a stable compaction: the unmarked particles keep their relative order, survivor o gets the new id
+ * o - #(marked ids below o), and position and velocity move together. *removed receives the number removed.
+ * sph_read_edit_map returns newIdOfOld[o] for every o below the count BEFORE the last removal: the new id, or -1 for a removed
+ * particle. The map stays readable until the next stage, step or edit that changes the set; after that it is SPH_ERR_ORDER.
+ * Removing NOTHING succeeds and changes nothing: no array is touched, the analysis state, meshes, labellings and selections stay
+ * valid, and the edit map becomes the identity of the current count. Removing EVERYTHING is SPH_ERR_INVALID with the state
+ * untouched: a solver holds at least one particle.
+ * ELASTIC MATTER: with numOfElasticP > 0 a removal that marks an id below elasticOffset + numOfElasticP is SPH_ERR_INVALID, the
+ * error names the lowest such id, and nothing changes: the connection, membrane and muscle tables address original ids in that
+ * range, so those ids never shift. Liquid stored behind the elastic block (generated scenes: elastic, liquid, boundary; file-mode
+ * scenes: boundary, elastic, liquid) can be drained; walls stored in front of it cannot; elastic particles are never removed or
+ * added.
+ * ADDING. sph_add_particles appends count particles at ids N .. N+count-1 in the given order. Each gets the validation of
+ * sph_create (finite coordinates; inside the box with wide cell ids) and (int)w must be 1 or 3; the first offender is named and
+ * nothing is committed unless all pass. N + count > capacity is SPH_ERR_SIZE. The liquid signature of
+ * sph_slab_liquid_signature is folded exactly as sph_create folds it. sph_emit_lattice does the same without a host array: it
+ * appends dims[0]*dims[1]*dims[2] particles in ascending k = (iz*ny + iy)*nx + ix (x fastest) at origin + (float)i * spacing per
+ * axis (one float multiply, one float add, no contraction: the lattice of sph_sample_grid), position.w = typeValue, velocity =
+ * (vx, vy, vz, 0). The points are generated and validated on the device in the unused tail of the arrays; the count is raised,
+ * and *added written, only if every point passed.
+ * EVERY SUCCESSFUL EDIT THAT CHANGES THE SET updates the particle count (sph_particle_count), and invalidates the sorted state:
+ * every analysis call returns SPH_ERR_ORDER until a step has run, exactly as on a new solver, and sph_read_selection,
+ * sph_surface_normals and sph_component_diagnostics see a changed state. Until that step sph_read_density holds the previous
+ * step's values in the previous sorted order, and the sorted exports of sph_read_buffer are undefined: a removal stages through
+ * them (sortedPosition / sortedVelocity then hold the original-order arrays of before the removal, particleIndexBack the edit map). An outstanding sph_read_position_async finishes its device copy before an edit moves
+ * anything; sph_read_position_wait then delivers the positions and the byte count of the time of the request.
+ * Rules: blocking, on the solver's stream, not stages (no stage timing). SPH_ERR_INVALID for a slab solver, a typeMask of 0 or
+ * with bits outside 1..3, a NaN region bound, null pointers, negative counts or dims. A count of 0 is a no-op. A failed call
+ * leaves the solver exactly as it was. Device memory: 40 bytes per 256 particles for the scan (the layout of the selection's);
+ * the compaction is staged through the sorted arrays, which the invalidation has just made dead. */
+int sph_remove_region(sph_solver* s, const float* region6 /* host or NULL = everywhere */, uint32_t typeMask, int32_t countOnly,
+                      int64_t* removed);
+int sph_remove_selection(sph_solver* s, int64_t* removed); /* the current sph_select_particles list */
+int sph_remove_ids(sph_solver* s, const uint32_t* origIds /* host */, int64_t count, int64_t* removed);
+int sph_add_particles(sph_solver* s, const float* position4, const float* velocity4 /* host, count x 4 */, int32_t count);
+int sph_emit_lattice(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3], const float velocity[3],
+                     float typeValue /* position.w: 1.0f liquid */, int64_t* added);
+int sph_read_edit_map(sph_solver* s, int32_t* newIdOfOld /* host, the count BEFORE the last removal */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

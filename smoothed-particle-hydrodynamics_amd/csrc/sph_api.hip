@@ -202,7 +202,7 @@ static void free_all(sph_solver* s) {
                   d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
                   s->blockHist};
   for (void* p : ptrs) if (p) hipFree(p);
-  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable, &s->selBuf, &s->selList, &s->elasticBuf, &s->renderBuf}) if (b->p) hipFree(b->p);
+  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable, &s->selBuf, &s->selList, &s->elasticBuf, &s->renderBuf, &s->editBuf}) if (b->p) hipFree(b->p);
   if (s->slabHost) hipHostFree(s->slabHost);
   for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
   s->numHostRegs = 0;
@@ -724,7 +724,7 @@ extern "C" int sph_read_position_wait(sph_solver* s) {
   if (!s->copyPending) return s->blownUp ? report_blown_up(s) : SPH_OK;
   SPH_HIP(hipEventSynchronize(s->evCopyDone));
   s->copyPending = false;
-  if (s->copyViaStage) memcpy(s->copyUserDst, s->copyStage, sizeof(float4) * (size_t)s->d.N);
+  if (s->copyViaStage) memcpy(s->copyUserDst, s->copyStage, s->copyBytes);  // (the count at request time: an edit may have changed d.N)
   if (s->pinnedFlags[0]) {  // (the device counter keeps counting; it is cleared by the next blocking check)
     if (!s->blownUp) s->blownUp = s->pinnedFlags[0];
     return report_blown_up(s);
@@ -754,6 +754,7 @@ extern "C" int sph_read_position_async(sph_solver* s, float* out) {
     s->copyViaStage = true;
   }
   s->copyUserDst = out;
+  s->copyBytes = bytes;
   SPH_HIP(hipEventRecord(s->evReadReady, s->stream));
   SPH_HIP(hipStreamWaitEvent(s->copyStream, s->evReadReady, 0));
   SPH_HIP(hipMemcpyAsync(dst, s->d.posOrig, bytes, hipMemcpyDeviceToHost, s->copyStream));

@@ -780,3 +780,7 @@ extern "C" int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex
   SPH_HIP(hipStreamSynchronize(s->stream));
   return SPH_OK;
 }
+
+// (for sph_api_edit.hip, which shares the scratch growth and the region check)
+int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes) { return grow_scratch(s, b, bytes); }
+int sph_region_ok(const float* region6, const char* what) { return diag_region_ok(region6, what); }

@@ -1,4 +1,4 @@
-// What the two translation units of the C ABI share (sph_api.hip: solver lifetime, stages, step, read-back, slab;
+// What the translation units of the C ABI share (sph_api_edit.hip: particle editing; sph_api.hip: solver lifetime, stages, step, read-back, slab;
 // sph_api_analysis.hip: sampling, surfaces, gradients, diagnostics, components, selection): the order contract and the entry checks.
 #pragma once
 #include "sph_common.h"
@@ -21,6 +21,9 @@ enum { P_HASH = 1, P_SORT = 2, P_SORTPOST = 4, P_INDEXX = 8, P_INDEXPOST = 16, P
 int sph_d2h(sph_solver* s, void* dst, const void* src, size_t bytes);  // blocking copy to the host on s->stream
 int sph_check_finite_state(sph_solver* s);                             // synchronises the stream; SPH_ERR_INVALID once the state has blown up
 int sph_slab_finish(sph_solver* s, int32_t counts[4]);
+// (bodies in sph_api_analysis.hip)
+int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes);  // device buffer b grown to at least `bytes`
+int sph_region_ok(const float* region6, const char* what);         // SPH_ERR_INVALID for a NaN bound
 
 // (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
 #define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)

@@ -121,6 +121,7 @@ struct sph_solver {
   float* copyUserDst;                  // where the caller wants the data
   void* copyStage; size_t copyStageBytes;  // pinned staging, only for destinations that cannot be page-locked in place
   bool copyViaStage;
+  size_t copyBytes;                    // bytes of the read-back in flight (the particle count may change before it is waited for)
   struct HostReg { void* p; size_t bytes; };
   HostReg hostRegs[8]; int numHostRegs;    // caller buffers page-locked in place by hipHostRegister (released by sph_destroy)
   uint32_t* pinnedFlags;               // pinned: [0] copy of dbg[6] taken with the last asynchronous read-back
@@ -153,6 +154,12 @@ struct sph_solver {
   SphScratch renderBuf;
   bool renderValid; bool renderThickness;  // a successful render exists / it accumulated thickness
   int renderW, renderH, renderN;           // ... its size and the particle count its buffer was laid out for
+  // particle editing (sph_remove_* / sph_add_particles / sph_emit_lattice): the compaction's scan scratch, grown on demand. The
+  // id map of the last removal lies in backIndex (dead until the next step's sort), or is the identity (an empty removal).
+  SphScratch editBuf;
+  bool mapValid, mapIdentity;
+  int mapN;                                // the particle count before that removal
+  uint64_t mapEpoch;                       // stateEpoch right after it (sph_read_edit_map)
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
@@ -332,6 +339,36 @@ int sphk_select_scatter(sph_solver* s, void* scratch, uint32_t total, int32_t* l
 // records (SPH_SELECT_WORDS floats each, 16-byte aligned) and original ids of list[0..n); device pointers
 int sphk_select_gather(sph_solver* s, float ss2, const int32_t* list, int n, float* records, uint32_t* origId);
 int sphk_particle_measure(sph_solver* s, float ss2, int first, int n, float* out);  // out[r] = m of sorted particle first + r
+// where the pieces of the scan lie in its scratch (bytes from its start): mask[4 nb] (64-bit ballots) | blockCnt[nb] | off[nb] | totals (256 bytes)
+struct SelLayout {
+  size_t mask, blockCnt, off, totals, bytes;
+  int nb;
+};
+SelLayout sphk_select_layout(int N);
+int sphk_select_scan(sph_solver* s, void* scratch, int N);  // off = exclusive offsets of blockCnt, totals[0..1] = its sum
+// sph_edit.hip (adding and removing particles between steps; acts on the original-order state posOrig / velOrig)
+struct EditRegion {
+  float box[6];
+  uint32_t typeMask;
+};
+struct EditLattice {
+  float ox, oy, oz, sx, sy, sz;
+  int nx, ny, nz;
+  float vx, vy, vz, typeValue;
+  int wide;  // wide cell ids: a point outside the box fails
+  float xmin, xmax, ymin, ymax, zmin, zmax;
+};
+size_t sphk_edit_scratch_bytes(int N);  // the selection scan's layout and size
+int sphk_edit_mark_region(sph_solver* s, const EditRegion& a, void* scratch);  // writes every mask word
+int sphk_edit_clear_marks(sph_solver* s, void* scratch);
+// or-s the marks of ids[0..count) (list == nullptr) or of vals[list[0..count)] into the mask; device pointers
+int sphk_edit_mark_ids(sph_solver* s, const uint32_t* ids, const int32_t* list, int count, void* scratch);
+// survivors per block + scan: *totals = device words {survivors, 0, lowest marked id < protectEnd or 0xffffffff}
+int sphk_edit_count(sph_solver* s, int protectEnd, void* scratch, uint32_t** totals);
+// after sphk_edit_count, same scratch: the survivors of posOrig / velOrig in order into posOut / velOut, map[old id] = new id or -1
+int sphk_edit_scatter(sph_solver* s, void* scratch, uint32_t total, float4* posOut, float4* velOut, int32_t* map);
+// lattice points into posOrig / velOrig [N, N + count); *counters = device words {points that fail validation, the lowest such k}
+int sphk_edit_emit(sph_solver* s, const EditLattice& a, int count, void* scratch, uint32_t** counters);
 // sph_elastic_measure.hip (spring strain, muscle groups, membrane areas; read-only on every solver array)
 // per elastic particle, device pointers, any of the four may be null; *bad: one device word of error flags (ids out of range)
 int sphk_elastic_measure(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records, float* connections, uint32_t* bad);

@@ -195,11 +195,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_particle_measure(SphDev d, float 
 static size_t sel_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // scratch layout: mask[4 nb] (64-bit ballots) | blockCnt[nb] | off[nb] | totals
-struct SelLayout {
-  size_t mask, blockCnt, off, totals, bytes;
-  int nb;
-};
-static SelLayout sel_layout(int N) {
+SelLayout sphk_select_layout(int N) {
   SelLayout L;
   L.nb = N > 0 ? sph_blocks(N) : 1;
   size_t at = 0;
@@ -211,24 +207,30 @@ static SelLayout sel_layout(int N) {
   return L;
 }
 
-size_t sphk_select_scratch_bytes(int N) { return sel_layout(N).bytes; }
+size_t sphk_select_scratch_bytes(int N) { return sphk_select_layout(N).bytes; }
 
 int sphk_select_count(sph_solver* s, const SelectArgs& a, void* scratch, uint32_t** totals) {
-  const SelLayout L = sel_layout(s->d.N);
+  const SelLayout L = sphk_select_layout(s->d.N);
   char* base = (char*)scratch;
   hipLaunchKernelGGL(k_select_flags, dim3(L.nb), dim3(SPH_BLOCK), 0, s->stream, s->d, a, (unsigned long long*)(base + L.mask),
                      (uint32_t*)(base + L.blockCnt));
   SPH_HIP(hipGetLastError());
+  *totals = (uint32_t*)(base + L.totals);
+  return sphk_select_scan(s, scratch, s->d.N);
+}
+
+int sphk_select_scan(sph_solver* s, void* scratch, int N) {
+  const SelLayout L = sphk_select_layout(N);
+  char* base = (char*)scratch;
   hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SEL_SCAN_THREADS), 0, s->stream, (const uint32_t*)(base + L.blockCnt), L.nb,
                      (uint32_t*)(base + L.off), (uint32_t*)(base + L.totals));
   SPH_HIP(hipGetLastError());
-  *totals = (uint32_t*)(base + L.totals);
   return SPH_OK;
 }
 
 int sphk_select_scatter(sph_solver* s, void* scratch, uint32_t total, int32_t* list) {
   if (total == 0) return SPH_OK;
-  const SelLayout L = sel_layout(s->d.N);
+  const SelLayout L = sphk_select_layout(s->d.N);
   char* base = (char*)scratch;
   hipLaunchKernelGGL(k_select_scatter, dim3(L.nb), dim3(SPH_BLOCK), 0, s->stream, s->d.N, (const unsigned long long*)(base + L.mask),
                      (const uint32_t*)(base + L.off), total, list);

@@ -157,6 +157,43 @@ class owHIPSolver {
     check(sph_read_render(s_, depth, sortedIndex, origId, rgba, thickness), "readRender");
   }
 
+  // beyond the reference: the particle set changes between two steps (emitters, drains, gates). removeRegion removes the
+  // particles of typeMask inside region6 (or null = everywhere) from the current state (read_position_buffer's order), or only
+  // counts them (countOnly); removeSelection those of the current selection; removeIds the listed original ids. The survivors keep
+  // their order, readEditMap tells where each went (new id or -1; as many ints as there were particles before the removal).
+  // addParticles appends count particles (x, y, z, type 1 or 3 / vx, vy, vz, 0), emitLattice a lattice generated on the device,
+  // within config().capacity. An edit that changes the set changes particleCount() (size read_*_buffer's arrays from it) and
+  // invalidates the analysis calls until the next step (include/sphmi.h, sph_remove_* / sph_add_particles / sph_emit_lattice)
+  int64_t removeRegion(const float* region6, unsigned int typeMask, bool countOnly = false) {
+    int64_t removed = 0;
+    check(sph_remove_region(s_, region6, typeMask, countOnly ? 1 : 0, &removed), "removeRegion");
+    return removed;
+  }
+  int64_t removeSelection() {
+    int64_t removed = 0;
+    check(sph_remove_selection(s_, &removed), "removeSelection");
+    return removed;
+  }
+  int64_t removeIds(const uint32_t* origIds, int64_t count) {
+    int64_t removed = 0;
+    check(sph_remove_ids(s_, origIds, count, &removed), "removeIds");
+    return removed;
+  }
+  void addParticles(const float* position4, const float* velocity4, int count) {
+    check(sph_add_particles(s_, position4, velocity4, count), "addParticles");
+  }
+  int64_t emitLattice(const float origin[3], const float spacing[3], const int dims[3], const float velocity[3], float typeValue = 1.0f) {
+    int64_t added = 0;
+    check(sph_emit_lattice(s_, origin, spacing, dims, velocity, typeValue, &added), "emitLattice");
+    return added;
+  }
+  void readEditMap(int32_t* newIdOfOld) { check(sph_read_edit_map(s_, newIdOfOld), "readEditMap"); }
+  int particleCount() {
+    const int n = sph_particle_count(s_);
+    if (n < 0) check(n, "particleCount");
+    return n;
+  }
+
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }
   sph_solver* handle() { return s_; }

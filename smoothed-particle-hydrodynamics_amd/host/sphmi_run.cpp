@@ -52,6 +52,17 @@
 //        --render-ortho S: orthographic, S pixels per scene unit; --render-focal F: perspective, focal length F pixels (default:
 //        perspective with F = W); the principal point is the image centre, the sphere radius defaults to r0 / 2, N is a field
 //        number 0..6 of sph_histogram; label colours need no other option (the components of the drawn types are labelled first)
+//   ... --capacity N --emit-lattice OX OY OZ NX NY NZ [--emit-spacing S] [--emit-velocity VX VY VZ] [--emit-every K] [--emit-until STEP]
+//       --drain-region X0 Y0 Z0 X1 Y1 Z1 [--drain-types T...] [--drain-every K] [--drain-at STEP]
+//        particles appear and disappear between steps (sph_emit_lattice / sph_remove_region). Edits happen BEFORE
+//        step S (S = steps done so far). Emitter: an NX x NY x NZ lattice of liquid at (OX, OY, OZ), spacing S (scene units;
+//        default 0.93 r0) with velocity VX VY VZ (default 0), before every step S with S % K == 0 (K default 1) and S < STEP
+//        (default: every step of the run); the solver needs room: --capacity N (at least the largest count reached). Drain: the
+//        particles of the given types (default 1; "inf" / "-inf" are accepted as bounds, --drain-region may be left out =
+//        everywhere) are removed before every step S > 0 with S % K == 0 (--drain-every) and before step STEP (--drain-at); a
+//        gate that opens at step 200 is `--drain-types 3 --drain-region ... --drain-at 200`. The drain runs before the emitter.
+//        Each step with an edit prints `_edit: step S removed R added A particles N`. With these options the position read-back
+//        is the blocking one, and --out holds the final count of particles.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -158,8 +169,34 @@ int main(int argc, char** argv) {
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
   float renOrtho = 0.f, renFocal = 0.f, renRadius = 0.f; bool renOrthoSeen = false, renFocalSeen = false, renRadiusSeen = false;
+  int capacity = 0; bool capSeen = false;
+  bool emitSeen = false, emitLatSeen = false; float emitOrigin[3] = {0, 0, 0}, emitSpacing = 0.f, emitVel[3] = {0, 0, 0};
+  int emitDims[3] = {0, 0, 0}, emitEvery = 1, emitUntil = -1;
+  bool drainSeen = false, drainRegionSeen = false, drainTypesSeen = false; unsigned drainMask = 0; int drainEvery = 0, drainAt = -1;
+  float drainRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
+    else if (!strcmp(argv[i], "--capacity") && i + 1 < argc) { capacity = atoi(argv[++i]); capSeen = true; }
+    else if (!strcmp(argv[i], "--emit-lattice") && i + 6 < argc) {
+      for (int k = 0; k < 3; k++) emitOrigin[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) emitDims[k] = atoi(argv[++i]);
+      emitSeen = emitLatSeen = true;
+    }
+    else if (!strcmp(argv[i], "--emit-spacing") && i + 1 < argc) { emitSpacing = (float)atof(argv[++i]); emitSeen = true; }
+    else if (!strcmp(argv[i], "--emit-velocity") && i + 3 < argc) { for (int k = 0; k < 3; k++) emitVel[k] = (float)atof(argv[++i]); emitSeen = true; }
+    else if (!strcmp(argv[i], "--emit-every") && i + 1 < argc) { emitEvery = atoi(argv[++i]); emitSeen = true; }
+    else if (!strcmp(argv[i], "--emit-until") && i + 1 < argc) { emitUntil = atoi(argv[++i]); emitSeen = true; }
+    else if (!strcmp(argv[i], "--drain-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) drainRegion[k] = (float)atof(argv[++i]); drainSeen = drainRegionSeen = true; }
+    else if (!strcmp(argv[i], "--drain-every") && i + 1 < argc) { drainEvery = atoi(argv[++i]); drainSeen = true; }
+    else if (!strcmp(argv[i], "--drain-at") && i + 1 < argc) { drainAt = atoi(argv[++i]); drainSeen = true; }
+    else if (!strcmp(argv[i], "--drain-types")) {
+      drainSeen = drainTypesSeen = true;
+      while (i + 1 < argc && argv[i + 1][0] != '-') {
+        const int t = atoi(argv[++i]);
+        if (t < 1 || t > 3) { fprintf(stderr, "--drain-types: a type is 1 (liquid), 2 (elastic) or 3 (boundary)\n"); return 2; }
+        drainMask |= 1u << t;
+      }
+    }
     else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
     else if (!strcmp(argv[i], "--forces-every") && i + 1 < argc) { forEvery = atoi(argv[++i]); forSeen = true; }
@@ -284,6 +321,22 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool rendering = renSeen;
+  if (capSeen && capacity <= 0) { fprintf(stderr, "--capacity N: N must be > 0\n"); return 2; }
+  if (emitSeen && (!emitLatSeen || emitDims[0] <= 0 || emitDims[1] <= 0 || emitDims[2] <= 0 || emitEvery <= 0)) {
+    fprintf(stderr, "--emit-lattice OX OY OZ NX NY NZ (NX, NY, NZ > 0) is needed by the other --emit options; --emit-every K needs K > 0\n");
+    return 2;
+  }
+  if (emitSeen && !capSeen) { fprintf(stderr, "--emit-lattice needs --capacity N: the solver's buffers are sized when it is made\n"); return 2; }
+  if (emitSeen && (std::isnan(emitSpacing) || emitSpacing < 0.f)) { fprintf(stderr, "--emit-spacing S: S must be > 0\n"); return 2; }
+  if (drainSeen && drainEvery <= 0 && drainAt < 0) { fprintf(stderr, "a drain needs --drain-every K (> 0) or --drain-at STEP (>= 0)\n"); return 2; }
+  if (drainTypesSeen && !drainMask) { fprintf(stderr, "--drain-types needs at least one type\n"); return 2; }
+  if (!drainMask) drainMask = 1u << SPH_LIQUID_PARTICLE;
+  for (float b : drainRegion)
+    if (std::isnan(b)) { fprintf(stderr, "--drain-region: a bound is not a number\n"); return 2; }
+  const bool emitting = emitSeen, draining = drainSeen, editing = emitSeen || drainSeen;
+  // the host buffer of the asynchronous read-back is page-locked in place at its first size: with a changing count the driver
+  // reads the positions the blocking way
+  if (editing) blockingRead = true;
   sph_render_view renView;
   memset(&renView, 0, sizeof(renView));
   if (rendering) {
@@ -345,6 +398,13 @@ int main(int argc, char** argv) {
       fprintf(stderr, "usage: sphmi_run (--position P --velocity V | --box X Y Z --lattice A B C | --worm [--muscles]) [--steps N] [--staged] [--wide] [--out F]\n");
       return 2;
     }
+    if (capSeen) {
+      if (capacity < cfg.particleCount) { fprintf(stderr, "--capacity %d is below the scene's %d particles\n", capacity, cfg.particleCount); return 2; }
+      cfg.capacity = capacity;
+    }
+    if (emitting && emitSpacing == 0.f) emitSpacing = 0.93f * cfg.r0;
+    if (emitUntil < 0) emitUntil = steps;
+    int particleCount = cfg.particleCount;  // changes with every edit
     if (measuringElastic && numOfElasticP == 0) { fprintf(stderr, "--elastic-every needs a scene with elastic matter (--worm)\n"); return 2; }
     printf("particles: %d (liquid %d, elastic %d, boundary %d), grid %d x %d x %d\n", cfg.particleCount, numOfLiquidP,
            numOfElasticP, numOfBoundaryP, cfg.gridCellsX, cfg.gridCellsY, cfg.gridCellsZ);
@@ -412,6 +472,25 @@ int main(int argc, char** argv) {
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
       helper.refresh();
       if (!quiet) printf("\n[[ Step %d ]]\n", iterationCount);
+      if (editing) {  // between two steps: the drain first, then the emitter
+        int64_t removed = 0, added = 0;
+        bool edited = false;
+        if (draining && ((drainEvery > 0 && iterationCount > 0 && iterationCount % drainEvery == 0) || iterationCount == drainAt)) {
+          removed = ocl_solver->removeRegion(drainRegionSeen ? drainRegion : nullptr, drainMask);
+          edited = true;
+        }
+        if (emitting && iterationCount % emitEvery == 0 && iterationCount < emitUntil) {
+          const float sp[3] = {emitSpacing, emitSpacing, emitSpacing};
+          added = ocl_solver->emitLattice(emitOrigin, sp, emitDims, emitVel, 1.0f);
+          edited = true;
+        }
+        if (edited) {
+          particleCount = ocl_solver->particleCount();
+          position_cpp.resize(4 * (size_t)particleCount);
+          printf("_edit: step %d removed %lld added %lld particles %d\n", iterationCount, (long long)removed, (long long)added, particleCount);
+          helper.report("_edit: \t\t\t%9.3f ms\n");
+        }
+      }
       if (staged) {  // owPhysicsFluidSimulator.cpp:88-113, call for call
         ocl_solver->_runClearBuffers();       sph_synchronize(ocl_solver->handle()); helper.report("_runClearBuffers: \t%9.3f ms\n");
         ocl_solver->_runHashParticles();      sph_synchronize(ocl_solver->handle()); helper.report("_runHashParticles: \t%9.3f ms\n");
@@ -558,7 +637,7 @@ int main(int argc, char** argv) {
                   fwrite(selRecords.data(), sizeof(float), selRecords.size(), f) == selRecords.size();
         if (f && fclose(f) != 0) ok = false;
         if (!ok) throw std::runtime_error("cannot write " + path);
-        if (!quiet) printf("_select: selected %lld of %d\n", (long long)n, cfg.particleCount);
+        if (!quiet) printf("_select: selected %lld of %d\n", (long long)n, particleCount);
         helper.report("_select: \t\t%9.3f ms\n");
       }
       if (measuringElastic && (iterationCount + 1) % elaEvery == 0) {
@@ -613,7 +692,7 @@ int main(int argc, char** argv) {
       total += helper.elapsed();
     }
     printf("%d steps, %.3f ms/step incl. the 16N-byte position read-back, %.3e particle-steps/s\n", steps, total / steps,
-           cfg.particleCount * 1000.0 / (total / steps));
+           particleCount * 1000.0 / (total / steps));
     if (outFile) {
       FILE* f = fopen(outFile, "wb");
       if (!f || fwrite(position_cpp.data(), sizeof(float), position_cpp.size(), f) != position_cpp.size()) throw std::runtime_error("cannot write --out file");

@@ -134,7 +134,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
                     "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
-                    "sph_render_particles", "sph_read_render", "sph_force_measure", "sph_force_diagnostics"] + _STAGE_FUNCS
+                    "sph_render_particles", "sph_read_render", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
+                    "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -234,6 +235,12 @@ def device_lib():
         L.sph_force_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_render_particles.argtypes = [C.c_void_p, C.POINTER(SphRenderView), C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
         L.sph_read_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_remove_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.sph_remove_selection.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_remove_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.sph_add_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.sph_emit_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        L.sph_read_edit_map.argtypes = [C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -827,6 +834,87 @@ class owHIPSolver:
         self._chk(self._L.sph_read_render(self._h, *[_ptr(out.get(k)) for k in ("depth", "index", "orig_id", "rgba", "thickness")]))
         return out
 
+    # --- particle editing (sph_remove_* / sph_add_particles / sph_emit_lattice / sph_read_edit_map) ---
+    def _edited(self):
+        """Every wrapper sizes its outputs from self.N: refresh it, and forget what an edit invalidated."""
+        n = self._L.sph_particle_count(self._h)
+        if n != self.N:
+            self._selected = 0
+            self._components = 0
+        self.N = n
+        return n
+
+    def remove_region(self, region=None, types=(1,), count_only=False):
+        """Remove the particles of `types` whose current position (read_position_buffer's, original order) lies in the half-open
+        box `region` (x0, y0, z0, x1, y1, z1; +-inf allowed; None = everywhere). The survivors keep their order; edit_map()
+        tells where each went. Returns the number removed. With count_only=True nothing changes and the number that WOULD be
+        removed is returned. An edit that changes the set invalidates the analysis state until the next step (include/sphmi.h)."""
+        rg = None
+        if region is not None:
+            rg = np.ascontiguousarray(region, np.float32)
+            if rg.size != 6:
+                raise SphError("remove_region: region must be (x0, y0, z0, x1, y1, z1)")
+        removed = np.zeros(1, np.int64)
+        n0 = self.N
+        self._chk(self._L.sph_remove_region(self._h, _ptr(rg), type_mask(types), 1 if count_only else 0, _ptr(removed)))
+        if not count_only:
+            self._map_len = n0
+            self._edited()
+        return int(removed[0])
+
+    def remove_selection(self):
+        """Remove the particles of the last select() (refused once the solver has stepped since). Returns the number removed."""
+        removed = np.zeros(1, np.int64)
+        n0 = self.N
+        self._chk(self._L.sph_remove_selection(self._h, _ptr(removed)))
+        self._map_len = n0
+        self._edited()
+        return int(removed[0])
+
+    def remove_ids(self, ids):
+        """Remove the particles with the listed original ids (duplicates allowed; an id >= N is refused). Returns the number
+        removed."""
+        a = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise SphError("remove_ids: ids must be unsigned 32-bit integers")
+        a = a.astype(np.uint32)
+        removed = np.zeros(1, np.int64)
+        n0 = self.N
+        self._chk(self._L.sph_remove_ids(self._h, _ptr(a) if a.size else None, a.size, _ptr(removed)))
+        self._map_len = n0
+        self._edited()
+        return int(removed[0])
+
+    def add_particles(self, position, velocity):
+        """Append particles ([K, 4] each: x, y, z, type 1 or 3 / vx, vy, vz, 0) at ids N .. N+K-1. Returns the new count.
+        Validated as the constructor validates; refused beyond cfg.capacity."""
+        pos = np.ascontiguousarray(position, np.float32).reshape(-1, 4)
+        vel = np.ascontiguousarray(velocity, np.float32).reshape(-1, 4)
+        if pos.shape != vel.shape:
+            raise SphError("add_particles: position and velocity must both be [K, 4]")
+        k = pos.shape[0]
+        self._chk(self._L.sph_add_particles(self._h, _ptr(pos) if k else None, _ptr(vel) if k else None, k))
+        return self._edited()
+
+    def emit_lattice(self, origin, spacing, dims, velocity=(0, 0, 0), type_value=1.0):
+        """Append the lattice origin + (float)i * spacing, i < dims = (nx, ny, nz), x fastest, generated on the device, every
+        particle with position.w = type_value and the given velocity. Returns the number added."""
+        o, sp, dm = _lattice(origin, spacing, dims)
+        v = np.ascontiguousarray(velocity, np.float32).reshape(3)
+        added = np.zeros(1, np.int64)
+        self._chk(self._L.sph_emit_lattice(self._h, _ptr(o), _ptr(sp), _ptr(dm), _ptr(v), float(np.float32(type_value)), _ptr(added)))
+        self._edited()
+        return int(added[0])
+
+    def edit_map(self):
+        """int32[count before the last removal]: the new id of every old particle, -1 for a removed one. Refused once a stage,
+        a step or another edit has run since. frames.track_ids carries particle identities across edits with it."""
+        # the count before the last SUCCESSFUL removal: a refused one leaves the library's map, and this length, as they were
+        n = getattr(self, "_map_len", 0)  # 0 without a removal: the library reports SPH_ERR_ORDER
+        out = np.empty(max(n, 1), np.int32)
+        self._chk(self._L.sph_read_edit_map(self._h, _ptr(out)))
+        return out[:n]
+
     # --- extras ---
     def step(self, iterationCount=0):
         """Fused fast path == the stage sequence of simulationStep()."""
@@ -960,6 +1048,10 @@ class owPhysicsFluidSimulator:
             s._run_pcisph_integrate(self.iterationCount)
             s._run_clearMembraneBuffers(); s._run_computeInteractionWithMembranes()
             s._run_computeInteractionWithMembranes_finalize()
+        if read_back and self.position_cpp.shape[0] != s.N:  # an edit changed the particle count
+            # (waits for a copy in flight, then releases the page lock read_position_buffer_async put on the old array)
+            s._chk(s._L.sph_host_unregister(s._h, _ptr(self.position_cpp)))
+            self.position_cpp = np.empty((s.N, 4), np.float32)
         if read_back and async_read_back:  # the copy overlaps the next step; getPosition_cpp() waits for it
             s.read_position_buffer_async(self.position_cpp)
         elif read_back:

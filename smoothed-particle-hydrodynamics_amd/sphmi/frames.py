@@ -833,3 +833,30 @@ def read_png(path):
     if rows[:, 0].any():
         raise ValueError("%s: a row uses a filter other than 0" % path)
     return rows[:, 1:].reshape(h, w, 4).copy()
+
+
+# ----------------------------------------------------------------------------- particle identities across edits
+def track_ids(ids, edit_map=None, added=0, next_id=None):
+    """Persistent particle identities across an edit of the particle set (owHIPSolver.remove_* / add_particles / emit_lattice).
+    `ids` (int64[N]) names the particle at every original id before the edit; identities of a new run are np.arange(N).
+    `edit_map` is owHIPSolver.edit_map() of a removal (None: nothing was removed): survivors keep their identity at their new
+    id. `added` particles were appended after that and get the fresh identities next_id, next_id + 1, ... (next_id None: one
+    above the largest identity in `ids`, or 0 for an empty set; pass the value returned by the previous call so that an identity
+    of a removed particle is never given out again). Returns (ids after the edit, the next unused identity). Joining two
+    frames on these identities gives trajectories by particle whatever was drained or emitted in between."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if next_id is None:
+        next_id = int(ids.max()) + 1 if ids.size else 0
+    if edit_map is not None:
+        m = np.asarray(edit_map, np.int64).reshape(-1)
+        if m.size != ids.size:
+            raise ValueError("track_ids: the edit map describes %d particles, ids %d" % (m.size, ids.size))
+        keep = m >= 0
+        out = np.empty(int(keep.sum()), np.int64)
+        out[m[keep]] = ids[keep]
+        ids = out
+    added = int(added)
+    if added < 0:
+        raise ValueError("track_ids: added must be >= 0")
+    fresh = np.arange(next_id, next_id + added, dtype=np.int64)
+    return np.concatenate([ids, fresh]), int(next_id) + added
