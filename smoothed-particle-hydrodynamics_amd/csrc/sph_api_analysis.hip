@@ -15,6 +15,15 @@
 // so that the scratch stays bounded whatever the request.
 static const size_t kSampleScratchBytes = (size_t)64 << 20;
 
+// region6 (or, when null, everything) into box, a NaN refused: the region half of sph_fill_selector, and the region lists' rule
+static int region_fill(float box[6], const float* region6, const char* what) {
+  for (int k = 0; k < 6; k++) {
+    box[k] = region6 ? region6[k] : (k < 3 ? -INFINITY : INFINITY);
+    if (std::isnan(box[k])) { sph_set_error("%s: a region bound is NaN", what); return SPH_ERR_INVALID; }
+  }
+  return SPH_OK;
+}
+
 // The argument and order rules every analysis call shares; a != nullptr: the constants of the sampling contract too.
 static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleArgs* a = nullptr) {
   if (s->hasSlab) { sph_set_error("%s: sampling a slab solver is not supported", what); return SPH_ERR_INVALID; }
@@ -28,8 +37,33 @@ static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, Samp
   return SPH_OK;
 }
 
+int sph_fill_selector(SphSelector* sel, const float* region6, uint32_t typeMask, const char* what) {
+  if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("%s: typeMask must be a non-empty set of bits 1..3", what); return SPH_ERR_INVALID; }
+  sel->typeMask = typeMask;
+  return region_fill(sel->box, region6, what);
+}
+
+int sph_labels_current(sph_solver* s, const char* what, const int32_t** labels) {
+  if (!s->ccValid) { sph_set_error("%s: no labelling has been made (sph_label_components)", what); return SPH_ERR_ORDER; }
+  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
+    sph_set_error("%s: the solver's state has changed since the labelling", what);
+    return SPH_ERR_ORDER;
+  }
+  *labels = sphk_components_labels(s->ccBuf.p, s->ccN);
+  return SPH_OK;
+}
+
+int sph_selection_current(sph_solver* s, const char* what) {
+  if (!s->selValid) { sph_set_error("%s: no selection has been made", what); return SPH_ERR_ORDER; }
+  if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
+    sph_set_error("%s: the solver's state has changed since the selection", what);
+    return SPH_ERR_ORDER;
+  }
+  return SPH_OK;
+}
+
 // device buffer b grown to at least `bytes` (the old one is freed once the stream has finished with it)
-static int grow_scratch(sph_solver* s, SphScratch& b, size_t bytes) {
+int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes) {
   if (b.bytes >= bytes) return SPH_OK;
   if (b.p) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(b.p); }
   b.p = nullptr; b.bytes = 0;
@@ -45,7 +79,7 @@ template <typename Launch>
 static int sample_point_runs(sph_solver* s, const float* points4, int count, int words, float* out, Launch launch) {
   const size_t rec = sizeof(float) * words, perPoint = sizeof(float4) + rec;
   const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perPoint);
-  int rc = grow_scratch(s, s->sampleBuf, (size_t)piece * perPoint);
+  int rc = sph_grow_scratch(s, s->sampleBuf, (size_t)piece * perPoint);
   if (rc != SPH_OK) return rc;
   float* dOut = (float*)s->sampleBuf.p;
   float* dPts = (float*)((char*)s->sampleBuf.p + (size_t)piece * rec);
@@ -67,7 +101,7 @@ template <typename Launch, typename Consume>
 static int sample_grid_chunks(sph_solver* s, const int32_t dims[3], int words, Launch launch, Consume consume) {
   const size_t plane = (size_t)dims[0] * (size_t)dims[1], planeBytes = sizeof(float) * words * plane;
   const int planes = (int)std::min<size_t>((size_t)dims[2], std::max<size_t>(kSampleScratchBytes / planeBytes / 4, 1) * 4);
-  int rc = grow_scratch(s, s->sampleBuf, planeBytes * (size_t)planes);
+  int rc = sph_grow_scratch(s, s->sampleBuf, planeBytes * (size_t)planes);
   if (rc != SPH_OK) return rc;
   float* records = (float*)s->sampleBuf.p;
   for (int k0 = 0; k0 < dims[2]; k0 += planes) {
@@ -128,7 +162,7 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
   SampleArgs a;
   int rc = sample_check(s, typeMask, "sph_extract_surface", &a);
   if (rc != SPH_OK) return rc;
-  rc = grow_scratch(s, s->surfBuf, sphk_surface_scratch_bytes(P));
+  rc = sph_grow_scratch(s, s->surfBuf, sphk_surface_scratch_bytes(P));
   if (rc != SPH_OK) return rc;
   float* lattice = (float*)s->surfBuf.p;  // the scratch's first P floats
   rc = sample_grid_chunks(
@@ -144,7 +178,7 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
     return SPH_ERR_SIZE;
   }
   const size_t vBytes = surf_bytes_align(sizeof(float) * 3 * (size_t)totals[0]);
-  rc = grow_scratch(s, s->meshBuf, std::max<size_t>(vBytes + sizeof(int32_t) * 3 * (size_t)totals[1], 1));
+  rc = sph_grow_scratch(s, s->meshBuf, std::max<size_t>(vBytes + sizeof(int32_t) * 3 * (size_t)totals[1], 1));
   if (rc != SPH_OK) return rc;
   rc = sphk_surface_emit(s, s->surfBuf.p, dims, iso, origin, spacing, (float*)s->meshBuf.p, (int32_t*)((char*)s->meshBuf.p + vBytes));
   if (rc != SPH_OK) return rc;
@@ -220,7 +254,7 @@ extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
   if (rc != SPH_OK || V == 0) return rc;
   const size_t rec = sizeof(float) * 3;
   const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
-  rc = grow_scratch(s, s->sampleBuf, (size_t)piece * rec);
+  rc = sph_grow_scratch(s, s->sampleBuf, (size_t)piece * rec);
   if (rc != SPH_OK) return rc;
   const float K = gradient_scale(s);
   for (int64_t first = 0; first < V; first += piece) {
@@ -235,15 +269,19 @@ extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
 
 // ---------------------------------------------------------------------------------------------- flow diagnostics
 // Reductions and histograms over the same state as sampling (sph_diag.hip); blocking, read-only, no stage timing.
-static int diag_region_ok(const float* b, const char* what) {
-  for (int k = 0; k < 6; k++)
-    if (std::isnan(b[k])) { sph_set_error("%s: a region bound is NaN", what); return SPH_ERR_INVALID; }
+// the `count` regions (6 floats each) and the types of a region-list call into its arguments (sample_check has checked the mask)
+static int diag_fill_regions(sph_solver* s, DiagArgs* a, const float* regions6, int count, uint32_t typeMask, const char* what) {
+  for (int r = 0; r < count; r++) {
+    const int rc = region_fill(a->box[r], regions6 + 6 * r, what);
+    if (rc != SPH_OK) return rc;
+  }
+  a->count = count; a->typeMask = typeMask; a->rho0 = s->d.rho0;
   return SPH_OK;
 }
 
 // the records of a.count selections: through the diagnostics scratch to `out`, then the check every blocking call ends with
 static int diag_records(sph_solver* s, const DiagArgs& a, double* out) {
-  int rc = grow_scratch(s, s->diagBuf, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, a.count));
+  int rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, a.count));
   if (rc != SPH_OK) return rc;
   double* records = nullptr;
   rc = sphk_diagnostics(s, a, (double*)s->diagBuf.p, &records);
@@ -259,13 +297,8 @@ extern "C" int sph_diagnostics(sph_solver* s, const float* regions6, int32_t cou
   int rc = sample_check(s, typeMask, "sph_diagnostics");
   if (rc != SPH_OK) return rc;
   DiagArgs a = {};
-  for (int r = 0; r < count; r++) {
-    rc = diag_region_ok(regions6 + 6 * r, "sph_diagnostics");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
-  }
-  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
-  return diag_records(s, a, out);
+  rc = diag_fill_regions(s, &a, regions6, count, typeMask, "sph_diagnostics");
+  return rc != SPH_OK ? rc : diag_records(s, a, out);
 }
 
 extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, int32_t bins, const float* region6, uint32_t typeMask,
@@ -278,17 +311,12 @@ extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, i
   int rc = sample_check(s, typeMask, "sph_histogram");
   if (rc != SPH_OK) return rc;
   HistArgs a = {};
-  if (region6) {
-    rc = diag_region_ok(region6, "sph_histogram");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
-  } else {
-    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
-  }
+  rc = sph_fill_selector(&a.sel, region6, typeMask, "sph_histogram");
+  if (rc != SPH_OK) return rc;
   volatile float width = hi - lo;
   volatile float scale = (float)bins / width;
-  a.typeMask = typeMask; a.field = field; a.bins = bins; a.lo = lo; a.hi = hi; a.scale = scale;
-  rc = grow_scratch(s, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
+  a.field = field; a.bins = bins; a.lo = lo; a.hi = hi; a.scale = scale;
+  rc = sph_grow_scratch(s, s->diagBuf, sizeof(uint32_t) * (size_t)(bins + 2));
   if (rc != SPH_OK) return rc;
   rc = sphk_histogram(s, a, (uint32_t*)s->diagBuf.p);
   if (rc != SPH_OK) return rc;
@@ -311,7 +339,7 @@ extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t ty
   NEED(s, P_FIND, "sph_label_components");
   const bool finite = !std::isinf(linkRadius);
   volatile float link2 = linkRadius * linkRadius;
-  rc = grow_scratch(s, s->ccBuf, sphk_components_scratch_bytes(s->d.N));
+  rc = sph_grow_scratch(s, s->ccBuf, sphk_components_scratch_bytes(s->d.N));
   if (rc != SPH_OK) return rc;
   uint32_t* dTotals = nullptr;
   rc = sphk_components_link(s, typeMask, finite, link2, s->ccBuf.p, &dTotals);
@@ -324,7 +352,7 @@ extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t ty
     return SPH_ERR_HIP;
   }
   const int C = (int)totals[1];
-  rc = grow_scratch(s, s->ccTable, sizeof(int32_t) * 8 * (size_t)std::max(C, 1));
+  rc = sph_grow_scratch(s, s->ccTable, sizeof(int32_t) * 8 * (size_t)std::max(C, 1));
   if (rc != SPH_OK) return rc;
   rc = sphk_components_number(s, s->ccBuf.p, C, (int32_t*)s->ccTable.p);
   if (rc != SPH_OK) return rc;
@@ -363,12 +391,9 @@ extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* component
   ENTER(s);
   if (!components || !out) { sph_set_error("sph_component_diagnostics: null pointer"); return SPH_ERR_INVALID; }
   if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_component_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
-  if (!s->ccValid) { sph_set_error("sph_component_diagnostics: no labelling has been made"); return SPH_ERR_ORDER; }
-  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
-    sph_set_error("sph_component_diagnostics: the solver's state has changed since the labelling");
-    return SPH_ERR_ORDER;
-  }
   DiagArgs a = {};
+  const int rc = sph_labels_current(s, "sph_component_diagnostics", &a.labels);
+  if (rc != SPH_OK) return rc;
   for (int r = 0; r < count; r++) {
     if (components[r] < 0 || (int64_t)components[r] >= s->ccCounts[1]) {
       sph_set_error("sph_component_diagnostics: component %d is not in 0..%lld", components[r], (long long)s->ccCounts[1] - 1);
@@ -377,7 +402,6 @@ extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* component
     a.comp[r] = components[r];
   }
   a.count = count; a.typeMask = 0xEu; a.rho0 = s->d.rho0;
-  a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
   return diag_records(s, a, out);
 }
 
@@ -403,7 +427,7 @@ extern "C" int sph_particle_measure(sph_solver* s, float* out) {
   const int N = s->d.N;
   if (N <= 0) return SPH_OK;
   const int piece = (int)std::min<size_t>(((size_t)N + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / sizeof(float));
-  rc = grow_scratch(s, s->sampleBuf, sizeof(float) * (size_t)piece);
+  rc = sph_grow_scratch(s, s->sampleBuf, sizeof(float) * (size_t)piece);
   if (rc != SPH_OK) return rc;
   for (int first = 0; first < N; first += piece) {
     const int n = std::min(piece, N - first);
@@ -425,14 +449,8 @@ extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_
   SelectArgs a = {};
   int rc = select_check(s, typeMask, "sph_select_particles", &a.ss2);
   if (rc != SPH_OK) return rc;
-  a.typeMask = typeMask;
-  if (region6) {
-    rc = diag_region_ok(region6, "sph_select_particles");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
-  } else {
-    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
-  }
+  rc = sph_fill_selector(&a.sel, region6, typeMask, "sph_select_particles");
+  if (rc != SPH_OK) return rc;
   if (termCount < 0 || termCount > SPH_SELECT_MAX_TERMS) {
     sph_set_error("sph_select_particles: termCount %d is not in 0..%d", termCount, SPH_SELECT_MAX_TERMS);
     return SPH_ERR_INVALID;
@@ -450,18 +468,15 @@ extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_
   a.component = -1;
   if (component < -1) { sph_set_error("sph_select_particles: component %d is below -1", component); return SPH_ERR_INVALID; }
   if (component >= 0) {
-    if (!s->ccValid || s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
-      sph_set_error("sph_select_particles: no labelling of the current state (sph_label_components)");
-      return SPH_ERR_ORDER;
-    }
+    rc = sph_labels_current(s, "sph_select_particles", &a.labels);
+    if (rc != SPH_OK) return rc;
     if ((int64_t)component >= s->ccCounts[1]) {
       sph_set_error("sph_select_particles: component %d is not in 0..%lld", component, (long long)s->ccCounts[1] - 1);
       return SPH_ERR_INVALID;
     }
     a.component = component;
-    a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
   }
-  rc = grow_scratch(s, s->selBuf, sphk_select_scratch_bytes(s->d.N));
+  rc = sph_grow_scratch(s, s->selBuf, sphk_select_scratch_bytes(s->d.N));
   if (rc != SPH_OK) return rc;
   uint32_t* dTotals = nullptr;
   rc = sphk_select_count(s, a, s->selBuf.p, &dTotals);
@@ -470,7 +485,7 @@ extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_
   rc = sph_d2h(s, totals, dTotals, sizeof(totals));  // the call's one wait for a result
   if (rc != SPH_OK) return rc;
   if (totals[0] > (uint32_t)std::max(s->d.N, 0)) { sph_set_error("sph_select_particles: the count %u exceeds N", totals[0]); return SPH_ERR_HIP; }
-  rc = grow_scratch(s, s->selList, sizeof(int32_t) * (size_t)std::max<uint32_t>(totals[0], 1u));
+  rc = sph_grow_scratch(s, s->selList, sizeof(int32_t) * (size_t)std::max<uint32_t>(totals[0], 1u));
   if (rc != SPH_OK) return rc;
   rc = sphk_select_scatter(s, s->selBuf.p, totals[0], (int32_t*)s->selList.p);
   if (rc != SPH_OK) return rc;
@@ -486,14 +501,10 @@ extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_
 
 extern "C" int sph_read_selection(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records) {
   ENTER(s);
-  if (!s->selValid) { sph_set_error("sph_read_selection: no selection has been made"); return SPH_ERR_ORDER; }
-  if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
-    sph_set_error("sph_read_selection: the solver's state has changed since the selection");
-    return SPH_ERR_ORDER;
-  }
+  int rc = sph_selection_current(s, "sph_read_selection");
+  if (rc != SPH_OK) return rc;
   const size_t n = (size_t)s->selCount;
   if (n == 0) return SPH_OK;
-  int rc = SPH_OK;
   const int32_t* list = (const int32_t*)s->selList.p;
   if (sortedIndex) rc = sph_d2h(s, sortedIndex, list, sizeof(int32_t) * n);
   if (rc != SPH_OK || (!origId && !records)) return rc;
@@ -502,7 +513,7 @@ extern "C" int sph_read_selection(sph_solver* s, int32_t* sortedIndex, uint32_t*
   if (rc != SPH_OK) return rc;
   const size_t rec = sizeof(float) * SPH_SELECT_WORDS, per = rec + sizeof(uint32_t);
   const size_t piece = std::min<size_t>(n, kSampleScratchBytes / per);
-  rc = grow_scratch(s, s->sampleBuf, piece * per);
+  rc = sph_grow_scratch(s, s->sampleBuf, piece * per);
   if (rc != SPH_OK) return rc;
   float* dRec = (float*)s->sampleBuf.p;
   uint32_t* dIds = (uint32_t*)((char*)s->sampleBuf.p + piece * rec);
@@ -540,7 +551,7 @@ extern "C" int sph_elastic_measure(sph_solver* s, int32_t* sortedIndex, uint32_t
   // [flags, 256 bytes][records][connections][sorted indices][original ids]; an output that is not asked for is not written
   const size_t E = (size_t)s->d.numElastic, head = 256;
   const size_t recBytes = sizeof(float) * SPH_ELASTIC_WORDS * E, conBytes = sizeof(float) * 2 * SPH_MAX_NEIGHBOR_COUNT * E;
-  rc = grow_scratch(s, s->elasticBuf, head + recBytes + conBytes + 2 * sizeof(uint32_t) * E);
+  rc = sph_grow_scratch(s, s->elasticBuf, head + recBytes + conBytes + 2 * sizeof(uint32_t) * E);
   if (rc != SPH_OK) return rc;
   char* base = (char*)s->elasticBuf.p;
   uint32_t* dBad = (uint32_t*)base;
@@ -569,7 +580,7 @@ extern "C" int sph_muscle_diagnostics(sph_solver* s, double* out) {
   int rc = elastic_check(s, "sph_muscle_diagnostics");
   if (rc != SPH_OK) return rc;
   const int groups = s->d.muscleCount + 1;
-  rc = grow_scratch(s, s->elasticBuf, sizeof(double) * sphk_group_tree_doubles((long long)s->d.numElastic * SPH_MAX_NEIGHBOR_COUNT, groups));
+  rc = sph_grow_scratch(s, s->elasticBuf, sizeof(double) * sphk_group_tree_doubles((long long)s->d.numElastic * SPH_MAX_NEIGHBOR_COUNT, groups));
   if (rc != SPH_OK) return rc;
   double* records = nullptr;
   rc = sphk_muscle_diagnostics(s, (double*)s->elasticBuf.p, &records);
@@ -592,7 +603,7 @@ extern "C" int sph_membrane_measure(sph_solver* s, float* out, double totals[4])
   if (M == 0 || !s->d.membraneData) { sph_set_error("sph_membrane_measure: the solver holds no membranes"); return SPH_ERR_INVALID; }
   // [records, 32 bytes per triangle][the tree's levels and flags]
   const size_t recBytes = sizeof(float) * SPH_MEMBRANE_WORDS * M;
-  rc = grow_scratch(s, s->elasticBuf, recBytes + sizeof(double) * sphk_group_tree_doubles((long long)M, 1));
+  rc = sph_grow_scratch(s, s->elasticBuf, recBytes + sizeof(double) * sphk_group_tree_doubles((long long)M, 1));
   if (rc != SPH_OK) return rc;
   float* dRec = (float*)s->elasticBuf.p;
   double* top = nullptr;
@@ -629,11 +640,8 @@ extern "C" int sph_force_measure(sph_solver* s, int32_t fromSelection, float* ou
   size_t n = (size_t)std::max(s->d.N, 0);
   const int32_t* list = nullptr;
   if (fromSelection) {
-    if (!s->selValid) { sph_set_error("sph_force_measure: no selection has been made"); return SPH_ERR_ORDER; }
-    if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
-      sph_set_error("sph_force_measure: the solver's state has changed since the selection");
-      return SPH_ERR_ORDER;
-    }
+    const int rcSel = sph_selection_current(s, "sph_force_measure");
+    if (rcSel != SPH_OK) return rcSel;
     n = (size_t)s->selCount;
     list = (const int32_t*)s->selList.p;
   }
@@ -643,7 +651,7 @@ extern "C" int sph_force_measure(sph_solver* s, int32_t fromSelection, float* ou
   if (!out) { sph_set_error("sph_force_measure: null pointer"); return SPH_ERR_INVALID; }
   const size_t rec = sizeof(float) * SPH_FORCE_WORDS;
   const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
-  rc = grow_scratch(s, s->sampleBuf, piece * rec);
+  rc = sph_grow_scratch(s, s->sampleBuf, piece * rec);
   if (rc != SPH_OK) return rc;
   for (size_t first = 0; first < n; first += piece) {
     const size_t m = std::min(piece, n - first);
@@ -662,18 +670,14 @@ extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32
   int rc = force_check(s, typeMask, "sph_force_diagnostics");
   if (rc != SPH_OK) return rc;
   DiagArgs a = {};
-  for (int r = 0; r < count; r++) {
-    rc = diag_region_ok(regions6 + 6 * r, "sph_force_diagnostics");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[r][k] = regions6[6 * r + k];
-  }
-  a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
+  rc = diag_fill_regions(s, &a, regions6, count, typeMask, "sph_force_diagnostics");
+  if (rc != SPH_OK) return rc;
   // the per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the diagnostics scratch
   const int chunks = s->d.N > 0 ? (s->d.N + 1023) / 1024 : 1;
   const int pieceChunks = (int)std::min<size_t>((size_t)chunks, kSampleScratchBytes / sphk_force_terms_bytes(1));
-  rc = grow_scratch(s, s->sampleBuf, sphk_force_terms_bytes(pieceChunks));
+  rc = sph_grow_scratch(s, s->sampleBuf, sphk_force_terms_bytes(pieceChunks));
   if (rc != SPH_OK) return rc;
-  rc = grow_scratch(s, s->diagBuf, sizeof(double) * sphk_force_diag_scratch_doubles(s->d.N, count));
+  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_force_diag_scratch_doubles(s->d.N, count));
   if (rc != SPH_OK) return rc;
   double* records = nullptr;
   rc = sphk_force_diagnostics(s, a, (float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
@@ -723,14 +727,8 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
   if (!render_view_ok(*view)) return SPH_ERR_INVALID;
   RenderArgs a = {};
   a.view = *view;
-  a.typeMask = typeMask;
-  if (region6) {
-    rc = diag_region_ok(region6, "sph_render_particles");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
-  } else {
-    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
-  }
+  rc = sph_fill_selector(&a.sel, region6, typeMask, "sph_render_particles");
+  if (rc != SPH_OK) return rc;
   if (view->colourMode == 2) {
     if (view->field == 3) NEED(s, P_FIND, "sph_render_particles (field 3)");
     volatile float width = view->hi - view->lo;
@@ -738,15 +736,12 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
     a.inv = inv;
   }
   if (view->colourMode == 3) {
-    if (!s->ccValid || s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
-      sph_set_error("sph_render_particles: no labelling of the current state (sph_label_components)");
-      return SPH_ERR_ORDER;
-    }
-    a.labels = sphk_components_labels(s->ccBuf.p, s->ccN);
+    rc = sph_labels_current(s, "sph_render_particles", &a.labels);
+    if (rc != SPH_OK) return rc;
   }
   const bool thickness = wantThickness != 0;
   const RenderLayout L = sphk_render_layout(view->width, view->height, thickness, s->d.N);
-  rc = grow_scratch(s, s->renderBuf, L.bytes);
+  rc = sph_grow_scratch(s, s->renderBuf, L.bytes);
   if (rc != SPH_OK) return rc;
   rc = sphk_render(s, a, thickness, s->renderBuf.p);
   if (rc != SPH_OK) return rc;
@@ -780,7 +775,3 @@ extern "C" int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex
   SPH_HIP(hipStreamSynchronize(s->stream));
   return SPH_OK;
 }
-
-// (for sph_api_edit.hip, which shares the scratch growth and the region check)
-int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes) { return grow_scratch(s, b, bytes); }
-int sph_region_ok(const float* region6, const char* what) { return diag_region_ok(region6, what); }

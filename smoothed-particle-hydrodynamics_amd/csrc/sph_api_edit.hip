@@ -78,16 +78,9 @@ extern "C" int sph_remove_region(sph_solver* s, const float* region6, uint32_t t
   int rc = edit_check(s, "sph_remove_region");
   if (rc != SPH_OK) return rc;
   if (!removed) { sph_set_error("sph_remove_region: null pointer"); return SPH_ERR_INVALID; }
-  if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("sph_remove_region: typeMask must be a non-empty set of bits 1..3"); return SPH_ERR_INVALID; }
-  EditRegion a = {};
-  a.typeMask = typeMask;
-  if (region6) {
-    rc = sph_region_ok(region6, "sph_remove_region");
-    if (rc != SPH_OK) return rc;
-    for (int k = 0; k < 6; k++) a.box[k] = region6[k];
-  } else {
-    for (int k = 0; k < 3; k++) { a.box[k] = -INFINITY; a.box[3 + k] = INFINITY; }
-  }
+  SphSelector a = {};
+  rc = sph_fill_selector(&a, region6, typeMask, "sph_remove_region");
+  if (rc != SPH_OK) return rc;
   rc = sph_grow_scratch(s, s->editBuf, sphk_edit_scratch_bytes(s->d.N));
   if (rc != SPH_OK) return rc;
   rc = sphk_edit_mark_region(s, a, s->editBuf.p);
@@ -100,11 +93,8 @@ extern "C" int sph_remove_selection(sph_solver* s, int64_t* removed) {
   int rc = edit_check(s, "sph_remove_selection");
   if (rc != SPH_OK) return rc;
   if (!removed) { sph_set_error("sph_remove_selection: null pointer"); return SPH_ERR_INVALID; }
-  if (!s->selValid) { sph_set_error("sph_remove_selection: no selection has been made"); return SPH_ERR_ORDER; }
-  if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
-    sph_set_error("sph_remove_selection: the solver's state has changed since the selection");
-    return SPH_ERR_ORDER;
-  }
+  rc = sph_selection_current(s, "sph_remove_selection");
+  if (rc != SPH_OK) return rc;
   rc = sph_grow_scratch(s, s->editBuf, sphk_edit_scratch_bytes(s->d.N));
   if (rc != SPH_OK) return rc;
   rc = sphk_edit_clear_marks(s, s->editBuf.p);

@@ -23,7 +23,12 @@ int sph_check_finite_state(sph_solver* s);                             // synchr
 int sph_slab_finish(sph_solver* s, int32_t counts[4]);
 // (bodies in sph_api_analysis.hip)
 int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes);  // device buffer b grown to at least `bytes`
-int sph_region_ok(const float* region6, const char* what);         // SPH_ERR_INVALID for a NaN bound
+// The selection arguments every call that takes them shares: typeMask must be a non-empty set of bits 1..3; region6 (x0, y0, z0,
+// x1, y1, z1) may be null (everything: -inf .. +inf) and must not hold a NaN. SPH_ERR_INVALID with "<what>: ..." otherwise.
+int sph_fill_selector(SphSelector* sel, const float* region6 /* may be null */, uint32_t typeMask, const char* what);
+// SPH_ERR_ORDER unless a labelling / a selection exists and was made on the current state; *labels: the N labels (device)
+int sph_labels_current(sph_solver* s, const char* what, const int32_t** labels);
+int sph_selection_current(sph_solver* s, const char* what);
 
 // (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
 #define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)

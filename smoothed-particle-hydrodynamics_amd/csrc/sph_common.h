@@ -294,6 +294,12 @@ int sphk_gradient_grid(sph_solver* s, const SampleArgs& a, float K, const float 
                        int kBase, int nz, float* out);  // as sphk_sample_grid, 32-word records
 // normals[3*i..] of the `count` packed (x, y, z) vertices at verts, from the gradient of record word `field` (0..5)
 int sphk_surface_normals(sph_solver* s, const SampleArgs& a, float K, int field, const float* verts, int count, float* normals);
+// One selection of particles: the half-open box x0, y0, z0, x1, y1, z1 (±inf: unbounded) and the types, bits 1..3. The entry
+// points fill it with sph_fill_selector (sph_api_internal.h); the kernels test it with the functions of sph_selector.h.
+struct SphSelector {
+  float box[6];
+  uint32_t typeMask;
+};
 // sph_diag.hip (the records and histograms of include/sphmi.h; read-only on every solver array)
 struct DiagArgs {
   float box[SPH_DIAG_MAX_REGIONS][6];  // x0, y0, z0, x1, y1, z1 per region
@@ -305,8 +311,7 @@ struct DiagArgs {
   int32_t comp[SPH_DIAG_MAX_REGIONS];
 };
 struct HistArgs {
-  float box[6];
-  uint32_t typeMask;
+  SphSelector sel;
   int field, bins;
   float lo, hi, scale;  // scale = (float)bins / (hi - lo)
 };
@@ -322,8 +327,7 @@ int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float li
 int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table);
 // sph_select.hip (particle selection, surface measure and compact read-back; read-only on every solver array)
 struct SelectArgs {
-  float box[6];
-  uint32_t typeMask;
+  SphSelector sel;
   int termCount;
   int field[SPH_SELECT_MAX_TERMS];
   float lo[SPH_SELECT_MAX_TERMS], hi[SPH_SELECT_MAX_TERMS];
@@ -347,10 +351,6 @@ struct SelLayout {
 SelLayout sphk_select_layout(int N);
 int sphk_select_scan(sph_solver* s, void* scratch, int N);  // off = exclusive offsets of blockCnt, totals[0..1] = its sum
 // sph_edit.hip (adding and removing particles between steps; acts on the original-order state posOrig / velOrig)
-struct EditRegion {
-  float box[6];
-  uint32_t typeMask;
-};
 struct EditLattice {
   float ox, oy, oz, sx, sy, sz;
   int nx, ny, nz;
@@ -359,7 +359,7 @@ struct EditLattice {
   float xmin, xmax, ymin, ymax, zmin, zmax;
 };
 size_t sphk_edit_scratch_bytes(int N);  // the selection scan's layout and size
-int sphk_edit_mark_region(sph_solver* s, const EditRegion& a, void* scratch);  // writes every mask word
+int sphk_edit_mark_region(sph_solver* s, const SphSelector& a, void* scratch);  // type and box only (posOrig has no keys); writes every mask word
 int sphk_edit_clear_marks(sph_solver* s, void* scratch);
 // or-s the marks of ids[0..count) (list == nullptr) or of vals[list[0..count)] into the mask; device pointers
 int sphk_edit_mark_ids(sph_solver* s, const uint32_t* ids, const int32_t* list, int count, void* scratch);
@@ -381,8 +381,7 @@ int sphk_membrane_measure(sph_solver* s, float* out, double* scratch, double** t
 // sph_render.hip (depth, id, colour and thickness images of the particles; read-only on every solver array)
 struct RenderArgs {
   sph_render_view view;
-  float box[6];
-  uint32_t typeMask;
+  SphSelector sel;
   float inv;              // 1.0f / (hi - lo), one float (colour mode 2)
   const int32_t* labels;  // the current labelling (colour mode 3)
 };

@@ -1,6 +1,7 @@
 // Connected components of the particles (include/sphmi.h: sph_label_components / sph_read_components). The graph:
-// nodes = the selected sorted particles, edges = the entries of the last step's neighbour rows between two selected particles
-// (either end's row; optionally only pairs closer than a link radius). Read-only on every solver array.
+// nodes = the selected sorted particles (type and key: sph_selector.h), edges = the entries of the last step's neighbour rows
+// between two selected particles (either end's row; optionally only pairs closer than a link radius). Read-only on every solver
+// array.
 //   k_cc_init      parent[j] = selected ? j : -1
 //   k_cc_prelink   parent[i] = the smallest particle below i that i's own row links it to: a forest without a single atomic
 //   k_cc_compress  pointer jumping on that forest, so that the hooks start from short trees
@@ -22,6 +23,7 @@
 // Every pointer walk and every retry loop is bounded by N + 1 steps; an overrun sets err[0] instead of spinning.
 #include "sph_common.h"
 #include "sph_row_walk.h"
+#include "sph_selector.h"  // the type and key pieces of the selection rule
 
 #include <algorithm>
 
@@ -32,15 +34,10 @@
 
 __device__ __forceinline__ int cc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ bool cc_selected(const SphDev& d, uint32_t typeMask, int j, const float4& p) {
-  const int type = (int)p.w;
-  return type >= 1 && type <= 3 && ((1u << type) & typeMask) && d.keys[j] < (uint32_t)d.G;
-}
-
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_init(SphDev d, uint32_t typeMask, int32_t* __restrict__ parent) {
   const int j = blockIdx.x * SPH_BLOCK + threadIdx.x;
   if (j >= d.N) return;
-  parent[j] = cc_selected(d, typeMask, j, d.sortedPos[j]) ? j : -1;
+  parent[j] = sph_type_key_selected(d, typeMask, j, d.sortedPos[j]) ? j : -1;
 }
 
 // Root of x's tree as far as this lane can see it (a value that was a root when it was read). Path halving: parent[x] moves to

@@ -1,6 +1,6 @@
 // Flow diagnostics: reductions over the selected particles of up to 16 axis-aligned regions, and histograms of one per-particle
 // quantity, read from the sorted state of the last completed step (include/sphmi.h: sph_diagnostics / sph_histogram, DESIGN.md
-// §15). Read-only on every solver array.
+// §15). Read-only on every solver array. Which particles a region or a histogram selects: sph_selector.h.
 //
 // The sums are doubles reduced in the FIXED TREE of the contract: the terms in ascending sorted index, padded with +0.0 to whole
 // chunks of 1024; in a chunk, a[i] += a[i + stride] for stride = 512 ... 1; the chunks' results are the terms of the next
@@ -11,6 +11,7 @@
 // No floating-point atomics anywhere. Extremes are order-independent (float compares; the max-v2 particle by the pair
 // (larger v2, then lower index)) and travel through the levels as exactly widened doubles.
 #include "sph_common.h"
+#include "sph_selector.h"  // the selection rule and the histogram's quantity
 #include "sph_tree.h"  // DIAG_CHUNK, diag_wave_sum, diag_block_reduce: shared with the elastic-matter reductions
 
 #include <algorithm>
@@ -53,10 +54,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
       const float4 v = d.sortedVel[j];
       const float rho = d.rho[j];
       const float pr = d.rp[j].y;
-      const uint32_t key = d.keys[j];
-      const int type = (int)p.w;
       if (COMP) { lab[e] = a.labels[j]; ok[e] = lab[e] >= 0; }
-      else ok[e] = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && key < (uint32_t)d.G;
+      else ok[e] = sph_type_key_selected(d, a.typeMask, j, p);
       f[e][0] = p.x; f[e][1] = p.y; f[e][2] = p.z;
       f[e][3] = v.x; f[e][4] = v.y; f[e][5] = v.z;
       f[e][6] = p.y * v.z - p.z * v.y;
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
     bool sel[4];
 #pragma unroll
     for (int e = 0; e < 4; e++)
-      sel[e] = COMP ? (ok[e] && lab[e] == a.comp[r]) : ok[e] && x0 <= f[e][0] && f[e][0] < x1 && y0 <= f[e][1] && f[e][1] < y1 && z0 <= f[e][2] && f[e][2] < z1;
+      sel[e] = COMP ? (ok[e] && lab[e] == a.comp[r]) : ok[e] && sph_box_holds(x0, y0, z0, x1, y1, z1, f[e][0], f[e][1], f[e][2]);
     // No particle of this chunk in the region (the sorted order is spatial, so that is the common case for a small region): every
     // sum of +0.0 terms is +0.0 and every extreme keeps its identity, which is what the tree below would produce.
     if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
@@ -250,6 +249,8 @@ int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double**
 // ---- histogram ---------------------------------------------------------------------------------------------------------------
 // Counts are integers, so any order gives the same result: a histogram per block in LDS (integer atomics), then one integer
 // atomicAdd per non-empty bin and block.
+// The neighbour count of field 3 keeps its own decoder of the row (plain loads), not sph_neighbor_count over the shared row walk
+// (non-temporal loads): the two have not been timed against each other on an MI355X.
 __device__ __forceinline__ float hist_neighbor_count(const SphDev& d, int id) {
   int n = 0;
   const bool wide = d.nbr16[nbr_index(id, 0)] == SPH_N16_WIDE;
@@ -280,20 +281,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_histogram(SphDev d, HistArgs a, u
   __syncthreads();
   for (int j = blockIdx.x * SPH_BLOCK + threadIdx.x; j < d.N; j += gridDim.x * SPH_BLOCK) {
     const float4 p = d.sortedPos[j];
-    const int type = (int)p.w;
-    if (!(type >= 1 && type <= 3 && ((1u << type) & a.typeMask))) continue;
-    if (!(d.keys[j] < (uint32_t)d.G)) continue;
-    if (!(a.box[0] <= p.x && p.x < a.box[3] && a.box[1] <= p.y && p.y < a.box[4] && a.box[2] <= p.z && p.z < a.box[5])) continue;
-    float q;
-    switch (a.field) {
-      case 0: q = d.rho[j]; break;
-      case 1: { const float4 v = d.sortedVel[j]; q = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); } break;
-      case 2: q = d.rp[j].y; break;
-      case 3: q = hist_neighbor_count(d, j); break;
-      case 4: q = p.x; break;
-      case 5: q = p.y; break;
-      default: q = p.z; break;
-    }
+    if (!sph_selected(d, a.sel, j, p)) continue;
+    const float q = a.field == 3 ? hist_neighbor_count(d, j) : sph_particle_quantity(d, a.field, j, p);
     int slot;
     if (q < a.lo) slot = 0;
     else if (q >= a.hi) slot = a.bins + 1;

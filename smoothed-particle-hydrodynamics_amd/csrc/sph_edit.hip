@@ -1,7 +1,7 @@
 // Particle editing between steps (include/sphmi.h: sph_remove_* / sph_add_particles / sph_emit_lattice): a stable
 // compaction of the original-order state (posOrig, velOrig) and a lattice emitter that appends to it.
-//   k_edit_mark_region  one lane per particle: type and half-open box on posOrig; one ballot word per wave, the mask layout of
-//                       k_select_flags (mask[4 b + w], bit l = particle 256 b + 64 w + l is MARKED for removal)
+//   k_edit_mark_region  one lane per particle: type and half-open box (sph_selector.h) on posOrig; one ballot word per wave, the
+//                       mask layout of k_select_flags (mask[4 b + w], bit l = particle 256 b + 64 w + l is MARKED for removal)
 //   k_edit_mark_ids     one lane per listed id (or per entry of the live selection, through vals): 64-bit atomicOr into a cleared mask
 //   k_edit_counts       one lane per 256-block: the survivors of the block from its four mask words, and the lowest marked id
 //                       below the protected (elastic) range, if any
@@ -13,19 +13,18 @@
 // entry point then swaps the pointers. Integer ballots, popcounts, sums, or and min only: every result is a function of the
 // state and the arguments, whatever the order the blocks run in.
 #include "sph_common.h"
+#include "sph_selector.h"  // the type and box pieces of the selection rule
 
 #define EDIT_WAVE 64
 #define EDIT_WAVES (SPH_BLOCK / EDIT_WAVE)
 
-__global__ __launch_bounds__(SPH_BLOCK) void k_edit_mark_region(const float4* __restrict__ pos, int N, EditRegion a,
+__global__ __launch_bounds__(SPH_BLOCK) void k_edit_mark_region(const float4* __restrict__ pos, int N, SphSelector a,
                                                                 unsigned long long* __restrict__ mask) {
   const int j = blockIdx.x * SPH_BLOCK + threadIdx.x;
   bool hit = false;
   if (j < N) {
     const float4 p = pos[j];
-    const int type = (int)p.w;
-    hit = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && a.box[0] <= p.x && p.x < a.box[3] && a.box[1] <= p.y &&
-          p.y < a.box[4] && a.box[2] <= p.z && p.z < a.box[5];
+    hit = sph_type_selected(p.w, a.typeMask) && sph_box_holds(a.box, p.x, p.y, p.z);  // no key test: posOrig has no keys
   }
   const unsigned long long word = __ballot(hit);
   if ((threadIdx.x & (EDIT_WAVE - 1)) == 0) mask[(size_t)blockIdx.x * EDIT_WAVES + threadIdx.x / EDIT_WAVE] = word;
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_edit_emit(EditLattice a, int coun
 // lowest marked id below protectEnd or 0xffffffff, totals[4..5] the emitter's counters
 size_t sphk_edit_scratch_bytes(int N) { return sphk_select_layout(N).bytes; }
 
-int sphk_edit_mark_region(sph_solver* s, const EditRegion& a, void* scratch) {
+int sphk_edit_mark_region(sph_solver* s, const SphSelector& a, void* scratch) {
   const SelLayout L = sphk_select_layout(s->d.N);
   hipLaunchKernelGGL(k_edit_mark_region, dim3(L.nb), dim3(SPH_BLOCK), 0, s->stream, (const float4*)s->d.posOrig, s->d.N, a,
                      (unsigned long long*)((char*)scratch + L.mask));

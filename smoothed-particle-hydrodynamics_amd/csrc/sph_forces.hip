@@ -16,6 +16,7 @@
 // ([word][particle of the piece], coalesced as they stand) and a leaf kernel in the shape of k_diag_leaf feeds them to the fixed
 // tree of sph_tree.h. No floating-point atomics.
 #include "sph_common.h"
+#include "sph_selector.h"  // the selection rule of the region totals
 #include "sph_tree.h"
 
 #include <algorithm>
@@ -249,8 +250,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_force_leaf(SphDev d, DiagArgs a, 
     px[e] = py[e] = pz[e] = 0.f;
     if (j < d.N) {
       const float4 p = d.sortedPos[j];
-      const int type = (int)p.w;
-      ok[e] = type >= 1 && type <= 3 && ((1u << type) & a.typeMask) && d.keys[j] < (uint32_t)d.G;
+      ok[e] = sph_type_key_selected(d, a.typeMask, j, p);
       px[e] = p.x; py[e] = p.y; pz[e] = p.z;
     }
   }
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_force_leaf(SphDev d, DiagArgs a, 
       const float x0 = a.box[r][0], y0 = a.box[r][1], z0 = a.box[r][2], x1 = a.box[r][3], y1 = a.box[r][4], z1 = a.box[r][5];
       bool sel[4];
 #pragma unroll
-      for (int e = 0; e < 4; e++) sel[e] = ok[e] && x0 <= px[e] && px[e] < x1 && y0 <= py[e] && py[e] < y1 && z0 <= pz[e] && pz[e] < z1;
+      for (int e = 0; e < 4; e++) sel[e] = ok[e] && sph_box_holds(x0, y0, z0, x1, y1, z1, px[e], py[e], pz[e]);
       // no particle of this chunk in the region: every sum of +0.0 terms is +0.0, which is what the tree below would produce
       if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
         if (t < FM_GROUP) part[fm_at(r, g * FM_GROUP + t, chunks, chunk)] = 0.0;

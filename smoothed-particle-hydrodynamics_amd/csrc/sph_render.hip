@@ -1,5 +1,5 @@
 // Particle rendering: depth, id, colour and thickness images of the sorted state of the last completed step (include/sphmi.h:
-// sph_render_particles / sph_read_render). Read-only on every solver array.
+// sph_render_particles / sph_read_render). Read-only on every solver array. The selection is sph_selector.h's.
 //   k_render_clear    one lane per pixel: key = all ones (uncovered), thickness sum = 0
 //   k_render_splat    one lane per sorted particle: selection, projection, then either the lane rasterises its clipped footprint
 //                     (at most 8 x 8 pixels) or the particle goes to the queue of large splats (one counter bump per wave)
@@ -11,7 +11,7 @@
 // integers: 64-bit integer atomics, whose results do not depend on the order they arrive in. No floating-point atomics.
 // Projection and fragment are one inline function each, used by the three kernels that need them, so their bits cannot differ.
 #include "sph_common.h"
-#include "sph_row_walk.h"
+#include "sph_selector.h"  // the selection rule and the quantity of colour mode 2
 
 #include <algorithm>
 
@@ -27,14 +27,6 @@ struct RenderSplat {
 
 __device__ static const float kRenderRamp[5][3] = SPH_RENDER_FIELD_RAMP;
 __device__ static const float kRenderPalette[SPH_RENDER_LABEL_COLOURS][3] = SPH_RENDER_LABEL_PALETTE;
-
-// the selection of sph_diagnostics / sph_histogram for one region
-__device__ __forceinline__ bool render_select(const SphDev& d, const RenderArgs& a, int j, const float4& p) {
-  const int type = (int)p.w;
-  if (!(type >= 1 && type <= 3 && ((1u << type) & a.typeMask))) return false;
-  if (!(d.keys[j] < (uint32_t)d.G)) return false;
-  return a.box[0] <= p.x && p.x < a.box[3] && a.box[1] <= p.y && p.y < a.box[4] && a.box[2] <= p.z && p.z < a.box[5];
-}
 
 // PROJECTION of the contract; false: the particle is not drawn
 __device__ __forceinline__ bool render_project(const sph_render_view& w, const float4& p, RenderSplat& s) {
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_render_splat(SphDev d, RenderArgs
   bool drawn = false;
   if (j < d.N) {
     const float4 p = d.sortedPos[j];
-    drawn = render_select(d, a, j, p) && render_project(a.view, p, s);
+    drawn = sph_selected(d, a.sel, j, p) && render_project(a.view, p, s);
   }
   const unsigned long long drawnWave = __ballot(drawn);
   if (lane == 0 && drawnWave) atomicAdd(&head[0], (uint32_t)__popcll(drawnWave));
@@ -136,19 +128,6 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_render_drain(SphDev d, RenderArgs
   }
 }
 
-// sph_histogram's quantity `field` of sorted particle j
-__device__ __forceinline__ float render_quantity(const SphDev& d, int field, int j, const float4& p) {
-  switch (field) {
-    case 0: return d.rho[j];
-    case 1: { const float4 v = d.sortedVel[j]; return sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); }
-    case 2: return d.rp[j].y;
-    case 3: { int n = 0; sph_row_for_each_slot(d, j, [&](int nb) { n += nb >= 0; }); return (float)n; }
-    case 4: return p.x;
-    case 5: return p.y;
-    default: return p.z;
-  }
-}
-
 __device__ __forceinline__ void render_colour(const SphDev& d, const RenderArgs& a, int j, const float4& p, float c[3]) {
   const sph_render_view& w = a.view;
   if (w.colourMode == 0) {
@@ -166,7 +145,7 @@ __device__ __forceinline__ void render_colour(const SphDev& d, const RenderArgs&
     dc = (100.0f * (rho - rho0 * 1.03f)) / rho0; if (dc > 0.f) { c[0] = 1.f; c[1] = 1.f - dc; c[2] = 0.f; }
     dc = (100.0f * (rho - rho0 * 1.04f)) / rho0; if (dc > 0.f) { c[0] = 1.f; c[1] = 0.f; c[2] = 0.f; }
   } else if (w.colourMode == 2) {
-    const float q = render_quantity(d, w.field, j, p);
+    const float q = sph_particle_quantity(d, w.field, j, p);
     const float s = fminf(fmaxf((q - w.lo) * a.inv, 0.f), 1.f);
     const float t = s * 4.0f;
     const int i = min((int)t, 3);

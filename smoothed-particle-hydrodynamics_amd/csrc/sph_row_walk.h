@@ -1,5 +1,5 @@
 // The slot loop over one sorted particle's neighbour row, shared by the analysis kernels that read the rows after a step
-// (sph_select.hip, sph_components.hip).
+// (sph_select.hip, sph_components.hip; through sph_selector.h the neighbour count of sph_diag.hip and sph_render.hip).
 #pragma once
 #include "sph_common.h"
 

@@ -1,5 +1,6 @@
 // Particle selection, the free-surface measure and the compact read-back (include/sphmi.h: sph_particle_measure /
-// sph_select_particles / sph_read_selection). Read-only on every solver array.
+// sph_select_particles / sph_read_selection). Read-only on every solver array. Type, key and box are the rule of
+// sph_selector.h, which also names the quantities of the streamed terms.
 //   k_select_flags     one lane per sorted particle: type / key / box / component and the terms on streamed arrays first, the row
 //                      walk (neighbour count, surface measure) only for lanes that are still alive; one ballot word per wave
 //                      (the 1-bit-per-particle mask) and the survivors per block
@@ -12,6 +13,7 @@
 // integer ballots, popcounts and sums. No floating-point atomics.
 #include "sph_common.h"
 #include "sph_row_walk.h"
+#include "sph_selector.h"  // the selection rule and the streamed terms' quantities
 
 #include <algorithm>
 
@@ -59,22 +61,11 @@ __device__ __forceinline__ void select_row(const SphDev& d, float ss2, int i, fl
 
 __device__ __forceinline__ bool select_test(const SphDev& d, const SelectArgs& a, int j) {
   const float4 p = d.sortedPos[j];
-  const int type = (int)p.w;
-  if (!(type >= 1 && type <= 3 && ((1u << type) & a.typeMask))) return false;
-  if (!(d.keys[j] < (uint32_t)d.G)) return false;
-  if (!(a.box[0] <= p.x && p.x < a.box[3] && a.box[1] <= p.y && p.y < a.box[4] && a.box[2] <= p.z && p.z < a.box[5])) return false;
+  if (!sph_selected(d, a.sel, j, p)) return false;
   if (a.component >= 0 && a.labels[j] != a.component) return false;
   for (int k = 0; k < a.termCount; k++) {  // the terms on streamed arrays
-    float q;
-    switch (a.field[k]) {
-      case 0: q = d.rho[j]; break;
-      case 1: { const float4 v = d.sortedVel[j]; q = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); } break;
-      case 2: q = d.rp[j].y; break;
-      case 4: q = p.x; break;
-      case 5: q = p.y; break;
-      case 6: q = p.z; break;
-      default: continue;  // 3 and 7 need the row
-    }
+    if (a.field[k] == 3 || a.field[k] == 7) continue;  // they need the row: below, once for both, by the lanes still alive
+    const float q = sph_particle_quantity(d, a.field[k], j, p);
     if (!(q >= a.lo[k] && q < a.hi[k])) return false;
   }
   if (!a.needRow) return true;

@@ -460,6 +460,35 @@ def _lattice(origin, spacing, dims):
             np.ascontiguousarray(dims, np.int32).reshape(3))
 
 
+def _region(region, what):
+    """One region (x0, y0, z0, x1, y1, z1; None = everywhere) as the float32[6] the calls read, or None."""
+    if region is None:
+        return None
+    rg = np.ascontiguousarray(region, np.float32)
+    if rg.size != 6:
+        raise SphError("%s: region must be (x0, y0, z0, x1, y1, z1)" % what)
+    return rg
+
+
+def _regions(regions, what):
+    """A list of regions (None = one region holding everything) as float32[R, 6]."""
+    if regions is None:
+        regions = [(-np.inf,) * 3 + (np.inf,) * 3]
+    rg = np.ascontiguousarray(regions, np.float32)
+    if rg.size % 6:
+        raise SphError("%s: regions must be [R, 6]" % what)
+    return rg.reshape(-1, 6)
+
+
+def _field_index(field, names, what):
+    """A field given by its name in `names` or by its number -> the number (the library checks a number's range)."""
+    if isinstance(field, str):
+        if field not in names:
+            raise SphError("%s: field must be one of %s" % (what, names))
+        field = names.index(field)
+    return int(field)
+
+
 def build_info():
     """sph_build_info() of the loaded libsphmi.so ("DIAG" in it: a timing-only variant with invalid results)."""
     return device_lib().sph_build_info().decode()
@@ -580,10 +609,7 @@ class owHIPSolver:
         spacing, dims, types), extracted on the device: (vertices float32[V, 3], triangles int32[T, 3]), triangles wound with
         normals toward lower f (include/sphmi.h)."""
         from . import frames
-        if isinstance(field, str):
-            if field not in frames.GRID_FIELDS[:SURFACE_FIELDS]:
-                raise SphError("extract_surface: field must be one of %s" % (frames.GRID_FIELDS[:SURFACE_FIELDS],))
-            field = frames.GRID_FIELDS.index(field)
+        field = _field_index(field, frames.GRID_FIELDS[:SURFACE_FIELDS], "extract_surface")
         o, sp, dm = _lattice(origin, spacing, dims)
         counts = np.zeros(2, np.int64)
         self._mesh_vertices = 0  # (a failed extraction leaves no mesh behind)
@@ -629,12 +655,7 @@ class owHIPSolver:
         pressure, then extremes; include/sphmi.h). The sums are added in a fixed tree, so a record depends on the state and
         its region alone. The default types are the moving matter: a boundary particle's `velocity` holds the wall normal,
         so sums over type 3 are legal but are not momenta. frames.diagnostics_summary turns a record into physical numbers."""
-        if regions is None:
-            regions = [(-np.inf,) * 3 + (np.inf,) * 3]
-        rg = np.ascontiguousarray(regions, np.float32)
-        if rg.size % 6:
-            raise SphError("diagnostics: regions must be [R, 6]")
-        rg = rg.reshape(-1, 6)
+        rg = _regions(regions, "diagnostics")
         out = np.zeros((max(rg.shape[0], 1), DIAG_WORDS), np.float64)
         self._chk(self._L.sph_diagnostics(self._h, _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
         return out
@@ -643,17 +664,10 @@ class owHIPSolver:
         """Distribution of one per-particle quantity (a name from HIST_FIELDS or 0..6) over the same selection as
         diagnostics(): uint32[bins + 2] = values below lo, `bins` equal bins of [lo, hi), values at or above hi.
         histogram("neighbors", 0, 33, 33)[1:-1] is the exact neighbour-count distribution."""
-        if isinstance(field, str):
-            if field not in HIST_FIELDS:
-                raise SphError("histogram: field must be one of %s" % (HIST_FIELDS,))
-            field = HIST_FIELDS.index(field)
-        rg = None
-        if region is not None:
-            rg = np.ascontiguousarray(region, np.float32)
-            if rg.size != 6:
-                raise SphError("histogram: region must be (x0, y0, z0, x1, y1, z1)")
+        field = _field_index(field, HIST_FIELDS, "histogram")
+        rg = _region(region, "histogram")
         out = np.zeros(max(int(bins), 0) + 2, np.uint32)
-        self._chk(self._L.sph_histogram(self._h, int(field), float(np.float32(lo)), float(np.float32(hi)), int(bins), _ptr(rg),
+        self._chk(self._L.sph_histogram(self._h, field, float(np.float32(lo)), float(np.float32(hi)), int(bins), _ptr(rg),
                                         type_mask(types), _ptr(out)))
         return out
 
@@ -701,19 +715,11 @@ class owHIPSolver:
         (field, lo, hi) -- lo <= q < hi in float32, field a name from SELECT_FIELDS (HIST_FIELDS plus "surface", the
         particle_measure() value) or 0..7, +-inf allowed -- and, if `component` is given, belong to that component of the last
         label_components(). Returns the number selected; selection() reads them back. Up to 4 terms."""
-        rg = None
-        if region is not None:
-            rg = np.ascontiguousarray(region, np.float32)
-            if rg.size != 6:
-                raise SphError("select: region must be (x0, y0, z0, x1, y1, z1)")
+        rg = _region(region, "select")
         terms = list(terms)
         arr = (SphSelectTerm * max(len(terms), 1))()
         for k, (field, lo, hi) in enumerate(terms):
-            if isinstance(field, str):
-                if field not in SELECT_FIELDS:
-                    raise SphError("select: field must be one of %s" % (SELECT_FIELDS,))
-                field = SELECT_FIELDS.index(field)
-            arr[k].field, arr[k].lo, arr[k].hi = int(field), float(np.float32(lo)), float(np.float32(hi))
+            arr[k].field, arr[k].lo, arr[k].hi = _field_index(field, SELECT_FIELDS, "select"), float(np.float32(lo)), float(np.float32(hi))
         count = np.zeros(1, np.int64)
         self._selected = 0  # (a failed selection leaves none behind)
         self._chk(self._L.sph_select_particles(self._h, _ptr(rg), type_mask(types), C.cast(arr, C.c_void_p) if terms else None,
@@ -790,12 +796,7 @@ class owHIPSolver:
         frames.FORCE_DIAG_FIELDS (count, the 27 per-class sums, the step's two accelerations, torque about the origin and power
         per class, neighbour counts), added in the fixed tree of diagnostics(). frames.force_summary turns a record into
         newtons, newton metres and watts."""
-        if regions is None:
-            regions = [(-np.inf,) * 3 + (np.inf,) * 3]
-        rg = np.ascontiguousarray(regions, np.float32)
-        if rg.size % 6:
-            raise SphError("force_diagnostics: regions must be [R, 6]")
-        rg = rg.reshape(-1, 6)
+        rg = _regions(regions, "force_diagnostics")
         out = np.zeros((max(rg.shape[0], 1), FORCE_DIAG_WORDS), np.float64)
         self._chk(self._L.sph_force_diagnostics(self._h, _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
         return out
@@ -807,11 +808,7 @@ class owHIPSolver:
         pixel, ties to the lower sorted index, and with thickness=True the summed chord of every fragment. Returns (particles
         drawn, covered pixels); rendered() reads the images. The state is the sorted state of the last completed step
         (include/sphmi.h)."""
-        rg = None
-        if region is not None:
-            rg = np.ascontiguousarray(region, np.float32)
-            if rg.size != 6:
-                raise SphError("render: region must be (x0, y0, z0, x1, y1, z1)")
+        rg = _region(region, "render")
         counts = np.zeros(2, np.int64)
         self._render_shape = None  # (a failed render leaves no image behind)
         self._chk(self._L.sph_render_particles(self._h, C.byref(view) if view is not None else None, _ptr(rg), type_mask(types),
@@ -849,11 +846,7 @@ class owHIPSolver:
         box `region` (x0, y0, z0, x1, y1, z1; +-inf allowed; None = everywhere). The survivors keep their order; edit_map()
         tells where each went. Returns the number removed. With count_only=True nothing changes and the number that WOULD be
         removed is returned. An edit that changes the set invalidates the analysis state until the next step (include/sphmi.h)."""
-        rg = None
-        if region is not None:
-            rg = np.ascontiguousarray(region, np.float32)
-            if rg.size != 6:
-                raise SphError("remove_region: region must be (x0, y0, z0, x1, y1, z1)")
+        rg = _region(region, "remove_region")
         removed = np.zeros(1, np.int64)
         n0 = self.N
         self._chk(self._L.sph_remove_region(self._h, _ptr(rg), type_mask(types), 1 if count_only else 0, _ptr(removed)))

@@ -223,6 +223,50 @@ def test_consistent_with_the_other_analysis_calls(name):
     hip.close()
 
 
+def test_every_call_selects_the_same_particles_at_a_bound_on_a_particle():
+    """diagnostics, force_diagnostics, histogram, select and selection count the same particles, the restatement's number, for
+    boxes whose x bound is exactly the float32 x of a selected particle: as a lower bound it holds the particle, as an upper bound
+    it does not, one float above as an upper bound it does again."""
+    hip = scenes.hip_for(_scene("tiny_jitter"))
+    for it in range(3):
+        hip.step(it)
+    snap = Snapshot(hip)
+    st = snap.state
+    for types in MASKS:
+        sel = np.flatnonzero(diag_ref.selected(st, diag_ref.EVERYTHING, types))
+        p = st["pos"][sel].astype(np.float32)
+        j = int(sel[np.argsort(p[:, 0], kind="stable")[sel.size // 3]])  # a selected particle a third of the way along x
+        x = f32(st["pos"][j, 0])
+        up = np.nextafter(x, f32(INF))
+        z0, z1 = f32(np.quantile(p[:, 2], 0.3)), f32(np.quantile(p[:, 2], 0.6))
+        far = f32(p.max() + 100)
+        regions = np.array([(-INF, -INF, -INF, INF, INF, INF),
+                            (x, -INF, -INF, INF, INF, INF),    # the particle is inside
+                            (-INF, -INF, -INF, x, INF, INF),   # ... outside
+                            (-INF, -INF, -INF, up, INF, INF),  # ... inside again
+                            (-INF, -INF, z0, INF, INF, z1),    # infinite on two axes
+                            (far, far, far, far + 100, far + 100, far + 100)], np.float32)  # empty
+        want = [sr.select(st, snap.q, tuple(r), types, (), None, None) for r in regions]
+        n_diag = hip.diagnostics(regions, types)[:, 0]
+        n_force = hip.force_diagnostics(regions, types)[:, 0]
+        for r, region in enumerate(regions):
+            arg = None if r == 0 else tuple(region)
+            n_hist = int(hip.histogram("x", 0.0, 10.0, 16, arg, types).sum())
+            n_sel = hip.select(arg, types)
+            idx = hip.selection()[0]
+            got = (int(n_diag[r]), int(n_force[r]), n_hist, n_sel, int(idx.size))
+            print("types %r region %d: diagnostics, force_diagnostics, histogram, select, selection = %r; restatement %d"
+                  % (types, r, got, want[r].size))
+            assert got == (want[r].size,) * 5, (types, r, got, want[r].size)
+            assert np.array_equal(idx, want[r]), (types, r)
+            assert (j in idx.tolist()) == (r in (0, 1, 3)) or r == 4, (types, r, j)
+        n = [w.size for w in want]
+        assert n[0] == sel.size and n[1] + n[2] == n[0] and 0 < n[4] < n[0]  # no case passes vacuously
+        assert n[3] - n[2] >= 1 and n[1] > 0 and n[2] > 0  # they differ by the particle on the bound
+        assert n[5] == 0
+    hip.close()
+
+
 def test_more_than_a_million_particles():
     """More than 1024^2 particles (the pressure-active 1.3 M box of the parity suite): the scan runs over more than 4096 blocks.
     Selections of 0, 1, all and about half of the particles."""
