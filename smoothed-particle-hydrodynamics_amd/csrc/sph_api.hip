@@ -1,13 +1,13 @@
-// C ABI of libsphmi.so (include/sphmi.h): solver lifetime, the 18 stage entry points that mirror
-// owOpenCLSolver::_run* (owOpenCLSolver.cpp:213-687), the fused step, read-back, reference-layout export and the slab
-// protocol. The analysis calls (sampling, surfaces, diagnostics, components) are in sph_api_analysis.hip.
+// C ABI of libsphmi.so (include/sphmi.h): errors and build info, stage timing, solver lifetime, the 18 stage entry points that mirror
+// owOpenCLSolver::_run* (owOpenCLSolver.cpp:213-687) and the fused step. Read-back and the reference-layout export are in
+// sph_api_read.hip, the slab protocol in sph_api_slab.hip, the analysis calls in sph_api_analysis.hip, particle editing in
+// sph_api_edit.hip; what they share is in sph_api_internal.h.
 // There is no CPU path in this library: every entry point needs a HIP device and fails with SPH_ERR_HIP otherwise.
 #include <stdarg.h>
 #include <string.h>
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
+#include <memory>
 
 #include "sph_api_internal.h"
 #include "sph_fastmath.h"
@@ -37,10 +37,12 @@ extern "C" const char* sph_build_info(void) {
       ;
 }
 
+// Every permanent device allocation: recorded in the solver, which frees the record (~sph_solver)
 template <typename T>
-static int dev_alloc(T** p, size_t count) {
+static int dev_alloc(sph_solver* s, T** p, size_t count) {
   *p = nullptr;
   SPH_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
+  s->allocs.push_back(*p);
   return SPH_OK;
 }
 
@@ -119,33 +121,35 @@ struct StageTimer {
   sph_solver* s; int stage; hipEvent_t a, b; bool on;
   StageTimer(sph_solver* s_, int stage_) : s(s_), stage(stage_), a(nullptr), b(nullptr), on(s_->timing) {
     if (!on) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
+    if (hipEventCreate(&a) != hipSuccess) { on = false; return; }
+    if (hipEventCreate(&b) != hipSuccess) { hipEventDestroy(a); on = false; return; }
     hipEventRecord(a, s->stream);
   }
   ~StageTimer() {
     if (!on) return;
     hipEventRecord(b, s->stream);
-    if (s->numPending == s->capPending) {
-      s->capPending = s->capPending ? s->capPending * 2 : 256;
-      s->pending = (sph_solver::Pending*)realloc(s->pending, sizeof(sph_solver::Pending) * s->capPending);
-    }
-    s->pending[s->numPending++] = {stage, a, b};
+    s->pending.push_back({stage, a, b});
   }
 };
 
-static int resolve_pending(sph_solver* s) {
-  if (s->numPending == 0) return SPH_OK;
-  SPH_HIP(hipStreamSynchronize(s->stream));
-  for (int i = 0; i < s->numPending; i++) {
+// the recorded event pairs are read into the stage totals (read == true) and destroyed
+static void release_pending(sph_solver* s, bool read) {
+  for (const sph_solver::Pending& p : s->pending) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->pending[i].a, s->pending[i].b) == hipSuccess) {
-      s->stageMs[s->pending[i].stage] += (double)ms;
-      s->stageLaunches[s->pending[i].stage] += 1;
+    if (read && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+      s->stageMs[p.stage] += (double)ms;
+      s->stageLaunches[p.stage] += 1;
     }
-    hipEventDestroy(s->pending[i].a);
-    hipEventDestroy(s->pending[i].b);
+    hipEventDestroy(p.a);
+    hipEventDestroy(p.b);
   }
-  s->numPending = 0;
+  s->pending.clear();
+}
+
+static int resolve_pending(sph_solver* s) {
+  if (s->pending.empty()) return SPH_OK;
+  SPH_HIP(hipStreamSynchronize(s->stream));
+  release_pending(s, true);
   return SPH_OK;
 }
 
@@ -195,27 +199,18 @@ static bool two_hip_runtimes(char* out, size_t cap) {
   return two;
 }
 
-static void free_all(sph_solver* s) {
-  SphDev& d = s->d;
-  void* ptrs[] = {d.elasticMask, d.bndMask, d.rp, d.gatherRec, d.posOrig, d.velOrig, d.membDelta, d.sortedPos, d.sortedVel, d.predPos, d.acc, d.accP, d.keys, d.vals,
-                  d.keysAlt, d.valsAlt, d.backIndex, d.cellStart, d.cellStartRaw, d.nbrId, d.nbrDist, d.nbr16, d.nbrBase, d.rho,
-                  d.elastic, d.membraneData, d.pml, d.muscle, d.dbg, (void*)d.binU, d.gid, d.owned, s->slabCounts,
-                  s->blockHist};
-  for (void* p : ptrs) if (p) hipFree(p);
-  for (SphScratch* b : {&s->sampleBuf, &s->surfBuf, &s->meshBuf, &s->diagBuf, &s->ccBuf, &s->ccTable, &s->selBuf, &s->selList, &s->elasticBuf, &s->renderBuf, &s->editBuf}) if (b->p) hipFree(b->p);
-  if (s->slabHost) hipHostFree(s->slabHost);
-  for (int i = 0; i < s->numHostRegs; i++) hipHostUnregister(s->hostRegs[i].p);
-  s->numHostRegs = 0;
-  if (s->copyStage) hipHostFree(s->copyStage);
-  if (s->pinnedFlags) hipHostFree(s->pinnedFlags);
-  if (s->evReadReady) hipEventDestroy(s->evReadReady);
-  if (s->evCopyDone) hipEventDestroy(s->evCopyDone);
-  if (s->copyStream) hipStreamDestroy(s->copyStream);
-  if (s->slabMsgEvent) hipEventDestroy(s->slabMsgEvent);
-  if (s->slabRebuildEvent) hipEventDestroy(s->slabRebuildEvent);
-  if (s->ownStream && s->stream) hipStreamDestroy(s->stream);
-  free(s->pending);
-  free(s->hostScratch);
+sph_solver::~sph_solver() {
+  for (void* p : allocs) hipFree(p);
+  if (slabHost) hipHostFree(slabHost);
+  for (int i = 0; i < numHostRegs; i++) hipHostUnregister(hostRegs[i].p);
+  if (copyStage) hipHostFree(copyStage);
+  if (pinnedFlags) hipHostFree(pinnedFlags);
+  if (evReadReady) hipEventDestroy(evReadReady);
+  if (evCopyDone) hipEventDestroy(evCopyDone);
+  if (copyStream) hipStreamDestroy(copyStream);
+  if (slabMsgEvent) hipEventDestroy(slabMsgEvent);
+  if (slabRebuildEvent) hipEventDestroy(slabRebuildEvent);
+  if (ownStream && stream) hipStreamDestroy(stream);
 }
 
 extern "C" int sph_destroy(sph_solver* s) {
@@ -223,9 +218,7 @@ extern "C" int sph_destroy(sph_solver* s) {
   hipSetDevice(s->cfg.device);
   if (s->stream) hipStreamSynchronize(s->stream);
   if (s->copyStream) hipStreamSynchronize(s->copyStream);
-  for (int i = 0; i < s->numPending; i++) { hipEventDestroy(s->pending[i].a); hipEventDestroy(s->pending[i].b); }
-  s->numPending = 0;
-  free_all(s);
+  release_pending(s, false);
   delete s;
   return SPH_OK;
 }
@@ -264,22 +257,12 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   // orders the bits a valid id can have. (Reference mode keeps the reference's behaviour for out-of-box input: ids alias.)
   // Creation is the only way in for such coordinates: integrate clamps every new position into the box (sphFluid.cl:1750-1755,
   // integrate_particle), and a NaN — which no clamp catches — is counted by the hash kernel (dbg[6], sph_check_finite_state).
-  {
-    const bool wide = cfg->cellIdMask == 0xffffffffu;
-    for (int i = 0; i < N; i++) {
-      if ((int)position[4 * (size_t)i + 3] != SPH_BOUNDARY_PARTICLE && liquidSig != 0xffffffffu) {  // (see sph_slab_liquid_signature)
-        uint32_t tb, wb;
-        memcpy(&tb, &position[4 * (size_t)i + 3], 4); memcpy(&wb, &velocity[4 * (size_t)i + 3], 4);
-        if (wb != 0u || tb == 0u || tb == 0xffffffffu || (liquidSig != 0u && liquidSig != tb)) liquidSig = 0xffffffffu;
-        else liquidSig = tb;
-      }
-      const float x = position[4 * (size_t)i], y = position[4 * (size_t)i + 1], z = position[4 * (size_t)i + 2];
-      const bool finite = std::isfinite(x) && std::isfinite(y) && std::isfinite(z);
-      const bool inside = x >= cfg->xmin && x <= cfg->xmax && y >= cfg->ymin && y <= cfg->ymax && z >= cfg->zmin && z <= cfg->zmax;
-      if (!finite || (wide && !inside)) {
-        sph_set_error("particle %d at (%g, %g, %g) is %s", i, x, y, z, finite ? "outside the box (wide cell ids need in-box input)" : "not finite");
-        return SPH_ERR_INVALID;
-      }
+  for (int i = 0; i < N; i++) {
+    const float* p4 = position + 4 * (size_t)i;
+    sph_fold_liquid_signature(liquidSig, p4, velocity + 4 * (size_t)i);
+    if (const char* fault = sph_position_fault(*cfg, p4)) {
+      sph_set_error("particle %d at (%g, %g, %g) is %s", i, p4[0], p4[1], p4[2], fault);
+      return SPH_ERR_INVALID;
     }
   }
   int ndev = 0;
@@ -296,14 +279,15 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   }
   SPH_HIP(hipSetDevice(cfg->device));
 
-  sph_solver* s = new sph_solver();
-  memset((void*)s, 0, sizeof(*s));
+  // (a return before the release below destroys the solver and, with it, everything it owns by then)
+  std::unique_ptr<sph_solver> owner(new sph_solver());
+  sph_solver* const s = owner.get();
   s->cfg = *cfg;
   s->liquidSig = liquidSig;
   if (cfg->stream) { s->stream = (hipStream_t)cfg->stream; s->ownStream = false; }
   else {
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { sph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); delete s; return SPH_ERR_HIP; }
+    if (e != hipSuccess) { sph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); return SPH_ERR_HIP; }
     s->ownStream = true;
   }
   SphDev& d = s->d;
@@ -350,7 +334,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
 
   int rc = SPH_OK;
   const size_t n = (size_t)cap, nUp = (size_t)N, G1 = (size_t)d.G + 1, mapN = (size_t)s->capTiles * 64 * 32;
-#define A(ptr, count) if (rc == SPH_OK) rc = dev_alloc(&(ptr), (count))
+#define A(ptr, count) if (rc == SPH_OK) rc = dev_alloc(s, &(ptr), (count))
   A(d.posOrig, n); A(d.velOrig, n); A(d.sortedPos, n); A(d.sortedVel, n); A(d.predPos, 3 * n); A(d.acc, n); A(d.accP, n); A(d.rp, n); A(d.bndMask, n); A(d.gatherRec, 2 * ((n + 3) / 4 * 4));
   A(d.keys, n); A(d.vals, n); A(d.keysAlt, n); A(d.valsAlt, n); A(d.backIndex, n);
   A(d.cellStart, G1); A(d.cellStartRaw, G1);
@@ -367,10 +351,10 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
     if (membraneData && pml && cfg->numOfMembranes > 0) { A(d.membraneData, (size_t)3 * cfg->numOfMembranes); A(d.pml, (size_t)7 * d.numElastic); }
   }
 #undef A
-  if (rc != SPH_OK) { free_all(s); delete s; return rc; }
+  if (rc != SPH_OK) return rc;
 
 #define UP(dst, src, bytes) do { hipError_t e_ = hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, s->stream); \
-    if (e_ != hipSuccess) { sph_set_error("upload failed: %s", hipGetErrorString(e_)); free_all(s); delete s; return SPH_ERR_HIP; } } while (0)
+    if (e_ != hipSuccess) { sph_set_error("upload failed: %s", hipGetErrorString(e_)); return SPH_ERR_HIP; } } while (0)
   UP(d.posOrig, position, sizeof(float4) * nUp);
   UP(d.velOrig, velocity, sizeof(float4) * nUp);
   if (d.hasElastic) {
@@ -408,144 +392,72 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   hipMemsetAsync(d.vals, 0, sizeof(uint32_t) * n, s->stream);
   hipMemsetAsync(d.backIndex, 0, sizeof(uint32_t) * n, s->stream);
   hipError_t e = hipStreamSynchronize(s->stream);  // host arrays may be freed by the caller after return
-  if (e != hipSuccess) { sph_set_error("sph_create: %s", hipGetErrorString(e)); free_all(s); delete s; return SPH_ERR_HIP; }
-  *out = s;
+  if (e != hipSuccess) { sph_set_error("sph_create: %s", hipGetErrorString(e)); return SPH_ERR_HIP; }
+  *out = owner.release();
   return SPH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- stages
-extern "C" int sph_run_clear_buffers(sph_solver* s) {
-  ENTER(s);
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_FIND_NEIGHBORS);
-  return sphk_clear_neighbors(s);
-}
-extern "C" int sph_run_hash_particles(sph_solver* s) {
-  ENTER(s);
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_HASH);
-  int rc = sphk_hash(s);
-  if (rc == SPH_OK) s->progress = P_HASH;  // a new step starts here
+// One row per stage entry point: the progress bits it needs, the timer slot it is booked on, its launcher and the bits it gains.
+struct Stage {
+  const char* name;
+  int need, timer;
+  int (*launch)(sph_solver*);
+  int gain;
+};
+#define LAUNCH(call) [](sph_solver* s) { return call; }
+static const Stage kClearBuffers = {"sph_run_clear_buffers", 0, SPH_ST_FIND_NEIGHBORS, LAUNCH(sphk_clear_neighbors(s)), 0};
+static const Stage kHashParticles = {"sph_run_hash_particles", 0, SPH_ST_HASH, LAUNCH(sphk_hash(s)), P_HASH};
+static const Stage kSort = {"sph_run_sort", P_HASH, SPH_ST_SORT, LAUNCH(sphk_sort(s)), P_SORT};
+static const Stage kSortPostPass = {"sph_run_sort_post_pass", P_SORT, SPH_ST_SORT_POST, LAUNCH(sphk_sort_post(s)), P_SORTPOST};
+static const Stage kIndexx = {"sph_run_indexx", P_SORT, SPH_ST_INDEX, LAUNCH(sphk_index_raw(s)), P_INDEXX};
+static const Stage kIndexPostPass = {"sph_run_index_post_pass", P_INDEXX, SPH_ST_INDEX, LAUNCH(sphk_index_fixed(s)), P_INDEXPOST};
+static const Stage kFindNeighbors = {"sph_run_find_neighbors", P_SORTPOST | P_INDEXPOST, SPH_ST_FIND_NEIGHBORS, LAUNCH(sphk_find_neighbors(s)), P_FIND};
+static const Stage kComputeDensity = {"sph_run_pcisph_compute_density", P_FIND, SPH_ST_DENSITY, LAUNCH(sphk_density(s)), P_DENSITY};
+static const Stage kComputeForces = {"sph_run_pcisph_compute_forces_and_init_pressure", P_DENSITY, SPH_ST_FORCES, LAUNCH(sphk_forces(s, false)), P_FORCES};
+static const Stage kElasticForces = {"sph_run_pcisph_compute_elastic_forces", P_FORCES, SPH_ST_ELASTIC, LAUNCH(sphk_elastic(s)), 0};
+static const Stage kPredictPositions = {"sph_run_pcisph_predict_positions", P_FORCES, SPH_ST_PRESSURE_FORCE, LAUNCH(sphk_predict_positions(s)), P_PREDICTPOS};
+static const Stage kPredictDensity = {"sph_run_pcisph_predict_density", P_PREDICTPOS, SPH_ST_PREDICT_DENSITY, LAUNCH(sphk_predict_density(s, false)), P_PREDICTDENS};
+static const Stage kCorrectPressure = {"sph_run_pcisph_correct_pressure", P_PREDICTDENS, SPH_ST_PREDICT_DENSITY, LAUNCH(sphk_correct_pressure(s)), 0};
+static const Stage kPressureForce = {"sph_run_pcisph_compute_pressure_force_acceleration", P_PREDICTDENS, SPH_ST_PRESSURE_FORCE, LAUNCH(sphk_pressure_force(s, 0)), P_PRESSUREFORCE};
+static const Stage kIntegrate = {"sph_run_pcisph_integrate", P_FORCES, SPH_ST_INTEGRATE, LAUNCH(sphk_integrate(s)), 0};
+static const Stage kClearMembraneBuffers = {"sph_run_clear_membrane_buffers", 0, SPH_ST_MEMBRANES, LAUNCH(sphk_clear_membranes(s)), 0};
+static const Stage kMembranes = {"sph_run_compute_interaction_with_membranes", P_FIND, SPH_ST_MEMBRANES, LAUNCH(sphk_membranes(s)), 0};
+static const Stage kMembranesFinalize = {"sph_run_compute_interaction_with_membranes_finalize", 0, SPH_ST_MEMBRANES, LAUNCH(sphk_membranes_finalize(s)), 0};
+#undef LAUNCH
+
+static int run_stage(sph_solver* s, const Stage& st) {
+  ENTER(s); NEED(s, st.need, st.name);
+  sph_state_changes(s);
+  StageTimer t(s, st.timer);
+  const int rc = st.launch(s);
+  if (rc == SPH_OK) s->progress = st.gain == P_HASH ? P_HASH : s->progress | st.gain;  // (a new step starts at the hash)
   return rc;
 }
-extern "C" int sph_run_sort(sph_solver* s) {
-  ENTER(s); NEED(s, P_HASH, "sph_run_sort");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_SORT);
-  int rc = sphk_sort(s);
-  if (rc == SPH_OK) s->progress |= P_SORT;
-  return rc;
-}
-extern "C" int sph_run_sort_post_pass(sph_solver* s) {
-  ENTER(s); NEED(s, P_SORT, "sph_run_sort_post_pass");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_SORT_POST);
-  int rc = sphk_sort_post(s);
-  if (rc == SPH_OK) s->progress |= P_SORTPOST;
-  return rc;
-}
-extern "C" int sph_run_indexx(sph_solver* s) {
-  ENTER(s); NEED(s, P_SORT, "sph_run_indexx");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_INDEX);
-  int rc = sphk_index_raw(s);
-  if (rc == SPH_OK) s->progress |= P_INDEXX;
-  return rc;
-}
-extern "C" int sph_run_index_post_pass(sph_solver* s) {
-  ENTER(s); NEED(s, P_INDEXX, "sph_run_index_post_pass");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_INDEX);
-  int rc = sphk_index_fixed(s);
-  if (rc == SPH_OK) s->progress |= P_INDEXPOST;
-  return rc;
-}
-extern "C" int sph_run_find_neighbors(sph_solver* s) {
-  ENTER(s); NEED(s, P_SORTPOST | P_INDEXPOST, "sph_run_find_neighbors");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_FIND_NEIGHBORS);
-  int rc = sphk_find_neighbors(s);
-  if (rc == SPH_OK) s->progress |= P_FIND;
-  return rc;
-}
-extern "C" int sph_run_pcisph_compute_density(sph_solver* s) {
-  ENTER(s); NEED(s, P_FIND, "sph_run_pcisph_compute_density");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_DENSITY);
-  int rc = sphk_density(s);
-  if (rc == SPH_OK) s->progress |= P_DENSITY;
-  return rc;
-}
-extern "C" int sph_run_pcisph_compute_forces_and_init_pressure(sph_solver* s) {
-  ENTER(s); NEED(s, P_DENSITY, "sph_run_pcisph_compute_forces_and_init_pressure");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_FORCES);
-  int rc = sphk_forces(s, false);
-  if (rc == SPH_OK) s->progress |= P_FORCES;
-  return rc;
-}
-extern "C" int sph_run_pcisph_compute_elastic_forces(sph_solver* s) {
-  ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_compute_elastic_forces");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_ELASTIC);
-  return sphk_elastic(s);
-}
-extern "C" int sph_run_pcisph_predict_positions(sph_solver* s) {
-  ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_predict_positions");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_PRESSURE_FORCE);
-  int rc = sphk_predict_positions(s);
-  if (rc == SPH_OK) s->progress |= P_PREDICTPOS;
-  return rc;
-}
-extern "C" int sph_run_pcisph_predict_density(sph_solver* s) {
-  ENTER(s); NEED(s, P_PREDICTPOS, "sph_run_pcisph_predict_density");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_PREDICT_DENSITY);
-  int rc = sphk_predict_density(s, false);
-  if (rc == SPH_OK) s->progress |= P_PREDICTDENS;
-  return rc;
-}
-extern "C" int sph_run_pcisph_correct_pressure(sph_solver* s) {
-  ENTER(s); NEED(s, P_PREDICTDENS, "sph_run_pcisph_correct_pressure");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_PREDICT_DENSITY);
-  return sphk_correct_pressure(s);
-}
-extern "C" int sph_run_pcisph_compute_pressure_force_acceleration(sph_solver* s) {
-  ENTER(s); NEED(s, P_PREDICTDENS, "sph_run_pcisph_compute_pressure_force_acceleration");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_PRESSURE_FORCE);
-  int rc = sphk_pressure_force(s, 0);
-  if (rc == SPH_OK) s->progress |= P_PRESSUREFORCE;
-  return rc;
-}
-extern "C" int sph_run_pcisph_integrate(sph_solver* s, int iterationCount) {
-  (void)iterationCount;  // only used by commented-out debug prints in the reference (sphFluid.cl:1784-1805)
-  ENTER(s); NEED(s, P_FORCES, "sph_run_pcisph_integrate");
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_INTEGRATE);
-  return sphk_integrate(s);
-}
-extern "C" int sph_run_clear_membrane_buffers(sph_solver* s) {
-  ENTER(s);
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_MEMBRANES);
-  return sphk_clear_membranes(s);
-}
+
+extern "C" int sph_run_clear_buffers(sph_solver* s) { return run_stage(s, kClearBuffers); }
+extern "C" int sph_run_hash_particles(sph_solver* s) { return run_stage(s, kHashParticles); }
+extern "C" int sph_run_sort(sph_solver* s) { return run_stage(s, kSort); }
+extern "C" int sph_run_sort_post_pass(sph_solver* s) { return run_stage(s, kSortPostPass); }
+extern "C" int sph_run_indexx(sph_solver* s) { return run_stage(s, kIndexx); }
+extern "C" int sph_run_index_post_pass(sph_solver* s) { return run_stage(s, kIndexPostPass); }
+extern "C" int sph_run_find_neighbors(sph_solver* s) { return run_stage(s, kFindNeighbors); }
+extern "C" int sph_run_pcisph_compute_density(sph_solver* s) { return run_stage(s, kComputeDensity); }
+extern "C" int sph_run_pcisph_compute_forces_and_init_pressure(sph_solver* s) { return run_stage(s, kComputeForces); }
+extern "C" int sph_run_pcisph_compute_elastic_forces(sph_solver* s) { return run_stage(s, kElasticForces); }
+extern "C" int sph_run_pcisph_predict_positions(sph_solver* s) { return run_stage(s, kPredictPositions); }
+extern "C" int sph_run_pcisph_predict_density(sph_solver* s) { return run_stage(s, kPredictDensity); }
+extern "C" int sph_run_pcisph_correct_pressure(sph_solver* s) { return run_stage(s, kCorrectPressure); }
+extern "C" int sph_run_pcisph_compute_pressure_force_acceleration(sph_solver* s) { return run_stage(s, kPressureForce); }
+// (iterationCount is only used by commented-out debug prints in the reference, sphFluid.cl:1784-1805)
+extern "C" int sph_run_pcisph_integrate(sph_solver* s, int /*iterationCount*/) { return run_stage(s, kIntegrate); }
+extern "C" int sph_run_clear_membrane_buffers(sph_solver* s) { return run_stage(s, kClearMembraneBuffers); }
 extern "C" int sph_run_compute_interaction_with_membranes(sph_solver* s) {
-  ENTER(s); NEED(s, P_FIND, "sph_run_compute_interaction_with_membranes");
-  if (!s->d.pml) return SPH_OK;  // no membrane lists were supplied
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_MEMBRANES);
-  return sphk_membranes(s);
+  ENTER(s); NEED(s, kMembranes.need, kMembranes.name);
+  if (!s->d.pml) return SPH_OK;  // no membrane lists were supplied: nothing runs and nothing changes
+  return run_stage(s, kMembranes);
 }
-extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s) {
-  ENTER(s);
-  s->stateEpoch++;
-  StageTimer t(s, SPH_ST_MEMBRANES);
-  return sphk_membranes_finalize(s);
-}
+extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s) { return run_stage(s, kMembranesFinalize); }
 
 // The fused fast path. Stage sequence of simulationStep() (owPhysicsFluidSimulator.cpp:88-113) with:
 //   clearBuffers folded into findNeighbors; sortPostPass + indexx + index fix-up in one kernel;
@@ -556,14 +468,9 @@ extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s
 // The launches of one fused step, in order, on s->stream. `tail` (slab mode, overlapped step only): the last stage —
 // pressure force + integrate, the only one whose results the halo messages carry — is launched first on the owned layers
 // next to the cuts, then the messages are packed (tail->packMessages), then the remaining owned layers follow.
-struct StepTail {
-  uint32_t *frameDown, *frameUp;
-  int capRecords;
-};
-
-static int enqueue_step(sph_solver* s, const StepTail* tail) {
+int enqueue_step(sph_solver* s, const StepTail* tail) {
   int rc;
-  s->stateEpoch++;
+  sph_state_changes(s);
 #define RUN(stage, call) do { StageTimer t_(s, stage); rc = (call); if (rc != SPH_OK) return rc; } while (0)
   if (s->hasSlab) {
     RUN(SPH_ST_SORT, sphk_hash_sort_post_slab(s));
@@ -658,519 +565,4 @@ extern "C" int sph_step_sort_passes(sph_solver* s) {
 extern "C" int sph_synchronize(sph_solver* s) {
   ENTER(s);
   return sph_check_finite_state(s);  // (synchronises the stream)
-}
-
-// ---------------------------------------------------------------------------------------------- read-back
-int sph_d2h(sph_solver* s, void* dst, const void* src, size_t bytes) {
-  SPH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream));
-  SPH_HIP(hipStreamSynchronize(s->stream));
-  return SPH_OK;
-}
-
-// dbg[6]: particles with a non-finite coordinate seen by the hash kernel (the state has blown up). Sticky: once seen, every
-// blocking call keeps reporting it until the solver is destroyed — a caller that ignores one SPH_ERR_INVALID does not continue
-// silently on NaN state.
-static int report_blown_up(sph_solver* s) {
-  sph_set_error("%llu particle coordinate(s) were not finite: the simulation state has blown up", (unsigned long long)s->blownUp);
-  return SPH_ERR_INVALID;
-}
-int sph_check_finite_state(sph_solver* s) {
-  uint32_t bad = 0;
-  SPH_HIP(hipMemcpyAsync(&bad, s->d.dbg + 6, sizeof(bad), hipMemcpyDeviceToHost, s->stream));
-  SPH_HIP(hipStreamSynchronize(s->stream));
-  if (bad) {
-    s->blownUp += bad;
-    SPH_HIP(hipMemsetAsync(s->d.dbg + 6, 0, sizeof(uint32_t), s->stream));
-  }
-  return s->blownUp ? report_blown_up(s) : SPH_OK;
-}
-
-extern "C" int sph_read_position(sph_solver* s, float* out) {
-  ENTER(s); if (!out) return SPH_ERR_INVALID;
-  const int rc = sph_d2h(s, out, s->d.posOrig, sizeof(float4) * (size_t)s->d.N);
-  return rc != SPH_OK ? rc : sph_check_finite_state(s);
-}
-// ---- asynchronous read_position_buffer. The reference's step always ends with a blocking 16N-byte read
-// (owPhysicsFluidSimulator.cpp:115; 264 MB at 16.5 M particles: +45 % on the step when it is waited for). posOrig is written by
-// exactly one kernel per step, the last one (integrate; + the membrane finalize pass), so the copy of step t can run on its own
-// stream under the search and PCISPH stages of step t+1: copyStream waits for an event recorded on s->stream when the read is
-// requested, and the next kernel that writes posOrig waits for the copy's event (sph_guard_position_write).
-static int copy_setup(sph_solver* s) {
-  if (s->copyStream) return SPH_OK;
-  SPH_HIP(hipStreamCreateWithFlags(&s->copyStream, hipStreamNonBlocking));
-  SPH_HIP(hipEventCreateWithFlags(&s->evReadReady, hipEventDisableTiming));
-  SPH_HIP(hipEventCreateWithFlags(&s->evCopyDone, hipEventDisableTiming));
-  SPH_HIP(hipHostMalloc((void**)&s->pinnedFlags, sizeof(uint32_t) * 4, hipHostMallocDefault));
-  s->pinnedFlags[0] = 0u;
-  return SPH_OK;
-}
-
-// true if the DMA engine can write [p, p + bytes) directly: pinned already, or page-locked in place now
-static bool host_pinned(sph_solver* s, void* p, size_t bytes) {
-  for (int i = 0; i < s->numHostRegs; i++)
-    if ((char*)p >= (char*)s->hostRegs[i].p && (char*)p + bytes <= (char*)s->hostRegs[i].p + s->hostRegs[i].bytes) return true;
-  unsigned int flags = 0;
-  if (hipHostGetFlags(&flags, p) == hipSuccess) return true;  // hipHostMalloc'ed or registered by the caller
-  (void)hipGetLastError();
-  if (s->numHostRegs >= 8) return false;
-  const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
-  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-  s->hostRegs[s->numHostRegs].p = p; s->hostRegs[s->numHostRegs].bytes = bytes; s->numHostRegs++;
-  return true;
-}
-
-extern "C" int sph_read_position_wait(sph_solver* s) {
-  ENTER(s);
-  if (!s->copyPending) return s->blownUp ? report_blown_up(s) : SPH_OK;
-  SPH_HIP(hipEventSynchronize(s->evCopyDone));
-  s->copyPending = false;
-  if (s->copyViaStage) memcpy(s->copyUserDst, s->copyStage, s->copyBytes);  // (the count at request time: an edit may have changed d.N)
-  if (s->pinnedFlags[0]) {  // (the device counter keeps counting; it is cleared by the next blocking check)
-    if (!s->blownUp) s->blownUp = s->pinnedFlags[0];
-    return report_blown_up(s);
-  }
-  return s->blownUp ? report_blown_up(s) : SPH_OK;
-}
-
-extern "C" int sph_read_position_async(sph_solver* s, float* out) {
-  ENTER(s); if (!out) return SPH_ERR_INVALID;
-  int rc = copy_setup(s);
-  if (rc != SPH_OK) return rc;
-  if (s->copyPending) {  // the previous read must have landed before its staging area / flags are reused (long done in a step loop)
-    rc = sph_read_position_wait(s);
-    if (rc != SPH_OK) return rc;
-  }
-  const size_t bytes = sizeof(float4) * (size_t)s->d.N;
-  void* dst = out;
-  s->copyViaStage = false;
-  if (!host_pinned(s, out, bytes)) {
-    if (s->copyStageBytes < bytes) {
-      if (s->copyStage) hipHostFree(s->copyStage);
-      s->copyStage = nullptr; s->copyStageBytes = 0;
-      SPH_HIP(hipHostMalloc(&s->copyStage, bytes, hipHostMallocDefault));
-      s->copyStageBytes = bytes;
-    }
-    dst = s->copyStage;
-    s->copyViaStage = true;
-  }
-  s->copyUserDst = out;
-  s->copyBytes = bytes;
-  SPH_HIP(hipEventRecord(s->evReadReady, s->stream));
-  SPH_HIP(hipStreamWaitEvent(s->copyStream, s->evReadReady, 0));
-  SPH_HIP(hipMemcpyAsync(dst, s->d.posOrig, bytes, hipMemcpyDeviceToHost, s->copyStream));
-  SPH_HIP(hipMemcpyAsync(s->pinnedFlags, s->d.dbg + 6, sizeof(uint32_t), hipMemcpyDeviceToHost, s->copyStream));
-  SPH_HIP(hipEventRecord(s->evCopyDone, s->copyStream));
-  s->copyPending = true;
-  return SPH_OK;
-}
-
-extern "C" int sph_host_unregister(sph_solver* s, void* p) {
-  ENTER(s);
-  if (s->copyPending) { const int rc = sph_read_position_wait(s); if (rc != SPH_OK && rc != SPH_ERR_INVALID) return rc; }
-  for (int i = 0; i < s->numHostRegs; i++)
-    if (s->hostRegs[i].p == p) {
-      hipHostUnregister(p);
-      s->hostRegs[i] = s->hostRegs[--s->numHostRegs];
-      return SPH_OK;
-    }
-  return SPH_OK;  // not one of ours: nothing to do
-}
-
-int sph_guard_position_write(sph_solver* s) {
-  if (s->copyPending) SPH_HIP(hipStreamWaitEvent(s->stream, s->evCopyDone, 0));
-  return SPH_OK;
-}
-
-extern "C" int sph_read_velocity(sph_solver* s, float* out) {
-  ENTER(s); if (!out) return SPH_ERR_INVALID;
-  return sph_d2h(s, out, s->d.velOrig, sizeof(float4) * (size_t)s->d.N);
-}
-extern "C" int sph_read_density(sph_solver* s, float* out) {
-  ENTER(s); if (!out) return SPH_ERR_INVALID;
-  return sph_d2h(s, out, s->d.rho, sizeof(float) * (size_t)s->d.N);
-}
-extern "C" int sph_read_particle_index(sph_solver* s, uint32_t* out) {
-  ENTER(s); if (!out) return SPH_ERR_INVALID;
-  const size_t n = (size_t)s->d.N;
-  std::vector<uint32_t> k(n), v(n);
-  int rc = sph_d2h(s, k.data(), s->d.keys, sizeof(uint32_t) * n);
-  if (rc == SPH_OK) rc = sph_d2h(s, v.data(), s->d.vals, sizeof(uint32_t) * n);
-  if (rc != SPH_OK) return rc;
-  for (size_t i = 0; i < n; i++) { out[2 * i] = k[i]; out[2 * i + 1] = v[i]; }
-  return SPH_OK;
-}
-
-// Export in the reference's layouts (SURVEY table 2.2). Test/inspection path: converts on the host.
-extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_t bytes, size_t* needed) {
-  ENTER(s);
-  if (!name) return SPH_ERR_INVALID;
-  const SphDev& d = s->d;
-  const size_t n = (size_t)d.N, G1 = (size_t)d.G + 1;
-  const int numTiles = (d.N + SPH_TILE - 1) / SPH_TILE;
-  size_t need = 0;
-  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE } which;
-  if (!strcmp(name, "position")) { which = B_POS; need = sizeof(float4) * 2 * n; }
-  else if (!strcmp(name, "velocity")) { which = B_VEL; need = sizeof(float4) * 2 * n; }
-  else if (!strcmp(name, "sortedPosition")) { which = B_SPOS; need = sizeof(float4) * 2 * n; }
-  else if (!strcmp(name, "sortedVelocity")) { which = B_SVEL; need = sizeof(float4) * n; }
-  else if (!strcmp(name, "acceleration")) { which = B_ACC; need = sizeof(float4) * 2 * n; }
-  else if (!strcmp(name, "neighborMap")) { which = B_NMAP; need = sizeof(float) * 2 * 32 * n; }
-  else if (!strcmp(name, "neighborIds")) { which = B_NIDS; need = sizeof(int32_t) * 32 * n; }
-  else if (!strcmp(name, "particleIndex")) { which = B_PI; need = sizeof(uint32_t) * 2 * n; }
-  else if (!strcmp(name, "particleIndexBack")) { which = B_PIB; need = sizeof(uint32_t) * n; }
-  else if (!strcmp(name, "gridCellIndex")) { which = B_GCI; need = sizeof(uint32_t) * G1; }
-  else if (!strcmp(name, "gridCellIndexFixedUp")) { which = B_GCIF; need = sizeof(uint32_t) * G1; }
-  else if (!strcmp(name, "pressure")) { which = B_P; need = sizeof(float) * n; }
-  else if (!strcmp(name, "rho")) { which = B_RHO; need = sizeof(float) * 2 * n; }
-  else if (!strcmp(name, "diagnosticTrace")) { which = B_TRACE; need = sizeof(uint32_t) * n; }  // scratch words of diagnostic builds
-  else if (!strcmp(name, "debugCounters")) { which = B_DBG; need = sizeof(uint32_t) * SPH_DBG_WORDS; }
-  else { sph_set_error("unknown buffer '%s'", name); return SPH_ERR_UNKNOWN_BUFFER; }
-  if (needed) *needed = need;
-  if (!out) return SPH_OK;
-  if (bytes != need) { sph_set_error("buffer '%s' is %zu bytes, caller gave %zu", name, need, bytes); return SPH_ERR_SIZE; }
-  int rc = SPH_OK;
-  char* o = (char*)out;
-  switch (which) {
-    case B_POS:
-      rc = sph_d2h(s, o, d.posOrig, sizeof(float4) * n);
-      if (rc == SPH_OK) { if (d.membDelta) rc = sph_d2h(s, o + sizeof(float4) * n, d.membDelta, sizeof(float4) * n); else memset(o + sizeof(float4) * n, 0, sizeof(float4) * n); }
-      break;
-    case B_VEL:
-      rc = sph_d2h(s, o, d.velOrig, sizeof(float4) * n);
-      memset(o + sizeof(float4) * n, 0, sizeof(float4) * n);  // the scratch half is only ever zeroed (App. B #16)
-      break;
-    case B_SPOS: {
-      std::vector<uint32_t> k(n);
-      std::vector<float4> sv(n);
-      rc = sph_d2h(s, o, d.sortedPos, sizeof(float4) * n);
-      if (rc == SPH_OK) {  // the predicted half: packed (x, y, z) on the device; .w is dead data in the reference
-        std::vector<float> p3(3 * n);
-        rc = sph_d2h(s, p3.data(), d.predPos, sizeof(float) * 3 * n);
-        float4* half = (float4*)(o + sizeof(float4) * n);
-        if (rc == SPH_OK) for (size_t i = 0; i < n; i++) half[i] = make_float4(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], 0.f);
-      }
-      if (rc == SPH_OK) rc = sph_d2h(s, k.data(), d.keys, sizeof(uint32_t) * n);
-      if (rc == SPH_OK) rc = sph_d2h(s, sv.data(), d.sortedVel, sizeof(float4) * n);
-      if (rc != SPH_OK) break;
-      float4* a = (float4*)o;
-      for (size_t i = 0; i < n; i++) {
-        const int type = (int)a[i].w;
-        const float cellf = (float)(int)k[i];  // POSITION_CELL_ID = (float)cellId (sphFluid.cl:461)
-        a[i].w = cellf;
-        // .w of the predicted half is dead data in the reference: cell id for boundary particles, cell id + posTimeStep *
-        // (v.w + dt*a_p.w) otherwise, with a_p.w == 0
-        a[n + i].w = (type == SPH_BOUNDARY_PARTICLE) ? cellf : cellf + d.posTimeStep * (sv[i].w + d.dt * 0.f);
-      }
-    } break;
-    case B_SVEL: rc = sph_d2h(s, o, d.sortedVel, sizeof(float4) * n); break;
-    case B_ACC:
-      rc = sph_d2h(s, o, d.acc, sizeof(float4) * n);
-      if (rc == SPH_OK) rc = sph_d2h(s, o + sizeof(float4) * n, d.accP, sizeof(float4) * n);
-      break;
-    case B_NMAP:
-    case B_NIDS: {
-      const size_t mapN = (size_t)numTiles * 64 * 32;
-      std::vector<int32_t> ids(mapN);
-      std::vector<float> dist(mapN);
-      std::vector<uint16_t> n16(mapN);
-      std::vector<int32_t> nbase((size_t)numTiles * 64);
-      rc = sph_d2h(s, ids.data(), d.nbrId, sizeof(int32_t) * mapN);
-      if (rc == SPH_OK) rc = sph_d2h(s, n16.data(), d.nbr16, sizeof(uint16_t) * mapN);
-      if (rc == SPH_OK) rc = sph_d2h(s, nbase.data(), d.nbrBase, sizeof(int32_t) * nbase.size());
-      if (rc == SPH_OK) rc = sph_d2h(s, dist.data(), d.nbrDist, sizeof(float) * mapN);
-      if (rc == SPH_OK)  // the ids live in the 16-bit map (sph_common.h); the 32-bit rows only where that could not be written
-        for (size_t id = 0; id < n; id++)
-          for (int k = 0; k < 32; k++) ids[nbr_index((int)id, k)] = nbr_decode(n16.data(), nbase.data(), ids.data(), (int)id, k);
-      if (rc != SPH_OK) break;
-      for (size_t id = 0; id < n; id++)
-        for (int k = 0; k < 32; k++) {
-          const size_t src = nbr_index((int)id, k);
-          if (which == B_NIDS) ((int32_t*)o)[id * 32 + k] = ids[src];
-          else { ((float*)o)[(id * 32 + k) * 2] = (float)ids[src]; ((float*)o)[(id * 32 + k) * 2 + 1] = dist[src]; }
-        }
-    } break;
-    case B_PI: rc = sph_read_particle_index(s, (uint32_t*)o); break;
-    case B_PIB: rc = sph_d2h(s, o, d.backIndex, sizeof(uint32_t) * n); break;
-    case B_GCI: rc = sph_d2h(s, o, d.cellStartRaw, sizeof(uint32_t) * G1); break;
-    case B_GCIF: rc = sph_d2h(s, o, d.cellStart, sizeof(uint32_t) * G1); break;
-    case B_P: {
-      std::vector<float2> rp(n);
-      rc = sph_d2h(s, rp.data(), d.rp, sizeof(float2) * n);
-      if (rc == SPH_OK) for (size_t i = 0; i < n; i++) ((float*)o)[i] = rp[i].y;
-    } break;
-    case B_TRACE: rc = sph_d2h(s, o, d.valsAlt, sizeof(uint32_t) * n); break;
-    case B_DBG: rc = sph_d2h(s, o, d.dbg, sizeof(uint32_t) * SPH_DBG_WORDS); break;
-    case B_RHO:
-      rc = sph_d2h(s, o, d.rho, sizeof(float) * n);
-      if (rc == SPH_OK) {
-        std::vector<float2> rp(n);
-        rc = sph_d2h(s, rp.data(), d.rp, sizeof(float2) * n);
-        if (rc == SPH_OK) for (size_t i = 0; i < n; i++) ((float*)o)[n + i] = rp[i].x;
-      }
-      break;
-  }
-  return rc;
-}
-
-extern "C" int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t count, int32_t* ids, float* dist) {
-  ENTER(s);
-  if (first < 0 || count < 0 || (long long)first + count > s->d.N) { sph_set_error("sph_read_neighbor_rows: range outside [0, N)"); return SPH_ERR_INVALID; }
-  if (count == 0) return SPH_OK;
-  const size_t t0 = (size_t)first / SPH_TILE, t1 = ((size_t)first + count + SPH_TILE - 1) / SPH_TILE;  // tiles [t0, t1)
-  const size_t words = (t1 - t0) * 64 * 32, base = t0 * 64 * 32;
-  std::vector<int32_t> ti;
-  std::vector<float> td;
-  int rc = SPH_OK;
-  std::vector<uint16_t> t16;
-  std::vector<int32_t> tb;
-  if (ids) {
-    ti.resize(words); t16.resize(words); tb.resize((t1 - t0) * 64);
-    rc = sph_d2h(s, ti.data(), s->d.nbrId + base, sizeof(int32_t) * words);
-    if (rc == SPH_OK) rc = sph_d2h(s, t16.data(), s->d.nbr16 + base, sizeof(uint16_t) * words);
-    if (rc == SPH_OK) rc = sph_d2h(s, tb.data(), s->d.nbrBase + t0 * 64, sizeof(int32_t) * tb.size());
-  }
-  if (rc == SPH_OK && dist) { td.resize(words); rc = sph_d2h(s, td.data(), s->d.nbrDist + base, sizeof(float) * words); }
-  if (rc != SPH_OK) return rc;
-  const int shift = (int)(t0 * 64);  // the copies start at tile t0: decode with tile-relative particle numbers
-  for (int32_t i = 0; i < count; i++)
-    for (int k = 0; k < 32; k++) {
-      const size_t src = nbr_index(first + i, k) - base;
-      if (ids) {
-        int j = nbr_decode(t16.data(), tb.data(), ti.data(), first + i - shift, k);
-        // (offsets are relative to the particle's own sorted index: undo the tile-relative numbering for the unflagged ones)
-        const uint32_t e = t16[src];
-        if (t16[nbr_index(first + i - shift, 0)] != SPH_N16_WIDE && e != SPH_N16_EMPTY && !(e & 0x8000u)) j += shift;
-        ids[(size_t)i * 32 + k] = j;
-      }
-      if (dist) dist[(size_t)i * 32 + k] = td[src];
-    }
-  return SPH_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- slab decomposition
-extern "C" int sph_particle_count(sph_solver* s) {
-  ENTER(s);
-  return s->d.N;
-}
-
-extern "C" int sph_slab_init(sph_solver* s, const sph_slab* slab, const uint32_t* globalIds) {
-  ENTER(s);
-  s->stateEpoch++;
-  if (!slab || !globalIds) { sph_set_error("sph_slab_init: null argument"); return SPH_ERR_INVALID; }
-  if (s->cfg.cellIdMask != 0xffffffffu) { sph_set_error("slab decomposition needs wide cell ids (cellIdMask = 0xffffffff)"); return SPH_ERR_INVALID; }
-  if (s->d.hasElastic) { sph_set_error("slab decomposition supports pure-liquid scenes only"); return SPH_ERR_INVALID; }
-  if (slab->layerLo >= slab->layerHi || slab->ghostLayers < 1 || slab->globalIdBits < 1 || slab->globalIdBits > 32) { sph_set_error("bad sph_slab"); return SPH_ERR_INVALID; }
-  if ((2 * s->cfg.maxIteration * 31 + 59) / 60 > slab->ghostLayers) {  // 2*maxIteration hops of 31h/30 must fit the ghost zone
-    sph_set_error("ghostLayers = %d is too thin for maxIteration = %d", slab->ghostLayers, s->cfg.maxIteration);
-    return SPH_ERR_INVALID;
-  }
-  s->slab = *slab; s->hasSlab = true; s->slabKept = -1; s->slabStepPending = false;
-  if (!s->slabHost) SPH_HIP(hipHostMalloc((void**)&s->slabHost, sizeof(uint32_t) * SPH_SLAB_COUNT_WORDS, hipHostMallocDefault));
-  if (!s->slabMsgEvent) SPH_HIP(hipEventCreateWithFlags(&s->slabMsgEvent, hipEventDisableTiming));
-  if (!s->slabRebuildEvent) SPH_HIP(hipEventCreateWithFlags(&s->slabRebuildEvent, hipEventDisableTiming));
-  SPH_HIP(hipMemcpyAsync(s->d.gid, globalIds, sizeof(uint32_t) * (size_t)s->d.N, hipMemcpyHostToDevice, s->stream));
-  // ownership flags from the initial positions: reuse the rebuild path with nothing received
-  SPH_HIP(hipMemcpyAsync(s->d.sortedPos, s->d.posOrig, sizeof(float4) * (size_t)s->d.N, hipMemcpyDeviceToDevice, s->stream));
-  SPH_HIP(hipMemcpyAsync(s->d.sortedVel, s->d.velOrig, sizeof(float4) * (size_t)s->d.N, hipMemcpyDeviceToDevice, s->stream));
-  SPH_HIP(hipMemcpyAsync(s->d.keys, s->d.gid, sizeof(uint32_t) * (size_t)s->d.N, hipMemcpyDeviceToDevice, s->stream));
-  SPH_HIP(hipMemsetAsync(s->slabCounts, 0, sizeof(uint32_t) * SPH_SLAB_COUNT_WORDS, s->stream));
-  int rc = sphk_slab_sort_rebuild(s, s->d.N);
-  if (rc != SPH_OK) return rc;
-  SPH_HIP(hipStreamSynchronize(s->stream));
-  return SPH_OK;
-}
-
-// An owned particle moved more than one cell layer in a step: the assumption behind the halo depth (include/sphmi.h) is broken
-static int slab_motion_error(sph_solver* s, uint32_t n) {
-  hipMemsetAsync(s->slabCounts + 7, 0, sizeof(uint32_t), s->stream);
-  sph_set_error("%u owned particle(s) moved more than one cell layer in one step: the %d-layer halo no longer guarantees "
-                "single-domain results (time step too large for these velocities?)", n, s->slab.ghostLayers);
-  return SPH_ERR_INVALID;
-}
-
-static int slab_pack(sph_solver* s, uint32_t* msgDown, uint32_t* msgUp, int32_t capRecords, int32_t counts[3], uint32_t* headDown,
-                     uint32_t* headUp) {
-  int rc = sphk_slab_pack(s, msgDown, msgUp, capRecords, headDown, headUp);
-  if (rc != SPH_OK) return rc;
-  uint32_t h[8];
-  SPH_HIP(hipMemcpyAsync(h, s->slabCounts, sizeof(h), hipMemcpyDeviceToHost, s->stream));
-  SPH_HIP(hipStreamSynchronize(s->stream));
-  counts[0] = (int32_t)h[0]; counts[1] = (int32_t)h[1]; counts[2] = (int32_t)h[2];
-  if (h[3]) {  // raised by the last rebuild's merge kernels
-    SPH_HIP(hipMemsetAsync(s->slabCounts + 3, 0, sizeof(uint32_t), s->stream));
-    sph_set_error("a halo message passed to the last sph_slab_rebuild was not sorted by global id");
-    return SPH_ERR_INVALID;
-  }
-  if (h[7]) return slab_motion_error(s, h[7]);
-  s->slabKept = (int)h[0];
-  if ((int)h[1] > capRecords || (int)h[2] > capRecords) { sph_set_error("halo message overflow: %u / %u records, room for %d", h[1], h[2], capRecords); return SPH_ERR_SIZE; }
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_pack(sph_solver* s, void* msgDown, void* msgUp, int32_t capRecords, int32_t counts[3]) {
-  ENTER(s);
-  if (!s->hasSlab || !counts || capRecords < 0 || ((s->slab.hasLower && !msgDown) || (s->slab.hasUpper && !msgUp))) {
-    sph_set_error("sph_slab_pack: slab not initialised or null message buffer"); return SPH_ERR_INVALID; }
-  return slab_pack(s, (uint32_t*)msgDown, (uint32_t*)msgUp, capRecords, counts, nullptr, nullptr);
-}
-
-extern "C" int sph_slab_pack_framed(sph_solver* s, void* frameDown, void* frameUp, int32_t capRecords, int32_t counts[3]) {
-  ENTER(s);
-  if (!s->hasSlab || !counts || capRecords < 0 || ((s->slab.hasLower && !frameDown) || (s->slab.hasUpper && !frameUp))) {
-    sph_set_error("sph_slab_pack_framed: slab not initialised or null frame buffer"); return SPH_ERR_INVALID; }
-  uint32_t* fd = (uint32_t*)frameDown;
-  uint32_t* fu = (uint32_t*)frameUp;
-  return slab_pack(s, fd ? fd + 1 : nullptr, fu ? fu + 1 : nullptr, capRecords, counts, fd, fu);
-}
-
-// ---- overlapped step: sph_slab_step_begin enqueues everything and returns; sph_slab_step_messages blocks only until the
-// messages are packed (the rest of the step is still running); sph_slab_rebuild then waits for the step itself.
-extern "C" int sph_slab_step_begin(sph_solver* s, int iterationCount, void* frameDown, void* frameUp, int32_t capRecords) {
-  (void)iterationCount;
-  ENTER(s);
-  if (!s->hasSlab || capRecords < 0 || (s->slab.hasLower && !frameDown) || (s->slab.hasUpper && !frameUp)) {
-    sph_set_error("sph_slab_step_begin: slab not initialised or null frame buffer"); return SPH_ERR_INVALID; }
-  if (s->slabStepPending) { sph_set_error("sph_slab_step_begin: the previous overlapped step was not rebuilt"); return SPH_ERR_ORDER; }
-  StepTail tail{(uint32_t*)frameDown, (uint32_t*)frameUp, (int)capRecords};
-  const int rc = enqueue_step(s, &tail);
-  if (rc != SPH_OK) return rc;
-  s->slabStepPending = true;
-  s->slabKept = -1;
-  s->slabCapRecords = (int)capRecords;
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_step_messages(sph_solver* s, int32_t counts[2]) {
-  ENTER(s);
-  if (!s->hasSlab || !s->slabStepPending || !counts) { sph_set_error("sph_slab_step_messages without sph_slab_step_begin"); return SPH_ERR_ORDER; }
-  SPH_HIP(hipEventSynchronize(s->slabMsgEvent));
-  counts[0] = (int32_t)s->slabHost[5]; counts[1] = (int32_t)s->slabHost[6];
-  if (counts[0] > s->slabCapRecords || counts[1] > s->slabCapRecords) {
-    sph_set_error("halo message overflow: %d / %d records, room for %d", counts[0], counts[1], s->slabCapRecords);
-    return SPH_ERR_SIZE;
-  }
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_rebuild(sph_solver* s, const void* recvDown, int32_t nDown, const void* recvUp, int32_t nUp) {
-  ENTER(s);
-  s->stateEpoch++;
-  if (!s->hasSlab || nDown < 0 || nUp < 0 || (nDown && !recvDown) || (nUp && !recvUp)) { sph_set_error("sph_slab_rebuild: bad arguments"); return SPH_ERR_INVALID; }
-  if (s->slabStepPending) {  // overlapped step: the kept count arrives with the end of the step
-    SPH_HIP(hipStreamSynchronize(s->stream));
-    s->slabStepPending = false;
-    if (s->slabHost[3]) {
-      SPH_HIP(hipMemsetAsync(s->slabCounts + 3, 0, sizeof(uint32_t), s->stream));
-      sph_set_error("a halo message passed to the last sph_slab_rebuild was not sorted by global id");
-      return SPH_ERR_INVALID;
-    }
-    if (s->slabHost[7]) return slab_motion_error(s, s->slabHost[7]);
-    s->slabKept = (int)s->slabHost[8];
-  }
-  if (s->slabKept < 0) { sph_set_error("sph_slab_rebuild without a preceding sph_slab_pack"); return SPH_ERR_ORDER; }
-  const int kept = s->slabKept;
-  s->slabKept = -1;
-  const long long total = (long long)kept + nDown + nUp;
-  if (total > s->capacity || total <= 0) { sph_set_error("slab holds %lld particles after the exchange, capacity %d", total, s->capacity); return SPH_ERR_SIZE; }
-  return sphk_slab_rebuild(s, (const uint32_t*)recvDown, nDown, (const uint32_t*)recvUp, nUp, kept);
-}
-
-// ---- the rebuild without a host round trip. The frames are what RCCL delivered: [payload words | payload]; the kept count is
-// where the pack left it on the device. Everything is enqueued at once; the totals come back through pinned memory and
-// sph_slab_finish (called by sph_slab_rebuild_finish, or implicitly by the next entry point) sets the new particle count.
-extern "C" int sph_slab_rebuild_framed(sph_solver* s, const void* frameDown, int32_t capDownRecords, const void* frameUp,
-                                       int32_t capUpRecords) {
-  ENTER(s);
-  s->stateEpoch++;
-  if (!s->hasSlab || capDownRecords < 0 || capUpRecords < 0 || (s->slab.hasLower && !frameDown) || (s->slab.hasUpper && !frameUp)) {
-    sph_set_error("sph_slab_rebuild_framed: slab not initialised, negative capacity, or no frame from a neighbour that exists");
-    return SPH_ERR_INVALID;
-  }
-  const uint32_t* keptPtr;
-  if (s->slabStepPending) keptPtr = s->slabCounts + 8;       // overlapped step: the kept pass of sph_slab_step_begin
-  else if (s->slabKept >= 0) keptPtr = s->slabCounts + 0;    // sph_slab_pack / sph_slab_pack_framed
-  else { sph_set_error("sph_slab_rebuild_framed without a preceding pack"); return SPH_ERR_ORDER; }
-  s->slabCapDown = frameDown ? capDownRecords : 0; s->slabCapUp = frameUp ? capUpRecords : 0;
-  int rc = sphk_slab_rebuild_framed(s, (const uint32_t*)frameDown, s->slabCapDown, (const uint32_t*)frameUp, s->slabCapUp, keptPtr, s->slabCounts + 12);
-  if (rc != SPH_OK) return rc;
-  SPH_HIP(hipMemcpyAsync(s->slabHost + 12, s->slabCounts + 12, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
-  SPH_HIP(hipEventRecord(s->slabRebuildEvent, s->stream));
-  s->slabRebuildPending = true;
-  return SPH_OK;
-}
-
-// counts: kept, records from below, records from above, and 1 if NOTHING was merged because a frame announced more records than
-// its buffer had room for (the caller fetches the missing part and rebuilds with sph_slab_rebuild; the state is untouched).
-int sph_slab_finish(sph_solver* s, int32_t counts[4]) {
-  SPH_HIP(hipEventSynchronize(s->slabRebuildEvent));
-  s->slabRebuildPending = false;
-  if (s->slabStepPending) {  // the flags that came back with the end of the overlapped step
-    s->slabStepPending = false;
-    if (s->slabHost[3]) {
-      SPH_HIP(hipMemsetAsync(s->slabCounts + 3, 0, sizeof(uint32_t), s->stream));
-      sph_set_error("a halo message passed to the last rebuild was not sorted by global id");
-      return SPH_ERR_INVALID;
-    }
-    if (s->slabHost[7]) return slab_motion_error(s, s->slabHost[7]);
-  }
-  const int kept = (int)s->slabHost[12], nDown = (int)s->slabHost[13], nUp = (int)s->slabHost[14];
-  const bool nothing = s->slabHost[15] != 0u;
-  if (counts) { counts[0] = kept; counts[1] = nDown; counts[2] = nUp; counts[3] = nothing ? 1 : 0; }
-  if (nothing) {
-    if (nDown <= s->slabCapDown && nUp <= s->slabCapUp) {
-      sph_set_error("slab holds %lld particles after the exchange, capacity %d", (long long)kept + nDown + nUp, s->capacity);
-      return SPH_ERR_SIZE;
-    }
-    s->slabKept = kept;  // the frames were too short: sph_slab_rebuild with the complete messages finishes the job
-    if (!counts) { sph_set_error("a halo frame announced %d / %d records, room for %d / %d", nDown, nUp, s->slabCapDown, s->slabCapUp); return SPH_ERR_SIZE; }
-    return SPH_OK;
-  }
-  s->slabKept = -1;
-  s->d.N = kept + nDown + nUp;
-  s->progress = 0;
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_rebuild_finish(sph_solver* s, int32_t counts[4]) {
-  ENTER_RAW(s);
-  if (!counts) { sph_set_error("sph_slab_rebuild_finish: null argument"); return SPH_ERR_INVALID; }
-  if (!s->slabRebuildPending) { sph_set_error("sph_slab_rebuild_finish without sph_slab_rebuild_framed"); return SPH_ERR_ORDER; }
-  return sph_slab_finish(s, counts);
-}
-
-extern "C" int sph_slab_liquid_signature(sph_solver* s, uint32_t* typeBits) {
-  ENTER(s);
-  if (!typeBits) return SPH_ERR_INVALID;
-  *typeBits = s->liquidSig;
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_set_record_format(sph_solver* s, int32_t recordWords, uint32_t typeBits) {
-  ENTER(s);
-  if (recordWords != SPH_SLAB_RECORD_WORDS && recordWords != SPH_SLAB_COMPACT_WORDS) { sph_set_error("record words must be %d or %d", SPH_SLAB_RECORD_WORDS, SPH_SLAB_COMPACT_WORDS); return SPH_ERR_INVALID; }
-  if (recordWords == SPH_SLAB_COMPACT_WORDS && (s->liquidSig == 0xffffffffu || (s->liquidSig != 0u && s->liquidSig != typeBits))) {
-    sph_set_error("compact halo records need one common type word and velocity.w == 0 for every non-boundary particle");
-    return SPH_ERR_INVALID;
-  }
-  s->slabRecWords = recordWords; s->slabTypeBits = typeBits;
-  return SPH_OK;
-}
-
-extern "C" int sph_stream_wait_event(sph_solver* s, void* hipEvent) {
-  ENTER(s);
-  if (!hipEvent) return SPH_ERR_INVALID;
-  SPH_HIP(hipStreamWaitEvent(s->stream, (hipEvent_t)hipEvent, 0));
-  return SPH_OK;
-}
-
-extern "C" int sph_slab_read(sph_solver* s, float* position4, float* velocity4, uint32_t* globalIds, uint32_t* owned) {
-  ENTER(s);
-  if (!s->hasSlab) { sph_set_error("slab not initialised"); return SPH_ERR_INVALID; }
-  const size_t n = (size_t)s->d.N;
-  int rc = SPH_OK;
-  if (position4) rc = sph_d2h(s, position4, s->d.posOrig, sizeof(float4) * n);
-  if (rc == SPH_OK && velocity4) rc = sph_d2h(s, velocity4, s->d.velOrig, sizeof(float4) * n);
-  if (rc == SPH_OK && globalIds) rc = sph_d2h(s, globalIds, s->d.gid, sizeof(uint32_t) * n);
-  if (rc == SPH_OK && owned) rc = sph_d2h(s, owned, s->d.owned, sizeof(uint32_t) * n);
-  return rc;
 }

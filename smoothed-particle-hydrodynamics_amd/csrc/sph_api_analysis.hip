@@ -1,6 +1,8 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, particle rendering. All of them read the sorted state of the last completed step and write
-// nothing the step reads; what they share with the solver's own entry points (sph_api.hip) is in sph_api_internal.h.
+// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, particle
+// rendering. All of them read the sorted state of the last completed step and write nothing the step reads. The results that
+// outlive their call (mesh, labelling, selection, image) are SphDerived records: dropped first, stamped on success, checked by
+// their readers. What the translation units of the ABI share is in sph_api_internal.h.
 #include <string.h>
 
 #include <algorithm>
@@ -44,22 +46,14 @@ int sph_fill_selector(SphSelector* sel, const float* region6, uint32_t typeMask,
 }
 
 int sph_labels_current(sph_solver* s, const char* what, const int32_t** labels) {
-  if (!s->ccValid) { sph_set_error("%s: no labelling has been made (sph_label_components)", what); return SPH_ERR_ORDER; }
-  if (s->ccEpoch != s->stateEpoch || s->ccN != s->d.N) {
-    sph_set_error("%s: the solver's state has changed since the labelling", what);
-    return SPH_ERR_ORDER;
-  }
-  *labels = sphk_components_labels(s->ccBuf.p, s->ccN);
-  return SPH_OK;
+  const int rc = sph_derived_check(s, s->cc, what, "no labelling has been made (sph_label_components)",
+                                   "the solver's state has changed since the labelling");
+  if (rc == SPH_OK) *labels = sphk_components_labels(s->ccBuf.p, s->cc.N);
+  return rc;
 }
 
 int sph_selection_current(sph_solver* s, const char* what) {
-  if (!s->selValid) { sph_set_error("%s: no selection has been made", what); return SPH_ERR_ORDER; }
-  if (s->selEpoch != s->stateEpoch || s->selN != s->d.N) {
-    sph_set_error("%s: the solver's state has changed since the selection", what);
-    return SPH_ERR_ORDER;
-  }
-  return SPH_OK;
+  return sph_derived_check(s, s->sel, what, "no selection has been made", "the solver's state has changed since the selection");
 }
 
 // device buffer b grown to at least `bytes` (the old one is freed once the stream has finished with it)
@@ -150,7 +144,7 @@ static size_t surf_bytes_align(size_t b) { return (b + 255) & ~(size_t)255; }  /
 extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const float spacing[3], const int32_t dims[3],
                                    uint32_t typeMask, int32_t field, float iso, int64_t counts[2]) {
   ENTER(s);
-  s->meshValid = false;  // a failed call leaves no mesh behind
+  sph_derived_drop(s->mesh);
   s->meshCounts[0] = s->meshCounts[1] = 0;
   if (counts) counts[0] = counts[1] = 0;
   if (!origin || !spacing || !dims || !counts) { sph_set_error("sph_extract_surface: null pointer"); return SPH_ERR_INVALID; }
@@ -184,10 +178,9 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
   if (rc != SPH_OK) return rc;
   s->meshCounts[0] = (int64_t)totals[0];
   s->meshCounts[1] = (int64_t)totals[1];
-  s->meshValid = true;
   s->meshTypeMask = typeMask;
   s->meshField = field;
-  s->meshEpoch = s->stateEpoch;
+  sph_derived_stamp(s, s->mesh);
   counts[0] = s->meshCounts[0];
   counts[1] = s->meshCounts[1];
   return SPH_OK;
@@ -195,9 +188,9 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
 
 extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangles) {
   ENTER(s);
-  if (!s->meshValid) { sph_set_error("sph_read_surface: no surface has been extracted"); return SPH_ERR_ORDER; }
+  int rc = sph_derived_check(s, s->mesh, "sph_read_surface", "no surface has been extracted", nullptr);
+  if (rc != SPH_OK) return rc;
   const size_t vBytes = sizeof(float) * 3 * (size_t)s->meshCounts[0];
-  int rc = SPH_OK;
   if (vertices && vBytes) rc = sph_d2h(s, vertices, s->meshBuf.p, vBytes);
   if (rc != SPH_OK) return rc;
   const size_t tBytes = sizeof(int32_t) * 3 * (size_t)s->meshCounts[1];
@@ -242,15 +235,13 @@ extern "C" int sph_sample_gradient_grid(sph_solver* s, const float origin[3], co
 // Normals of the mesh in meshBuf, computed from its vertices where they lie; runs of vertices through the sampling scratch.
 extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
   ENTER(s);
-  if (!s->meshValid) { sph_set_error("sph_surface_normals: no surface has been extracted"); return SPH_ERR_ORDER; }
-  if (s->meshEpoch != s->stateEpoch) {
-    sph_set_error("sph_surface_normals: the solver's state has changed since the surface was extracted");
-    return SPH_ERR_ORDER;
-  }
+  int rc = sph_derived_check(s, s->mesh, "sph_surface_normals", "no surface has been extracted",
+                             "the solver's state has changed since the surface was extracted");
+  if (rc != SPH_OK) return rc;
   const int64_t V = s->meshCounts[0];
   if (V > 0 && !normals) { sph_set_error("sph_surface_normals: null pointer"); return SPH_ERR_INVALID; }
   SampleArgs a;
-  int rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &a);
+  rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &a);
   if (rc != SPH_OK || V == 0) return rc;
   const size_t rec = sizeof(float) * 3;
   const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
@@ -329,7 +320,7 @@ extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, i
 // lives in ccBuf / ccTable until the next one; the per-component records reuse the diagnostics tree with the labels as selection.
 extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t typeMask, int64_t counts[2]) {
   ENTER(s);
-  s->ccValid = false;  // a failed call leaves no labelling behind
+  sph_derived_drop(s->cc);
   s->ccCounts[0] = s->ccCounts[1] = 0;
   if (counts) counts[0] = counts[1] = 0;
   if (!counts) { sph_set_error("sph_label_components: null pointer"); return SPH_ERR_INVALID; }
@@ -360,9 +351,7 @@ extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t ty
   if (rc != SPH_OK) return rc;
   s->ccCounts[0] = (int64_t)totals[0];
   s->ccCounts[1] = (int64_t)C;
-  s->ccN = s->d.N;
-  s->ccEpoch = s->stateEpoch;
-  s->ccValid = true;
+  sph_derived_stamp(s, s->cc);
   counts[0] = s->ccCounts[0];
   counts[1] = s->ccCounts[1];
   return SPH_OK;
@@ -370,9 +359,9 @@ extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t ty
 
 extern "C" int sph_read_components(sph_solver* s, int32_t* labels, int32_t* rootCount, float* bbox) {
   ENTER(s);
-  if (!s->ccValid) { sph_set_error("sph_read_components: no labelling has been made"); return SPH_ERR_ORDER; }
-  int rc = SPH_OK;
-  if (labels && s->ccN > 0) rc = sph_d2h(s, labels, sphk_components_labels(s->ccBuf.p, s->ccN), sizeof(int32_t) * (size_t)s->ccN);
+  int rc = sph_derived_check(s, s->cc, "sph_read_components", "no labelling has been made", nullptr);
+  if (rc != SPH_OK) return rc;
+  if (labels && s->cc.N > 0) rc = sph_d2h(s, labels, sphk_components_labels(s->ccBuf.p, s->cc.N), sizeof(int32_t) * (size_t)s->cc.N);
   if (rc != SPH_OK) return rc;
   const size_t C = (size_t)s->ccCounts[1];
   if ((rootCount || bbox) && C > 0) {
@@ -408,7 +397,7 @@ extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* component
 
 // ---------------------------------------------------------------------------------------------- particle selection
 // Which particles, not what about them (sph_select.hip): a counting pass sizes the list, the list is written in ascending
-// sorted index, and the records are gathered from the live state when they are asked for (the meshEpoch / ccEpoch pattern).
+// sorted index, and the records are gathered from the live state when they are asked for (an SphDerived record, like the mesh and the labelling).
 static int select_check(sph_solver* s, uint32_t typeMask, const char* what, float* ss2) {
   SampleArgs a;
   const int rc = sample_check(s, typeMask, what, &a);
@@ -442,7 +431,7 @@ extern "C" int sph_particle_measure(sph_solver* s, float* out) {
 extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_t typeMask, const sph_select_term* terms,
                                     int32_t termCount, int32_t component, int64_t* count) {
   ENTER(s);
-  s->selValid = false;  // a failed call leaves no selection behind
+  sph_derived_drop(s->sel);
   s->selCount = 0;
   if (count) *count = 0;
   if (!count) { sph_set_error("sph_select_particles: null count"); return SPH_ERR_INVALID; }
@@ -492,9 +481,7 @@ extern "C" int sph_select_particles(sph_solver* s, const float* region6, uint32_
   rc = sph_check_finite_state(s);  // (synchronises the stream)
   if (rc != SPH_OK) return rc;
   s->selCount = (int64_t)totals[0];
-  s->selN = s->d.N;
-  s->selEpoch = s->stateEpoch;
-  s->selValid = true;
+  sph_derived_stamp(s, s->sel);
   *count = s->selCount;
   return SPH_OK;
 }
@@ -719,7 +706,7 @@ static bool render_view_ok(const sph_render_view& v) {
 extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, const float* region6, uint32_t typeMask,
                                     int32_t wantThickness, int64_t counts[2]) {
   ENTER(s);
-  s->renderValid = false;  // a failed render leaves no image behind
+  sph_derived_drop(s->render);
   if (counts) counts[0] = counts[1] = 0;
   if (!view || !counts) { sph_set_error("sph_render_particles: null pointer"); return SPH_ERR_INVALID; }
   int rc = sample_check(s, typeMask, "sph_render_particles");
@@ -752,8 +739,7 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
   if (rc != SPH_OK) return rc;
   s->renderW = view->width; s->renderH = view->height;
   s->renderThickness = thickness;
-  s->renderN = s->d.N;
-  s->renderValid = true;
+  sph_derived_stamp(s, s->render);
   counts[0] = (int64_t)head[0];
   counts[1] = (int64_t)head[1];
   return SPH_OK;
@@ -761,9 +747,10 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
 
 extern "C" int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba, uint32_t* thickness) {
   ENTER(s);
-  if (!s->renderValid) { sph_set_error("sph_read_render: nothing has been rendered"); return SPH_ERR_ORDER; }
+  const int rc = sph_derived_check(s, s->render, "sph_read_render", "nothing has been rendered", nullptr);
+  if (rc != SPH_OK) return rc;
   if (thickness && !s->renderThickness) { sph_set_error("sph_read_render: the last render accumulated no thickness"); return SPH_ERR_INVALID; }
-  const RenderLayout L = sphk_render_layout(s->renderW, s->renderH, s->renderThickness, s->renderN);
+  const RenderLayout L = sphk_render_layout(s->renderW, s->renderH, s->renderThickness, s->render.N);
   const size_t words = sizeof(uint32_t) * (size_t)s->renderW * (size_t)s->renderH;
   const char* base = (const char*)s->renderBuf.p;
   // enqueued together, waited for once

@@ -11,7 +11,7 @@
 // ---------------------------------------------------------------------------------------------- particle editing
 // Adding and removing particles between steps (sph_edit.hip). The calls act on the current state in original-id
 // order (posOrig, velOrig), not on the sorted state the analysis calls above read; one that changes the set invalidates that sorted
-// state (progress = 0, a new stateEpoch), which is what frees the sorted arrays to stage the compaction. Blocking, no stage timing.
+// state (progress = 0, sph_state_changes), which is what frees the sorted arrays to stage the compaction. Blocking, no stage timing.
 static int edit_check(sph_solver* s, const char* what) {
   if (s->hasSlab) { sph_set_error("%s: a slab solver is not supported", what); return SPH_ERR_INVALID; }
   return SPH_OK;
@@ -20,17 +20,14 @@ static int edit_check(sph_solver* s, const char* what) {
 // what every successful edit that changes the set does
 static void edit_commit(sph_solver* s, int newN) {
   s->d.N = newN;
-  s->stateEpoch++;
+  sph_state_changes(s);
   s->progress = 0;
 }
 
-// sph_create's fold of one particle into the liquid signature (see sph_slab_liquid_signature)
-static void edit_fold_signature(uint32_t& sig, const float* p4, const float* v4) {
-  if ((int)p4[3] == SPH_BOUNDARY_PARTICLE || sig == 0xffffffffu) return;
-  uint32_t tb, wb;
-  memcpy(&tb, &p4[3], 4); memcpy(&wb, &v4[3], 4);
-  if (wb != 0u || tb == 0u || tb == 0xffffffffu || (sig != 0u && sig != tb)) sig = 0xffffffffu;
-  else sig = tb;
+// the id map of a removal of a set of N particles is current from now on (identity: nothing was marked, nothing moved)
+static void edit_stamp_map(sph_solver* s, int N, bool identity) {
+  sph_derived_stamp(s, s->map);
+  s->mapIdentity = identity; s->mapLength = N;
 }
 
 // The marks are in editBuf: count them and, unless countOnly, compact the state. *removed receives the number of marked particles.
@@ -49,7 +46,7 @@ static int edit_remove_marked(sph_solver* s, const char* what, bool countOnly, i
   if (countOnly) { *removed = N - kept; return SPH_OK; }
   if (kept == N) {  // nothing marked: the solver, its analysis state and its epoch stay as they are; the map is the identity
     *removed = 0;
-    s->mapValid = true; s->mapIdentity = true; s->mapN = N; s->mapEpoch = s->stateEpoch;
+    edit_stamp_map(s, N, true);
     return SPH_OK;
   }
   if (t[2] != 0xffffffffu) {
@@ -68,7 +65,7 @@ static int edit_remove_marked(sph_solver* s, const char* what, bool countOnly, i
   std::swap(s->d.posOrig, s->d.sortedPos);
   std::swap(s->d.velOrig, s->d.sortedVel);
   edit_commit(s, kept);
-  s->mapValid = true; s->mapIdentity = false; s->mapN = N; s->mapEpoch = s->stateEpoch;
+  edit_stamp_map(s, N, false);
   *removed = N - kept;
   return SPH_OK;
 }
@@ -133,26 +130,20 @@ extern "C" int sph_remove_ids(sph_solver* s, const uint32_t* origIds, int64_t co
 extern "C" int sph_read_edit_map(sph_solver* s, int32_t* newIdOfOld) {
   ENTER(s);
   if (!newIdOfOld) { sph_set_error("sph_read_edit_map: null pointer"); return SPH_ERR_INVALID; }
-  if (!s->mapValid) { sph_set_error("sph_read_edit_map: no removal has been made"); return SPH_ERR_ORDER; }
-  if (s->mapEpoch != s->stateEpoch) {
-    sph_set_error("sph_read_edit_map: a stage, step or edit has run since the removal");
-    return SPH_ERR_ORDER;
-  }
+  const int rc = sph_derived_check(s, s->map, "sph_read_edit_map", "no removal has been made", "a stage, step or edit has run since the removal");
+  if (rc != SPH_OK) return rc;
   if (s->mapIdentity) {
-    for (int o = 0; o < s->mapN; o++) newIdOfOld[o] = o;
+    for (int o = 0; o < s->mapLength; o++) newIdOfOld[o] = o;
     return SPH_OK;
   }
-  return sph_d2h(s, newIdOfOld, s->d.backIndex, sizeof(int32_t) * (size_t)s->mapN);
+  return sph_d2h(s, newIdOfOld, s->d.backIndex, sizeof(int32_t) * (size_t)s->mapLength);
 }
 
-// sph_create's validation of one particle to be added; k: its index in the call's list
+// one particle to be added: sph_create's test of its position, and its type; k: its index in the call's list
 static int edit_validate(const sph_solver* s, const char* what, int k, const float* p4) {
-  const sph_config& c = s->cfg;
-  const float x = p4[0], y = p4[1], z = p4[2], w = p4[3];
-  const bool finite = std::isfinite(x) && std::isfinite(y) && std::isfinite(z);
-  const bool inside = x >= c.xmin && x <= c.xmax && y >= c.ymin && y <= c.ymax && z >= c.zmin && z <= c.zmax;
-  if (!finite || (c.cellIdMask == 0xffffffffu && !inside)) {
-    sph_set_error("%s: particle %d at (%g, %g, %g) is %s", what, k, x, y, z, finite ? "outside the box (wide cell ids need in-box input)" : "not finite");
+  const float w = p4[3];
+  if (const char* fault = sph_position_fault(s->cfg, p4)) {
+    sph_set_error("%s: particle %d at (%g, %g, %g) is %s", what, k, p4[0], p4[1], p4[2], fault);
     return SPH_ERR_INVALID;
   }
   if (!(w >= 1.f && w < 4.f) || ((int)w != SPH_LIQUID_PARTICLE && (int)w != SPH_BOUNDARY_PARTICLE)) {
@@ -177,7 +168,7 @@ extern "C" int sph_add_particles(sph_solver* s, const float* position4, const fl
   for (int k = 0; k < count; k++) {
     rc = edit_validate(s, "sph_add_particles", k, position4 + 4 * (size_t)k);
     if (rc != SPH_OK) return rc;
-    edit_fold_signature(sig, position4 + 4 * (size_t)k, velocity4 + 4 * (size_t)k);
+    sph_fold_liquid_signature(sig, position4 + 4 * (size_t)k, velocity4 + 4 * (size_t)k);
   }
   rc = sph_guard_position_write(s);
   if (rc != SPH_OK) return rc;
@@ -236,7 +227,7 @@ extern "C" int sph_emit_lattice(sph_solver* s, const float origin[3], const floa
     return SPH_ERR_INVALID;
   }
   const float p4[4] = {0.f, 0.f, 0.f, typeValue}, v4[4] = {velocity[0], velocity[1], velocity[2], 0.f};
-  edit_fold_signature(s->liquidSig, p4, v4);
+  sph_fold_liquid_signature(s->liquidSig, p4, v4);
   edit_commit(s, N + (int)count);
   *added = count;
   return SPH_OK;

@@ -1,6 +1,13 @@
-// What the translation units of the C ABI share (sph_api_edit.hip: particle editing; sph_api.hip: solver lifetime, stages, step, read-back, slab;
-// sph_api_analysis.hip: sampling, surfaces, gradients, diagnostics, components, selection): the order contract and the entry checks.
+// What the translation units of the C ABI share (sph_api.hip: errors, timing, solver lifetime, stages, the fused step; sph_api_read.hip:
+// read-back and reference-layout export; sph_api_slab.hip: the slab protocol; sph_api_analysis.hip: sampling, surfaces, gradients,
+// diagnostics, components, selection, rendering; sph_api_edit.hip: particle editing): the order contract and the entry checks,
+// the one rule for "the state has changed" and for results derived from it, and the per-particle input checks of sph_create
+// and the adding calls.
 #pragma once
+#include <string.h>
+
+#include <cmath>
+
 #include "sph_common.h"
 
 // stage progress bits for the order contract of simulationStep()
@@ -17,9 +24,50 @@ enum { P_HASH = 1, P_SORT = 2, P_SORTPOST = 4, P_INDEXX = 8, P_INDEXPOST = 16, P
     }                                                                                    \
   } while (0)
 
+// ---- the state and what is derived from it
+// The sorted state or the particle set is about to change: every stage, step, slab call and edit says so here, and nowhere else.
+static inline void sph_state_changes(sph_solver* s) { s->stateEpoch++; }
+// r is current from now on / there is no r (a producer drops its result first, so a failed call leaves none behind)
+static inline void sph_derived_stamp(const sph_solver* s, SphDerived& r) { r.valid = true; r.N = s->d.N; r.epoch = s->stateEpoch; }
+static inline void sph_derived_drop(SphDerived& r) { r.valid = false; }
+// SPH_ERR_ORDER with "<what>: <none>" unless r exists, and with "<what>: <stale>" unless it was made on the current state;
+// stale == nullptr: r is self-contained by contract and only has to exist
+static inline int sph_derived_check(const sph_solver* s, const SphDerived& r, const char* what, const char* none, const char* stale) {
+  if (!r.valid) { sph_set_error("%s: %s", what, none); return SPH_ERR_ORDER; }
+  if (stale && (r.epoch != s->stateEpoch || r.N != s->d.N)) { sph_set_error("%s: %s", what, stale); return SPH_ERR_ORDER; }
+  return SPH_OK;
+}
+
+// ---- one particle of sph_create's or an adding call's input
+// folded into the liquid signature (see sph_slab_liquid_signature): the common position.w bits of the non-boundary particles
+// with velocity.w == +0; 0 = none seen yet, 0xffffffff = not uniform
+static inline void sph_fold_liquid_signature(uint32_t& sig, const float* p4, const float* v4) {
+  if ((int)p4[3] == SPH_BOUNDARY_PARTICLE || sig == 0xffffffffu) return;
+  uint32_t tb, wb;
+  memcpy(&tb, &p4[3], 4); memcpy(&wb, &v4[3], 4);
+  if (wb != 0u || tb == 0u || tb == 0xffffffffu || (sig != 0u && sig != tb)) sig = 0xffffffffu;
+  else sig = tb;
+}
+// nullptr if the position is finite and, with wide cell ids, inside the box; otherwise what is wrong with it, for the caller's message
+static inline const char* sph_position_fault(const sph_config& c, const float* p4) {
+  const float x = p4[0], y = p4[1], z = p4[2];
+  if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) return "not finite";
+  const bool inside = x >= c.xmin && x <= c.xmax && y >= c.ymin && y <= c.ymax && z >= c.zmin && z <= c.zmax;
+  return c.cellIdMask == 0xffffffffu && !inside ? "outside the box (wide cell ids need in-box input)" : nullptr;
+}
+
 // (bodies in sph_api.hip)
+// The launches of one fused step on s->stream. tail (slab mode, the overlapped step of sph_slab_step_begin only): where the halo
+// messages go, packed as soon as the owned layers next to the cuts are integrated.
+struct StepTail {
+  uint32_t *frameDown, *frameUp;
+  int capRecords;
+};
+int enqueue_step(sph_solver* s, const StepTail* tail);
+// (bodies in sph_api_read.hip)
 int sph_d2h(sph_solver* s, void* dst, const void* src, size_t bytes);  // blocking copy to the host on s->stream
 int sph_check_finite_state(sph_solver* s);                             // synchronises the stream; SPH_ERR_INVALID once the state has blown up
+// (body in sph_api_slab.hip)
 int sph_slab_finish(sph_solver* s, int32_t counts[4]);
 // (bodies in sph_api_analysis.hip)
 int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes);  // device buffer b grown to at least `bytes`

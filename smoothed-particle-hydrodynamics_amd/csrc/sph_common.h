@@ -16,6 +16,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "sphmi.h"
 
 #define SPH_BLOCK 256
@@ -73,93 +75,114 @@ struct SphDev {  // what the kernels see; passed by value
   uint32_t* dbg;  // SPH_DBG_WORDS diagnostic counters (neighbour-search fallbacks etc.), zeroed by sph_reset_stage_times
 };
 
-struct SphScratch { void* p; size_t bytes; };  // a device buffer that only grows
+// A device buffer that only grows (sph_grow_scratch) and frees itself with the solver that holds it.
+struct SphScratch {
+  void* p = nullptr;
+  size_t bytes = 0;
+  SphScratch() = default;
+  SphScratch(const SphScratch&) = delete;
+  SphScratch& operator=(const SphScratch&) = delete;
+  ~SphScratch() { if (p) hipFree(p); }
+};
+
+// A result derived from the solver's state that a later call reads (a mesh, a labelling, a selection, an id map, an image): whether
+// one exists, and the particle count and stateEpoch it was made at. Stamped, dropped and checked by sph_derived_stamp /
+// sph_derived_drop / sph_derived_check (sph_api_internal.h) only.
+struct SphDerived {
+  bool valid = false;
+  int N = 0;
+  uint64_t epoch = 0;
+};
 
 struct sph_solver {
-  sph_config cfg;
-  SphDev d;
-  hipStream_t stream;
-  bool ownStream;
-  int sortBits;              // significant bits of the sort key
-  int capacity;              // particles the buffers are sized for (>= d.N)
-  int capTiles;              // ceil(capacity/64)
-  sph_slab slab; bool hasSlab;
-  uint32_t* slabCounts;      // device, SPH_SLAB_COUNT_WORDS words: [0..2] kept / down / up of sph_slab_pack, [3] unsorted-message flag,
+  sph_config cfg = {};
+  SphDev d = {};
+  // every permanent device allocation (dev_alloc, sph_api.hip): the destructor frees these, whichever SphDev member points at
+  // them by then (an edit swaps posOrig / sortedPos and velOrig / sortedVel)
+  std::vector<void*> allocs;
+  hipStream_t stream = nullptr;
+  bool ownStream = false;
+  int sortBits = 0;              // significant bits of the sort key
+  int capacity = 0;              // particles the buffers are sized for (>= d.N)
+  int capTiles = 0;              // ceil(capacity/64)
+  sph_slab slab = {}; bool hasSlab = false;
+  uint32_t* slabCounts = nullptr;  // device, SPH_SLAB_COUNT_WORDS words: [0..2] kept / down / up of sph_slab_pack, [3] unsorted-message flag,
                              // [4..6] and [8..10] the same triples of the overlapped step's message / kept passes, [7] owned
                              // particles that moved more than a layer, [12..15] totals of sph_slab_rebuild_framed (kept, from
                              // below, from above, 1 = nothing merged)
-  uint32_t* slabHost;        // pinned host mirror of slabCounts (overlapped step)
-  hipEvent_t slabMsgEvent;   // recorded when the messages of the overlapped step are packed
-  bool slabStepPending;      // sph_slab_step_begin issued, rebuild not yet done
-  int slabCapRecords;        // frame capacity given to sph_slab_step_begin
-  int slabKept;              // host copy of the kept count of the last sph_slab_pack (-1: none pending)
-  int slabRecWords;          // words per message record: 9 (full) or 7 (compact); 0 = 9
-  uint32_t slabTypeBits;     // compact records: the type word every non-boundary particle carries
-  uint32_t liquidSig;        // from sph_create: common position.w bits of the non-boundary particles with velocity.w == +0,
+  uint32_t* slabHost = nullptr;        // pinned host mirror of slabCounts (overlapped step)
+  hipEvent_t slabMsgEvent = nullptr;   // recorded when the messages of the overlapped step are packed
+  bool slabStepPending = false;  // sph_slab_step_begin issued, rebuild not yet done
+  int slabCapRecords = 0;        // frame capacity given to sph_slab_step_begin
+  int slabKept = 0;              // host copy of the kept count of the last sph_slab_pack (-1: none pending)
+  int slabRecWords = 0;          // words per message record: 9 (full) or 7 (compact); 0 = 9
+  uint32_t slabTypeBits = 0;     // compact records: the type word every non-boundary particle carries
+  uint32_t liquidSig = 0;        // from sph_create: common position.w bits of the non-boundary particles with velocity.w == +0,
                              // 0 = there are none, 0xffffffff = not uniform
-  bool slabRebuildPending;   // sph_slab_rebuild_framed issued: the particle count is still on its way to the host
-  hipEvent_t slabRebuildEvent;
-  int slabCapDown, slabCapUp;  // records the frames given to sph_slab_rebuild_framed had room for
+  bool slabRebuildPending = false;  // sph_slab_rebuild_framed issued: the particle count is still on its way to the host
+  hipEvent_t slabRebuildEvent = nullptr;
+  int slabCapDown = 0, slabCapUp = 0;  // records the frames given to sph_slab_rebuild_framed had room for
   // radix-sort workspace
-  uint32_t* blockHist;       // [SPH_SORT_MAX_DIGITS][maxSortBlocks] block histograms + SPH_SORT_MAX_DIGITS digit totals
-  int maxSortBlocks;
+  uint32_t* blockHist = nullptr;  // [SPH_SORT_MAX_DIGITS][maxSortBlocks] block histograms + SPH_SORT_MAX_DIGITS digit totals
+  int maxSortBlocks = 0;
   // stage progress for SPH_ERR_ORDER checks
-  int progress;
+  int progress = 0;
   // stage timing
-  bool timing;
-  hipEvent_t evStart[SPH_ST_COUNT], evStop[SPH_ST_COUNT];
+  bool timing = false;
   struct Pending { int stage; hipEvent_t a, b; };
-  Pending* pending; int numPending, capPending;
-  double stageMs[SPH_ST_COUNT];
-  int64_t stageLaunches[SPH_ST_COUNT];
-  // host staging for exports
-  void* hostScratch; size_t hostScratchBytes;
+  std::vector<Pending> pending;  // event pairs recorded and not yet read (resolve_pending, sph_destroy)
+  double stageMs[SPH_ST_COUNT] = {};
+  int64_t stageLaunches[SPH_ST_COUNT] = {};
   // asynchronous position read-back (sph_read_position_async): a copy stream of its own, ordered against s->stream by events
-  hipStream_t copyStream;
-  hipEvent_t evReadReady, evCopyDone;  // positions final on s->stream / copy landed on the host
-  bool copyPending;                    // a copy was issued and sph_read_position_wait has not run since
-  float* copyUserDst;                  // where the caller wants the data
-  void* copyStage; size_t copyStageBytes;  // pinned staging, only for destinations that cannot be page-locked in place
-  bool copyViaStage;
-  size_t copyBytes;                    // bytes of the read-back in flight (the particle count may change before it is waited for)
+  hipStream_t copyStream = nullptr;
+  hipEvent_t evReadReady = nullptr, evCopyDone = nullptr;  // positions final on s->stream / copy landed on the host
+  bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
+  float* copyUserDst = nullptr;        // where the caller wants the data
+  void* copyStage = nullptr; size_t copyStageBytes = 0;  // pinned staging, only for destinations that cannot be page-locked in place
+  bool copyViaStage = false;
+  size_t copyBytes = 0;                // bytes of the read-back in flight (the particle count may change before it is waited for)
   struct HostReg { void* p; size_t bytes; };
-  HostReg hostRegs[8]; int numHostRegs;    // caller buffers page-locked in place by hipHostRegister (released by sph_destroy)
-  uint32_t* pinnedFlags;               // pinned: [0] copy of dbg[6] taken with the last asynchronous read-back
-  uint64_t blownUp;                    // sticky: non-finite coordinates seen so far (sph_check_finite_state)
+  HostReg hostRegs[8] = {}; int numHostRegs = 0;  // caller buffers page-locked in place by hipHostRegister (released with the solver)
+  uint32_t* pinnedFlags = nullptr;     // pinned: [0] copy of dbg[6] taken with the last asynchronous read-back
+  uint64_t blownUp = 0;                // sticky: non-finite coordinates seen so far (sph_check_finite_state)
+  // bumped by sph_state_changes (sph_api_internal.h), which every call that rewrites the sorted state or the particle set makes
+  // (stages, steps, slab calls, edits): a derived result is current while its epoch still equals this
+  uint64_t stateEpoch = 0;
   // device scratch of the analysis calls (sph_api_analysis.hip), each grown on demand and kept: query points and records of
   // field / gradient sampling; the diagnostics tree's partials and the histogram bins; the isosurface lattice; the last mesh
   SphScratch sampleBuf, diagBuf, surfBuf, meshBuf;
-  int64_t meshCounts[2]; bool meshValid;  // vertices, triangles of the last successful extraction
-  uint32_t meshTypeMask; int meshField;   // ... and its arguments (sph_surface_normals)
-  uint64_t meshEpoch;                     // stateEpoch when it was extracted
-  // bumped by every call that rewrites the sorted state sampling reads (stages, steps, slab calls): sph_surface_normals is
-  // only allowed while it still equals meshEpoch
-  uint64_t stateEpoch;
+  SphDerived mesh;                            // the last successful extraction (sph_surface_normals needs it current)
+  int64_t meshCounts[2] = {};                 // ... its vertices, triangles
+  uint32_t meshTypeMask = 0; int meshField = 0;  // ... and its arguments (sph_surface_normals)
   // connected components (sph_label_components / sph_read_components): the labelling's scratch and table, grown on demand
   SphScratch ccBuf, ccTable;
-  int64_t ccCounts[2]; bool ccValid;  // selected particles, components of the last successful labelling
-  int ccN;                            // ... the particle count it was made for
-  uint64_t ccEpoch;                   // ... and stateEpoch at that time (sph_component_diagnostics)
+  SphDerived cc;                      // the last successful labelling (sph_component_diagnostics needs it current)
+  int64_t ccCounts[2] = {};           // ... its selected particles, components
   // particle selection (sph_select_particles / sph_read_selection): the scan's scratch (mask, block counts) and the list of
   // selected sorted indices, grown on demand; the records go through sampleBuf in pieces
   SphScratch selBuf, selList;
-  int64_t selCount; bool selValid;    // length of the last successful selection
-  int selN;                           // ... the particle count it was made for
-  uint64_t selEpoch;                  // ... and stateEpoch at that time (sph_read_selection gathers from the live state)
+  SphDerived sel;                     // the last successful selection (sph_read_selection gathers from the live state)
+  int64_t selCount = 0;               // ... its length
   // elastic-matter diagnostics (sph_elastic_measure / sph_muscle_diagnostics / sph_membrane_measure): records on their way to
   // the host and the group tree's partials, grown on demand
   SphScratch elasticBuf;
   // particle rendering (sph_render_particles / sph_read_render): keys, thickness sums, the resolved images and the queue of large
-  // splats in one buffer, grown on demand; the images are self-contained, so there is no epoch
+  // splats in one buffer, grown on demand; the images are self-contained, so no reader asks whether they are current
   SphScratch renderBuf;
-  bool renderValid; bool renderThickness;  // a successful render exists / it accumulated thickness
-  int renderW, renderH, renderN;           // ... its size and the particle count its buffer was laid out for
+  SphDerived render;                  // the last successful render; N: the particle count its buffer was laid out for
+  bool renderThickness = false;       // ... it accumulated thickness
+  int renderW = 0, renderH = 0;       // ... its size
   // particle editing (sph_remove_* / sph_add_particles / sph_emit_lattice): the compaction's scan scratch, grown on demand. The
   // id map of the last removal lies in backIndex (dead until the next step's sort), or is the identity (an empty removal).
   SphScratch editBuf;
-  bool mapValid, mapIdentity;
-  int mapN;                                // the particle count before that removal
-  uint64_t mapEpoch;                       // stateEpoch right after it (sph_read_edit_map)
+  SphDerived map;                     // stamped right after that removal (sph_read_edit_map)
+  bool mapIdentity = false;
+  int mapLength = 0;                  // the particle count before that removal: the map's length
+
+  sph_solver() = default;
+  // Frees everything the solver owns (sph_api.hip): the recorded device allocations, then pinned buffers, host registrations,
+  // events and streams; the scratch buffers free themselves after that. The caller has set the device and drained the streams.
+  ~sph_solver();
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for

@@ -1,6 +1,7 @@
 """Scene builders shared by the tests, the golden generator and bench.py (inputs only — no solver code)."""
 import hashlib
 import os
+import re
 import sys
 
 import numpy as np
@@ -207,6 +208,18 @@ HIP_STAGE_METHOD = {
     "integrate": "_run_pcisph_integrate", "clearMembraneBuffers": "_run_clearMembraneBuffers",
     "computeInteractionWithMembranes": "_run_computeInteractionWithMembranes",
     "computeInteractionWithMembranes_finalize": "_run_computeInteractionWithMembranes_finalize"}
+
+
+def staged_step(hip, it):
+    """One step through the 18 stage entry points in simulationStep's order."""
+    for st in STAGE_SEQUENCE:
+        m = getattr(hip, HIP_STAGE_METHOD[st])
+        m(it) if st == "integrate" else m()
+
+
+def error_status(exc):
+    """The library's status code in the message of the RuntimeError that pytest.raises caught."""
+    return int(re.search(r"\(status (-?\d+)\)", str(exc.value)).group(1))
 
 
 def canonical(get, N):

@@ -14,6 +14,7 @@ import edit_ref as er
 import scenes
 import sphmi
 from sphmi import slab as S
+from scenes import error_status as _status, staged_step
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +29,8 @@ def _scene(name):
     return scenes.worm_scene() if name == "worm" else scenes.SCENES[name]()
 
 
-def _status(exc):
-    return int(re.search(r"\(status (-?\d+)\)", str(exc.value)).group(1))
-
-
 def _hip(sc, cfg, pos, vel):
     return sphmi.owHIPSolver(cfg, pos, vel, sc["elastic"], sc["membranes"], sc["particle_membranes"])
-
-
-def staged_step(hip, it):
-    for st in scenes.STAGE_SEQUENCE:
-        m = getattr(hip, scenes.HIP_STAGE_METHOD[st])
-        m(it) if st == "integrate" else m()
 
 
 def read_state(hip):

@@ -15,6 +15,7 @@ import scenes
 import sphmi
 from sphmi import frames
 from sphmi import slab as S
+from scenes import staged_step
 
 pytestmark = pytest.mark.gpu
 
@@ -49,12 +50,6 @@ def _signal(name, cfg, it):
     s[0] = f32(0.25) * f32(it + 1)
     s[1] = f32(-1.0)
     return s
-
-
-def staged_step(hip, it):
-    for st in scenes.STAGE_SEQUENCE:
-        m = getattr(hip, scenes.HIP_STAGE_METHOD[st])
-        m(it) if st == "integrate" else m()
 
 
 def first_diff(got, want, view):

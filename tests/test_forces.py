@@ -15,6 +15,7 @@ import scenes
 import sphmi
 from sphmi import frames
 from sphmi import slab as S
+from scenes import staged_step
 
 pytestmark = pytest.mark.gpu
 
@@ -36,12 +37,6 @@ def _scene(name):
     if name == "worm":
         return scenes.worm_scene()
     return scenes.config1() if name == "config1" else scenes.SCENES[name]()
-
-
-def staged_step(hip, it):
-    for st in scenes.STAGE_SEQUENCE:
-        m = getattr(hip, scenes.HIP_STAGE_METHOD[st])
-        m(it) if st == "integrate" else m()
 
 
 def first_diff(got, want, view):

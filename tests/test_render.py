@@ -16,6 +16,7 @@ import scenes
 import sphmi
 from sphmi import frames
 from sphmi import slab as S
+from scenes import staged_step
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,6 @@ IMAGES = ("depth", "index", "orig_id", "rgba", "thickness")
 
 def _scene(name):
     return scenes.worm_scene() if name == "worm" else scenes.SCENES[name]()
-
-
-def staged_step(hip, it):
-    for st in scenes.STAGE_SEQUENCE:
-        m = getattr(hip, scenes.HIP_STAGE_METHOD[st])
-        m(it) if st == "integrate" else m()
 
 
 def view_cases(state, cfg, size):
