@@ -631,6 +631,69 @@ int sph_emit_lattice(sph_solver* s, const float origin[3], const float spacing[3
                      float typeValue /* position.w: 1.0f liquid */, int64_t* added);
 int sph_read_edit_map(sph_solver* s, int32_t* newIdOfOld /* host, the count BEFORE the last removal */);
 
+/* ---- Carried particle fields: paint, diffuse, measure a dye (no reference counterpart) -------------------------
+ * Up to SPH_FIELD_SLOTS scalar float fields per solver, one value per particle, stored in ORIGINAL-id order (the order of
+ * sph_read_position) and sized by the capacity given to sph_create. A step never reads or writes them; the edits carry them
+ * along; the calls below paint them, diffuse them along the neighbour rows and reduce them.
+ * STATE AND LIFETIME. A slot exists from sph_field_create to sph_field_release or sph_destroy. sph_field_create sets the N values
+ * from valuesN (NULL: all +0) and remembers `inflow`, the value new particles receive. Creating a slot that exists, or using one
+ * that does not, is SPH_ERR_ORDER; a slot outside 0..SPH_FIELD_SLOTS-1 is SPH_ERR_INVALID. Finite values only: a non-finite
+ * value, inflow or coefficient is SPH_ERR_INVALID, and so is a non-finite entry of a host array, with the first offender named
+ * and nothing written. No field call changes the solver's state: a mesh, a labelling, a selection, a render and an edit map stay
+ * valid across all of them. sph_field_read, sph_field_write, sph_field_set_region and sph_field_set_selection act on the CURRENT
+ * particle set, like the edits, and are legal at any time between steps, also right after an edit. sph_field_diffuse and
+ * sph_field_diagnostics read the sorted state of the last completed step: SPH_ERR_ORDER before one, and after an edit until the
+ * next step. sph_field_diffuse needs that step's neighbour and density stages, sph_field_diagnostics what sph_diagnostics needs.
+ * PAINTING. sph_field_set_region marks particle o by the rule of sph_remove_region, word for word ((int)position[o].w is 1, 2 or
+ * 3 with that bit set in typeMask; the float position in the half-open box; no cell-key condition; region6 == NULL is
+ * "everywhere"), sets the marked particles to `value` and writes their number to *painted. sph_field_set_selection sets
+ * origId[r] of every entry of the live selection of sph_select_particles, under the epoch rule of sph_read_selection, and
+ * writes the selection's length.
+ * EDITS CARRY THE FIELDS. A successful removal compacts every existing slot with the same old-to-new map as position and
+ * velocity (sph_read_edit_map). A successful sph_add_particles or sph_emit_lattice gives the new ids the slot's inflow. A failed
+ * or counting edit, and a removal of nothing, leave the fields untouched.
+ * DIFFUSION is the viscous sum of the step's kernel K7 with the scalar in place of a velocity component. P(x) holds when the type
+ * of sorted particle x is 1..3 with its bit in typeMask and its cell key is valid (as sph_diagnostics selects). row, dist, hs and
+ * del2W as in the force decomposition above; c_x is the value of the particle whose original id is particleIndex[x]. For sorted
+ * particle i with P(i), the slots k = 0..31 in ascending order, j = row(i)[k], rk = dist(i)[k]; a slot is USED when
+ * j != -1 && rk < hs && P(j). All arithmetic in float in the written order, no contraction, IEEE division; the sums start at +0,
+ * run in slot order, and a slot that is not used leaves them untouched:
+ *     S_i = sum ((c_j - c_i) * (hs - rk)) / rho_j          W_i = sum (hs - rk) / rho_j
+ *     sD_i = mass * (float)(del2W / (double)rho_i)         a_i = coefficient * sD_i
+ *     c_i' = c_i + a_i * S_i                               sigma = max over P(i) of a_i * W_i, float compares from +0
+ * A particle without P(i) keeps its value. `coefficient` is diffusivity x time in the units in which `viscosity` multiplies the
+ * same sum; it is >= 0 (< 0: SPH_ERR_INVALID), and so is substeps. The update is JACOBI: every c' of a substep is computed from
+ * the c of before that substep; it is repeated `substeps` times on the same rows and densities. *stability (may be NULL) receives
+ * sigma, the same for every substep; substeps == 0 only measures sigma and changes nothing. Two properties: for sigma <= 1 each
+ * new value is a convex combination of old ones (c_i' = (1 - a_i W_i) c_i + sum of non-negative weights times c_j), up to
+ * rounding, so the field keeps its bounds; and the sum of c over the participants is conserved, up to rounding, exactly when the
+ * used slots are symmetric (j used by i with the same distance whenever i is used by j; then the weight a_i (hs - rk) / rho_j is
+ * mass * del2W * coefficient * (hs - rk) / (rho_i rho_j) both ways). That holds unless a row was truncated at 32 entries.
+ * DIAGNOSTICS. sph_field_diagnostics: selection, region rules, count limit and errors exactly as sph_diagnostics. Per selected
+ * particle c is widened to double. Record, SPH_FIELD_DIAG_WORDS doubles per region:
+ *   0  n, the number of selected particles      1  sum c       2  sum c*c (the product in double)
+ *   3  min c     4  max c (float compares, canonicalised by + 0.0f; 0 when n = 0)
+ *   5  the number of selected particles with c != 0              6, 7  0
+ * The sums are reduce(a) of sph_diagnostics over all N terms in ascending sorted index, an unselected particle contributing +0.0.
+ * No floating-point atomics anywhere.
+ * Rules: blocking, on the solver's stream, not stages (no stage timing). SPH_ERR_INVALID for a slab solver, null pointers (only
+ * region6 and stability may be NULL), a typeMask of 0 or with bits outside 1..3, a NaN region bound, count outside
+ * 1..SPH_DIAG_MAX_REGIONS. Device memory: 4 bytes per slot and particle of capacity, one more such buffer once a removal has
+ * moved a field, and 16 bytes per particle for the diffusion's sorted records; grown on demand, freed by sph_field_release
+ * (the slot) and sph_destroy. */
+#define SPH_FIELD_SLOTS 4
+#define SPH_FIELD_DIAG_WORDS 8
+int sph_field_create(sph_solver* s, int32_t slot, const float* valuesN /* host, orig order, or NULL = all +0 */, float inflow);
+int sph_field_release(sph_solver* s, int32_t slot);
+int sph_field_write(sph_solver* s, int32_t slot, const float* valuesN /* host, N, orig order */);
+int sph_field_read(sph_solver* s, int32_t slot, float* outN /* host, N, orig order */);
+int sph_field_set_region(sph_solver* s, int32_t slot, const float* region6 /* or NULL */, uint32_t typeMask, float value,
+                         int64_t* painted);
+int sph_field_set_selection(sph_solver* s, int32_t slot, float value, int64_t* painted);
+int sph_field_diffuse(sph_solver* s, int32_t slot, float coefficient, int32_t substeps, uint32_t typeMask, float* stability);
+int sph_field_diagnostics(sph_solver* s, int32_t slot, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
+                          uint32_t typeMask, double* out /* host, count x 8 */);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

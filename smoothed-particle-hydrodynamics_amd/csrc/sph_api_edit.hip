@@ -61,6 +61,8 @@ static int edit_remove_marked(sph_solver* s, const char* what, bool countOnly, i
   if (rc != SPH_OK) return rc;
   // membDelta (orig-indexed): all zero again, as sph_create leaves it (the step clears it before it reads it anyway)
   if (s->d.membDelta) SPH_HIP(hipMemsetAsync(s->d.membDelta, 0, sizeof(float4) * (size_t)N, s->stream));
+  rc = sph_fields_follow_removal(s, N, (const int32_t*)s->d.backIndex);  // the carried fields move with position and velocity
+  if (rc != SPH_OK) return rc;
   SPH_HIP(hipStreamSynchronize(s->stream));
   std::swap(s->d.posOrig, s->d.sortedPos);
   std::swap(s->d.velOrig, s->d.sortedVel);
@@ -175,6 +177,8 @@ extern "C" int sph_add_particles(sph_solver* s, const float* position4, const fl
   SPH_HIP(hipMemcpyAsync(s->d.posOrig + N, position4, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, s->stream));
   SPH_HIP(hipMemcpyAsync(s->d.velOrig + N, velocity4, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, s->stream));
   if (s->d.membDelta) SPH_HIP(hipMemsetAsync(s->d.membDelta + N, 0, sizeof(float4) * (size_t)count, s->stream));
+  rc = sph_fields_follow_add(s, N, count);  // the new ids carry each field's inflow
+  if (rc != SPH_OK) return rc;
   SPH_HIP(hipStreamSynchronize(s->stream));
   s->liquidSig = sig;
   edit_commit(s, N + count);
@@ -217,6 +221,8 @@ extern "C" int sph_emit_lattice(sph_solver* s, const float origin[3], const floa
   rc = sphk_edit_emit(s, a, (int)count, s->editBuf.p, &dCounters);  // into the unused tail [N, N + count)
   if (rc != SPH_OK) return rc;
   if (s->d.membDelta) SPH_HIP(hipMemsetAsync(s->d.membDelta + N, 0, sizeof(float4) * (size_t)count, s->stream));
+  rc = sph_fields_follow_add(s, N, (int)count);  // into the fields' unused tail too: it only counts once the count is raised
+  if (rc != SPH_OK) return rc;
   uint32_t bad[2] = {0, 0};
   rc = sph_d2h(s, bad, dCounters, sizeof(bad));
   if (rc != SPH_OK) return rc;

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (sph_api.hip: errors, timing, solver lifetime, stages, the fused step; sph_api_read.hip:
 // read-back and reference-layout export; sph_api_slab.hip: the slab protocol; sph_api_analysis.hip: sampling, surfaces, gradients,
-// diagnostics, components, selection, rendering; sph_api_edit.hip: particle editing): the order contract and the entry checks,
+// diagnostics, components, selection, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields): the order contract and the entry checks,
 // the one rule for "the state has changed" and for results derived from it, and the per-particle input checks of sph_create
 // and the adding calls.
 #pragma once
@@ -77,6 +77,11 @@ int sph_fill_selector(SphSelector* sel, const float* region6 /* may be null */, 
 // SPH_ERR_ORDER unless a labelling / a selection exists and was made on the current state; *labels: the N labels (device)
 int sph_labels_current(sph_solver* s, const char* what, const int32_t** labels);
 int sph_selection_current(sph_solver* s, const char* what);
+
+// (bodies in sph_api_fields.hip) What an edit does to the carried fields, enqueued on s->stream next to the edit's own work; with
+// no slot in existence neither enqueues anything.
+int sph_fields_follow_removal(sph_solver* s, int oldN, const int32_t* map);  // every slot through the removal's old-to-new map
+int sph_fields_follow_add(sph_solver* s, int first, int count);              // ids first .. first + count get each slot's inflow
 
 // (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
 #define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)

@@ -178,6 +178,13 @@ struct sph_solver {
   SphDerived map;                     // stamped right after that removal (sph_read_edit_map)
   bool mapIdentity = false;
   int mapLength = 0;                  // the particle count before that removal: the map's length
+  // carried particle fields (sph_field_*, sph_fields.hip): one float per particle in ORIGINAL-id order, `capacity` floats per slot.
+  // A slot exists while fieldLive says so; its buffer is dropped by sph_field_release. fieldBuf: the diffusion's two sorted
+  // (c, rho) records per particle and its stability word; fieldStage: the buffer a removal compacts a slot into (then swapped
+  // with the slot's own)
+  SphScratch fieldSlot[SPH_FIELD_SLOTS], fieldBuf, fieldStage;
+  bool fieldLive[SPH_FIELD_SLOTS] = {};
+  float fieldInflow[SPH_FIELD_SLOTS] = {};  // what the ids an adding call creates receive
 
   sph_solver() = default;
   // Frees everything the solver owns (sph_api.hip): the recorded device allocations, then pinned buffers, host registrations,
@@ -392,6 +399,18 @@ int sphk_edit_count(sph_solver* s, int protectEnd, void* scratch, uint32_t** tot
 int sphk_edit_scatter(sph_solver* s, void* scratch, uint32_t total, float4* posOut, float4* velOut, int32_t* map);
 // lattice points into posOrig / velOrig [N, N + count); *counters = device words {points that fail validation, the lowest such k}
 int sphk_edit_emit(sph_solver* s, const EditLattice& a, int count, void* scratch, uint32_t** counters);
+// sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
+// values in original-id order (device). Read-only on every solver array.
+size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word
+// `substeps` Jacobi substeps of the diffusion contract on `field`; *sigma: one device word, the bits of the stability number
+int sphk_field_diffuse(sph_solver* s, float* field, float coefficient, int substeps, uint32_t typeMask, void* scratch, uint32_t** sigma);
+// field[o] = value for the particles sph_remove_region would mark; *count (one device word) += their number
+int sphk_field_paint_region(sph_solver* s, float* field, const SphSelector& a, float value, uint32_t* count);
+int sphk_field_paint_list(sph_solver* s, float* field, const int32_t* list, int n, float value);  // field[vals[list[r]]] = value
+int sphk_field_compact(sph_solver* s, const float* in, const int32_t* map, int nOld, float* out);  // out[map[o]] = in[o], map[o] >= 0
+int sphk_field_fill(sph_solver* s, float* field, int first, int n, float value);
+size_t sphk_field_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_FIELD_DIAG_WORDS records
+int sphk_field_diagnostics(sph_solver* s, const float* field, const DiagArgs& a, double* scratch, double** records);
 // sph_elastic_measure.hip (spring strain, muscle groups, membrane areas; read-only on every solver array)
 // per elastic particle, device pointers, any of the four may be null; *bad: one device word of error flags (ids out of range)
 int sphk_elastic_measure(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, float* records, float* connections, uint32_t* bad);

@@ -194,6 +194,36 @@ class owHIPSolver {
     return n;
   }
 
+  // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
+  // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
+  // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would
+  // remove, fieldSetSelection those of the current selection; fieldDiffuse runs `substeps` Jacobi substeps of K7's viscous sum
+  // with the scalar in place of a velocity component over the last step's neighbour rows and returns the stability number (<= 1:
+  // the field keeps its bounds); fieldDiagnostics writes SPH_FIELD_DIAG_WORDS doubles per region (n, sum, sum of squares, min,
+  // max, non-zero count) (include/sphmi.h, sph_field_*)
+  void fieldCreate(int slot, const float* valuesN = nullptr, float inflow = 0.f) { check(sph_field_create(s_, slot, valuesN, inflow), "fieldCreate"); }
+  void fieldRelease(int slot) { check(sph_field_release(s_, slot), "fieldRelease"); }
+  void fieldWrite(int slot, const float* valuesN) { check(sph_field_write(s_, slot, valuesN), "fieldWrite"); }
+  void fieldRead(int slot, float* outN) { check(sph_field_read(s_, slot, outN), "fieldRead"); }
+  int64_t fieldSetRegion(int slot, float value, const float* region6, unsigned int typeMask) {
+    int64_t painted = 0;
+    check(sph_field_set_region(s_, slot, region6, typeMask, value, &painted), "fieldSetRegion");
+    return painted;
+  }
+  int64_t fieldSetSelection(int slot, float value) {
+    int64_t painted = 0;
+    check(sph_field_set_selection(s_, slot, value, &painted), "fieldSetSelection");
+    return painted;
+  }
+  float fieldDiffuse(int slot, float coefficient, int substeps, unsigned int typeMask) {
+    float stability = 0.f;
+    check(sph_field_diffuse(s_, slot, coefficient, substeps, typeMask, &stability), "fieldDiffuse");
+    return stability;
+  }
+  void fieldDiagnostics(int slot, const float* regions6, int count, unsigned int typeMask, double* out) {
+    check(sph_field_diagnostics(s_, slot, regions6, count, typeMask, out), "fieldDiagnostics");
+  }
+
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }
   sph_solver* handle() { return s_; }

@@ -63,6 +63,13 @@
 //        gate that opens at step 200 is `--drain-types 3 --drain-region ... --drain-at 200`. The drain runs before the emitter.
 //        Each step with an edit prints `_edit: step S removed R added A particles N`. With these options the position read-back
 //        is the blocking one, and --out holds the final count of particles.
+//   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
+//        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
+//        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
+//        dyes only what the emitter adds). After every step the dye diffuses among the liquid by one substep of sph_field_diffuse
+//        with coefficient = D * timeStep (default D = 0: it is only carried), and after every K-th step one line is printed:
+//        `dye step=S n=N sum=... mean=... var=... min=... max=... stability=...` (S steps done; the liquid of the whole scene;
+//        %.17g; stability is sph_field_diffuse's number for that step's substep, <= 1: the dye keeps its bounds)
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -174,6 +181,7 @@ int main(int argc, char** argv) {
   int emitDims[3] = {0, 0, 0}, emitEvery = 1, emitUntil = -1;
   bool drainSeen = false, drainRegionSeen = false, drainTypesSeen = false; unsigned drainMask = 0; int drainEvery = 0, drainAt = -1;
   float drainRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+  bool dyeSeen = false, dyeRegionSeen = false, dyeEverySeen = false; float dyeRegion[6] = {0, 0, 0, 0, 0, 0}, dyeInflow = 0.f, dyeDiffusivity = 0.f; int dyeEvery = 0;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
     else if (!strcmp(argv[i], "--capacity") && i + 1 < argc) { capacity = atoi(argv[++i]); capSeen = true; }
@@ -197,6 +205,10 @@ int main(int argc, char** argv) {
         drainMask |= 1u << t;
       }
     }
+    else if (!strcmp(argv[i], "--dye-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) dyeRegion[k] = (float)atof(argv[++i]); dyeSeen = dyeRegionSeen = true; }
+    else if (!strcmp(argv[i], "--dye-inflow") && i + 1 < argc) { dyeInflow = (float)atof(argv[++i]); dyeSeen = true; }
+    else if (!strcmp(argv[i], "--dye-diffusivity") && i + 1 < argc) { dyeDiffusivity = (float)atof(argv[++i]); dyeSeen = true; }
+    else if (!strcmp(argv[i], "--dye-every") && i + 1 < argc) { dyeEvery = atoi(argv[++i]); dyeSeen = dyeEverySeen = true; }
     else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
     else if (!strcmp(argv[i], "--forces-every") && i + 1 < argc) { forEvery = atoi(argv[++i]); forSeen = true; }
@@ -333,6 +345,13 @@ int main(int argc, char** argv) {
   if (!drainMask) drainMask = 1u << SPH_LIQUID_PARTICLE;
   for (float b : drainRegion)
     if (std::isnan(b)) { fprintf(stderr, "--drain-region: a bound is not a number\n"); return 2; }
+  for (float b : dyeRegion)
+    if (std::isnan(b)) { fprintf(stderr, "--dye-region: a bound is not a number\n"); return 2; }
+  if (dyeSeen && (!std::isfinite(dyeInflow) || !std::isfinite(dyeDiffusivity) || dyeDiffusivity < 0.f || (dyeEverySeen && dyeEvery <= 0))) {
+    fprintf(stderr, "--dye-inflow V: a finite number; --dye-diffusivity D: a finite number >= 0; --dye-every K: K > 0\n");
+    return 2;
+  }
+  const bool dyeing = dyeSeen;
   const bool emitting = emitSeen, draining = drainSeen, editing = emitSeen || drainSeen;
   // the host buffer of the asynchronous read-back is page-locked in place at its first size: with a changing count the driver
   // reads the positions the blocking way
@@ -466,6 +485,11 @@ int main(int argc, char** argv) {
             "n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
             "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
             "reserved31\n", compCsv);
+    }
+    const unsigned dyeMask = 1u << SPH_LIQUID_PARTICLE;
+    if (dyeing) {
+      ocl_solver->fieldCreate(0, nullptr, dyeInflow);
+      if (dyeRegionSeen) ocl_solver->fieldSetRegion(0, 1.0f, dyeRegion, dyeMask);
     }
     Watch helper; helper.quiet = quiet;
     double total = 0;
@@ -679,6 +703,18 @@ int main(int argc, char** argv) {
           printf("_forces: step %d  on liquid (n %.0f): boundary load %.9e %.9e %.9e N  liquid load %.9e %.9e %.9e N\n", iterationCount + 1,
                  r[0], load(3, 0), load(3, 1), load(3, 2), load(1, 0), load(1, 1), load(1, 2));
         helper.report("_forces: \t\t%9.3f ms\n");
+      }
+      if (dyeing) {
+        const float stability = ocl_solver->fieldDiffuse(0, dyeDiffusivity * cfg.timeStep, dyeDiffusivity > 0.f ? 1 : 0, dyeMask);
+        if (dyeEvery > 0 && (iterationCount + 1) % dyeEvery == 0) {
+          const float everything[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+          double r[SPH_FIELD_DIAG_WORDS];
+          ocl_solver->fieldDiagnostics(0, everything, 1, dyeMask, r);
+          const double mean = r[0] > 0 ? r[1] / r[0] : 0.0, var = r[0] > 0 ? r[2] / r[0] - mean * mean : 0.0;
+          printf("dye step=%d n=%.0f sum=%.17g mean=%.17g var=%.17g min=%.17g max=%.17g stability=%.9g\n", iterationCount + 1, r[0], r[1],
+                 mean, var, r[3], r[4], (double)stability);
+        }
+        helper.report("_dye: \t\t\t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

@@ -30,6 +30,8 @@ MUSCLE_WORDS = 16  # sph_muscle_diagnostics record (frames.MUSCLE_FIELDS)
 MEMBRANE_WORDS = 8  # sph_membrane_measure record: area, unit normal, centroid, 0 (frames.MEMBRANE_FIELDS)
 FORCE_WORDS = 40  # sph_force_measure record (frames.FORCE_FIELDS)
 FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
+FIELD_SLOTS = 4  # carried particle fields per solver (sph_field_*)
+FIELD_DIAG_WORDS = 8  # sph_field_diagnostics record (frames.FIELD_DIAG_FIELDS)
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -135,7 +137,9 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
                     "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
                     "sph_render_particles", "sph_read_render", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
-                    "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map"] + _STAGE_FUNCS
+                    "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map", "sph_field_create",
+                    "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
+                    "sph_field_diffuse", "sph_field_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -241,6 +245,14 @@ def device_lib():
         L.sph_add_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         L.sph_emit_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         L.sph_read_edit_map.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_field_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_float]
+        L.sph_field_release.argtypes = [C.c_void_p, C.c_int32]
+        L.sph_field_write.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.sph_field_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.sph_field_set_region.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
+        L.sph_field_set_selection.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]
+        L.sph_field_diffuse.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.c_void_p]
+        L.sph_field_diagnostics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         _dev = L
     return _dev
 
@@ -907,6 +919,65 @@ class owHIPSolver:
         out = np.empty(max(n, 1), np.int32)
         self._chk(self._L.sph_read_edit_map(self._h, _ptr(out)))
         return out[:n]
+
+    # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
+    def _field_values(self, values, what):
+        a = np.ascontiguousarray(values, np.float32).reshape(-1)
+        if a.size != self.N:
+            raise SphError("%s: values must hold one float per particle (%d)" % (what, self.N))
+        return a
+
+    def field_create(self, slot, values=None, inflow=0.0):
+        """Create carried field `slot` (0..3): float32[N] `values` in original-id order (the order of read_position_buffer;
+        None = all zero). Particles added later start at `inflow`. A step never touches a field; remove_*, add_particles
+        and emit_lattice carry it along (include/sphmi.h)."""
+        a = None if values is None else self._field_values(values, "field_create")
+        self._chk(self._L.sph_field_create(self._h, int(slot), _ptr(a), float(np.float32(inflow))))
+
+    def field_release(self, slot):
+        self._chk(self._L.sph_field_release(self._h, int(slot)))
+
+    def field_read(self, slot):
+        """float32[N]: the field of the current particle set, in original-id order."""
+        out = np.empty(max(self.N, 1), np.float32)
+        self._chk(self._L.sph_field_read(self._h, int(slot), _ptr(out)))
+        return out[:self.N]
+
+    def field_write(self, slot, values):
+        self._chk(self._L.sph_field_write(self._h, int(slot), _ptr(self._field_values(values, "field_write"))))
+
+    def field_set_region(self, slot, value, region=None, types=(1,)):
+        """Set the field to `value` on the particles remove_region(region, types) would remove, by their current position.
+        Returns their number."""
+        rg = _region(region, "field_set_region")
+        painted = np.zeros(1, np.int64)
+        self._chk(self._L.sph_field_set_region(self._h, int(slot), _ptr(rg), type_mask(types), float(np.float32(value)), _ptr(painted)))
+        return int(painted[0])
+
+    def field_set_selection(self, slot, value):
+        """Set the field to `value` on the particles of the last select() (refused once the solver has stepped since).
+        Returns their number."""
+        painted = np.zeros(1, np.int64)
+        self._chk(self._L.sph_field_set_selection(self._h, int(slot), float(np.float32(value)), _ptr(painted)))
+        return int(painted[0])
+
+    def field_diffuse(self, slot, coefficient, substeps=1, types=(1,)):
+        """`substeps` Jacobi substeps of c_i += a_i * sum_j ((c_j - c_i) * (hs - r_ij)) / rho_j over the neighbour rows of the
+        last completed step, among the particles of `types` (K7's viscous sum with the scalar in place of a velocity
+        component; `coefficient` = diffusivity * time in the units of cfg.viscosity). Returns the stability number sigma =
+        max_i a_i * sum_j (hs - r_ij) / rho_j: for sigma <= 1 the field keeps its bounds. substeps=0 only measures it."""
+        sigma = np.zeros(1, np.float32)
+        self._chk(self._L.sph_field_diffuse(self._h, int(slot), float(np.float32(coefficient)), int(substeps), type_mask(types), _ptr(sigma)))
+        return float(sigma[0])
+
+    def field_diagnostics(self, slot, regions=None, types=(1,)):
+        """Reductions of the field over the particles diagnostics() selects for each region: float64[R, 8] records named by
+        frames.FIELD_DIAG_FIELDS (count, sum, sum of squares, min, max, particles with a non-zero value), added in the fixed
+        tree of diagnostics(). frames.field_summary turns a record into mean and variance."""
+        rg = _regions(regions, "field_diagnostics")
+        out = np.zeros((max(rg.shape[0], 1), FIELD_DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_field_diagnostics(self._h, int(slot), _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
+        return out
 
     # --- extras ---
     def step(self, iterationCount=0):

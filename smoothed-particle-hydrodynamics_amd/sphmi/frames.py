@@ -860,3 +860,30 @@ def track_ids(ids, edit_map=None, added=0, next_id=None):
         raise ValueError("track_ids: added must be >= 0")
     fresh = np.arange(next_id, next_id + added, dtype=np.int64)
     return np.concatenate([ids, fresh]), int(next_id) + added
+
+
+# ----------------------------------------------------------------------------- carried particle fields
+FIELD_DIAG_FIELDS = ("n", "sum", "sum_sq", "min", "max", "tagged", "unused6", "unused7")  # owHIPSolver.field_diagnostics
+
+
+def field_summary(record):
+    """One record of owHIPSolver.field_diagnostics as numbers: count, mean, variance (sum_sq / n - mean * mean, in double: the
+    spread that mixing removes), min, max, and tagged, the particles with a non-zero value. An empty selection gives zeros."""
+    r = np.asarray(record, np.float64).reshape(-1)
+    if r.size != len(FIELD_DIAG_FIELDS):
+        raise ValueError("field_summary: a record holds %d doubles" % len(FIELD_DIAG_FIELDS))
+    n = int(r[0])
+    mean = r[1] / n if n else 0.0
+    var = r[2] / n - mean * mean if n else 0.0
+    return dict(count=n, mean=float(mean), variance=float(var), min=float(r[3]), max=float(r[4]), tagged=int(r[5]))
+
+
+def field_sorted(values, particle_index):
+    """A carried field (owHIPSolver.field_read: one float per particle in ORIG order) in SORTED order, from the (cell, orig id)
+    pairs of read_particleIndex_buffer taken in the same step: out[sorted position] = values[orig id]. The sorted order is the
+    one of force_measure, the selection's sorted indices and the rendered index image."""
+    v = np.asarray(values, np.float32).reshape(-1)
+    pi = np.asarray(particle_index).reshape(-1, 2)
+    if pi.shape[0] != v.shape[0]:
+        raise ValueError("field_sorted: one value per particle expected")
+    return v[pi[:, 1].astype(np.int64)]
