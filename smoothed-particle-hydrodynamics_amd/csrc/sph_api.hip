@@ -223,6 +223,58 @@ extern "C" int sph_destroy(sph_solver* s) {
   return SPH_OK;
 }
 
+// The index arrays of the elastic matter, checked like the coordinates: every one of these words becomes a device address
+// (k_elastic: backIndex[(int)conn.x]; k_membranes: posOrig[membraneData[..]], pml[orig id * 7 + ..] for ANY neighbour whose type
+// truncates to 2), and the reference checks none of them. One pass over 39 E + 3 M + N words.
+static int check_elastic_input(const sph_config& c, const float* position, const float* elastic, const int32_t* membraneData,
+                               const int32_t* pml) {
+  const int N = c.particleCount, E = c.numOfElasticP, M = c.numOfMembranes;
+  if (M < 0) { sph_set_error("numOfMembranes %d is negative", M); return SPH_ERR_INVALID; }
+  for (int i = 0; i < E; i++) {
+    bool ended = false;
+    for (int k = 0; k < SPH_MAXN; k++) {
+      const float* w = elastic + 4 * ((size_t)i * SPH_MAXN + k);
+      const float x = w[0];  // every kernel truncates it with (int): (-2, -1] is NO_PARTICLE_ID, (-1, 0] is particle 0
+      if (!std::isfinite(x)) { sph_set_error("elastic connection %d of particle %d: partner %g is not finite", k, i, x); return SPH_ERR_INVALID; }
+      if (ended) continue;   // past the first -1 only the (int) of this word is ever formed
+      if (x <= -2.f || (double)x >= (double)N) {
+        sph_set_error("elastic connection %d of particle %d: partner %g is neither -1 nor in [0, %d)", k, i, x, N);
+        return SPH_ERR_INVALID;
+      }
+      if ((int)x == -1) { ended = true; continue; }
+      if (!std::isfinite(w[1])) { sph_set_error("elastic connection %d of particle %d: rest length %g is not finite", k, i, w[1]); return SPH_ERR_INVALID; }
+      if (!(w[2] >= -2147483648.f && w[2] < 2147483648.f)) {  // (int)conn.z must be defined (a NaN fails both comparisons)
+        sph_set_error("elastic connection %d of particle %d: muscle word %g does not convert to int", k, i, w[2]);
+        return SPH_ERR_INVALID;
+      }
+    }
+  }
+  if (!(membraneData && pml && M > 0)) return SPH_OK;  // (the condition under which sph_create uploads the lists and the stage runs)
+  for (size_t k = 0; k < (size_t)3 * M; k++)
+    if (membraneData[k] < 0 || membraneData[k] >= N) {
+      sph_set_error("membraneData[%zu] (corner %zu of membrane %zu) = %d is not in [0, %d)", k, k % 3, k / 3, membraneData[k], N);
+      return SPH_ERR_INVALID;
+    }
+  for (int i = 0; i < E; i++)
+    for (int k = 0; k < SPH_MAX_MEMBRANES_INCLUDING_SAME_PARTICLE; k++) {
+      const int32_t m = pml[(size_t)i * SPH_MAX_MEMBRANES_INCLUDING_SAME_PARTICLE + k];
+      if (m < 0) break;  // any negative entry ends the list, as in the kernel
+      if (m >= M) {
+        sph_set_error("particleMembranesList[%d][%d] = %d is not below numOfMembranes %d", i, k, m, M);
+        return SPH_ERR_INVALID;
+      }
+    }
+  // the list has numOfElasticP rows and the kernel indexes it by the ORIGINAL id of whichever neighbour has elastic type
+  if (c.elasticOffset != 0) { sph_set_error("membrane lists need elasticOffset 0 (got %d): they are indexed by original particle id", c.elasticOffset); return SPH_ERR_INVALID; }
+  for (int i = E; i < N; i++)
+    if (position[4 * (size_t)i + 3] >= 2.f && position[4 * (size_t)i + 3] < 3.f) {  // (int)type == SPH_ELASTIC_PARTICLE
+      sph_set_error("particle %d has elastic type %g but lies outside the elastic block [0, %d) that the membrane lists cover", i,
+                    position[4 * (size_t)i + 3], E);
+      return SPH_ERR_INVALID;
+    }
+  return SPH_OK;
+}
+
 extern "C" int sph_create(const sph_config* cfg, const float* position, const float* velocity, const float* elastic,
                           const int32_t* membraneData, const int32_t* pml, sph_solver** out) {
   if (!cfg || !position || !velocity || !out) { sph_set_error("sph_create: null argument"); return SPH_ERR_INVALID; }
@@ -243,7 +295,8 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
     return SPH_ERR_INVALID;
   }
   if (cfg->cellIdMask != 0xffffu && cfg->cellIdMask != 0xffffffffu) { sph_set_error("cellIdMask must be 0xffff (reference) or 0xffffffff (wide)"); return SPH_ERR_INVALID; }
-  if (cfg->numOfElasticP < 0 || cfg->numOfElasticP + cfg->elasticOffset > N || (cfg->numOfElasticP > 0 && !elastic)) {
+  if (cfg->numOfElasticP < 0 || (cfg->numOfElasticP > 0 && cfg->elasticOffset < 0) || (long long)cfg->numOfElasticP + cfg->elasticOffset > N ||
+      (cfg->numOfElasticP > 0 && !elastic)) {
     sph_set_error("elastic configuration inconsistent");
     return SPH_ERR_INVALID;
   }
@@ -265,6 +318,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
       return SPH_ERR_INVALID;
     }
   }
+  { const int rc = check_elastic_input(*cfg, position, elastic, membraneData, pml); if (rc != SPH_OK) return rc; }
   int ndev = 0;
   const hipError_t devErr = hipGetDeviceCount(&ndev);
   if (devErr != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {

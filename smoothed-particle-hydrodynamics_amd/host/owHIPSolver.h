@@ -7,6 +7,7 @@
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "sphmi.h"
 #include "sphmi_host.h"
@@ -20,6 +21,22 @@ class owHIPSolver {
     // owOpenCLSolver.cpp:88-91: setup failures surface as std::exception ("ERROR: ..." + exit(-1) in the caller)
     check(sph_create(&cfg_, position_cpp, velocity_cpp, elasticConnectionsData_cpp, membraneData_cpp,
                      particleMembranesList_cpp, &s_), "sph_create");
+  }
+  // The same from containers, whose lengths are checked against the counts in cfg first (the C ABI and the constructor above see
+  // pointers only): 4 N floats of position and velocity, 4 * 32 * numOfElasticP, 3 * numOfMembranes, 7 * numOfElasticP. An empty
+  // vector stands for "not given".
+  owHIPSolver(const sph_config& cfg, const std::vector<float>& position, const std::vector<float>& velocity,
+              const std::vector<float>& elasticConnections = {}, const std::vector<int>& membraneData = {},
+              const std::vector<int>& particleMembranesList = {})
+      : cfg_(cfg), s_(nullptr) {
+    expect(position.size(), 4 * (long long)cfg.particleCount, "position", "4*particleCount");
+    expect(velocity.size(), 4 * (long long)cfg.particleCount, "velocity", "4*particleCount");
+    if (!elasticConnections.empty()) expect(elasticConnections.size(), 4LL * 32 * cfg.numOfElasticP, "elasticConnectionsData", "4*32*numOfElasticP");
+    if (!membraneData.empty()) expect(membraneData.size(), 3LL * cfg.numOfMembranes, "membraneData", "3*numOfMembranes");
+    if (!particleMembranesList.empty()) expect(particleMembranesList.size(), 7LL * cfg.numOfElasticP, "particleMembranesList", "7*numOfElasticP");
+    check(sph_create(&cfg_, position.data(), velocity.data(), elasticConnections.empty() ? nullptr : elasticConnections.data(),
+                     membraneData.empty() ? nullptr : membraneData.data(),
+                     particleMembranesList.empty() ? nullptr : particleMembranesList.data(), &s_), "sph_create");
   }
   ~owHIPSolver() { sph_destroy(s_); }
   owHIPSolver(const owHIPSolver&) = delete;
@@ -232,6 +249,11 @@ class owHIPSolver {
  private:
   static void check(int rc, const char* what) {
     if (rc != SPH_OK) throw std::runtime_error(std::string(what) + ": " + sph_last_error());
+  }
+  static void expect(size_t have, long long want, const char* array, const char* rule) {
+    if (want < 0 || have != (size_t)want)
+      throw std::runtime_error(std::string(array) + " holds " + std::to_string(have) + " words, the configuration asks for " + rule +
+                               " = " + std::to_string(want));
   }
   sph_config cfg_;
   sph_solver* s_;

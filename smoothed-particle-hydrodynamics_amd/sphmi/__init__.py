@@ -521,6 +521,12 @@ class owHIPSolver:
         el = None if elasticConnectionsData_cpp is None else np.ascontiguousarray(elasticConnectionsData_cpp, np.float32)
         mb = None if membraneData_cpp is None else np.ascontiguousarray(membraneData_cpp, np.int32)
         pm = None if particleMembranesList_cpp is None else np.ascontiguousarray(particleMembranesList_cpp, np.int32)
+        # the C ABI sees pointers only: the lengths the library will read are checked here
+        for name, a, want, rule in (("elasticConnectionsData", el, 4 * 32 * cfg.numOfElasticP, "4*32*numOfElasticP"),
+                                    ("membraneData", mb, 3 * cfg.numOfMembranes, "3*numOfMembranes"),
+                                    ("particleMembranesList", pm, 7 * cfg.numOfElasticP, "7*numOfElasticP")):
+            if a is not None and a.size != max(want, 0):
+                raise SphError("%s holds %d words, the configuration asks for %s = %d" % (name, a.size, rule, want))
         h = C.c_void_p()
         self._chk(self._L.sph_create(C.byref(cfg), _ptr(pos), _ptr(vel), _ptr(el), _ptr(mb), _ptr(pm), C.byref(h)))
         self._h = h

@@ -125,6 +125,238 @@ def elastic_offset_box():
                 membranes=None, particle_membranes=None, numOfLiquidP=nl, numOfElasticP=E, numOfBoundaryP=nb)
 
 
+HARD_MUSCLE_IDS = (1, 2, 50, 100, 101, 0, 7)  # per sheet row: 100 = MUSCLE_COUNT (the guard's edge), 101 = beyond it
+# (cos, sin) of the two tilts as literals, so that the scene does not depend on a libm: ~0.35 / 0.2 rad and ~0.03 / 0.03 rad
+HARD_TILT = {False: ((0.939372, 0.342898), (0.980067, 0.198669)), True: ((0.99955, 0.029996), (0.99955, 0.029996))}
+
+
+def _near_any(points, centres, radius, chunk=1024):
+    """points[i] lies closer than `radius` to some row of centres (float32 arithmetic, fixed summation order)."""
+    out = np.zeros(points.shape[0], bool)
+    r2 = np.float32(radius) * np.float32(radius)
+    for a in range(0, points.shape[0], chunk):
+        p = points[a:a + chunk]
+        d2 = (p[:, None, 0] - centres[None, :, 0]) ** 2
+        d2 += (p[:, None, 1] - centres[None, :, 1]) ** 2
+        d2 += (p[:, None, 2] - centres[None, :, 2]) ** 2
+        out[a:a + chunk] = d2.min(1) <= r2
+    return out
+
+
+def _near_elastic(liq, sheet_pos, normal, block_pos, radius):
+    """Liquid closer than `radius` to an elastic particle. The sheet is planar, so only liquid within `radius` of its plane is
+    measured against it (and only liquid in the block's inflated bounding box against the block): no N x E matrix."""
+    out = np.zeros(liq.shape[0], bool)
+    rel = liq[:, :3] - sheet_pos[0, :3]
+    off = np.abs(rel[:, 0] * normal[0] + rel[:, 1] * normal[1] + rel[:, 2] * normal[2])
+    cand = np.flatnonzero(off <= np.float32(1.05) * np.float32(radius))
+    out[cand] = _near_any(liq[cand, :3], sheet_pos[:, :3], radius)
+    lo, hi = block_pos[:, :3].min(0) - np.float32(radius), block_pos[:, :3].max(0) + np.float32(radius)
+    cand = np.flatnonzero(((liq[:, :3] >= lo) & (liq[:, :3] <= hi)).all(1))
+    out[cand] |= _near_any(liq[cand, :3], block_pos[:, :3], radius)
+    return out
+
+
+def elastic_hard_box(large=False, mask=0xffff, degenerate=True, offset=False, blob=False, zero_spring=False, bar=False):
+    """The elastic / membrane inputs the committed scenes do not contain. Order: elastic (sheet, then block), liquid,
+    boundary; encodings as in elastic_sheet_box.
+      * a TILTED sheet (no triangle normal has a zero component) with a UNION-JACK triangulation: interior vertices have 8 or 4
+        incident triangles, so the 7-entry membrane lists fill up without a terminator;
+      * a 5x5x5 elastic block at 0.8 r0 without membranes: the centre particle has exactly 32 spring partners (no -1 in its row);
+      * muscle ids per sheet row from HARD_MUSCLE_IDS;
+      * degenerate=True: a triangle with a repeated vertex (v, v, v+1), whose determinant is an exact zero, is put FIRST in the
+        membrane list of every fifth vertex along the sheet's diagonal: liquid that has such a vertex as a neighbour is abandoned;
+      * offset=True: file-mode order (boundary, elastic, liquid) without membranes, as elastic_offset_box;
+      * blob=True: a dense liquid blob (0.45 r0, the recipe of the overcrowded-cells test) around the middle of the sheet;
+      * zero_spring=True: sheet particle 1 is moved onto particle 0, to which a spring joins it (r = 0 in the elastic kernel);
+      * bar=True: the box is 70 h long in x and a bar of dense liquid (0.45 r0, 81 x 240 particles) fills the cell row through the
+        sheet's middle from 3.1 r0 beyond the lattice on: more than 16,384 particles then lie, in sorted order, between liquid next to
+        the sheet and its neighbours one cell row up, which is more than a 16-bit neighbour entry can span;
+      * large=True: a 90x90 sheet in a (50, 8, 50) h box, for the grid-stride sweep of the membrane kernel."""
+    box, lattice, (sx, sz) = (((50.0, 8.0, 50.0), (100, 12, 100), (90, 90)) if large else ((10.0, 8.0, 10.0), (16, 12, 16), (9, 9)))
+    if bar:
+        box = (70.0, 8.0, 10.0)
+    base = liquid_box(box, lattice, spacing_in_r0=0.93, mask=mask)
+    cfg = base["cfg"]
+    r0 = np.float32(cfg.r0)
+    f = np.float32
+    (ca, sa), (cb, sb) = [(f(c), f(s)) for c, s in HARD_TILT[large]]
+    # sheet: local (u, 0, w), turned about x by a, then about y by b, centred in the lattice and lifted 1.5 r0
+    centre = [f(3.0) * r0 + f(0.5 * (n - 1)) * f(0.93) * r0 for n in lattice]
+    centre[1] = centre[1] + f(1.5) * r0
+    iz, ix = np.meshgrid(np.arange(sz), np.arange(sx), indexing="ij")
+    u = ((ix.ravel() - f(0.5 * (sx - 1))) * r0).astype(np.float32)
+    w = ((iz.ravel() - f(0.5 * (sz - 1))) * r0).astype(np.float32)
+    y1, z1 = -w * sa, w * ca
+    spos = np.zeros((sx * sz, 4), np.float32)
+    spos[:, 0] = centre[0] + (u * cb + z1 * sb)
+    spos[:, 1] = centre[1] + y1
+    spos[:, 2] = centre[2] + (z1 * cb - u * sb)
+    spos[:, 3] = f(2.1)
+    normal = np.array([sa * sb, ca, sa * cb], np.float32)
+    # block in the low corner of the lattice, well away from the sheet
+    g = (f(3.4) * r0 + np.arange(5, dtype=np.float32) * (f(0.8) * r0)).astype(np.float32)
+    bz, by, bx = np.meshgrid(g, g, g, indexing="ij")
+    bpos = np.stack([bx.ravel(), by.ravel(), bz.ravel(), np.full(125, f(2.1))], 1).astype(np.float32)
+    epos = np.concatenate([spos, bpos])
+    S, E = spos.shape[0], epos.shape[0]
+    nl = base["numOfLiquidP"]
+    liq = base["position"][:nl]
+    if blob:
+        n = 8
+        o = np.array([centre[0] - f(1.6) * r0, centre[1] - f(1.0) * r0, centre[2] - f(1.6) * r0], np.float32)
+        k = (np.arange(n, dtype=np.float32) * (f(0.45) * r0)).astype(np.float32)
+        qz, qy, qx = np.meshgrid(k, k, k, indexing="ij")
+        dense = np.stack([o[0] + qx.ravel(), o[1] + qy.ravel(), o[2] + qz.ravel(), np.full(n ** 3, f(1.1))], 1).astype(np.float32)
+        inside = ((liq[:, :3] >= o - f(0.45) * r0) & (liq[:, :3] <= o + k[-1] + f(0.45) * r0)).all(1)
+        liq = np.concatenate([liq[~inside], dense])
+    gone = _near_elastic(liq, spos, normal, bpos, f(0.6) * r0)
+    blob_count = int((~gone[-8 ** 3:]).sum()) if blob else 0  # the blob's survivors are the last liquid particles
+    liq = liq[~gone]
+    if bar:  # cells are 2 h = 4 r0 wide: the row y, z in [8, 12) r0 holds the sheet's middle; the lattice ends at x = 17 r0
+        k = (f(8.1) * r0 + np.arange(9, dtype=np.float32) * (f(0.45) * r0)).astype(np.float32)
+        kx = (f(20.1) * r0 + np.arange(240, dtype=np.float32) * (f(0.45) * r0)).astype(np.float32)
+        qx, qz, qy = np.meshgrid(kx, k, k, indexing="ij")
+        liq = np.concatenate([liq, np.stack([qx.ravel(), qy.ravel(), qz.ravel(), np.full(qx.size, f(1.1))], 1).astype(np.float32)])
+    bnd_p, bnd_v = base["position"][nl:], base["velocity"][nl:]
+    # springs: partners within r0*sqrt(2.7), ascending id, at most 32 (the cap of owHelper.cpp:989)
+    elastic = np.zeros((E * 32, 4), np.float32)
+    elastic[:, 0] = -1.0
+    sim = f(cfg.simulationScale)
+    reach = r0 * np.sqrt(f(2.7))
+    row_of = np.concatenate([np.arange(S) // sx, np.full(E - S, -1)])
+    ecc = np.zeros(E, np.int64)
+    for a in range(0, E, 512):
+        p = epos[a:a + 512]
+        d2 = (p[:, None, 0] - epos[None, :, 0]) ** 2
+        d2 += (p[:, None, 1] - epos[None, :, 1]) ** 2
+        d2 += (p[:, None, 2] - epos[None, :, 2]) ** 2
+        r = np.sqrt(d2)
+        for i, j in zip(*np.nonzero(r <= reach)):
+            i += a
+            if i == j:
+                continue
+            if ecc[i] >= 32:
+                continue
+            slot = i * 32 + ecc[i]
+            ecc[i] += 1
+            muscle = 0.0
+            if row_of[i] >= 0 and row_of[i] == row_of[j]:
+                m = HARD_MUSCLE_IDS[row_of[i] % len(HARD_MUSCLE_IDS)]
+                muscle = m + 0.2 if m else 0.0
+            elastic[slot] = (f(j) + f(0.1), f(r[i - a, j] * sim * f(0.95)), muscle, 0)
+    # membranes: union jack over the sheet; per-particle lists (<= 7, -1 padded), degenerate triangles first where asked
+    tris = []
+    for z_ in range(sz - 1):
+        for x_ in range(sx - 1):
+            a, b, c, d = z_ * sx + x_, z_ * sx + x_ + 1, (z_ + 1) * sx + x_, (z_ + 1) * sx + x_ + 1
+            tris += [(a, b, c), (b, d, c)] if (x_ + z_) % 2 == 0 else [(a, b, d), (a, d, c)]
+    pml = -np.ones((E, 7), np.int32)
+    fill = np.zeros(E, np.int32)
+    if degenerate:
+        for k in range(2, min(sx, sz) - 1, 5):
+            v = k * sx + k
+            pml[v, 0] = len(tris)
+            fill[v] = 1
+            tris.append((v, v, v + 1))
+    for m, t in enumerate(tris):
+        if t[0] == t[1]:
+            continue
+        for v in t:
+            if fill[v] < 7:
+                pml[v, fill[v]] = m
+                fill[v] += 1
+    membranes = np.array(tris, np.int32)
+    if zero_spring:
+        epos[1, :3] = epos[0, :3]
+    pos = np.concatenate([epos, liq, bnd_p]).astype(np.float32)
+    vel = np.concatenate([np.zeros_like(epos), np.zeros_like(liq), bnd_v]).astype(np.float32)
+    nb = int(bnd_p.shape[0])
+    cfg.particleCount = pos.shape[0]
+    cfg.numOfElasticP = E
+    cfg.numOfMembranes = membranes.shape[0]
+    cfg.elasticOffset = 0
+    if offset:
+        order = np.concatenate([np.arange(E + len(liq), E + len(liq) + nb), np.arange(E), np.arange(E, E + len(liq))])
+        live = elastic[:, 0] >= 0
+        elastic[live, 0] = elastic[live, 0] + f(nb)  # partners are orig ids: shifted by the boundary block now in front
+        cfg.elasticOffset = nb
+        cfg.numOfMembranes = 0
+        pos, vel, membranes, pml = np.ascontiguousarray(pos[order]), np.ascontiguousarray(vel[order]), None, None
+    return dict(cfg=cfg, position=pos, velocity=vel, elastic=elastic, membranes=membranes, particle_membranes=pml,
+                numOfLiquidP=int(liq.shape[0]), numOfElasticP=E, numOfBoundaryP=nb, sheetCount=S, blobCount=blob_count, barCount=81 * 240 if bar else 0)
+
+
+def hard_muscle_signal(step):
+    """sphmi.muscle_signal with entry 99 (muscle id 100, which the generator's signal leaves at 0) switched on at odd steps: id 100
+    then carries a contraction at odd steps and meets `signal > 0` false at even ones."""
+    sig = sphmi.muscle_signal(step).copy()
+    if step % 2 == 1:
+        sig[99] = np.float32(0.4)
+    return sig
+
+
+def membrane_queue(canon, N):
+    """Sorted ids of the liquid particles with at least one elastic neighbour — what k_membrane_collect queues — from the
+    canonical buffers of a state whose neighbour search is current (positions' .w have not changed since)."""
+    pi = canon["particleIndex"].reshape(-1, 2)[:, 1].astype(np.int64)
+    typ = canon["position"][:, 3].astype(np.int32)[pi]  # type by sorted id
+    ids = canon["neighborIds"].reshape(N, 32)
+    nt = np.where(ids >= 0, typ[np.clip(ids, 0, N - 1)], 0)
+    return np.flatnonzero((typ == 1) & (nt == 2).any(1))
+
+
+def crowded_particles(canon, h, more_than=96):
+    """Sorted ids of the particles with more than `more_than` others within h at the neighbour search of the step that left
+    `canon` (sortedPosition is the state that search saw; d^2 in the reference's float expression). findNeighbors gives each of a
+    particle's two lanes a list of 48 candidates within h, so with more than 96 one list must overflow: such a particle is served
+    by the exact walk, whatever cells its neighbours lie in."""
+    p = canon["sortedPosition"][:, :3]
+    h2 = np.float32(h) * np.float32(h)
+    count = np.zeros(p.shape[0], np.int64)
+    for a in range(0, p.shape[0], 512):
+        q = p[a:a + 512]
+        ex, ey, ez = (q[:, None, k] - p[None, :, k] for k in range(3))
+        count[a:a + 512] = (ex * ex + ey * ey + ez * ez <= h2).sum(1) - 1  # (without the particle itself)
+    return np.flatnonzero(count > more_than)
+
+
+def certainly_wide_rows(canon, cfg, N):
+    """Sorted ids whose neighbour row findNeighbors' fast path cannot encode in 16 bits, from the buffers of the step's search: the
+    particle has at most 48 others within 31/30 h (so neither of its two 48-entry lists can overflow: it is on the fast path unless
+    one of its cells went unstaged, which debugCounters[0] counts), and a non-empty cell of the neighbouring y row in its own z layer
+    (the cells whose entries are offsets from the particle itself) lies more than 16,384 below or 16,381 above it in sorted order
+    (sph_common.h, SPH_N16_*). Their number less debugCounters[0] is a lower bound on debugCounters[2]."""
+    f = np.float32
+    sp = canon["sortedPosition"]
+    key = canon["particleIndex"].reshape(-1, 2)[:, 0].astype(np.int64)
+    gx, gy = cfg.gridCellsX, cfg.gridCellsY
+    start = np.searchsorted(key, np.arange(cfg.gridCellCount + 1))
+    inv, size, h = f(cfg.hashGridCellSizeInv), f(cfg.hashGridCellSize), f(cfg.h)
+    half = []
+    for axis, lo in ((0, cfg.xmin), (1, cfg.ymin)):
+        corner = (sp[:, axis] * inv).astype(np.int32).astype(np.float32) * size
+        half.append(np.where((sp[:, axis] - f(lo)) - corner < h, -1, 1))
+    cy = (key // gx) % gy + half[1]
+    cx = key % gx
+    ids = np.arange(N)
+    far = np.zeros(N, bool)
+    for xs in (0, half[0]):
+        ok = (cy >= 0) & (cy < gy) & (cx + xs >= 0) & (cx + xs < gx)
+        c = np.where(ok, key + half[1] * gx + xs, 0)
+        lo, hi = start[c], start[c + 1]
+        far |= ok & (hi > lo) & ((lo - ids + 16384 < 0) | (hi - 1 - ids + 16384 > 0x7FFD))
+    cand = np.flatnonzero(far)
+    p = sp[:, :3]
+    r2 = (h * f(31.0 / 30.0) * f(1.00001)) ** 2
+    few = np.zeros(cand.size, bool)
+    for a in range(0, cand.size, 256):
+        q = p[cand[a:a + 256]]
+        ex, ey, ez = (q[:, None, k] - p[None, :, k] for k in range(3))
+        few[a:a + 256] = (ex * ex + ey * ey + ez * ez <= r2).sum(1) - 1 <= 48
+    return cand[few]
+
+
 # name -> builder. Sizes chosen so that the C oracle finishes 10 steps in well under a second.
 SCENES = {
     "tiny": lambda: liquid_box((8.0, 8.0, 8.0), (12, 10, 12)),

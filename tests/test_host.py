@@ -218,6 +218,130 @@ def test_create_rejects_non_finite_and_out_of_box_input():
             sphmi.owHIPSolver(sc["cfg"], pos, sc["velocity"])
 
 
+def _accepted(sc):
+    """sph_create takes the scene's arrays as far as the device look-up: a solver on a machine with a GPU, "no HIP device" elsewhere."""
+    try:
+        scenes.hip_for(sc).close()
+    except sphmi.SphError as e:
+        assert "no HIP device" in str(e), str(e)
+
+
+def _hard(**kw):
+    sc = scenes.elastic_hard_box(**kw)
+    return sc, {k: None if sc[k] is None else sc[k].copy() for k in ("position", "elastic", "membranes", "particle_membranes")}
+
+
+def _refused(sc, arrays, message, status=-1):
+    with pytest.raises(sphmi.SphError, match=message) as e:
+        sphmi.owHIPSolver(sc["cfg"], arrays["position"], sc["velocity"], arrays["elastic"], arrays["membranes"],
+                          arrays["particle_membranes"])
+    if status is not None:
+        assert scenes.error_status(e) == status  # SPH_ERR_INVALID
+
+
+def test_create_accepts_the_committed_elastic_scenes_and_the_edge_scenes():
+    for sc in (scenes.worm_scene(), scenes.SCENES["tiny_elastic"](), scenes.elastic_offset_box(), scenes.elastic_hard_box(),
+               scenes.elastic_hard_box(offset=True), scenes.elastic_hard_box(blob=True, mask=0xffffffff),
+               scenes.elastic_hard_box(zero_spring=True, degenerate=False)):
+        _accepted(sc)
+
+
+def test_create_rejects_malformed_elastic_and_membrane_arrays():
+    """Every word of `elastic`, `membraneData` and `particleMembranesList` that a kernel turns into an address is checked before
+    the device is looked up (so also on a machine without one): one case per rule, each with the message that names the array,
+    the index and the value. These tests only ever construct: no solver that was given a malformed array is stepped."""
+    sc, a = _hard()
+    N, E, M = sc["cfg"].particleCount, sc["numOfElasticP"], sc["cfg"].numOfMembranes
+    row = 32 * 3  # particle 3, an inner slot of a live row
+    assert a["elastic"][row + 1, 0] >= 0
+
+    def case(array, index, value, message):
+        b = dict(a)
+        b[array] = a[array].copy()
+        b[array][index] = value
+        _refused(sc, b, message)
+
+    case("elastic", (row + 1, 0), np.nan, r"elastic connection 1 of particle 3: partner nan is not finite")
+    case("elastic", (row + 31, 0), np.inf, r"elastic connection 31 of particle 3: partner inf is not finite")  # past the -1: still cast
+    case("elastic", (row + 1, 1), np.inf, r"elastic connection 1 of particle 3: rest length inf is not finite")
+    case("elastic", (row + 1, 2), np.nan, r"elastic connection 1 of particle 3: muscle word nan does not convert to int")
+    case("elastic", (row + 1, 2), 3.0e9, r"elastic connection 1 of particle 3: muscle word 3e\+09 does not convert to int")
+    case("elastic", (row + 1, 0), float(N), r"elastic connection 1 of particle 3: partner %d is neither -1 nor in \[0, %d\)" % (N, N))
+    case("elastic", (row + 1, 0), -2.0, r"elastic connection 1 of particle 3: partner -2 is neither -1 nor in \[0, %d\)" % N)
+    case("membranes", (5, 2), N, r"membraneData\[17\] \(corner 2 of membrane 5\) = %d is not in \[0, %d\)" % (N, N))
+    case("membranes", (5, 0), -1, r"membraneData\[15\] \(corner 0 of membrane 5\) = -1 is not in \[0, %d\)" % N)
+    case("particle_membranes", (4, 1), M, r"particleMembranesList\[4\]\[1\] = %d is not below numOfMembranes %d" % (M, M))
+    # the edges that are NOT refused: what truncates to -1 or to N - 1, a negative list entry in front of a bad one, and
+    # anything behind a row's terminator except a non-finite word
+    ok = dict(a, elastic=a["elastic"].copy(), particle_membranes=a["particle_membranes"].copy())
+    ok["elastic"][row + 1, 0] = np.float32(N - 1) + np.float32(0.4)
+    ok["elastic"][row + 2, 0] = -1.9
+    ok["elastic"][row + 3] = (5.0e9, np.inf, np.nan, 0)
+    ok["particle_membranes"][4, 1:3] = (-7, M + 5)
+    _accepted(dict(sc, **ok))
+
+    bad = scenes.elastic_hard_box()
+    bad["cfg"].numOfMembranes = -1
+    _refused(bad, dict(a, membranes=None, particle_membranes=None), r"numOfMembranes -1 is negative")
+    # membrane lists are indexed by original id: they need the elastic block in front ...
+    off, b = _hard(offset=True)
+    nb = off["cfg"].elasticOffset
+    off["cfg"].numOfMembranes = M
+    pml = a["particle_membranes"]
+    _refused(off, dict(b, membranes=a["membranes"], particle_membranes=pml), r"membrane lists need elasticOffset 0 \(got %d\)" % nb)
+    # ... and no particle of elastic type behind it
+    b = dict(a, position=a["position"].copy())
+    b["position"][E + 9, 3] = 2.9
+    _refused(sc, b, r"particle %d has elastic type 2.9 but lies outside the elastic block \[0, %d\)" % (E + 9, E))
+    # without membrane lists neither rule applies (elastic_offset_box, the worm's file order)
+    _accepted(dict(sc, **dict(b, membranes=None, particle_membranes=None)))
+    neg = scenes.elastic_hard_box(offset=True)
+    neg["cfg"].elasticOffset = -1
+    with pytest.raises(sphmi.SphError, match="elastic configuration inconsistent"):
+        scenes.hip_for(neg)
+
+
+def test_wrappers_refuse_arrays_whose_length_does_not_match_the_counts(tmp_path):
+    """The C ABI sees pointers only; the ctypes wrapper and the C++ facade's container constructor check the lengths."""
+    sc, a = _hard()
+    for name, rule in (("elastic", "elasticConnectionsData holds %d words, the configuration asks for 4\\*32\\*numOfElasticP = %d"),
+                       ("membranes", "membraneData holds %d words, the configuration asks for 3\\*numOfMembranes = %d"),
+                       ("particle_membranes", "particleMembranesList holds %d words, the configuration asks for 7\\*numOfElasticP = %d")):
+        b = dict(a)
+        b[name] = a[name][:-1]
+        _refused(sc, b, rule % (b[name].size, a[name].size), status=None)
+    import subprocess
+    src = """#include <cstdio>
+#include <cstring>
+#include "owHIPSolver.h"
+int main() {
+  sph_config c;
+  sphmi_default_config(&c);
+  c.particleCount = 10; c.numOfElasticP = 2; c.numOfMembranes = 4;
+  std::vector<float> pos(40), vel(40), el(4 * 32 * 2);
+  std::vector<int> mem(12), pml(14);
+  const char* want[] = {"position holds 39", "elasticConnectionsData holds 255", "membraneData holds 11", "particleMembranesList holds 15"};
+  for (int k = 0; k < 4; k++) {
+    std::vector<float> p = pos, e = el;
+    std::vector<int> m = mem, l = pml;
+    if (k == 0) p.pop_back();
+    if (k == 1) e.pop_back();
+    if (k == 2) m.pop_back();
+    if (k == 3) l.push_back(0);
+    try { owHIPSolver s(c, p, vel, e, m, l); printf("case %d: accepted\\n", k); return 1; }
+    catch (const std::exception& x) { if (!strstr(x.what(), want[k])) { printf("case %d: %s\\n", k, x.what()); return 1; } }
+  }
+  puts("ok");
+  return 0;
+}
+"""
+    cpp, exe = tmp_path / "lengths.cpp", tmp_path / "lengths"
+    cpp.write_text(src)
+    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(scenes.ROOT, "include"), "-I", os.path.join(scenes.PKG, "host"),
+                           str(cpp), "-o", str(exe), "-L", scenes.PKG, "-lsphmi", "-lsphmi_host", "-Wl,-rpath," + scenes.PKG])
+    assert subprocess.check_output([str(exe)]).decode().strip() == "ok"
+
+
 def test_config_struct_layout_matches_header():
     """ctypes mirror of sph_config has the size the C compiler gives the header's struct."""
     import subprocess, tempfile
