@@ -578,6 +578,74 @@ int sph_render_particles(sph_solver* s, const sph_render_view* view, const float
 int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba /* 4 per pixel */,
                     uint32_t* thickness);  /* host, width x height each; any may be NULL */
 
+/* ---- Triangle rendering: the extracted surface and the membranes in the same images (the reference's viewer draws
+ * the membrane table, owWorldSimulation.cpp) -----------------------------------------------------------------------------------
+ * sph_render_mesh draws a triangle table into the images of sph_render_particles, as a fresh render (compose 0) or over the
+ * images of the last successful render, depth-correct (compose 1). Coverage is decided in integers, so every word is a function
+ * of the inputs alone. `view` is checked exactly as by sph_render_particles; its radius, maxRadiusPx, colourMode, field, lo, hi and
+ * typeColour are not used, ambient and background are.
+ * VERTICES. source 0: vertex i of the mesh of the last sph_extract_surface, at its float coordinates. source 1: the membrane table
+ * given to sph_create; corner o (an original id) is at sortedPosition[particleIndexBack[o]], the state of sph_membrane_measure.
+ * Projection is sph_render_particles' PROJECTION up to v (d, cx, cy, cz, k, u, v in float, in that order, no contraction). A
+ * vertex is USABLE when cz > nearPlane, fabsf(u) < 1048576.f and fabsf(v) < 1048576.f. Snap: X = (int)floorf(u*256.0f + 0.5f),
+ * Y likewise from v (1/256-pixel fixed point); zi = 1.0f/cz under perspective, zi = cz under orthographic.
+ * TRIANGLE t = (a, b, c) in table order is SKIPPED when any corner is not usable (there is NO NEAR-PLANE CLIPPING: a triangle that
+ * crosses the near plane is not drawn) or when A = E(a, b, c) == 0, with
+ *   E(p, q, r) = (int64)(Xq - Xp)*(Yr - Yp) - (int64)(Yq - Yp)*(Xr - Xp)     (operands below 2^29: exact)
+ * When A < 0, b and c are exchanged for everything that follows and A is negated. It is DRAWN otherwise, whether or not a pixel is
+ * hit.
+ * COVERAGE. Pixel (px, py) has its centre at P = (256*px + 128, 256*py + 128); w0 = E(b, c, P), w1 = E(c, a, P), w2 = E(a, b, P).
+ * Edge p -> q with dx = Xq - Xp, dy = Yq - Yp OWNS ITS LINE when dy > 0 || (dy == 0 && dx < 0). The pixel is covered when each
+ * wi > 0, or wi == 0 and that edge (b -> c, c -> a, a -> b) owns its line. An edge and its reverse get opposite verdicts: two
+ * triangles that share an edge never both cover a pixel centre on it, and a closed mesh covers every pixel an even number of times.
+ * The pixel set is that test over the whole image (the kernels search the box floor(min) .. floor(max) of the snapped corners in
+ * pixels, clipped to the image, which contains it).
+ * FRAGMENT. l1 = (float)w1/(float)A, l2 = (float)w2/(float)A (int64 -> float round to nearest, IEEE division);
+ * z = (zi_a + l1*(zi_b - zi_a)) + l2*(zi_c - zi_a); depth = 1.0f/z under perspective, z under orthographic. The fragment exists
+ * when depth > nearPlane and depth is finite. key = ((uint64)bits(depth) << 32) | t; the pixel keeps the minimum key: the nearest
+ * fragment, and on equal depth bits the lower triangle index.
+ * RESOLVE, once per pixel, the winner recomputed by the same expressions. Flat normal (shading 0): sph_membrane_measure's, from
+ * the three scene positions in table order: e1 = b - a, e2 = c - a, n = e1 x e2, len = sqrtf((nx*nx + ny*ny) + nz*nz), n/len or 0
+ * when len == 0. Smooth normal (shading 1, source 0 only): n = (na + l1*(nb - na)) + l2*(nc - na) per component from the normals
+ * sph_surface_normals defines (computed on the device), len as above, n/len, or 0 when len is 0 or not finite.
+ * facing = fabsf((nx*forward.x + ny*forward.y) + nz*forward.z) (two-sided: the membranes are not consistently oriented);
+ * shade = ambient + (1.0f - ambient)*facing. Base colour: `colour` (colourMode 0) or the ramp of sph_render_particles' mode 2 of
+ * q = (qa + l1*(qb - qa)) + l2*(qc - qa), with inv = 1.0f/(hi - lo) computed once on the host (a NaN q gives s = 0). The vertex
+ * scalar: source 0, field 0..5 = that word of the sph_sample_points record at the vertex with the extraction's typeMask, field 6
+ * = sqrtf((vx*vx + vy*vy) + vz*vz) of its words 2..4; source 1, sph_histogram's quantity `field` of the corner's sorted particle.
+ * Bytes as sph_render_particles, A = 255.
+ * IMAGES. compose 0: depth, rgba and the triangle image (int32; the winning t, -1 where none) come from the mesh; sortedIndex = -1
+ * and origId = 0xFFFFFFFF everywhere; no thickness. compose 1: the mesh takes a pixel when its depth < the depth image's value
+ * there (a float compare; a tie stays with what is there); taken pixels get the mesh's depth and rgba, sortedIndex = -1,
+ * origId = 0xFFFFFFFF and triangle = t; every other pixel keeps its bytes and gets triangle = -1; a thickness image stays as it is.
+ * counts = { triangles drawn, triangles skipped, pixels the mesh holds, pixels covered by anything }. sph_read_render keeps working
+ * on the result; sph_read_render_triangles copies the triangle image out; a later sph_render_particles drops it.
+ * Rules: blocking, on the solver's stream, read-only on every solver array (the mesh, a labelling, a selection and the fields stay
+ * valid), not a stage. SPH_ERR_ORDER before a step's density and pressure-force stages have run; for source 0 before any
+ * extraction, and with shading 1 or colourMode 1 once the state has changed since the extraction (sph_surface_normals' rule; flat
+ * shading with a constant colour draws a stale mesh); for source 1 with colourMode 1 and field 3 before the neighbour stage; for
+ * compose 1 without a successful render; for sph_read_render_triangles when the last render had no mesh pass. SPH_ERR_INVALID for
+ * a slab solver, null pointers, a view sph_render_particles would refuse, any style field out of range or not finite, shading 1
+ * with source 1, source 1 without membranes, and compose 1 when width .. nearPlane of `view` differ in any byte from the last
+ * render's. A membrane corner outside 0..N-1 is reported as by sph_membrane_measure and never followed. A failed call leaves the
+ * previous images as they were under compose 1 and none under compose 0.
+ * Device memory, grown on demand and freed by sph_destroy: the render buffer (its key plane is reused), 4 bytes per pixel for the
+ * triangle image, 32 bytes per vertex (44 with smooth shading; 92 with colourMode 1 on source 0: query points and sample records)
+ * and 4 bytes per triangle for the queue of large triangles. Source 1 has three vertices per membrane triangle. */
+typedef struct sph_render_mesh_style {
+  int32_t source;      /* 0: the mesh of the last sph_extract_surface; 1: the membrane triangles (sph_create's table) */
+  int32_t shading;     /* 0 flat (face normal); 1 smooth (vertex normals; source 0 only) */
+  int32_t colourMode;  /* 0 constant `colour`; 1 a per-vertex scalar through SPH_RENDER_FIELD_RAMP */
+  int32_t field;       /* mode 1. source 0: 0..5 = that word of the sample record at the vertex, 6 = speed.
+                          source 1: sph_histogram's field 0..6 of the corner's sorted particle */
+  float lo, hi;        /* mode 1: lo < hi, finite */
+  float colour[3];     /* mode 0: finite */
+  int32_t compose;     /* 0: a fresh image; 1: over the images of the last successful render */
+} sph_render_mesh_style;
+int sph_render_mesh(sph_solver* s, const sph_render_view* view, const sph_render_mesh_style* style,
+                    int64_t counts[4] /* triangles drawn, triangles skipped, pixels won by the mesh, covered pixels */);
+int sph_read_render_triangles(sph_solver* s, int32_t* triangle /* host, width x height; -1 where no triangle won */);
+
 /* ---- Particle editing: emitters, drains, gates (no reference counterpart: the reference fixes the particle set
  * when the solver is made) -----------------------------------------------------------------------------------------------------
  * Particles are removed from and appended to a live solver between two steps, within the capacity given to sph_create.

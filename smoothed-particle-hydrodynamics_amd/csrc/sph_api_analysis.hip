@@ -1,8 +1,9 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
 // diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, particle
-// rendering. All of them read the sorted state of the last completed step and write nothing the step reads. The results that
+// and triangle rendering. All of them read the sorted state of the last completed step and write nothing the step reads. The results that
 // outlive their call (mesh, labelling, selection, image) are SphDerived records: dropped first, stamped on success, checked by
 // their readers. What the translation units of the ABI share is in sph_api_internal.h.
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -707,6 +708,7 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
                                     int32_t wantThickness, int64_t counts[2]) {
   ENTER(s);
   sph_derived_drop(s->render);
+  s->renderHasMesh = false;
   if (counts) counts[0] = counts[1] = 0;
   if (!view || !counts) { sph_set_error("sph_render_particles: null pointer"); return SPH_ERR_INVALID; }
   int rc = sample_check(s, typeMask, "sph_render_particles");
@@ -739,6 +741,7 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
   if (rc != SPH_OK) return rc;
   s->renderW = view->width; s->renderH = view->height;
   s->renderThickness = thickness;
+  s->renderView = *view;
   sph_derived_stamp(s, s->render);
   counts[0] = (int64_t)head[0];
   counts[1] = (int64_t)head[1];
@@ -761,4 +764,129 @@ extern "C" int sph_read_render(sph_solver* s, float* depth, int32_t* sortedIndex
   if (thickness) SPH_HIP(hipMemcpyAsync(thickness, base + L.thickOut, words, hipMemcpyDeviceToHost, s->stream));
   SPH_HIP(hipStreamSynchronize(s->stream));
   return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- triangle rendering
+// The mesh of the last extraction or the membrane triangles into the same images (sph_render_mesh.hip), fresh or composed over the
+// last render by depth. Normals and vertex scalars come from the gradient and sampling kernels on the device; everything is
+// enqueued together and waited for once, for the counts.
+extern "C" int sph_render_mesh(sph_solver* s, const sph_render_view* view, const sph_render_mesh_style* style, int64_t counts[4]) {
+  ENTER(s);
+  const char* what = "sph_render_mesh";
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  if (!view || !style || !counts) { sph_set_error("%s: null pointer", what); return SPH_ERR_INVALID; }
+  const sph_render_mesh_style& y = *style;
+  if (y.compose != 0 && y.compose != 1) { sph_set_error("%s: compose %d is not 0 or 1", what, y.compose); return SPH_ERR_INVALID; }
+  if (!y.compose) {  // a fresh image: a failed call leaves none behind
+    sph_derived_drop(s->render);
+    s->renderHasMesh = false;
+  }
+  int rc = sample_check(s, 0xEu, what);
+  if (rc != SPH_OK) return rc;
+  if (!render_view_ok(*view)) return SPH_ERR_INVALID;
+  if (y.source != 0 && y.source != 1) { sph_set_error("%s: source %d is not 0 or 1", what, y.source); return SPH_ERR_INVALID; }
+  if (y.shading != 0 && y.shading != 1) { sph_set_error("%s: shading %d is not 0 or 1", what, y.shading); return SPH_ERR_INVALID; }
+  if (y.colourMode != 0 && y.colourMode != 1) { sph_set_error("%s: colourMode %d is not 0 or 1", what, y.colourMode); return SPH_ERR_INVALID; }
+  if (y.shading == 1 && y.source == 1) { sph_set_error("%s: smooth shading needs the surface mesh (source 0)", what); return SPH_ERR_INVALID; }
+  RenderMeshArgs a = {};
+  if (y.colourMode == 1) {
+    if (y.field < 0 || y.field > 6) { sph_set_error("%s: field %d is not in 0..6", what, y.field); return SPH_ERR_INVALID; }
+    if (!std::isfinite(y.lo) || !std::isfinite(y.hi) || !(y.lo < y.hi)) { sph_set_error("%s: lo and hi must be finite with lo < hi", what); return SPH_ERR_INVALID; }
+    volatile float width = y.hi - y.lo;
+    volatile float inv = 1.0f / width;
+    a.inv = inv;
+  } else {
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(y.colour[k])) { sph_set_error("%s: colour must be finite", what); return SPH_ERR_INVALID; }
+  }
+  int64_t V = 0, T = 0;
+  if (y.source == 1) {
+    if (s->d.numMembranes <= 0 || !s->d.membraneData) { sph_set_error("%s: the solver holds no membranes", what); return SPH_ERR_INVALID; }
+    T = s->d.numMembranes; V = 3 * T;
+    if (y.colourMode == 1 && y.field == 3) NEED(s, P_FIND, "sph_render_mesh (field 3)");
+  } else {
+    const bool live = y.shading == 1 || y.colourMode == 1;  // these read the state at the vertices
+    rc = sph_derived_check(s, s->mesh, what, "no surface has been extracted",
+                           live ? "the solver's state has changed since the surface was extracted (flat shading with a constant colour draws a stale mesh)" : nullptr);
+    if (rc != SPH_OK) return rc;
+    V = s->meshCounts[0]; T = s->meshCounts[1];
+  }
+  if (V > 0x7fffffffLL || T > 0x7fffffffLL) { sph_set_error("%s: more than 2^31-1 vertices or triangles", what); return SPH_ERR_SIZE; }
+  RenderLayout I;
+  if (y.compose) {
+    rc = sph_derived_check(s, s->render, what, "compose needs the images of a successful render", nullptr);
+    if (rc != SPH_OK) return rc;
+    if (memcmp(view, &s->renderView, offsetof(sph_render_view, radius)) != 0) {
+      sph_set_error("%s: compose needs the last render's width .. nearPlane, byte for byte", what);
+      return SPH_ERR_INVALID;
+    }
+    I = sphk_render_layout(s->renderW, s->renderH, s->renderThickness, s->render.N);
+  } else {
+    I = sphk_render_layout(view->width, view->height, false, s->d.N);
+    rc = sph_grow_scratch(s, s->renderBuf, I.bytes);
+    if (rc != SPH_OK) return rc;
+  }
+  a.view = *view;
+  a.source = y.source; a.shading = y.shading; a.colourMode = y.colourMode; a.field = y.field; a.compose = y.compose;
+  a.lo = y.lo;
+  for (int k = 0; k < 3; k++) a.colour[k] = y.colour[k];
+  a.V = (int)V; a.T = (int)T;
+  const bool normals = y.shading == 1, samples = y.source == 0 && y.colourMode == 1;
+  const RenderMeshLayout L = sphk_render_mesh_layout(V, T, normals, samples);
+  rc = sph_grow_scratch(s, s->renderMeshBuf, L.bytes);
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->renderTriBuf, sizeof(int32_t) * (size_t)view->width * (size_t)view->height);
+  if (rc != SPH_OK) return rc;
+  char* base = (char*)s->renderMeshBuf.p;
+  const float* verts = nullptr;
+  const int32_t* tris = nullptr;
+  if (y.source == 0) {
+    verts = (const float*)s->meshBuf.p;
+    tris = (const int32_t*)((const char*)s->meshBuf.p + surf_bytes_align(sizeof(float) * 3 * (size_t)V));
+    if ((normals || samples) && V > 0) {
+      SampleArgs sa;
+      rc = sample_check(s, s->meshTypeMask, what, &sa);
+      if (rc != SPH_OK) return rc;
+      if (normals) rc = sphk_surface_normals(s, sa, gradient_scale(s), s->meshField, verts, (int)V, (float*)(base + L.normals));
+      if (rc != SPH_OK) return rc;
+      if (samples) {
+        rc = sphk_render_mesh_points(s, (int)V, verts, (float*)(base + L.points));
+        if (rc != SPH_OK) return rc;
+        rc = sphk_sample_points(s, sa, (const float*)(base + L.points), (int)V, (float*)(base + L.records));
+        if (rc != SPH_OK) return rc;
+      }
+    }
+  }
+  rc = sphk_render_mesh(s, a, verts, tris, base, L, I, s->renderBuf.p, (int32_t*)s->renderTriBuf.p);
+  if (rc != SPH_OK) return rc;
+  uint32_t head[6] = {};
+  rc = sph_d2h(s, head, base + L.head, sizeof(head));  // the call's one wait for a result
+  if (rc != SPH_OK) return rc;
+  if (head[3]) {
+    sph_set_error("%s: a membrane id lies outside 0..N-1 (flags 0x%x); it was not followed and nothing was drawn", what, head[3]);
+    return SPH_ERR_INVALID;
+  }
+  rc = sph_check_finite_state(s);
+  if (rc != SPH_OK) return rc;
+  if (!y.compose) {
+    s->renderW = view->width; s->renderH = view->height;
+    s->renderThickness = false;
+    s->renderView = *view;
+    sph_derived_stamp(s, s->render);
+  }
+  s->renderHasMesh = true;
+  counts[0] = (int64_t)head[0];
+  counts[1] = (int64_t)head[1];
+  counts[2] = (int64_t)head[4];
+  counts[3] = (int64_t)head[5];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_render_triangles(sph_solver* s, int32_t* triangle) {
+  ENTER(s);
+  const int rc = sph_derived_check(s, s->render, "sph_read_render_triangles", "nothing has been rendered", nullptr);
+  if (rc != SPH_OK) return rc;
+  if (!s->renderHasMesh) { sph_set_error("sph_read_render_triangles: the last render had no mesh pass"); return SPH_ERR_ORDER; }
+  if (!triangle) { sph_set_error("sph_read_render_triangles: null pointer"); return SPH_ERR_INVALID; }
+  return sph_d2h(s, triangle, s->renderTriBuf.p, sizeof(int32_t) * (size_t)s->renderW * (size_t)s->renderH);
 }

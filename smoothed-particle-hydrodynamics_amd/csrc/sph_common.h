@@ -172,6 +172,11 @@ struct sph_solver {
   SphDerived render;                  // the last successful render; N: the particle count its buffer was laid out for
   bool renderThickness = false;       // ... it accumulated thickness
   int renderW = 0, renderH = 0;       // ... its size
+  // triangle rendering (sph_render_mesh / sph_read_render_triangles): vertex records, normals, sample records and the queue of
+  // large triangles in renderMeshBuf, the triangle image in renderTriBuf, both grown on demand
+  SphScratch renderMeshBuf, renderTriBuf;
+  bool renderHasMesh = false;         // the last render had a mesh pass: the triangle image exists
+  sph_render_view renderView = {};    // the view of the last successful render (compose needs the same width .. nearPlane)
   // particle editing (sph_remove_* / sph_add_particles / sph_emit_lattice): the compaction's scan scratch, grown on demand. The
   // id map of the last removal lies in backIndex (dead until the next step's sort), or is the identity (an empty removal).
   SphScratch editBuf;
@@ -432,6 +437,24 @@ struct RenderLayout { size_t head, keys, thick, depth, index, origId, rgba, thic
 RenderLayout sphk_render_layout(int width, int height, bool thickness, int N);
 // clear, splat, drain the queue of large splats, resolve; head words afterwards: [0] particles drawn, [1] covered pixels
 int sphk_render(sph_solver* s, const RenderArgs& a, bool thickness, void* buf);
+// sph_render_mesh.hip (triangles into the same images, fresh or composed by depth; read-only on every solver array)
+struct RmVertex { int32_t X, Y; float zi; int32_t usable; };  // snapped screen position (1/256 pixel), 1/cz (perspective) or cz
+struct RenderMeshArgs {
+  sph_render_view view;
+  int source, shading, colourMode, field, compose;
+  float lo, inv;      // inv = 1.0f / (hi - lo), one float (colour mode 1)
+  float colour[3];
+  int V, T;           // vertices (source 1: 3 per membrane triangle, in table order) and triangles
+};
+// where the pieces of a mesh pass lie in its scratch (bytes from its start); normals / points / records are 0 when not asked for
+struct RenderMeshLayout { size_t head, vtx, attr, normals, points, records, queue, bytes; };
+RenderMeshLayout sphk_render_mesh_layout(int64_t V, int64_t T, bool normals, bool samples);
+int sphk_render_mesh_points(sph_solver* s, int V, const float* verts, float* pts4);  // packed (x, y, z) -> (x, y, z, 0) query points
+// clear, vertex pass, raster, drain, resolve into the images laid out by I at `images` (keys reused) and the triangle image. verts /
+// tris: the mesh (source 0; source 1 reads the solver's tables). Head words afterwards: [0] drawn, [1] skipped, [3] error flags,
+// [4] pixels the mesh holds, [5] covered pixels
+int sphk_render_mesh(sph_solver* s, const RenderMeshArgs& a, const float* verts, const int32_t* tris, void* scratch,
+                     const RenderMeshLayout& L, const RenderLayout& I, void* images, int32_t* triangleImage);
 // sph_forces.hip (the K7 / K12 accelerations by the class of the neighbour that exerted them; read-only on every
 // solver array). Device pointers.
 // records (SPH_FORCE_WORDS floats each, 16-byte aligned) of the sorted particles first .. first + n, or of list[0..n) if given

@@ -173,6 +173,15 @@ class owHIPSolver {
   void readRender(float* depth, int32_t* sortedIndex, uint32_t* origId, uint8_t* rgba, uint32_t* thickness) {
     check(sph_read_render(s_, depth, sortedIndex, origId, rgba, thickness), "readRender");
   }
+  // beyond the reference: triangles in the same picture. renderMesh draws the mesh of the last extractSurface (style.source 0) or
+  // the membrane triangles (1) through `view`, as a fresh render (style.compose 0) or over the images of the last render by depth
+  // (1: the same width .. nearPlane), and fills counts = {triangles drawn, triangles skipped, pixels the mesh holds, covered
+  // pixels}; readRender keeps working; readRenderTriangles copies out the winning triangle per pixel, -1 where none
+  // (include/sphmi.h, sph_render_mesh / sph_read_render_triangles)
+  void renderMesh(const sph_render_view& view, const sph_render_mesh_style& style, int64_t counts[4]) {
+    check(sph_render_mesh(s_, &view, &style, counts), "renderMesh");
+  }
+  void readRenderTriangles(int32_t* triangle) { check(sph_read_render_triangles(s_, triangle), "readRenderTriangles"); }
 
   // beyond the reference: the particle set changes between two steps (emitters, drains, gates). removeRegion removes the
   // particles of typeMask inside region6 (or null = everywhere) from the current state (read_position_buffer's order), or only

@@ -43,7 +43,7 @@
 //        with its torque about the origin and its power; otherwise the boundary's and the liquid's load on the liquid (type 1)
 //   ... --render-every K --render-out DIR [--render-size W H] [--render-eye X Y Z] [--render-target X Y Z] [--render-up X Y Z]
 //       [--render-ortho S | --render-focal F] [--render-radius R] [--render-colour type|density|field:N:LO:HI|label]
-//       [--render-thickness]
+//       [--render-thickness] [--render-surface] [--render-membranes] [--render-types T...]
 //        after every K-th step, draw the liquid and elastic particles on the device (sph_render_particles) and write
 //        DIR/frame_<steps done>.ppm (binary P6; sphmi.frames.read_ppm), DIR/frame_<steps done>.depth.f32 (raw float32, H x W, +inf
 //        where nothing was drawn) and, with --render-thickness, DIR/frame_<steps done>.thickness.u32. The camera is at --render-eye
@@ -52,6 +52,11 @@
 //        --render-ortho S: orthographic, S pixels per scene unit; --render-focal F: perspective, focal length F pixels (default:
 //        perspective with F = W); the principal point is the image centre, the sphere radius defaults to r0 / 2, N is a field
 //        number 0..6 of sph_histogram; label colours need no other option (the components of the drawn types are labelled first)
+//        --render-surface: in each frame, extract the isosurface of --surface-grid NX NY NZ (--surface-iso; no PLY file unless
+//        --surface-every / --surface-out are given too) and draw it smooth-shaded (sph_render_mesh); --render-membranes: draw the
+//        membrane triangles flat-shaded (--worm). Without --render-types T... the frame shows the triangles alone; with it the
+//        particles of those types are drawn first and the triangles are composed over them by depth. One "_render_mesh:" line
+//        per frame.
 //   ... --capacity N --emit-lattice OX OY OZ NX NY NZ [--emit-spacing S] [--emit-velocity VX VY VZ] [--emit-every K] [--emit-until STEP]
 //       --drain-region X0 Y0 Z0 X1 Y1 Z1 [--drain-types T...] [--drain-every K] [--drain-at STEP]
 //        particles appear and disappear between steps (sph_emit_lattice / sph_remove_region). Edits happen BEFORE
@@ -176,6 +181,7 @@ int main(int argc, char** argv) {
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
   float renOrtho = 0.f, renFocal = 0.f, renRadius = 0.f; bool renOrthoSeen = false, renFocalSeen = false, renRadiusSeen = false;
+  bool renSurface = false, renMembranes = false, renTypesSeen = false; unsigned renTypes = 0;
   int capacity = 0; bool capSeen = false;
   bool emitSeen = false, emitLatSeen = false; float emitOrigin[3] = {0, 0, 0}, emitSpacing = 0.f, emitVel[3] = {0, 0, 0};
   int emitDims[3] = {0, 0, 0}, emitEvery = 1, emitUntil = -1;
@@ -223,6 +229,16 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--render-radius") && i + 1 < argc) { renRadius = (float)atof(argv[++i]); renSeen = renRadiusSeen = true; }
     else if (!strcmp(argv[i], "--render-colour") && i + 1 < argc) { renColour = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-thickness")) { renThickness = renSeen = true; }
+    else if (!strcmp(argv[i], "--render-surface")) { renSurface = renSeen = true; }
+    else if (!strcmp(argv[i], "--render-membranes")) { renMembranes = renSeen = true; }
+    else if (!strcmp(argv[i], "--render-types")) {
+      renSeen = renTypesSeen = true;
+      while (i + 1 < argc && argv[i + 1][0] != '-') {
+        const int t = atoi(argv[++i]);
+        if (t < 1 || t > 3) { fprintf(stderr, "--render-types: a type is 1 (liquid), 2 (elastic) or 3 (boundary)\n"); return 2; }
+        renTypes |= 1u << t;
+      }
+    }
     else if (!strcmp(argv[i], "--select-every") && i + 1 < argc) { selEvery = atoi(argv[++i]); selSeen = true; }
     else if (!strcmp(argv[i], "--select-out") && i + 1 < argc) { selDir = argv[++i]; selSeen = true; }
     else if (!strcmp(argv[i], "--select-surface") && i + 1 < argc) { selTerms.push_back(sph_select_term{SPH_SELECT_FIELD_SURFACE, (float)atof(argv[++i]), INFINITY}); selSeen = true; }
@@ -284,7 +300,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--sample-grid NX NY NZ (all > 0), --sample-every K (> 0) and --sample-out DIR go together\n");
     return 2;
   }
-  const bool surfacing = surfDims[0] > 0 || surfEvery > 0 || surfDir;
+  // --render-surface draws the --surface-grid mesh; the PLY files need --surface-every and --surface-out as before
+  const bool surfacing = surfEvery > 0 || surfDir || (surfDims[0] > 0 && !renSurface);
   if (surfacing && (surfDims[0] < 2 || surfDims[1] < 2 || surfDims[2] < 2 || surfEvery <= 0 || !surfDir)) {
     fprintf(stderr, "--surface-grid NX NY NZ (all >= 2), --surface-every K (> 0) and --surface-out DIR go together\n");
     return 2;
@@ -333,6 +350,12 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool rendering = renSeen;
+  const bool renMeshes = renSurface || renMembranes;
+  if (renSurface && (surfDims[0] < 2 || surfDims[1] < 2 || surfDims[2] < 2)) { fprintf(stderr, "--render-surface needs --surface-grid NX NY NZ (all >= 2)\n"); return 2; }
+  if (renTypesSeen && (!renMeshes || !renTypes)) {
+    fprintf(stderr, "--render-types T... (at least one type) chooses the particles --render-surface / --render-membranes are drawn over\n"); return 2;
+  }
+  if (renMeshes && !renTypesSeen && renThickness) { fprintf(stderr, "--render-thickness needs particles: give --render-types\n"); return 2; }
   if (capSeen && capacity <= 0) { fprintf(stderr, "--capacity N: N must be > 0\n"); return 2; }
   if (emitSeen && (!emitLatSeen || emitDims[0] <= 0 || emitDims[1] <= 0 || emitDims[2] <= 0 || emitEvery <= 0)) {
     fprintf(stderr, "--emit-lattice OX OY OZ NX NY NZ (NX, NY, NZ > 0) is needed by the other --emit options; --emit-every K needs K > 0\n");
@@ -425,6 +448,7 @@ int main(int argc, char** argv) {
     if (emitUntil < 0) emitUntil = steps;
     int particleCount = cfg.particleCount;  // changes with every edit
     if (measuringElastic && numOfElasticP == 0) { fprintf(stderr, "--elastic-every needs a scene with elastic matter (--worm)\n"); return 2; }
+    if (renMembranes && membraneData_cpp.empty()) { fprintf(stderr, "--render-membranes needs a scene with membranes (--worm)\n"); return 2; }
     printf("particles: %d (liquid %d, elastic %d, boundary %d), grid %d x %d x %d\n", cfg.particleCount, numOfLiquidP,
            numOfElasticP, numOfBoundaryP, cfg.gridCellsX, cfg.gridCellsY, cfg.gridCellsZ);
     owOpenCLSolver* ocl_solver = new owOpenCLSolver(cfg, position_cpp.data(), velocity_cpp.data(),
@@ -632,10 +656,28 @@ int main(int argc, char** argv) {
         helper.report("_components: \t\t%9.3f ms\n");
       }
       if (rendering && (iterationCount + 1) % renEvery == 0) {
-        const unsigned renMask = (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE);
+        const unsigned renMask = renTypesSeen ? renTypes : (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE);
+        const bool particles = !renMeshes || renTypesSeen;
         int64_t counts[2] = {0, 0};
-        if (renView.colourMode == 3) ocl_solver->labelComponents(INFINITY, renMask, counts);
-        ocl_solver->renderParticles(renView, nullptr, renMask, renThickness, counts);
+        if (particles) {
+          if (renView.colourMode == 3) ocl_solver->labelComponents(INFINITY, renMask, counts);
+          ocl_solver->renderParticles(renView, nullptr, renMask, renThickness, counts);
+        }
+        // the triangle passes: the surface of this frame's state, then the membranes, each over what is there already
+        int64_t meshCounts[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        bool drawnOver = particles;
+        if (renSurface) {
+          int64_t mesh[2];
+          ocl_solver->extractSurface(sampleOrigin, surfSpacing, surfDims, (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE),
+                                     1 /* shepard */, surfIso, mesh);
+          sph_render_mesh_style st = {0, 1, 0, 0, 0.f, 1.f, {0.35f, 0.6f, 0.95f}, drawnOver ? 1 : 0};  // smooth, one colour
+          ocl_solver->renderMesh(renView, st, meshCounts[0]);
+          drawnOver = true;
+        }
+        if (renMembranes) {
+          sph_render_mesh_style st = {1, 0, 0, 0, 0.f, 1.f, {0.95f, 0.6f, 0.25f}, drawnOver ? 1 : 0};  // flat, one colour
+          ocl_solver->renderMesh(renView, st, meshCounts[1]);
+        }
         const size_t pixels = (size_t)renView.width * (size_t)renView.height;
         renRgba.resize(4 * pixels); renDepth.resize(pixels); renThick.resize(renThickness ? pixels : 0);
         ocl_solver->readRender(renDepth.data(), nullptr, nullptr, renRgba.data(), renThickness ? renThick.data() : nullptr);
@@ -647,7 +689,13 @@ int main(int argc, char** argv) {
         if (!write_file(base + ".depth.f32", header, 0, renDepth.data(), sizeof(float) * pixels)) throw std::runtime_error("cannot write " + base + ".depth.f32");
         if (renThickness && !write_file(base + ".thickness.u32", header, 0, renThick.data(), sizeof(uint32_t) * pixels))
           throw std::runtime_error("cannot write " + base + ".thickness.u32");
-        if (!quiet) printf("_render: drew %lld particles, covered %lld of %zu pixels -> %s.ppm\n", (long long)counts[0], (long long)counts[1], pixels, base.c_str());
+        if (!quiet && particles) printf("_render: drew %lld particles, covered %lld of %zu pixels -> %s.ppm\n", (long long)counts[0], (long long)counts[1], pixels, base.c_str());
+        if (!quiet && renMeshes) {
+          const int64_t* last = meshCounts[renMembranes ? 1 : 0];
+          printf("_render_mesh: surface drew %lld skipped %lld holds %lld, membranes drew %lld skipped %lld holds %lld, covered %lld of %zu pixels -> %s.ppm\n",
+                 (long long)meshCounts[0][0], (long long)meshCounts[0][1], (long long)meshCounts[0][2], (long long)meshCounts[1][0],
+                 (long long)meshCounts[1][1], (long long)meshCounts[1][2], (long long)last[3], pixels, base.c_str());
+        }
         helper.report("_render: \t\t%9.3f ms\n");
       }
       if (selecting && (iterationCount + 1) % selEvery == 0) {

@@ -77,6 +77,17 @@ class SphRenderView(C.Structure):
 RENDER_COLOUR_MODES = ("type", "density", "field", "label")  # sph_render_view.colourMode 0..3
 
 
+class SphRenderMeshStyle(C.Structure):
+    """sph_render_mesh_style of include/sphmi.h (owHIPSolver.render_mesh fills one)."""
+    _fields_ = [("source", C.c_int32), ("shading", C.c_int32), ("colourMode", C.c_int32), ("field", C.c_int32),
+                ("lo", C.c_float), ("hi", C.c_float), ("colour", C.c_float * 3), ("compose", C.c_int32)]
+
+
+RENDER_MESH_SOURCES = ("surface", "membranes")  # sph_render_mesh_style.source 0..1
+RENDER_MESH_SHADINGS = ("flat", "smooth")  # sph_render_mesh_style.shading 0..1
+RENDER_MESH_SURFACE_FIELDS = ("density", "shepard", "vx", "vy", "vz", "pressure", "speed")  # field 0..6 with source 0
+
+
 class SphError(RuntimeError):
     pass
 
@@ -136,7 +147,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
                     "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
-                    "sph_render_particles", "sph_read_render", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
+                    "sph_render_particles", "sph_read_render", "sph_render_mesh", "sph_read_render_triangles", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
                     "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map", "sph_field_create",
                     "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
                     "sph_field_diffuse", "sph_field_diagnostics"] + _STAGE_FUNCS
@@ -239,6 +250,8 @@ def device_lib():
         L.sph_force_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_render_particles.argtypes = [C.c_void_p, C.POINTER(SphRenderView), C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
         L.sph_read_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_render_mesh.argtypes = [C.c_void_p, C.POINTER(SphRenderView), C.POINTER(SphRenderMeshStyle), C.c_void_p]
+        L.sph_read_render_triangles.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_remove_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
         L.sph_remove_selection.argtypes = [C.c_void_p, C.c_void_p]
         L.sph_remove_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -829,16 +842,51 @@ class owHIPSolver:
         rg = _region(region, "render")
         counts = np.zeros(2, np.int64)
         self._render_shape = None  # (a failed render leaves no image behind)
+        self._render_triangles = False
         self._chk(self._L.sph_render_particles(self._h, C.byref(view) if view is not None else None, _ptr(rg), type_mask(types),
                                                1 if thickness else 0, _ptr(counts)))
         self._render_shape = (int(view.height), int(view.width))
         return int(counts[0]), int(counts[1])
 
-    def rendered(self, depth=True, index=True, orig_id=True, rgba=True, thickness=False):
-        """The images of the last render() as a dict of the ones asked for: depth float32[H, W] (+inf where uncovered), index
-        int32[H, W] (the winner's sorted index, -1), orig_id uint32[H, W] (0xFFFFFFFF), rgba uint8[H, W, 4] (the view's
-        background) and thickness uint32[H, W] (units of radius / 128; frames.thickness_in_scene_units). They stay readable
-        after further steps."""
+    def render_mesh(self, view, source="surface", shading="flat", colour=(0.8, 0.8, 0.8), field=None, lo=0.0, hi=1.0, compose=False):
+        """Draw triangles through `view` into the images of render(): the mesh of the last extract_surface (source="surface") or
+        the membrane triangles (source="membranes"), flat or (surface only) smooth shaded, two-sided, in the constant `colour`
+        or, with `field` given, in the ramp of render()'s field mode over a per-vertex scalar between lo and hi (surface: a name
+        from RENDER_MESH_SURFACE_FIELDS or 0..6, sampled at the vertices; membranes: a name from HIST_FIELDS or 0..6 of the
+        corner particles). compose=True draws over the images of the last render by depth (same width .. near plane); otherwise
+        the result is a fresh render. Returns (triangles drawn, triangles skipped, pixels the mesh holds, covered pixels);
+        rendered(triangle=True) reads the images (include/sphmi.h)."""
+        if not isinstance(view, SphRenderView):
+            raise SphError("render_mesh: view must be an SphRenderView")
+        st = SphRenderMeshStyle()
+        st.source = _field_index(source, RENDER_MESH_SOURCES, "render_mesh")
+        st.shading = _field_index(shading, RENDER_MESH_SHADINGS, "render_mesh")
+        col = np.asarray(colour, np.float32).reshape(-1)
+        if col.size != 3:
+            raise SphError("render_mesh: colour holds %d values, not 3" % col.size)
+        for k in range(3):
+            st.colour[k] = float(col[k])
+        if field is not None:
+            st.colourMode = 1
+            st.field = _field_index(field, HIST_FIELDS if st.source == 1 else RENDER_MESH_SURFACE_FIELDS, "render_mesh")
+            st.lo, st.hi = float(lo), float(hi)
+        if not isinstance(compose, (bool, np.bool_)):
+            raise SphError("render_mesh: compose must be a bool")
+        st.compose = 1 if compose else 0
+        counts = np.zeros(4, np.int64)
+        if not compose:
+            self._render_shape = None  # (a failed fresh render leaves no image behind)
+            self._render_triangles = False
+        self._chk(self._L.sph_render_mesh(self._h, C.byref(view), C.byref(st), _ptr(counts)))
+        self._render_shape = (int(view.height), int(view.width))
+        self._render_triangles = True
+        return tuple(int(c) for c in counts)
+
+    def rendered(self, depth=True, index=True, orig_id=True, rgba=True, thickness=False, triangle=False):
+        """The images of the last render() / render_mesh() as a dict of the ones asked for: depth float32[H, W] (+inf where
+        uncovered), index int32[H, W] (the winner's sorted index, -1), orig_id uint32[H, W] (0xFFFFFFFF), rgba uint8[H, W, 4]
+        (the view's background), thickness uint32[H, W] (units of radius / 128; frames.thickness_in_scene_units) and triangle
+        int32[H, W] (the winning triangle of the last render_mesh, -1). They stay readable after further steps."""
         shape = getattr(self, "_render_shape", None) or (1, 1)  # without a render the library reports SPH_ERR_ORDER
         out = {}
         if depth: out["depth"] = np.empty(shape, np.float32)
@@ -847,6 +895,9 @@ class owHIPSolver:
         if rgba: out["rgba"] = np.empty(shape + (4,), np.uint8)
         if thickness: out["thickness"] = np.empty(shape, np.uint32)
         self._chk(self._L.sph_read_render(self._h, *[_ptr(out.get(k)) for k in ("depth", "index", "orig_id", "rgba", "thickness")]))
+        if triangle:
+            out["triangle"] = np.empty(shape, np.int32)
+            self._chk(self._L.sph_read_render_triangles(self._h, _ptr(out["triangle"])))
         return out
 
     # --- particle editing (sph_remove_* / sph_add_particles / sph_emit_lattice / sph_read_edit_map) ---
