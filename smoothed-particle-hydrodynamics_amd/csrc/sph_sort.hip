@@ -281,11 +281,14 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_sort_post(SphDev d) {
 // is its first sorted index (what the reference's binary search finds); for an empty one it is the start of the next
 // non-empty cell (what the backward fill writes); [0] = 0 and [G] = N. The key array is L2-resident (4 B/particle).
 // Slab mode: only cells [first, last) are computed — the layers the slab's particles and their neighbour cells can lie in — plus
-// the two ends of the table, which ranged launches read (sph_ranged: cellStart[0], cellStart[G]).
-__global__ __launch_bounds__(SPH_BLOCK) void k_cell_start(SphDev d, int first, int last) {
+// the two ends of the table, which ranged launches read (sph_ranged: cellStart[0], cellStart[G]), plus [first2, last2): the cells
+// at the other end of the table that searchCell's wrap can turn a neighbour cell of those layers into (sphk_index_fixed).
+__global__ __launch_bounds__(SPH_BLOCK) void k_cell_start(SphDev d, int first, int last, int first2, int last2) {
   int c = first + blockIdx.x * SPH_BLOCK + threadIdx.x;
   if (c >= last) {
-    if (c == last) c = 0; else if (c == last + 1) c = d.G; else return;  // two spare lanes take the table's ends
+    const int spare = c - last;  // two spare lanes take the table's ends, the lanes after them the wrapped cells
+    if (spare == 0) c = 0; else if (spare == 1) c = d.G; else c = first2 + (spare - 2);
+    if (spare >= 2 && c >= last2) return;
   }
   if (c > d.G) return;
   int lo = 0, hi = d.N;  // first index in [0, N] whose key is >= c
@@ -302,17 +305,26 @@ int sphk_sort_post(sph_solver* s) {
   return SPH_OK;
 }
 int sphk_index_fixed(sph_solver* s) {
-  int first = 0, last = s->d.G + 1;
+  int first = 0, last = s->d.G + 1, first2 = 0, last2 = 0;
   if (s->hasSlab) {
     // A slab's particles lie in its own layers +- ghostLayers; the search reads the table for their cells, the cells one layer
     // up and down and two cells beyond a run's end: layers [layerLo - W - 2, layerHi + W + 3) cover that. The declared grid is the
     // global one (39 us of binary searches per step at 16.5 M cells, whatever the rank's share of the particles).
-    const long long layerCells = (long long)s->d.gx * s->d.gy, W = s->slab.ghostLayers;
+    const long long layerCells = (long long)s->d.gx * s->d.gy, W = s->slab.ghostLayers, G = s->d.G;
     const long long lo = max((long long)s->slab.layerLo - W - 2, 0LL) * layerCells;
-    const long long hi = min(((long long)s->slab.layerHi + W + 3) * layerCells, (long long)s->d.G + 1);
-    first = (int)min(lo, (long long)s->d.G + 1); last = (int)max(hi, (long long)first);
+    const long long hi = min(((long long)s->slab.layerHi + W + 3) * layerCells, G + 1);
+    first = (int)min(lo, G + 1); last = (int)max(hi, (long long)first);
+    // searchCell wraps a neighbour cell below 0 to c + G and one from G on to c - G, and the search reads cellStart[c] and [c + 1]
+    // there. A raw cell is at least -(layerCells + gx + 1) and then belongs to a particle of layers 0 or 1, which only a
+    // slab with first == 0 holds; it is at most G + layerCells + gx and then belongs to a particle of the top layer, which only a slab
+    // with last == G + 1 holds. That one layer of cells at the other end of the table is computed too, every step (N changes with
+    // every rebuild), unless the main range already holds it.
+    const long long reach = layerCells + s->d.gx + 2;
+    if (first == 0 && last < G + 1) { first2 = (int)max(G - reach, (long long)last); last2 = (int)G; }
+    else if (last == G + 1 && first > 0) { first2 = 1; last2 = (int)min(reach + 1, (long long)first); }
   }
-  hipLaunchKernelGGL(k_cell_start, dim3(sph_blocks(last - first + 2)), dim3(SPH_BLOCK), 0, s->stream, s->d, first, last);
+  const int lanes = (last - first) + 2 + max(last2 - first2, 0);
+  hipLaunchKernelGGL(k_cell_start, dim3(sph_blocks(lanes)), dim3(SPH_BLOCK), 0, s->stream, s->d, first, last, first2, last2);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }

@@ -411,9 +411,13 @@ class SlabDecomposition:
                 self._bound_out[p] = self._bound_in[p] = 0
         out, inn = {}, {}
         for p in peers:
-            b = min(self._bound_out[p], frames[p].numel() - 1)
-            self._bound_out[p] = b
-            out[p] = frames[p][:1 + b]
+            # Both ends of a link post the agreed length, whatever the backend's frame holds: the receiver knows nothing else.
+            b = self._bound_out[p]
+            if 1 + b <= frames[p].numel():
+                out[p] = frames[p][:1 + b]
+            else:  # the agreed length outgrows the backend's own frame: assemble one of that length, as exchange() does
+                out[p] = self._frame(("out", p), b)
+                out[p][:1 + n_out[p]] = frames[p][:1 + n_out[p]]  # count word and payload (a message always fits its frame)
             inn[p] = self._frame(("in", p), self._bound_in[p])
         ops = [dist.P2POp(dist.isend, out[p], p) for p in peers] + [dist.P2POp(dist.irecv, inn[p], p) for p in peers]
         for w in dist.batch_isend_irecv(ops):

@@ -45,6 +45,9 @@ def _scene():
         box = (float(rng.integers(6, 11)), float(rng.integers(6, 11)), float(2 * rng.integers(40, 101)))
         lattice = tuple(int(max(2, (2.0 * b - 7.0) / 0.93 * f)) for b, f in zip(box, rng.uniform(0.6, 1.0, size=3)))
         return scenes.liquid_box(box, lattice, mask=0xffffffff, jitter_in_r0=float(rng.uniform(0.0, 0.3)), seed=int(rng.integers(1, 1 << 30)))
+    if os.environ.get("SPHMI_TEST_CORNER_SCENE"):  # liquid in the low corner of the box: its walks reach wrapped cells (slab_ref.py)
+        import slab_ref
+        return slab_ref.corner_scene(tall=os.environ["SPHMI_TEST_CORNER_SCENE"] == "tall")  # "tall": liquid above rank 0's layers too
     if os.environ.get("SPHMI_TEST_EIGHT_SLABS"):  # 72 layers, thin in x and y: eight slabs of nine layers
         return scenes.liquid_box((6.0, 6.0, 144.0), (8, 8, 290), mask=0xffffffff, jitter_in_r0=0.05)
     if os.environ.get("SPHMI_TEST_LONG_SCENE"):  # 42 layers: three slabs of 14, so the middle one has an interior between its two cut zones
@@ -120,9 +123,14 @@ class OracleSlabBackend:
     def pack_framed(self):
         """[payload word count | payload] frames on the CPU, like HipSlabBackend's in HBM (exercises the zero-copy path)."""
         kept, down, up = self.pack()
+        self.message_words = getattr(self, "message_words", []) + [(int(down.numel()), int(up.numel()))]
         frames = []
         for t in (down, up):
-            f = self.torch.zeros(1 + 2 * t.numel() + 8192 * REC, dtype=self.torch.int32)  # room for the agreed padding
+            words = 2 * t.numel() + 8192 * REC  # room for the agreed padding
+            if os.environ.get("SPHMI_TEST_FRAME_RECORDS"):  # a frame the agreed length outgrows, like a full HipSlabBackend frame
+                words = int(os.environ["SPHMI_TEST_FRAME_RECORDS"]) * self.record_words
+                assert t.numel() <= words, "the message itself must fit its frame"
+            f = self.torch.zeros(1 + words, dtype=self.torch.int32)
             f[0] = t.numel()
             f[1:1 + t.numel()] = t
             frames.append(f)
@@ -174,6 +182,20 @@ class OracleSlabBackend:
         return self.gid[self.owned], self.pos[self.owned], self.vel[self.owned]
 
 
+class RecordingDist:
+    """torch.distributed, noting (0 send / 1 receive, peer, words) of every point-to-point operation that is posted."""
+
+    def __init__(self, dist):
+        self._dist, self.posted = dist, []
+
+    def __getattr__(self, name):
+        return getattr(self._dist, name)
+
+    def P2POp(self, op, tensor, peer):
+        self.posted.append((0 if op is self._dist.isend else 1, peer, int(tensor.numel())))
+        return self._dist.P2POp(op, tensor, peer)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rank", type=int, required=True)
@@ -190,7 +212,9 @@ def main():
     cfg = sc["cfg"]
     n_global = cfg.particleCount
     layers = S.particle_layers(sc["position"], cfg)
-    cuts = S.balanced_cuts(layers, a.world)
+    cuts = S.balanced_cuts(layers, a.world) if not os.environ.get("SPHMI_TEST_CUTS") else \
+        [int(c) for c in os.environ["SPHMI_TEST_CUTS"].split(",")]  # given cuts (slabs thinner than balanced_cuts would make them)
+    assert len(cuts) == a.world + 1
     slab = S.make_slab(cuts, a.rank, a.world, n_global)
     idx = S.local_indices(layers, slab)
     pos, vel = sc["position"][idx], sc["velocity"][idx]
@@ -202,7 +226,8 @@ def main():
     if os.environ.get("SPHMI_TEST_BOUND_WORDS"):  # force the "payload outgrew its bound" path: tiny agreed bounds
         words = int(os.environ["SPHMI_TEST_BOUND_WORDS"])
         S.SlabDecomposition.next_bound = staticmethod(lambda n: words)
-    dd = S.SlabDecomposition(backend, a.rank, a.world, dist, comm_device="cpu")  # gloo: messages staged through host
+    rdist = RecordingDist(dist)
+    dd = S.SlabDecomposition(backend, a.rank, a.world, rdist, comm_device="cpu")  # gloo: messages staged through host
     counts = []
     for it in range(a.steps):
         n = dd.step(it)
@@ -212,7 +237,9 @@ def main():
     first_owner = np.searchsorted(np.array(cuts[1:-1]), layers, side="right")  # rank that owned each particle at the start
     np.savez(os.path.join(a.out, "rank%d.npz" % a.rank), gid=gid, pos=p, vel=v, counts=np.array(counts),
              cuts=np.array(cuts), sent=dd.bytes_sent, transfers=dd.transfers, record_words=dd.rec, asynchronous=dd._can_run_async(),
-             adopted=int((first_owner[gid.astype(np.int64)] != a.rank).sum()))  # owned now, owned by another rank at the start
+             adopted=int((first_owner[gid.astype(np.int64)] != a.rank).sum()),  # owned now, owned by another rank at the start
+             posted=np.array(rdist.posted, np.int64).reshape(-1, 3),
+             message_words=np.array(getattr(backend, "message_words", []), np.int64).reshape(-1, 2))  # (down, up) per framed pack
     dist.barrier()
     dist.destroy_process_group()
 

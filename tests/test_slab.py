@@ -27,13 +27,19 @@ def free_port():
         return s.getsockname()[1]
 
 
-def run_ranks(backend, world, out, steps=STEPS, env=None):
+def run_ranks(backend, world, out, steps=STEPS, env=None, timeout=600):
     port = free_port()
     procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "slab_worker.py"), "--rank", str(r), "--world", str(world),
                                "--port", str(port), "--backend", backend, "--steps", str(steps), "--out", str(out)],
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                               env=dict(os.environ, **(env or {}))) for r in range(world)]
-    outs = [p.communicate(timeout=600)[0] for p in procs]
+    try:
+        outs = [p.communicate(timeout=timeout)[0] for p in procs]
+    except subprocess.TimeoutExpired:  # ranks stuck in a transfer that never completes: a failure, not a stuck suite
+        for p in procs:
+            p.kill()
+        tails = [p.communicate()[0][-1500:] for p in procs]
+        pytest.fail("slab ranks did not finish within %d s:\n%s" % (timeout, "\n---\n".join(tails)))
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     return [np.load(os.path.join(out, "rank%d.npz" % r)) for r in range(world)]
