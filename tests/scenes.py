@@ -357,6 +357,22 @@ def certainly_wide_rows(canon, cfg, N):
     return cand[few]
 
 
+def corrupt_rows(ids, which, kind):
+    """A copy of the neighbour ids int[N, 32] with the rows of the sorted ids `which` read wrongly, for asking a restatement what a
+    wrong reader of those rows would change: "empty": every entry -1 (the reader finds nothing); "shift": every entry >= 0
+    replaced by min(id + 1, N - 1) (an off-by-one decode). The stored distances stay as they are."""
+    out = np.array(ids, copy=True).reshape(-1, 32)
+    rows = out[which]
+    if kind == "empty":
+        rows[:] = -1
+    elif kind == "shift":
+        rows[:] = np.where(rows >= 0, np.minimum(rows + 1, out.shape[0] - 1), rows)
+    else:
+        raise ValueError("corrupt_rows: kind is 'empty' or 'shift'")
+    out[which] = rows
+    return out
+
+
 # name -> builder. Sizes chosen so that the C oracle finishes 10 steps in well under a second.
 SCENES = {
     "tiny": lambda: liquid_box((8.0, 8.0, 8.0), (12, 10, 12)),
