@@ -554,11 +554,15 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1)));
   RUN(SPH_ST_DENSITY, sphk_density(s, layersFor(1)));
   if (slab) RUN(SPH_ST_FORCES, sphk_ghost_init(s));
-  RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0)));
+  // Outside slab mode the forces kernel is also the first predictDensity: every neighbour's iteration-0 predicted position follows
+  // from the (x, v) it gathers anyway. (In slab mode the forces run on fewer layers than that predictDensity.)
+  const bool densityInForces = !slab && M >= 1;
+  RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0), densityInForces));
   if (s->d.hasElastic) RUN(SPH_ST_ELASTIC, sphk_elastic(s));
   for (int iter = 0; iter < M; iter++) {
     const int left = M - 1 - iter;  // iterations after this one
-    RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0));
+    if (iter > 0 || !densityInForces) RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0));
+    else RUN(SPH_ST_PREDICT_DENSITY, SPH_OK);  // the stage ran inside the forces kernel: counted (M per step, as ever), an empty interval
     if (left > 0 || !tail) { RUN(SPH_ST_PRESSURE_FORCE, sphk_pressure_force(s, left == 0 ? 2 : 1, layersFor(2 * left))); continue; }
     // ---- overlapped tail. A particle that ends the step within W layers of a cut started it within W + 1 layers (particles
     // move less than one layer per step — the same assumption the ghost depth rests on), so integrating the W + 1 owned

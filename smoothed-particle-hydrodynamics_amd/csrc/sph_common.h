@@ -286,7 +286,7 @@ int sphk_clear_neighbors(sph_solver* s);
 int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1);
 // sph_pcisph.hip
 int sphk_density(sph_solver* s, int ghostDepth = -1);
-int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth = -1);
+int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth = -1, bool fuseDensity = false);  // fuseDensity: + the first predictDensity
 int sphk_ghost_init(sph_solver* s);  // what K7 does besides the acceleration, for every particle (slab mode)
 int sphk_predict_positions(sph_solver* s);
 int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth = -1, bool first = false);  // first: fused step, iteration 0

@@ -178,13 +178,23 @@ int sphk_predict_positions(sph_solver* s) {
 }
 
 // ------------------------------------------------------------------ K7 pcisph_computeForcesAndInitPressure (sphFluid.cl:589-708)
-template <bool FUSE_PREDICT>
+__device__ __forceinline__ float corrected_pressure(const SphDev& d, float p, float rhoPred);  // (K11, below)
+
+// FUSE_DENSITY (fused step outside slab mode; needs FUSE_PREDICT): the kernel is also iteration 0 of K10 + K11. The pressure
+// acceleration is still zero there, so a neighbour's predicted position follows from the (x_j, v_j) this kernel gathers anyway:
+// it is formed again in registers by the same predict_position() call that wrote predPos, and the density sum runs over the
+// same 32 slots in the same order with k_predict_density's expressions. That launch then neither streams the id rows a second
+// time nor gathers 32 predicted positions per particle. Boundary particles have a predicted density too (the pressure force
+// gathers their (rho*, p)), so they run the loop here and leave without the force half's stores.
+template <bool FUSE_PREDICT, bool FUSE_DENSITY>
 __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) {  // <= 128 VGPRs: four waves per SIMD
+  static_assert(FUSE_PREDICT || !FUSE_DENSITY, "the density half reads what the predict half forms");
   int id;
   if (!xcd_range_id(d, id)) return;
   const float4 xi = d.sortedPos[id];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE) {
+  const bool boundary = TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE;
+  if (!FUSE_DENSITY && boundary) {
     d.acc[id] = zero;
     if (FUSE_PREDICT) store_pred(d, id, xi);
     else { d.accP[id] = zero; d.rp[id].y = 0.f; }  // (fused step: nobody reads either before the next kernel overwrites it)
@@ -192,6 +202,9 @@ __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) 
   }
   const float4 vi = d.sortedVel[id];
   const NbrTile t(d, id);
+  float4 xpi = xi;  // FUSE_DENSITY: the particle's own iteration-0 predicted position (a boundary particle's is its position)
+  if (FUSE_DENSITY) xpi = predict_position(d, xi, vi, zero);
+  double density = 0.0;
   float sx = 0.f, sy = 0.f, sz = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
   uint32_t bnd = 0u, ela = 0u;  // which neighbour slots hold boundary / elastic particles: saves integrate and the
                                 // membrane kernel 32 type gathers per particle
@@ -241,7 +254,23 @@ __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) 
       tx = use ? tx + d.surfTens * (xi.x - xj[k].x) : tx;
       ty = use ? ty + d.surfTens * (xi.y - xj[k].y) : ty;
       tz = use ? tz + d.surfTens * (xi.z - xj[k].z) : tz;
+      if (FUSE_DENSITY) {  // k_predict_density's term, on the neighbour's predicted position formed here
+        const float4 xpj = predict_position(d, xj[k], vr[k], zero);
+        const float rx = xpi.x - xpj.x, ry = xpi.y - xpj.y, rz = xpi.z - xpj.z;
+        const float r2 = (rx * rx + ry * ry + rz * rz) * d.simScale * d.simScale;
+        const float a = d.hs2 - r2;
+        const float term = (valid && r2 < d.hs2) ? a * a * a : 0.f;
+        density += (double)term;
+      }
     }
+  }
+  if (FUSE_DENSITY) {
+    if (density < (double)d.hs6) density = (double)d.hs6;
+    density *= d.massWpoly6;
+    const float rhoP = (float)density;
+    d.rp[id] = make_float2(rhoP, corrected_pressure(d, 0.f, rhoP));
+    store_pred(d, id, xpi);
+    if (boundary) { d.acc[id] = zero; return; }
   }
   d.bndMask[id] = bnd;
   if (d.hasElastic) d.elasticMask[id] = ela;
@@ -252,6 +281,7 @@ __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) 
   a.z = sz * scale + d.gravz + tz;
   a.w = 0.f;  // acceleration.w is never read (integrate zeroes it, sphFluid.cl:1721)
   d.acc[id] = a;
+  if (FUSE_DENSITY) return;  // (predPos and rp are written above)
   // The staged API needs pressure = 0 and a zero pressure acceleration in memory; in the fused step the first predictDensity
   // starts from p = 0 by itself and the pressure acceleration is not read before the last pressure-force kernel writes it.
   if (FUSE_PREDICT) store_pred(d, id, predict_position(d, xi, vi, zero));
@@ -287,12 +317,15 @@ int sphk_ghost_init(sph_solver* s) {
   return SPH_OK;
 }
 
-int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth) {
+// fuseDensity: the launch is also the first predictDensity + correctPressure of the fused step (every particle, so not in slab mode)
+int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth, bool fuseDensity) {
+  if (fuseDensity && (!fusePredict || s->hasSlab)) { sph_set_error("sphk_forces: the density half needs the fused step outside slab mode"); return SPH_ERR_INVALID; }
   const int nb = sph_blocks(s->d.N);
   const SphDev d = sph_ranged(s, ghostDepth);
   hipLaunchKernelGGL(k_pack_gather_records, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d);
-  if (fusePredict) hipLaunchKernelGGL((k_forces<true>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
-  else hipLaunchKernelGGL((k_forces<false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
+  if (fuseDensity) hipLaunchKernelGGL((k_forces<true, true>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
+  else if (fusePredict) hipLaunchKernelGGL((k_forces<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
+  else hipLaunchKernelGGL((k_forces<false, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
