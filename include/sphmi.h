@@ -776,6 +776,11 @@ int sph_get_stage_times(sph_solver* s, double* ms_total, int64_t* launches, int 
 int sph_reset_stage_times(sph_solver* s);
 /* Radix passes (8- or 9-bit digits) the sort of sph_step() takes for this solver: 24 algorithmic bytes per particle each. */
 int sph_step_sort_passes(sph_solver* s);
+/* sph_step() outside slab mode and with stage timing off can run the density pass and the forces kernel's record pack of one
+ * range of sorted particles while findNeighbors works on the next range. chunks = 0 (the default): the solver
+ * decides by its particle count; 1: never; 2 .. 16: that many ranges, whatever the particle count. Results do not depend on it:
+ * every particle is computed from the same inputs by the same code whichever launch serves it. */
+int sph_set_step_chunks(sph_solver* s, int32_t chunks);
 
 /* ---- Spatial decomposition (no reference counterpart: the reference is single-device) -----------------
  * The global box is cut into z-slabs of whole cell layers, one solver (one GPU, one process) per slab. A solver holds the

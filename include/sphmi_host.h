@@ -86,6 +86,10 @@ int sphmi_trajectory_membranes(const char* dir, int numOfMembranes, int32_t* mem
  * 96 values for step t, entries 96..muscleCount-1 left 0. */
 int sphmi_muscle_signal(int step, float* out, int muscleCount);
 
+/* The ranges of sorted particles that the overlapped step of sph_step() launches findNeighbors, density and the record pack by
+ * (sphmi_chunks.h): edges[0 .. chunks] with chunk c = [edges[c], edges[c + 1]). n >= 0, chunks >= 1. */
+int sphmi_step_chunk_edges(int64_t n, int32_t chunks, int64_t* edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,11 @@ sph_solver::~sph_solver() {
   if (evReadReady) hipEventDestroy(evReadReady);
   if (evCopyDone) hipEventDestroy(evCopyDone);
   if (copyStream) hipStreamDestroy(copyStream);
+  for (hipEvent_t e : evChunk) if (e) hipEventDestroy(e);
+  if (evChunkJoin) hipEventDestroy(evChunkJoin);
+  if (chunkStream) hipStreamDestroy(chunkStream);
+  if (evSearchFork) hipEventDestroy(evSearchFork);
+  if (searchStream) hipStreamDestroy(searchStream);
   if (slabMsgEvent) hipEventDestroy(slabMsgEvent);
   if (slabRebuildEvent) hipEventDestroy(slabRebuildEvent);
   if (ownStream && stream) hipStreamDestroy(stream);
@@ -218,6 +223,8 @@ extern "C" int sph_destroy(sph_solver* s) {
   hipSetDevice(s->cfg.device);
   if (s->stream) hipStreamSynchronize(s->stream);
   if (s->copyStream) hipStreamSynchronize(s->copyStream);
+  if (s->searchStream) hipStreamSynchronize(s->searchStream);  // (both idle already: every step joins them into s->stream)
+  if (s->chunkStream) hipStreamSynchronize(s->chunkStream);
   release_pending(s, false);
   delete s;
   return SPH_OK;
@@ -344,6 +351,12 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
     if (e != hipSuccess) { sph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); return SPH_ERR_HIP; }
     s->ownStream = true;
   }
+  // the overlapped step's streams and events; like the copy stream, never the caller's
+  SPH_HIP(hipStreamCreateWithFlags(&s->chunkStream, hipStreamNonBlocking));
+  SPH_HIP(hipStreamCreateWithFlags(&s->searchStream, hipStreamNonBlocking));
+  SPH_HIP(hipEventCreateWithFlags(&s->evSearchFork, hipEventDisableTiming));
+  for (hipEvent_t& e : s->evChunk) SPH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  SPH_HIP(hipEventCreateWithFlags(&s->evChunkJoin, hipEventDisableTiming));
   SphDev& d = s->d;
   d.N = N; d.G = cfg->gridCellCount; d.gx = cfg->gridCellsX; d.gy = cfg->gridCellsY; d.gz = cfg->gridCellsZ;
   d.cellMask = cfg->cellIdMask;
@@ -396,7 +409,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   A(d.rho, n);
   A(s->blockHist, (size_t)SPH_SORT_MAX_DIGITS * s->maxSortBlocks + SPH_SORT_MAX_DIGITS);  // block histograms + digit totals
   A(d.gid, n); A(d.owned, n); A(s->slabCounts, SPH_SLAB_COUNT_WORDS);
-  A(d.dbg, SPH_DBG_WORDS);
+  A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1);
   float* binU = nullptr;
   A(binU, 64);
   d.binU = binU;
@@ -513,6 +526,75 @@ extern "C" int sph_run_compute_interaction_with_membranes(sph_solver* s) {
 }
 extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s) { return run_stage(s, kMembranesFinalize); }
 
+// ---- the overlapped search. findNeighbors is bound by vector ALU issue and leaves HBM nearly idle; the density
+// pass and the record pack that follow it are pure HBM streams over the particle's own rows and records. So the sorted particles
+// are cut into chunks. findNeighbors(c) runs on s->stream (even c) or searchStream (odd c): the chunks do not depend on each
+// other, and with two streams the tail of one launch — workgroups of the last wave of tiles running on a half-empty GPU — is
+// filled by the next. density(c) and pack(c) run on chunkStream behind the event of findNeighbors(c), under the launches of the
+// later chunks. Results do not depend on the chunk count: every kernel computes a particle from the same inputs whichever launch
+// serves it.
+// The chunk count the fused step takes when sph_set_step_chunks left it automatic, and the particle count from which it does
+// (both measured, profiles/r23/README.md).
+#ifndef SPH_OVERLAP_CHUNKS
+#define SPH_OVERLAP_CHUNKS 16
+#endif
+#ifndef SPH_OVERLAP_MIN_PARTICLES
+#define SPH_OVERLAP_MIN_PARTICLES (4 << 20)
+#endif
+static_assert(SPH_OVERLAP_CHUNKS >= 1 && SPH_OVERLAP_CHUNKS <= SPH_STEP_CHUNKS_MAX, "chunk count");
+
+extern "C" int sph_set_step_chunks(sph_solver* s, int32_t chunks) {
+  ENTER(s);
+  if (chunks < 0 || chunks > SPH_STEP_CHUNKS_MAX) { sph_set_error("sph_set_step_chunks: %d is not in [0, %d]", chunks, SPH_STEP_CHUNKS_MAX); return SPH_ERR_INVALID; }
+  s->stepChunks = chunks;
+  return SPH_OK;
+}
+
+// 1: the serial search. Slab mode launches by ghost layers; with stage timing on, the step stays the sequence of stages that
+// stages_ms and the density roofline describe.
+static int step_chunks(const sph_solver* s) {
+  if (s->hasSlab || s->timing) return 1;
+  if (s->stepChunks > 0) return s->stepChunks;
+  return s->d.N >= SPH_OVERLAP_MIN_PARTICLES ? SPH_OVERLAP_CHUNKS : 1;
+}
+
+struct ChunkEdges { uint32_t e[SPH_STEP_CHUNKS_MAX + 1]; };  // (a kernel argument: no host buffer has to outlive the call)
+__global__ void k_chunk_edges(uint32_t* edges, ChunkEdges v) {
+  if (threadIdx.x <= SPH_STEP_CHUNKS_MAX) edges[threadIdx.x] = v.e[threadIdx.x];
+}
+
+static int enqueue_search_overlapped(sph_solver* s, int chunks) {
+  const int N = s->d.N;
+  if (s->chunkEdgesN != N || s->chunkEdgesC != chunks) {  // the partition on the device, for sphk_density_chunk
+    ChunkEdges v;
+    for (int i = 0; i <= SPH_STEP_CHUNKS_MAX; i++) v.e[i] = (uint32_t)sphChunkEdge(N, chunks, i);
+    hipLaunchKernelGGL(k_chunk_edges, dim3(1), dim3(64), 0, s->stream, s->chunkEdges, v);
+    SPH_HIP(hipGetLastError());
+    s->chunkEdgesN = N; s->chunkEdgesC = chunks;
+  }
+  // searchStream starts where s->stream stands now: behind the sort and the cell table
+  SPH_HIP(hipEventRecord(s->evSearchFork, s->stream));
+  SPH_HIP(hipStreamWaitEvent(s->searchStream, s->evSearchFork, 0));
+  auto chunk = [s, N, chunks](int c) -> int {
+    const int lo = (int)sphChunkEdge(N, chunks, c), hi = (int)sphChunkEdge(N, chunks, c + 1);
+    if (hi <= lo) return SPH_OK;  // more chunks than blocks of 256 particles
+    hipStream_t fnStream = (c & 1) ? s->searchStream : s->stream;
+    int rc = sphk_find_neighbors(s, -1, lo, hi, fnStream);
+    if (rc != SPH_OK) return rc;
+    SPH_HIP(hipEventRecord(s->evChunk[c], fnStream));
+    SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evChunk[c], 0));
+    rc = sphk_density_chunk(s, c, lo, hi, s->chunkStream);
+    return rc != SPH_OK ? rc : sphk_pack_gather_records(s, lo, hi, s->chunkStream);
+  };
+  int rc = SPH_OK;
+  for (int c = 0; c < chunks && rc == SPH_OK; c++) rc = chunk(c);
+  // The join, on the device, also after a failed launch. Every findNeighbors launch, on either stream, has a density launch behind
+  // it on chunkStream, so chunkStream's last event covers searchStream too.
+  SPH_HIP(hipEventRecord(s->evChunkJoin, s->chunkStream));
+  SPH_HIP(hipStreamWaitEvent(s->stream, s->evChunkJoin, 0));
+  return rc;
+}
+
 // The fused fast path. Stage sequence of simulationStep() (owPhysicsFluidSimulator.cpp:88-113) with:
 //   clearBuffers folded into findNeighbors; sortPostPass + indexx + index fix-up in one kernel;
 //   predictPositions folded into the kernel that produces the pressure acceleration it integrates
@@ -551,13 +633,19 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   const bool slab = s->hasSlab;
   const int M = s->cfg.maxIteration;
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
-  RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1)));
-  RUN(SPH_ST_DENSITY, sphk_density(s, layersFor(1)));
+  const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
+  if (chunks > 1) {
+    rc = enqueue_search_overlapped(s, chunks);
+    if (rc != SPH_OK) return rc;
+  } else {
+    RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1)));
+    RUN(SPH_ST_DENSITY, sphk_density(s, layersFor(1)));
+  }
   if (slab) RUN(SPH_ST_FORCES, sphk_ghost_init(s));
   // Outside slab mode the forces kernel is also the first predictDensity: every neighbour's iteration-0 predicted position follows
   // from the (x, v) it gathers anyway. (In slab mode the forces run on fewer layers than that predictDensity.)
   const bool densityInForces = !slab && M >= 1;
-  RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0), densityInForces));
+  RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0), densityInForces, chunks <= 1));  // (the chunks packed their records)
   if (s->d.hasElastic) RUN(SPH_ST_ELASTIC, sphk_elastic(s));
   for (int iter = 0; iter < M; iter++) {
     const int left = M - 1 - iter;  // iterations after this one

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "sphmi.h"
+#include "sphmi_chunks.h"
 
 #define SPH_BLOCK 256
 #define SPH_TILE 64
@@ -27,6 +28,8 @@
 #define SPH_DBG_WORDS 32  // diagnostic counters (SphDev::dbg)
 #define SPH_SLAB_COUNT_WORDS 24
 #define SPH_SORT_MAX_DIGITS 512   // radix digits per pass: 256 (8 bits) or 512 (9 bits)
+#define SPH_STEP_CHUNKS_MAX 16    // most chunks the overlapped step takes (sph_set_step_chunks)
+static_assert(SPH_CHUNK_ALIGN == SPH_BLOCK, "chunk edges are launch-block edges of the density and pack passes");
 
 struct SphDev {  // what the kernels see; passed by value
   int N, G;
@@ -136,6 +139,15 @@ struct sph_solver {
   // asynchronous position read-back (sph_read_position_async): a copy stream of its own, ordered against s->stream by events
   hipStream_t copyStream = nullptr;
   hipEvent_t evReadReady = nullptr, evCopyDone = nullptr;  // positions final on s->stream / copy landed on the host
+  // overlapped step (sph_api.hip): the findNeighbors launches of the chunks of sorted particles alternate between
+  // s->stream and searchStream (which starts behind evSearchFork, recorded on s->stream); density and the record pack of chunk c
+  // run on chunkStream behind evChunk[c]; s->stream waits for evChunkJoin before the forces kernel, so nothing is pending on either
+  // stream when enqueue_step returns. Created by sph_create, destroyed with the solver.
+  hipStream_t chunkStream = nullptr, searchStream = nullptr;
+  hipEvent_t evChunk[SPH_STEP_CHUNKS_MAX] = {}, evChunkJoin = nullptr, evSearchFork = nullptr;
+  int stepChunks = 0;                  // sph_set_step_chunks: 0 = automatic, 1 = serial, else that many chunks
+  uint32_t* chunkEdges = nullptr;      // device, SPH_STEP_CHUNKS_MAX + 1 words: the partition chunkEdgesN / chunkEdgesC was made for
+  int chunkEdgesN = -1, chunkEdgesC = -1;
   bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
   float* copyUserDst = nullptr;        // where the caller wants the data
   void* copyStage = nullptr; size_t copyStageBytes = 0;  // pinned staging, only for destinations that cannot be page-locked in place
@@ -283,10 +295,17 @@ int sphk_sort_post_and_index(sph_solver* s);  // fused K3 + K4 + H2
 int sphk_hash_sort_post_slab(sph_solver* s);  // slab mode: K2 + sort + K3 with compacted sort keys (2 radix passes)
 // sph_neighbors.hip
 int sphk_clear_neighbors(sph_solver* s);
-int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1);
+// [idxLo, idxHi): the sorted particles of the launch, intersected with the cell range that ghostDepth gives; the grid covers
+// min(idxHi, N) - idxLo particles. On `stream` (nullptr: s->stream).
+int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1, int idxLo = 0, int idxHi = INT32_MAX, hipStream_t stream = nullptr);
 // sph_pcisph.hip
 int sphk_density(sph_solver* s, int ghostDepth = -1);
-int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth = -1, bool fuseDensity = false);  // fuseDensity: + the first predictDensity
+// density and the record pack of chunk c of the partition that enqueue_search_overlapped (sph_api.hip) keeps in s->chunkEdges
+// (sphChunkEdge, sphmi_chunks.h), on `stream`
+int sphk_density_chunk(sph_solver* s, int c, int idxLo, int idxHi, hipStream_t stream);
+int sphk_pack_gather_records(sph_solver* s, int idxLo, int idxHi, hipStream_t stream);
+// packRecords: launch the record pack over all particles first (false: the caller has packed them, sphk_pack_gather_records)
+int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth = -1, bool fuseDensity = false, bool packRecords = true);  // fuseDensity: + the first predictDensity
 int sphk_ghost_init(sph_solver* s);  // what K7 does besides the acceleration, for every particle (slab mode)
 int sphk_predict_positions(sph_solver* s);
 int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth = -1, bool first = false);  // first: fused step, iteration 0

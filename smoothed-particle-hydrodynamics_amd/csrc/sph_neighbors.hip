@@ -51,6 +51,7 @@ int sphk_clear_neighbors(sph_solver* s) {
 // `__restrict__` kernel arguments so that loads with a workgroup-uniform address become scalar loads.
 struct FnParams {
   int G, gx, gy, rangeLo, rangeHi;
+  int idxLo, idxHi;  // the launch serves the sorted particles [idxLo, idxHi) of that cell range (a chunk of the overlapped step)
   float h, cellSize, cellSizeInv, simScale, xmin, ymin, zmin;
 };
 struct FnArrays {  // (what the exact walk needs; built inside the kernel from its arguments)
@@ -238,7 +239,8 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   FnShared& sh = *reinterpret_cast<FnShared*>(fn_smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = tid >> 1, laneB = tid & 1;  // the particle; 0: its lane A, 1: its lane B
-  const int rangeBegin = (int)cellStart[d.rangeLo], rangeEnd = (int)cellStart[d.rangeHi];  // all particles, or fewer ghost layers
+  // all particles, or fewer ghost layers; of those, the launch's chunk (idxLo is a multiple of SPH_BLOCK, so map tiles stay whole)
+  const int rangeBegin = max((int)cellStart[d.rangeLo], d.idxLo), rangeEnd = min((int)cellStart[d.rangeHi], d.idxHi);
   // (an XCD-aware tile order — each XCD one contiguous eighth of the tiles — was measured: 0.441 vs 0.430 ms on config #2, no change at 16.5 M)
   const int p0 = rangeBegin + blockIdx.x * FN_PART;
   if (p0 >= rangeEnd) return;  // uniform
@@ -734,16 +736,20 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
 #ifdef FN_STAMPS
   __syncthreads();
   if (tid < 16) atomicAdd(&dbg[16 + tid], sh.stamps[tid] >> 6);
-  if (tid == 0) {  // residency trace: when and where this workgroup ran
-    trace[4 * blockIdx.x + 0] = (uint32_t)wgStart_;
-    trace[4 * blockIdx.x + 1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    trace[4 * blockIdx.x + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID
-    trace[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
+  if (tid == 0) {  // residency trace: when and where this workgroup ran (row = the workgroup's tile among those of all chunk launches)
+    const size_t row = 4 * ((size_t)(d.idxLo / FN_PART) + blockIdx.x);
+    trace[row + 0] = (uint32_t)wgStart_;
+    trace[row + 1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+    trace[row + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID
+    trace[row + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
   }
 #endif
 }
 
-int sphk_find_neighbors(sph_solver* s, int ghostDepth) {
+int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hipStream_t stream) {
+  if (idxLo < 0 || idxLo % SPH_BLOCK != 0) { sph_set_error("sphk_find_neighbors: idxLo %d is not a multiple of %d", idxLo, SPH_BLOCK); return SPH_ERR_INVALID; }
+  idxHi = min(idxHi, s->d.N);
+  if (idxHi <= idxLo) return SPH_OK;  // an empty range: no launch
   {  // opt in to > 64 KB of dynamic LDS once per DEVICE (the attribute lives on the device's function object)
     static std::mutex mu;
     static bool attrSet[64] = {};
@@ -757,9 +763,10 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth) {
   const SphDev r = sph_ranged(s, ghostDepth);
   FnParams a;
   a.G = r.G; a.gx = r.gx; a.gy = r.gy; a.rangeLo = r.rangeLo; a.rangeHi = r.rangeHi;
+  a.idxLo = idxLo; a.idxHi = idxHi;
   a.h = r.h; a.cellSize = r.cellSize; a.cellSizeInv = r.cellSizeInv; a.simScale = r.simScale;
   a.xmin = r.xmin; a.ymin = r.ymin; a.zmin = r.zmin;
-  hipLaunchKernelGGL(k_find_neighbors, dim3(sph_blocks(s->d.N, FN_PART)), dim3(FN_THREADS), sizeof(FnShared), s->stream, a,
+  hipLaunchKernelGGL(k_find_neighbors, dim3(sph_blocks(idxHi - idxLo, FN_PART)), dim3(FN_THREADS), sizeof(FnShared), stream ? stream : s->stream, a,
                      (const float4*)r.sortedPos, (const uint32_t*)r.keys, (const uint32_t*)r.cellStart, r.binU, r.nbrId, r.nbrDist, r.nbr16,
                      r.nbrBase, r.dbg,
                      r.valsAlt /* idle between the sort and the next step's sort */);

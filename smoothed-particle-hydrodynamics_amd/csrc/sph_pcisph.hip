@@ -294,9 +294,10 @@ __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) 
 // 1.54 ms; everything in one line 1.22 ms + this pack pass (68 B per particle, 0.2 ms). A wave's gather instruction costs by
 // the number of different lines it touches. Kept out of k_density so that the roofline-graded pass moves exactly its 132 B.
 
-__global__ __launch_bounds__(SPH_BLOCK) void k_pack_gather_records(SphDev d) {
-  const int id = blockIdx.x * SPH_BLOCK + threadIdx.x;
-  if (id >= d.N) return;
+// The launch packs the sorted particles [lo, hi); lo is a multiple of four, so record groups stay whole.
+__global__ __launch_bounds__(SPH_BLOCK) void k_pack_gather_records(SphDev d, int lo, int hi) {
+  const int id = lo + blockIdx.x * SPH_BLOCK + threadIdx.x;
+  if (id >= hi) return;
   const float4 v = d.sortedVel[id];
   d.gatherRec[rec_index(id, 0)] = d.sortedPos[id];
   d.gatherRec[rec_index(id, 1)] = make_float4(v.x, v.y, v.z, d.rho[id]);
@@ -317,12 +318,40 @@ int sphk_ghost_init(sph_solver* s) {
   return SPH_OK;
 }
 
+int sphk_pack_gather_records(sph_solver* s, int idxLo, int idxHi, hipStream_t stream) {
+  if (idxLo < 0 || idxLo % 4 != 0) { sph_set_error("sphk_pack_gather_records: idxLo %d is not a multiple of 4", idxLo); return SPH_ERR_INVALID; }
+  idxHi = min(idxHi, s->d.N);
+  if (idxHi <= idxLo) return SPH_OK;
+  hipLaunchKernelGGL(k_pack_gather_records, dim3(sph_blocks(idxHi - idxLo)), dim3(SPH_BLOCK), 0, stream, s->d, idxLo, idxHi);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
+// The density pass of chunk c = [idxLo, idxHi) of the partition that s->chunkEdges holds on the device. k_density takes its range
+// as two entries of a table it calls the cell table; here that table is the chunk partition and the "cells" are c and c + 1, so
+// the roofline-graded kernel runs unchanged (it reads nothing else of the cell table) and its grid covers the chunk alone.
+// INVARIANT this rests on: k_density and the NbrTile constructor read of d.cellStart exactly cellStart[rangeLo] and
+// cellStart[rangeHi]. A change that makes either read the cell table for anything else must give this launcher a kernel of its
+// own (tests/test_step_overlap.py compares the chunked density with the oracle's and would fail). The trade: the source text
+// that bench.py's density_sources_sha() hashes stays as it was, so a PMC traffic figure taken on k_density describes the
+// kernel of both paths, at the price of a one-block launch per change of (N, chunk count) and 17 device words.
+int sphk_density_chunk(sph_solver* s, int c, int idxLo, int idxHi, hipStream_t stream) {
+  if (c < 0 || c >= SPH_STEP_CHUNKS_MAX || idxLo < 0 || idxHi > s->d.N) { sph_set_error("sphk_density_chunk: chunk %d [%d, %d) of %d particles", c, idxLo, idxHi, s->d.N); return SPH_ERR_INVALID; }
+  if (idxHi <= idxLo) return SPH_OK;
+  SphDev d = s->d;
+  d.cellStart = s->chunkEdges; d.rangeLo = c; d.rangeHi = c + 1;
+  const int nb = sph_blocks(idxHi - idxLo, SPH_BLOCK * DENSITY_ITEMS);
+  hipLaunchKernelGGL(k_density, dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
 // fuseDensity: the launch is also the first predictDensity + correctPressure of the fused step (every particle, so not in slab mode)
-int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth, bool fuseDensity) {
+int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth, bool fuseDensity, bool packRecords) {
   if (fuseDensity && (!fusePredict || s->hasSlab)) { sph_set_error("sphk_forces: the density half needs the fused step outside slab mode"); return SPH_ERR_INVALID; }
   const int nb = sph_blocks(s->d.N);
   const SphDev d = sph_ranged(s, ghostDepth);
-  hipLaunchKernelGGL(k_pack_gather_records, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d);
+  if (packRecords) { const int rc = sphk_pack_gather_records(s, 0, s->d.N, s->stream); if (rc != SPH_OK) return rc; }
   if (fuseDensity) hipLaunchKernelGGL((k_forces<true, true>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   else if (fusePredict) hipLaunchKernelGGL((k_forces<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   else hipLaunchKernelGGL((k_forces<false, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);

@@ -2,6 +2,7 @@
 // Every function cites the reference lines whose behaviour it reproduces. Build with g++ -O2 -ffp-contract=off:
 // the constants below depend on IEEE gradual underflow and on float-typed sub-expressions.
 #include "sphmi_host.h"
+#include "sphmi_chunks.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -444,6 +445,12 @@ int sphmi_muscle_signal(int step, float* out, int muscleCount) {
   }
   // main_sim.py:49-52: [W1, W2, W2, W1]
   memcpy(out, w1, sizeof(w1)); memcpy(out + 24, w2, sizeof(w2)); memcpy(out + 48, w2, sizeof(w2)); memcpy(out + 72, w1, sizeof(w1));
+  return SPH_OK;
+}
+
+int sphmi_step_chunk_edges(int64_t n, int32_t chunks, int64_t* edges) {
+  if (!edges || n < 0 || chunks < 1) return SPH_ERR_INVALID;
+  for (int32_t i = 0; i <= chunks; i++) edges[i] = sphChunkEdge(n, chunks, i);
   return SPH_OK;
 }
 

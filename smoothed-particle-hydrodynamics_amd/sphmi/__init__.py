@@ -117,6 +117,7 @@ def host_lib():
         L.sphmi_box_layer_histogram.argtypes = _box + [C.c_void_p, C.c_int]
         L.sphmi_generate_box_slice.argtypes = _box + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.sphmi_muscle_signal.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.sphmi_step_chunk_edges.argtypes = [C.c_int64, C.c_int32, C.c_void_p]
         L.sphmi_trajectory_info.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 4
         L.sphmi_trajectory_frame.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
         L.sphmi_trajectory_connections.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
@@ -140,7 +141,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_position", "sph_read_velocity", "sph_read_density", "sph_read_particle_index",
                     "sph_read_position_async", "sph_read_position_wait", "sph_host_unregister", "sph_build_info",
                     "sph_read_buffer", "sph_read_neighbor_rows", "sph_synchronize", "sph_set_stage_timing", "sph_get_stage_times",
-                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
+                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
@@ -153,7 +154,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_field_diffuse", "sph_field_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
-                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_save_configuration", "sphmi_worm_counts",
+                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_save_configuration", "sphmi_worm_counts",
                          "sphmi_generate_worm", "sphmi_trajectory_info", "sphmi_trajectory_frame", "sphmi_trajectory_connections",
                          "sphmi_trajectory_membranes"]
 
@@ -212,6 +213,7 @@ def device_lib():
         L.sph_read_buffer.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.sph_read_neighbor_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.sph_set_stage_timing.argtypes = [C.c_void_p, C.c_int]
+        L.sph_set_step_chunks.argtypes = [C.c_void_p, C.c_int32]
         L.sph_get_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
         L.sph_last_error.restype = C.c_char_p
         L.sph_slab_init.argtypes = [C.c_void_p, C.POINTER(SphSlab), C.c_void_p]
@@ -444,6 +446,17 @@ def muscle_signal(step, muscle_count=100):
     rc = host_lib().sphmi_muscle_signal(step, out.ctypes.data, muscle_count)
     if rc:
         raise SphError("sphmi_muscle_signal failed: %d" % rc)
+    return out
+
+
+def step_chunk_edges(n, chunks):
+    """The chunks + 1 edges of the ranges of sorted particles that the overlapped step launches by (host library, no GPU)."""
+    if n < 0 or chunks < 1:
+        raise SphError("step_chunk_edges: n >= 0 and chunks >= 1")
+    out = np.zeros(chunks + 1, np.int64)
+    rc = host_lib().sphmi_step_chunk_edges(n, chunks, out.ctypes.data)
+    if rc:
+        raise SphError("sphmi_step_chunk_edges failed: %d" % rc)
     return out
 
 
@@ -1118,6 +1131,11 @@ class owHIPSolver:
 
     def set_stage_timing(self, enable=True):
         return self._chk(self._L.sph_set_stage_timing(self._h, int(enable)))
+
+    def set_step_chunks(self, chunks=0):
+        """How many ranges of sorted particles step() overlaps density and the record pack with findNeighbors by: 0 automatic
+        (by particle count), 1 never, 2..16 forced (tests use it on small scenes). Results do not depend on the chunk count."""
+        return self._chk(self._L.sph_set_step_chunks(self._h, int(chunks)))
 
     def reset_stage_times(self):
         return self._chk(self._L.sph_reset_stage_times(self._h))
