@@ -781,6 +781,13 @@ int sph_step_sort_passes(sph_solver* s);
  * decides by its particle count; 1: never; 2 .. 16: that many ranges, whatever the particle count. Results do not depend on it:
  * every particle is computed from the same inputs by the same code whichever launch serves it. */
 int sph_set_step_chunks(sph_solver* s, int32_t chunks);
+/* Where that step runs in chunks it can also run the kernels behind the search chunk by chunk on the chunk stream, each stage one
+ * chunk behind the stage before it: the forces kernel, then predicted density and pressure force of every
+ * predict-correct iteration. depth = -1 (the default): the solver's built-in depth; 0: none (every kernel behind the search runs
+ * once over all particles); 1 .. 6: that many stages, clamped to the 2 * maxIteration the step has and to 1 with elastic matter.
+ * A check on the device decides every step whether the chunks are wide enough for it; if not, the same stages run over all
+ * particles behind the search. Results do not depend on it. */
+int sph_set_step_pipeline(sph_solver* s, int32_t depth);
 
 /* ---- Spatial decomposition (no reference counterpart: the reference is single-device) -----------------
  * The global box is cut into z-slabs of whole cell layers, one solver (one GPU, one process) per slab. A solver holds the

@@ -90,6 +90,20 @@ int sphmi_muscle_signal(int step, float* out, int muscleCount);
  * (sphmi_chunks.h): edges[0 .. chunks] with chunk c = [edges[c], edges[c + 1]). n >= 0, chunks >= 1. */
 int sphmi_step_chunk_edges(int64_t n, int32_t chunks, int64_t* edges);
 
+/* The launches of the pipelined step's chunk stream in issue order (sphmi_chunks.h) for `chunks` ranges, a requested
+ * depth 0 .. 6, maxIteration predict-correct iterations and a scene with (1) or without (0) elastic matter: stage[i] (0: density
+ * and record pack; 1: forces; 2j + 1, 2j + 2: predicted density and pressure force of iteration j) and chunk[i], cap entries
+ * each (7 * chunks always suffice). Returns the count, or a negative SPH_ERR_* code. *depthOut (may be NULL): the clamped depth. */
+int sphmi_step_pipeline_schedule(int32_t chunks, int32_t depth, int32_t maxIteration, int32_t hasElastic, int32_t* stage,
+                                 int32_t* chunk, int32_t cap, int32_t* depthOut);
+
+/* The halo check the pipelined step runs on the device every step, restated on the host: 1 if for every chunk c of the partition
+ * edges[0 .. chunks] every particle the search can give a particle of chunk c as a neighbour lies in chunks c - 1 .. c + 1,
+ * judged from the sorted cell ids keys[0 .. n) and the cell table cellStart[0 .. G] of a gx x gy x (G / (gx gy)) grid alone;
+ * 0 if not (the check is conservative, never permissive); a negative SPH_ERR_* code for bad arguments. */
+int sphmi_step_halo_check(const uint32_t* keys, int64_t n, const uint32_t* cellStart, int64_t G, const int64_t* edges, int32_t chunks,
+                          int32_t gx, int32_t gy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -409,7 +409,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   A(d.rho, n);
   A(s->blockHist, (size_t)SPH_SORT_MAX_DIGITS * s->maxSortBlocks + SPH_SORT_MAX_DIGITS);  // block histograms + digit totals
   A(d.gid, n); A(d.owned, n); A(s->slabCounts, SPH_SLAB_COUNT_WORDS);
-  A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1);
+  A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1); A(s->pipeTable, SPH_STEP_CHUNKS_MAX + 3);
   float* binU = nullptr;
   A(binU, 64);
   d.binU = binU;
@@ -542,11 +542,30 @@ extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s
 #define SPH_OVERLAP_MIN_PARTICLES (4 << 20)
 #endif
 static_assert(SPH_OVERLAP_CHUNKS >= 1 && SPH_OVERLAP_CHUNKS <= SPH_STEP_CHUNKS_MAX, "chunk count");
+// ---- the pipelined step. Where the search runs in chunks, the first D of the kernels behind it (forces; then
+// predicted density and pressure force of every iteration) can follow it on chunkStream chunk by chunk, stage k one chunk behind
+// stage k - 1: a stage reads of other particles only what the stage before wrote for direct neighbours, so if the neighbours of
+// chunk c lie in chunks c - 1 .. c + 1 the one in-order stream orders every read after its write and every overwrite after its
+// last read, and no array needs a second copy. k_halo_check tests that premise on the device every step and either way leaves two
+// tables by which each stage runs exactly once per particle: chunk by chunk, or over all particles behind the join.
+// The depth the step takes when sph_set_step_pipeline left it automatic: the forces kernel alone. Deeper pipelines were measured
+// and are slower, the whole loop (6) slower than none (profiles/r24/README.md).
+#ifndef SPH_PIPELINE_DEPTH
+#define SPH_PIPELINE_DEPTH 1
+#endif
+static_assert(SPH_PIPELINE_DEPTH >= 0 && SPH_PIPELINE_DEPTH <= SPH_PIPELINE_STAGES_MAX, "pipeline depth");
 
 extern "C" int sph_set_step_chunks(sph_solver* s, int32_t chunks) {
   ENTER(s);
   if (chunks < 0 || chunks > SPH_STEP_CHUNKS_MAX) { sph_set_error("sph_set_step_chunks: %d is not in [0, %d]", chunks, SPH_STEP_CHUNKS_MAX); return SPH_ERR_INVALID; }
   s->stepChunks = chunks;
+  return SPH_OK;
+}
+
+extern "C" int sph_set_step_pipeline(sph_solver* s, int32_t depth) {
+  ENTER(s);
+  if (depth < -1 || depth > SPH_PIPELINE_STAGES_MAX) { sph_set_error("sph_set_step_pipeline: %d is not in [-1, %d]", depth, SPH_PIPELINE_STAGES_MAX); return SPH_ERR_INVALID; }
+  s->stepPipeline = depth;
   return SPH_OK;
 }
 
@@ -563,21 +582,53 @@ __global__ void k_chunk_edges(uint32_t* edges, ChunkEdges v) {
   if (threadIdx.x <= SPH_STEP_CHUNKS_MAX) edges[threadIdx.x] = v.e[threadIdx.x];
 }
 
-static int enqueue_search_overlapped(sph_solver* s, int chunks) {
+// Stages of the chunked step that follow the search chunk by chunk (0: none; only asked where the search runs in chunks)
+static int step_pipeline(const sph_solver* s) {
+  return sphPipelineDepth(s->stepPipeline >= 0 ? s->stepPipeline : SPH_PIPELINE_DEPTH, s->cfg.maxIteration, s->d.hasElastic ? 1 : 0);
+}
+
+// The halo check of the pipelined step, one lane per chunk (sphChunkHaloOk, sphmi_chunks.h: every table index is clamped there).
+// table: the pipeline table (the edges, or zeros), then the serial table {0, passed ? 0 : N}. dbg[9] counts the steps that took
+// the serial table, dbg[10] those that ran chunk by chunk.
+__global__ void k_halo_check(const uint32_t* keys, const uint32_t* cellStart, int G, int gx, int gy, int N, int chunks, ChunkEdges v,
+                             uint32_t* table, uint32_t* dbg) {
+  const int c = threadIdx.x;  // one wave
+  int ok = 1;
+  if (c < chunks) {
+    const int64_t reach = (int64_t)gx * gy + gx + 1;
+    ok = sphChunkHaloOk(keys, cellStart, G, reach, N, v.e[c], v.e[c + 1], v.e[max(c - 1, 0)], v.e[min(c + 2, chunks)]);
+  }
+  const bool passed = __all(ok);
+  if (c <= SPH_STEP_CHUNKS_MAX) table[c] = passed ? v.e[c] : 0u;
+  if (c == 0) {
+    table[SPH_STEP_CHUNKS_MAX + 1] = 0u;
+    table[SPH_STEP_CHUNKS_MAX + 2] = passed ? 0u : (uint32_t)N;
+    atomicAdd(&dbg[passed ? 10 : 9], 1u);
+  }
+}
+
+// depth: stages 1 .. depth run here as well (clamped by the caller), by the schedule of sphPipelineSchedule.
+static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth) {
   const int N = s->d.N;
+  ChunkEdges v;
+  for (int i = 0; i <= SPH_STEP_CHUNKS_MAX; i++) v.e[i] = (uint32_t)sphChunkEdge(N, chunks, i);
   if (s->chunkEdgesN != N || s->chunkEdgesC != chunks) {  // the partition on the device, for sphk_density_chunk
-    ChunkEdges v;
-    for (int i = 0; i <= SPH_STEP_CHUNKS_MAX; i++) v.e[i] = (uint32_t)sphChunkEdge(N, chunks, i);
     hipLaunchKernelGGL(k_chunk_edges, dim3(1), dim3(64), 0, s->stream, s->chunkEdges, v);
     SPH_HIP(hipGetLastError());
     s->chunkEdgesN = N; s->chunkEdgesC = chunks;
   }
+  if (depth > 0) {  // behind the sort and the cell table, in front of everything that reads the tables
+    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(64), 0, s->stream, s->d.keys, s->d.cellStart, s->d.G, s->d.gx, s->d.gy, N, chunks, v,
+                       s->pipeTable, s->d.dbg);
+    SPH_HIP(hipGetLastError());
+  }
   // searchStream starts where s->stream stands now: behind the sort and the cell table
   SPH_HIP(hipEventRecord(s->evSearchFork, s->stream));
   SPH_HIP(hipStreamWaitEvent(s->searchStream, s->evSearchFork, 0));
-  auto chunk = [s, N, chunks](int c) -> int {
+  auto launch = [s, N, chunks](int stage, int c) -> int {
     const int lo = (int)sphChunkEdge(N, chunks, c), hi = (int)sphChunkEdge(N, chunks, c + 1);
     if (hi <= lo) return SPH_OK;  // more chunks than blocks of 256 particles
+    if (stage > 0) return sphk_pipeline_stage(s, stage, c, lo, hi, s->chunkStream);
     hipStream_t fnStream = (c & 1) ? s->searchStream : s->stream;
     int rc = sphk_find_neighbors(s, -1, lo, hi, fnStream);
     if (rc != SPH_OK) return rc;
@@ -586,12 +637,17 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks) {
     rc = sphk_density_chunk(s, c, lo, hi, s->chunkStream);
     return rc != SPH_OK ? rc : sphk_pack_gather_records(s, lo, hi, s->chunkStream);
   };
+  // The issue order is the schedule's (depth 0: stage 0 of every chunk, the overlapped search alone), never derived here.
+  int32_t stage[SPH_PIPELINE_ITEMS_MAX(SPH_STEP_CHUNKS_MAX)], chunk[SPH_PIPELINE_ITEMS_MAX(SPH_STEP_CHUNKS_MAX)];
+  const int items = sphPipelineSchedule(chunks, depth, s->cfg.maxIteration, s->d.hasElastic ? 1 : 0, stage, chunk);
   int rc = SPH_OK;
-  for (int c = 0; c < chunks && rc == SPH_OK; c++) rc = chunk(c);
+  for (int i = 0; i < items && rc == SPH_OK; i++) rc = launch(stage[i], chunk[i]);
   // The join, on the device, also after a failed launch. Every findNeighbors launch, on either stream, has a density launch behind
   // it on chunkStream, so chunkStream's last event covers searchStream too.
   SPH_HIP(hipEventRecord(s->evChunkJoin, s->chunkStream));
   SPH_HIP(hipStreamWaitEvent(s->stream, s->evChunkJoin, 0));
+  // The same stages again over all particles, by the serial table: empty launches unless the halo check failed.
+  for (int k = 1; k <= depth && rc == SPH_OK; k++) rc = sphk_pipeline_stage(s, k, -1, 0, N, s->stream);
   return rc;
 }
 
@@ -634,8 +690,9 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   const int M = s->cfg.maxIteration;
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
   const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
+  const int piped = chunks > 1 ? step_pipeline(s) : 0;  // stages 1 .. piped are enqueued with the search
   if (chunks > 1) {
-    rc = enqueue_search_overlapped(s, chunks);
+    rc = enqueue_search_overlapped(s, chunks, piped);
     if (rc != SPH_OK) return rc;
   } else {
     RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1)));
@@ -645,12 +702,15 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   // Outside slab mode the forces kernel is also the first predictDensity: every neighbour's iteration-0 predicted position follows
   // from the (x, v) it gathers anyway. (In slab mode the forces run on fewer layers than that predictDensity.)
   const bool densityInForces = !slab && M >= 1;
-  RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0), densityInForces, chunks <= 1));  // (the chunks packed their records)
+  if (piped < 1) RUN(SPH_ST_FORCES, sphk_forces(s, true, layersFor(0), densityInForces, chunks <= 1));  // (the chunks packed their records)
   if (s->d.hasElastic) RUN(SPH_ST_ELASTIC, sphk_elastic(s));
   for (int iter = 0; iter < M; iter++) {
     const int left = M - 1 - iter;  // iterations after this one
-    if (iter > 0 || !densityInForces) RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0));
-    else RUN(SPH_ST_PREDICT_DENSITY, SPH_OK);  // the stage ran inside the forces kernel: counted (M per step, as ever), an empty interval
+    if (piped >= 2 * iter + 2) continue;  // both stages of the iteration ran with the search
+    if (piped < 2 * iter + 1) {           // (else the predicted density did)
+      if (iter > 0 || !densityInForces) RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0));
+      else RUN(SPH_ST_PREDICT_DENSITY, SPH_OK);  // the stage ran inside the forces kernel: counted (M per step, as ever), an empty interval
+    }
     if (left > 0 || !tail) { RUN(SPH_ST_PRESSURE_FORCE, sphk_pressure_force(s, left == 0 ? 2 : 1, layersFor(2 * left))); continue; }
     // ---- overlapped tail. A particle that ends the step within W layers of a cut started it within W + 1 layers (particles
     // move less than one layer per step — the same assumption the ghost depth rests on), so integrating the W + 1 owned

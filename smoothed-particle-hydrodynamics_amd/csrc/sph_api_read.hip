@@ -123,8 +123,8 @@ extern "C" int sph_host_unregister(sph_solver* s, void* p) {
   return SPH_OK;  // not one of ours: nothing to do
 }
 
-int sph_guard_position_write(sph_solver* s) {
-  if (s->copyPending) SPH_HIP(hipStreamWaitEvent(s->stream, s->evCopyDone, 0));
+int sph_guard_position_write(sph_solver* s, hipStream_t stream) {
+  if (s->copyPending) SPH_HIP(hipStreamWaitEvent(stream ? stream : s->stream, s->evCopyDone, 0));
   return SPH_OK;
 }
 

@@ -141,13 +141,18 @@ struct sph_solver {
   hipEvent_t evReadReady = nullptr, evCopyDone = nullptr;  // positions final on s->stream / copy landed on the host
   // overlapped step (sph_api.hip): the findNeighbors launches of the chunks of sorted particles alternate between
   // s->stream and searchStream (which starts behind evSearchFork, recorded on s->stream); density and the record pack of chunk c
-  // run on chunkStream behind evChunk[c]; s->stream waits for evChunkJoin before the forces kernel, so nothing is pending on either
-  // stream when enqueue_step returns. Created by sph_create, destroyed with the solver.
+  // run on chunkStream behind evChunk[c], and behind them the stages of the pipelined step; s->stream waits for
+  // evChunkJoin before the rest of the step, so nothing is pending on either stream when enqueue_step returns. Created by sph_create, destroyed with the solver.
   hipStream_t chunkStream = nullptr, searchStream = nullptr;
   hipEvent_t evChunk[SPH_STEP_CHUNKS_MAX] = {}, evChunkJoin = nullptr, evSearchFork = nullptr;
   int stepChunks = 0;                  // sph_set_step_chunks: 0 = automatic, 1 = serial, else that many chunks
   uint32_t* chunkEdges = nullptr;      // device, SPH_STEP_CHUNKS_MAX + 1 words: the partition chunkEdgesN / chunkEdgesC was made for
   int chunkEdgesN = -1, chunkEdgesC = -1;
+  // pipelined step (sph_api.hip): up to stepPipeline stages behind the search run on chunkStream chunk by chunk.
+  // pipeTable, device, written every step by k_halo_check: [0 .. SPH_STEP_CHUNKS_MAX] the pipeline table (the chunk edges if the
+  // halo check passed, zeros if not), then the two words of the serial table {0, passed ? 0 : N}
+  int stepPipeline = -1;               // sph_set_step_pipeline: -1 = the built-in depth, else that many stages
+  uint32_t* pipeTable = nullptr;
   bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
   float* copyUserDst = nullptr;        // where the caller wants the data
   void* copyStage = nullptr; size_t copyStageBytes = 0;  // pinned staging, only for destinations that cannot be page-locked in place
@@ -210,8 +215,8 @@ struct sph_solver {
 };
 
 // Called by every launcher whose kernel WRITES posOrig (integrate, membranes finalize, slab rebuild): makes s->stream wait for
-// an asynchronous position read-back that is still in flight.
-int sph_guard_position_write(sph_solver* s);
+// an asynchronous position read-back that is still in flight. `stream`: the stream the kernel runs on, if not s->stream.
+int sph_guard_position_write(sph_solver* s, hipStream_t stream = nullptr);
 
 void sph_set_error(const char* fmt, ...);
 
@@ -312,6 +317,10 @@ int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth = -1, b
 int sphk_correct_pressure(sph_solver* s);
 int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth = -1);  // 0 none, 1 + predictPositions, 2 + integrate
 int sphk_integrate(sph_solver* s);
+// Stage `stage` (1 .. 2 * maxIteration, numbered as in sphmi_chunks.h) of the fused step outside slab mode, on `stream`: for c >= 0
+// over chunk c = [idxLo, idxHi) by the pipeline table, for c < 0 over all particles by the serial table (s->pipeTable: the
+// launch's blocks leave at once where k_halo_check left the table empty).
+int sphk_pipeline_stage(sph_solver* s, int stage, int c, int idxLo, int idxHi, hipStream_t stream);
 // sph_slab.hip
 // Which part of the pack a launch does. ALL: kept set + both messages (sph_slab_pack). The overlapped step packs the MESSAGES
 // as soon as the particles near the cuts (CELL ranges [a0,a1) and [b0,b1) of the sorted order) are integrated, and the KEPT set

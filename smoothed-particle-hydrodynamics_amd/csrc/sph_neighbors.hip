@@ -111,7 +111,9 @@ static_assert(FN_LIST_CAP <= 64, "one bit per list entry");
 // d.dbg layout: [0] particles handed to the exact wave-per-particle walk because a cell was not staged, [1] because a list
 // overflowed, [2] rows without a 16-bit copy because an offset was out of range, [3] candidate runs dropped for LDS capacity;
 // [6] non-finite coordinates seen by the hash kernel (sph_api.hip: sph_check_finite_state; not cleared by sph_reset_stage_times);
-// [8] (wave, batch) pairs of k_pressure_force that left the short division / square-root path (sph_pcisph.hip). With FN_STAMPS (diagnostic build only): [16..25] cycles / 64 per phase.
+// [8] (wave, batch) pairs of k_pressure_force that left the short division / square-root path (sph_pcisph.hip);
+// [9] steps whose halo check failed, so that the pipelined stages ran over all particles behind the search, [10] steps whose
+// pipelined stages ran chunk by chunk (k_halo_check, sph_api.hip). With FN_STAMPS (diagnostic build only): [16..25] cycles / 64 per phase.
 #ifdef FN_STAMPS
 #define FN_STAMP(ph)                                                                                      \
   {                                                                                                       \

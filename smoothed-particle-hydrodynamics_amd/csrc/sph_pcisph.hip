@@ -31,6 +31,7 @@ __device__ __forceinline__ void store_pred(const SphDev& d, int id, const float4
 #define FC_BATCH 8   // forces: two 16-B gathers per neighbour
 #define PF_BATCH 8   // pressure force: 16 B + 4 B per neighbour
 #define PD_BATCH 16  // predicted density: 16 B per neighbour
+#define SPH_SERIAL_GRID 2048  // blocks of the grid-stride entry points (sphk_pipeline_stage); a multiple of 8, the XCD count
 
 // index into SphDev::gatherRec: groups of four particles, [4 x part 0][4 x part 1] (one 128-byte line; see k_pack_gather_records)
 __device__ __forceinline__ size_t rec_index(int j, int part) { return ((size_t)(j >> 2) << 3) + (size_t)(part << 2) + (size_t)(j & 3); }
@@ -79,10 +80,10 @@ struct NbrTile {
 // XCD-aware block order (xcd_block, sph_common.h) in its range-aware form, for launches restricted to a cell range (slab mode): the remap must run over the blocks that HAVE work.
 // Remapping over the whole grid would hand the first eighth of the logical blocks — for a short range, all of the work — to
 // one XCD (a 5-layer launch then took as long as the full one: 120 us instead of 17).
-__device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) {
+// b: the launch's block (blockIdx.x in a launch of one block per 256 particles; a grid-stride launch passes each of its blocks)
+__device__ __forceinline__ bool xcd_range_id(const SphDev& d, int b, int& id) {
   const int begin = (int)d.cellStart[d.rangeLo], end = (int)d.cellStart[d.rangeHi];
   const int active = (end - begin + SPH_BLOCK - 1) / SPH_BLOCK;
-  int b = blockIdx.x;
   if (b >= active) return false;
   const int per = active >> 3, even = per << 3;
   if (b < even) {
@@ -94,6 +95,11 @@ __device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) {
   }
   id = begin + b * SPH_BLOCK + threadIdx.x;
   return id < end;
+}
+__device__ __forceinline__ bool xcd_range_id(const SphDev& d, int& id) { return xcd_range_id(d, (int)blockIdx.x, id); }
+// blocks of 256 particles in the launch's range: what a grid-stride launch loops over
+__device__ __forceinline__ int range_blocks(const SphDev& d) {
+  return ((int)d.cellStart[d.rangeHi] - (int)d.cellStart[d.rangeLo] + SPH_BLOCK - 1) / SPH_BLOCK;
 }
 
 // ------------------------------------------------------------------ K6 pcisph_computeDensity (sphFluid.cl:472-518)
@@ -186,11 +192,11 @@ __device__ __forceinline__ float corrected_pressure(const SphDev& d, float p, fl
 // same 32 slots in the same order with k_predict_density's expressions. That launch then neither streams the id rows a second
 // time nor gathers 32 predicted positions per particle. Boundary particles have a predicted density too (the pressure force
 // gathers their (rho*, p)), so they run the loop here and leave without the force half's stores.
+// The kernel's body for sorted particle id. Two entry points share it: k_forces, one block per 256 particles, and k_forces_strided,
+// a small grid looping over those blocks (the pipelined step's launch over all particles, which is empty on most steps).
 template <bool FUSE_PREDICT, bool FUSE_DENSITY>
-__global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) {  // <= 128 VGPRs: four waves per SIMD
+__device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
   static_assert(FUSE_PREDICT || !FUSE_DENSITY, "the density half reads what the predict half forms");
-  int id;
-  if (!xcd_range_id(d, id)) return;
   const float4 xi = d.sortedPos[id];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   const bool boundary = TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE;
@@ -288,6 +294,21 @@ __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) 
   else { d.accP[id] = zero; d.rp[id].y = 0.f; }
 }
 
+template <bool FUSE_PREDICT, bool FUSE_DENSITY>
+__global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) {  // <= 128 VGPRs: four waves per SIMD
+  int id;
+  if (!xcd_range_id(d, id)) return;
+  forces_particle<FUSE_PREDICT, FUSE_DENSITY>(d, id);
+}
+template <bool FUSE_PREDICT, bool FUSE_DENSITY>
+__global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces_strided(SphDev d) {
+  const int active = range_blocks(d);
+  for (int b = blockIdx.x; b < active; b += gridDim.x) {  // (the grid is a multiple of 8 blocks: b keeps its XCD)
+    int id;
+    if (xcd_range_id(d, b, id)) forces_particle<FUSE_PREDICT, FUSE_DENSITY>(d, id);
+  }
+}
+
 // Gather records of the forces kernel: what it needs of a neighbour — (x, y, z, type) and (v.xyz, rho) — in ONE 128-byte line,
 // groups of four particles: [4 x (x,y,z,type)][4 x (vx,vy,vz,rho)]. A/B on MI355X at 16.5 M particles (tools/time_stage.py):
 // three gathers from three arrays (position, velocity, density) 2.06 ms; position and velocity in one line, density apart
@@ -370,9 +391,7 @@ __device__ __forceinline__ float corrected_pressure(const SphDev& d, float p, fl
 
 // FIRST (fused step, iteration 0): the pressure being corrected is the 0 that K7 sets, without reading it.
 template <bool FUSE_CORRECT, bool FIRST>
-__global__ __launch_bounds__(SPH_BLOCK) void k_predict_density(SphDev d, int nblocks) {
-  int id;
-  if (!xcd_range_id(d, id)) return;
+__device__ __forceinline__ void predict_density_particle(const SphDev& d, const int id) {  // (two entry points, as for forces_particle)
   const float4 xi = load_pred(d, id);
   const NbrTile t(d, id);
   // Branch-free: all 8 id loads first, then the gathers in batches of 8 with an always-valid index (empty slots read
@@ -415,6 +434,21 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_predict_density(SphDev d, int nbl
     d.rp[id] = make_float2(rhoP, corrected_pressure(d, pOld, rhoP));
   } else {
     d.rp[id].x = rhoP;
+  }
+}
+
+template <bool FUSE_CORRECT, bool FIRST>
+__global__ __launch_bounds__(SPH_BLOCK) void k_predict_density(SphDev d, int nblocks) {
+  int id;
+  if (!xcd_range_id(d, id)) return;
+  predict_density_particle<FUSE_CORRECT, FIRST>(d, id);
+}
+template <bool FUSE_CORRECT, bool FIRST>
+__global__ __launch_bounds__(SPH_BLOCK) void k_predict_density_strided(SphDev d) {
+  const int active = range_blocks(d);
+  for (int b = blockIdx.x; b < active; b += gridDim.x) {
+    int id;
+    if (xcd_range_id(d, b, id)) predict_density_particle<FUSE_CORRECT, FIRST>(d, id);
   }
 }
 
@@ -568,9 +602,7 @@ __device__ __forceinline__ bool pf_batch(const SphDev& d, const float4 xi, const
 }
 
 template <int FUSE>
-__global__ __launch_bounds__(SPH_BLOCK) void k_pressure_force(SphDev d, int nblocks) {
-  int id;
-  if (!xcd_range_id(d, id)) return;
+__device__ __forceinline__ void pressure_force_particle(const SphDev& d, const int id) {  // (two entry points, as for forces_particle)
   const float4 xi = d.sortedPos[id];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   if (TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE) {
@@ -633,18 +665,75 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_pressure_force(SphDev d, int nblo
   if (FUSE == 2) integrate_particle(d, id, xi, d.sortedVel[id], d.acc[id], ap);
 }
 
-static int launch_pressure_force(sph_solver* s, int fuse, const SphDev& d) {
-  const int nb = sph_blocks(s->d.N);
-  if (fuse == 2) { const int g = sph_guard_position_write(s); if (g != SPH_OK) return g; }  // (+ integrate: writes posOrig)
-  if (fuse == 0) hipLaunchKernelGGL((k_pressure_force<0>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
-  else if (fuse == 1) hipLaunchKernelGGL((k_pressure_force<1>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
-  else hipLaunchKernelGGL((k_pressure_force<2>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
+template <int FUSE>
+__global__ __launch_bounds__(SPH_BLOCK) void k_pressure_force(SphDev d, int nblocks) {
+  int id;
+  if (!xcd_range_id(d, id)) return;
+  pressure_force_particle<FUSE>(d, id);
+}
+template <int FUSE>
+__global__ __launch_bounds__(SPH_BLOCK) void k_pressure_force_strided(SphDev d) {
+  const int active = range_blocks(d);
+  for (int b = blockIdx.x; b < active; b += gridDim.x) {
+    int id;
+    if (xcd_range_id(d, b, id)) pressure_force_particle<FUSE>(d, id);
+  }
+}
+
+static int launch_pressure_force(sph_solver* s, int fuse, const SphDev& d, int nb, hipStream_t stream) {
+  if (fuse == 2) { const int g = sph_guard_position_write(s, stream); if (g != SPH_OK) return g; }  // (+ integrate: writes posOrig)
+  if (fuse == 0) hipLaunchKernelGGL((k_pressure_force<0>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
+  else if (fuse == 1) hipLaunchKernelGGL((k_pressure_force<1>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
+  else hipLaunchKernelGGL((k_pressure_force<2>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
 
-int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth) { return launch_pressure_force(s, fuse, sph_ranged(s, ghostDepth)); }
+int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth) {
+  return launch_pressure_force(s, fuse, sph_ranged(s, ghostDepth), sph_blocks(s->d.N), s->stream);
+}
 
 int sphk_pressure_force_layers(sph_solver* s, int fuse, long long loLayer, long long hiLayer) {
-  return launch_pressure_force(s, fuse, sph_ranged_layers(s, loLayer, hiLayer));
+  return launch_pressure_force(s, fuse, sph_ranged_layers(s, loLayer, hiLayer), sph_blocks(s->d.N), s->stream);
+}
+
+// One stage of the pipelined step over one chunk, or over all particles behind the join. As in sphk_density_chunk the
+// kernel is handed a small table in place of the cell table: the pipeline table with "cells" c and c + 1 and a grid that covers the
+// chunk, or the serial table with "cells" 0 and 1 and the full grid. k_halo_check fills both every step, so that exactly one of the
+// two launches of a stage finds particles and the blocks of the other leave in xcd_range_id (b >= active = 0).
+// INVARIANT this rests on: k_forces, k_predict_density and k_pressure_force — with predict_position, integrate_particle, the NbrTile
+// constructor and xcd_range_id — read of d.cellStart exactly cellStart[rangeLo] and cellStart[rangeHi] (integrate_particle finds a
+// boundary neighbour through the neighbour row, not through the cell table). tests/test_step_pipeline.py compares every depth with
+// the oracle and the serial step.
+int sphk_pipeline_stage(sph_solver* s, int stage, int c, int idxLo, int idxHi, hipStream_t stream) {
+  const int M = s->cfg.maxIteration;
+  if (s->hasSlab || !s->pipeTable || stage < 1 || stage > 2 * M || c >= SPH_STEP_CHUNKS_MAX || idxLo < 0 || idxHi > s->d.N) {
+    sph_set_error("sphk_pipeline_stage: stage %d of %d, chunk %d [%d, %d) of %d particles", stage, 2 * M, c, idxLo, idxHi, s->d.N);
+    return SPH_ERR_INVALID;
+  }
+  if (idxHi <= idxLo) return SPH_OK;
+  SphDev d = s->d;
+  d.cellStart = c >= 0 ? s->pipeTable : s->pipeTable + SPH_STEP_CHUNKS_MAX + 1;
+  d.rangeLo = c >= 0 ? c : 0; d.rangeHi = d.rangeLo + 1;
+  const int nb = sph_blocks(idxHi - idxLo);
+  const bool last = stage == 2 * M;
+  if (c < 0) {
+    // Over all particles the grid-stride entry points: the launch is empty on every step whose halo check passed, and a grid of
+    // one block per 256 particles would cost 17 us there at 16.5 M particles whereas this one costs what a launch costs
+    // (profiles/r24/README.md). 8 blocks per CU of a 256-CU part.
+    const int grid = min(nb, SPH_SERIAL_GRID);
+    if (last) { const int g = sph_guard_position_write(s, stream); if (g != SPH_OK) return g; }
+    if (stage == 1) hipLaunchKernelGGL((k_forces_strided<true, true>), dim3(grid), dim3(SPH_BLOCK), 0, stream, d);
+    else if (stage & 1) hipLaunchKernelGGL((k_predict_density_strided<true, false>), dim3(grid), dim3(SPH_BLOCK), 0, stream, d);
+    else if (last) hipLaunchKernelGGL((k_pressure_force_strided<2>), dim3(grid), dim3(SPH_BLOCK), 0, stream, d);
+    else hipLaunchKernelGGL((k_pressure_force_strided<1>), dim3(grid), dim3(SPH_BLOCK), 0, stream, d);
+  } else if (stage == 1) {
+    hipLaunchKernelGGL((k_forces<true, true>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
+  } else if (stage & 1) {  // predicted density (+ pressure correction) of iteration stage / 2 >= 1
+    hipLaunchKernelGGL((k_predict_density<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
+  } else {  // pressure force of iteration stage / 2 - 1: + the next iteration's predicted positions, or + integrate behind the last
+    return launch_pressure_force(s, last ? 2 : 1, d, nb, stream);
+  }
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
 }

@@ -454,4 +454,24 @@ int sphmi_step_chunk_edges(int64_t n, int32_t chunks, int64_t* edges) {
   return SPH_OK;
 }
 
+int sphmi_step_pipeline_schedule(int32_t chunks, int32_t depth, int32_t maxIteration, int32_t hasElastic, int32_t* stage,
+                                 int32_t* chunk, int32_t cap, int32_t* depthOut) {
+  if (!stage || !chunk || chunks < 1 || depth < 0 || depth > SPH_PIPELINE_STAGES_MAX || maxIteration < 0) return SPH_ERR_INVALID;
+  if ((int64_t)cap < (int64_t)SPH_PIPELINE_ITEMS_MAX((int64_t)chunks)) return SPH_ERR_SIZE;
+  if (depthOut) *depthOut = sphPipelineDepth(depth, maxIteration, hasElastic);
+  return sphPipelineSchedule(chunks, depth, maxIteration, hasElastic, stage, chunk);
+}
+
+int sphmi_step_halo_check(const uint32_t* keys, int64_t n, const uint32_t* cellStart, int64_t G, const int64_t* edges, int32_t chunks,
+                          int32_t gx, int32_t gy) {
+  if (!keys || !cellStart || !edges || n < 0 || G < 1 || chunks < 1 || gx < 1 || gy < 1) return SPH_ERR_INVALID;
+  if (edges[0] != 0 || edges[chunks] != n) return SPH_ERR_INVALID;
+  for (int32_t c = 0; c < chunks; c++) if (edges[c + 1] < edges[c]) return SPH_ERR_INVALID;
+  const int64_t reach = (int64_t)gx * gy + gx + 1;
+  for (int32_t c = 0; c < chunks; c++)
+    if (!sphChunkHaloOk(keys, cellStart, G, reach, n, edges[c], edges[c + 1], edges[c > 0 ? c - 1 : 0], edges[c + 2 < chunks ? c + 2 : chunks]))
+      return 0;
+  return 1;
+}
+
 }  // extern "C"

@@ -118,6 +118,8 @@ def host_lib():
         L.sphmi_generate_box_slice.argtypes = _box + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.sphmi_muscle_signal.argtypes = [C.c_int, C.c_void_p, C.c_int]
         L.sphmi_step_chunk_edges.argtypes = [C.c_int64, C.c_int32, C.c_void_p]
+        L.sphmi_step_pipeline_schedule.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.sphmi_step_halo_check.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         L.sphmi_trajectory_info.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 4
         L.sphmi_trajectory_frame.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
         L.sphmi_trajectory_connections.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
@@ -141,7 +143,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_position", "sph_read_velocity", "sph_read_density", "sph_read_particle_index",
                     "sph_read_position_async", "sph_read_position_wait", "sph_host_unregister", "sph_build_info",
                     "sph_read_buffer", "sph_read_neighbor_rows", "sph_synchronize", "sph_set_stage_timing", "sph_get_stage_times",
-                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
+                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_set_step_pipeline", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
@@ -154,7 +156,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_field_diffuse", "sph_field_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
-                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_save_configuration", "sphmi_worm_counts",
+                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
                          "sphmi_generate_worm", "sphmi_trajectory_info", "sphmi_trajectory_frame", "sphmi_trajectory_connections",
                          "sphmi_trajectory_membranes"]
 
@@ -214,6 +216,8 @@ def device_lib():
         L.sph_read_neighbor_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.sph_set_stage_timing.argtypes = [C.c_void_p, C.c_int]
         L.sph_set_step_chunks.argtypes = [C.c_void_p, C.c_int32]
+        if hasattr(L, "sph_set_step_pipeline"):  # (optional: an A/B library built from an older csrc/ has no pipelined step)
+            L.sph_set_step_pipeline.argtypes = [C.c_void_p, C.c_int32]
         L.sph_get_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
         L.sph_last_error.restype = C.c_char_p
         L.sph_slab_init.argtypes = [C.c_void_p, C.POINTER(SphSlab), C.c_void_p]
@@ -458,6 +462,35 @@ def step_chunk_edges(n, chunks):
     if rc:
         raise SphError("sphmi_step_chunk_edges failed: %d" % rc)
     return out
+
+
+def step_pipeline_schedule(chunks, depth, max_iteration=3, has_elastic=False):
+    """(clamped depth, [(stage, chunk), ...]): the launches of the pipelined step's chunk stream in issue order (host library, no
+    GPU). Stage 0 is a chunk's density pass and record pack, 1 the forces kernel, 2j + 1 / 2j + 2 the predicted density / the
+    pressure force of iteration j."""
+    if chunks < 1 or not 0 <= depth <= 6 or max_iteration < 0:
+        raise SphError("step_pipeline_schedule: chunks >= 1, 0 <= depth <= 6, max_iteration >= 0")
+    cap = 7 * chunks
+    stage, chunk = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    clamped = C.c_int32(-1)
+    n = host_lib().sphmi_step_pipeline_schedule(chunks, depth, max_iteration, int(bool(has_elastic)), stage.ctypes.data,
+                                                chunk.ctypes.data, cap, C.byref(clamped))
+    if n < 0:
+        raise SphError("sphmi_step_pipeline_schedule failed: %d" % n)
+    return clamped.value, [(int(a), int(b)) for a, b in zip(stage[:n], chunk[:n])]
+
+
+def step_halo_check(keys, cell_start, edges, gx, gy):
+    """The pipelined step's halo check restated on the host: True if, judged from the sorted cell ids and the cell table
+    (G + 1 entries) alone, every possible neighbour of a particle of chunk c of the partition `edges` lies in chunks c - 1 .. c + 1."""
+    keys = np.ascontiguousarray(keys, np.uint32)
+    cell_start = np.ascontiguousarray(cell_start, np.uint32)
+    edges = np.ascontiguousarray(edges, np.int64)
+    rc = host_lib().sphmi_step_halo_check(keys.ctypes.data, keys.size, cell_start.ctypes.data, cell_start.size - 1, edges.ctypes.data,
+                                          edges.size - 1, int(gx), int(gy))
+    if rc < 0:
+        raise SphError("sphmi_step_halo_check failed: %d" % rc)
+    return bool(rc)
 
 
 # ----------------------------------------------------------------------------- device solver
@@ -1136,6 +1169,14 @@ class owHIPSolver:
         """How many ranges of sorted particles step() overlaps density and the record pack with findNeighbors by: 0 automatic
         (by particle count), 1 never, 2..16 forced (tests use it on small scenes). Results do not depend on the chunk count."""
         return self._chk(self._L.sph_set_step_chunks(self._h, int(chunks)))
+
+    def set_step_pipeline(self, depth=-1):
+        """How many of the kernels behind the search the chunked step() runs chunk by chunk under it (forces, then predicted
+        density and pressure force per iteration): -1 the built-in depth, 0 none, 1..6 forced (clamped to the stages the step
+        has, and to 1 with elastic matter). Results do not depend on it."""
+        if not hasattr(self._L, "sph_set_step_pipeline"):
+            raise SphError("this libsphmi has no sph_set_step_pipeline")
+        return self._chk(self._L.sph_set_step_pipeline(self._h, int(depth)))
 
     def reset_stage_times(self):
         return self._chk(self._L.sph_reset_stage_times(self._h))
