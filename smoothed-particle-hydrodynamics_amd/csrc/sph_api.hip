@@ -407,6 +407,8 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   A(d.cellStart, G1); A(d.cellStartRaw, G1);
   A(d.nbrId, mapN); A(d.nbrDist, mapN); A(d.nbr16, mapN); A(d.nbrBase, (size_t)s->capTiles * 64);
   A(d.rho, n);
+  const size_t waves = (size_t)s->capTiles;  // (SPH_TILE == 64: a tile of the neighbour map is a wave of the gather kernels)
+  A(d.pBlk, waves); A(d.cBlk, waves); A(d.xBlk, waves); A(d.k12Skip, waves); A(d.k10Skip, waves); A(d.skipGate, SPH_GATE_SLOTS);
   A(s->blockHist, (size_t)SPH_SORT_MAX_DIGITS * s->maxSortBlocks + SPH_SORT_MAX_DIGITS);  // block histograms + digit totals
   A(d.gid, n); A(d.owned, n); A(s->slabCounts, SPH_SLAB_COUNT_WORDS);
   A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1); A(s->pipeTable, SPH_STEP_CHUNKS_MAX + 3);
@@ -446,11 +448,13 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   hipMemsetAsync(d.accP, 0, sizeof(float4) * n, s->stream);
   hipMemsetAsync(d.rho, 0, sizeof(float) * n, s->stream);
   hipMemsetAsync(d.rp, 0, sizeof(float2) * n, s->stream);
+  for (uint8_t* f : {d.pBlk, d.cBlk, d.xBlk, d.k12Skip, d.k10Skip}) hipMemsetAsync(f, 0, waves, s->stream);  // (for a read-back before the first step: the kernels never rely on it)
   hipMemsetAsync(d.nbrId, 0xff, sizeof(int32_t) * mapN, s->stream);
   hipMemsetAsync(d.nbrDist, 0, sizeof(float) * mapN, s->stream);
   hipMemsetAsync(d.nbr16, 0xff, sizeof(uint16_t) * mapN, s->stream);
   hipMemsetAsync(d.nbrBase, 0, sizeof(int32_t) * (size_t)s->capTiles * 64, s->stream);
   hipMemsetAsync(d.dbg, 0, sizeof(uint32_t) * SPH_DBG_WORDS, s->stream);
+  hipMemsetAsync(d.skipGate, 0, sizeof(uint32_t) * SPH_GATE_SLOTS, s->stream);
   hipMemsetAsync(d.cellStartRaw, 0, sizeof(uint32_t) * G1, s->stream);
   hipMemsetAsync(d.cellStart, 0, sizeof(uint32_t) * G1, s->stream);
   hipMemsetAsync(d.sortedPos, 0, sizeof(float4) * n, s->stream);
@@ -691,6 +695,10 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
   const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
   const int piped = chunks > 1 ? step_pipeline(s) : 0;  // stages 1 .. piped are enqueued with the search
+  // The per-wave flags of the predict-correct loop need launch ranges that start at multiples of SPH_BLOCK, so that a
+  // wave is one id >> 6, and every writer of a flag finished before its first reader starts: the serial step, the chunked search
+  // and the forces kernel behind it chunk by chunk. Deeper pipelines and slab mode run without them.
+  s->waveSkip = !slab && piped <= 1;
   if (chunks > 1) {
     rc = enqueue_search_overlapped(s, chunks, piped);
     if (rc != SPH_OK) return rc;
@@ -708,10 +716,10 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
     const int left = M - 1 - iter;  // iterations after this one
     if (piped >= 2 * iter + 2) continue;  // both stages of the iteration ran with the search
     if (piped < 2 * iter + 1) {           // (else the predicted density did)
-      if (iter > 0 || !densityInForces) RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0));
+      if (iter > 0 || !densityInForces) RUN(SPH_ST_PREDICT_DENSITY, sphk_predict_density(s, true, layersFor(2 * left + 1), iter == 0, iter));
       else RUN(SPH_ST_PREDICT_DENSITY, SPH_OK);  // the stage ran inside the forces kernel: counted (M per step, as ever), an empty interval
     }
-    if (left > 0 || !tail) { RUN(SPH_ST_PRESSURE_FORCE, sphk_pressure_force(s, left == 0 ? 2 : 1, layersFor(2 * left))); continue; }
+    if (left > 0 || !tail) { RUN(SPH_ST_PRESSURE_FORCE, sphk_pressure_force(s, left == 0 ? 2 : 1, layersFor(2 * left), iter)); continue; }
     // ---- overlapped tail. A particle that ends the step within W layers of a cut started it within W + 1 layers (particles
     // move less than one layer per step — the same assumption the ghost depth rests on), so integrating the W + 1 owned
     // layers next to each cut first makes every message particle final; the pack below only looks at those.

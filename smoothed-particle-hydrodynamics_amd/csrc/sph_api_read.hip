@@ -154,7 +154,7 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   const SphDev& d = s->d;
   const size_t n = (size_t)d.N, G1 = (size_t)d.G + 1;
   size_t need = 0;
-  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE } which;
+  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE, B_K12SKIP, B_K10SKIP } which;
   if (!strcmp(name, "position")) { which = B_POS; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "velocity")) { which = B_VEL; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "sortedPosition")) { which = B_SPOS; need = sizeof(float4) * 2 * n; }
@@ -170,6 +170,9 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   else if (!strcmp(name, "rho")) { which = B_RHO; need = sizeof(float) * 2 * n; }
   else if (!strcmp(name, "diagnosticTrace")) { which = B_TRACE; need = sizeof(uint32_t) * n; }  // scratch words of diagnostic builds
   else if (!strcmp(name, "debugCounters")) { which = B_DBG; need = sizeof(uint32_t) * SPH_DBG_WORDS; }
+  // one byte per 64 sorted particles: 1 = the wave skipped its neighbour loop in the last launch that consulted the per-wave flags
+  else if (!strcmp(name, "pressureForceSkipped")) { which = B_K12SKIP; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  else if (!strcmp(name, "predictDensitySkipped")) { which = B_K10SKIP; need = (n + SPH_TILE - 1) / SPH_TILE; }
   else { sph_set_error("unknown buffer '%s'", name); return SPH_ERR_UNKNOWN_BUFFER; }
   if (needed) *needed = need;
   if (!out) return SPH_OK;
@@ -231,6 +234,8 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
     } break;
     case B_TRACE: rc = sph_d2h(s, o, d.valsAlt, sizeof(uint32_t) * n); break;
     case B_DBG: rc = sph_d2h(s, o, d.dbg, sizeof(uint32_t) * SPH_DBG_WORDS); break;
+    case B_K12SKIP: rc = sph_d2h(s, o, d.k12Skip, need); break;
+    case B_K10SKIP: rc = sph_d2h(s, o, d.k10Skip, need); break;
     case B_RHO:
       rc = sph_d2h(s, o, d.rho, sizeof(float) * n);
       if (rc == SPH_OK) {

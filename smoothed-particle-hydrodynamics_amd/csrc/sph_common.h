@@ -28,6 +28,7 @@
 #define SPH_DBG_WORDS 32  // diagnostic counters (SphDev::dbg)
 #define SPH_SLAB_COUNT_WORDS 24
 #define SPH_SORT_MAX_DIGITS 512   // radix digits per pass: 256 (8 bits) or 512 (9 bits)
+#define SPH_GATE_SLOTS 16         // words of SphDev::skipGate: one per stage of the predict-correct loop (stage & 15)
 #define SPH_STEP_CHUNKS_MAX 16    // most chunks the overlapped step takes (sph_set_step_chunks)
 static_assert(SPH_CHUNK_ALIGN == SPH_BLOCK, "chunk edges are launch-block edges of the density and pack passes");
 
@@ -62,6 +63,21 @@ struct SphDev {  // what the kernels see; passed by value
   uint32_t* bndMask;  // bit k set: neighbour slot k holds a boundary particle (written by the forces kernel, read by integrate)
   float4* gatherRec; // 2 x ceil4(N) float4, groups of four particles [4 x (x,y,z,type)][4 x (v.xyz, rho)]: the forces kernel's neighbour gathers
   float2* rp;        // (rhoPred, pressure) per sorted particle: one 8-byte record, gathered per neighbour by the pressure-force kernel
+  // Per-wave flags of the predict-correct loop: one byte per 64 consecutive sorted particles (index id >> 6), each
+  // written with a plain store by the wave that owns those particles, in the kernel and at the point where it writes the data the
+  // byte summarises. Null in every launch that does not take part (staged entry points, slab mode, pipeline depths 2-6).
+  uint8_t* pBlk;     // some particle of the wave has p != 0 in rp (forces kernel at iteration 0, k_predict_density<true, *>)
+  uint8_t* cBlk;     // some non-boundary particle of the wave has a valid neighbour at a stored distance < closeRf (forces kernel)
+  uint8_t* xBlk;     // some particle of the wave got a predicted position whose bits differ from the one before (k_pressure_force<1>)
+  // The launch-level gate in front of them: a writer of flags counts its flagged waves, from a sample of blocks (every 64th), into
+  // skipGate[gateOut]; the consumer of those flags reads skipGate[gateIn] at entry and, unless the sample found nothing flagged, runs
+  // without consulting anything. A heuristic: results never depend on it. The hash kernel zeroes the words. One word per stage of
+  // the loop, stage & (SPH_GATE_SLOTS - 1): with maxIteration > 7 stages share words and their counts add up, which can only close
+  // a gate that would have been open.
+  uint32_t* skipGate;
+  int gateIn, gateOut;
+  uint8_t *k12Skip, *k10Skip;  // the decision of the wave in the last launch of the pressure-force / predicted-density kernel that
+                               // consulted the flags: 1 = it skipped its neighbour loop (read-back only: "pressureForceSkipped", "predictDensitySkipped")
   uint32_t *keys, *vals, *keysAlt, *valsAlt, *backIndex;
   uint32_t *cellStart, *cellStartRaw;
   uint32_t *gid, *owned;  // slab decomposition: global id and ownership flag per local particle (orig order)
@@ -152,6 +168,8 @@ struct sph_solver {
   // pipeTable, device, written every step by k_halo_check: [0 .. SPH_STEP_CHUNKS_MAX] the pipeline table (the chunk edges if the
   // halo check passed, zeros if not), then the two words of the serial table {0, passed ? 0 : N}
   int stepPipeline = -1;               // sph_set_step_pipeline: -1 = the built-in depth, else that many stages
+  bool waveSkip = false;               // set by enqueue_step: the fused kernels of this step write and consult the per-wave flags
+                                       // (SphDev::pBlk ...); the launchers of sph_pcisph.hip hand every other launch null pointers
   uint32_t* pipeTable = nullptr;
   bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
   float* copyUserDst = nullptr;        // where the caller wants the data
@@ -313,9 +331,9 @@ int sphk_pack_gather_records(sph_solver* s, int idxLo, int idxHi, hipStream_t st
 int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth = -1, bool fuseDensity = false, bool packRecords = true);  // fuseDensity: + the first predictDensity
 int sphk_ghost_init(sph_solver* s);  // what K7 does besides the acceleration, for every particle (slab mode)
 int sphk_predict_positions(sph_solver* s);
-int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth = -1, bool first = false);  // first: fused step, iteration 0
+int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth = -1, bool first = false, int iteration = 0);  // first: fused step, iteration 0
 int sphk_correct_pressure(sph_solver* s);
-int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth = -1);  // 0 none, 1 + predictPositions, 2 + integrate
+int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth = -1, int iteration = 0);  // 0 none, 1 + predictPositions, 2 + integrate
 int sphk_integrate(sph_solver* s);
 // Stage `stage` (1 .. 2 * maxIteration, numbered as in sphmi_chunks.h) of the fused step outside slab mode, on `stream`: for c >= 0
 // over chunk c = [idxLo, idxHi) by the pipeline table, for c < 0 over all particles by the serial table (s->pipeTable: the

@@ -102,6 +102,48 @@ __device__ __forceinline__ int range_blocks(const SphDev& d) {
   return ((int)d.cellStart[d.rangeHi] - (int)d.cellStart[d.rangeLo] + SPH_BLOCK - 1) / SPH_BLOCK;
 }
 
+// ---- per-wave flags of the predict-correct loop (SphDev::pBlk ...). Where they are in use the launch's range starts
+// at a multiple of SPH_BLOCK, so the lanes of a wave are the particles of one id >> 6.
+// The lane that writes the wave's byte: the lowest one still active (boundary lanes of K12 and lanes past the range have left).
+__device__ __forceinline__ bool wave_leader() { return (int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1; }
+__device__ __forceinline__ bool wave_flag_store(uint8_t* flags, int id, bool set) {  // returns the byte
+  const bool any = __any(set);
+  if (wave_leader()) flags[id >> 6] = any ? 1 : 0;
+  return any;
+}
+// The launch-level gate (SphDev::skipGate): the writers count their flagged waves over every 64th block and the consumer decides once,
+// by a uniform load. It consults only where the sample found nothing flagged — liquid at rest or in free fall. Where some waves are
+// flagged, a wave that consults and then runs its loop pays for it, and the scenes measured in that state (a worm, a collapsed
+// column; profiles/r26) came out 1-3 % slower than without the flags whatever share of their waves skipped.
+__device__ __forceinline__ bool gate_open(const SphDev& d) { return d.skipGate[d.gateIn] == 0u; }
+__device__ __forceinline__ void gate_count(const SphDev& d, int id, bool waveFlagged) {
+  // (only "none" against "some" is read, so a wave that already sees a count leaves it: thousands of atomic adds on one word
+  // cost a pressure-active launch more than everything else the flags add to it)
+  if (waveFlagged && ((id >> 8) & 63) == 0 && wave_leader() && *(volatile uint32_t*)&d.skipGate[d.gateOut] == 0u)
+    atomicAdd(&d.skipGate[d.gateOut], 1u);
+}
+// Does a valid neighbour of the row lie in a wave whose byte is set? Branch-free like the gathers it stands in front of: an empty
+// slot reads byte 0 and counts as clear. A wave's 64 loads of one slot fall into a few cache lines.
+__device__ __forceinline__ bool nbr_wave_flags(const NbrTile& t, const uint2 (&v16)[8], const bool wideRow, const uint8_t* flags) {
+  uint32_t seen = 0u;
+#pragma unroll
+  for (int g = 0; g < 8; g++) {
+    int jj[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) jj[k] = t.decode(v16[g], k);
+    if (wideRow) {  // rare
+#pragma unroll
+      for (int k = 0; k < 4; k++) jj[k] = t.id_wide(g * 4 + k);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t f = flags[NBR_INDEX(jj[k]) >> 6];
+      seen |= jj[k] != -1 ? f : 0u;
+    }
+  }
+  return seen != 0u;
+}
+
 // ------------------------------------------------------------------ K6 pcisph_computeDensity (sphFluid.cl:472-518)
 // The HBM-roofline-graded pass: reads 32 x 4 B of distances, writes 4 B. The empty-slot test uses the distance
 // sentinel (-1), which is set iff the id is -1 (both are written together), so the id half of the map is not read.
@@ -215,6 +257,7 @@ __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
   uint32_t bnd = 0u, ela = 0u;  // which neighbour slots hold boundary / elastic particles: saves integrate and the
                                 // membrane kernel 32 type gathers per particle
   bool wideRow = false;
+  bool closePair = false;  // FUSE_DENSITY: a valid neighbour at a stored distance < closeRf, the pairs K12 treats apart (cBlk)
   // Branch-free (see k_predict_density): per batch of FC_BATCH neighbours the map loads, then all gathers in flight together.
   // The map is read batch by batch (not all 32 entries up front) and the velocity gather takes 12 bytes: at 193 VGPRs the
   // kernel ran two waves per SIMD, too few to cover its gathers.
@@ -252,6 +295,7 @@ __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
       if (valid && TYPE_OF(xj[k]) == SPH_BOUNDARY_PARTICLE) bnd |= 1u << slot;
       if (valid && TYPE_OF(xj[k]) == SPH_ELASTIC_PARTICLE) ela |= 1u << slot;
       const bool use = valid && rr[k] < d.hs;
+      if (FUSE_DENSITY) closePair |= valid && rr[k] < d.closeRf;  // (an empty slot holds -1)
       const float rj = vr[k].w;
       const float w = d.hs - rr[k];
       sx = use ? sx + (vr[k].x - vi.x) * w / rj : sx;
@@ -274,8 +318,14 @@ __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
     if (density < (double)d.hs6) density = (double)d.hs6;
     density *= d.massWpoly6;
     const float rhoP = (float)density;
-    d.rp[id] = make_float2(rhoP, corrected_pressure(d, 0.f, rhoP));
+    const float p = corrected_pressure(d, 0.f, rhoP);
+    d.rp[id] = make_float2(rhoP, p);
     store_pred(d, id, xpi);
+    if (d.pBlk) {  // (every lane of the wave is still here; K12 never walks a boundary particle's row)
+      const bool anyP = wave_flag_store(d.pBlk, id, p != 0.f);
+      const bool anyC = wave_flag_store(d.cBlk, id, closePair && !boundary);
+      gate_count(d, id, anyP || anyC);
+    }
     if (boundary) { d.acc[id] = zero; return; }
   }
   d.bndMask[id] = bnd;
@@ -367,11 +417,21 @@ int sphk_density_chunk(sph_solver* s, int c, int idxLo, int idxHi, hipStream_t s
   return SPH_OK;
 }
 
+// The launch's view of the per-wave flags: the fused kernels of a step that enqueue_step set waveSkip for see them, every other
+// launch gets null pointers and runs the code without them. (The null pointer is also the A/B switch when measuring.)
+// stage: the launch's place in the loop (1 the forces kernel, 2 i + 1 / 2 i + 2 predicted density / pressure force of iteration i):
+// it counts into the gate word of its stage and reads the one of the stage before.
+static SphDev wave_skip_view(const sph_solver* s, SphDev d, bool fused, int stage) {
+  if (!(fused && s->waveSkip)) d.pBlk = d.cBlk = d.xBlk = d.k12Skip = d.k10Skip = nullptr;
+  d.gateIn = (stage - 1) & (SPH_GATE_SLOTS - 1); d.gateOut = stage & (SPH_GATE_SLOTS - 1);
+  return d;
+}
+
 // fuseDensity: the launch is also the first predictDensity + correctPressure of the fused step (every particle, so not in slab mode)
 int sphk_forces(sph_solver* s, bool fusePredict, int ghostDepth, bool fuseDensity, bool packRecords) {
   if (fuseDensity && (!fusePredict || s->hasSlab)) { sph_set_error("sphk_forces: the density half needs the fused step outside slab mode"); return SPH_ERR_INVALID; }
   const int nb = sph_blocks(s->d.N);
-  const SphDev d = sph_ranged(s, ghostDepth);
+  const SphDev d = wave_skip_view(s, sph_ranged(s, ghostDepth), fuseDensity, 1);
   if (packRecords) { const int rc = sphk_pack_gather_records(s, 0, s->d.N, s->stream); if (rc != SPH_OK) return rc; }
   if (fuseDensity) hipLaunchKernelGGL((k_forces<true, true>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   else if (fusePredict) hipLaunchKernelGGL((k_forces<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
@@ -400,6 +460,24 @@ __device__ __forceinline__ void predict_density_particle(const SphDev& d, const 
 #pragma unroll
   for (int g = 0; g < 8; g++) v16[g] = t.vec16(g);
   const bool wideRow = NbrTile::wide(v16[0]);
+  // Iterations >= 1 of the fused step: if neither the wave's own predicted positions nor those of any wave that holds a valid
+  // neighbour changed a bit in the pressure-force kernel before this launch (xBlk), the sum below would run over the inputs of the
+  // launch before, in the same order: rho* is the value that launch left in rp. One wave-uniform branch.
+  if (FUSE_CORRECT && !FIRST && d.xBlk) {
+    bool skip = false;
+    const float2 old = d.rp[id];  // (requested in front of the decision: a skipping wave is a chain of round trips and little else)
+    if (gate_open(d)) {
+      const bool moved = d.xBlk[id >> 6] != 0 || nbr_wave_flags(t, v16, wideRow, d.xBlk);
+      skip = !__any(moved);
+    }
+    if (wave_leader()) d.k10Skip[id >> 6] = skip ? 1 : 0;
+    if (skip) {
+      const float p = corrected_pressure(d, old.y, old.x);
+      d.rp[id] = make_float2(old.x, p);
+      gate_count(d, id, wave_flag_store(d.pBlk, id, p != 0.f) || d.cBlk[id >> 6] != 0);
+      return;
+    }
+  }
   double density = 0.0;
 #pragma unroll
   for (int b = 0; b < 32 / PD_BATCH; b++) {
@@ -431,7 +509,9 @@ __device__ __forceinline__ void predict_density_particle(const SphDev& d, const 
   const float rhoP = (float)density;
   if (FUSE_CORRECT) {  // (rho*, p) is one 8-byte record: what the pressure-force kernel gathers per neighbour besides the position
     const float pOld = FIRST ? 0.f : d.rp[id].y;
-    d.rp[id] = make_float2(rhoP, corrected_pressure(d, pOld, rhoP));
+    const float p = corrected_pressure(d, pOld, rhoP);
+    d.rp[id] = make_float2(rhoP, p);
+    if (d.pBlk) gate_count(d, id, wave_flag_store(d.pBlk, id, p != 0.f) || d.cBlk[id >> 6] != 0);  // (what K12 will be stopped by)
   } else {
     d.rp[id].x = rhoP;
   }
@@ -452,9 +532,9 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_predict_density_strided(SphDev d)
   }
 }
 
-int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth, bool first) {
+int sphk_predict_density(sph_solver* s, bool fuseCorrect, int ghostDepth, bool first, int iteration) {
   const int nb = sph_blocks(s->d.N);
-  const SphDev d = sph_ranged(s, ghostDepth);
+  const SphDev d = wave_skip_view(s, sph_ranged(s, ghostDepth), fuseCorrect, 2 * iteration + 1);
   if (fuseCorrect && first) hipLaunchKernelGGL((k_predict_density<true, true>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   else if (fuseCorrect) hipLaunchKernelGGL((k_predict_density<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
   else hipLaunchKernelGGL((k_predict_density<false, false>), dim3(nb), dim3(SPH_BLOCK), 0, s->stream, d, nb);
@@ -605,12 +685,22 @@ template <int FUSE>
 __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const int id) {  // (two entry points, as for forces_particle)
   const float4 xi = d.sortedPos[id];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE) {
-    if (FUSE == 1) store_pred(d, id, xi);
+  const bool boundary = TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE;
+  if (FUSE != 0 && d.pBlk && !__any(!boundary) && wave_leader()) {  // a wave of boundary particles: nobody is left below to write its bytes
+    d.k12Skip[id >> 6] = 1;
+    if (FUSE == 1) d.xBlk[id >> 6] = 0;
+  }
+  if (boundary) {
+    if (FUSE == 1) store_pred(d, id, xi);  // (the bits it has held since the forces kernel: "unchanged" for xBlk)
     else d.accP[id] = zero;  // (FUSE == 1, a middle iteration of the fused step: the next pressure-force kernel overwrites it unread)
     return;
   }
   const float2 rpi = d.rp[id];  // (rho*, p) of this particle
+  // (the gate word and the velocity the tail needs are requested here, in front of the decision: a skipping wave is a chain of
+  // round trips and little else)
+  const bool consult = FUSE != 0 && d.pBlk && gate_open(d);
+  float4 vi = zero;
+  if (FUSE != 0) vi = d.sortedVel[id];
   const float pi_ = rpi.y;
   // precondition of the short division sequence (sph_fastmath.h): own coordinates not within 2^-4 of zero
   const bool ownOk = sph_exp_in(xi.x, SPH_FAST_COORD_EXP_LO, 100) && sph_exp_in(xi.y, SPH_FAST_COORD_EXP_LO, 100) &&
@@ -628,41 +718,65 @@ __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const i
 #pragma unroll
   for (int g = 0; g < 8; g++) v16[g] = t.vec16(g);
   const bool wideRow = NbrTile::wide(v16[0]);
+  // The wave has nothing to add if the pressure sum p_i + p_j is +0 for every pair it would walk and no pair is closer than hs / 4:
+  // every term is then a +-0 added to a sum that starts at +0 and cannot become -0. p >= +0 always, so that is: no
+  // own pressure, no valid neighbour in a wave that holds one (pBlk; a NaN counts as one), no close pair in the wave's own rows
+  // (cBlk). Such a wave takes rx = ry = rz = 0 through the unchanged tail below. One wave-uniform branch.
+  bool skip = false;
+  if (consult) {
+    const bool live = pi_ != 0.f || nbr_wave_flags(t, v16, wideRow, d.pBlk);
+    skip = d.cBlk[id >> 6] == 0 && !__any(live);
+  }
+  if (FUSE != 0 && d.pBlk && wave_leader()) d.k12Skip[id >> 6] = skip ? 1 : 0;
+  if (!skip) {
 #pragma unroll
-  for (int b = 0; b < 32 / PF_BATCH; b++) {
-    int jj[PF_BATCH];
+    for (int b = 0; b < 32 / PF_BATCH; b++) {
+      int jj[PF_BATCH];
 #pragma unroll
-    for (int k = 0; k < PF_BATCH; k++) {
-      const int slot = b * PF_BATCH + k;
-      jj[k] = t.decode(v16[slot >> 2], slot & 3);
-    }
-    if (wideRow) {  // rare
+      for (int k = 0; k < PF_BATCH; k++) {
+        const int slot = b * PF_BATCH + k;
+        jj[k] = t.decode(v16[slot >> 2], slot & 3);
+      }
+      if (wideRow) {  // rare
 #pragma unroll
-      for (int k = 0; k < PF_BATCH; k++) jj[k] = t.id_wide(b * PF_BATCH + k);
-    }
-    float4 xj[PF_BATCH];
-    float2 rpj[PF_BATCH];
+        for (int k = 0; k < PF_BATCH; k++) jj[k] = t.id_wide(b * PF_BATCH + k);
+      }
+      float4 xj[PF_BATCH];
+      float2 rpj[PF_BATCH];
 #pragma unroll
-    for (int k = 0; k < PF_BATCH; k++) {
-      const int jc = NBR_INDEX(jj[k]);
-      xj[k] = d.sortedPos[jc];
-      rpj[k] = d.rp[jc];
-    }
-    // The kernel is bound by its arithmetic: the IEEE square root and the three IEEE divisions by r take the short sequences of
-    // sph_fastmath.h, bit-identical inside their operand ranges; a batch in which any lane of the wave leaves those ranges is
-    // simply computed again with the compiler's sqrtf and `/` (same results for the lanes that were inside).
-    const float bx = rx, by = ry, bz = rz;
-    if (!pf_batch<true>(d, xi, pi_, hq, xj, rpj, jj, rx, ry, rz, ownOk)) {
-      if ((threadIdx.x & 63) == 0) atomicAdd(&d.dbg[8], 1u);  // (wave, batch) pairs recomputed with sqrtf and `/`: rare (tests assert it)
-      rx = bx; ry = by; rz = bz;
-      pf_batch<false>(d, xi, pi_, hq, xj, rpj, jj, rx, ry, rz, true);
+      for (int k = 0; k < PF_BATCH; k++) {
+        const int jc = NBR_INDEX(jj[k]);
+        xj[k] = d.sortedPos[jc];
+        rpj[k] = d.rp[jc];
+      }
+      // The kernel is bound by its arithmetic: the IEEE square root and the three IEEE divisions by r take the short sequences of
+      // sph_fastmath.h, bit-identical inside their operand ranges; a batch in which any lane of the wave leaves those ranges is
+      // simply computed again with the compiler's sqrtf and `/` (same results for the lanes that were inside).
+      const float bx = rx, by = ry, bz = rz;
+      if (!pf_batch<true>(d, xi, pi_, hq, xj, rpj, jj, rx, ry, rz, ownOk)) {
+        if ((threadIdx.x & 63) == 0) atomicAdd(&d.dbg[8], 1u);  // (wave, batch) pairs recomputed with sqrtf and `/`: rare (tests assert it)
+        rx = bx; ry = by; rz = bz;
+        pf_batch<false>(d, xi, pi_, hq, xj, rpj, jj, rx, ry, rz, true);
+      }
     }
   }
   const float scale = (float)(d.massGradW / (double)rpi.x);
   const float4 ap = make_float4(rx * scale, ry * scale, rz * scale, 0.f);
   if (FUSE != 1) d.accP[id] = ap;
-  if (FUSE == 1) store_pred(d, id, predict_position(d, xi, d.sortedVel[id], ap));
-  if (FUSE == 2) integrate_particle(d, id, xi, d.sortedVel[id], d.acc[id], ap);
+  if (FUSE == 1) {
+    const float4 xp = predict_position(d, xi, vi, ap);
+    if (d.xBlk) {
+      bool changed = true;  // (behind a closed gate nothing was skipped: "changed" without looking is the safe byte)
+      if (consult) {  // compared on bits: a zero velocity's sign decides whether v + dt * (-0) equals the v + dt * (+0) before it
+        const float4 was = load_pred(d, id);
+        changed = __float_as_uint(was.x) != __float_as_uint(xp.x) || __float_as_uint(was.y) != __float_as_uint(xp.y) ||
+                  __float_as_uint(was.z) != __float_as_uint(xp.z);
+      }
+      gate_count(d, id, wave_flag_store(d.xBlk, id, changed));
+    }
+    store_pred(d, id, xp);
+  }
+  if (FUSE == 2) integrate_particle(d, id, xi, vi, d.acc[id], ap);
 }
 
 template <int FUSE>
@@ -680,7 +794,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_pressure_force_strided(SphDev d) 
   }
 }
 
-static int launch_pressure_force(sph_solver* s, int fuse, const SphDev& d, int nb, hipStream_t stream) {
+static int launch_pressure_force(sph_solver* s, int fuse, const SphDev& ranged, int nb, hipStream_t stream, int stage) {
+  const SphDev d = wave_skip_view(s, ranged, fuse != 0, stage);
   if (fuse == 2) { const int g = sph_guard_position_write(s, stream); if (g != SPH_OK) return g; }  // (+ integrate: writes posOrig)
   if (fuse == 0) hipLaunchKernelGGL((k_pressure_force<0>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
   else if (fuse == 1) hipLaunchKernelGGL((k_pressure_force<1>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
@@ -689,12 +804,12 @@ static int launch_pressure_force(sph_solver* s, int fuse, const SphDev& d, int n
   return SPH_OK;
 }
 
-int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth) {
-  return launch_pressure_force(s, fuse, sph_ranged(s, ghostDepth), sph_blocks(s->d.N), s->stream);
+int sphk_pressure_force(sph_solver* s, int fuse, int ghostDepth, int iteration) {
+  return launch_pressure_force(s, fuse, sph_ranged(s, ghostDepth), sph_blocks(s->d.N), s->stream, 2 * iteration + 2);
 }
 
 int sphk_pressure_force_layers(sph_solver* s, int fuse, long long loLayer, long long hiLayer) {
-  return launch_pressure_force(s, fuse, sph_ranged_layers(s, loLayer, hiLayer), sph_blocks(s->d.N), s->stream);
+  return launch_pressure_force(s, fuse, sph_ranged_layers(s, loLayer, hiLayer), sph_blocks(s->d.N), s->stream, 0);  // (slab mode: no flags)
 }
 
 // One stage of the pipelined step over one chunk, or over all particles behind the join. As in sphk_density_chunk the
@@ -712,7 +827,7 @@ int sphk_pipeline_stage(sph_solver* s, int stage, int c, int idxLo, int idxHi, h
     return SPH_ERR_INVALID;
   }
   if (idxHi <= idxLo) return SPH_OK;
-  SphDev d = s->d;
+  SphDev d = wave_skip_view(s, s->d, true, stage);
   d.cellStart = c >= 0 ? s->pipeTable : s->pipeTable + SPH_STEP_CHUNKS_MAX + 1;
   d.rangeLo = c >= 0 ? c : 0; d.rangeHi = d.rangeLo + 1;
   const int nb = sph_blocks(idxHi - idxLo);
@@ -732,7 +847,7 @@ int sphk_pipeline_stage(sph_solver* s, int stage, int c, int idxLo, int idxHi, h
   } else if (stage & 1) {  // predicted density (+ pressure correction) of iteration stage / 2 >= 1
     hipLaunchKernelGGL((k_predict_density<true, false>), dim3(nb), dim3(SPH_BLOCK), 0, stream, d, nb);
   } else {  // pressure force of iteration stage / 2 - 1: + the next iteration's predicted positions, or + integrate behind the last
-    return launch_pressure_force(s, last ? 2 : 1, d, nb, stream);
+    return launch_pressure_force(s, last ? 2 : 1, d, nb, stream, stage);
   }
   SPH_HIP(hipGetLastError());
   return SPH_OK;

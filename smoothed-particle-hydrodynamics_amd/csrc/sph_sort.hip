@@ -6,6 +6,7 @@
 // ------------------------------------------------------------------ K2 hashParticles (sphFluid.cl:187-201,332-383)
 __global__ __launch_bounds__(SPH_BLOCK) void k_hash(SphDev d) {
   const int id = blockIdx.x * SPH_BLOCK + threadIdx.x;
+  if (id < SPH_GATE_SLOTS) d.skipGate[id] = 0u;  // the step's first kernel: the gate counts of the predict-correct loop start at zero
   if (id >= d.N) return;
   const float4 p = d.posOrig[id];
   // A non-finite coordinate means the simulation has blown up; such particles all hash into one cell and the search turns
@@ -26,6 +27,7 @@ struct CompactKey { int usedX, usedY, czBase, layers; };
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_hash_compact(SphDev d, CompactKey c) {
   const int id = blockIdx.x * SPH_BLOCK + threadIdx.x;
+  if (id < SPH_GATE_SLOTS) d.skipGate[id] = 0u;  // (see k_hash)
   if (id >= d.N) return;
   const float4 p = d.posOrig[id];
   if (!(fabsf(p.x) <= 3.0e38f && fabsf(p.y) <= 3.0e38f && fabsf(p.z) <= 3.0e38f)) atomicAdd(&d.dbg[6], 1u);  // (see k_hash)
