@@ -762,6 +762,73 @@ int sph_field_diffuse(sph_solver* s, int32_t slot, float coefficient, int32_t su
 int sph_field_diagnostics(sph_solver* s, int32_t slot, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
                           uint32_t typeMask, double* out /* host, count x 8 */);
 
+/* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
+ * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
+ * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER
+ * before a step's density and pressure-force stages have run, SPH_ERR_INVALID for a slab solver and for a typeMask of 0 or with
+ * bits outside 1..3. Read-only on every solver array; blocking, on the solver's stream; not stages (no stage timing).
+ * velocity(p): S, Ux, Uy, Uz of the sampling contract at p (the same operations in the same order); hit = (S != 0) and
+ * u = (Ux/S, Uy/S, Uz/S): the bits of words 2..4 of the sph_sample_points record at p. speed(u) = sqrtf(ux*ux + uy*uy + uz*uz),
+ * the products summed left to right. All arithmetic in float in the written order, no contraction, IEEE division and square root.
+ * THE STEP at a curve's vertex p_k (k counts from 0), with step (may be negative: upstream), minSpeed >= 0, mode and integrator
+ * of sph_trace_params and an optional region (x0, y0, z0, x1, y1, z1):
+ *   1. p_k not finite: vertex (p_k, 0) is written and the curve stops with SPH_TRACE_NONFINITE.
+ *   2. u = velocity(p_k); vertex (p_k.x, p_k.y, p_k.z, s) is written, s = speed(u), or 0 without a hit.
+ *   3. no hit: stop with SPH_TRACE_LEFT_MATTER.
+ *   4. a region is given and x0 <= x && x <= x1 is false for some axis of p_k: stop with SPH_TRACE_LEFT_REGION.
+ *   5. !(s > minSpeed): stop with SPH_TRACE_STAGNANT (a NaN speed stops here too).
+ *   6. k == maxSteps: stop with SPH_TRACE_MAX_STEPS.
+ *   7. c = step (SPH_TRACE_TIME) or step / s (SPH_TRACE_ARC).
+ *      SPH_TRACE_EULER:    p_{k+1} = p_k + c*u, per component one multiply, then one add.
+ *      SPH_TRACE_MIDPOINT: q = p_k + (0.5f*c)*u; u2 = velocity(q); if q is not finite, there is no hit at q or
+ *                          !(speed(u2) > minSpeed), the curve stops with SPH_TRACE_NONFINITE, SPH_TRACE_LEFT_MATTER or
+ *                          SPH_TRACE_STAGNANT (tested in that order) and no further vertex is written; otherwise
+ *                          c2 = step or step / speed(u2), and p_{k+1} = p_k + c2*u2.
+ * In SPH_TRACE_TIME mode `step` is in scene units per unit of velocity: a time dt in seconds is dt / simulationScale, the factor
+ * the step's integration applies. In SPH_TRACE_ARC mode it is the chord length in scene units.
+ * sph_trace_streamlines runs the step from every seed until the curve stops, in one launch per piece of seeds. vertices holds
+ * count x (maxSteps + 1) x 4 floats, curve by curve; lengths[i] >= 1 is the number of vertices written for seed i, the slots
+ * behind them are +0, and status[i] is the code the curve stopped with (never SPH_TRACE_MOVING). The results do not depend on
+ * the order or the number of the seeds. count == 0 is a no-op. Seeds go through the sampling scratch in pieces.
+ * TRACERS are points carried along with a run: a device buffer of the solver's own (16 + 8 bytes per tracer, freed by
+ * sph_tracers_set with count 0 and by sph_destroy), not derived from the particle state: steps, stages and edits leave them alone.
+ * sph_tracers_set replaces them by `count` points with status SPH_TRACE_MOVING and 0 steps; it is legal at any time, on any
+ * solver. sph_tracers_advect applies the step (items 1-5 and 7; there is no maxSteps test, params->maxSteps is not read) once to
+ * every tracer whose status is SPH_TRACE_MOVING: the tracer moves to p_{k+1} or stops where it is with the step's code, and its
+ * step count grows by 1. A stopped tracer keeps its position and code. Several calls without a step in between integrate the
+ * frozen field. counts = {tracers still moving, tracers stopped} after the call. sph_tracers_read copies them out (any pointer
+ * may be NULL): pos4 = x, y, z and the speed at the tracer's last sample (item 2; 0 before the first), status, steps.
+ * sph_tracers_advect and sph_tracers_read are SPH_ERR_ORDER while there are no tracers.
+ * Errors beside those above: SPH_ERR_INVALID for null pointers (region6 may be NULL), count < 0, a step that is 0 or not finite,
+ * a minSpeed that is negative or NaN, maxSteps outside 0..65535 (streamlines), a mode or integrator outside 0..1, a NaN region
+ * bound. */
+#define SPH_TRACE_TIME 0
+#define SPH_TRACE_ARC 1
+#define SPH_TRACE_EULER 0
+#define SPH_TRACE_MIDPOINT 1
+#define SPH_TRACE_MOVING 0
+#define SPH_TRACE_MAX_STEPS 1
+#define SPH_TRACE_LEFT_MATTER 2
+#define SPH_TRACE_LEFT_REGION 3
+#define SPH_TRACE_STAGNANT 4
+#define SPH_TRACE_NONFINITE 5
+#define SPH_TRACE_MAX_STEPS_LIMIT 65535
+typedef struct sph_trace_params {
+  float step;
+  float minSpeed;
+  int32_t maxSteps;
+  int32_t mode;        /* SPH_TRACE_TIME or SPH_TRACE_ARC */
+  int32_t integrator;  /* SPH_TRACE_EULER or SPH_TRACE_MIDPOINT */
+} sph_trace_params;
+int sph_trace_streamlines(sph_solver* s, const float* seeds4 /* host, count x (x,y,z,unused) */, int32_t count, uint32_t typeMask,
+                          const sph_trace_params* params, const float* region6 /* or NULL */,
+                          float* vertices /* host, count x (maxSteps+1) x 4 */, int32_t* lengths /* host, count */,
+                          int32_t* status /* host, count */);
+int sph_tracers_set(sph_solver* s, const float* points4 /* host, count x (x,y,z,unused) */, int32_t count); /* 0 releases them */
+int sph_tracers_advect(sph_solver* s, uint32_t typeMask, const sph_trace_params* params, const float* region6 /* or NULL */,
+                       int64_t counts[2] /* out: still moving, stopped */);
+int sph_tracers_read(sph_solver* s, float* pos4 /* host, count x (x,y,z,speed) */, int32_t* status, int32_t* steps);
+
 int sph_synchronize(sph_solver* s);
 
 /* Per-stage device timing with hipEvents on the solver's stream (the reference prints per-stage wall time,

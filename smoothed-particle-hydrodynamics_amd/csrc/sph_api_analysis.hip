@@ -1,6 +1,6 @@
 // C ABI of libsphmi.so (include/sphmi.h), the analysis calls: field and gradient sampling, isosurfaces and their normals, flow
-// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, particle
-// and triangle rendering. All of them read the sorted state of the last completed step and write nothing the step reads. The results that
+// diagnostics and histograms, connected components, particle selection, elastic-matter diagnostics, force decomposition, integral
+// curves, particle and triangle rendering. All of them read the sorted state of the last completed step and write nothing the step reads. The results that
 // outlive their call (mesh, labelling, selection, image) are SphDerived records: dropped first, stamped on success, checked by
 // their readers. What the translation units of the ABI share is in sph_api_internal.h.
 #include <stddef.h>
@@ -672,6 +672,133 @@ extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32
   if (rc != SPH_OK) return rc;
   rc = sph_d2h(s, out, records, sizeof(double) * SPH_FORCE_DIAG_WORDS * (size_t)count);
   return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+// ---------------------------------------------------------------------------------------------- integral curves
+// Streamlines and tracers (sph_trace.hip): the rules of sampling, the step's parameters checked here. Streamlines go through the
+// sampling scratch in pieces of seeds, [vertices][seeds][lengths][status] each; the tracers live in a buffer of their own.
+static int trace_check(sph_solver* s, uint32_t typeMask, const sph_trace_params* p, const float* region6, bool curves,
+                       const char* what, SampleArgs* a, TraceArgs* t) {
+  if (!p) { sph_set_error("%s: null params", what); return SPH_ERR_INVALID; }
+  const int rc = sample_check(s, typeMask, what, a);
+  if (rc != SPH_OK) return rc;
+  if (!std::isfinite(p->step) || p->step == 0.f) { sph_set_error("%s: step must be finite and not 0", what); return SPH_ERR_INVALID; }
+  if (!(p->minSpeed >= 0.f)) { sph_set_error("%s: minSpeed must be >= 0", what); return SPH_ERR_INVALID; }
+  if (curves && (p->maxSteps < 0 || p->maxSteps > SPH_TRACE_MAX_STEPS_LIMIT)) {
+    sph_set_error("%s: maxSteps %d is not in 0..%d", what, p->maxSteps, SPH_TRACE_MAX_STEPS_LIMIT);
+    return SPH_ERR_INVALID;
+  }
+  if (p->mode != SPH_TRACE_TIME && p->mode != SPH_TRACE_ARC) { sph_set_error("%s: mode %d is not 0 or 1", what, p->mode); return SPH_ERR_INVALID; }
+  if (p->integrator != SPH_TRACE_EULER && p->integrator != SPH_TRACE_MIDPOINT) {
+    sph_set_error("%s: integrator %d is not 0 or 1", what, p->integrator);
+    return SPH_ERR_INVALID;
+  }
+  *t = TraceArgs{};
+  t->step = p->step; t->minSpeed = p->minSpeed; t->maxSteps = curves ? p->maxSteps : 0; t->mode = p->mode; t->integrator = p->integrator;
+  t->hasRegion = region6 != nullptr;
+  return region_fill(t->box, region6, what);
+}
+
+extern "C" int sph_trace_streamlines(sph_solver* s, const float* seeds4, int32_t count, uint32_t typeMask, const sph_trace_params* params,
+                                     const float* region6, float* vertices, int32_t* lengths, int32_t* status) {
+  ENTER(s);
+  const char* what = "sph_trace_streamlines";
+  if (count < 0 || (count > 0 && (!seeds4 || !vertices || !lengths || !status))) { sph_set_error("%s: bad count or null pointer", what); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  TraceArgs t;
+  int rc = trace_check(s, typeMask, params, region6, true, what, &a, &t);
+  if (rc != SPH_OK || count == 0) return rc;
+  const size_t curve = sizeof(float4) * (size_t)(t.maxSteps + 1), perSeed = curve + sizeof(float4) + 2 * sizeof(int32_t);
+  const int piece = (int)std::min<size_t>((size_t)count, kSampleScratchBytes / perSeed);  // >= 63: a curve is at most 1 MiB
+  rc = sph_grow_scratch(s, s->sampleBuf, (size_t)piece * perSeed);
+  if (rc != SPH_OK) return rc;
+  char* base = (char*)s->sampleBuf.p;
+  float* dVerts = (float*)base;
+  float* dSeeds = (float*)(base + (size_t)piece * curve);
+  int32_t* dLen = (int32_t*)(base + (size_t)piece * (curve + sizeof(float4)));
+  int32_t* dStatus = dLen + piece;
+  for (int first = 0; first < count; first += piece) {
+    const int n = std::min(piece, count - first);
+    SPH_HIP(hipMemcpyAsync(dSeeds, seeds4 + (size_t)first * 4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    SPH_HIP(hipMemsetAsync(dVerts, 0, curve * (size_t)n, s->stream));  // the slots behind a curve's last vertex
+    rc = sphk_trace_streamlines(s, a, t, dSeeds, n, dVerts, dLen, dStatus);
+    if (rc != SPH_OK) return rc;
+    // enqueued together, waited for once
+    SPH_HIP(hipMemcpyAsync(vertices + (size_t)first * 4 * (size_t)(t.maxSteps + 1), dVerts, curve * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    SPH_HIP(hipMemcpyAsync(lengths + first, dLen, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    rc = sph_d2h(s, status + first, dStatus, sizeof(int32_t) * (size_t)n);
+    if (rc != SPH_OK) return rc;
+  }
+  return SPH_OK;
+}
+
+static const size_t kTracerHead = 256;  // the advect's counter in front of the tracers
+static float* tracer_pos(const sph_solver* s) { return (float*)((char*)s->tracerBuf.p + kTracerHead); }
+static int32_t* tracer_status(const sph_solver* s) { return (int32_t*)((char*)s->tracerBuf.p + kTracerHead + sizeof(float4) * (size_t)s->tracerCount); }
+
+extern "C" int sph_tracers_set(sph_solver* s, const float* points4, int32_t count) {
+  ENTER(s);
+  if (count < 0 || (count > 0 && !points4)) { sph_set_error("sph_tracers_set: bad count or null pointer"); return SPH_ERR_INVALID; }
+  s->tracerCount = 0;
+  if (count == 0) {
+    if (s->tracerBuf.p) { SPH_HIP(hipStreamSynchronize(s->stream)); hipFree(s->tracerBuf.p); }
+    s->tracerBuf.p = nullptr; s->tracerBuf.bytes = 0;
+    return SPH_OK;
+  }
+  const size_t n = (size_t)count;
+  int rc = sph_grow_scratch(s, s->tracerBuf, kTracerHead + n * (sizeof(float4) + 2 * sizeof(int32_t)));
+  if (rc != SPH_OK) return rc;
+  std::vector<float> p4(points4, points4 + 4 * n);
+  for (size_t i = 0; i < n; i++) p4[4 * i + 3] = 0.f;  // no sample yet
+  s->tracerCount = count;
+  SPH_HIP(hipMemcpyAsync(tracer_pos(s), p4.data(), sizeof(float4) * n, hipMemcpyHostToDevice, s->stream));
+  SPH_HIP(hipMemsetAsync(tracer_status(s), 0, 2 * sizeof(int32_t) * n, s->stream));  // SPH_TRACE_MOVING, 0 steps
+  SPH_HIP(hipStreamSynchronize(s->stream));  // (p4 is read until then)
+  return SPH_OK;
+}
+
+static int tracers_exist(const sph_solver* s, const char* what) {
+  if (s->tracerCount > 0) return SPH_OK;
+  sph_set_error("%s: no tracers have been set (sph_tracers_set)", what);
+  return SPH_ERR_ORDER;
+}
+
+extern "C" int sph_tracers_advect(sph_solver* s, uint32_t typeMask, const sph_trace_params* params, const float* region6, int64_t counts[2]) {
+  ENTER(s);
+  const char* what = "sph_tracers_advect";
+  if (counts) counts[0] = counts[1] = 0;
+  if (!counts) { sph_set_error("%s: null counts", what); return SPH_ERR_INVALID; }
+  SampleArgs a;
+  TraceArgs t;
+  int rc = trace_check(s, typeMask, params, region6, false, what, &a, &t);
+  if (rc != SPH_OK) return rc;
+  rc = tracers_exist(s, what);
+  if (rc != SPH_OK) return rc;
+  uint32_t* dMoving = (uint32_t*)s->tracerBuf.p;
+  SPH_HIP(hipMemsetAsync(dMoving, 0, sizeof(uint32_t), s->stream));
+  int32_t* st = tracer_status(s);
+  rc = sphk_tracers_advect(s, a, t, tracer_pos(s), st, st + s->tracerCount, s->tracerCount, dMoving);
+  if (rc != SPH_OK) return rc;
+  uint32_t moving = 0;
+  rc = sph_d2h(s, &moving, dMoving, sizeof(moving));
+  if (rc != SPH_OK) return rc;
+  counts[0] = (int64_t)moving;
+  counts[1] = (int64_t)s->tracerCount - (int64_t)moving;
+  return SPH_OK;
+}
+
+extern "C" int sph_tracers_read(sph_solver* s, float* pos4, int32_t* status, int32_t* steps) {
+  ENTER(s);
+  const int rc = tracers_exist(s, "sph_tracers_read");
+  if (rc != SPH_OK) return rc;
+  const size_t n = (size_t)s->tracerCount;
+  const int32_t* st = tracer_status(s);
+  // enqueued together, waited for once
+  if (pos4) SPH_HIP(hipMemcpyAsync(pos4, tracer_pos(s), sizeof(float4) * n, hipMemcpyDeviceToHost, s->stream));
+  if (status) SPH_HIP(hipMemcpyAsync(status, st, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+  if (steps) SPH_HIP(hipMemcpyAsync(steps, st + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+  SPH_HIP(hipStreamSynchronize(s->stream));
+  return SPH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- particle rendering

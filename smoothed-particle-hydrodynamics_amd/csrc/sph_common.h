@@ -225,6 +225,10 @@ struct sph_solver {
   SphScratch fieldSlot[SPH_FIELD_SLOTS], fieldBuf, fieldStage;
   bool fieldLive[SPH_FIELD_SLOTS] = {};
   float fieldInflow[SPH_FIELD_SLOTS] = {};  // what the ids an adding call creates receive
+  // tracers (sph_tracers_*, sph_trace.hip): [the advect's counter, 256 bytes][float4 x, y, z, last speed][status][steps] for
+  // tracerCount tracers; independent of the particle state, so no stage, step or edit touches it
+  SphScratch tracerBuf;
+  int tracerCount = 0;
 
   sph_solver() = default;
   // Frees everything the solver owns (sph_api.hip): the recorded device allocations, then pinned buffers, host registrations,
@@ -375,6 +379,19 @@ int sphk_gradient_grid(sph_solver* s, const SampleArgs& a, float K, const float 
                        int kBase, int nz, float* out);  // as sphk_sample_grid, 32-word records
 // normals[3*i..] of the `count` packed (x, y, z) vertices at verts, from the gradient of record word `field` (0..5)
 int sphk_surface_normals(sph_solver* s, const SampleArgs& a, float K, int field, const float* verts, int count, float* normals);
+// sph_trace.hip (integral curves of the sampled velocity; read-only on every solver array). Device pointers.
+struct TraceArgs {
+  float step, minSpeed;
+  int maxSteps, mode, integrator;
+  int hasRegion;
+  float box[6];  // x0, y0, z0, x1, y1, z1, both ends inside
+};
+// one curve per seed, curve-major: verts = count x (maxSteps + 1) float4, zeroed by the caller; lengths, status = count words
+int sphk_trace_streamlines(sph_solver* s, const SampleArgs& a, const TraceArgs& t, const float* seeds4, int count, float* verts,
+                           int32_t* lengths, int32_t* status);
+// one step of every moving tracer; *moving (one device word, zeroed by the caller) += the tracers still moving afterwards
+int sphk_tracers_advect(sph_solver* s, const SampleArgs& a, const TraceArgs& t, float* pos4, int32_t* status, int32_t* steps,
+                        int count, uint32_t* moving);
 // One selection of particles: the half-open box x0, y0, z0, x1, y1, z1 (±inf: unbounded) and the types, bits 1..3. The entry
 // points fill it with sph_fill_selector (sph_api_internal.h); the kernels test it with the functions of sph_selector.h.
 struct SphSelector {

@@ -249,6 +249,22 @@ class owHIPSolver {
   void fieldDiagnostics(int slot, const float* regions6, int count, unsigned int typeMask, double* out) {
     check(sph_field_diagnostics(s_, slot, regions6, count, typeMask, out), "fieldDiagnostics");
   }
+  // beyond the reference: curves that follow the sampled velocity field (include/sphmi.h, sph_trace_streamlines / sph_tracers_*).
+  // traceStreamlines: one curve per seed of the field frozen at the last completed step; vertices holds count x (maxSteps + 1) x
+  // 4 floats (x, y, z, speed; +0 behind a curve's end), lengths and status one int per seed. Tracers are points kept on the device
+  // and moved by one step of the same rule per tracersAdvect call (returns the number still moving); steps and edits leave them
+  // alone. region6 may be null.
+  void traceStreamlines(const float* seeds4, int count, unsigned int typeMask, const sph_trace_params& params, const float* region6,
+                        float* vertices, int32_t* lengths, int32_t* status) {
+    check(sph_trace_streamlines(s_, seeds4, count, typeMask, &params, region6, vertices, lengths, status), "traceStreamlines");
+  }
+  void tracersSet(const float* points4, int count) { check(sph_tracers_set(s_, points4, count), "tracersSet"); }
+  int64_t tracersAdvect(unsigned int typeMask, const sph_trace_params& params, const float* region6 = nullptr) {
+    int64_t counts[2] = {0, 0};
+    check(sph_tracers_advect(s_, typeMask, &params, region6, counts), "tracersAdvect");
+    return counts[0];
+  }
+  void tracersRead(float* pos4, int32_t* status, int32_t* steps) { check(sph_tracers_read(s_, pos4, status, steps), "tracersRead"); }
 
   // beyond the reference: the whole stage sequence of simulationStep() as one call, and per-stage device timing
   unsigned int step(int iterationCount) { return (unsigned)sph_step(s_, iterationCount); }

@@ -75,6 +75,17 @@
 //        with coefficient = D * timeStep (default D = 0: it is only carried), and after every K-th step one line is printed:
 //        `dye step=S n=N sum=... mean=... var=... min=... max=... stability=...` (S steps done; the liquid of the whole scene;
 //        %.17g; stability is sph_field_diffuse's number for that step's substep, <= 1: the dye keeps its bounds)
+//   ... --streamlines NU NV --stream-every K --stream-out DIR [--stream-step S] [--stream-max-steps M]
+//        after every K-th step, streamlines of the liquid and elastic matter's velocity field (sph_trace_streamlines; DESIGN.md
+//        §34; midpoint rule, chord length S in scene units, default h/2; at most M steps, default 256) from NU x NV seeds on the
+//        plane across the box's mid-height (y = (ymin + ymax) / 2; seed (i, j) at x = xmin + (i + 0.5) (xmax - xmin) / NU,
+//        z likewise with NV) into DIR/streamlines_<steps done>.vtk: legacy-VTK POLYDATA, one polyline per seed, the speed as point
+//        data (sphmi.frames.read_polylines)
+//   ... --tracers NU NV [--tracers-every K]
+//        tracers carried with the run (sph_tracers_*): the same seed plane, set once; after every step they are advected through
+//        that step's velocity field of the liquid by the scene's time step (midpoint rule), and after every K-th step (default 1)
+//        one line is printed: `tracers step=S moving=M stopped=T`
+//   --help   prints the usage line
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -128,6 +139,38 @@ static void write_ply(const std::string& path, const std::vector<float>& verts, 
     memcpy(&faces[t * 13 + 1], &tris[t * 3], 12);  // little-endian host
   }
   ok = ok && fwrite(faces.data(), 1, faces.size(), f) == faces.size();
+  if (fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
+}
+
+// legacy-VTK POLYDATA, binary (big-endian): the vertices of every curve as POINTS, one LINES cell per curve, the vertices' fourth
+// word as the point scalar "speed" (sphmi.frames.write_vtk_polylines)
+static void write_vtk_polylines(const std::string& path, const std::vector<float>& vertices, const std::vector<int32_t>& lengths, int slots) {
+  auto be = [](const void* word) { uint32_t v; memcpy(&v, word, 4); return __builtin_bswap32(v); };  // little-endian host
+  size_t total = 0;
+  for (int32_t n : lengths) total += (size_t)n;
+  std::vector<uint32_t> points(3 * total), speed(total), cells(total + lengths.size());
+  size_t at = 0, cell = 0;
+  for (size_t c = 0; c < lengths.size(); c++) {
+    const int32_t n = lengths[c];
+    const uint32_t count = (uint32_t)n;
+    cells[cell++] = be(&count);
+    for (int32_t k = 0; k < n; k++, at++) {
+      const float* v = &vertices[(c * (size_t)slots + (size_t)k) * 4];
+      for (int a = 0; a < 3; a++) points[3 * at + a] = be(v + a);
+      speed[at] = be(v + 3);
+      const uint32_t id = (uint32_t)at;
+      cells[cell++] = be(&id);
+    }
+  }
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot write " + path);
+  fprintf(f, "# vtk DataFile Version 3.0\nsphmi streamlines\nBINARY\nDATASET POLYDATA\nPOINTS %zu float\n", total);
+  bool ok = fwrite(points.data(), 4, points.size(), f) == points.size();
+  fprintf(f, "\nLINES %zu %zu\n", lengths.size(), cells.size());
+  ok = ok && fwrite(cells.data(), 4, cells.size(), f) == cells.size();
+  fprintf(f, "\nPOINT_DATA %zu\nSCALARS speed float\nLOOKUP_TABLE default\n", total);
+  ok = ok && fwrite(speed.data(), 4, speed.size(), f) == speed.size();
+  fputc('\n', f);
   if (fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
 }
 
@@ -188,8 +231,21 @@ int main(int argc, char** argv) {
   bool drainSeen = false, drainRegionSeen = false, drainTypesSeen = false; unsigned drainMask = 0; int drainEvery = 0, drainAt = -1;
   float drainRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   bool dyeSeen = false, dyeRegionSeen = false, dyeEverySeen = false; float dyeRegion[6] = {0, 0, 0, 0, 0, 0}, dyeInflow = 0.f, dyeDiffusivity = 0.f; int dyeEvery = 0;
+  int streamSeeds[2] = {0, 0}, streamEvery = 0, streamMaxSteps = 256; float streamStep = 0.f; bool streamSeen = false; const char* streamDir = nullptr;
+  int tracerSeeds[2] = {0, 0}, tracersEvery = 1; bool tracersSeen = false;
+  const char* usage = "usage: sphmi_run (--position P --velocity V | --box X Y Z --lattice A B C | --worm [--muscles]) [--steps N] [--staged] [--wide] [--out F]\n"
+                      "       [--streamlines NU NV --stream-every K --stream-out DIR [--stream-step S] [--stream-max-steps M]] [--tracers NU NV [--tracers-every K]]\n"
+                      "       (every option: the comment at the top of host/sphmi_run.cpp)\n";
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--position") && i + 1 < argc) posFile = argv[++i];
+    else if (!strcmp(argv[i], "--help")) { fputs(usage, stdout); return 0; }
+    else if (!strcmp(argv[i], "--streamlines") && i + 2 < argc) { streamSeeds[0] = atoi(argv[++i]); streamSeeds[1] = atoi(argv[++i]); streamSeen = true; }
+    else if (!strcmp(argv[i], "--stream-step") && i + 1 < argc) { streamStep = (float)atof(argv[++i]); streamSeen = true; }
+    else if (!strcmp(argv[i], "--stream-max-steps") && i + 1 < argc) { streamMaxSteps = atoi(argv[++i]); streamSeen = true; }
+    else if (!strcmp(argv[i], "--stream-every") && i + 1 < argc) { streamEvery = atoi(argv[++i]); streamSeen = true; }
+    else if (!strcmp(argv[i], "--stream-out") && i + 1 < argc) { streamDir = argv[++i]; streamSeen = true; }
+    else if (!strcmp(argv[i], "--tracers") && i + 2 < argc) { tracerSeeds[0] = atoi(argv[++i]); tracerSeeds[1] = atoi(argv[++i]); tracersSeen = true; }
+    else if (!strcmp(argv[i], "--tracers-every") && i + 1 < argc) { tracersEvery = atoi(argv[++i]); tracersSeen = true; }
     else if (!strcmp(argv[i], "--capacity") && i + 1 < argc) { capacity = atoi(argv[++i]); capSeen = true; }
     else if (!strcmp(argv[i], "--emit-lattice") && i + 6 < argc) {
       for (int k = 0; k < 3; k++) emitOrigin[k] = (float)atof(argv[++i]);
@@ -304,6 +360,16 @@ int main(int argc, char** argv) {
   const bool surfacing = surfEvery > 0 || surfDir || (surfDims[0] > 0 && !renSurface);
   if (surfacing && (surfDims[0] < 2 || surfDims[1] < 2 || surfDims[2] < 2 || surfEvery <= 0 || !surfDir)) {
     fprintf(stderr, "--surface-grid NX NY NZ (all >= 2), --surface-every K (> 0) and --surface-out DIR go together\n");
+    return 2;
+  }
+  const long long kSeedMax = 1 << 24;
+  if (streamSeen && (streamSeeds[0] <= 0 || streamSeeds[1] <= 0 || (long long)streamSeeds[0] * streamSeeds[1] > kSeedMax || streamEvery <= 0 || !streamDir ||
+                     streamMaxSteps < 0 || streamMaxSteps > SPH_TRACE_MAX_STEPS_LIMIT || !std::isfinite(streamStep))) {
+    fprintf(stderr, "--streamlines NU NV (> 0), --stream-every K (> 0) and --stream-out DIR go together; --stream-step S: finite, not 0; --stream-max-steps M: 0..65535\n");
+    return 2;
+  }
+  if (tracersSeen && (tracerSeeds[0] <= 0 || tracerSeeds[1] <= 0 || (long long)tracerSeeds[0] * tracerSeeds[1] > kSeedMax || tracersEvery <= 0)) {
+    fprintf(stderr, "--tracers NU NV (> 0) [--tracers-every K (> 0)]\n");
     return 2;
   }
   if (sampleGradients && !sampling) { fprintf(stderr, "--sample-gradients needs --sample-grid\n"); return 2; }
@@ -437,7 +503,7 @@ int main(int argc, char** argv) {
       if (sphmi_generate_box(&cfg, box[0], box[1], box[2], lat[0], lat[1], lat[2], sp, o, o, o, 0.f, 20261004ull, position_cpp.data(), velocity_cpp.data()))
         throw std::runtime_error("box generation failed");
     } else {
-      fprintf(stderr, "usage: sphmi_run (--position P --velocity V | --box X Y Z --lattice A B C | --worm [--muscles]) [--steps N] [--staged] [--wide] [--out F]\n");
+      fputs(usage, stderr);
       return 2;
     }
     if (capSeen) {
@@ -509,6 +575,31 @@ int main(int argc, char** argv) {
             "n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
             "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
             "reserved31\n", compCsv);
+    }
+    // the seed plane of --streamlines / --tracers: across the box at mid-height, one multiply and one add per axis
+    auto seed_plane = [&](const int n[2]) {
+      std::vector<float> seeds(4 * (size_t)n[0] * (size_t)n[1], 0.f);
+      const float dx = (cfg.xmax - cfg.xmin) / (float)n[0], dz = (cfg.zmax - cfg.zmin) / (float)n[1];
+      const float x0 = cfg.xmin + 0.5f * dx, z0 = cfg.zmin + 0.5f * dz, y = 0.5f * (cfg.ymin + cfg.ymax);
+      for (int j = 0; j < n[1]; j++)
+        for (int i = 0; i < n[0]; i++) {
+          float* p = &seeds[4 * ((size_t)j * n[0] + i)];
+          p[0] = x0 + (float)i * dx; p[1] = y; p[2] = z0 + (float)j * dz;
+        }
+      return seeds;
+    };
+    std::vector<float> streamSeedPoints, streamVerts;
+    std::vector<int32_t> streamLengths, streamStatus;
+    const sph_trace_params streamParams = {streamStep != 0.f ? streamStep : 0.5f * cfg.h, 0.f, streamMaxSteps, SPH_TRACE_ARC, SPH_TRACE_MIDPOINT};
+    if (streamSeen) {
+      streamSeedPoints = seed_plane(streamSeeds);
+      const size_t count = streamSeedPoints.size() / 4;
+      streamVerts.resize(count * (size_t)(streamMaxSteps + 1) * 4); streamLengths.resize(count); streamStatus.resize(count);
+    }
+    const sph_trace_params tracerParams = {cfg.timeStep / cfg.simulationScale, 0.f, 0, SPH_TRACE_TIME, SPH_TRACE_MIDPOINT};
+    if (tracersSeen) {
+      const std::vector<float> points = seed_plane(tracerSeeds);
+      ocl_solver->tracersSet(points.data(), (int)(points.size() / 4));
     }
     const unsigned dyeMask = 1u << SPH_LIQUID_PARTICLE;
     if (dyeing) {
@@ -763,6 +854,20 @@ int main(int argc, char** argv) {
                  mean, var, r[3], r[4], (double)stability);
         }
         helper.report("_dye: \t\t\t%9.3f ms\n");
+      }
+      if (streamSeen && (iterationCount + 1) % streamEvery == 0) {
+        ocl_solver->traceStreamlines(streamSeedPoints.data(), (int)streamLengths.size(), (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE),
+                                     streamParams, nullptr, streamVerts.data(), streamLengths.data(), streamStatus.data());
+        write_vtk_polylines(std::string(streamDir) + "/streamlines_" + std::to_string(iterationCount + 1) + ".vtk", streamVerts, streamLengths,
+                            streamMaxSteps + 1);
+        helper.report("_streamlines: \t\t%9.3f ms\n");
+      }
+      if (tracersSeen) {
+        const int64_t moving = ocl_solver->tracersAdvect(1u << SPH_LIQUID_PARTICLE, tracerParams);
+        if ((iterationCount + 1) % tracersEvery == 0)
+          printf("tracers step=%d moving=%lld stopped=%lld\n", iterationCount + 1, (long long)moving,
+                 (long long)tracerSeeds[0] * tracerSeeds[1] - (long long)moving);
+        helper.report("_tracers: \t\t%9.3f ms\n");
       }
       if (muscles) {  // signals computed after step t drive step t+1 (owPhysicsFluidSimulator.cpp:134-141)
         sphmi_muscle_signal(iterationCount, muscle_activation_signal_cpp.data(), cfg.muscleCount);

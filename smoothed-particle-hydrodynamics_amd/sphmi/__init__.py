@@ -32,6 +32,13 @@ FORCE_WORDS = 40  # sph_force_measure record (frames.FORCE_FIELDS)
 FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
 FIELD_SLOTS = 4  # carried particle fields per solver (sph_field_*)
 FIELD_DIAG_WORDS = 8  # sph_field_diagnostics record (frames.FIELD_DIAG_FIELDS)
+TRACE_TIME, TRACE_ARC = 0, 1  # sph_trace_params.mode
+TRACE_EULER, TRACE_MIDPOINT = 0, 1  # sph_trace_params.integrator
+# why a curve stopped (sph_trace_streamlines status; a tracer that has not stopped is TRACE_MOVING)
+TRACE_MOVING, TRACE_MAX_STEPS, TRACE_LEFT_MATTER, TRACE_LEFT_REGION, TRACE_STAGNANT, TRACE_NONFINITE = 0, 1, 2, 3, 4, 5
+TRACE_MAX_STEPS_LIMIT = 65535
+TRACE_MODES = ("time", "arc")
+TRACE_INTEGRATORS = ("euler", "midpoint")
 MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
@@ -86,6 +93,11 @@ class SphRenderMeshStyle(C.Structure):
 RENDER_MESH_SOURCES = ("surface", "membranes")  # sph_render_mesh_style.source 0..1
 RENDER_MESH_SHADINGS = ("flat", "smooth")  # sph_render_mesh_style.shading 0..1
 RENDER_MESH_SURFACE_FIELDS = ("density", "shepard", "vx", "vy", "vz", "pressure", "speed")  # field 0..6 with source 0
+
+
+class SphTraceParams(C.Structure):
+    """sph_trace_params of include/sphmi.h (owHIPSolver.streamlines / tracers_advect fill one)."""
+    _fields_ = [("step", C.c_float), ("minSpeed", C.c_float), ("maxSteps", C.c_int32), ("mode", C.c_int32), ("integrator", C.c_int32)]
 
 
 class SphError(RuntimeError):
@@ -153,7 +165,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_render_particles", "sph_read_render", "sph_render_mesh", "sph_read_render_triangles", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
                     "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map", "sph_field_create",
                     "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
-                    "sph_field_diffuse", "sph_field_diagnostics"] + _STAGE_FUNCS
+                    "sph_field_diffuse", "sph_field_diagnostics", "sph_trace_streamlines", "sph_tracers_set", "sph_tracers_advect",
+                    "sph_tracers_read"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -272,6 +285,11 @@ def device_lib():
         L.sph_field_set_selection.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]
         L.sph_field_diffuse.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_field_diagnostics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        L.sph_trace_streamlines.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(SphTraceParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_tracers_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sph_tracers_advect.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SphTraceParams), C.c_void_p, C.c_void_p]
+        L.sph_tracers_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -1082,6 +1100,63 @@ class owHIPSolver:
         out = np.zeros((max(rg.shape[0], 1), FIELD_DIAG_WORDS), np.float64)
         self._chk(self._L.sph_field_diagnostics(self._h, int(slot), _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
         return out
+
+    # --- integral curves (sph_trace_streamlines / sph_tracers_*): streamlines of the frozen field, tracers carried with a run ---
+    def _trace_params(self, what, step, mode, integrator, max_steps, min_speed, dt):
+        """The sph_trace_params of a call: `step` as it is, or dt seconds as dt / simulationScale (mode "time" only)."""
+        mode = _field_index(mode, TRACE_MODES, what)
+        if dt is not None:
+            if step is not None or mode != TRACE_TIME:
+                raise SphError("%s: dt replaces step, in mode \"time\"" % what)
+            step = np.float32(dt) / np.float32(self.cfg.simulationScale)
+        if step is None:
+            raise SphError("%s: step or dt must be given" % what)
+        return SphTraceParams(float(np.float32(step)), float(np.float32(min_speed)), int(max_steps), mode,
+                              _field_index(integrator, TRACE_INTEGRATORS, what))
+
+    def streamlines(self, seeds, types=(1,), step=None, mode="arc", integrator="midpoint", max_steps=256, min_speed=0.0, region=None,
+                    dt=None):
+        """Streamlines of the velocity field sample_points interpolates over the particles of `types`, frozen at the last completed
+        step, one from each of `seeds` ([Q, 3] or [Q, 4]), traced on the device in one call (include/sphmi.h): mode "arc"
+        advances by chords of length `step` (scene units), "time" by step * velocity (or give dt in seconds); a negative step goes
+        upstream. Returns (vertices float32[Q, max_steps + 1, 4]: x, y, z and the speed there, +0 behind a curve's end;
+        lengths int32[Q]; status int32[Q], the TRACE_* code each curve stopped with)."""
+        p4 = _points4(seeds, "streamlines")
+        prm = self._trace_params("streamlines", step, mode, integrator, max_steps, min_speed, dt)
+        rg = _region(region, "streamlines")
+        Q, M = p4.shape[0], max(int(max_steps), 0)
+        verts = np.empty((Q, M + 1, 4), np.float32)
+        lengths = np.empty(Q, np.int32)
+        status = np.empty(Q, np.int32)
+        self._chk(self._L.sph_trace_streamlines(self._h, _ptr(p4), Q, type_mask(types), C.byref(prm), _ptr(rg), _ptr(verts),
+                                                _ptr(lengths), _ptr(status)))
+        return verts, lengths, status
+
+    def tracers_set(self, points):
+        """Replace the solver's tracers by `points` ([Q, 3] or [Q, 4]; none releases them): points on the device that
+        tracers_advect moves and that steps and edits leave alone."""
+        p4 = _points4(points, "tracers_set") if points is not None and np.size(points) else np.zeros((0, 4), np.float32)
+        self._chk(self._L.sph_tracers_set(self._h, _ptr(p4) if p4.size else None, p4.shape[0]))
+        self._tracers = p4.shape[0]
+
+    def tracers_advect(self, types=(1,), step=None, mode="time", integrator="midpoint", min_speed=0.0, region=None, dt=None):
+        """One step of the streamline rule for every tracer that is still moving, through the field of the last completed step
+        (dt: seconds, e.g. cfg.timeStep after every step()). Returns (still moving, stopped)."""
+        prm = self._trace_params("tracers_advect", step, mode, integrator, 0, min_speed, dt)
+        rg = _region(region, "tracers_advect")
+        counts = np.zeros(2, np.int64)
+        self._chk(self._L.sph_tracers_advect(self._h, type_mask(types), C.byref(prm), _ptr(rg), _ptr(counts)))
+        return int(counts[0]), int(counts[1])
+
+    def tracers(self):
+        """(positions float32[Q, 4]: x, y, z and the speed at the tracer's last sample; status int32[Q], TRACE_MOVING or the code it
+        stopped with; steps int32[Q], the advects it took part in)."""
+        n = getattr(self, "_tracers", 0)  # 0 without tracers: the library reports SPH_ERR_ORDER
+        pos = np.empty((n, 4), np.float32)
+        status = np.empty(n, np.int32)
+        steps = np.empty(n, np.int32)
+        self._chk(self._L.sph_tracers_read(self._h, _ptr(pos) if n else None, _ptr(status) if n else None, _ptr(steps) if n else None))
+        return pos, status, steps
 
     # --- extras ---
     def step(self, iterationCount=0):

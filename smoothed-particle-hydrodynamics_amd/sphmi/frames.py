@@ -39,6 +39,10 @@ as a point cloud with their strain record (ELASTIC_FIELDS) as point data.
 Pictures (owHIPSolver.render / rendered): `look_at` makes the camera frame, `render_view` fills an SphRenderView that frames a
 bounding box, `write_ppm` / `read_ppm` (binary P6) and `write_png` / `read_png` (8-bit RGBA, zlib from the standard library) store
 the colour image, `thickness_in_scene_units` scales the thickness image; FIELD_RAMP and LABEL_PALETTE are the header's tables.
+
+Integral curves (owHIPSolver.streamlines / tracers): `seed_rake` and `seed_plane` make seed points on a segment and on a plane,
+`write_vtk_polylines` / `read_polylines` write and read the curves as legacy-VTK polylines with the speed as point data, the
+format `sphmi_run --stream-out` writes.
 """
 import math
 import struct
@@ -887,3 +891,103 @@ def field_sorted(values, particle_index):
     if pi.shape[0] != v.shape[0]:
         raise ValueError("field_sorted: one value per particle expected")
     return v[pi[:, 1].astype(np.int64)]
+
+
+# ----------------------------------------------------------------------------- integral curves
+def seed_rake(p0, p1, n):
+    """n seeds on the segment p0 .. p1, both ends included (n == 1: p0), float32[n, 3]: p0 + (float)i * ((p1 - p0) / (n - 1)) per
+    axis, one multiply and one add like sample_grid's lattice."""
+    a, b = np.asarray(p0, np.float32).reshape(3), np.asarray(p1, np.float32).reshape(3)
+    n = int(n)
+    if n < 1:
+        raise ValueError("seed_rake: n must be >= 1")
+    d = (b - a) / np.float32(n - 1) if n > 1 else np.zeros(3, np.float32)
+    return a[None, :] + np.arange(n, dtype=np.float32)[:, None] * d[None, :]
+
+
+def seed_plane(origin, du, dv, nu, nv):
+    """nu x nv seeds origin + (float)i * du + (float)j * dv (i fastest), float32[nv * nu, 3]: per axis one multiply and one add
+    for each of the two directions, in that order."""
+    o, du, dv = (np.asarray(v, np.float32).reshape(3) for v in (origin, du, dv))
+    nu, nv = int(nu), int(nv)
+    if nu < 1 or nv < 1:
+        raise ValueError("seed_plane: nu and nv must be >= 1")
+    i = np.arange(nu, dtype=np.float32)[None, :, None]
+    j = np.arange(nv, dtype=np.float32)[:, None, None]
+    return ((o[None, None, :] + i * du[None, None, :]) + j * dv[None, None, :]).reshape(-1, 3)
+
+
+def write_vtk_polylines(path, vertices, lengths, scalars=None):
+    """Legacy-VTK POLYDATA (binary, big-endian like write_vtk) of owHIPSolver.streamlines' result: the first lengths[c] vertices of
+    every curve c of `vertices` [Q, M + 1, >= 3] as POINTS, one LINES cell per curve, and as point data the scalar `speed`: the
+    vertices' fourth word, or `scalars` [Q, M + 1]. The format `sphmi_run --stream-out` writes. Returns the number of points."""
+    v = np.asarray(vertices, np.float32)
+    ln = np.asarray(lengths, np.int64).reshape(-1)
+    if v.ndim != 3 or v.shape[2] < 3 or v.shape[0] != ln.shape[0] or (ln < 0).any() or (ln > v.shape[1]).any():
+        raise ValueError("write_vtk_polylines: vertices [Q, M + 1, >= 3] and lengths [Q] within 0..M + 1 expected")
+    if scalars is None:
+        if v.shape[2] < 4:
+            raise ValueError("write_vtk_polylines: no scalars and no fourth vertex word")
+        sc = v[..., 3]
+    else:
+        sc = np.asarray(scalars, np.float32)
+        if sc.shape != v.shape[:2]:
+            raise ValueError("write_vtk_polylines: scalars must be [Q, M + 1]")
+    keep = np.arange(v.shape[1])[None, :] < ln[:, None]
+    total = int(ln.sum())
+    cells = np.empty(total + ln.shape[0], np.int64)
+    is_head = np.zeros(cells.shape[0], bool)
+    is_head[np.cumsum(ln + 1) - (ln + 1)] = True  # each cell: its length, then its point ids
+    cells[is_head] = ln
+    cells[~is_head] = np.arange(total)
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi streamlines\nBINARY\nDATASET POLYDATA\n")
+        f.write(("POINTS %d float\n" % total).encode())
+        f.write(np.ascontiguousarray(v[..., :3][keep]).astype(">f4").tobytes())
+        f.write(("\nLINES %d %d\n" % (ln.shape[0], cells.shape[0])).encode())
+        f.write(cells.astype(">i4").tobytes())
+        f.write(("\nPOINT_DATA %d\nSCALARS speed float\nLOOKUP_TABLE default\n" % total).encode())
+        f.write(np.ascontiguousarray(sc[keep]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return total
+
+
+def read_polylines(path):
+    """A file of write_vtk_polylines / `sphmi_run --stream-out` as (points float32[P, 3], lengths int32[Q], speed float32[P]): the
+    curves' vertices one curve after the other."""
+    data = open(path, "rb").read()
+    pos = 0
+
+    def line():
+        nonlocal pos
+        end = data.index(b"\n", pos)
+        out = data[pos:end].decode()
+        pos = end + 1
+        return out
+
+    def block(count, dtype):
+        nonlocal pos
+        out = np.frombuffer(data, dtype, count, pos)
+        pos += 4 * count
+        if data[pos:pos + 1] != b"\n":
+            raise ValueError("read_polylines: %s is not a polyline file of write_vtk_polylines" % path)
+        pos += 1
+        return out
+
+    head = [line() for _ in range(4)]
+    if head[0] != "# vtk DataFile Version 3.0" or head[2] != "BINARY" or head[3] != "DATASET POLYDATA":
+        raise ValueError("read_polylines: %s is not a binary legacy-VTK POLYDATA file" % path)
+    total = int(line().split()[1])
+    points = block(3 * total, ">f4").astype(np.float32).reshape(total, 3)
+    q, words = (int(w) for w in line().split()[1:3])
+    cells = block(words, ">i4").astype(np.int64)
+    lengths = np.empty(q, np.int32)
+    at = 0
+    for c in range(q):
+        lengths[c] = cells[at]
+        at += 1 + int(cells[at])
+    if at != words or int(lengths.sum()) != total:
+        raise ValueError("read_polylines: the LINES of %s do not cover its points once" % path)
+    if int(line().split()[1]) != total or not line().startswith("SCALARS speed") or line() != "LOOKUP_TABLE default":
+        raise ValueError("read_polylines: %s has no speed point data" % path)
+    return points, lengths, block(total, ">f4").astype(np.float32)
