@@ -856,6 +856,12 @@ int sph_set_step_chunks(sph_solver* s, int32_t chunks);
  * particles behind the search. Results do not depend on it. */
 int sph_set_step_pipeline(sph_solver* s, int32_t depth);
 
+/* The per-wave skipping of the predict-correct loop in sph_step(): a wave of 64 sorted particles leaves out the neighbour loop of
+ * the pressure-force or predicted-density kernel where its terms cannot change a bit of the result. 0: the built-in policy (a
+ * launch consults the per-wave bytes only where the launch before found nothing flagged); 1: always mark and consult; 2: off.
+ * Results do not depend on it. */
+int sph_set_wave_skip(sph_solver* s, int32_t mode);
+
 /* ---- Spatial decomposition (no reference counterpart: the reference is single-device) -----------------
  * The global box is cut into z-slabs of whole cell layers, one solver (one GPU, one process) per slab. A solver holds the
  * particles of its own layers [layerLo, layerHi) plus `ghostLayers` layers on each side and advances ALL of them with the

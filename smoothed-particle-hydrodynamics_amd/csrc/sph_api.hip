@@ -408,7 +408,10 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   A(d.nbrId, mapN); A(d.nbrDist, mapN); A(d.nbr16, mapN); A(d.nbrBase, (size_t)s->capTiles * 64);
   A(d.rho, n);
   const size_t waves = (size_t)s->capTiles;  // (SPH_TILE == 64: a tile of the neighbour map is a wave of the gather kernels)
-  A(d.pBlk, waves); A(d.cBlk, waves); A(d.xBlk, waves); A(d.k12Skip, waves); A(d.k10Skip, waves); A(d.skipGate, SPH_GATE_SLOTS);
+  const size_t waves4 = (waves + 3) / 4 * 4;     // (the consumers load a wave's byte as part of its aligned word: a scalar load)
+  A(d.pBlk, waves4); A(d.cBlk, waves4); A(d.xBlk, waves4); A(d.k12Skip, waves); A(d.k10Skip, waves); A(d.skipGate, SPH_GATE_SLOTS);
+  A(d.nbhd, waves4 * SPH_GATE_SLOTS);
+  d.nbStride = (int)waves4; d.nbOut = d.nbIn = d.nbhd; d.gatePolicy = 1; d.cellTable = d.cellStart;
   A(s->blockHist, (size_t)SPH_SORT_MAX_DIGITS * s->maxSortBlocks + SPH_SORT_MAX_DIGITS);  // block histograms + digit totals
   A(d.gid, n); A(d.owned, n); A(s->slabCounts, SPH_SLAB_COUNT_WORDS);
   A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1); A(s->pipeTable, SPH_STEP_CHUNKS_MAX + 3);
@@ -449,6 +452,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   hipMemsetAsync(d.rho, 0, sizeof(float) * n, s->stream);
   hipMemsetAsync(d.rp, 0, sizeof(float2) * n, s->stream);
   for (uint8_t* f : {d.pBlk, d.cBlk, d.xBlk, d.k12Skip, d.k10Skip}) hipMemsetAsync(f, 0, waves, s->stream);  // (for a read-back before the first step: the kernels never rely on it)
+  hipMemsetAsync(d.nbhd, 0, waves4 * SPH_GATE_SLOTS, s->stream);
   hipMemsetAsync(d.nbrId, 0xff, sizeof(int32_t) * mapN, s->stream);
   hipMemsetAsync(d.nbrDist, 0, sizeof(float) * mapN, s->stream);
   hipMemsetAsync(d.nbr16, 0xff, sizeof(uint16_t) * mapN, s->stream);
@@ -570,6 +574,15 @@ extern "C" int sph_set_step_pipeline(sph_solver* s, int32_t depth) {
   ENTER(s);
   if (depth < -1 || depth > SPH_PIPELINE_STAGES_MAX) { sph_set_error("sph_set_step_pipeline: %d is not in [-1, %d]", depth, SPH_PIPELINE_STAGES_MAX); return SPH_ERR_INVALID; }
   s->stepPipeline = depth;
+  return SPH_OK;
+}
+
+// The per-wave flags of the predict-correct loop: 0 the built-in policy (the launch-level gate), 1 the writers
+// always mark and the consumers always consult, 2 the flags are off. Results do not depend on it.
+extern "C" int sph_set_wave_skip(sph_solver* s, int32_t mode) {
+  ENTER(s);
+  if (mode < 0 || mode > 2) { sph_set_error("sph_set_wave_skip: %d is not in [0, 2]", mode); return SPH_ERR_INVALID; }
+  s->waveSkipMode = mode;
   return SPH_OK;
 }
 
@@ -698,7 +711,8 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   // The per-wave flags of the predict-correct loop need launch ranges that start at multiples of SPH_BLOCK, so that a
   // wave is one id >> 6, and every writer of a flag finished before its first reader starts: the serial step, the chunked search
   // and the forces kernel behind it chunk by chunk. Deeper pipelines and slab mode run without them.
-  s->waveSkip = !slab && piped <= 1;
+  // The neighbourhood bytes invert the search's cell relation with one cell per offset, which needs a grid larger than an offset.
+  s->waveSkip = !slab && piped <= 1 && s->waveSkipMode != 2 && (long long)s->d.G > (long long)s->d.gx * s->d.gy + s->d.gx + 1;
   if (chunks > 1) {
     rc = enqueue_search_overlapped(s, chunks, piped);
     if (rc != SPH_OK) return rc;

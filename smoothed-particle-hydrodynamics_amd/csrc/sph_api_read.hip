@@ -154,7 +154,7 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   const SphDev& d = s->d;
   const size_t n = (size_t)d.N, G1 = (size_t)d.G + 1;
   size_t need = 0;
-  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE, B_K12SKIP, B_K10SKIP } which;
+  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE, B_K12SKIP, B_K10SKIP, B_NBP, B_NBX, B_PBLK, B_XBLK } which;
   if (!strcmp(name, "position")) { which = B_POS; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "velocity")) { which = B_VEL; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "sortedPosition")) { which = B_SPOS; need = sizeof(float4) * 2 * n; }
@@ -173,6 +173,12 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   // one byte per 64 sorted particles: 1 = the wave skipped its neighbour loop in the last launch that consulted the per-wave flags
   else if (!strcmp(name, "pressureForceSkipped")) { which = B_K12SKIP; need = (n + SPH_TILE - 1) / SPH_TILE; }
   else if (!strcmp(name, "predictDensitySkipped")) { which = B_K10SKIP; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  // the neighbourhood bytes the last pressure-force launch (stage 2 M) / the last predicted-density launch behind a pressure-force
+  // kernel (stage 2 M - 1) read, and the per-wave flags pBlk / xBlk as their last writers left them
+  else if (!strcmp(name, "pressureNeighbourhood")) { which = B_NBP; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  else if (!strcmp(name, "movedNeighbourhood")) { which = B_NBX; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  else if (!strcmp(name, "pressureFlags")) { which = B_PBLK; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  else if (!strcmp(name, "movedFlags")) { which = B_XBLK; need = (n + SPH_TILE - 1) / SPH_TILE; }
   else { sph_set_error("unknown buffer '%s'", name); return SPH_ERR_UNKNOWN_BUFFER; }
   if (needed) *needed = need;
   if (!out) return SPH_OK;
@@ -236,6 +242,11 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
     case B_DBG: rc = sph_d2h(s, o, d.dbg, sizeof(uint32_t) * SPH_DBG_WORDS); break;
     case B_K12SKIP: rc = sph_d2h(s, o, d.k12Skip, need); break;
     case B_K10SKIP: rc = sph_d2h(s, o, d.k10Skip, need); break;
+    // (stage k reads the array of stage k - 1; with maxIteration < 2 no predicted-density launch consults: the array of stage 0, zeros)
+    case B_NBP: rc = sph_d2h(s, o, d.nbhd + (size_t)((2 * s->cfg.maxIteration - 1) & (SPH_GATE_SLOTS - 1)) * d.nbStride, need); break;
+    case B_NBX: rc = sph_d2h(s, o, d.nbhd + (size_t)((s->cfg.maxIteration >= 2 ? 2 * s->cfg.maxIteration - 2 : 0) & (SPH_GATE_SLOTS - 1)) * d.nbStride, need); break;
+    case B_PBLK: rc = sph_d2h(s, o, d.pBlk, need); break;
+    case B_XBLK: rc = sph_d2h(s, o, d.xBlk, need); break;
     case B_RHO:
       rc = sph_d2h(s, o, d.rho, sizeof(float) * n);
       if (rc == SPH_OK) {

@@ -71,11 +71,23 @@ struct SphDev {  // what the kernels see; passed by value
   uint8_t* xBlk;     // some particle of the wave got a predicted position whose bits differ from the one before (k_pressure_force<1>)
   // The launch-level gate in front of them: a writer of flags counts its flagged waves, from a sample of blocks (every 64th), into
   // skipGate[gateOut]; the consumer of those flags reads skipGate[gateIn] at entry and, unless the sample found nothing flagged, runs
-  // without consulting anything. A heuristic: results never depend on it. The hash kernel zeroes the words. One word per stage of
+  // without consulting anything. A heuristic: results never depend on it. The words also carry the closures the exactness of the
+  // neighbourhood bytes needs: a wave that cannot name its readers adds to its stage's word, and k_cell_start sets all of them
+  // in a blown-up state. The hash kernel zeroes the words. One word per stage of
   // the loop, stage & (SPH_GATE_SLOTS - 1): with maxIteration > 7 stages share words and their counts add up, which can only close
   // a gate that would have been open.
   uint32_t* skipGate;
   int gateIn, gateOut;
+  // Neighbourhood bytes: what a consumer wave asks in place of its neighbours' flags. A writer wave whose pBlk (forces kernel,
+  // k_predict_density) or xBlk (k_pressure_force<1>) byte is set stores a 1 for every wave that could hold a particle with a
+  // neighbour in it, judged by cells as findNeighbors looks them up (mark_readers, sph_pcisph.hip). SPH_GATE_SLOTS arrays of nbStride
+  // bytes in one allocation, indexed like the gate words; nbOut / nbIn are the launch's two (wave_skip_view). The hash kernel
+  // zeroes them. cellTable: the real cell table (in launches of the pipelined step cellStart is the pipeline table).
+  uint8_t* nbhd;
+  uint8_t *nbOut, *nbIn;
+  int nbStride;
+  int gatePolicy;  // 1: the writers count their flagged waves into the gate (and stop marking behind a closed one); 0: they always mark
+  const uint32_t* cellTable;
   uint8_t *k12Skip, *k10Skip;  // the decision of the wave in the last launch of the pressure-force / predicted-density kernel that
                                // consulted the flags: 1 = it skipped its neighbour loop (read-back only: "pressureForceSkipped", "predictDensitySkipped")
   uint32_t *keys, *vals, *keysAlt, *valsAlt, *backIndex;
@@ -170,6 +182,7 @@ struct sph_solver {
   int stepPipeline = -1;               // sph_set_step_pipeline: -1 = the built-in depth, else that many stages
   bool waveSkip = false;               // set by enqueue_step: the fused kernels of this step write and consult the per-wave flags
                                        // (SphDev::pBlk ...); the launchers of sph_pcisph.hip hand every other launch null pointers
+  int waveSkipMode = 0;                // sph_set_wave_skip: 0 the built-in policy, 1 always mark and consult, 2 flags off
   uint32_t* pipeTable = nullptr;
   bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
   float* copyUserDst = nullptr;        // where the caller wants the data

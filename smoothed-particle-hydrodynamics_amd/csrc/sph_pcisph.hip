@@ -113,35 +113,60 @@ __device__ __forceinline__ bool wave_flag_store(uint8_t* flags, int id, bool set
 }
 // The launch-level gate (SphDev::skipGate): the writers count their flagged waves over every 64th block and the consumer decides once,
 // by a uniform load. It consults only where the sample found nothing flagged — liquid at rest or in free fall. Where some waves are
-// flagged, a wave that consults and then runs its loop pays for it, and the scenes measured in that state (a worm, a collapsed
-// column; profiles/r26) came out 1-3 % slower than without the flags whatever share of their waves skipped.
+// flagged, the writers' marking of the neighbourhood bytes has to be paid for by the waves that skip, and of the states measured
+// (profiles/r28) only the config #2 cube gained from always consulting; the worm, the dam break and the box at 0.85 r0 came out
+// 1.4-4 % slower. SphDev::gatePolicy switches the counting off (sph_set_wave_skip mode 1).
 __device__ __forceinline__ bool gate_open(const SphDev& d) { return d.skipGate[d.gateIn] == 0u; }
 __device__ __forceinline__ void gate_count(const SphDev& d, int id, bool waveFlagged) {
   // (only "none" against "some" is read, so a wave that already sees a count leaves it: thousands of atomic adds on one word
   // cost a pressure-active launch more than everything else the flags add to it)
-  if (waveFlagged && ((id >> 8) & 63) == 0 && wave_leader() && *(volatile uint32_t*)&d.skipGate[d.gateOut] == 0u)
+  if (d.gatePolicy && waveFlagged && ((id >> 8) & 63) == 0 && wave_leader() && *(volatile uint32_t*)&d.skipGate[d.gateOut] == 0u)
     atomicAdd(&d.skipGate[d.gateOut], 1u);
 }
-// Does a valid neighbour of the row lie in a wave whose byte is set? Branch-free like the gathers it stands in front of: an empty
-// slot reads byte 0 and counts as clear. A wave's 64 loads of one slot fall into a few cache lines.
-__device__ __forceinline__ bool nbr_wave_flags(const NbrTile& t, const uint2 (&v16)[8], const bool wideRow, const uint8_t* flags) {
-  uint32_t seen = 0u;
-#pragma unroll
-  for (int g = 0; g < 8; g++) {
-    int jj[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) jj[k] = t.decode(v16[g], k);
-    if (wideRow) {  // rare
-#pragma unroll
-      for (int k = 0; k < 4; k++) jj[k] = t.id_wide(g * 4 + k);
+// The neighbourhood bytes (SphDev::nbhd). A writer wave whose flag is set stores a 1 for every wave that could hold a particle with
+// a neighbour in it. "Could" is judged by cells: findNeighbors, on its fast path and in its exact walk, looks for the neighbours of a
+// particle with key ki only in the cells wrap_cell(ki + dx + dy gx + dz gx gy, G), d in {-1, 0, 1}^3, so a particle with key kj can
+// be a neighbour only of particles in the 27 cells ki = kj - delta, wrapped back into [0, G) (the inverse of that rule; one cell
+// per offset because G exceeds every offset, which enqueue_step checks). Keys, not cells: 16-bit aliasing is the search's too.
+// The wave walks the distinct keys of its active lanes (1-3 as a rule) and deals the 27 offsets of each to those lanes; a cell's
+// sorted range [lo, hi) marks the waves lo >> 6 .. (hi - 1) >> 6 with plain stores of the same value. delta = 0 marks the wave
+// itself and its cell-mates. A key outside [0, G) (a blown-up state) cannot name its readers and closes the stage's gate instead,
+// as does a cell the search would refuse to walk. With gatePolicy the wave leaves the marking out once the gate reads closed: the
+// word only grows within a step, so every consumer of that stage will read it closed too and consult nothing.
+__device__ __forceinline__ void mark_readers(const SphDev& d, const int id) {
+  if (d.gatePolicy && *(volatile uint32_t*)&d.skipGate[d.gateOut] != 0u) return;
+  const uint32_t mine = d.keys[id];
+  const unsigned long long act = __ballot(1);
+  const int lane = (int)__lane_id();
+  const int rank = __popcll(act & ((1ull << lane) - 1ull)), n = __popcll(act);
+  const int layer = d.gx * d.gy;
+  bool todo = true;
+  for (;;) {
+    const unsigned long long m = __ballot(todo);
+    if (m == 0ull) break;
+    const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)mine, __ffsll(m) - 1);
+    todo = todo && mine != kj;
+    bool refuse = kj >= (uint32_t)d.G;
+    if (!refuse) {
+      for (int o = rank; o < 27; o += n) {
+        const int off = (o % 3 - 1) + ((o / 3) % 3 - 1) * d.gx + (o / 9 - 1) * layer;
+        int ki = (int)kj - off;
+        if (ki < 0) ki += d.G;
+        if (ki >= d.G) ki -= d.G;
+        if (ki < 0 || ki >= d.G) continue;
+        const uint32_t lo = d.cellTable[ki], hi = min(d.cellTable[ki + 1], (uint32_t)d.N);
+        if (hi <= lo) continue;  // an empty cell marks nothing
+        if (hi - lo > (1u << 20)) { refuse = true; continue; }  // (fn_exact_walk does not walk such a cell)
+        for (uint32_t w = lo >> 6; w <= (hi - 1u) >> 6; w++) d.nbOut[w] = 1;
+      }
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t f = flags[NBR_INDEX(jj[k]) >> 6];
-      seen |= jj[k] != -1 ? f : 0u;
-    }
+    if (__any(refuse) && rank == 0) atomicAdd(&d.skipGate[d.gateOut], 1u);
   }
-  return seen != 0u;
+}
+// A wave's byte of a per-wave array, as part of its aligned word: the address is wave-uniform, so the load is a scalar one and
+// leaves with the first loads of the kernel. w: the wave's index in an SGPR (readfirstlane of id >> 6).
+__device__ __forceinline__ uint32_t wave_byte(const uint8_t* a, int w) {
+  return (reinterpret_cast<const uint32_t*>(a)[w >> 2] >> ((w & 3) * 8)) & 0xffu;
 }
 
 // ------------------------------------------------------------------ K6 pcisph_computeDensity (sphFluid.cl:472-518)
@@ -236,7 +261,10 @@ __device__ __forceinline__ float corrected_pressure(const SphDev& d, float p, fl
 // gathers their (rho*, p)), so they run the loop here and leave without the force half's stores.
 // The kernel's body for sorted particle id. Two entry points share it: k_forces, one block per 256 particles, and k_forces_strided,
 // a small grid looping over those blocks (the pipelined step's launch over all particles, which is empty on most steps).
-template <bool FUSE_PREDICT, bool FUSE_DENSITY>
+// MARK: a wave that holds a pressure marks its readers' neighbourhood bytes (mark_readers); without it such a wave closes the gate
+// of its stage instead, which is exact as well. The grid-stride entry point goes without: its launch over all particles is empty
+// unless the halo check failed, and with the marking inlined it would need scratch memory.
+template <bool FUSE_PREDICT, bool FUSE_DENSITY, bool MARK>
 __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
   static_assert(FUSE_PREDICT || !FUSE_DENSITY, "the density half reads what the predict half forms");
   const float4 xi = d.sortedPos[id];
@@ -314,6 +342,7 @@ __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
       }
     }
   }
+  bool mark = false;  // FUSE_DENSITY: the wave holds a pressure and marks its readers' neighbourhood bytes, behind the last store
   if (FUSE_DENSITY) {
     if (density < (double)d.hs6) density = (double)d.hs6;
     density *= d.massWpoly6;
@@ -322,21 +351,28 @@ __device__ __forceinline__ void forces_particle(const SphDev& d, const int id) {
     d.rp[id] = make_float2(rhoP, p);
     store_pred(d, id, xpi);
     if (d.pBlk) {  // (every lane of the wave is still here; K12 never walks a boundary particle's row)
-      const bool anyP = wave_flag_store(d.pBlk, id, p != 0.f);
+      mark = wave_flag_store(d.pBlk, id, p != 0.f);
       const bool anyC = wave_flag_store(d.cBlk, id, closePair && !boundary);
-      gate_count(d, id, anyP || anyC);
+      gate_count(d, id, mark || anyC);
     }
-    if (boundary) { d.acc[id] = zero; return; }
   }
-  d.bndMask[id] = bnd;
-  if (d.hasElastic) d.elasticMask[id] = ela;
-  const float scale = d.massMu * (float)(d.del2W / (double)d.rho[id]);
-  float4 a;
-  a.x = sx * scale + d.gravx + tx;
-  a.y = sy * scale + d.gravy + ty;
-  a.z = sz * scale + d.gravz + tz;
-  a.w = 0.f;  // acceleration.w is never read (integrate zeroes it, sphFluid.cl:1721)
-  d.acc[id] = a;
+  if (FUSE_DENSITY && boundary) {
+    d.acc[id] = zero;
+  } else {
+    d.bndMask[id] = bnd;
+    if (d.hasElastic) d.elasticMask[id] = ela;
+    const float scale = d.massMu * (float)(d.del2W / (double)d.rho[id]);
+    float4 a;
+    a.x = sx * scale + d.gravx + tx;
+    a.y = sy * scale + d.gravy + ty;
+    a.z = sz * scale + d.gravz + tz;
+    a.w = 0.f;  // acceleration.w is never read (integrate zeroes it, sphFluid.cl:1721)
+    d.acc[id] = a;
+  }
+  if (mark) {  // (every lane, the boundary ones too: K12 gathers a boundary neighbour's pressure)
+    if (MARK) mark_readers(d, id);
+    else if (wave_leader() && *(volatile uint32_t*)&d.skipGate[d.gateOut] == 0u) atomicAdd(&d.skipGate[d.gateOut], 1u);
+  }
   if (FUSE_DENSITY) return;  // (predPos and rp are written above)
   // The staged API needs pressure = 0 and a zero pressure acceleration in memory; in the fused step the first predictDensity
   // starts from p = 0 by itself and the pressure acceleration is not read before the last pressure-force kernel writes it.
@@ -348,14 +384,14 @@ template <bool FUSE_PREDICT, bool FUSE_DENSITY>
 __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces(SphDev d, int nblocks) {  // <= 128 VGPRs: four waves per SIMD
   int id;
   if (!xcd_range_id(d, id)) return;
-  forces_particle<FUSE_PREDICT, FUSE_DENSITY>(d, id);
+  forces_particle<FUSE_PREDICT, FUSE_DENSITY, true>(d, id);
 }
 template <bool FUSE_PREDICT, bool FUSE_DENSITY>
 __global__ __launch_bounds__(SPH_BLOCK, 4) void k_forces_strided(SphDev d) {
   const int active = range_blocks(d);
   for (int b = blockIdx.x; b < active; b += gridDim.x) {  // (the grid is a multiple of 8 blocks: b keeps its XCD)
     int id;
-    if (xcd_range_id(d, b, id)) forces_particle<FUSE_PREDICT, FUSE_DENSITY>(d, id);
+    if (xcd_range_id(d, b, id)) forces_particle<FUSE_PREDICT, FUSE_DENSITY, false>(d, id);
   }
 }
 
@@ -420,10 +456,17 @@ int sphk_density_chunk(sph_solver* s, int c, int idxLo, int idxHi, hipStream_t s
 // The launch's view of the per-wave flags: the fused kernels of a step that enqueue_step set waveSkip for see them, every other
 // launch gets null pointers and runs the code without them. (The null pointer is also the A/B switch when measuring.)
 // stage: the launch's place in the loop (1 the forces kernel, 2 i + 1 / 2 i + 2 predicted density / pressure force of iteration i):
-// it counts into the gate word of its stage and reads the one of the stage before.
+// it counts into the gate word of its stage and marks the neighbourhood bytes of its stage, and reads those of the stage before.
+// The built-in policy (sph_set_wave_skip mode 0): 1 the launch-level gate, 0 always mark and consult (mode 1).
+#ifndef SPH_WAVE_SKIP_GATED
+#define SPH_WAVE_SKIP_GATED 1
+#endif
 static SphDev wave_skip_view(const sph_solver* s, SphDev d, bool fused, int stage) {
   if (!(fused && s->waveSkip)) d.pBlk = d.cBlk = d.xBlk = d.k12Skip = d.k10Skip = nullptr;
   d.gateIn = (stage - 1) & (SPH_GATE_SLOTS - 1); d.gateOut = stage & (SPH_GATE_SLOTS - 1);
+  d.nbIn = s->d.nbhd + (size_t)d.gateIn * s->d.nbStride; d.nbOut = s->d.nbhd + (size_t)d.gateOut * s->d.nbStride;
+  d.cellTable = s->d.cellStart;  // (the real one: the launches of the pipelined step hand the kernels a table of their own as cellStart)
+  d.gatePolicy = s->waveSkipMode == 1 ? 0 : SPH_WAVE_SKIP_GATED;
   return d;
 }
 
@@ -449,9 +492,34 @@ __device__ __forceinline__ float corrected_pressure(const SphDev& d, float p, fl
   return p + p_corr;
 }
 
+// What k_predict_density leaves for the pressure-force kernel behind it besides rp: the wave's pBlk byte, its count into the gate
+// (pBlk or cBlk: what K12 will be stopped by) and, if the wave holds a pressure, the neighbourhood bytes of its readers.
+__device__ __forceinline__ void publish_pressure(const SphDev& d, const int id, const float p) {
+  const bool anyP = wave_flag_store(d.pBlk, id, p != 0.f);
+  gate_count(d, id, anyP || d.cBlk[id >> 6] != 0);
+  if (anyP) mark_readers(d, id);
+}
+
 // FIRST (fused step, iteration 0): the pressure being corrected is the 0 that K7 sets, without reading it.
 template <bool FUSE_CORRECT, bool FIRST>
 __device__ __forceinline__ void predict_density_particle(const SphDev& d, const int id) {  // (two entry points, as for forces_particle)
+  // Iterations >= 1 of the fused step: if no wave that could hold a neighbour of this wave's particles, itself included, changed a
+  // bit of a predicted position in the pressure-force kernel before this launch (its neighbourhood byte, marked by the waves whose
+  // xBlk byte that kernel set), the sum below would run over the inputs of the launch before, in the same order: rho* is the value
+  // that launch left in rp. One wave-uniform branch, decided from the gate word and one byte, both scalar loads
+  // that leave with the kernel's first loads; only a wave that runs its loop requests its id rows.
+  if (FUSE_CORRECT && !FIRST && d.xBlk) {
+    const int w = __builtin_amdgcn_readfirstlane(id) >> 6;
+    const bool skip = gate_open(d) && wave_byte(d.nbIn, w) == 0u;
+    const float2 old = d.rp[id];  // (requested in front of the decision: a skipping wave is a chain of round trips and little else)
+    if (wave_leader()) d.k10Skip[id >> 6] = skip ? 1 : 0;
+    if (skip) {
+      const float p = corrected_pressure(d, old.y, old.x);
+      d.rp[id] = make_float2(old.x, p);
+      publish_pressure(d, id, p);
+      return;
+    }
+  }
   const float4 xi = load_pred(d, id);
   const NbrTile t(d, id);
   // Branch-free: all 8 id loads first, then the gathers in batches of 8 with an always-valid index (empty slots read
@@ -460,24 +528,6 @@ __device__ __forceinline__ void predict_density_particle(const SphDev& d, const 
 #pragma unroll
   for (int g = 0; g < 8; g++) v16[g] = t.vec16(g);
   const bool wideRow = NbrTile::wide(v16[0]);
-  // Iterations >= 1 of the fused step: if neither the wave's own predicted positions nor those of any wave that holds a valid
-  // neighbour changed a bit in the pressure-force kernel before this launch (xBlk), the sum below would run over the inputs of the
-  // launch before, in the same order: rho* is the value that launch left in rp. One wave-uniform branch.
-  if (FUSE_CORRECT && !FIRST && d.xBlk) {
-    bool skip = false;
-    const float2 old = d.rp[id];  // (requested in front of the decision: a skipping wave is a chain of round trips and little else)
-    if (gate_open(d)) {
-      const bool moved = d.xBlk[id >> 6] != 0 || nbr_wave_flags(t, v16, wideRow, d.xBlk);
-      skip = !__any(moved);
-    }
-    if (wave_leader()) d.k10Skip[id >> 6] = skip ? 1 : 0;
-    if (skip) {
-      const float p = corrected_pressure(d, old.y, old.x);
-      d.rp[id] = make_float2(old.x, p);
-      gate_count(d, id, wave_flag_store(d.pBlk, id, p != 0.f) || d.cBlk[id >> 6] != 0);
-      return;
-    }
-  }
   double density = 0.0;
 #pragma unroll
   for (int b = 0; b < 32 / PD_BATCH; b++) {
@@ -511,7 +561,7 @@ __device__ __forceinline__ void predict_density_particle(const SphDev& d, const 
     const float pOld = FIRST ? 0.f : d.rp[id].y;
     const float p = corrected_pressure(d, pOld, rhoP);
     d.rp[id] = make_float2(rhoP, p);
-    if (d.pBlk) gate_count(d, id, wave_flag_store(d.pBlk, id, p != 0.f) || d.cBlk[id >> 6] != 0);  // (what K12 will be stopped by)
+    if (d.pBlk) publish_pressure(d, id, p);
   } else {
     d.rp[id].x = rhoP;
   }
@@ -685,6 +735,18 @@ template <int FUSE>
 __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const int id) {  // (two entry points, as for forces_particle)
   const float4 xi = d.sortedPos[id];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  // The wave has nothing to add if the pressure sum p_i + p_j is +0 for every pair it would walk and no pair is closer than hs / 4:
+  // every term is then a +-0 added to a sum that starts at +0 and cannot become -0 (DESIGN.md 33). p >= +0 always, so that is: no
+  // wave that could hold a neighbour of this wave's particles, itself included, holds a pressure (its neighbourhood byte, marked by
+  // the waves whose pBlk byte is set; a NaN counts as a pressure) and no close pair in the wave's own rows (cBlk). Such a wave takes
+  // rx = ry = rz = 0 through the unchanged tail below. One wave-uniform branch, decided from the gate word and two bytes: scalar
+  // loads that leave with the kernel's first loads, in front of the id rows, which only a wave that runs its loop requests.
+  bool consult = false, skip = false;
+  if (FUSE != 0 && d.pBlk) {
+    const int w = __builtin_amdgcn_readfirstlane(id) >> 6;
+    consult = gate_open(d);
+    skip = consult && (wave_byte(d.nbIn, w) | wave_byte(d.cBlk, w)) == 0u;
+  }
   const bool boundary = TYPE_OF(xi) == SPH_BOUNDARY_PARTICLE;
   if (FUSE != 0 && d.pBlk && !__any(!boundary) && wave_leader()) {  // a wave of boundary particles: nobody is left below to write its bytes
     d.k12Skip[id >> 6] = 1;
@@ -696,39 +758,27 @@ __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const i
     return;
   }
   const float2 rpi = d.rp[id];  // (rho*, p) of this particle
-  // (the gate word and the velocity the tail needs are requested here, in front of the decision: a skipping wave is a chain of
-  // round trips and little else)
-  const bool consult = FUSE != 0 && d.pBlk && gate_open(d);
   float4 vi = zero;
-  if (FUSE != 0) vi = d.sortedVel[id];
+  if (FUSE != 0) vi = d.sortedVel[id];  // (the tail's: requested in front of the loop, a skipping wave is a chain of round trips and little else)
   const float pi_ = rpi.y;
-  // precondition of the short division sequence (sph_fastmath.h): own coordinates not within 2^-4 of zero
-  const bool ownOk = sph_exp_in(xi.x, SPH_FAST_COORD_EXP_LO, 100) && sph_exp_in(xi.y, SPH_FAST_COORD_EXP_LO, 100) &&
-                     sph_exp_in(xi.z, SPH_FAST_COORD_EXP_LO, 100);
-  const NbrTile t(d, id);
   float rx = 0.f, ry = 0.f, rz = 0.f;
-  const float hq = d.hs * 0.25f;
-  // Branch-free, like k_predict_density: map loads first, gathers in batches of PF_BATCH with an always-valid index,
-  // masked accumulation (a skipped term leaves the sum untouched, exactly as the reference's `if`).
-  // The distances are NOT read: r_ij is recomputed from the two position records this kernel has anyway, with the expression
-  // findNeighbors stored it with (sphFluid.cl:131-136,172; IEEE sqrt) — bit-identical, and 128 of the 272 bytes the kernel
-  // streamed per particle are gone (1.24 -> 1.17 ms per launch at 16.5 M particles; re-measured in round 3 with the short
-  // arithmetic in place: reading the rows instead of taking the square root is 1.26 vs 1.00 ms per launch).
-  uint2 v16[8];
-#pragma unroll
-  for (int g = 0; g < 8; g++) v16[g] = t.vec16(g);
-  const bool wideRow = NbrTile::wide(v16[0]);
-  // The wave has nothing to add if the pressure sum p_i + p_j is +0 for every pair it would walk and no pair is closer than hs / 4:
-  // every term is then a +-0 added to a sum that starts at +0 and cannot become -0 (DESIGN.md 33). p >= +0 always, so that is: no
-  // own pressure, no valid neighbour in a wave that holds one (pBlk; a NaN counts as one), no close pair in the wave's own rows
-  // (cBlk). Such a wave takes rx = ry = rz = 0 through the unchanged tail below. One wave-uniform branch.
-  bool skip = false;
-  if (consult) {
-    const bool live = pi_ != 0.f || nbr_wave_flags(t, v16, wideRow, d.pBlk);
-    skip = d.cBlk[id >> 6] == 0 && !__any(live);
-  }
   if (FUSE != 0 && d.pBlk && wave_leader()) d.k12Skip[id >> 6] = skip ? 1 : 0;
   if (!skip) {
+    // precondition of the short division sequence (sph_fastmath.h): own coordinates not within 2^-4 of zero
+    const bool ownOk = sph_exp_in(xi.x, SPH_FAST_COORD_EXP_LO, 100) && sph_exp_in(xi.y, SPH_FAST_COORD_EXP_LO, 100) &&
+                       sph_exp_in(xi.z, SPH_FAST_COORD_EXP_LO, 100);
+    const NbrTile t(d, id);
+    const float hq = d.hs * 0.25f;
+    // Branch-free, like k_predict_density: map loads first, gathers in batches of PF_BATCH with an always-valid index,
+    // masked accumulation (a skipped term leaves the sum untouched, exactly as the reference's `if`).
+    // The distances are NOT read: r_ij is recomputed from the two position records this kernel has anyway, with the expression
+    // findNeighbors stored it with (sphFluid.cl:131-136,172; IEEE sqrt) — bit-identical, and 128 of the 272 bytes the kernel
+    // streamed per particle are gone (1.24 -> 1.17 ms per launch at 16.5 M particles; re-measured in round 3 with the short
+    // arithmetic in place: reading the rows instead of taking the square root is 1.26 vs 1.00 ms per launch).
+    uint2 v16[8];
+#pragma unroll
+    for (int g = 0; g < 8; g++) v16[g] = t.vec16(g);
+    const bool wideRow = NbrTile::wide(v16[0]);
 #pragma unroll
     for (int b = 0; b < 32 / PF_BATCH; b++) {
       int jj[PF_BATCH];
@@ -765,6 +815,7 @@ __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const i
   if (FUSE != 1) d.accP[id] = ap;
   if (FUSE == 1) {
     const float4 xp = predict_position(d, xi, vi, ap);
+    bool moved = false;
     if (d.xBlk) {
       bool changed = true;  // (behind a closed gate nothing was skipped: "changed" without looking is the safe byte)
       if (consult) {  // compared on bits: a zero velocity's sign decides whether v + dt * (-0) equals the v + dt * (+0) before it
@@ -772,9 +823,11 @@ __device__ __forceinline__ void pressure_force_particle(const SphDev& d, const i
         changed = __float_as_uint(was.x) != __float_as_uint(xp.x) || __float_as_uint(was.y) != __float_as_uint(xp.y) ||
                   __float_as_uint(was.z) != __float_as_uint(xp.z);
       }
-      gate_count(d, id, wave_flag_store(d.xBlk, id, changed));
+      moved = wave_flag_store(d.xBlk, id, changed);
+      gate_count(d, id, moved);
     }
     store_pred(d, id, xp);
+    if (moved) mark_readers(d, id);  // (the keys of the lanes still here: a boundary particle's predicted position never changes)
   }
   if (FUSE == 2) integrate_particle(d, id, xi, vi, d.acc[id], ap);
 }

@@ -4,9 +4,17 @@
 #include "sph_common.h"
 
 // ------------------------------------------------------------------ K2 hashParticles (sphFluid.cl:187-201,332-383)
+// The step's first kernel: the gate counts of the predict-correct loop and the neighbourhood bytes of its stages start at zero
+// (SPH_GATE_SLOTS arrays of one byte per 64 particles, cleared a word per lane: 16 * ceil(N / 256) lanes, never more than the grid has).
+__device__ __forceinline__ void clear_wave_skip_state(const SphDev& d, int id) {
+  if (id < SPH_GATE_SLOTS) d.skipGate[id] = 0u;
+  const int words = (((d.N + 63) >> 6) + 3) >> 2;
+  if (id < SPH_GATE_SLOTS * words) reinterpret_cast<uint32_t*>(d.nbhd + (size_t)(id / words) * d.nbStride)[id % words] = 0u;
+}
+
 __global__ __launch_bounds__(SPH_BLOCK) void k_hash(SphDev d) {
   const int id = blockIdx.x * SPH_BLOCK + threadIdx.x;
-  if (id < SPH_GATE_SLOTS) d.skipGate[id] = 0u;  // the step's first kernel: the gate counts of the predict-correct loop start at zero
+  clear_wave_skip_state(d, id);
   if (id >= d.N) return;
   const float4 p = d.posOrig[id];
   // A non-finite coordinate means the simulation has blown up; such particles all hash into one cell and the search turns
@@ -27,7 +35,7 @@ struct CompactKey { int usedX, usedY, czBase, layers; };
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_hash_compact(SphDev d, CompactKey c) {
   const int id = blockIdx.x * SPH_BLOCK + threadIdx.x;
-  if (id < SPH_GATE_SLOTS) d.skipGate[id] = 0u;  // (see k_hash)
+  clear_wave_skip_state(d, id);
   if (id >= d.N) return;
   const float4 p = d.posOrig[id];
   if (!(fabsf(p.x) <= 3.0e38f && fabsf(p.y) <= 3.0e38f && fabsf(p.z) <= 3.0e38f)) atomicAdd(&d.dbg[6], 1u);  // (see k_hash)
@@ -299,6 +307,11 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cell_start(SphDev d, int first, i
     if (d.keys[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
   }
   d.cellStart[c] = (c == d.G) ? (uint32_t)d.N : (uint32_t)lo;
+  // A blown-up state — a key outside [0, G) (fewer than N keys lie below G) or a non-finite coordinate (counted by the hash
+  // kernel of this step) — closes every stage of the per-wave skipping: the search clamps the cells of such particles, which the
+  // cell relation of the neighbourhood bytes does not describe. Behind the kernel that zeroed the words.
+  if (c == d.G && (lo < d.N || d.dbg[6] != 0u))
+    for (int i = 0; i < SPH_GATE_SLOTS; i++) d.skipGate[i] = 1u;
 }
 
 int sphk_sort_post(sph_solver* s) {

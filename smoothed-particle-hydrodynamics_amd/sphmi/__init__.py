@@ -155,7 +155,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_position", "sph_read_velocity", "sph_read_density", "sph_read_particle_index",
                     "sph_read_position_async", "sph_read_position_wait", "sph_host_unregister", "sph_build_info",
                     "sph_read_buffer", "sph_read_neighbor_rows", "sph_synchronize", "sph_set_stage_timing", "sph_get_stage_times",
-                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_set_step_pipeline", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
+                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_set_step_pipeline", "sph_set_wave_skip", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
@@ -231,6 +231,8 @@ def device_lib():
         L.sph_set_step_chunks.argtypes = [C.c_void_p, C.c_int32]
         if hasattr(L, "sph_set_step_pipeline"):  # (optional: an A/B library built from an older csrc/ has no pipelined step)
             L.sph_set_step_pipeline.argtypes = [C.c_void_p, C.c_int32]
+        if hasattr(L, "sph_set_wave_skip"):  # (optional, likewise)
+            L.sph_set_wave_skip.argtypes = [C.c_void_p, C.c_int32]
         L.sph_get_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
         L.sph_last_error.restype = C.c_char_p
         L.sph_slab_init.argtypes = [C.c_void_p, C.POINTER(SphSlab), C.c_void_p]
@@ -517,7 +519,8 @@ _BUF_DTYPE = {"position": np.float32, "velocity": np.float32, "sortedPosition": 
               "neighborIds": np.int32, "particleIndex": np.uint32, "particleIndexBack": np.uint32,
               "gridCellIndex": np.uint32, "gridCellIndexFixedUp": np.uint32, "pressure": np.float32,
               "rho": np.float32, "debugCounters": np.uint32, "diagnosticTrace": np.uint32,
-              "pressureForceSkipped": np.uint8, "predictDensitySkipped": np.uint8}
+              "pressureForceSkipped": np.uint8, "predictDensitySkipped": np.uint8,
+              "pressureNeighbourhood": np.uint8, "movedNeighbourhood": np.uint8, "pressureFlags": np.uint8, "movedFlags": np.uint8}
 
 
 def type_mask(types):
@@ -1253,6 +1256,13 @@ class owHIPSolver:
         if not hasattr(self._L, "sph_set_step_pipeline"):
             raise SphError("this libsphmi has no sph_set_step_pipeline")
         return self._chk(self._L.sph_set_step_pipeline(self._h, int(depth)))
+
+    def set_wave_skip(self, mode=0):
+        """The per-wave skipping of the predict-correct loop: 0 the built-in policy, 1 the writers always mark and the consumers
+        always consult, 2 off. Results do not depend on it."""
+        if not hasattr(self._L, "sph_set_wave_skip"):
+            raise SphError("this libsphmi has no sph_set_wave_skip")
+        return self._chk(self._L.sph_set_wave_skip(self._h, int(mode)))
 
     def reset_stage_times(self):
         return self._chk(self._L.sph_reset_stage_times(self._h))

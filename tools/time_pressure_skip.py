@@ -9,7 +9,8 @@ bench.py; a library without the decision bytes reports null shares.
   config2     bench.py's config2_1M_cube block: 5 + K steps
   worm        bench.py's config3_worm block (muscles on): 5 + K steps
   dam_break   bench.py's evolved_dam_break block: --evolve steps, then K
-"""
+
+--wave-skip MODE sets the solver's policy (sph_set_wave_skip: 0 the built-in one, 1 always mark and consult, 2 the flags off)."""
 import argparse
 import json
 import os
@@ -52,15 +53,21 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=4)
     ap.add_argument("--evolve", type=int, default=1500)
+    ap.add_argument("--wave-skip", type=int, default=None, choices=[0, 1, 2])
     a = ap.parse_args()
-    out = {"scene": a.scene, "lib": os.path.basename(sphmi.LIB_PATH)}
+    out = {"scene": a.scene, "lib": os.path.basename(sphmi.LIB_PATH), "wave_skip": a.wave_skip}
+
+    def policy(hip):
+        if a.wave_skip is not None:
+            hip.set_wave_skip(a.wave_skip)
+        return hip
     if a.scene in ("box085", "box093"):
         box, lattice, mask = bench.WORKLOADS["config4_16M_box"]
         sc = scenes.liquid_box(box, lattice, spacing_in_r0=0.85 if a.scene == "box085" else 0.93, mask=mask)
         k = a.steps or 10
         ms = []
         for _ in range(a.repeats):
-            hip = scenes.hip_for(sc)
+            hip = policy(scenes.hip_for(sc))
             ms.append(round(timed(hip, 0, k), 4))
             out.update(shares(hip))
             out["pressure_max"] = float(hip.buffer("pressure").max())
@@ -69,7 +76,7 @@ def main():
     elif a.scene == "config2":
         box, lattice, mask = bench.WORKLOADS["config2_1M_cube"]
         sc = scenes.liquid_box(box, lattice, mask=mask)
-        hip = scenes.hip_for(sc)
+        hip = policy(scenes.hip_for(sc))
         k = a.steps or 50
         timed(hip, 0, 5)
         out.update(particles=sc["cfg"].particleCount, steps=k, ms_per_step=[round(timed(hip, 5 + r * k, k), 4) for r in range(a.repeats)], **shares(hip))
@@ -77,7 +84,7 @@ def main():
     elif a.scene == "worm":
         cfg = sphmi.default_config()
         w = sphmi.generate_worm(cfg)
-        hip = sphmi.owHIPSolver(cfg, w["position"], w["velocity"], w["elastic"], w["membranes"], w["particle_membranes"])
+        hip = policy(sphmi.owHIPSolver(cfg, w["position"], w["velocity"], w["elastic"], w["membranes"], w["particle_membranes"]))
         k = a.steps or 50
         signal = lambda i: hip.updateMuscleActivityData(sphmi.muscle_signal(i, cfg.muscleCount))  # noqa: E731
         timed(hip, 0, 5, signal)
@@ -86,7 +93,7 @@ def main():
     else:
         box, lattice, mask = bench.DAM_BREAK
         sc = scenes.liquid_box(box, lattice, mask=mask)
-        hip = scenes.hip_for(sc)
+        hip = policy(scenes.hip_for(sc))
         k = a.steps or 50
         rest = timed(hip, 0, k)
         at_rest = shares(hip)
