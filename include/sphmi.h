@@ -762,6 +762,64 @@ int sph_field_diffuse(sph_solver* s, int32_t slot, float coefficient, int32_t su
 int sph_field_diagnostics(sph_solver* s, int32_t slot, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
                           uint32_t typeMask, double* out /* host, count x 8 */);
 
+/* ---- Kinematic bodies: groups of boundary particles moved between steps (no reference counterpart: the
+ * reference's walls stay where the scene put them) -------------------------------------------------------------------------------
+ * Up to SPH_MAX_BODIES bodies per solver. A body is an ORDERED list of original ids of boundary particles ((int)position.w == 3)
+ * together with their REFERENCE PLACEMENT: the position float4 and the wall normal float4 (a boundary particle's velocity slot)
+ * they had when the body was defined, kept on the device. sph_body_set_pose places the members at a rigid image of the reference
+ * placement; the liquid answers through what the step already does with boundary neighbours (the density sum, and the position
+ * and velocity correction of the integration). No step kernel knows about bodies.
+ * STATE: like the particle edits above, the calls act on the CURRENT state (sph_read_position / sph_read_velocity, original-id
+ * order). Between two steps that pair of arrays is the solver's state, so a solver whose walls were moved in place continues bit
+ * for bit like a solver newly created from the moved arrays.
+ * DEFINING. sph_body_define_ids keeps the members in the caller's order. An entry r is an OFFENDER when origIds[r] >= N, when
+ * that particle is not a boundary particle, or when its id occurs more than once in the list (every occurrence counts). With any
+ * offender the call is SPH_ERR_INVALID, the message names their number and the lowest offending list index, and the slot keeps
+ * what it held. count == 0, count > N and a slot outside 0..SPH_MAX_BODIES-1 are SPH_ERR_INVALID too. sph_body_define_region
+ * takes every boundary particle whose float position lies in the half-open box, by the compare of sph_remove_region with typeMask
+ * fixed to type 3 (+-infinity allowed, NULL = everywhere, a NaN bound is SPH_ERR_INVALID); the members come in ascending original
+ * id and *count receives their number. An empty result is SPH_ERR_INVALID (*count = 0) and leaves the slot as it was. Defining a
+ * slot that is in use replaces its body once the new definition has succeeded. sph_body_release frees a slot (a free slot:
+ * a no-op); sph_body_count gives the member count, 0 for a free slot; sph_body_read copies out the ids and the reference rows in
+ * member order (any pointer may be NULL; a free slot writes nothing). Bodies may overlap: poses apply in call order and the last
+ * one wins.
+ * POSE. pose = 12 floats, row-major 3 x 4, (R | t): R00 R01 R02 tx, R10 R11 R12 ty, R20 R21 R22 tz. For member k with reference
+ * position p and reference normal n, every operation one float operation in exactly this order, no contraction:
+ *     x' = ((R00*p.x + R01*p.y) + R02*p.z) + tx        nx' = (R00*n.x + R01*n.y) + R02*n.z
+ *     y' = ((R10*p.x + R11*p.y) + R12*p.z) + ty        ny' = (R10*n.x + R11*n.y) + R12*n.z
+ *     z' = ((R20*p.x + R21*p.y) + R22*p.z) + tz        nz' = (R20*n.x + R21*n.y) + R22*n.z
+ * and p.w and n.w copied bit for bit. position[id_k] = (x', y', z', p.w), velocity[id_k] = (nx', ny', nz', n.w). The linear part
+ * is applied to the normal as given and the result is not renormalised: passing a rotation is the caller's business. The pose is
+ * always applied to the REFERENCE placement, never to the current one: a body driven for 10^5 steps accumulates no rounding.
+ * A pose word that is not finite is SPH_ERR_INVALID. Every new position gets the validation of sph_add_particles (finite; inside
+ * the box with wide cell ids). The call is ALL OR NOTHING: if any member fails, nothing is written, *offenders receives their
+ * number, *lowestMember the lowest failing member index k (not an id), and the call returns SPH_ERR_INVALID. On success
+ * *offenders = 0, *lowestMember = -1 and *maxMoveInR0 = sqrtf(max_k d2_k) / r0 in float, with d = new - current position per
+ * axis and d2 = (dx*dx + dy*dy) + dz*dz in float on the device, the maximum taken on the bit patterns of the non-negative floats
+ * (order-independent). This is the caller's TUNNELLING NUMBER, the counterpart of sph_field_diffuse's stability number: a wall
+ * that moves about r0 or more in one step passes through liquid instead of pushing it. No limit is enforced. The three outputs may
+ * be NULL.
+ * WHAT A POSE LEAVES ALONE. The particle set does not change, so the sorted state of the last completed step, which the analysis
+ * calls read, stays valid (it is one step behind the current state anyway), and so do selections, meshes, labellings, renders, the
+ * edit map, tracers and carried fields. The liquid signature of sph_slab_liquid_signature does not see boundary particles.
+ * EDITS CARRY THE BODIES, like the fields. A successful removal maps every member id through the removal's old-to-new map
+ * (sph_read_edit_map); removed members are dropped together with their reference rows, the others keep their order; a body left
+ * without members is released. Additions, failed or counting edits, and a removal of nothing leave the bodies untouched.
+ * Rules: on the solver's stream, not stages (no stage timing); each call waits for the results it returns. SPH_ERR_INVALID for a
+ * slab solver and for null pointers where none is allowed. SPH_ERR_ORDER while a stage-by-stage step is half done (from the first
+ * stage entry point of a step until its integrate stage, or with elastic matter its membranes-finalize stage, has run; sph_step is
+ * never half done), and for sph_body_set_pose on a free slot. A failed call leaves the solver and the slot as they were. An
+ * outstanding sph_read_position_async finishes its device copy before a pose moves anything. Device memory: 36 bytes per member,
+ * once more for the largest body as staging, and 16 bytes per 64 particles while a definition is checked. */
+#define SPH_MAX_BODIES 16
+int sph_body_define_ids(sph_solver* s, int32_t slot, const uint32_t* origIds /* host */, int64_t count);
+int sph_body_define_region(sph_solver* s, int32_t slot, const float* region6 /* host or NULL = everywhere */, int64_t* count);
+int sph_body_release(sph_solver* s, int32_t slot);
+int sph_body_count(sph_solver* s, int32_t slot, int64_t* count);
+int sph_body_read(sph_solver* s, int32_t slot, uint32_t* origIds, float* refPosition4, float* refNormal4 /* host, count x 4 */);
+int sph_body_set_pose(sph_solver* s, int32_t slot, const float pose[12], int64_t* offenders, int64_t* lowestMember,
+                      float* maxMoveInR0);
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -507,6 +507,12 @@ static int run_stage(sph_solver* s, const Stage& st) {
   StageTimer t(s, st.timer);
   const int rc = st.launch(s);
   if (rc == SPH_OK) s->progress = st.gain == P_HASH ? P_HASH : s->progress | st.gain;  // (a new step starts at the hash)
+  // posOrig / velOrig are the solver's state again once integrate has run, or with elastic matter the membranes' finalize pass,
+  // which rewrites them; the membrane stages of a solver without elastic matter are no-ops behind integrate
+  const bool membraneStage = st.timer == SPH_ST_MEMBRANES;
+  if (&st == &kIntegrate) s->stepOpen = s->d.hasElastic != 0;
+  else if (&st == &kMembranesFinalize) s->stepOpen = false;
+  else if (!membraneStage) s->stepOpen = true;
   return rc;
 }
 
@@ -766,6 +772,7 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
 #undef RUN
   s->progress = P_HASH | P_SORT | P_SORTPOST | P_INDEXPOST | P_FIND | P_DENSITY | P_FORCES | P_PREDICTPOS | P_PREDICTDENS |
                 P_PRESSUREFORCE;
+  s->stepOpen = false;
   return SPH_OK;
 }
 

@@ -22,6 +22,7 @@ static void edit_commit(sph_solver* s, int newN) {
   s->d.N = newN;
   sph_state_changes(s);
   s->progress = 0;
+  s->stepOpen = false;  // (a stage-by-stage step the edit cut short is abandoned: the next stage has to be the hash)
 }
 
 // the id map of a removal of a set of N particles is current from now on (identity: nothing was marked, nothing moved)
@@ -62,6 +63,8 @@ static int edit_remove_marked(sph_solver* s, const char* what, bool countOnly, i
   // membDelta (orig-indexed): all zero again, as sph_create leaves it (the step clears it before it reads it anyway)
   if (s->d.membDelta) SPH_HIP(hipMemsetAsync(s->d.membDelta, 0, sizeof(float4) * (size_t)N, s->stream));
   rc = sph_fields_follow_removal(s, N, (const int32_t*)s->d.backIndex);  // the carried fields move with position and velocity
+  if (rc != SPH_OK) return rc;
+  rc = sph_bodies_follow_removal(s, N, (const int32_t*)s->d.backIndex);  // the kinematic bodies keep their surviving members
   if (rc != SPH_OK) return rc;
   SPH_HIP(hipStreamSynchronize(s->stream));
   std::swap(s->d.posOrig, s->d.sortedPos);

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (sph_api.hip: errors, timing, solver lifetime, stages, the fused step; sph_api_read.hip:
 // read-back and reference-layout export; sph_api_slab.hip: the slab protocol; sph_api_analysis.hip: sampling, surfaces, gradients,
-// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields): the order contract and the entry checks,
+// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields; sph_api_body.hip: kinematic bodies): the order contract and the entry checks,
 // the one rule for "the state has changed" and for results derived from it, and the per-particle input checks of sph_create
 // and the adding calls.
 #pragma once
@@ -82,6 +82,9 @@ int sph_selection_current(sph_solver* s, const char* what);
 // no slot in existence neither enqueues anything.
 int sph_fields_follow_removal(sph_solver* s, int oldN, const int32_t* map);  // every slot through the removal's old-to-new map
 int sph_fields_follow_add(sph_solver* s, int first, int count);              // ids first .. first + count get each slot's inflow
+// (body in sph_api_body.hip) What a removal does to the kinematic bodies, next to the fields: member ids through the old-to-new map,
+// removed members dropped with their reference rows, a body left empty released. Blocking per body in use (its new count).
+int sph_bodies_follow_removal(sph_solver* s, int oldN, const int32_t* map);
 
 // (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
 #define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)

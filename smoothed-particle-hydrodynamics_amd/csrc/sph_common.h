@@ -242,6 +242,15 @@ struct sph_solver {
   // tracerCount tracers; independent of the particle state, so no stage, step or edit touches it
   SphScratch tracerBuf;
   int tracerCount = 0;
+  // kinematic bodies (sph_body_*, sph_body.hip): per slot the members' original ids (uint32[count]) and their
+  // reference rows (float4[2 count]: position, normal, position, ...); a slot is in use while its count is > 0. A definition and a
+  // removal's compaction build the new arrays in the stage pair, which is then swapped with the slot's own. bodyBuf: the counters
+  // of a call (256 bytes), then the two 1-bit-per-particle masks of a definition by ids or the scan scratch of a compaction.
+  SphScratch bodyIds[SPH_MAX_BODIES], bodyRef[SPH_MAX_BODIES], bodyStageIds, bodyStageRef, bodyBuf;
+  int bodyCount[SPH_MAX_BODIES] = {};
+  // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
+  // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
+  bool stepOpen = false;
 
   sph_solver() = default;
   // Frees everything the solver owns (sph_api.hip): the recorded device allocations, then pinned buffers, host registrations,
@@ -480,6 +489,26 @@ int sphk_edit_count(sph_solver* s, int protectEnd, void* scratch, uint32_t** tot
 int sphk_edit_scatter(sph_solver* s, void* scratch, uint32_t total, float4* posOut, float4* velOut, int32_t* map);
 // lattice points into posOrig / velOrig [N, N + count); *counters = device words {points that fail validation, the lowest such k}
 int sphk_edit_emit(sph_solver* s, const EditLattice& a, int count, void* scratch, uint32_t** counters);
+// sph_body.hip (kinematic bodies; acts on the original-order state posOrig / velOrig). Device pointers.
+struct BodyPose {
+  float m[12];  // row-major 3 x 4, (R | t)
+  int wide;     // wide cell ids: a position outside the box fails
+  float xmin, xmax, ymin, ymax, zmin, zmax;
+};
+size_t sphk_body_check_bytes(int N);  // the counters and the two masks of sphk_body_check_ids
+// *counters = device words {offending entries of ids[0..count), the lowest offending index or 0xffffffff}
+int sphk_body_check_ids(sph_solver* s, const uint32_t* ids, int count, void* scratch, uint32_t** counters);
+// blockCnt of the selection layout from the mask sphk_edit_mark_region wrote (marked particles per block), then its scan:
+// *totals = 2 device words, the number of marked particles; sphk_select_scatter then lists them in ascending id
+int sphk_body_count_marks(sph_solver* s, void* scratch, uint32_t** totals);
+int sphk_body_gather(sph_solver* s, const uint32_t* ids, int count, float4* ref);  // ref[2k], ref[2k+1] = posOrig, velOrig [ids[k]]
+// *counters = device words {members whose new position fails, the lowest such member or 0xffffffff, the bits of max d2}
+int sphk_body_pose_validate(sph_solver* s, const BodyPose& a, const uint32_t* ids, const float4* ref, int count, uint32_t* counters);
+int sphk_body_pose_commit(sph_solver* s, const BodyPose& a, const uint32_t* ids, const float4* ref, int count);
+size_t sphk_body_compact_bytes(int count);  // the counters and the scan scratch of sphk_body_compact for a body of `count` members
+// members whose map[id] >= 0, in order, with their rows: idsOut / refOut (room for `count`); *totals = device word, their number
+int sphk_body_compact(sph_solver* s, const uint32_t* ids, const float4* ref, int count, const int32_t* map, int oldN, void* scratch,
+                      uint32_t* idsOut, float4* refOut, uint32_t** totals);
 // sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
 // values in original-id order (device). Read-only on every solver array.
 size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word

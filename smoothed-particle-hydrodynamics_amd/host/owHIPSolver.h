@@ -220,6 +220,34 @@ class owHIPSolver {
     return n;
   }
 
+  // beyond the reference: walls that move between two steps (a piston, a paddle, a blade, a sliding gate). Up to SPH_MAX_BODIES
+  // bodies, each an ordered list of original ids of boundary particles with the position and normal they had when the body was
+  // defined (its reference placement). bodyDefineIds takes a list, bodyDefineRegion every boundary particle inside region6 (or
+  // null = everywhere) in ascending id, and returns the member count; bodyRead copies ids and reference rows (any pointer may be
+  // null). bodySetPose places the members at pose (row-major 3 x 4, (R | t)) applied to the reference placement, all or nothing,
+  // and returns the largest displacement against the current position in units of r0: from about 1 on the wall tunnels through
+  // liquid. The analysis state stays valid; removals carry the bodies along (include/sphmi.h, sph_body_*)
+  void bodyDefineIds(int slot, const uint32_t* origIds, int64_t count) { check(sph_body_define_ids(s_, slot, origIds, count), "bodyDefineIds"); }
+  int64_t bodyDefineRegion(int slot, const float* region6) {
+    int64_t count = 0;
+    check(sph_body_define_region(s_, slot, region6, &count), "bodyDefineRegion");
+    return count;
+  }
+  void bodyRelease(int slot) { check(sph_body_release(s_, slot), "bodyRelease"); }
+  int64_t bodyCount(int slot) {
+    int64_t count = 0;
+    check(sph_body_count(s_, slot, &count), "bodyCount");
+    return count;
+  }
+  void bodyRead(int slot, uint32_t* origIds, float* refPosition4, float* refNormal4) {
+    check(sph_body_read(s_, slot, origIds, refPosition4, refNormal4), "bodyRead");
+  }
+  float bodySetPose(int slot, const float pose[12], int64_t* offenders = nullptr, int64_t* lowestMember = nullptr) {
+    float maxMove = 0.f;
+    check(sph_body_set_pose(s_, slot, pose, offenders, lowestMember, &maxMove), "bodySetPose");
+    return maxMove;
+  }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

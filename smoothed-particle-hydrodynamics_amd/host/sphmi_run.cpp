@@ -68,6 +68,14 @@
 //        gate that opens at step 200 is `--drain-types 3 --drain-region ... --drain-at 200`. The drain runs before the emitter.
 //        Each step with an edit prints `_edit: step S removed R added A particles N`. With these options the position read-back
 //        is the blocking one, and --out holds the final count of particles.
+//   ... --body-region X0 Y0 Z0 X1 Y1 Z1 [--body-velocity VX VY VZ] [--body-spin AX AY AZ CX CY CZ RATE] [--body-from STEP] [--body-until STEP]
+//        a wall that moves (sph_body_*): the boundary particles inside the region at the start ("inf" / "-inf" are
+//        accepted as bounds) are body 0, and their placement then is its reference placement. Before every step S with
+//        from <= S < until (defaults 0 and the end of the run), with k = S - from + 1, the body is placed at the reference
+//        placement turned by k * RATE radians about the line through (CX, CY, CZ) along (AX, AY, AZ) and then shifted by
+//        k * (VX, VY, VZ) (scene units per step); the pose is computed in double and narrowed once. Each moved step prints
+//        `_body: step S members M max_move X` (X: the largest displacement in units of r0, %.9g; from about 1 on the wall
+//        tunnels through liquid). With these options the position read-back is the blocking one.
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -204,6 +212,26 @@ static bool write_file(const std::string& path, const void* header, size_t heade
   return ok;
 }
 
+// The pose (row-major 3 x 4, (R | t)) of the --body options after k moved steps: the reference placement turned by k * rate about
+// the line through c along a (spin = ax ay az cx cy cz rate; Rodrigues' formula as sphmi.frames.pose_rotate writes it), then
+// shifted by k * vel. Computed in double, narrowed once; without a spin the linear part is the exact identity.
+static void body_pose(const double spin[7], const double vel[3], double k, float pose[12]) {
+  double a[3] = {spin[0], spin[1], spin[2]};
+  const double n = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  for (double& x : a) x /= n;
+  const double angle = spin[6] * k, c = std::cos(angle), s = std::sin(angle);
+  const double K[3][3] = {{0.0, -a[2], a[1]}, {a[2], 0.0, -a[0]}, {-a[1], a[0], 0.0}};
+  for (int r = 0; r < 3; r++) {
+    double row[3], t = spin[3 + r];
+    for (int q = 0; q < 3; q++) {
+      row[q] = (c * (r == q ? 1.0 : 0.0) + s * K[r][q]) + (1.0 - c) * (a[r] * a[q]);
+      t -= row[q] * spin[3 + q];
+    }
+    for (int q = 0; q < 3; q++) pose[4 * r + q] = (float)row[q];
+    pose[4 * r + 3] = (float)(t + vel[r] * k);
+  }
+}
+
 int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
@@ -230,6 +258,8 @@ int main(int argc, char** argv) {
   int emitDims[3] = {0, 0, 0}, emitEvery = 1, emitUntil = -1;
   bool drainSeen = false, drainRegionSeen = false, drainTypesSeen = false; unsigned drainMask = 0; int drainEvery = 0, drainAt = -1;
   float drainRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+  bool bodySeen = false, bodyRegionSeen = false, bodySpinSeen = false; float bodyRegion[6] = {0, 0, 0, 0, 0, 0};
+  double bodyVel[3] = {0, 0, 0}, bodySpin[7] = {0, 0, 1, 0, 0, 0, 0}; int bodyFrom = 0, bodyUntil = -1;
   bool dyeSeen = false, dyeRegionSeen = false, dyeEverySeen = false; float dyeRegion[6] = {0, 0, 0, 0, 0, 0}, dyeInflow = 0.f, dyeDiffusivity = 0.f; int dyeEvery = 0;
   int streamSeeds[2] = {0, 0}, streamEvery = 0, streamMaxSteps = 256; float streamStep = 0.f; bool streamSeen = false; const char* streamDir = nullptr;
   int tracerSeeds[2] = {0, 0}, tracersEvery = 1; bool tracersSeen = false;
@@ -257,6 +287,11 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--emit-every") && i + 1 < argc) { emitEvery = atoi(argv[++i]); emitSeen = true; }
     else if (!strcmp(argv[i], "--emit-until") && i + 1 < argc) { emitUntil = atoi(argv[++i]); emitSeen = true; }
     else if (!strcmp(argv[i], "--drain-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) drainRegion[k] = (float)atof(argv[++i]); drainSeen = drainRegionSeen = true; }
+    else if (!strcmp(argv[i], "--body-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) bodyRegion[k] = (float)atof(argv[++i]); bodySeen = bodyRegionSeen = true; }
+    else if (!strcmp(argv[i], "--body-velocity") && i + 3 < argc) { for (int k = 0; k < 3; k++) bodyVel[k] = atof(argv[++i]); bodySeen = true; }
+    else if (!strcmp(argv[i], "--body-spin") && i + 7 < argc) { for (int k = 0; k < 7; k++) bodySpin[k] = atof(argv[++i]); bodySeen = bodySpinSeen = true; }
+    else if (!strcmp(argv[i], "--body-from") && i + 1 < argc) { bodyFrom = atoi(argv[++i]); bodySeen = true; }
+    else if (!strcmp(argv[i], "--body-until") && i + 1 < argc) { bodyUntil = atoi(argv[++i]); bodySeen = true; }
     else if (!strcmp(argv[i], "--drain-every") && i + 1 < argc) { drainEvery = atoi(argv[++i]); drainSeen = true; }
     else if (!strcmp(argv[i], "--drain-at") && i + 1 < argc) { drainAt = atoi(argv[++i]); drainSeen = true; }
     else if (!strcmp(argv[i], "--drain-types")) {
@@ -440,11 +475,24 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--dye-inflow V: a finite number; --dye-diffusivity D: a finite number >= 0; --dye-every K: K > 0\n");
     return 2;
   }
+  if (bodySeen) {
+    bool ok = bodyRegionSeen && bodyFrom >= 0;
+    for (float b : bodyRegion) ok = ok && !std::isnan(b);
+    for (double v : bodyVel) ok = ok && std::isfinite(v);
+    for (double v : bodySpin) ok = ok && std::isfinite(v);
+    if (bodySpinSeen && !(bodySpin[0] * bodySpin[0] + bodySpin[1] * bodySpin[1] + bodySpin[2] * bodySpin[2] > 0)) ok = false;
+    if (!ok) {
+      fprintf(stderr, "--body-region X0 Y0 Z0 X1 Y1 Z1 (no bound a NaN) is needed by the other --body options; --body-velocity and "
+                      "--body-spin take finite numbers, the spin axis is not zero; --body-from STEP: STEP >= 0\n");
+      return 2;
+    }
+  }
   const bool dyeing = dyeSeen;
   const bool emitting = emitSeen, draining = drainSeen, editing = emitSeen || drainSeen;
+  const bool moving = bodySeen;
   // the host buffer of the asynchronous read-back is page-locked in place at its first size: with a changing count the driver
-  // reads the positions the blocking way
-  if (editing) blockingRead = true;
+  // reads the positions the blocking way; so it does with a body, whose pose waits for a read-back in flight anyway
+  if (editing || moving) blockingRead = true;
   sph_render_view renView;
   memset(&renView, 0, sizeof(renView));
   if (rendering) {
@@ -606,11 +654,24 @@ int main(int argc, char** argv) {
       ocl_solver->fieldCreate(0, nullptr, dyeInflow);
       if (dyeRegionSeen) ocl_solver->fieldSetRegion(0, 1.0f, dyeRegion, dyeMask);
     }
+    int64_t bodyMembers = 0;
+    if (moving) {
+      bodyMembers = ocl_solver->bodyDefineRegion(0, bodyRegion);
+      if (bodyUntil < 0) bodyUntil = steps;
+    }
     Watch helper; helper.quiet = quiet;
     double total = 0;
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
       helper.refresh();
       if (!quiet) printf("\n[[ Step %d ]]\n", iterationCount);
+      if (moving && ocl_solver->bodyCount(0) > 0 && iterationCount >= bodyFrom && iterationCount < bodyUntil) {  // (a drain may have taken the body)
+        float pose[12];
+        body_pose(bodySpin, bodyVel, (double)(iterationCount - bodyFrom + 1), pose);
+        const float maxMove = ocl_solver->bodySetPose(0, pose);
+        bodyMembers = ocl_solver->bodyCount(0);
+        printf("_body: step %d members %lld max_move %.9g\n", iterationCount, (long long)bodyMembers, (double)maxMove);
+        helper.report("_body: \t\t\t%9.3f ms\n");
+      }
       if (editing) {  // between two steps: the drain first, then the emitter
         int64_t removed = 0, added = 0;
         bool edited = false;

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SPHMI_LIB", os.path.join(_PKG, "libsphmi.so"))  # SPH
 HOST_LIB_PATH = os.path.join(_PKG, "libsphmi_host.so")
 
 ABI_VERSION = 2
+MAX_BODIES = 16  # SPH_MAX_BODIES: kinematic-body slots per solver
 SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
 SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
 DIAG_WORDS = 32  # sph_diagnostics record (frames.DIAG_FIELDS)
@@ -166,7 +167,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_remove_selection", "sph_remove_ids", "sph_add_particles", "sph_emit_lattice", "sph_read_edit_map", "sph_field_create",
                     "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
                     "sph_field_diffuse", "sph_field_diagnostics", "sph_trace_streamlines", "sph_tracers_set", "sph_tracers_advect",
-                    "sph_tracers_read"] + _STAGE_FUNCS
+                    "sph_tracers_read", "sph_body_define_ids", "sph_body_define_region", "sph_body_release", "sph_body_count",
+                    "sph_body_read", "sph_body_set_pose"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -292,6 +294,13 @@ def device_lib():
         L.sph_tracers_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sph_tracers_advect.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SphTraceParams), C.c_void_p, C.c_void_p]
         L.sph_tracers_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_body_set_pose"):  # (optional: an A/B library built from an older csrc/ has no kinematic bodies)
+            L.sph_body_define_ids.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+            L.sph_body_define_region.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+            L.sph_body_release.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_body_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            L.sph_body_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sph_body_set_pose.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -1044,6 +1053,60 @@ class owHIPSolver:
         out = np.empty(max(n, 1), np.int32)
         self._chk(self._L.sph_read_edit_map(self._h, _ptr(out)))
         return out[:n]
+
+    # --- kinematic bodies (sph_body_*): groups of boundary particles placed by a pose between two steps ---
+    def body_define_ids(self, slot, ids):
+        """Make body `slot` (0..MAX_BODIES-1) of the boundary particles with the listed original ids, in that order; their current
+        position and normal become the body's reference placement. An id >= N, a particle that is not a boundary particle and
+        an id listed twice are refused. Returns the member count."""
+        a = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise SphError("body_define_ids: ids must be unsigned 32-bit integers")
+        a = a.astype(np.uint32)
+        self._chk(self._L.sph_body_define_ids(self._h, int(slot), _ptr(a) if a.size else None, a.size))
+        return int(a.size)
+
+    def body_define_region(self, slot, region=None):
+        """Make body `slot` of every boundary particle whose current position lies in the half-open box `region` (remove_region's
+        compare; None = everywhere), in ascending original id. An empty result is refused. Returns the member count."""
+        rg = _region(region, "body_define_region")
+        count = np.zeros(1, np.int64)
+        self._chk(self._L.sph_body_define_region(self._h, int(slot), _ptr(rg), _ptr(count)))
+        return int(count[0])
+
+    def body_release(self, slot):
+        self._chk(self._L.sph_body_release(self._h, int(slot)))
+
+    def body_count(self, slot):
+        """The member count of body `slot`; 0 for a free slot."""
+        count = np.zeros(1, np.int64)
+        self._chk(self._L.sph_body_count(self._h, int(slot), _ptr(count)))
+        return int(count[0])
+
+    def body_read(self, slot):
+        """(ids uint32[M], reference position float32[M, 4], reference normal float32[M, 4]) of body `slot`, in member order."""
+        m = self.body_count(slot)
+        ids, pos, nrm = np.empty(max(m, 1), np.uint32), np.empty((max(m, 1), 4), np.float32), np.empty((max(m, 1), 4), np.float32)
+        self._chk(self._L.sph_body_read(self._h, int(slot), _ptr(ids), _ptr(pos), _ptr(nrm)))
+        return ids[:m], pos[:m], nrm[:m]
+
+    def body_set_pose(self, slot, pose):
+        """Place the members of body `slot` at pose (float32[3, 4] = (R | t), frames.pose_*) applied to their REFERENCE placement:
+        position and wall normal (include/sphmi.h states the float expression). All or nothing: if a new position is not finite,
+        or with wide cell ids outside the box, nothing moves and the SphError carries `offenders` and `lowest_member`. Returns
+        max_move, the largest displacement of a member against its current position in units of r0: from about 1 on the wall
+        tunnels through liquid."""
+        p = np.ascontiguousarray(pose, np.float32).reshape(-1)
+        if p.size != 12:
+            raise SphError("body_set_pose: pose must be 3 x 4 (R | t)")
+        counts = np.zeros(2, np.int64)
+        move = np.zeros(1, np.float32)
+        rc = self._L.sph_body_set_pose(self._h, int(slot), _ptr(p), _ptr(counts[0:1]), _ptr(counts[1:2]), _ptr(move))
+        if rc != 0:
+            e = SphError("libsphmi: %s (status %d)" % (self._L.sph_last_error().decode(), rc))
+            e.offenders, e.lowest_member = int(counts[0]), int(counts[1])
+            raise e
+        return np.float32(move[0])
 
     # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
     def _field_values(self, values, what):

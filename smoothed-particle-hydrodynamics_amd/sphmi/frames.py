@@ -43,6 +43,10 @@ the colour image, `thickness_in_scene_units` scales the thickness image; FIELD_R
 Integral curves (owHIPSolver.streamlines / tracers): `seed_rake` and `seed_plane` make seed points on a segment and on a plane,
 `write_vtk_polylines` / `read_polylines` write and read the curves as legacy-VTK polylines with the speed as point data, the
 format `sphmi_run --stream-out` writes.
+
+Kinematic bodies (owHIPSolver.body_set_pose): `pose_identity`, `pose_translate`, `pose_rotate` and `pose_compose` build the
+float32[3, 4] pose (R | t) in float64 and narrow it once; `piston` and `spin` return the pose of a wave-maker or a blade for a
+step number, always relative to the body's reference placement.
 """
 import math
 import struct
@@ -991,3 +995,59 @@ def read_polylines(path):
     if int(line().split()[1]) != total or not line().startswith("SCALARS speed") or line() != "LOOKUP_TABLE default":
         raise ValueError("read_polylines: %s has no speed point data" % path)
     return points, lengths, block(total, ">f4").astype(np.float32)
+
+
+# ---- kinematic bodies (owHIPSolver.body_set_pose; include/sphmi.h, sph_body_set_pose) ----
+# A pose is float32[3, 4] = (R | t), always relative to the body's REFERENCE placement. Every helper computes in float64 and
+# narrows once, at the end; pose_compose widens its arguments again, so a chain of compositions rounds once per link.
+def _pose32(R, t):
+    out = np.empty((3, 4), np.float64)
+    out[:, :3] = R
+    out[:, 3] = t
+    return out.astype(np.float32)
+
+
+def pose_identity():
+    return _pose32(np.eye(3), np.zeros(3))
+
+
+def pose_translate(v):
+    """The pose that shifts the reference placement by v = (vx, vy, vz)."""
+    return _pose32(np.eye(3), np.asarray(v, np.float64).reshape(3))
+
+
+def pose_rotate(axis, angle, about=(0.0, 0.0, 0.0)):
+    """The pose that turns the reference placement by `angle` (radians, right-handed) about the line through the point `about`
+    along `axis` (normalised here): Rodrigues' R = cos I + sin [a]x + (1 - cos) a a^T and t = about - R about."""
+    a = np.asarray(axis, np.float64).reshape(3)
+    n = math.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
+    if not n > 0:
+        raise ValueError("pose_rotate: the axis is zero")
+    a = a / n
+    c, s = math.cos(float(angle)), math.sin(float(angle))
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    R = c * np.eye(3) + s * K + (1.0 - c) * np.outer(a, a)
+    o = np.asarray(about, np.float64).reshape(3)
+    return _pose32(R, o - R @ o)
+
+
+def pose_compose(a, b):
+    """The pose that applies b first and a second: (Ra Rb | Ra tb + ta)."""
+    a, b = (np.asarray(p, np.float64).reshape(3, 4) for p in (a, b))
+    return _pose32(a[:, :3] @ b[:, :3], a[:, :3] @ b[:, 3] + a[:, 3])
+
+
+def piston(direction, amplitude, period, step):
+    """The pose of a piston at step number `step`: the reference placement shifted along `direction` (normalised here) by
+    amplitude * sin(2 pi step / period); the identity at step 0."""
+    d = np.asarray(direction, np.float64).reshape(3)
+    n = math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    if not n > 0 or not float(period) != 0.0:
+        raise ValueError("piston: the direction and the period must not be zero")
+    return pose_translate(d / n * (float(amplitude) * math.sin(2.0 * math.pi * float(step) / float(period))))
+
+
+def spin(axis, about, rate, step):
+    """The pose of a blade at step number `step`: the reference placement turned by rate * step radians about the line through
+    `about` along `axis`; the identity at step 0."""
+    return pose_rotate(axis, float(rate) * float(step), about)
