@@ -490,7 +490,8 @@ int sph_membrane_measure(sph_solver* s, float* out /* host, numOfMembranes x 8, 
  *   28..30   sum aF          31..33   sum aP           34..42   sum tau_c for c = 1, 2, 3 (torque about the origin per unit mass)
  *   43..45   sum w_c (power per unit mass)             46..48   sum n_c             49..63   0
  * SCOPE. Only K7 and K12 are decomposed. The spring and muscle accelerations are sph_elastic_measure's. The boundary hand-off
- * inside integrate and the membrane interaction are position corrections, not forces, and are not reported. The reference's
+ * inside integrate and the membrane interaction are position corrections, not forces, and are not reported here
+ * (sph_wall_measure reports the former). The reference's
  * pressure term divides by rhoStar_j, so it is not antisymmetric: the reaction on class c is only approximately minus what
  * class c exerts, and no word here pretends otherwise.
  * Rules: blocking, on the solver's stream, read-only on every solver array (a mesh, a labelling, a selection and a render stay
@@ -819,6 +820,80 @@ int sph_body_count(sph_solver* s, int32_t slot, int64_t* count);
 int sph_body_read(sph_solver* s, int32_t slot, uint32_t* origIds, float* refPosition4, float* refNormal4 /* host, count x 4 */);
 int sph_body_set_pose(sph_solver* s, int32_t slot, const float pose[12], int64_t* offenders, int64_t* lowestMember,
                       float* maxMoveInR0);
+
+/* ---- Wall loads: contact and force terms per kinematic body (no reference counterpart) --------------------------
+ * What a set of boundary particles did to each non-boundary particle in the last completed step: the wall's main action, the
+ * position shift and velocity reflection inside integrate (the reference's computeInteractionWithBoundaryParticles), and the K7 /
+ * K12 terms of sph_force_measure, both attributed to the set.
+ * STATE: the sorted state and neighbour rows of the last completed step, as sph_force_measure describes them, and that step's
+ * buffer "acceleration", both halves (a0 = acceleration[i], a1 = acceleration[N + i]). The walls are where that step saw them:
+ * a pose applied since does not change the answer. dt = timeStep, posTimeStep = timeStep * simulationScaleInv (float).
+ * THE WALL SET S. slot 0..SPH_MAX_BODIES-1: the members of that body as it is defined now, by original id, mapped to sorted
+ * indices through the step's particleIndex; SPH_WALL_ALL: every boundary particle; SPH_WALL_NO_BODY: the boundary particles that
+ * are members of no body. The set of a free slot is SPH_ERR_ORDER.
+ * CONTRACT, for a sorted particle i that is not a boundary particle; all arithmetic in float, one operation at a time in the
+ * written order, no contraction, IEEE division and square root. x, v: sortedPosition[i], sortedVelocity[i].
+ *   Before contact, exactly as integrate:
+ *     a = a0 + a1 per component (xyz);  nv = v + dt*a (xyz), nv.w = v.w + dt*0.f;  x0 = x + posTimeStep*nv (xyz);
+ *     x0 clamped to the box: x0.c < min_c -> min_c, then x0.c > max_c - 0.000001f -> max_c - 0.000001f;
+ *     u0 = (v + nv) * 0.5f on all four lanes.
+ *   Slot walk, k = 0..31 ascending, over the slots with j = row(i)[k] != -1 and (int)sortedPosition[j].w == 3; pb =
+ *   sortedPosition[j], nb = sortedVelocity[j] (a boundary particle's velocity slot holds its wall normal); sums start at +0:
+ *     dx = x0.x - pb.x, likewise dy, dz;  d = dx*dx; d += dy*dy; d += dz*dz; d = sqrtf(d);
+ *     w = fmaxf(0, (r0 - d) / r0);  n += nb*w on four lanes;  wsum += w;  wsum2 += w * (r0 - d);
+ *     when j is in S:  wS += w;  mS += 1;  cS += 1 when w > 0.
+ *   Contact:
+ *     len2 = ((n.x*n.x + n.y*n.y) + n.z*n.z) + n.w*n.w;  contact <=> len2 != 0;
+ *     sh_c = ((n_c / sqrtf(len2)) * wsum2) / wsum for c = x, y, z (0 without contact);  x1 = x0 + sh;
+ *     vn = (n.x*u0.x + n.y*u0.y) + n.z*u0.z;  reflected <=> contact && vn < 0;
+ *     reflected: u1_c = (u0_c - n_c*vn) * 0.99f for xyz and u1.w = u0.w * 0.99f;  otherwise u1 = u0;
+ *     DV = u1 - u0 per component;  share = contact ? wS / wsum : 0.
+ *   Force-stage terms of S: the K7 and K12 terms of sph_force_measure's contract (tv, tt, tq with their use conditions), summed in
+ *   slot order over the used slots whose neighbour is a boundary particle in S: V_S, T_S, P_S, scaled as there: V_S*sF, T_S,
+ *   P_S*sP. The scales are applied whatever the sums hold: without a used slot in S the words are +0 * sF, +0 and +0 * sP (sP is
+ *   negative: -0), as in sph_force_measure.
+ * RECORD, SPH_WALL_WORDS floats per particle:
+ *   0..2     sh * share                      3..5     DV * share (xyz)              6   share      7   wS      8   cS      9   mS
+ *   10..18   V_S*sF (xyz), T_S (xyz), P_S*sP (xyz)
+ *   19..21   the position exactly as integrate stores it: x1, and in a solver without elastic matter x1 + 0.f (integrate's fold
+ *            of the membrane stages)
+ *   22..25   u1, the velocity as integrate stores it
+ *   26       contact (1 or 0)                27       reflected (1 or 0)             28..31   0
+ * A boundary particle's record is all zero. Values are per unit mass: cfg.mass * DV / timeStep is the contact's force on the
+ * particle, cfg.mass times words 10..18 the force-stage force.
+ * TIES TO THE STEP. In a solver without elastic matter words 19..21 equal sph_read_position and words 22..25 sph_read_velocity
+ * right after the step, at the particle's original id, for every non-boundary particle, bit for bit; with elastic matter they
+ * equal the two at the integrate stage of a staged step, before the membrane stages rewrite positions. With slot = SPH_WALL_ALL
+ * wS has the bits of wsum, so share is exactly 1 wherever there is contact, words 0..5 are sh and DV themselves, and words 10..18
+ * equal words 18..26 of sph_force_measure.
+ * sph_wall_measure: fromSelection as in sph_force_measure (0: all N sorted particles in sorted order; 1: the particles of the
+ * current selection in its order, under sph_read_selection's SPH_ERR_ORDER rules).
+ * sph_wall_diagnostics: selection, region rules, count limit and errors exactly as sph_force_diagnostics. Per-particle terms,
+ * floats widened to double, an unselected particle contributing +0.0, summed by the fixed tree reduce(a) of sph_diagnostics over
+ * all N terms in ascending sorted index. Record, SPH_WALL_DIAG_WORDS doubles per region:
+ *   0        n selected         1   n with contact        2   n with share > 0        3   n reflected with share > 0
+ *   4..6     sum words 0..2     7..9     sum words 3..5        10..18   sum words 10..18
+ *   19..21   sum x_i x (words 3..5)          22..24   sum x_i x h_S,  h_S = (visc + pres) + tens of words 10..18 per component
+ *   25       sum share          26       sum wS                27..31   0
+ * Both cross products are a x b = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x) in float with x_i the SORTED position
+ * (the state the step started from), as in sph_force_diagnostics.
+ * SCOPE. The split of sh and DV by w / wsum is this library's attribution; the reference has none, because the direction of the
+ * shift is shared by all walls in reach. The K12 term is not antisymmetric (see sph_force_measure). The load on the body is
+ * approximately minus these sums, and no word claims more than that.
+ * Rules: blocking, on the solver's stream, read-only on every solver array, not stages (no stage timing). SPH_ERR_ORDER until the
+ * last step's integrate stage has run (in the staged path too; sph_step is never half done), after an edit, for a free slot, and
+ * for fromSelection without a current selection. SPH_ERR_INVALID for a slab solver, a slot outside 0..SPH_MAX_BODIES-1 that is
+ * neither SPH_WALL_ALL nor SPH_WALL_NO_BODY, null pointers, fromSelection outside 0..1, a typeMask of 0 or with bits outside 1..3,
+ * count outside 1..SPH_DIAG_MAX_REGIONS, a NaN region bound. A blown-up state is reported as by every blocking call. Device
+ * scratch, grown on demand and freed by sph_destroy: 1 bit per particle for the set, the sampling scratch (at most 64 MiB) and 256
+ * bytes per region and 1024 particles for the totals. */
+#define SPH_WALL_WORDS 32
+#define SPH_WALL_DIAG_WORDS 32
+#define SPH_WALL_ALL (-1)     /* the wall set = every boundary particle */
+#define SPH_WALL_NO_BODY (-2) /* the wall set = boundary particles that are members of no body */
+int sph_wall_measure(sph_solver* s, int32_t slot, int32_t fromSelection, float* out /* host, N (or the selection's count) x 32 */);
+int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
+                         uint32_t typeMask, double* out /* host, count x 32 */);
 
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of

@@ -495,7 +495,7 @@ static const Stage kPredictPositions = {"sph_run_pcisph_predict_positions", P_FO
 static const Stage kPredictDensity = {"sph_run_pcisph_predict_density", P_PREDICTPOS, SPH_ST_PREDICT_DENSITY, LAUNCH(sphk_predict_density(s, false)), P_PREDICTDENS};
 static const Stage kCorrectPressure = {"sph_run_pcisph_correct_pressure", P_PREDICTDENS, SPH_ST_PREDICT_DENSITY, LAUNCH(sphk_correct_pressure(s)), 0};
 static const Stage kPressureForce = {"sph_run_pcisph_compute_pressure_force_acceleration", P_PREDICTDENS, SPH_ST_PRESSURE_FORCE, LAUNCH(sphk_pressure_force(s, 0)), P_PRESSUREFORCE};
-static const Stage kIntegrate = {"sph_run_pcisph_integrate", P_FORCES, SPH_ST_INTEGRATE, LAUNCH(sphk_integrate(s)), 0};
+static const Stage kIntegrate = {"sph_run_pcisph_integrate", P_FORCES, SPH_ST_INTEGRATE, LAUNCH(sphk_integrate(s)), P_INTEGRATE};
 static const Stage kClearMembraneBuffers = {"sph_run_clear_membrane_buffers", 0, SPH_ST_MEMBRANES, LAUNCH(sphk_clear_membranes(s)), 0};
 static const Stage kMembranes = {"sph_run_compute_interaction_with_membranes", P_FIND, SPH_ST_MEMBRANES, LAUNCH(sphk_membranes(s)), 0};
 static const Stage kMembranesFinalize = {"sph_run_compute_interaction_with_membranes_finalize", 0, SPH_ST_MEMBRANES, LAUNCH(sphk_membranes_finalize(s)), 0};
@@ -513,6 +513,8 @@ static int run_stage(sph_solver* s, const Stage& st) {
   if (&st == &kIntegrate) s->stepOpen = s->d.hasElastic != 0;
   else if (&st == &kMembranesFinalize) s->stepOpen = false;
   else if (!membraneStage) s->stepOpen = true;
+  // a new step has begun (its first stage may be clearBuffers, which gains nothing): the last integrate is no longer "this step's"
+  if (&st != &kIntegrate && !membraneStage) s->progress &= ~P_INTEGRATE;
   return rc;
 }
 
@@ -771,7 +773,7 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   }
 #undef RUN
   s->progress = P_HASH | P_SORT | P_SORTPOST | P_INDEXPOST | P_FIND | P_DENSITY | P_FORCES | P_PREDICTPOS | P_PREDICTDENS |
-                P_PRESSUREFORCE;
+                P_PRESSUREFORCE | P_INTEGRATE;
   s->stepOpen = false;
   return SPH_OK;
 }

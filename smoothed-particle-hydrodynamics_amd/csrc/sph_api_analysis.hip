@@ -674,6 +674,95 @@ extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32
   return rc != SPH_OK ? rc : sph_check_finite_state(s);
 }
 
+// ---------------------------------------------------------------------------------------------- wall loads
+// What a set of boundary particles did to each particle in integrate, K7 and K12 (sph_wall.hip): the rules and the two piece
+// loops of the force decomposition, and in front of them the call's wall set as a bit mask over sorted indices.
+static int wall_check(sph_solver* s, int32_t slot, uint32_t typeMask, const char* what) {
+  const int rc = force_check(s, typeMask, what);
+  if (rc != SPH_OK) return rc;
+  if (slot != SPH_WALL_ALL && slot != SPH_WALL_NO_BODY && (slot < 0 || slot >= SPH_MAX_BODIES)) {
+    sph_set_error("%s: slot %d is not in 0..%d, SPH_WALL_ALL or SPH_WALL_NO_BODY", what, slot, SPH_MAX_BODIES - 1);
+    return SPH_ERR_INVALID;
+  }
+  NEED(s, P_INTEGRATE, what);  // acceleration and the boundary masks are what the step's integrate read
+  if (slot >= 0 && !s->bodyCount[slot]) { sph_set_error("%s: slot %d holds no body (sph_body_define_ids / sph_body_define_region)", what, slot); return SPH_ERR_ORDER; }
+  return SPH_OK;
+}
+
+// *mask: the set's bits (null: every boundary particle), *inverted: the set is the particles whose bit is clear
+static int wall_set(sph_solver* s, int32_t slot, const uint32_t** mask, bool* inverted) {
+  *mask = nullptr; *inverted = false;
+  if (slot == SPH_WALL_ALL) return SPH_OK;
+  int rc = sph_grow_scratch(s, s->wallBuf, sphk_wall_mask_bytes(s->d.N));
+  if (rc != SPH_OK) return rc;
+  uint32_t* m = (uint32_t*)s->wallBuf.p;
+  rc = sphk_wall_mask_clear(s, m);
+  for (int32_t b = 0; b < SPH_MAX_BODIES && rc == SPH_OK; b++)
+    if (slot == SPH_WALL_NO_BODY || slot == b) rc = sphk_wall_mask_add(s, (const uint32_t*)s->bodyIds[b].p, s->bodyCount[b], m);
+  *mask = m; *inverted = slot == SPH_WALL_NO_BODY;
+  return rc;
+}
+
+extern "C" int sph_wall_measure(sph_solver* s, int32_t slot, int32_t fromSelection, float* out) {
+  ENTER(s);
+  if (fromSelection != 0 && fromSelection != 1) { sph_set_error("sph_wall_measure: fromSelection %d is not 0 or 1", fromSelection); return SPH_ERR_INVALID; }
+  int rc = wall_check(s, slot, 0xEu, "sph_wall_measure");
+  if (rc != SPH_OK) return rc;
+  size_t n = (size_t)std::max(s->d.N, 0);
+  const int32_t* list = nullptr;
+  if (fromSelection) {
+    rc = sph_selection_current(s, "sph_wall_measure");
+    if (rc != SPH_OK) return rc;
+    n = (size_t)s->selCount;
+    list = (const int32_t*)s->selList.p;
+  }
+  if (n == 0) return sph_check_finite_state(s);
+  if (!out) { sph_set_error("sph_wall_measure: null pointer"); return SPH_ERR_INVALID; }
+  const uint32_t* mask = nullptr;
+  bool inverted = false;
+  rc = wall_set(s, slot, &mask, &inverted);
+  if (rc != SPH_OK) return rc;
+  const size_t rec = sizeof(float) * SPH_WALL_WORDS;
+  const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
+  rc = sph_grow_scratch(s, s->sampleBuf, piece * rec);
+  if (rc != SPH_OK) return rc;
+  for (size_t first = 0; first < n; first += piece) {
+    const size_t m = std::min(piece, n - first);
+    rc = sphk_wall_records(s, mask, inverted, (int)first, (int)m, list ? list + first : nullptr, (float*)s->sampleBuf.p);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, out + first * SPH_WALL_WORDS, s->sampleBuf.p, rec * m);
+    if (rc != SPH_OK) return rc;
+  }
+  return sph_check_finite_state(s);
+}
+
+extern "C" int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
+  ENTER(s);
+  if (!regions6 || !out) { sph_set_error("sph_wall_diagnostics: null pointer"); return SPH_ERR_INVALID; }
+  if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_wall_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
+  int rc = wall_check(s, slot, typeMask, "sph_wall_diagnostics");
+  if (rc != SPH_OK) return rc;
+  DiagArgs a = {};
+  rc = diag_fill_regions(s, &a, regions6, count, typeMask, "sph_wall_diagnostics");
+  if (rc != SPH_OK) return rc;
+  const uint32_t* mask = nullptr;
+  bool inverted = false;
+  rc = wall_set(s, slot, &mask, &inverted);
+  if (rc != SPH_OK) return rc;
+  // the per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the diagnostics scratch
+  const int chunks = s->d.N > 0 ? (s->d.N + 1023) / 1024 : 1;
+  const int pieceChunks = (int)std::min<size_t>((size_t)chunks, kSampleScratchBytes / sphk_wall_terms_bytes(1));
+  rc = sph_grow_scratch(s, s->sampleBuf, sphk_wall_terms_bytes(pieceChunks));
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_wall_diag_scratch_doubles(s->d.N, count));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_wall_diagnostics(s, mask, inverted, a, (float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, records, sizeof(double) * SPH_WALL_DIAG_WORDS * (size_t)count);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
 // ---------------------------------------------------------------------------------------------- integral curves
 // Streamlines and tracers (sph_trace.hip): the rules of sampling, the step's parameters checked here. Streamlines go through the
 // sampling scratch in pieces of seeds, [vertices][seeds][lengths][status] each; the tracers live in a buffer of their own.

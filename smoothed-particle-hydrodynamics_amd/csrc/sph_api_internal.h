@@ -12,7 +12,8 @@
 
 // stage progress bits for the order contract of simulationStep()
 enum { P_HASH = 1, P_SORT = 2, P_SORTPOST = 4, P_INDEXX = 8, P_INDEXPOST = 16, P_FIND = 32, P_DENSITY = 64, P_FORCES = 128,
-       P_PREDICTPOS = 256, P_PREDICTDENS = 512, P_PRESSUREFORCE = 1024 };
+       P_PREDICTPOS = 256, P_PREDICTDENS = 512, P_PRESSUREFORCE = 1024,
+       P_INTEGRATE = 2048 /* the step's integrate has run: acceleration and the boundary masks are what it read (sph_wall_*) */ };
 
 #define NEED(s, bits, what)                                                              \
   do {                                                                                   \

@@ -248,6 +248,8 @@ struct sph_solver {
   // of a call (256 bytes), then the two 1-bit-per-particle masks of a definition by ids or the scan scratch of a compaction.
   SphScratch bodyIds[SPH_MAX_BODIES], bodyRef[SPH_MAX_BODIES], bodyStageIds, bodyStageRef, bodyBuf;
   int bodyCount[SPH_MAX_BODIES] = {};
+  // wall loads (sph_wall_*, sph_wall.hip): the call's wall set, 1 bit per sorted particle, grown on demand
+  SphScratch wallBuf;
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -568,6 +570,18 @@ size_t sphk_force_diag_scratch_doubles(int N, int regions);  // partials of ever
 size_t sphk_force_terms_bytes(int chunks);                   // the staged per-particle terms of `chunks` chunks of 1024 particles
 // the particles go through `terms` in pieces of pieceChunks chunks; *records: where the records land (in scratch)
 int sphk_force_diagnostics(sph_solver* s, const DiagArgs& a, float* terms, int pieceChunks, double* scratch, double** records);
+// sph_wall.hip (what a set of boundary particles did to each particle in integrate, K7 and K12; read-only on every
+// solver array). Device pointers. mask: 1 bit per SORTED particle (sphk_wall_mask_bytes), null = every boundary particle;
+// inverted: the set is the boundary particles whose bit is clear.
+size_t sphk_wall_mask_bytes(int N);
+int sphk_wall_mask_clear(sph_solver* s, uint32_t* mask);
+int sphk_wall_mask_add(sph_solver* s, const uint32_t* origIds, int count, uint32_t* mask);  // or-s the bits of backIndex[origIds[..]]
+// records (SPH_WALL_WORDS floats each, 16-byte aligned) of the sorted particles first .. first + n, or of list[0..n) if given
+int sphk_wall_records(sph_solver* s, const uint32_t* mask, bool inverted, int first, int n, const int32_t* list, float* out);
+size_t sphk_wall_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_WALL_DIAG_WORDS records
+size_t sphk_wall_terms_bytes(int chunks);                   // the staged per-particle terms of `chunks` chunks of 1024 particles
+int sphk_wall_diagnostics(sph_solver* s, const uint32_t* mask, bool inverted, const DiagArgs& a, float* terms, int pieceChunks,
+                          double* scratch, double** records);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)
 size_t sphk_surface_scratch_bytes(long long P);  // the lattice scratch; its first P floats are the field
 int sphk_surface_field(sph_solver* s, const float* records, int word, int n, float* field);  // word of n sample records

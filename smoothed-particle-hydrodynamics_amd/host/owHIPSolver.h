@@ -248,6 +248,18 @@ class owHIPSolver {
     return maxMove;
   }
 
+  // beyond the reference: the load on a wall. slot: a body slot, SPH_WALL_ALL (every boundary particle) or SPH_WALL_NO_BODY (the
+  // boundary particles of no body). wallMeasure writes SPH_WALL_WORDS floats per sorted particle (fromSelection = true: per
+  // particle of the current selection): the set's share of the position shift and velocity change of the contact inside the last
+  // step's integrate, the set's K7 / K12 words of forceMeasure, the position and velocity integrate stored; wallDiagnostics writes
+  // their totals over `count` (1..16) regions, SPH_WALL_DIAG_WORDS doubles each. Per unit mass, on the liquid: cfg.mass times the
+  // summed velocity change over timeStep is the contact's force, and minus that, approximately, the load on the body
+  // (include/sphmi.h, sph_wall_measure / sph_wall_diagnostics)
+  void wallMeasure(int slot, bool fromSelection, float* out) { check(sph_wall_measure(s_, slot, fromSelection ? 1 : 0, out), "wallMeasure"); }
+  void wallDiagnostics(int slot, const float* regions6, int count, unsigned int typeMask, double* out) {
+    check(sph_wall_diagnostics(s_, slot, regions6, count, typeMask, out), "wallDiagnostics");
+  }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

@@ -76,6 +76,12 @@
 //        k * (VX, VY, VZ) (scene units per step); the pose is computed in double and narrowed once. Each moved step prints
 //        `_body: step S members M max_move X` (X: the largest displacement in units of r0, %.9g; from about 1 on the wall
 //        tunnels through liquid). With these options the position read-back is the blocking one.
+//   ... --wall-load-every K
+//        after every K-th step, sph_wall_diagnostics over the liquid of the whole scene, one line per defined body B
+//        (with no body defined: one line for all walls, `body all`):
+//        `_wall: step S body B (members M): contact n C shared H reflected R  contact force X Y Z N  stage force X Y Z N  load on
+//        body X Y Z N  torque on body X Y Z` -- the numbers of frames.wall_summary (%.9e): cfg.mass / timeStep times the summed
+//        velocity change of the contact inside integrate, cfg.mass times the body's K7 / K12 terms, and minus their sum.
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -248,6 +254,7 @@ int main(int argc, char** argv) {
   std::vector<sph_select_term> selTerms;
   int elaEvery = 0; bool elaSeen = false; const char* elaDir = nullptr;
   int forEvery = 0; bool forSeen = false;
+  int wallEvery = 0; bool wallSeen = false;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -309,6 +316,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--elastic-every") && i + 1 < argc) { elaEvery = atoi(argv[++i]); elaSeen = true; }
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
     else if (!strcmp(argv[i], "--forces-every") && i + 1 < argc) { forEvery = atoi(argv[++i]); forSeen = true; }
+    else if (!strcmp(argv[i], "--wall-load-every") && i + 1 < argc) { wallEvery = atoi(argv[++i]); wallSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -446,6 +454,7 @@ int main(int argc, char** argv) {
   const bool measuringElastic = elaSeen;
   if (forSeen && forEvery <= 0) { fprintf(stderr, "--forces-every K needs K > 0\n"); return 2; }
   const bool measuringForces = forSeen;
+  if (wallSeen && wallEvery <= 0) { fprintf(stderr, "--wall-load-every K needs K > 0\n"); return 2; }
   if (renSeen && (renEvery <= 0 || !renDir)) {
     fprintf(stderr, "--render-every K (> 0) and --render-out DIR go together (the other --render options need both)\n");
     return 2;
@@ -903,6 +912,32 @@ int main(int argc, char** argv) {
           printf("_forces: step %d  on liquid (n %.0f): boundary load %.9e %.9e %.9e N  liquid load %.9e %.9e %.9e N\n", iterationCount + 1,
                  r[0], load(3, 0), load(3, 1), load(3, 2), load(1, 0), load(1, 1), load(1, 2));
         helper.report("_forces: \t\t%9.3f ms\n");
+      }
+      if (wallSeen && (iterationCount + 1) % wallEvery == 0) {
+        const float everything[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
+        const double m = (double)cfg.mass, perDt = (double)cfg.mass / (double)cfg.timeStep;
+        int defined = 0;
+        for (int b = 0; b < SPH_MAX_BODIES; b++) defined += ocl_solver->bodyCount(b) > 0;
+        for (int b = defined ? 0 : SPH_WALL_ALL; b < (defined ? SPH_MAX_BODIES : 0); b++) {
+          const long long members = b >= 0 ? (long long)ocl_solver->bodyCount(b) : 0;
+          if (b >= 0 && !members) continue;
+          double r[SPH_WALL_DIAG_WORDS];
+          ocl_solver->wallDiagnostics(b, everything, 1, 1u << SPH_LIQUID_PARTICLE, r);
+          double contact[3], stage[3], load[3], torque[3];
+          for (int a = 0; a < 3; a++) {
+            contact[a] = perDt * r[7 + a];
+            stage[a] = (m * r[10 + a] + m * r[16 + a]) + m * r[13 + a];
+            load[a] = -(contact[a] + stage[a]);
+            torque[a] = -(perDt * r[19 + a] + m * r[22 + a]);
+          }
+          char name[16];
+          if (b >= 0) snprintf(name, sizeof(name), "%d", b); else snprintf(name, sizeof(name), "all");
+          printf("_wall: step %d body %s (members %lld): contact n %.0f shared %.0f reflected %.0f  contact force %.9e %.9e %.9e N  "
+                 "stage force %.9e %.9e %.9e N  load on body %.9e %.9e %.9e N  torque on body %.9e %.9e %.9e\n", iterationCount + 1, name,
+                 members, r[1], r[2], r[3], contact[0], contact[1], contact[2], stage[0], stage[1], stage[2], load[0], load[1], load[2],
+                 torque[0], torque[1], torque[2]);
+        }
+        helper.report("_wall: \t\t\t%9.3f ms\n");
       }
       if (dyeing) {
         const float stability = ocl_solver->fieldDiffuse(0, dyeDiffusivity * cfg.timeStep, dyeDiffusivity > 0.f ? 1 : 0, dyeMask);

@@ -31,6 +31,9 @@ MUSCLE_WORDS = 16  # sph_muscle_diagnostics record (frames.MUSCLE_FIELDS)
 MEMBRANE_WORDS = 8  # sph_membrane_measure record: area, unit normal, centroid, 0 (frames.MEMBRANE_FIELDS)
 FORCE_WORDS = 40  # sph_force_measure record (frames.FORCE_FIELDS)
 FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
+WALL_WORDS = 32  # sph_wall_measure record (frames.WALL_FIELDS)
+WALL_DIAG_WORDS = 32  # sph_wall_diagnostics record (frames.WALL_DIAG_FIELDS)
+WALL_ALL, WALL_NO_BODY = -1, -2  # the wall set in place of a body slot: every boundary particle / those that belong to no body
 FIELD_SLOTS = 4  # carried particle fields per solver (sph_field_*)
 FIELD_DIAG_WORDS = 8  # sph_field_diagnostics record (frames.FIELD_DIAG_FIELDS)
 TRACE_TIME, TRACE_ARC = 0, 1  # sph_trace_params.mode
@@ -168,7 +171,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
                     "sph_field_diffuse", "sph_field_diagnostics", "sph_trace_streamlines", "sph_tracers_set", "sph_tracers_advect",
                     "sph_tracers_read", "sph_body_define_ids", "sph_body_define_region", "sph_body_release", "sph_body_count",
-                    "sph_body_read", "sph_body_set_pose"] + _STAGE_FUNCS
+                    "sph_body_read", "sph_body_set_pose", "sph_wall_measure", "sph_wall_diagnostics"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -301,6 +304,9 @@ def device_lib():
             L.sph_body_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
             L.sph_body_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sph_body_set_pose.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_wall_measure"):  # (optional: an A/B library built from an older csrc/ has no wall loads)
+            L.sph_wall_measure.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+            L.sph_wall_diagnostics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         _dev = L
     return _dev
 
@@ -907,6 +913,27 @@ class owHIPSolver:
         rg = _regions(regions, "force_diagnostics")
         out = np.zeros((max(rg.shape[0], 1), FORCE_DIAG_WORDS), np.float64)
         self._chk(self._L.sph_force_diagnostics(self._h, _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
+        return out
+
+    # --- wall loads (sph_wall_measure / sph_wall_diagnostics) ---
+    def wall_measure(self, slot, selection=False):
+        """What the wall set `slot` (a body slot 0..15, WALL_ALL or WALL_NO_BODY) did to every sorted particle in the last
+        completed step (selection=False: float32[N, 32]) or to the particles of the last select(), in its order: records named by
+        frames.WALL_FIELDS -- the set's share of the position shift and of the velocity change of the contact inside integrate,
+        the share and its weights, the set's nine K7 / K12 words of force_measure(), the position and velocity integrate stored,
+        and the contact / reflected flags. Per unit mass: cfg.mass * dv / timeStep is the contact's force (include/sphmi.h)."""
+        n = getattr(self, "_selected", 0) if selection else self.N  # without a selection the library reports SPH_ERR_ORDER
+        out = np.zeros((n, WALL_WORDS), np.float32)
+        self._chk(self._L.sph_wall_measure(self._h, int(slot), 1 if selection else 0, _ptr(out) if n else None))
+        return out
+
+    def wall_diagnostics(self, slot, regions=None, types=(1, 2)):
+        """Totals of wall_measure(slot) over the particles diagnostics() selects for each region: float64[R, 32] records named by
+        frames.WALL_DIAG_FIELDS, added in the fixed tree of diagnostics(). frames.wall_summary turns a record into newtons and
+        newton metres on the liquid and, negated, on the body."""
+        rg = _regions(regions, "wall_diagnostics")
+        out = np.zeros((max(rg.shape[0], 1), WALL_DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_wall_diagnostics(self._h, int(slot), _ptr(rg), rg.shape[0], type_mask(types), _ptr(out)))
         return out
 
     # --- particle rendering (sph_render_particles / sph_read_render) ---

@@ -615,6 +615,38 @@ def force_summary(record, mass):
     return out
 
 
+# ---- wall loads (owHIPSolver.wall_measure / wall_diagnostics; include/sphmi.h, sph_wall_measure) ----
+WALL_FIELDS = ("shift_x", "shift_y", "shift_z", "dv_x", "dv_y", "dv_z", "share", "w_set", "n_touching", "n_slots") + \
+    tuple("%s_%s" % (k, a) for k in _FORCE_KINDS for a in "xyz") + ("x", "y", "z", "vx", "vy", "vz", "vw", "contact", "reflected") + \
+    ("unused28", "unused29", "unused30", "unused31")
+WALL_DIAG_FIELDS = ("n", "n_contact", "n_shared", "n_reflected") + tuple("sum_" + f for f in WALL_FIELDS[:6]) + \
+    tuple("sum_" + f for f in WALL_FIELDS[10:19]) + tuple("sum_torque_contact_" + a for a in "xyz") + \
+    tuple("sum_torque_force_" + a for a in "xyz") + ("sum_share", "sum_w_set") + tuple("reserved%d" % w for w in range(27, 32))
+
+
+def wall_summary(record, mass, time_step):
+    """A wall_diagnostics() record as physical numbers, a dict of float64 values. The record's sums are per unit mass: `mass`
+    (cfg.mass, kg per particle) times the summed velocity change over `time_step` (cfg.timeStep) is the contact's force in
+    newtons, `mass` times the summed K7 / K12 accelerations the force-stage force. contact_force, viscous, tension, pressure and
+    stage_force = (viscous + pressure) + tension: [3], on the selected liquid; contact_torque, stage_torque: [3] about the origin
+    in newton x scene unit; shift: the summed position shift (scene units); body_contact_load, body_stage_load, body_load and
+    body_torque: the negatives, approximately what the liquid does to the body (include/sphmi.h, SCOPE); n, n_contact, n_shared,
+    n_reflected, share and w_set: the counts and the summed share and weight."""
+    r = np.asarray(record, np.float64).reshape(len(WALL_DIAG_FIELDS))
+    m, per_dt = float(mass), float(mass) / float(time_step)
+    out = {"n": r[0], "n_contact": r[1], "n_shared": r[2], "n_reflected": r[3], "shift": r[4:7].copy(), "share": r[25], "w_set": r[26]}
+    out["contact_force"] = per_dt * r[7:10]
+    out["viscous"], out["tension"], out["pressure"] = m * r[10:13], m * r[13:16], m * r[16:19]
+    out["stage_force"] = (out["viscous"] + out["pressure"]) + out["tension"]
+    out["contact_torque"] = per_dt * r[19:22]
+    out["stage_torque"] = m * r[22:25]
+    out["body_contact_load"] = -out["contact_force"]
+    out["body_stage_load"] = -out["stage_force"]
+    out["body_load"] = -(out["contact_force"] + out["stage_force"])
+    out["body_torque"] = -(out["contact_torque"] + out["stage_torque"])
+    return out
+
+
 def write_vtk_forces(path, position, orig_id, records, mass=1.0):
     """Legacy-VTK polydata (binary, big-endian like write_vtk) of the particles of force_measure(selection=True): one point per
     record at position[orig_id] (`position`: [N, 4] in orig order; orig_id from selection()), with `id` (int), the three
