@@ -895,6 +895,78 @@ int sph_wall_measure(sph_solver* s, int32_t slot, int32_t fromSelection, float* 
 int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* regions6 /* host, count x (x0,y0,z0,x1,y1,z1) */, int32_t count,
                          uint32_t typeMask, double* out /* host, count x 32 */);
 
+/* ---- Free bodies: rigid-body dynamics driven by the wall loads (no reference counterpart) ------------------------
+ * A kinematic body gets a DYNAMIC STATE (sph_body_set_dynamics); after a completed step one call, sph_bodies_advance, computes
+ * the load of that step on every dynamic body, advances its state by one step and places its members, all on the device. The step
+ * kernels know nothing of it; every other call behaves as before.
+ * UNITS. The state lives in the solver's own units: positions in position units, velocities as the particles' velocities. A
+ * velocity moves a position by posTimeStep * V and an angular velocity turns by posTimeStep * omega (posTimeStep = the float
+ * timeStep * simulationScaleInv of the step, widened); inertia is therefore in kg * (position unit)^2.
+ * sph_body_set_dynamics checks the parameters (SPH_ERR_INVALID: mass not finite or <= 0; any non-finite word; inertiaInv with a
+ * negative diagonal word, or a 2 x 2 principal minor or a determinant below zero by more than 1e-9 of the size of its terms; |q| outside [0.5, 2]; locks with bits above 3), normalises q
+ * (n = sqrt(((w*w + x*x) + y*y) + z*z) in double, q / n) and stores the state on the device. The advance counter restarts at 0.
+ * Two dynamic bodies must not share a member: the call counts, blocking, the members of the slot that are members of another
+ * dynamic body, and refuses with SPH_ERR_INVALID naming their number and the lowest shared original id. dyn == NULL makes the
+ * body kinematic again. sph_body_get_dynamics (blocking) returns the live state; *isDynamic = 0 and `out` untouched otherwise.
+ * sph_bodies_advance. With out == NULL everything is enqueued on the solver's stream and the call returns without a host wait;
+ * with `out` it waits once and copies SPH_MAX_BODIES records of SPH_BODY_STATE_WORDS doubles. For every dynamic body:
+ *  1. LOAD. D[0..31] is the record sph_wall_diagnostics(slot, one region = everything, typeMask = types 1..3) returns on this
+ *     state (the last completed step's, the walls where that step saw them). The words used below and words 1 and 2 are equal as
+ *     IEEE values to that call's; the sign of a zero total is not part of the contract (chunks without a neighbour of the body
+ *     contribute +0.0).
+ *  2. INTEGRATE, all in double, one operation at a time in the written order, no contraction, IEEE / and sqrt. dt =
+ *     (double)timeStep, hp = (double)posTimeStep, mp = (double)cfg.mass, c over x, y, z:
+ *       C_c = D[7+c];  H_c = (D[10+c] + D[16+c]) + D[13+c];  TC_c = D[19+c];  TH_c = D[22+c]
+ *       Fl_c = -(mp * (contactGain*(C_c/dt) + forceGain*H_c));  T0_c = -(mp * (contactGain*(TC_c/dt) + forceGain*TH_c))
+ *       Tl = T0 - X x Fl, written T0.x - (X.y*Fl.z - X.z*Fl.y), T0.y - (X.z*Fl.x - X.x*Fl.z), T0.z - (X.x*Fl.y - X.y*Fl.x)
+ *       F_c = (Fl_c + mass*gravity_c) + force_c;  V'_c = V_c on a locked axis, else V_c + dt*(F_c/mass);  X'_c = X_c + hp*V'_c
+ *       rotation free:   L'_c = L_c + dt*(Tl_c + torque_c);  R = R(q);  u = R^T L';  w = Jinv u;  omega = R w, every matrix row
+ *                        (a*b + c*d) + e*f  (u_x = (R00*L'x + R10*L'y) + R20*L'z; w_x = (Jxx*u_x + Jxy*u_y) + Jxz*u_z)
+ *       rotation locked: L' = L, omega = spin
+ *       dw = -((ox*x + oy*y) + oz*z);  dx = (ox*w + oy*z) - oz*y;  dy = (oy*w + oz*x) - ox*z;  dz = (oz*w + ox*y) - oy*x
+ *       q* = q + (0.5*hp)*d;  n = sqrt(((w*w + x*x) + y*y) + z*z) of q*;  q' = q* / n
+ *       R00 = 1 - 2*(y*y + z*z)   R01 = 2*(x*y - w*z)       R02 = 2*(x*z + w*y)
+ *       R10 = 2*(x*y + w*z)       R11 = 1 - 2*(x*x + z*z)   R12 = 2*(y*z - w*x)
+ *       R20 = 2*(x*z - w*y)       R21 = 2*(y*z + w*x)       R22 = 1 - 2*(x*x + y*y)
+ *  3. PLACE. R' = R(q'), t_c = X'_c - ((R'c0*com.x + R'c1*com.y) + R'c2*com.z); the twelve numbers narrowed to float once are the
+ *     pose, applied with the expressions, the validation, the all-or-nothing rule and the tunnelling number of sph_body_set_pose.
+ *     If a member fails, nothing of that body is written, its dynamic state stays as it was and its status is 1; a non-finite
+ *     word in X', q', V', L' or the pose gives status 2 with the same consequences. Other bodies are not affected and the call
+ *     is SPH_OK.
+ * RECORD per slot, doubles:  0 status (-1 not dynamic, 0 advanced, 1 pose refused, 2 non-finite)   1 member count
+ *   2 advances since sph_body_set_dynamics (this one included when status is 0)   3 tunnelling number (status 0)
+ *   4..6 X'   7..10 q'   11..13 V'   14..16 L'   17..19 omega   20..22 Fl   23..25 Tl   (the computed values, whatever the status)
+ *   26 n with contact (D[1])   27 n with share > 0 (D[2])   28 offenders   29 lowest failing member (status 1)   30..47 0
+ * RULES. SPH_OK with nothing to do when no body is dynamic. SPH_ERR_ORDER under exactly the conditions of sph_wall_diagnostics
+ * (no completed step, a half-done staged step, after an edit); sph_body_set_dynamics on a free slot is SPH_ERR_ORDER too.
+ * SPH_ERR_INVALID for a slab solver and a slot out of range. Defining or releasing a slot clears its dynamics; a removal carries
+ * them along unchanged (the mass properties are the caller's) unless it empties the body. sph_body_set_pose on a dynamic body
+ * stays legal and moves the particles only: the next advance places them from the dynamic state again. An advance leaves analysis
+ * state valid, like a pose.
+ * SCOPE. The coupling is explicit and one step behind. The load inherits the caveats of the wall loads above. A body much lighter
+ * than the liquid it displaces will be unstable; no limit is enforced, the tunnelling number is what the caller watches. No
+ * body-body contact, no no-slip walls. Device memory, grown on demand: one byte per particle and 2.6 KB per 1024 particles (152 bytes for each of the 16 slots and
+ * for the contact count), plus 17 KB of states and records. */
+typedef struct sph_body_dynamics {
+  double mass;          /* kg, finite, > 0 */
+  double com[3];        /* centre of mass in the REFERENCE placement, position units */
+  double inertiaInv[6]; /* inverse inertia about com in reference axes: xx yy zz xy xz yz, 1/(kg * position unit^2);
+                           finite, symmetric positive semi-definite (all zero: never turns) */
+  double position[3];   /* X: current centre of mass, position units */
+  double orientation[4];/* q = (w, x, y, z), maps reference axes to world; normalised by the call, |q| in [0.5, 2] else INVALID */
+  double velocity[3];   /* V, the particles' velocity units */
+  double angularMomentum[3]; /* L about the centre of mass, world axes, kg * position unit * velocity unit */
+  double spin[3];       /* the angular velocity used while rotation is locked */
+  double gravity[3];    /* acceleration on the body (the wrappers default it to cfg.gravity_*) */
+  double force[3], torque[3]; /* constant external force and torque about the centre of mass */
+  double contactGain, forceGain; /* weights of the two load terms; 1, 1 by default */
+  uint32_t locks;       /* bits 0..2: V.x / V.y / V.z keep their value (a driven axis); bit 3: rotation locked (omega = spin) */
+} sph_body_dynamics;
+#define SPH_BODY_STATE_WORDS 48
+int sph_body_set_dynamics(sph_solver* s, int32_t slot, const sph_body_dynamics* dyn /* NULL: the body is kinematic again */);
+int sph_body_get_dynamics(sph_solver* s, int32_t slot, sph_body_dynamics* out, int32_t* isDynamic); /* blocking */
+int sph_bodies_advance(sph_solver* s, double* out /* host, SPH_MAX_BODIES x SPH_BODY_STATE_WORDS, or NULL */);
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -763,6 +763,28 @@ extern "C" int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* re
   return rc != SPH_OK ? rc : sph_check_finite_state(s);
 }
 
+// ---------------------------------------------------------------------------------------------- free bodies
+// One step of every dynamic body (sph_body_dynamics.hip) under the order rules of the wall loads, whose state it reads. With
+// out == NULL nothing here waits for the device.
+extern "C" int sph_bodies_advance(sph_solver* s, double* out) {
+  ENTER(s);
+  int rc = wall_check(s, SPH_WALL_ALL, 0xEu, "sph_bodies_advance");
+  if (rc != SPH_OK) return rc;
+  if (s->stepOpen) { sph_set_error("sph_bodies_advance: a stage-by-stage step is half done; bodies are moved between two steps"); return SPH_ERR_ORDER; }
+  const BodyDynSet set = sph_body_dyn_set(s);
+  if (!set.dynMask) {
+    if (out)
+      for (int k = 0; k < SPH_MAX_BODIES * SPH_BODY_STATE_WORDS; k++) out[k] = k % SPH_BODY_STATE_WORDS == 0 ? -1.0 : 0.0;
+    return SPH_OK;
+  }
+  rc = sph_grow_scratch(s, s->bodyDynScratch, sphk_bdyn_scratch_bytes(s->d.N));
+  if (rc != SPH_OK) return rc;
+  BodyDynDev* D = (BodyDynDev*)s->bodyDynBuf.p;  // (exists: sph_body_set_dynamics made the bodies dynamic)
+  rc = sphk_bdyn_advance(s, set, sph_body_pose_box(s), s->bodyDynScratch.p, D);
+  if (rc != SPH_OK || !out) return rc;
+  return sph_d2h(s, out, D->record, sizeof(double) * SPH_MAX_BODIES * SPH_BODY_STATE_WORDS);
+}
+
 // ---------------------------------------------------------------------------------------------- integral curves
 // Streamlines and tracers (sph_trace.hip): the rules of sampling, the step's parameters checked here. Streamlines go through the
 // sampling scratch in pieces of seeds, [vertices][seeds][lengths][status] each; the tracers live in a buffer of their own.

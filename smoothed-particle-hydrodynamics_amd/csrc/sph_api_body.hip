@@ -1,5 +1,6 @@
 // C ABI of libsphmi.so (include/sphmi.h), the kinematic bodies: sph_body_define_ids / sph_body_define_region / sph_body_release /
-// sph_body_count / sph_body_read / sph_body_set_pose, and what a removal does to the bodies (sph_bodies_follow_removal). A pose
+// sph_body_count / sph_body_read / sph_body_set_pose, the dynamic state of a free body (sph_body_set_dynamics / sph_body_get_dynamics,
+// DESIGN.md §37), and what a removal does to the bodies (sph_bodies_follow_removal). A pose
 // rewrites rows of posOrig / velOrig but not the particle set: no call here says sph_state_changes or touches `progress`, so the
 // analysis state and everything derived from it stay valid. What the translation units of the ABI share is in
 // sph_api_internal.h.
@@ -43,6 +44,7 @@ static void body_drop(sph_solver* s, int32_t slot) {
     b->p = nullptr; b->bytes = 0;
   }
   s->bodyCount[slot] = 0;
+  s->bodyDynamic[slot] = false;  // a body that is gone has no dynamics
 }
 
 extern "C" int sph_body_define_ids(sph_solver* s, int32_t slot, const uint32_t* origIds, int64_t count) {
@@ -76,6 +78,7 @@ extern "C" int sph_body_define_ids(sph_solver* s, int32_t slot, const uint32_t* 
   rc = sphk_body_gather(s, ids, n, (float4*)s->bodyStageRef.p);
   if (rc != SPH_OK) return rc;
   body_install(s, slot, n);
+  s->bodyDynamic[slot] = false;  // a new definition is kinematic
   return SPH_OK;
 }
 
@@ -109,6 +112,7 @@ extern "C" int sph_body_define_region(sph_solver* s, int32_t slot, const float* 
   rc = sphk_body_gather(s, (const uint32_t*)s->bodyStageIds.p, n, (float4*)s->bodyStageRef.p);
   if (rc != SPH_OK) return rc;
   body_install(s, slot, n);
+  s->bodyDynamic[slot] = false;  // a new definition is kinematic
   *count = n;
   return SPH_OK;
 }
@@ -160,14 +164,11 @@ extern "C" int sph_body_set_pose(sph_solver* s, int32_t slot, const float pose[1
   int rc = body_check(s, slot, "sph_body_set_pose");
   if (rc != SPH_OK) return rc;
   if (!pose) { sph_set_error("sph_body_set_pose: null pointer"); return SPH_ERR_INVALID; }
-  const sph_config& c = s->cfg;
-  BodyPose a = {};
+  BodyPose a = sph_body_pose_box(s);
   for (int k = 0; k < 12; k++) {
     if (!std::isfinite(pose[k])) { sph_set_error("sph_body_set_pose: pose word %d (%g) is not finite", k, pose[k]); return SPH_ERR_INVALID; }
     a.m[k] = pose[k];
   }
-  a.wide = c.cellIdMask == 0xffffffffu;
-  a.xmin = c.xmin; a.xmax = c.xmax; a.ymin = c.ymin; a.ymax = c.ymax; a.zmin = c.zmin; a.zmax = c.zmax;
   const int n = s->bodyCount[slot];
   if (!n) { sph_set_error("sph_body_set_pose: slot %d holds no body (sph_body_define_ids / sph_body_define_region)", slot); return SPH_ERR_ORDER; }
   rc = sph_grow_scratch(s, s->bodyBuf, sphk_body_check_bytes(0));  // the counters
@@ -196,6 +197,89 @@ extern "C" int sph_body_set_pose(sph_solver* s, int32_t slot, const float pose[1
     memcpy(&d2, &t[2], sizeof(d2));
     *maxMoveInR0 = sqrtf(d2) / s->d.r0;
   }
+  return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- free bodies: the dynamic state
+// (sph_bodies_advance is in sph_api_analysis.hip, next to the wall loads whose order rules it shares)
+static bool dyn_finite(const double* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+extern "C" int sph_body_set_dynamics(sph_solver* s, int32_t slot, const sph_body_dynamics* dyn) {
+  ENTER(s);
+  const char* what = "sph_body_set_dynamics";
+  int rc = body_check(s, slot, what);
+  if (rc != SPH_OK) return rc;
+  if (!s->bodyCount[slot]) { sph_set_error("%s: slot %d holds no body (sph_body_define_ids / sph_body_define_region)", what, slot); return SPH_ERR_ORDER; }
+  if (!dyn) { s->bodyDynamic[slot] = false; return SPH_OK; }
+  sph_body_dynamics p = *dyn;
+  const bool finite = std::isfinite(p.mass) && dyn_finite(p.com, 3) && dyn_finite(p.inertiaInv, 6) && dyn_finite(p.position, 3) &&
+                      dyn_finite(p.orientation, 4) && dyn_finite(p.velocity, 3) && dyn_finite(p.angularMomentum, 3) &&
+                      dyn_finite(p.spin, 3) && dyn_finite(p.gravity, 3) && dyn_finite(p.force, 3) && dyn_finite(p.torque, 3) &&
+                      std::isfinite(p.contactGain) && std::isfinite(p.forceGain);
+  if (!finite) { sph_set_error("%s: a parameter is not finite", what); return SPH_ERR_INVALID; }
+  if (!(p.mass > 0.0)) { sph_set_error("%s: mass %g is not > 0", what, p.mass); return SPH_ERR_INVALID; }
+  const double* J = p.inertiaInv;  // xx yy zz xy xz yz
+  // positive semi-definite up to rounding (a pseudo-inverse of a singular inertia has minors that are zero but for it): no
+  // diagonal word, 2 x 2 principal minor or determinant below -1e-9 of the size of its terms
+  auto minor_bad = [](double a, double b, double c) { return a * b - c * c < -1e-9 * (a * b + c * c); };
+  const double det = J[0] * (J[1] * J[2] - J[5] * J[5]) - J[3] * (J[3] * J[2] - J[5] * J[4]) + J[4] * (J[3] * J[5] - J[1] * J[4]);
+  const double tr = J[0] + J[1] + J[2];
+  if (J[0] < 0.0 || J[1] < 0.0 || J[2] < 0.0 || minor_bad(J[0], J[1], J[3]) || minor_bad(J[0], J[2], J[4]) || minor_bad(J[1], J[2], J[5]) ||
+      det < -1e-9 * tr * tr * tr) {
+    sph_set_error("%s: inertiaInv is not positive semi-definite", what);
+    return SPH_ERR_INVALID;
+  }
+  if (p.locks & ~0xFu) { sph_set_error("%s: locks 0x%x has bits above 3", what, p.locks); return SPH_ERR_INVALID; }
+  double* q = p.orientation;
+  const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+  if (!(n >= 0.5 && n <= 2.0)) { sph_set_error("%s: |orientation| = %g is not in [0.5, 2]", what, n); return SPH_ERR_INVALID; }
+  for (int k = 0; k < 4; k++) q[k] = q[k] / n;
+  rc = sph_grow_scratch(s, s->bodyDynBuf, sizeof(BodyDynDev));
+  if (rc != SPH_OK) return rc;
+  BodyDynDev* D = (BodyDynDev*)s->bodyDynBuf.p;
+  // members shared with another dynamic body: counted on the device, the call's one wait
+  BodyDynSet set = sph_body_dyn_set(s);
+  set.dynMask &= ~(1u << slot);
+  if (set.dynMask) {
+    set.count[slot] = s->bodyCount[slot];
+    set.ids[slot] = (const uint32_t*)s->bodyIds[slot].p;
+    rc = sph_grow_scratch(s, s->bodyBuf, sphk_body_check_bytes(s->d.N));
+    if (rc != SPH_OK) return rc;
+    rc = sphk_bdyn_overlap(s, set, slot, (unsigned long long*)((char*)s->bodyBuf.p + 256), D);
+    if (rc != SPH_OK) return rc;
+    uint32_t shared[2] = {0, 0};
+    rc = sph_d2h(s, shared, D->overlap, sizeof(shared));
+    if (rc != SPH_OK) return rc;
+    if (shared[0]) {
+      sph_set_error("%s: %u of the %d members of slot %d are members of another dynamic body; the lowest shared id is %u", what,
+                    shared[0], s->bodyCount[slot], slot, shared[1]);
+      return SPH_ERR_INVALID;
+    }
+  }
+  BodyDynSlot rec = {};
+  rec.p = p;
+  rc = hipMemcpyAsync(&D->live[slot], &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream) == hipSuccess ? SPH_OK : SPH_ERR_HIP;
+  if (rc == SPH_OK) rc = hipStreamSynchronize(s->stream) == hipSuccess ? SPH_OK : SPH_ERR_HIP;  // (rec is a local)
+  if (rc != SPH_OK) { sph_set_error("%s: the copy of the state to the device failed", what); return rc; }
+  s->bodyDynamic[slot] = true;
+  return SPH_OK;
+}
+
+extern "C" int sph_body_get_dynamics(sph_solver* s, int32_t slot, sph_body_dynamics* out, int32_t* isDynamic) {
+  ENTER(s);
+  const int rc = body_check(s, slot, "sph_body_get_dynamics");
+  if (rc != SPH_OK) return rc;
+  if (!isDynamic) { sph_set_error("sph_body_get_dynamics: null pointer"); return SPH_ERR_INVALID; }
+  *isDynamic = s->bodyDynamic[slot] ? 1 : 0;
+  if (!s->bodyDynamic[slot] || !out) return SPH_OK;
+  BodyDynSlot rec = {};
+  const int rcCopy = sph_d2h(s, &rec, &((BodyDynDev*)s->bodyDynBuf.p)->live[slot], sizeof(rec));
+  if (rcCopy != SPH_OK) return rcCopy;
+  *out = rec.p;
   return SPH_OK;
 }
 

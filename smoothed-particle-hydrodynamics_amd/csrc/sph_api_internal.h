@@ -86,6 +86,26 @@ int sph_fields_follow_add(sph_solver* s, int first, int count);              // 
 // (body in sph_api_body.hip) What a removal does to the kinematic bodies, next to the fields: member ids through the old-to-new map,
 // removed members dropped with their reference rows, a body left empty released. Blocking per body in use (its new count).
 int sph_bodies_follow_removal(sph_solver* s, int oldN, const int32_t* map);
+// the dynamic bodies as the launches of sph_body_dynamics.hip take them (sph_api_body.hip: set_dynamics; sph_api_analysis.hip: advance)
+static inline BodyDynSet sph_body_dyn_set(const sph_solver* s) {
+  BodyDynSet set = {};
+  for (int b = 0; b < SPH_MAX_BODIES; b++) {
+    if (!s->bodyDynamic[b] || !s->bodyCount[b]) continue;
+    set.dynMask |= 1u << b;
+    set.count[b] = s->bodyCount[b];
+    set.ids[b] = (const uint32_t*)s->bodyIds[b].p;
+    set.ref[b] = (const float4*)s->bodyRef[b].p;
+  }
+  return set;
+}
+// the box a pose is validated against (sph_body_set_pose and the advance)
+static inline BodyPose sph_body_pose_box(const sph_solver* s) {
+  const sph_config& c = s->cfg;
+  BodyPose a = {};
+  a.wide = c.cellIdMask == 0xffffffffu;
+  a.xmin = c.xmin; a.xmax = c.xmax; a.ymin = c.ymin; a.ymax = c.ymax; a.zmin = c.zmin; a.zmax = c.zmax;
+  return a;
+}
 
 // (a rebuild whose particle count is still on its way to the host — sph_slab_rebuild_framed — is finished first)
 #define ENTER_RAW(s) do { if (!(s)) { sph_set_error("null solver"); return SPH_ERR_INVALID; } SPH_HIP(hipSetDevice((s)->cfg.device)); } while (0)

@@ -250,6 +250,11 @@ struct sph_solver {
   int bodyCount[SPH_MAX_BODIES] = {};
   // wall loads (sph_wall_*, sph_wall.hip): the call's wall set, 1 bit per sorted particle, grown on demand
   SphScratch wallBuf;
+  // free bodies (sph_body_set_dynamics / sph_bodies_advance, sph_body_dynamics.hip): which slots are dynamic;
+  // bodyDynBuf: one BodyDynDev (live and staged states, poses, counters, records); bodyDynScratch: the body-of-particle map (one
+  // byte per sorted particle), then the load tree's partials. Both grown on demand.
+  bool bodyDynamic[SPH_MAX_BODIES] = {};
+  SphScratch bodyDynBuf, bodyDynScratch;
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -511,6 +516,30 @@ size_t sphk_body_compact_bytes(int count);  // the counters and the scan scratch
 // members whose map[id] >= 0, in order, with their rows: idsOut / refOut (room for `count`); *totals = device word, their number
 int sphk_body_compact(sph_solver* s, const uint32_t* ids, const float4* ref, int count, const int32_t* map, int oldN, void* scratch,
                       uint32_t* idsOut, float4* refOut, uint32_t** totals);
+// sph_body_dynamics.hip (free bodies: the fused per-body load, the rigid-body step and the pose from device memory)
+struct BodyDynSlot {
+  sph_body_dynamics p;  // parameters and state, as the caller's struct (q normalised)
+  uint32_t advances, pad;
+};
+struct BodyDynDev {  // everything of the feature that lives on the device, one allocation
+  BodyDynSlot live[SPH_MAX_BODIES], staged[SPH_MAX_BODIES];
+  BodyPose pose[SPH_MAX_BODIES];          // the pose of the advance in flight
+  uint32_t counters[SPH_MAX_BODIES][4];   // its validation: offenders, lowest failing member, bits of max d2
+  double record[SPH_MAX_BODIES][SPH_BODY_STATE_WORDS];
+  uint32_t overlap[2];                    // sph_body_set_dynamics: shared members, the lowest shared id
+};
+struct BodyDynSet {  // the bodies of a launch, by value
+  uint32_t dynMask;  // bit b: slot b is dynamic
+  int count[SPH_MAX_BODIES];
+  const uint32_t* ids[SPH_MAX_BODIES];
+  const float4* ref[SPH_MAX_BODIES];
+};
+size_t sphk_bdyn_scratch_bytes(int N);  // the map and every tree level's partials
+// D->overlap = {members of `slot` that are members of another body of set.dynMask, the lowest such original id or 0xffffffff};
+// seen: N bits, cleared here
+int sphk_bdyn_overlap(sph_solver* s, const BodyDynSet& set, int slot, unsigned long long* seen, BodyDynDev* D);
+// one advance of every body of set.dynMask, enqueued on s->stream: map, fused load, tree, integrate, validate, commit, finish
+int sphk_bdyn_advance(sph_solver* s, const BodyDynSet& set, const BodyPose& box, void* scratch, BodyDynDev* D);
 // sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
 // values in original-id order (device). Read-only on every solver array.
 size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word

@@ -248,6 +248,18 @@ class owHIPSolver {
     return maxMove;
   }
 
+  // beyond the reference: free bodies. bodySetDynamics gives body `slot` a dynamic state (null: kinematic again), bodyGetDynamics
+  // returns whether it has one and, if so, the live state; bodiesAdvance, after a completed step, computes the load of that step on
+  // every dynamic body, advances its rigid-body state by one step and places its members, all on the GPU: with out == null nothing
+  // waits for the device, otherwise SPH_MAX_BODIES x SPH_BODY_STATE_WORDS doubles are copied out (include/sphmi.h, sph_bodies_advance)
+  void bodySetDynamics(int slot, const sph_body_dynamics* dyn) { check(sph_body_set_dynamics(s_, slot, dyn), "bodySetDynamics"); }
+  bool bodyGetDynamics(int slot, sph_body_dynamics* out) {
+    int32_t isDynamic = 0;
+    check(sph_body_get_dynamics(s_, slot, out, &isDynamic), "bodyGetDynamics");
+    return isDynamic != 0;
+  }
+  void bodiesAdvance(double* out = nullptr) { check(sph_bodies_advance(s_, out), "bodiesAdvance"); }
+
   // beyond the reference: the load on a wall. slot: a body slot, SPH_WALL_ALL (every boundary particle) or SPH_WALL_NO_BODY (the
   // boundary particles of no body). wallMeasure writes SPH_WALL_WORDS floats per sorted particle (fromSelection = true: per
   // particle of the current selection): the set's share of the position shift and velocity change of the contact inside the last

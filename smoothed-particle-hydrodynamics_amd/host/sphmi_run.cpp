@@ -76,6 +76,15 @@
 //        k * (VX, VY, VZ) (scene units per step); the pose is computed in double and narrowed once. Each moved step prints
 //        `_body: step S members M max_move X` (X: the largest displacement in units of r0, %.9g; from about 1 on the wall
 //        tunnels through liquid). With these options the position read-back is the blocking one.
+//   ... --body-region ... --body-free [--body-mass M] [--body-locks xyzr] [--body-gains C F]
+//        the body is free (sph_body_set_dynamics / sph_bodies_advance): the liquid moves it. Its members are equal
+//        point masses, M in total (default: members x cfg.mass); the centre of mass is their mean, summed in member order in
+//        double; the inverse inertia is the inverse of the point masses' inertia tensor, or all zero (the body never turns) where
+//        that tensor is singular (det <= 1e-12 x trace^3: a single row of particles, a single particle). --body-locks: the letters
+//        of the locked velocity axes and r for a locked rotation; --body-gains: contactGain and forceGain (default 1 1); gravity
+//        is the scene's. --body-velocity gives the initial velocity (scene units per step, divided by posTimeStep in double);
+//        --body-spin, --body-from and --body-until do not apply. After every step one line per advance is printed (%.9e):
+//        `_free: step S body 0 status T advances A max_move M  X x y z  V x y z  F x y z` (S steps done; F the load in newtons).
 //   ... --wall-load-every K
 //        after every K-th step, sph_wall_diagnostics over the liquid of the whole scene, one line per defined body B
 //        (with no body defined: one line for all walls, `body all`):
@@ -267,6 +276,7 @@ int main(int argc, char** argv) {
   float drainRegion[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
   bool bodySeen = false, bodyRegionSeen = false, bodySpinSeen = false; float bodyRegion[6] = {0, 0, 0, 0, 0, 0};
   double bodyVel[3] = {0, 0, 0}, bodySpin[7] = {0, 0, 1, 0, 0, 0, 0}; int bodyFrom = 0, bodyUntil = -1;
+  bool bodyFree = false; double bodyMass = 0, bodyGains[2] = {1, 1}; unsigned bodyLocks = 0; bool bodyLocksOk = true;
   bool dyeSeen = false, dyeRegionSeen = false, dyeEverySeen = false; float dyeRegion[6] = {0, 0, 0, 0, 0, 0}, dyeInflow = 0.f, dyeDiffusivity = 0.f; int dyeEvery = 0;
   int streamSeeds[2] = {0, 0}, streamEvery = 0, streamMaxSteps = 256; float streamStep = 0.f; bool streamSeen = false; const char* streamDir = nullptr;
   int tracerSeeds[2] = {0, 0}, tracersEvery = 1; bool tracersSeen = false;
@@ -299,6 +309,16 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--body-spin") && i + 7 < argc) { for (int k = 0; k < 7; k++) bodySpin[k] = atof(argv[++i]); bodySeen = bodySpinSeen = true; }
     else if (!strcmp(argv[i], "--body-from") && i + 1 < argc) { bodyFrom = atoi(argv[++i]); bodySeen = true; }
     else if (!strcmp(argv[i], "--body-until") && i + 1 < argc) { bodyUntil = atoi(argv[++i]); bodySeen = true; }
+    else if (!strcmp(argv[i], "--body-free")) { bodyFree = bodySeen = true; }
+    else if (!strcmp(argv[i], "--body-mass") && i + 1 < argc) { bodyMass = atof(argv[++i]); bodySeen = true; if (!(bodyMass > 0) || !std::isfinite(bodyMass)) bodyLocksOk = false; }
+    else if (!strcmp(argv[i], "--body-gains") && i + 2 < argc) { for (int k = 0; k < 2; k++) bodyGains[k] = atof(argv[++i]); bodySeen = true; }
+    else if (!strcmp(argv[i], "--body-locks") && i + 1 < argc) {
+      bodySeen = true;
+      for (const char* c = argv[++i]; *c; c++) {
+        const char* at = strchr("xyzr", *c);
+        if (at) bodyLocks |= 1u << (at - "xyzr"); else bodyLocksOk = false;
+      }
+    }
     else if (!strcmp(argv[i], "--drain-every") && i + 1 < argc) { drainEvery = atoi(argv[++i]); drainSeen = true; }
     else if (!strcmp(argv[i], "--drain-at") && i + 1 < argc) { drainAt = atoi(argv[++i]); drainSeen = true; }
     else if (!strcmp(argv[i], "--drain-types")) {
@@ -490,6 +510,8 @@ int main(int argc, char** argv) {
     for (double v : bodyVel) ok = ok && std::isfinite(v);
     for (double v : bodySpin) ok = ok && std::isfinite(v);
     if (bodySpinSeen && !(bodySpin[0] * bodySpin[0] + bodySpin[1] * bodySpin[1] + bodySpin[2] * bodySpin[2] > 0)) ok = false;
+    if (!bodyLocksOk || !std::isfinite(bodyGains[0]) || !std::isfinite(bodyGains[1])) ok = false;
+    if (!ok && bodyFree) fprintf(stderr, "--body-free: --body-mass M > 0, --body-locks of the letters x y z r, --body-gains C F finite\n");
     if (!ok) {
       fprintf(stderr, "--body-region X0 Y0 Z0 X1 Y1 Z1 (no bound a NaN) is needed by the other --body options; --body-velocity and "
                       "--body-spin take finite numbers, the spin axis is not zero; --body-from STEP: STEP >= 0\n");
@@ -667,13 +689,48 @@ int main(int argc, char** argv) {
     if (moving) {
       bodyMembers = ocl_solver->bodyDefineRegion(0, bodyRegion);
       if (bodyUntil < 0) bodyUntil = steps;
+      if (bodyFree) {  // equal point masses at the reference placement, where the body stands now
+        std::vector<float> ref(4 * (size_t)bodyMembers);
+        ocl_solver->bodyRead(0, nullptr, ref.data(), nullptr);
+        sph_body_dynamics dyn = {};
+        dyn.mass = bodyMass > 0 ? bodyMass : (double)bodyMembers * (double)cfg.mass;
+        double sum[3] = {0, 0, 0};
+        for (int64_t k = 0; k < bodyMembers; k++)
+          for (int c = 0; c < 3; c++) sum[c] = sum[c] + (double)ref[4 * k + c];
+        for (int c = 0; c < 3; c++) dyn.com[c] = dyn.position[c] = sum[c] / (double)bodyMembers;
+        double I[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        const double mk = dyn.mass / (double)bodyMembers;
+        for (int64_t k = 0; k < bodyMembers; k++) {
+          const double r[3] = {(double)ref[4 * k] - dyn.com[0], (double)ref[4 * k + 1] - dyn.com[1], (double)ref[4 * k + 2] - dyn.com[2]};
+          const double r2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+          for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) I[a][b] += mk * ((a == b ? r2 : 0.0) - r[a] * r[b]);
+        }
+        const double c00 = I[1][1] * I[2][2] - I[1][2] * I[2][1], c01 = I[1][2] * I[2][0] - I[1][0] * I[2][2], c02 = I[1][0] * I[2][1] - I[1][1] * I[2][0];
+        const double det = I[0][0] * c00 + I[0][1] * c01 + I[0][2] * c02, tr = I[0][0] + I[1][1] + I[2][2];
+        if (det > 1e-12 * tr * tr * tr) {  // symmetric: the inverse is the adjugate over the determinant
+          dyn.inertiaInv[0] = c00 / det;
+          dyn.inertiaInv[1] = (I[0][0] * I[2][2] - I[0][2] * I[2][0]) / det;
+          dyn.inertiaInv[2] = (I[0][0] * I[1][1] - I[0][1] * I[1][0]) / det;
+          dyn.inertiaInv[3] = c01 / det;
+          dyn.inertiaInv[4] = c02 / det;
+          dyn.inertiaInv[5] = (I[0][2] * I[1][0] - I[0][0] * I[1][2]) / det;
+        }
+        dyn.orientation[0] = 1.0;
+        const float posTimeStep = cfg.timeStep * cfg.simulationScaleInv;
+        for (int c = 0; c < 3; c++) dyn.velocity[c] = bodyVel[c] / (double)posTimeStep;
+        dyn.gravity[0] = cfg.gravity_x; dyn.gravity[1] = cfg.gravity_y; dyn.gravity[2] = cfg.gravity_z;
+        dyn.contactGain = bodyGains[0]; dyn.forceGain = bodyGains[1];
+        dyn.locks = bodyLocks;
+        ocl_solver->bodySetDynamics(0, &dyn);
+      }
     }
     Watch helper; helper.quiet = quiet;
     double total = 0;
     for (int iterationCount = 0; iterationCount < steps; iterationCount++) {
       helper.refresh();
       if (!quiet) printf("\n[[ Step %d ]]\n", iterationCount);
-      if (moving && ocl_solver->bodyCount(0) > 0 && iterationCount >= bodyFrom && iterationCount < bodyUntil) {  // (a drain may have taken the body)
+      if (moving && !bodyFree && ocl_solver->bodyCount(0) > 0 && iterationCount >= bodyFrom && iterationCount < bodyUntil) {  // (a drain may have taken the body)
         float pose[12];
         body_pose(bodySpin, bodyVel, (double)(iterationCount - bodyFrom + 1), pose);
         const float maxMove = ocl_solver->bodySetPose(0, pose);
@@ -938,6 +995,14 @@ int main(int argc, char** argv) {
                  torque[0], torque[1], torque[2]);
         }
         helper.report("_wall: \t\t\t%9.3f ms\n");
+      }
+      if (bodyFree && ocl_solver->bodyCount(0) > 0) {  // the load of the step just done moves the body (a drain may have taken it)
+        std::vector<double> rec((size_t)SPH_MAX_BODIES * SPH_BODY_STATE_WORDS);
+        ocl_solver->bodiesAdvance(rec.data());
+        const double* r = rec.data();
+        printf("_free: step %d body 0 status %.0f advances %.0f max_move %.9e  X %.9e %.9e %.9e  V %.9e %.9e %.9e  F %.9e %.9e %.9e\n",
+               iterationCount + 1, r[0], r[2], r[3], r[4], r[5], r[6], r[11], r[12], r[13], r[20], r[21], r[22]);
+        helper.report("_free: \t\t\t%9.3f ms\n");
       }
       if (dyeing) {
         const float stability = ocl_solver->fieldDiffuse(0, dyeDiffusivity * cfg.timeStep, dyeDiffusivity > 0.f ? 1 : 0, dyeMask);

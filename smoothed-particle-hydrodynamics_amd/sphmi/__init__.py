@@ -33,6 +33,11 @@ FORCE_WORDS = 40  # sph_force_measure record (frames.FORCE_FIELDS)
 FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
 WALL_WORDS = 32  # sph_wall_measure record (frames.WALL_FIELDS)
 WALL_DIAG_WORDS = 32  # sph_wall_diagnostics record (frames.WALL_DIAG_FIELDS)
+BODY_STATE_WORDS = 48  # sph_bodies_advance record per slot (BODY_STATE_FIELDS)
+# word ranges of that record (include/sphmi.h): name -> (first word, count)
+BODY_STATE_FIELDS = {"status": (0, 1), "members": (1, 1), "advances": (2, 1), "max_move": (3, 1), "position": (4, 3),
+                     "orientation": (7, 4), "velocity": (11, 3), "angular_momentum": (14, 3), "omega": (17, 3), "load_force": (20, 3),
+                     "load_torque": (23, 3), "n_contact": (26, 1), "n_share": (27, 1), "offenders": (28, 1), "lowest_member": (29, 1)}
 WALL_ALL, WALL_NO_BODY = -1, -2  # the wall set in place of a body slot: every boundary particle / those that belong to no body
 FIELD_SLOTS = 4  # carried particle fields per solver (sph_field_*)
 FIELD_DIAG_WORDS = 8  # sph_field_diagnostics record (frames.FIELD_DIAG_FIELDS)
@@ -104,6 +109,14 @@ class SphTraceParams(C.Structure):
     _fields_ = [("step", C.c_float), ("minSpeed", C.c_float), ("maxSteps", C.c_int32), ("mode", C.c_int32), ("integrator", C.c_int32)]
 
 
+class SphBodyDynamics(C.Structure):
+    """sph_body_dynamics of include/sphmi.h (owHIPSolver.body_set_dynamics fills one, body_dynamics returns its fields)."""
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("inertiaInv", C.c_double * 6), ("position", C.c_double * 3),
+                ("orientation", C.c_double * 4), ("velocity", C.c_double * 3), ("angularMomentum", C.c_double * 3),
+                ("spin", C.c_double * 3), ("gravity", C.c_double * 3), ("force", C.c_double * 3), ("torque", C.c_double * 3),
+                ("contactGain", C.c_double), ("forceGain", C.c_double), ("locks", C.c_uint32)]
+
+
 class SphError(RuntimeError):
     pass
 
@@ -171,7 +184,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_field_release", "sph_field_write", "sph_field_read", "sph_field_set_region", "sph_field_set_selection",
                     "sph_field_diffuse", "sph_field_diagnostics", "sph_trace_streamlines", "sph_tracers_set", "sph_tracers_advect",
                     "sph_tracers_read", "sph_body_define_ids", "sph_body_define_region", "sph_body_release", "sph_body_count",
-                    "sph_body_read", "sph_body_set_pose", "sph_wall_measure", "sph_wall_diagnostics"] + _STAGE_FUNCS
+                    "sph_body_read", "sph_body_set_pose", "sph_wall_measure", "sph_wall_diagnostics", "sph_body_set_dynamics",
+                    "sph_body_get_dynamics", "sph_bodies_advance"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -304,6 +318,10 @@ def device_lib():
             L.sph_body_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
             L.sph_body_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sph_body_set_pose.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_bodies_advance"):  # (optional: an A/B library built from an older csrc/ has no free bodies)
+            L.sph_body_set_dynamics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            L.sph_body_get_dynamics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+            L.sph_bodies_advance.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "sph_wall_measure"):  # (optional: an A/B library built from an older csrc/ has no wall loads)
             L.sph_wall_measure.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
             L.sph_wall_diagnostics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
@@ -1134,6 +1152,66 @@ class owHIPSolver:
             e.offenders, e.lowest_member = int(counts[0]), int(counts[1])
             raise e
         return np.float32(move[0])
+
+    # --- free bodies (sph_body_set_dynamics / sph_bodies_advance): rigid-body dynamics driven by the wall loads ---
+    _BODY_VEC = {"com": 3, "inertiaInv": 6, "position": 3, "orientation": 4, "velocity": 3, "angularMomentum": 3, "spin": 3,
+                 "gravity": 3, "force": 3, "torque": 3}
+
+    def body_set_dynamics(self, slot, **params):
+        """Give body `slot` a dynamic state (include/sphmi.h: sph_body_dynamics; keyword = field name). `mass`, `com` and
+        `position` are required; inertiaInv, velocity, angularMomentum, spin, force and torque default to zero, orientation to
+        (1, 0, 0, 0), gravity to cfg.gravity_*, the gains to 1; `locks` is the bit word or a string of the letters x, y, z, r.
+        With no keyword at all the body is kinematic again. Two dynamic bodies may not share a member."""
+        if not params:
+            self._chk(self._L.sph_body_set_dynamics(self._h, int(slot), None))
+            return
+        d = SphBodyDynamics()
+        for need in ("mass", "com", "position"):
+            if need not in params:
+                raise SphError("body_set_dynamics: %s is required" % need)
+        vals = {"orientation": (1.0, 0.0, 0.0, 0.0), "gravity": (self.cfg.gravity_x, self.cfg.gravity_y, self.cfg.gravity_z),
+                "contactGain": 1.0, "forceGain": 1.0, "locks": 0}
+        vals.update(params)
+        for k, v in vals.items():
+            if k in self._BODY_VEC:
+                a = np.asarray(v, np.float64).reshape(-1)
+                if a.size != self._BODY_VEC[k]:
+                    raise SphError("body_set_dynamics: %s takes %d numbers" % (k, self._BODY_VEC[k]))
+                setattr(d, k, (C.c_double * a.size)(*a))
+            elif k in ("mass", "contactGain", "forceGain"):
+                setattr(d, k, float(v))
+            elif k == "locks":
+                if isinstance(v, str):
+                    if set(v) - set("xyzr"):
+                        raise SphError("body_set_dynamics: locks is a string of the letters x, y, z, r")
+                    v = sum(1 << "xyzr".index(ch) for ch in set(v))
+                d.locks = int(v)
+            else:
+                raise SphError("body_set_dynamics: unknown parameter %s" % k)
+        self._chk(self._L.sph_body_set_dynamics(self._h, int(slot), C.byref(d)))
+
+    def body_dynamics(self, slot):
+        """The live dynamic state of body `slot` as a dict of float64 arrays / numbers named like sph_body_dynamics, or None for
+        a body that is not dynamic. Blocking."""
+        d = SphBodyDynamics()
+        flag = np.zeros(1, np.int32)
+        self._chk(self._L.sph_body_get_dynamics(self._h, int(slot), C.byref(d), _ptr(flag)))
+        if not flag[0]:
+            return None
+        out = {k: np.array(getattr(d, k), np.float64) for k in self._BODY_VEC}
+        out.update(mass=d.mass, contactGain=d.contactGain, forceGain=d.forceGain, locks=int(d.locks))
+        return out
+
+    def bodies_advance(self, read=True):
+        """One step of rigid-body dynamics for every dynamic body, on the GPU: the load of the last completed step on the body,
+        the new state, the new placement of the members (include/sphmi.h states every operation). read=True waits once and returns
+        float64[MAX_BODIES, 48] records (BODY_STATE_FIELDS); read=False enqueues everything and returns None without a wait."""
+        if not read:
+            self._chk(self._L.sph_bodies_advance(self._h, None))
+            return None
+        out = np.zeros((MAX_BODIES, BODY_STATE_WORDS), np.float64)
+        self._chk(self._L.sph_bodies_advance(self._h, _ptr(out)))
+        return out
 
     # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
     def _field_values(self, values, what):

@@ -1083,3 +1083,39 @@ def spin(axis, about, rate, step):
     """The pose of a blade at step number `step`: the reference placement turned by rate * step radians about the line through
     `about` along `axis`; the identity at step 0."""
     return pose_rotate(axis, float(rate) * float(step), about)
+
+
+# ---- free bodies (owHIPSolver.body_set_dynamics / bodies_advance; include/sphmi.h, sph_bodies_advance) ----
+def body_mass_properties(ref_positions, mass):
+    """Mass properties of a body whose members are equal point masses: ref_positions [M, 3 or 4] (body_read's reference
+    positions), `mass` the body's total mass. Returns (com float64[3], inertia float64[3, 3] about com in reference axes, position
+    units squared times kg, inertiaInv float64[6] = xx yy zz xy xz yz as sph_body_dynamics takes it). The inverse is the
+    pseudo-inverse: a principal axis along which the members have no extent (a single row of particles about its own line, a
+    single particle) has zero inertia and gets a zero row, so the body never turns about it."""
+    p = np.asarray(ref_positions, np.float64)
+    p = p.reshape(-1, p.shape[-1])[:, :3]
+    if p.shape[0] < 1 or not float(mass) > 0:
+        raise ValueError("body_mass_properties: at least one member and a mass > 0")
+    com = p.mean(axis=0)
+    r = p - com
+    m = float(mass) / p.shape[0]
+    inertia = m * (np.eye(3) * (r * r).sum() - r.T @ r)
+    w, v = np.linalg.eigh(inertia)
+    keep = w > 1e-12 * max(float(w.max()), 0.0)
+    inv = (v[:, keep] / w[keep]) @ v[:, keep].T if keep.any() else np.zeros((3, 3))
+    inv = 0.5 * (inv + inv.T)
+    return com, inertia, np.array([inv[0, 0], inv[1, 1], inv[2, 2], inv[0, 1], inv[0, 2], inv[1, 2]], np.float64)
+
+
+def body_state_summary(record, cfg):
+    """One slot's bodies_advance() record as physical numbers, a dict: status, members, advances, max_move (in r0); position
+    (metres: position units times simulationScale), velocity (the particles' velocity units, metres per second), orientation,
+    angular_momentum, omega as they are; load_force in newtons; load_torque about the centre of mass in newton x position unit;
+    n_contact, n_share, offenders, lowest_member."""
+    r = np.asarray(record, np.float64).reshape(48)
+    out = {"status": int(r[0]), "members": int(r[1]), "advances": int(r[2]), "max_move": r[3],
+           "position": r[4:7] * float(cfg.simulationScale), "orientation": r[7:11].copy(), "velocity": r[11:14].copy(),
+           "angular_momentum": r[14:17].copy(), "omega": r[17:20].copy(), "load_force": r[20:23].copy(),
+           "load_torque": r[23:26].copy(), "n_contact": int(r[26]), "n_share": int(r[27]), "offenders": int(r[28]),
+           "lowest_member": int(r[29]) if r[0] == 1 else -1}
+    return out
