@@ -1041,10 +1041,12 @@ int sph_synchronize(sph_solver* s);
 typedef enum sph_stage {
   SPH_ST_HASH = 0, SPH_ST_SORT, SPH_ST_SORT_POST, SPH_ST_INDEX, SPH_ST_FIND_NEIGHBORS, SPH_ST_DENSITY,
   SPH_ST_FORCES, SPH_ST_ELASTIC, SPH_ST_PREDICT_DENSITY, SPH_ST_PRESSURE_FORCE, SPH_ST_INTEGRATE, SPH_ST_MEMBRANES,
+  SPH_ST_BANDS, /* the search bands of sph_step() (sph_set_search_bands), built between the cell table and the search */
   SPH_ST_COUNT
 } sph_stage;
 int sph_set_stage_timing(sph_solver* s, int enable);
-int sph_get_stage_times(sph_solver* s, double* ms_total, int64_t* launches, int n); /* n = SPH_ST_COUNT */
+/* n = SPH_ST_COUNT, or SPH_ST_BANDS for a caller that knows the stages in front of it only */
+int sph_get_stage_times(sph_solver* s, double* ms_total, int64_t* launches, int n);
 int sph_reset_stage_times(sph_solver* s);
 /* Radix passes (8- or 9-bit digits) the sort of sph_step() takes for this solver: 24 algorithmic bytes per particle each. */
 int sph_step_sort_passes(sph_solver* s);
@@ -1066,6 +1068,14 @@ int sph_set_step_pipeline(sph_solver* s, int32_t depth);
  * launch consults the per-wave bytes only where the launch before found nothing flagged); 1: always mark and consult; 2: off.
  * Results do not depend on it. */
 int sph_set_wave_skip(sph_solver* s, int32_t mode);
+
+/* The search bands of sph_step(): once per step, the sorted particles within the search radius of a y or z face of their cell are
+ * compacted into one array per neighbour row of cells, and findNeighbors tests only those of the cells it visits across a face
+ * or an edge. 0 (the default): automatic — used outside slab mode on every grid for which the bands are provably a superset of
+ * the neighbours (a cell id mask that changes no id of the grid, at least 3 cells per axis, the 27 cell offsets distinct); 1: off. Results do not depend on
+ * it. The flags, the arrays and their start tables of the last step that used them: sph_read_buffer "searchBandFlags",
+ * "searchBands", "searchBandStart" (SPH_ERR_ORDER if the last step did not build them). */
+int sph_set_search_bands(sph_solver* s, int32_t mode);
 
 /* ---- Spatial decomposition (no reference counterpart: the reference is single-device) -----------------
  * The global box is cut into z-slabs of whole cell layers, one solver (one GPU, one process) per slab. A solver holds the

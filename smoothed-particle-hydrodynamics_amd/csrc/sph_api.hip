@@ -169,7 +169,7 @@ extern "C" int sph_reset_stage_times(sph_solver* s) {
   return rc;
 }
 extern "C" int sph_get_stage_times(sph_solver* s, double* ms_total, int64_t* launches, int n) {
-  if (!s || n != SPH_ST_COUNT) return SPH_ERR_INVALID;
+  if (!s || (n != SPH_ST_COUNT && n != SPH_ST_BANDS)) return SPH_ERR_INVALID;  // (SPH_ST_BANDS: a caller from before the band stage)
   int rc = resolve_pending(s);
   if (rc) return rc;
   for (int i = 0; i < n; i++) {
@@ -443,6 +443,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
     float U[64];
     compute_bin_thresholds(cfg->h, U);
     UP(binU, U, sizeof(U));
+    s->bandRadius = sph_band_radius(d, U[63]);
   }
 #undef UP
   // buffers the reference leaves uninitialised but that an export may read before they are written
@@ -558,6 +559,10 @@ extern "C" int sph_run_compute_interaction_with_membranes_finalize(sph_solver* s
 #define SPH_OVERLAP_MIN_PARTICLES (4 << 20)
 #endif
 static_assert(SPH_OVERLAP_CHUNKS >= 1 && SPH_OVERLAP_CHUNKS <= SPH_STEP_CHUNKS_MAX, "chunk count");
+// Fewest particles for which the automatic mode of sph_set_search_bands builds bands
+#ifndef SPH_BANDS_MIN_PARTICLES
+#define SPH_BANDS_MIN_PARTICLES 0
+#endif
 // ---- the pipelined step. Where the search runs in chunks, the first D of the kernels behind it (forces; then
 // predicted density and pressure force of every iteration) can follow it on chunkStream chunk by chunk, stage k one chunk behind
 // stage k - 1: a stage reads of other particles only what the stage before wrote for direct neighbours, so if the neighbours of
@@ -592,6 +597,29 @@ extern "C" int sph_set_wave_skip(sph_solver* s, int32_t mode) {
   if (mode < 0 || mode > 2) { sph_set_error("sph_set_wave_skip: %d is not in [0, 2]", mode); return SPH_ERR_INVALID; }
   s->waveSkipMode = mode;
   return SPH_OK;
+}
+
+// The search bands: 0 automatic, 1 off. Results do not depend on it.
+extern "C" int sph_set_search_bands(sph_solver* s, int32_t mode) {
+  ENTER(s);
+  if (mode < 0 || mode > 1) { sph_set_error("sph_set_search_bands: %d is not in [0, 1]", mode); return SPH_ERR_INVALID; }
+  s->bandsMode = mode;
+  return SPH_OK;
+}
+
+// Whether this step's search may read bands. The superset proof needs keys that are cell ids (an id mask that changes no id of the grid), at least
+// three cells per axis (a cell reached by an offset that crosses the grid's edge along an axis is then farther away than the search
+// radius) and the 27 cell offsets distinct, also modulo G (a key difference then names one step per axis).
+static bool sph_bands_apply(const sph_solver* s) {
+  const SphDev& d = s->d;
+  if (s->hasSlab || s->bandsMode != 0 || (unsigned long long)d.G > (unsigned long long)d.cellMask + 1ull || d.N < SPH_BANDS_MIN_PARTICLES) return false;
+  if (d.gx < 3 || d.gy < 3 || d.gz < 3 || (long long)d.gx * d.gy * d.gz != (long long)d.G) return false;
+  long long off[27];
+  for (int k = 0; k < 27; k++) off[k] = (k % 3 - 1) + (long long)(k / 3 % 3 - 1) * d.gx + (long long)(k / 9 - 1) * d.gx * d.gy;
+  for (int a = 0; a < 27; a++)
+    for (int b = a + 1; b < 27; b++)
+      if ((off[a] - off[b]) % (long long)d.G == 0) return false;
+  return true;
 }
 
 // 1: the serial search. Slab mode launches by ghost layers; with stage timing on, the step stays the sequence of stages that
@@ -655,7 +683,7 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth) {
     if (hi <= lo) return SPH_OK;  // more chunks than blocks of 256 particles
     if (stage > 0) return sphk_pipeline_stage(s, stage, c, lo, hi, s->chunkStream);
     hipStream_t fnStream = (c & 1) ? s->searchStream : s->stream;
-    int rc = sphk_find_neighbors(s, -1, lo, hi, fnStream);
+    int rc = sphk_find_neighbors(s, -1, lo, hi, fnStream, s->bandsStep);
     if (rc != SPH_OK) return rc;
     SPH_HIP(hipEventRecord(s->evChunk[c], fnStream));
     SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evChunk[c], 0));
@@ -713,6 +741,13 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   // layers only; the iteration-0 predicted positions one hop further than anything else (k_ghost_init: everywhere).
   const bool slab = s->hasSlab;
   const int M = s->cfg.maxIteration;
+  // The search bands, behind the cell table and in front of everything that forks off this stream.
+  s->bandsStep = sph_bands_apply(s);
+  if (s->bandsStep) {
+    rc = sph_grow_scratch(s, s->bandBuf, sphk_bands_bytes(s, nullptr));  // (the first such step allocates)
+    if (rc != SPH_OK) { s->bandsStep = false; return rc; }
+    RUN(SPH_ST_BANDS, sphk_build_bands(s));
+  }
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
   const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
   const int piped = chunks > 1 ? step_pipeline(s) : 0;  // stages 1 .. piped are enqueued with the search
@@ -725,7 +760,7 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
     rc = enqueue_search_overlapped(s, chunks, piped);
     if (rc != SPH_OK) return rc;
   } else {
-    RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1)));
+    RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1), 0, INT32_MAX, nullptr, s->bandsStep));
     RUN(SPH_ST_DENSITY, sphk_density(s, layersFor(1)));
   }
   if (slab) RUN(SPH_ST_FORCES, sphk_ghost_init(s));

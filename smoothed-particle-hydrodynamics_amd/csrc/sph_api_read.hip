@@ -154,7 +154,7 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   const SphDev& d = s->d;
   const size_t n = (size_t)d.N, G1 = (size_t)d.G + 1;
   size_t need = 0;
-  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE, B_K12SKIP, B_K10SKIP, B_NBP, B_NBX, B_PBLK, B_XBLK } which;
+  enum { B_POS, B_VEL, B_SPOS, B_SVEL, B_ACC, B_NMAP, B_NIDS, B_PI, B_PIB, B_GCI, B_GCIF, B_P, B_RHO, B_DBG, B_TRACE, B_K12SKIP, B_K10SKIP, B_NBP, B_NBX, B_PBLK, B_XBLK, B_BANDFLAGS, B_BANDS, B_BANDSTART } which;
   if (!strcmp(name, "position")) { which = B_POS; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "velocity")) { which = B_VEL; need = sizeof(float4) * 2 * n; }
   else if (!strcmp(name, "sortedPosition")) { which = B_SPOS; need = sizeof(float4) * 2 * n; }
@@ -179,7 +179,16 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
   else if (!strcmp(name, "movedNeighbourhood")) { which = B_NBX; need = (n + SPH_TILE - 1) / SPH_TILE; }
   else if (!strcmp(name, "pressureFlags")) { which = B_PBLK; need = (n + SPH_TILE - 1) / SPH_TILE; }
   else if (!strcmp(name, "movedFlags")) { which = B_XBLK; need = (n + SPH_TILE - 1) / SPH_TILE; }
+  // the search bands of the last step: one flag byte per sorted particle (bit s: member of band s); the eight band
+  // arrays, N records (x, y, z, sorted index as bits) each, zeros behind a band's entries; the eight start tables of G + 1 words
+  else if (!strcmp(name, "searchBandFlags")) { which = B_BANDFLAGS; need = n; }
+  else if (!strcmp(name, "searchBands")) { which = B_BANDS; need = sizeof(float4) * 8 * n; }
+  else if (!strcmp(name, "searchBandStart")) { which = B_BANDSTART; need = sizeof(uint32_t) * 8 * G1; }
   else { sph_set_error("unknown buffer '%s'", name); return SPH_ERR_UNKNOWN_BUFFER; }
+  if ((which == B_BANDFLAGS || which == B_BANDS || which == B_BANDSTART) && !s->bandsStep) {
+    sph_set_error("buffer '%s': the last step built no search bands", name);
+    return SPH_ERR_ORDER;
+  }
   if (needed) *needed = need;
   if (!out) return SPH_OK;
   if (bytes != need) { sph_set_error("buffer '%s' is %zu bytes, caller gave %zu", name, need, bytes); return SPH_ERR_SIZE; }
@@ -247,6 +256,19 @@ extern "C" int sph_read_buffer(sph_solver* s, const char* name, void* out, size_
     case B_NBX: rc = sph_d2h(s, o, d.nbhd + (size_t)((s->cfg.maxIteration >= 2 ? 2 * s->cfg.maxIteration - 2 : 0) & (SPH_GATE_SLOTS - 1)) * d.nbStride, need); break;
     case B_PBLK: rc = sph_d2h(s, o, d.pBlk, need); break;
     case B_XBLK: rc = sph_d2h(s, o, d.xBlk, need); break;
+    case B_BANDFLAGS: { SphBands b; sphk_bands_bytes(s, &b); rc = sph_d2h(s, o, b.flags, need); } break;
+    case B_BANDSTART: { SphBands b; sphk_bands_bytes(s, &b); rc = sph_d2h(s, o, b.start, need); } break;
+    case B_BANDS: {
+      SphBands b;
+      sphk_bands_bytes(s, &b);
+      memset(o, 0, need);
+      for (int k = 0; k < 8 && rc == SPH_OK; k++) {
+        uint32_t count = 0;  // the band's total: the last entry of its start table
+        rc = sph_d2h(s, &count, b.start + (size_t)k * G1 + d.G, sizeof(uint32_t));
+        if (rc == SPH_OK && count > n) { sph_set_error("buffer '%s': band %d holds %u entries of %zu particles", name, k, count, n); rc = SPH_ERR_INVALID; }
+        if (rc == SPH_OK && count) rc = sph_d2h(s, o + sizeof(float4) * n * k, b.pos + (size_t)k * b.cap, sizeof(float4) * count);
+      }
+    } break;
     case B_RHO:
       rc = sph_d2h(s, o, d.rho, sizeof(float) * n);
       if (rc == SPH_OK) {

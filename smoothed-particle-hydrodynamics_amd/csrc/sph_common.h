@@ -106,6 +106,22 @@ struct SphDev {  // what the kernels see; passed by value
   uint32_t* dbg;  // SPH_DBG_WORDS diagnostic counters (neighbour-search fallbacks etc.), zeroed by sph_reset_stage_times
 };
 
+// Search bands (sph_bands.hip). Slot s = r - (r > 4) belongs to the search kernel's row r != 4 of cells.
+struct SphBandGeom {  // what the band kernels need of the step's geometry
+  int N, G, gx, gy, gz, waves;  // waves = ceil(N / 64)
+  int aliased;  // the id mask can change a cell id of the grid (G > mask + 1): keys are not cell ids, every particle is in every band
+  float cellSize, cellSizeInv, Rb;
+};
+struct SphBands {  // the arrays, all in sph_solver::bandBuf
+  float4* pos;               // [8][cap] records (x, y, z, sorted index as bits), each band in sorted order
+  uint32_t* start;           // [8][G + 1] band entries in front of cellStart[c]
+  uint8_t* flags;            // [cap] bit s: the sorted particle is in band s
+  unsigned long long* mask;  // [waveStride][8] the ballot of each wave of 64 sorted particles, per band
+  uint32_t* waveOff;         // [waveStride][8] counts, then exclusive offsets, per wave and band; entry ceil(N / 64): the bands' totals
+  uint32_t* superCnt;        // [8][superStride] entries per 1024 waves
+  int cap, waveStride, superStride;
+};
+
 // A device buffer that only grows (sph_grow_scratch) and frees itself with the solver that holds it.
 struct SphScratch {
   void* p = nullptr;
@@ -184,7 +200,12 @@ struct sph_solver {
                                        // (SphDev::pBlk ...); the launchers of sph_pcisph.hip hand every other launch null pointers
   int waveSkipMode = 0;                // sph_set_wave_skip: 0 the built-in policy, 1 always mark and consult, 2 flags off
   uint32_t* pipeTable = nullptr;
-  bool copyPending = false;            // a copy was issued and sph_read_position_wait has not run since
+  // search bands (sph_bands.hip): built by enqueue_step behind the cell table where sph_bands_apply allows it
+  int bandsMode = 0;                   // sph_set_search_bands: 0 automatic, 1 off
+  bool bandsStep = false;              // set by enqueue_step: this step's search reads the bands (and bandBuf holds them)
+  float bandRadius = 0.f;              // Rb of the bands in bandBuf
+  SphScratch bandBuf;                  // grown on the first step that builds bands
+  bool copyPending = false;           // a copy was issued and sph_read_position_wait has not run since
   float* copyUserDst = nullptr;        // where the caller wants the data
   void* copyStage = nullptr; size_t copyStageBytes = 0;  // pinned staging, only for destinations that cannot be page-locked in place
   bool copyViaStage = false;
@@ -353,7 +374,14 @@ int sphk_hash_sort_post_slab(sph_solver* s);  // slab mode: K2 + sort + K3 with 
 int sphk_clear_neighbors(sph_solver* s);
 // [idxLo, idxHi): the sorted particles of the launch, intersected with the cell range that ghostDepth gives; the grid covers
 // min(idxHi, N) - idxLo particles. On `stream` (nullptr: s->stream).
-int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1, int idxLo = 0, int idxHi = INT32_MAX, hipStream_t stream = nullptr);
+// bands: stage the eight non-own rows from this step's search bands (the caller built them: sphk_build_bands)
+int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1, int idxLo = 0, int idxHi = INT32_MAX, hipStream_t stream = nullptr,
+                        bool bands = false);
+// sph_bands.hip
+size_t sphk_bands_bytes(const sph_solver* s, SphBands* out);  // bytes of bandBuf for the solver's capacity and grid; *out: the arrays in it
+SphBandGeom sph_band_geom(const sph_solver* s);
+float sph_band_radius(const SphDev& d, float filterR2);       // Rb from the search filter's radius^2 (binU[63])
+int sphk_build_bands(sph_solver* s);                          // flags, scan, scatter, start tables; on s->stream behind the cell table
 // sph_pcisph.hip
 int sphk_density(sph_solver* s, int ghostDepth = -1);
 // density and the record pack of chunk c of the partition that enqueue_search_overlapped (sph_api.hip) keeps in s->chunkEdges

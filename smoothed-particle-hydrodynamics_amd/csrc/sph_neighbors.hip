@@ -52,6 +52,7 @@ int sphk_clear_neighbors(sph_solver* s) {
 struct FnParams {
   int G, gx, gy, rangeLo, rangeHi;
   int idxLo, idxHi;  // the launch serves the sorted particles [idxLo, idxHi) of that cell range (a chunk of the overlapped step)
+  int gz, bandCap;   // search bands (BANDS launches): the grid's z extent, records per band array
   float h, cellSize, cellSizeInv, simScale, xmin, ymin, zmin;
 };
 struct FnArrays {  // (what the exact walk needs; built inside the kernel from its arguments)
@@ -96,6 +97,7 @@ struct FnShared {
   float binU[64];                                 // U[j]: d^2 < U[j]  <=>  counted in histogram bins 0..j; r_thr^2 table; filter radius (see SphDev::binU)
   int rowLo[9], rowHi[9], rowBase[9];             // staged runs: sorted-index range and first LDS slot
   int win[9][FN_WIN];                             // cellStart[] of the cells cLo-1 .. of every row (see the staging code)
+  int winTrue[9][FN_WIN];                         // BANDS: win holds bandStart[] for the rows != 4, this the cellStart[] of the same cells
   uint32_t hist[FN_WAVES][32];                    // radial histograms of the wave-per-particle walk
 #ifdef FN_STAMPS
   uint32_t stamps[16];                            // diagnostic build: cycles per phase, summed over the workgroup's waves
@@ -129,6 +131,8 @@ static_assert(FN_LIST_CAP <= 64, "one bit per list entry");
 // 30-bin histogram (LDS atomics), every lane derives the same r_thr, pass 1 assigns slots in traversal order with a ballot
 // prefix (lane order == candidate order inside a chunk) and stops at 32. Candidates come from the staged LDS copy where the
 // cell is staged (the usual case: a list overflowed) and from global memory otherwise (wrapped / aliased / dropped cells).
+// BANDS: the rows other than the own one are staged from the search bands, incomplete copies of their cells — global memory.
+template <bool BANDS>
 __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays& g, FnShared& sh, int id, int wave, int lane) {
   const float4 me = g.sortedPos[id];
   const int myCell = (int)g.keys[id];
@@ -149,7 +153,7 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
     for (int k = 0; k < 8; k++) {
       const int raw = myCell + off[k];
       int c = wrap_cell(raw, d.G);
-      const int r = (c == raw) ? rows[k] : -1;  // wrapped cells are never staged
+      const int r = (c == raw && (!BANDS || rows[k] == 4)) ? rows[k] : -1;  // wrapped cells are never staged
       c = min(max(c, 0), d.G - 1);              // no-op for particles inside the box; keeps the table read in range
       lo[k] = (int)g.cellStart[c];
       hi[k] = (int)g.cellStart[c + 1];
@@ -230,13 +234,21 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
 // Synchronisation: ONE workgroup barrier per batch, between the staging of the candidates and their use. Everything before it
 // (batch bounds, the 9 candidate runs, their LDS layout) is computed redundantly by every wave from loads with workgroup-uniform
 // addresses, everything after it is private to a wave (its lists, its d^2 staging area, the exact walks of its own particles).
+//
+// BANDS: the eight rows other than the own x-row are staged from the search bands of the step — bandPos[slot of the
+// row], with bandStart[slot] read where cellStart is read for the own row — so a piece of those rows holds only the candidates within
+// the filter's reach of the face(s) it shares with the particle's cell, and the sorted index of an accepted entry comes from
+// the index word of its record. Particles whose key is not the id of the in-grid cell their coordinates truncate to take the exact walk.
+template <bool BANDS>
 __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, const float4* __restrict__ sortedPos,
                                                                    const uint32_t* __restrict__ keys,
                                                                    const uint32_t* __restrict__ cellStart,
                                                                    const float* __restrict__ binU, int32_t* __restrict__ nbrId,
                                                                    float* __restrict__ nbrDist, uint16_t* __restrict__ nbr16,
                                                                    int32_t* __restrict__ nbrBase, uint32_t* __restrict__ dbg,
-                                                                   uint32_t* __restrict__ trace) {  // trace: FN_STAMPS builds only
+                                                                   uint32_t* __restrict__ trace,  // trace: FN_STAMPS builds only
+                                                                   const float4* __restrict__ bandPos,
+                                                                   const uint32_t* __restrict__ bandStart) {
   extern __shared__ __align__(16) unsigned char fn_smem[];
   FnShared& sh = *reinterpret_cast<FnShared*>(fn_smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -297,7 +309,9 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     const int r = (int)((0x862071534ull >> (4 * q)) & 15ull);  // order[q]
     const int shift = (r % 3 - 1) * d.gx + (r / 3 - 1) * d.gx * d.gy;
     const int cell = ((lane & 1) ? cHi + 2 : cLo - 1) + shift;
-    const int v = (int)cellStart[min(max(cell, 0), d.G)];  // (clamped table reads: an out-of-grid run is empty)
+    const uint32_t* tbl = cellStart;
+    if (BANDS && r != 4) tbl = bandStart + (size_t)(r - (r > 4 ? 1 : 0)) * ((size_t)d.G + 1);
+    const int v = (int)tbl[min(max(cell, 0), d.G)];  // (clamped table reads: an out-of-grid run is empty)
 #pragma unroll
     for (int qq = 0; qq < 9; qq++) {
       const int lo = __builtin_amdgcn_readlane(v, 2 * qq), hi = __builtin_amdgcn_readlane(v, 2 * qq + 1);
@@ -321,6 +335,10 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     int base = 0;
 #pragma unroll
     for (int q = 0; q < 9; q++) { sd[q] = runLo[q] - base; base += runN[q]; se[q] = base; }
+    if (BANDS) {  // runs 1 .. 8 are read from bandPos: record = slot + sd[q] of the row's band array (8 bandCap < 2^31: N <= 2^27)
+#pragma unroll
+      for (int q = 1; q < 9; q++) sd[q] += (order[q] - (order[q] > 4 ? 1 : 0)) * d.bandCap;
+    }
   }
   if (tid == 0) {  // the tables the per-particle setup and the exact walk index by row
 #pragma unroll
@@ -329,7 +347,13 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   if (winOk && tid < 9 * FN_WIN) {
     const int r = tid / FN_WIN, i = tid % FN_WIN;
     const int shift = (r % 3 - 1) * d.gx + (r / 3 - 1) * d.gx * d.gy;
-    if (i <= nc) sh.win[r][i] = (int)cellStart[min(max(cLo - 1 + shift + i, 0), d.G)];
+    const int wc = min(max(cLo - 1 + shift + i, 0), d.G);
+    if (BANDS) {
+      const uint32_t* tbl = (r == 4) ? cellStart : bandStart + (size_t)(r - (r > 4 ? 1 : 0)) * ((size_t)d.G + 1);
+      if (i <= nc) { sh.win[r][i] = (int)tbl[wc]; sh.winTrue[r][i] = (int)cellStart[wc]; }
+    } else {
+      if (i <= nc) sh.win[r][i] = (int)cellStart[wc];
+    }
   }
   if (tid >= 192 && tid < 256) sh.binU[tid - 192] = binU[tid - 192];
   FN_STAMP(0)
@@ -346,7 +370,8 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
         int delta = sd[0];
 #pragma unroll
         for (int q = 0; q < 8; q++) delta = (f >= se[q]) ? sd[q + 1] : delta;  // runs are laid out in order of q
-        rec[u] = sortedPos[f + delta];
+        if (BANDS) rec[u] = (f >= se[0] ? bandPos : sortedPos)[f + delta];
+        else rec[u] = sortedPos[f + delta];
       }
 #pragma unroll
       for (int u = 0; u < PER; u++) {
@@ -369,6 +394,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   int pLo[4], pHi[4], absDelta[4];  // this lane's four pieces as LDS slot ranges; sorted index = LDS slot + absDelta
   int selfSlot = -1;
   int zLoMine = 0;  // lane B: first sorted index of cell 3, the z neighbour (base of the flagged 16-bit offsets)
+  int trueLo[4] = {0, 0, 0, 0}, trueHi[4] = {0, 0, 0, 0};  // BANDS: the four cells' ranges of sorted indices
   {  // the lane's four cells (sphFluid.cl:253-308) with the cell table read from the LDS window where possible
     const float px = me.x - d.xmin, py = me.y - d.ymin, pz = me.z - d.zmin;
     const float cfx = (float)(int)(me.x * d.cellSizeInv) * d.cellSize;
@@ -390,15 +416,24 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
       const int row = (stepY[i] ? ry : 1) + 3 * (stepZ[i] ? rz : 1);
       const int c = wrap_cell(raw, d.G);
       int lo, hi;
+      int tLo, tHi;  // BANDS: the cell's true range of sorted indices (lo, hi: its range in the row's band array)
       const bool staged = c == raw;  // wrapped cells are never staged: only their emptiness matters
+      const bool banded = BANDS && i != 0;  // (piece 0 lies in the own x-row in both lanes, the others never do)
       if (staged && winOk) {
         const int w = myCellNow - cLo + 1 + xs;  // in [0, nc): the batch's cells are cLo..cHi, the window starts at cLo-1
         lo = sh.win[row][w];
         hi = sh.win[row][w + 1];
+        tLo = lo; tHi = hi;
+        if (banded) { tLo = sh.winTrue[row][w]; tHi = sh.winTrue[row][w + 1]; }
       } else {  // wrapped cells and batches wider than the window
         const int cc = min(max(c, 0), d.G - 1);
-        lo = (int)cellStart[cc];
-        hi = (int)cellStart[cc + 1];
+        lo = tLo = (int)cellStart[cc];
+        hi = tHi = (int)cellStart[cc + 1];
+        if (banded && staged) {
+          const uint32_t* tbl = bandStart + (size_t)(row - (row > 4 ? 1 : 0)) * ((size_t)d.G + 1);
+          lo = (int)tbl[cc];
+          hi = (int)tbl[cc + 1];
+        }
       }
       const int n = hi - lo;
       int base = 0;
@@ -409,8 +444,29 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
       pLo[i] = base;
       pHi[i] = base + n;
       absDelta[i] = lo - base;
-      if (i == 2) zLoMine = lo;
+      if (banded) absDelta[i] += (row - (row > 4 ? 1 : 0)) * d.bandCap;  // record of the entry: bandPos[LDS slot + absDelta]
+      if (i == 2) zLoMine = tLo;
       if (i == 0 && laneB == 0) selfSlot = base + (idNow - lo);  // the particle itself sits in its own cell
+      if (BANDS) { trueLo[i] = tLo; trueHi[i] = tHi; }
+    }
+    if (BANDS) {
+      // the band argument needs a particle whose key is the id of the in-grid cell its coordinates truncate to (as a candidate
+      // needs it to be left out of a band, sph_bands.hip); any other takes the exact walk, which reads whole cells
+      const int cx = (int)(me.x * d.cellSizeInv), cy = (int)(me.y * d.cellSizeInv), cz = (int)(me.z * d.cellSizeInv);
+      const bool premise = me.x >= 0.f && me.y >= 0.f && me.z >= 0.f && me.x < 1.0e9f && me.y < 1.0e9f && me.z < 1.0e9f && cx < d.gx &&
+                           cy < d.gy && cz < d.gz && myCellNow == cx + cy * d.gx + cz * d.gx * d.gy;
+      if (!premise) slow = true;
+    }
+  }
+  int wideB = 0;  // BANDS: the row has no 16-bit copy (decided here, from the cells' true ranges; without bands: at the store)
+  if (BANDS) {
+    const int zOther = pair_other(zLoMine);  // (a DPP move: executed by both lanes of the particle)
+    const int zB = laneB ? zLoMine : zOther;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const bool zf = laneB ? (i == 2) : (i != 0);
+      const int rel = SPH_N16_BIAS - (zf ? zB : idNow);
+      if (trueHi[i] > trueLo[i] && (trueLo[i] + rel < 0 || trueHi[i] - 1 + rel > SPH_N16_MAX)) wideB = 1;
     }
   }
   {  // both lanes must agree. The DPP move is executed by BOTH lanes — under a short-circuit `||` a lane that is already slow
@@ -532,13 +588,28 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   // kept (two per register): the list area is about to be reused.
   const int total = segEnd[3];
   float d2v[FN_LIST_CAP];
-  uint32_t slotPk[FN_LIST_CAP / 2];
+  uint32_t slotPk[FN_LIST_CAP / 2];  // (not with BANDS)
+  int idxv[FN_LIST_CAP];  // BANDS only: the entries' sorted indices — own-row entries slot + delta, the others from their records
 #pragma unroll
   for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {
     if (__any(c0 < total)) {
       int slotv[FN_CHUNK];
 #pragma unroll
       for (int u = 0; u < FN_CHUNK; u++) slotv[u] = min((int)myList[c0 + u][lane], FN_CAND_CAP + FN_CAND_PAD - 1);
+      if (BANDS) {
+        // issued here, used at the store: the loads are in flight during the replay (a load under a branch, not a select, so that
+        // nothing waits for it here)
+#pragma unroll
+        for (int u = 0; u < FN_CHUNK; u++) {
+          const int e = c0 + u;
+          int dlt = absDelta[1];
+          dlt = (e >= segEnd[1]) ? absDelta[2] : dlt;
+          dlt = (e >= segEnd[2]) ? absDelta[3] : dlt;
+          int v = slotv[u] + absDelta[0];
+          if (e >= segEnd[0] && e < total) v = __float_as_int(bandPos[slotv[u] + dlt].w);
+          idxv[e] = v;
+        }
+      }
 #pragma unroll
       for (int u = 0; u < FN_CHUNK; u++) {
         const int sl = slotv[u];
@@ -546,13 +617,20 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
         const float v = ex * ex + ey * ey + ez * ez;
         d2v[c0 + u] = (c0 + u < total) ? v : __builtin_inff();  // +inf never passes a `<` / `<=` test below
       }
+      if (!BANDS) {
 #pragma unroll
-      for (int u = 0; u < FN_CHUNK; u += 2) slotPk[(c0 + u) >> 1] = (uint32_t)slotv[u] | ((uint32_t)slotv[u + 1] << 16);
+        for (int u = 0; u < FN_CHUNK; u += 2) slotPk[(c0 + u) >> 1] = (uint32_t)slotv[u] | ((uint32_t)slotv[u + 1] << 16);
+      }
     } else {
 #pragma unroll
       for (int u = 0; u < FN_CHUNK; u++) d2v[c0 + u] = __builtin_inff();
+      if (BANDS) {
 #pragma unroll
-      for (int u = 0; u < FN_CHUNK; u += 2) slotPk[(c0 + u) >> 1] = 0u;
+        for (int u = 0; u < FN_CHUNK; u++) idxv[c0 + u] = 0;
+      } else {
+#pragma unroll
+        for (int u = 0; u < FN_CHUNK; u += 2) slotPk[(c0 + u) >> 1] = 0u;
+      }
     }
   }
   FN_STAMP(6)
@@ -634,6 +712,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
       rel16[i] = absDelta[i] - (zf ? zBase : idNow) + SPH_N16_BIAS;
       if (pHi[i] > pLo[i] && (pLo[i] + rel16[i] < 0 || pHi[i] - 1 + rel16[i] > SPH_N16_MAX)) wide = 1;
     }
+    if (BANDS) wide = wideB;  // (the pieces of band rows are not their cells: decided from the cells' true ranges at the setup)
     // (per entry below: the offset from the particle itself if that fits, else the flagged one — which fits where the checks above
     // passed; the reader only follows the flag, so no per-piece bookkeeping is needed)
     int own16 = SPH_N16_BIAS - idNow, far16 = SPH_N16_BIAS + 0x8000 - zBase;
@@ -664,7 +743,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
           const int pos = curStart + rank;
           rank++;
           if (pos < SPH_MAXN) {
-            const int jn = (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
+            const int jn = BANDS ? idxv[e] : (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
             const int o16 = jn + own16;
             idRow[pos] = (uint16_t)((uint32_t)o16 <= (uint32_t)SPH_N16_MAX ? o16 : jn + far16);
             dstRow[pos] = d2v[e];
@@ -688,7 +767,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
           const int pos = curStart + rank;
           rank++;
           if (pos < SPH_MAXN) {
-            const int jn = (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
+            const int jn = BANDS ? idxv[e] : (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
             if (wide) nbrId[mapBase + (uint32_t)(((pos >> 2) << 8) + (pos & 3))] = jn;  // tiled map: group stride 64 lanes * 4 slots
           }
         }
@@ -730,7 +809,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     while (todo != 0ull) {
       const int b = __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
-      fn_exact_walk(d, g, sh, p0 + wave * FN_PER_WAVE + (b >> 1), wave, lane);
+      fn_exact_walk<BANDS>(d, g, sh, p0 + wave * FN_PER_WAVE + (b >> 1), wave, lane);
     }
   }
   FN_STAMP(9)
@@ -750,8 +829,9 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
 #endif
 }
 
-int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hipStream_t stream) {
+int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hipStream_t stream, bool bands) {
   if (idxLo < 0 || idxLo % SPH_BLOCK != 0) { sph_set_error("sphk_find_neighbors: idxLo %d is not a multiple of %d", idxLo, SPH_BLOCK); return SPH_ERR_INVALID; }
+  if (bands && !s->bandBuf.p) { sph_set_error("sphk_find_neighbors: no search bands were built"); return SPH_ERR_ORDER; }
   idxHi = min(idxHi, s->d.N);
   if (idxHi <= idxLo) return SPH_OK;  // an empty range: no launch
   {  // opt in to > 64 KB of dynamic LDS once per DEVICE (the attribute lives on the device's function object)
@@ -760,7 +840,8 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hip
     std::lock_guard<std::mutex> lock(mu);
     const int dev = s->cfg.device;
     if (dev < 0 || dev >= 64 || !attrSet[dev]) {
-      SPH_HIP(hipFuncSetAttribute((const void*)k_find_neighbors, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FnShared)));
+      SPH_HIP(hipFuncSetAttribute((const void*)k_find_neighbors<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FnShared)));
+      SPH_HIP(hipFuncSetAttribute((const void*)k_find_neighbors<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FnShared)));
       if (dev >= 0 && dev < 64) attrSet[dev] = true;
     }
   }
@@ -768,12 +849,16 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hip
   FnParams a;
   a.G = r.G; a.gx = r.gx; a.gy = r.gy; a.rangeLo = r.rangeLo; a.rangeHi = r.rangeHi;
   a.idxLo = idxLo; a.idxHi = idxHi;
+  a.gz = r.gz; a.bandCap = s->capacity;
   a.h = r.h; a.cellSize = r.cellSize; a.cellSizeInv = r.cellSizeInv; a.simScale = r.simScale;
   a.xmin = r.xmin; a.ymin = r.ymin; a.zmin = r.zmin;
-  hipLaunchKernelGGL(k_find_neighbors, dim3(sph_blocks(idxHi - idxLo, FN_PART)), dim3(FN_THREADS), sizeof(FnShared), stream ? stream : s->stream, a,
+  SphBands b = {};
+  if (bands) sphk_bands_bytes(s, &b);
+  hipLaunchKernelGGL(bands ? k_find_neighbors<true> : k_find_neighbors<false>, dim3(sph_blocks(idxHi - idxLo, FN_PART)), dim3(FN_THREADS),
+                     sizeof(FnShared), stream ? stream : s->stream, a,
                      (const float4*)r.sortedPos, (const uint32_t*)r.keys, (const uint32_t*)r.cellStart, r.binU, r.nbrId, r.nbrDist, r.nbr16,
                      r.nbrBase, r.dbg,
-                     r.valsAlt /* idle between the sort and the next step's sort */);
+                     r.valsAlt /* idle between the sort and the next step's sort */, (const float4*)b.pos, (const uint32_t*)b.start);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }

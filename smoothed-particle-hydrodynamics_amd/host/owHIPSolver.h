@@ -80,6 +80,8 @@ class owHIPSolver {
   void read_particleIndex_buffer(unsigned int* particleIndexBuffer) {
     check(sph_read_particle_index(s_, particleIndexBuffer), "read_particleIndex_buffer");
   }
+  // beyond the reference: the search bands of the fused step (sph_set_search_bands): 0 automatic, 1 off; results do not depend on it
+  void setSearchBands(int mode) { check(sph_set_search_bands(s_, mode), "setSearchBands"); }
 
   // beyond the reference: SPH interpolation over the sorted state of the last completed step (include/sphmi.h, sph_sample_*);
   // out holds count x SPH_SAMPLE_WORDS / dims[2] x dims[1] x dims[0] x SPH_SAMPLE_WORDS floats. typeMask bits: 1 liquid, 2 elastic, 3 boundary

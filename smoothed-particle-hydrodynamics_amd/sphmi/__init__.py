@@ -52,7 +52,7 @@ MAX_NEIGHBOR_COUNT = 32
 LIQUID_PARTICLE, ELASTIC_PARTICLE, BOUNDARY_PARTICLE = 1, 2, 3
 
 STAGE_NAMES = ["hash", "sort", "sort_post", "index", "find_neighbors", "density", "forces", "elastic",
-               "predict_density", "pressure_force", "integrate", "membranes"]
+               "predict_density", "pressure_force", "integrate", "membranes", "bands"]
 
 
 class SphConfig(C.Structure):
@@ -172,7 +172,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_position", "sph_read_velocity", "sph_read_density", "sph_read_particle_index",
                     "sph_read_position_async", "sph_read_position_wait", "sph_host_unregister", "sph_build_info",
                     "sph_read_buffer", "sph_read_neighbor_rows", "sph_synchronize", "sph_set_stage_timing", "sph_get_stage_times",
-                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_set_step_pipeline", "sph_set_wave_skip", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
+                    "sph_reset_stage_times", "sph_step_sort_passes", "sph_set_step_chunks", "sph_set_step_pipeline", "sph_set_wave_skip", "sph_set_search_bands", "sph_last_error", "sph_abi_version", "sph_slab_init", "sph_slab_pack", "sph_slab_pack_framed", "sph_slab_step_begin", "sph_slab_step_messages",
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
@@ -252,6 +252,8 @@ def device_lib():
             L.sph_set_step_pipeline.argtypes = [C.c_void_p, C.c_int32]
         if hasattr(L, "sph_set_wave_skip"):  # (optional, likewise)
             L.sph_set_wave_skip.argtypes = [C.c_void_p, C.c_int32]
+        if hasattr(L, "sph_set_search_bands"):  # (optional, likewise)
+            L.sph_set_search_bands.argtypes = [C.c_void_p, C.c_int32]
         L.sph_get_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
         L.sph_last_error.restype = C.c_char_p
         L.sph_slab_init.argtypes = [C.c_void_p, C.POINTER(SphSlab), C.c_void_p]
@@ -553,7 +555,8 @@ _BUF_DTYPE = {"position": np.float32, "velocity": np.float32, "sortedPosition": 
               "gridCellIndex": np.uint32, "gridCellIndexFixedUp": np.uint32, "pressure": np.float32,
               "rho": np.float32, "debugCounters": np.uint32, "diagnosticTrace": np.uint32,
               "pressureForceSkipped": np.uint8, "predictDensitySkipped": np.uint8,
-              "pressureNeighbourhood": np.uint8, "movedNeighbourhood": np.uint8, "pressureFlags": np.uint8, "movedFlags": np.uint8}
+              "pressureNeighbourhood": np.uint8, "movedNeighbourhood": np.uint8, "pressureFlags": np.uint8, "movedFlags": np.uint8,
+              "searchBandFlags": np.uint8, "searchBands": np.float32, "searchBandStart": np.uint32}
 
 
 def type_mask(types):
@@ -1432,6 +1435,13 @@ class owHIPSolver:
             raise SphError("this libsphmi has no sph_set_wave_skip")
         return self._chk(self._L.sph_set_wave_skip(self._h, int(mode)))
 
+    def set_search_bands(self, mode=0):
+        """The search bands of step(): 0 automatic (used wherever they are provably a superset of the neighbours), 1 off.
+        Results do not depend on it."""
+        if not hasattr(self._L, "sph_set_search_bands"):
+            raise SphError("this libsphmi has no sph_set_search_bands")
+        return self._chk(self._L.sph_set_search_bands(self._h, int(mode)))
+
     def reset_stage_times(self):
         return self._chk(self._L.sph_reset_stage_times(self._h))
 
@@ -1444,6 +1454,8 @@ class owHIPSolver:
 
     def stage_times(self):
         n = len(STAGE_NAMES)
+        if not hasattr(self._L, "sph_set_search_bands"):  # (an A/B library built from an older csrc/: no band stage)
+            n -= 1
         ms = (C.c_double * n)()
         cnt = (C.c_int64 * n)()
         self._chk(self._L.sph_get_stage_times(self._h, ms, cnt, n))
