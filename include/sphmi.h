@@ -154,7 +154,9 @@ int sph_read_neighbor_rows(sph_solver* s, int32_t first, int32_t count, int32_t*
  * hs2 = (h*simScale)^2 as the step computes it), w = a*a*a, v_j = w * (1.0f/rho_j); W += w, S += v_j, U += v_j*vel_j.xyz,
  * P += v_j*p_j as sequential float sums. Record (SPH_SAMPLE_WORDS floats):
  *   { rho = (float)massWpoly6 * W, shepard = (float)massWpoly6 * S, vx, vy, vz = U/S, p = P/S, n = count, 0 }
- * with zeros in place of the quotients when S == 0; a non-finite query point gives an all-zero record.
+ * with zeros in place of the quotients when S == 0; a non-finite query point gives an all-zero record. The sums start at +0, and
+ * f32 denormals are kept: in the last ulps of r2 below h*h the weight w underflows to +0 or -0 (a may be negative there), such
+ * a particle counts in n and leaves +0 in every sum; farther in, W and S are subnormal numbers, and S may be 0 while W is not.
  * Allowed once the density and pressure-force stages of a step have run (sph_step or the sph_run_* path), SPH_ERR_ORDER before;
  * SPH_ERR_INVALID for a slab solver, a typeMask of 0 or with bits outside 1..3, dims <= 0, count < 0, or null pointers
  * (count == 0 is a no-op). Blocking, on the solver's stream; device scratch is grown on demand (bounded: large grids go in
