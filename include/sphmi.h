@@ -969,6 +969,88 @@ int sph_body_set_dynamics(sph_solver* s, int32_t slot, const sph_body_dynamics* 
 int sph_body_get_dynamics(sph_solver* s, int32_t slot, sph_body_dynamics* out, int32_t* isDynamic); /* blocking */
 int sph_bodies_advance(sph_solver* s, double* out /* host, SPH_MAX_BODIES x SPH_BODY_STATE_WORDS, or NULL */);
 
+/* ---- Flow gauges: particle crossings of oriented gates (no reference counterpart) -------------------------------
+ * A gauge counts the particles that went through an oriented parallelogram (or plane) in the last completed step, and sums what
+ * they carried. Up to SPH_MAX_GAUGES gauges per solver, all served by one pass over the particles. No step kernel knows of them;
+ * every call below is read-only on every solver array and leaves mesh, labelling, selection, render, edit map, fields, tracers and
+ * body state valid.
+ * THE GAUGE is the set origin + alpha*u + beta*v with 0 <= alpha < 1 and 0 <= beta < 1: half-open, so gauges that tile a section
+ * count a particle once. With SPH_GAUGE_PLANE in flags it is the whole plane through origin spanned by u and v. The positive
+ * direction is n = u x v. sph_gauge_define derives, in double from the floats, one operation at a time, no contraction:
+ *     n = u x v, written n.x = u.y*v.z - u.z*v.y, n.y = u.z*v.x - u.x*v.z, n.z = u.x*v.y - u.y*v.x
+ *     nn = (n.x*n.x + n.y*n.y) + n.z*n.z        A = (v x n) / nn        B = (n x u) / nn      (the cross products written as n is)
+ * so that A.u = 1, A.v = 0, B.v = 1, B.u = 0 up to rounding. It is SPH_ERR_INVALID for a word of origin, u or v that is not finite,
+ * for nn == 0 or not finite, for a typeMask of 0 or with a bit outside 1..2, for a fieldSlot that is neither -1 nor an existing
+ * slot of the carried fields, for flags other than 0 and SPH_GAUGE_PLANE, for a slot outside 0..SPH_MAX_GAUGES-1 and for a slab
+ * solver; the slot then keeps what it held. g == NULL releases the slot. Boundary particles are never counted: a pose or
+ * sph_bodies_advance rewrites their current position after the step. sph_gauge_get returns the definition (*defined = 0 and `out`
+ * untouched for a free slot). Definitions live on the host; a definition, a redefinition and a release clear the slot's totals.
+ * THE STATE is that of a completed step: a_i = sortedPosition[i], where sorted particle i was when the step began, and with
+ * id = particleIndex[i] its original id, b_i = position[id] and w_i = velocity[id], where the step's integration (with elastic
+ * matter, the membranes' finalize pass) left it, and c_i = field[id] of the gauge's carried field (+0.0 with fieldSlot -1), all
+ * widened to double. Sorted particle i is CONSIDERED by a gauge when (int)a_i.w is 1 or 2 with that bit in typeMask.
+ *     s(p) = (n.x*(p.x - o.x) + n.y*(p.y - o.y)) + n.z*(p.z - o.z)
+ *     a positive crossing: s(a) < 0 && s(b) >= 0        a negative crossing: s(a) >= 0 && s(b) < 0       (a NaN crosses nothing)
+ *     t = s(a) / (s(a) - s(b));   x = a + t*(b - a) per component;
+ *     alpha = (A.x*(x.x - o.x) + A.y*(x.y - o.y)) + A.z*(x.z - o.z),  beta likewise with B
+ * The crossing is COUNTED if the gauge is a plane or 0 <= alpha && alpha < 1 && 0 <= beta && beta < 1. All in double, one
+ * operation at a time in the written order, no contraction, IEEE division. A particle on the plane counts as on its non-negative
+ * side, so the net count of a plane over K steps equals, exactly, the change of the number of considered particles with s >= 0.
+ * RECORD, SPH_GAUGE_WORDS doubles per gauge and call. A counted crossing contributes the terms
+ *     1, w.x, w.y, w.z, (w.x*w.x + w.y*w.y) + w.z*w.z, c, alpha, beta
+ * to words 0..7 if it is positive and to words 8..15 if it is negative; every other particle contributes +0.0. Each of the 16
+ * words is reduce() of sph_diagnostics over all N terms in ascending sorted index. The sign of a zero total is not part of the
+ * contract. The record of a free slot is all +0.0. No floating-point atomics anywhere.
+ * sph_gauges_accumulate computes the record of every defined gauge, adds it to the gauge's totals on the device and appends it to
+ * the history. With out == NULL everything is enqueued on the solver's stream and the call returns without a host wait; with
+ * `out` it waits once and copies SPH_MAX_GAUGES records. Every successful call has an INDEX, counted from 0 per solver and never
+ * reset. Calling it twice after one step counts that step twice; that is not detected.
+ * TOTALS, SPH_GAUGE_TOTAL_WORDS doubles per gauge, on the device:  0..15 total = total + record, once per call
+ *   16 calls accumulated since the slot's totals were cleared     17 index of the first call with a positive crossing, -1 if none
+ *   18 index of the first call with a negative crossing, -1 if none      19 index of the last call with any crossing, -1 if none
+ * Totals survive steps, edits and pose changes. sph_gauges_reset (slot, or -1: all), a definition and a release clear a slot's
+ * totals (words 0..16 to +0.0, 17..19 to -1). sph_gauges_read (blocking) copies the totals; *calls (may be NULL) receives the
+ * number of calls so far, which is the index of the next one.
+ * HISTORY. sph_gauges_history(rows) gives the solver a device ring of `rows` rows of SPH_MAX_GAUGES records (rows == 0 releases
+ * it; rows outside 0..SPH_GAUGE_HISTORY_MAX is SPH_ERR_INVALID; a new ring starts empty). Every accumulate writes its row, index %
+ * rows, without a host wait. sph_gauges_read_history (blocking) copies the records of calls firstCall .. firstCall + count - 1,
+ * count x SPH_MAX_GAUGES x SPH_GAUGE_WORDS doubles, and *callsWritten (may be NULL) the number of calls so far. It is
+ * SPH_ERR_INVALID unless every asked call was made since the ring was set up and is among the last `rows`, and SPH_ERR_ORDER
+ * without a ring.
+ * CROSSING LIST. sph_gauge_crossings (blocking) finds the counted crossings of ONE gauge on the same state and writes their number
+ * to *count; sph_read_gauge_crossings copies them out (any pointer may be NULL), in ascending sorted index: the sorted index, the
+ * original id, the direction (+1, -1) and t, alpha, beta narrowed to float once. It touches neither totals nor history. The list
+ * is a derived result: reading it is SPH_ERR_ORDER without one and after anything that changes the state (a stage, a step, an
+ * edit). sph_remove_ids and sph_field_write can act on its ids.
+ * ORDER. sph_gauges_accumulate and sph_gauge_crossings are SPH_ERR_ORDER unless the integrate stage of the last step has run,
+ * while a stage-by-stage step is half done (with elastic matter the positions are final only after the membranes' finalize stage),
+ * after an edit until the next step (removed and added particles are not crossings), with no gauge defined (the crossing list:
+ * with `slot` free), and when a gauge's carried field has been released. SPH_ERR_INVALID for a slab solver, a slot out of range
+ * and null pointers where none is allowed.
+ * SCOPE. Flat gauges only. A particle that crosses and returns within one step is not seen. The path between a and b is taken as
+ * straight. Device memory, grown on demand: 2 bytes per particle for the tree, 5 KB of totals and records, 2 KB per history row,
+ * and for the crossing list the scan's scratch plus 24 bytes per crossing. */
+#define SPH_MAX_GAUGES 16
+#define SPH_GAUGE_WORDS 16
+#define SPH_GAUGE_TOTAL_WORDS 20
+#define SPH_GAUGE_HISTORY_MAX 16384
+#define SPH_GAUGE_PLANE 1u
+typedef struct sph_gauge {
+  float origin[3], u[3], v[3];
+  uint32_t typeMask; /* bits 1..2: liquid, elastic */
+  int32_t fieldSlot; /* a carried field, or -1 */
+  uint32_t flags;    /* 0 or SPH_GAUGE_PLANE */
+} sph_gauge;
+int sph_gauge_define(sph_solver* s, int32_t slot, const sph_gauge* g /* NULL releases the slot */);
+int sph_gauge_get(sph_solver* s, int32_t slot, sph_gauge* out, int32_t* defined);
+int sph_gauges_accumulate(sph_solver* s, double* out /* host, SPH_MAX_GAUGES x SPH_GAUGE_WORDS, or NULL: no host wait */);
+int sph_gauges_read(sph_solver* s, double* totals /* host, SPH_MAX_GAUGES x SPH_GAUGE_TOTAL_WORDS */, int64_t* calls); /* blocking */
+int sph_gauges_reset(sph_solver* s, int32_t slot /* -1: all */);
+int sph_gauges_history(sph_solver* s, int32_t rows /* 0 releases; at most SPH_GAUGE_HISTORY_MAX */);
+int sph_gauges_read_history(sph_solver* s, int64_t firstCall, int32_t count, double* out, int64_t* callsWritten); /* blocking */
+int sph_gauge_crossings(sph_solver* s, int32_t slot, int64_t* count); /* blocking */
+int sph_read_gauge_crossings(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, int32_t* direction, float* tab3 /* t, alpha, beta */);
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -276,6 +276,18 @@ struct sph_solver {
   // byte per sorted particle), then the load tree's partials. Both grown on demand.
   bool bodyDynamic[SPH_MAX_BODIES] = {};
   SphScratch bodyDynBuf, bodyDynScratch;
+  // flow gauges (sph_gauge_* / sph_gauges_*, sph_gauge.hip): the definitions live here, on the host, and travel to the
+  // kernels by value; gaugeBuf: one GaugeDev (totals and the last records); gaugeTree: the partials of every tree level;
+  // gaugeHist: the history ring of gaugeHistRows rows, written for the calls from gaugeHistFirst on; gaugeScan / gaugeList: the
+  // crossing list's scan scratch and the list itself (sorted index, original id, direction, t alpha beta). All grown on demand.
+  sph_gauge gaugeDef[SPH_MAX_GAUGES] = {};
+  bool gaugeLive[SPH_MAX_GAUGES] = {};
+  int64_t gaugeCalls = 0;             // successful sph_gauges_accumulate calls so far: the index of the next one
+  int gaugeHistRows = 0;
+  int64_t gaugeHistFirst = 0;
+  SphScratch gaugeBuf, gaugeTree, gaugeHist, gaugeScan, gaugeList;
+  SphDerived gaugeCross;              // the last successful sph_gauge_crossings
+  int64_t gaugeCrossCount = 0;        // ... its length
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -568,6 +580,29 @@ size_t sphk_bdyn_scratch_bytes(int N);  // the map and every tree level's partia
 int sphk_bdyn_overlap(sph_solver* s, const BodyDynSet& set, int slot, unsigned long long* seen, BodyDynDev* D);
 // one advance of every body of set.dynMask, enqueued on s->stream: map, fused load, tree, integrate, validate, commit, finish
 int sphk_bdyn_advance(sph_solver* s, const BodyDynSet& set, const BodyPose& box, void* scratch, BodyDynDev* D);
+// sph_gauge.hip (flow gauges: crossings of oriented gates between the sorted state and the current one; read-only on
+// every solver array)
+struct GaugeOne {  // what sph_gauge_define derived, in double (include/sphmi.h)
+  double o[3], n[3], A[3], B[3];
+  const float* field;  // the gauge's carried field in original-id order, or null
+  uint32_t typeMask, plane;
+};
+struct GaugeSet {  // the gauges of a launch, by value: the kernels read them through scalar loads
+  uint32_t defMask;  // bit g: slot g is defined
+  GaugeOne g[SPH_MAX_GAUGES];
+};
+struct GaugeDev {  // everything of the feature that lives on the device besides tree, ring and list; one allocation
+  double totals[SPH_MAX_GAUGES][SPH_GAUGE_TOTAL_WORDS];
+  double record[SPH_MAX_GAUGES][SPH_GAUGE_WORDS];
+};
+size_t sphk_gauge_tree_bytes(int N);  // the partials of every tree level
+int sphk_gauge_clear(sph_solver* s, GaugeDev* D, uint32_t slots);  // the totals of the slots in the mask: words 0..16 +0.0, 17..19 -1
+// record, totals and history row of call `call`, enqueued on s->stream; hist: the ring of `rows` rows, or null
+int sphk_gauges_accumulate(sph_solver* s, const GaugeSet& set, double* tree, GaugeDev* D, double* hist, int rows, int64_t call);
+// the counted crossings of gauge g into the selection scan's layout at `scratch` (mask, block counts, scan): *totals = 2 device words
+int sphk_gauge_mark(sph_solver* s, const GaugeOne& g, void* scratch, uint32_t** totals);
+// after sphk_gauge_mark and sphk_select_scatter: original id, direction and (t, alpha, beta) of list[0..n)
+int sphk_gauge_list(sph_solver* s, const GaugeOne& g, const int32_t* list, int n, uint32_t* origId, int32_t* direction, float* tab3);
 // sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
 // values in original-id order (device). Read-only on every solver array.
 size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word

@@ -274,6 +274,40 @@ class owHIPSolver {
     check(sph_wall_diagnostics(s_, slot, regions6, count, typeMask, out), "wallDiagnostics");
   }
 
+  // beyond the reference: flow gauges. Up to SPH_MAX_GAUGES oriented parallelograms (or planes); after a completed step
+  // gaugesAccumulate counts the particles that went through each and sums what they carried, adds the record to the totals on the
+  // device and appends it to the history ring (out == null: no host wait; otherwise SPH_MAX_GAUGES x SPH_GAUGE_WORDS doubles).
+  // gaugeDefine with null releases a slot; gaugesRead returns the totals (SPH_MAX_GAUGES x SPH_GAUGE_TOTAL_WORDS) and the number of
+  // calls so far; gaugeCrossings lists the crossings of one gauge and returns their number, readGaugeCrossings copies the list (any
+  // pointer may be null) (include/sphmi.h, sph_gauge_define / sph_gauges_accumulate)
+  void gaugeDefine(int slot, const sph_gauge* g) { check(sph_gauge_define(s_, slot, g), "gaugeDefine"); }
+  bool gaugeGet(int slot, sph_gauge* out) {
+    int32_t defined = 0;
+    check(sph_gauge_get(s_, slot, out, &defined), "gaugeGet");
+    return defined != 0;
+  }
+  void gaugesAccumulate(double* out = nullptr) { check(sph_gauges_accumulate(s_, out), "gaugesAccumulate"); }
+  int64_t gaugesRead(double* totals) {
+    int64_t calls = 0;
+    check(sph_gauges_read(s_, totals, &calls), "gaugesRead");
+    return calls;
+  }
+  void gaugesReset(int slot = -1) { check(sph_gauges_reset(s_, slot), "gaugesReset"); }
+  void gaugesHistory(int rows) { check(sph_gauges_history(s_, rows), "gaugesHistory"); }
+  int64_t gaugesReadHistory(int64_t firstCall, int count, double* out) {
+    int64_t calls = 0;
+    check(sph_gauges_read_history(s_, firstCall, count, out, &calls), "gaugesReadHistory");
+    return calls;
+  }
+  int64_t gaugeCrossings(int slot) {
+    int64_t n = 0;
+    check(sph_gauge_crossings(s_, slot, &n), "gaugeCrossings");
+    return n;
+  }
+  void readGaugeCrossings(int32_t* sortedIndex, uint32_t* origId, int32_t* direction, float* tab3) {
+    check(sph_read_gauge_crossings(s_, sortedIndex, origId, direction, tab3), "readGaugeCrossings");
+  }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

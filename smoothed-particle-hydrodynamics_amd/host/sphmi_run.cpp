@@ -91,6 +91,14 @@
 //        `_wall: step S body B (members M): contact n C shared H reflected R  contact force X Y Z N  stage force X Y Z N  load on
 //        body X Y Z N  torque on body X Y Z` -- the numbers of frames.wall_summary (%.9e): cfg.mass / timeStep times the summed
 //        velocity change of the contact inside integrate, cfg.mass times the body's K7 / K12 terms, and minus their sum.
+//   ... --gauge "OX OY OZ UX UY UZ VX VY VZ" [--gauge-plane] [--gauge-field SLOT] ... --gauge-every K
+//        flow gauges (sph_gauge_* / sph_gauges_*): every --gauge (one argument of nine numbers, scene units) defines
+//        the next slot as the parallelogram origin + alpha U + beta V over the liquid, positive along U x V; --gauge-plane behind it
+//        makes it the whole plane, --gauge-field SLOT sums carried field SLOT (0 with --dye-region) over its crossings. After every
+//        step the crossings are accumulated on the device without a wait; after every K-th step one line per gauge G is printed from
+//        the totals: `_gauge: step S gauge G plus P minus M net N calls C first F last L  mean velocity plus X Y Z minus X Y Z
+//        field plus A minus B` (counts %.0f; F: the first call, counted from 0, with a crossing in either direction, -1: none yet;
+//        mean velocities and field sums %.9e, the velocity sums over the counts, 0 without a crossing)
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -264,6 +272,7 @@ int main(int argc, char** argv) {
   int elaEvery = 0; bool elaSeen = false; const char* elaDir = nullptr;
   int forEvery = 0; bool forSeen = false;
   int wallEvery = 0; bool wallSeen = false;
+  std::vector<sph_gauge> gaugeDefs; int gaugeEvery = 0; bool gaugeSeen = false, gaugeOk = true;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -337,6 +346,19 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--elastic-out") && i + 1 < argc) { elaDir = argv[++i]; elaSeen = true; }
     else if (!strcmp(argv[i], "--forces-every") && i + 1 < argc) { forEvery = atoi(argv[++i]); forSeen = true; }
     else if (!strcmp(argv[i], "--wall-load-every") && i + 1 < argc) { wallEvery = atoi(argv[++i]); wallSeen = true; }
+    else if (!strcmp(argv[i], "--gauge") && i + 1 < argc) {
+      sph_gauge g = {};
+      float w[9];
+      int used = 0;
+      gaugeOk = gaugeOk && sscanf(argv[++i], "%f %f %f %f %f %f %f %f %f %n", &w[0], &w[1], &w[2], &w[3], &w[4], &w[5], &w[6], &w[7], &w[8], &used) == 9 &&
+                argv[i][used] == 0 && gaugeDefs.size() < SPH_MAX_GAUGES;
+      for (int k = 0; k < 3; k++) { g.origin[k] = w[k]; g.u[k] = w[3 + k]; g.v[k] = w[6 + k]; }
+      g.typeMask = 1u << SPH_LIQUID_PARTICLE; g.fieldSlot = -1;
+      gaugeDefs.push_back(g); gaugeSeen = true;
+    }
+    else if (!strcmp(argv[i], "--gauge-plane")) { if (gaugeDefs.empty()) gaugeOk = false; else gaugeDefs.back().flags |= SPH_GAUGE_PLANE; gaugeSeen = true; }
+    else if (!strcmp(argv[i], "--gauge-field") && i + 1 < argc) { if (gaugeDefs.empty()) { gaugeOk = false; ++i; } else gaugeDefs.back().fieldSlot = atoi(argv[++i]); gaugeSeen = true; }
+    else if (!strcmp(argv[i], "--gauge-every") && i + 1 < argc) { gaugeEvery = atoi(argv[++i]); gaugeSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -475,6 +497,11 @@ int main(int argc, char** argv) {
   if (forSeen && forEvery <= 0) { fprintf(stderr, "--forces-every K needs K > 0\n"); return 2; }
   const bool measuringForces = forSeen;
   if (wallSeen && wallEvery <= 0) { fprintf(stderr, "--wall-load-every K needs K > 0\n"); return 2; }
+  if (gaugeSeen && (!gaugeOk || gaugeDefs.empty() || gaugeEvery <= 0)) {
+    fprintf(stderr, "--gauge \"OX OY OZ UX UY UZ VX VY VZ\" (nine numbers in one argument, at most %d gauges) and --gauge-every K (> 0) go "
+                    "together; --gauge-plane and --gauge-field SLOT follow the gauge they belong to\n", SPH_MAX_GAUGES);
+    return 2;
+  }
   if (renSeen && (renEvery <= 0 || !renDir)) {
     fprintf(stderr, "--render-every K (> 0) and --render-out DIR go together (the other --render options need both)\n");
     return 2;
@@ -685,6 +712,7 @@ int main(int argc, char** argv) {
       ocl_solver->fieldCreate(0, nullptr, dyeInflow);
       if (dyeRegionSeen) ocl_solver->fieldSetRegion(0, 1.0f, dyeRegion, dyeMask);
     }
+    for (size_t g = 0; g < gaugeDefs.size(); g++) ocl_solver->gaugeDefine((int)g, &gaugeDefs[g]);  // (behind the dye: a gauge may sum field 0)
     int64_t bodyMembers = 0;
     if (moving) {
       bodyMembers = ocl_solver->bodyDefineRegion(0, bodyRegion);
@@ -995,6 +1023,23 @@ int main(int argc, char** argv) {
                  torque[0], torque[1], torque[2]);
         }
         helper.report("_wall: \t\t\t%9.3f ms\n");
+      }
+      if (gaugeSeen) {  // in front of the free body's advance, like every reader of the step just done
+        ocl_solver->gaugesAccumulate(nullptr);
+        if ((iterationCount + 1) % gaugeEvery == 0) {
+          double tot[SPH_MAX_GAUGES * SPH_GAUGE_TOTAL_WORDS];
+          ocl_solver->gaugesRead(tot);
+          for (size_t g = 0; g < gaugeDefs.size(); g++) {
+            const double* r = tot + g * SPH_GAUGE_TOTAL_WORDS;
+            const double first = r[17] < 0 ? r[18] : r[18] < 0 ? r[17] : std::min(r[17], r[18]);
+            double mp[3], mm[3];
+            for (int a = 0; a < 3; a++) { mp[a] = r[0] > 0 ? r[1 + a] / r[0] : 0.0; mm[a] = r[8] > 0 ? r[9 + a] / r[8] : 0.0; }
+            printf("_gauge: step %d gauge %d plus %.0f minus %.0f net %.0f calls %.0f first %.0f last %.0f  mean velocity plus %.9e %.9e %.9e "
+                   "minus %.9e %.9e %.9e  field plus %.9e minus %.9e\n", iterationCount + 1, (int)g, r[0], r[8], r[0] - r[8], r[16], first, r[19],
+                   mp[0], mp[1], mp[2], mm[0], mm[1], mm[2], r[5], r[13]);
+          }
+        }
+        helper.report("_gauge: \t\t%9.3f ms\n");
       }
       if (bodyFree && ocl_solver->bodyCount(0) > 0) {  // the load of the step just done moves the body (a drain may have taken it)
         std::vector<double> rec((size_t)SPH_MAX_BODIES * SPH_BODY_STATE_WORDS);

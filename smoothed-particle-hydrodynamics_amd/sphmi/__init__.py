@@ -34,6 +34,11 @@ FORCE_DIAG_WORDS = 64  # sph_force_diagnostics record (frames.FORCE_DIAG_FIELDS)
 WALL_WORDS = 32  # sph_wall_measure record (frames.WALL_FIELDS)
 WALL_DIAG_WORDS = 32  # sph_wall_diagnostics record (frames.WALL_DIAG_FIELDS)
 BODY_STATE_WORDS = 48  # sph_bodies_advance record per slot (BODY_STATE_FIELDS)
+MAX_GAUGES = 16  # SPH_MAX_GAUGES: flow-gauge slots per solver
+GAUGE_WORDS = 16  # sph_gauges_accumulate record per gauge (frames.GAUGE_FIELDS)
+GAUGE_TOTAL_WORDS = 20  # sph_gauges_read totals per gauge (frames.GAUGE_TOTAL_FIELDS)
+GAUGE_HISTORY_MAX = 16384
+GAUGE_PLANE = 1  # sph_gauge.flags
 # word ranges of that record (include/sphmi.h): name -> (first word, count)
 BODY_STATE_FIELDS = {"status": (0, 1), "members": (1, 1), "advances": (2, 1), "max_move": (3, 1), "position": (4, 3),
                      "orientation": (7, 4), "velocity": (11, 3), "angular_momentum": (14, 3), "omega": (17, 3), "load_force": (20, 3),
@@ -117,6 +122,11 @@ class SphBodyDynamics(C.Structure):
                 ("contactGain", C.c_double), ("forceGain", C.c_double), ("locks", C.c_uint32)]
 
 
+class SphGauge(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("typeMask", C.c_uint32),
+                ("fieldSlot", C.c_int32), ("flags", C.c_uint32)]
+
+
 class SphError(RuntimeError):
     pass
 
@@ -185,7 +195,9 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_field_diffuse", "sph_field_diagnostics", "sph_trace_streamlines", "sph_tracers_set", "sph_tracers_advect",
                     "sph_tracers_read", "sph_body_define_ids", "sph_body_define_region", "sph_body_release", "sph_body_count",
                     "sph_body_read", "sph_body_set_pose", "sph_wall_measure", "sph_wall_diagnostics", "sph_body_set_dynamics",
-                    "sph_body_get_dynamics", "sph_bodies_advance"] + _STAGE_FUNCS
+                    "sph_body_get_dynamics", "sph_bodies_advance", "sph_gauge_define", "sph_gauge_get", "sph_gauges_accumulate",
+                    "sph_gauges_read", "sph_gauges_reset", "sph_gauges_history", "sph_gauges_read_history", "sph_gauge_crossings",
+                    "sph_read_gauge_crossings"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -327,6 +339,16 @@ def device_lib():
         if hasattr(L, "sph_wall_measure"):  # (optional: an A/B library built from an older csrc/ has no wall loads)
             L.sph_wall_measure.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
             L.sph_wall_diagnostics.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        if hasattr(L, "sph_gauges_accumulate"):  # (optional: an A/B library built from an older csrc/ has no flow gauges)
+            L.sph_gauge_define.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            L.sph_gauge_get.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+            L.sph_gauges_accumulate.argtypes = [C.c_void_p, C.c_void_p]
+            L.sph_gauges_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sph_gauges_reset.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_gauges_history.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_gauges_read_history.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+            L.sph_gauge_crossings.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            L.sph_read_gauge_crossings.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -1215,6 +1237,79 @@ class owHIPSolver:
         out = np.zeros((MAX_BODIES, BODY_STATE_WORDS), np.float64)
         self._chk(self._L.sph_bodies_advance(self._h, _ptr(out)))
         return out
+
+    # --- flow gauges (sph_gauge_* / sph_gauges_*): particle crossings of oriented gates, per completed step ---
+    def gauge_define(self, slot, origin=None, u=None, v=None, types=(1,), field=None, plane=False):
+        """Define gauge `slot` (0..15) as the parallelogram origin + alpha u + beta v, 0 <= alpha, beta < 1 (plane=True: the whole
+        plane), counting particles of `types` (1 liquid, 2 elastic) that cross it, positive along u x v; `field`: a carried field
+        whose values the crossings sum, or None. origin=None releases the slot. A definition clears the slot's totals.
+        frames.gauge_rect / frames.gauge_plane build the arguments: gauge_define(slot, **frames.gauge_rect(...))."""
+        if origin is None:
+            self._chk(self._L.sph_gauge_define(self._h, int(slot), None))
+            return
+        g = SphGauge()
+        for name, val in (("origin", origin), ("u", u), ("v", v)):
+            a = np.asarray(val, np.float32).reshape(-1)
+            if a.size != 3:
+                raise SphError("gauge_define: %s must hold 3 floats" % name)
+            setattr(g, name, (C.c_float * 3)(*[float(x) for x in a]))
+        g.typeMask = type_mask(types)
+        g.fieldSlot = -1 if field is None else int(field)
+        g.flags = GAUGE_PLANE if plane else 0
+        self._chk(self._L.sph_gauge_define(self._h, int(slot), C.byref(g)))
+
+    def gauge(self, slot):
+        """The definition of gauge `slot` as a dict (origin, u, v float32[3]; typeMask; field or None; plane), or None."""
+        g = SphGauge()
+        flag = np.zeros(1, np.int32)
+        self._chk(self._L.sph_gauge_get(self._h, int(slot), C.byref(g), _ptr(flag)))
+        if not flag[0]:
+            return None
+        return dict(origin=np.array(g.origin, np.float32), u=np.array(g.u, np.float32), v=np.array(g.v, np.float32),
+                    typeMask=int(g.typeMask), field=None if g.fieldSlot < 0 else int(g.fieldSlot), plane=bool(g.flags & GAUGE_PLANE))
+
+    def gauges_accumulate(self, read=True):
+        """The crossings of the last completed step through every defined gauge: added to the totals and the history on the device.
+        read=True waits once and returns the records, float64[MAX_GAUGES, 16] (frames.GAUGE_FIELDS; a free slot is all zero);
+        read=False enqueues everything and returns None without a wait. Once per step: a second call counts the step again."""
+        if not read:
+            self._chk(self._L.sph_gauges_accumulate(self._h, None))
+            return None
+        out = np.zeros((MAX_GAUGES, GAUGE_WORDS), np.float64)
+        self._chk(self._L.sph_gauges_accumulate(self._h, _ptr(out)))
+        return out
+
+    def gauges(self):
+        """(totals float64[MAX_GAUGES, 20] named by frames.GAUGE_TOTAL_FIELDS, the number of accumulate calls so far). Blocking."""
+        out = np.zeros((MAX_GAUGES, GAUGE_TOTAL_WORDS), np.float64)
+        calls = np.zeros(1, np.int64)
+        self._chk(self._L.sph_gauges_read(self._h, _ptr(out), _ptr(calls)))
+        return out, int(calls[0])
+
+    def gauges_reset(self, slot=-1):
+        """Clear the totals of gauge `slot`, or of all gauges."""
+        self._chk(self._L.sph_gauges_reset(self._h, int(slot)))
+
+    def gauges_history(self, rows):
+        """Keep the records of the last `rows` accumulate calls in a ring on the device (0 releases it)."""
+        self._chk(self._L.sph_gauges_history(self._h, int(rows)))
+
+    def gauge_history(self, first, count):
+        """float64[count, MAX_GAUGES, 16]: the records of accumulate calls first .. first + count - 1, while the ring holds them."""
+        out = np.zeros((max(int(count), 1), MAX_GAUGES, GAUGE_WORDS), np.float64)
+        self._chk(self._L.sph_gauges_read_history(self._h, int(first), int(count), _ptr(out), None))
+        return out[:max(int(count), 0)]
+
+    def gauge_crossings(self, slot):
+        """The counted crossings of gauge `slot` in the last completed step, in ascending sorted index: (sorted index int32[n],
+        original id uint32[n], direction int32[n] (+1, -1), float32[n, 3] of t, alpha, beta). The ids can go to remove_ids."""
+        n = np.zeros(1, np.int64)
+        self._chk(self._L.sph_gauge_crossings(self._h, int(slot), _ptr(n)))
+        n = int(n[0])
+        idx, ids, way = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int32)
+        tab = np.zeros((max(n, 1), 3), np.float32)
+        self._chk(self._L.sph_read_gauge_crossings(self._h, _ptr(idx), _ptr(ids), _ptr(way), _ptr(tab)))
+        return idx[:n], ids[:n], way[:n], tab[:n]
 
     # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
     def _field_values(self, values, what):

@@ -1119,3 +1119,69 @@ def body_state_summary(record, cfg):
            "load_torque": r[23:26].copy(), "n_contact": int(r[26]), "n_share": int(r[27]), "offenders": int(r[28]),
            "lowest_member": int(r[29]) if r[0] == 1 else -1}
     return out
+
+
+# ---- flow gauges (owHIPSolver.gauge_define / gauges_accumulate; include/sphmi.h, sph_gauges_accumulate) ----
+_GAUGE_TERMS = ("n", "sum_vx", "sum_vy", "sum_vz", "sum_v2", "sum_field", "sum_alpha", "sum_beta")
+GAUGE_FIELDS = tuple("plus_" + t for t in _GAUGE_TERMS) + tuple("minus_" + t for t in _GAUGE_TERMS)
+GAUGE_TOTAL_FIELDS = GAUGE_FIELDS + ("calls", "first_plus_call", "first_minus_call", "last_call")
+
+
+def gauge_rect(centre, normal, width, height, up=(0.0, 1.0, 0.0)):
+    """The definition of a rectangular gauge, a dict with origin, u, v (float32[3] each) for owHIPSolver.gauge_define: `width` along
+    u and `height` along v about `centre`, u x v pointing along `normal`. v is `up` made orthogonal to the normal (an `up` along the
+    normal is refused), u = v x normal."""
+    n = np.asarray(normal, np.float64).reshape(3)
+    ln = float(np.sqrt((n * n).sum()))
+    if not (ln > 0 and np.isfinite(ln)) or not (float(width) > 0 and float(height) > 0):
+        raise ValueError("gauge_rect: a normal that is not zero, and a width and a height > 0")
+    n = n / ln
+    v = np.asarray(up, np.float64).reshape(3)
+    v = v - n * float((v * n).sum())
+    lv = float(np.sqrt((v * v).sum()))
+    if not lv > 1e-9:
+        raise ValueError("gauge_rect: up is along the normal")
+    v = v / lv
+    u = np.cross(v, n)  # u x v = (v x n) x v = n
+    u, v = u * float(width), v * float(height)
+    origin = np.asarray(centre, np.float64).reshape(3) - 0.5 * u - 0.5 * v
+    return dict(origin=origin.astype(np.float32), u=u.astype(np.float32), v=v.astype(np.float32))
+
+
+def gauge_plane(point, normal):
+    """The definition of a whole-plane gauge through `point` with positive direction `normal`: a dict with origin, u, v and
+    plane=True for owHIPSolver.gauge_define. u and v are unit vectors, so alpha and beta are scene units along them."""
+    n = np.asarray(normal, np.float64).reshape(3)
+    ln = float(np.sqrt((n * n).sum()))
+    if not (ln > 0 and np.isfinite(ln)):
+        raise ValueError("gauge_plane: a normal that is not zero")
+    n = n / ln
+    k = int(np.argmin(np.abs(n)))  # the axis the normal has least of
+    v = np.cross(n, np.eye(3)[k])
+    v = v / np.sqrt((v * v).sum())
+    u = np.cross(v, n)
+    return dict(origin=np.asarray(point, np.float32).reshape(3), u=u.astype(np.float32), v=v.astype(np.float32), plane=True)
+
+
+def gauge_summary(record_or_total, cfg, calls=1):
+    """A gauge's record (16 words) or totals (20 words) as physical numbers, a dict of float64 values. plus, minus, net, gross: the
+    particle counts; volume_rate: net count times the particle's volume cfg.mass / cfg.rho0 per `calls` steps of cfg.timeStep (cubic
+    metres per second; with totals `calls` defaults to their word 16); mean_velocity_plus / _minus [3] and mean_v2_plus / _minus:
+    what the crossing particles had on average (nan without a crossing); field_flux: the carried field's net sum, plus minus minus;
+    centroid_plus / _minus: the mean (alpha, beta) of the crossings."""
+    r = np.asarray(record_or_total, np.float64).reshape(-1)
+    if r.size not in (len(GAUGE_FIELDS), len(GAUGE_TOTAL_FIELDS)):
+        raise ValueError("gauge_summary: a record of %d or totals of %d words" % (len(GAUGE_FIELDS), len(GAUGE_TOTAL_FIELDS)))
+    if r.size == len(GAUGE_TOTAL_FIELDS) and calls == 1:
+        calls = r[16]
+    p, m = r[0:8], r[8:16]
+    out = {"plus": p[0], "minus": m[0], "net": p[0] - m[0], "gross": p[0] + m[0]}
+    seconds = float(calls) * float(cfg.timeStep)
+    out["volume_rate"] = (p[0] - m[0]) * (float(cfg.mass) / float(cfg.rho0)) / seconds if seconds > 0 else np.nan
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for name, h in (("plus", p), ("minus", m)):
+            out["mean_velocity_" + name] = h[1:4] / h[0]
+            out["mean_v2_" + name] = h[4] / h[0]
+            out["centroid_" + name] = h[6:8] / h[0]
+    out["field_flux"] = p[5] - m[5]
+    return out
