@@ -718,20 +718,27 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   sph_state_changes(s);
 #define RUN(stage, call) do { StageTimer t_(s, stage); rc = (call); if (rc != SPH_OK) return rc; } while (0)
   if (s->hasSlab) {
+    s->bandsStep = false;  // (sph_bands_apply: never in slab mode)
     RUN(SPH_ST_SORT, sphk_hash_sort_post_slab(s));
     RUN(SPH_ST_SORT_POST, sphk_index_fixed(s));
   } else {
+    // The search bands are decided in front of the gather: it writes their flags, ballots and counts beside its own outputs.
+    s->bandsStep = sph_bands_apply(s);
+    if (s->bandsStep) {
+      rc = sph_grow_scratch(s, s->bandBuf, sphk_bands_bytes(s, nullptr));  // (the first such step allocates)
+      if (rc != SPH_OK) { s->bandsStep = false; return rc; }
+    }
     int bits = s->sortBits;
     bool compact = false;  // wide cell ids: only ~1/8 of the declared index space is reachable, which can save a radix pass
     RUN(SPH_ST_HASH, sphk_hash_for_step(s, &bits, &compact));
     RUN(SPH_ST_SORT, sphk_sort_pairs(s, s->d.N, bits));
     if (compact) {
       StageTimer t_(s, SPH_ST_SORT_POST);
-      rc = sphk_sort_post_rekey(s);
+      rc = sphk_sort_post_rekey(s, s->bandsStep);
       if (rc == SPH_OK) rc = sphk_index_fixed(s);
       if (rc != SPH_OK) return rc;
     } else {
-      RUN(SPH_ST_SORT_POST, sphk_sort_post_and_index(s));
+      RUN(SPH_ST_SORT_POST, sphk_sort_post_and_index(s, s->bandsStep));
     }
   }
   // Slab mode: a stage runs only on the ghost layers its results are needed on (owned layers + depth layers per side).
@@ -741,13 +748,8 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   // layers only; the iteration-0 predicted positions one hop further than anything else (k_ghost_init: everywhere).
   const bool slab = s->hasSlab;
   const int M = s->cfg.maxIteration;
-  // The search bands, behind the cell table and in front of everything that forks off this stream.
-  s->bandsStep = sph_bands_apply(s);
-  if (s->bandsStep) {
-    rc = sph_grow_scratch(s, s->bandBuf, sphk_bands_bytes(s, nullptr));  // (the first such step allocates)
-    if (rc != SPH_OK) { s->bandsStep = false; return rc; }
-    RUN(SPH_ST_BANDS, sphk_build_bands(s));
-  }
+  // The rest of the search bands (scan, scatter, start tables), behind the cell table and in front of everything that forks off this stream.
+  if (s->bandsStep) RUN(SPH_ST_BANDS, sphk_build_bands(s));
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
   const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
   const int piped = chunks > 1 ? step_pipeline(s) : 0;  // stages 1 .. piped are enqueued with the search

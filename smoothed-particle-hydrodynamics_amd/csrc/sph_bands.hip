@@ -9,8 +9,9 @@
 //     row (-,-)    (0,-) (+,-)    (-,0) (+,0) (-,+)    (0,+) (+,+)          (sy, sz): the step from the visiting particle's cell
 //     Q   hiY&hiZ  hiZ   loY&hiZ  hiY   loY   hiY&loZ  loZ   loY&loZ        the face(s) of its OWN cell the candidate is near
 //
-// Four launches on the solver's stream behind k_cell_start:
-//   k_band_flags    one flag byte per sorted particle (bit s: member of band s); per wave and band the ballot and its count
+// The step's gather kernel (sph_sort.hip, with sph_band_flags.h) leaves one flag byte per sorted particle (bit s: member of band s)
+// and, per wave and band, the ballot and its count: it holds the record and the key in registers. Four launches on the solver's
+// stream behind k_cell_start do the rest:
 //   k_band_super    the counts summed per 1024 waves and band
 //   k_band_offsets  exclusive scan of the wave counts per band (the sums of the blocks in front, then a scan inside the block)
 //   k_band_scatter  records (x, y, z, sorted index) to band[s][offset of the wave + rank inside the ballot]: stable
@@ -19,36 +20,6 @@
 #include "sph_common.h"
 
 #define BAND_SUPER 1024  // wave entries per block of the scan
-
-// Bit s of the result: the particle is in band s. A particle whose key is not the id of the in-grid cell its coordinates
-// truncate to (negative or non-finite coordinates, a cell outside the grid, ids that the mask aliases) is in every band.
-__device__ __forceinline__ uint32_t band_flags(const SphBandGeom& g, const float4 q, const uint32_t key) {
-  if (!(q.x >= 0.f && q.y >= 0.f && q.z >= 0.f && q.x < 1.0e9f && q.y < 1.0e9f && q.z < 1.0e9f) || g.aliased) return 0xffu;
-  const int cx = (int)(q.x * g.cellSizeInv), cy = (int)(q.y * g.cellSizeInv), cz = (int)(q.z * g.cellSizeInv);  // as k_hash
-  if (cx >= g.gx || cy >= g.gy || cz >= g.gz || key != (uint32_t)(cx + cy * g.gx + cz * g.gx * g.gy)) return 0xffu;
-  const bool loY = q.y - (float)cy * g.cellSize <= g.Rb, hiY = (float)(cy + 1) * g.cellSize - q.y <= g.Rb;
-  const bool loZ = q.z - (float)cz * g.cellSize <= g.Rb, hiZ = (float)(cz + 1) * g.cellSize - q.z <= g.Rb;
-  return (hiY && hiZ ? 1u : 0u) | (hiZ ? 2u : 0u) | (loY && hiZ ? 4u : 0u) | (hiY ? 8u : 0u) | (loY ? 16u : 0u) |
-         (hiY && loZ ? 32u : 0u) | (loZ ? 64u : 0u) | (loY && loZ ? 128u : 0u);
-}
-
-__global__ __launch_bounds__(SPH_BLOCK) void k_band_flags(SphBandGeom g, SphBands b, const float4* __restrict__ sortedPos,
-                                                           const uint32_t* __restrict__ keys) {
-  const int i = blockIdx.x * SPH_BLOCK + threadIdx.x, lane = threadIdx.x & 63;
-  const uint32_t f = i < g.N ? band_flags(g, sortedPos[i], keys[i]) : 0u;
-  if (i < g.N) b.flags[i] = (uint8_t)f;
-  unsigned long long mine = 0ull;
-#pragma unroll
-  for (int s = 0; s < 8; s++) {
-    const unsigned long long m = __ballot((f >> s) & 1u);
-    if (lane == s) mine = m;
-  }
-  const int w = i >> 6;  // (whole waves: the block starts at a multiple of 64)
-  if (lane < 8 && w < g.waves) {  // one 64-byte and one 32-byte store per wave
-    b.mask[(size_t)w * 8 + lane] = mine;
-    b.waveOff[(size_t)w * 8 + lane] = (uint32_t)__popcll(mine);
-  }
-}
 
 // block x: superCnt[s][x] = entries of band s in the waves [1024 x, 1024 x + 1024)
 __global__ __launch_bounds__(SPH_BLOCK) void k_band_super(SphBandGeom g, SphBands b) {
@@ -189,8 +160,6 @@ int sphk_build_bands(sph_solver* s) {
   sphk_bands_bytes(s, &b);
   const SphBandGeom g = sph_band_geom(s);
   const int supers = (g.waves + 1 + BAND_SUPER - 1) / BAND_SUPER;  // (<= superStride: waves + 1 <= waveStride)
-  hipLaunchKernelGGL(k_band_flags, dim3(sph_blocks(g.N)), dim3(SPH_BLOCK), 0, s->stream, g, b, (const float4*)s->d.sortedPos,
-                     (const uint32_t*)s->d.keys);
   hipLaunchKernelGGL(k_band_super, dim3(supers), dim3(SPH_BLOCK), 0, s->stream, g, b);
   hipLaunchKernelGGL(k_band_offsets, dim3(supers, 8), dim3(SPH_BLOCK), 0, s->stream, g, b);
   hipLaunchKernelGGL(k_band_scatter, dim3(sph_blocks(g.N)), dim3(SPH_BLOCK), 0, s->stream, g, b, (const float4*)s->d.sortedPos);

@@ -376,11 +376,13 @@ int sphk_sort_pairs(sph_solver* s, int n, int bits);  // stable LSD sort of (key
 int sph_sort_passes(int bits);                         // radix passes sphk_sort_pairs takes for `bits` key bits (8- or 9-bit digits)
 int sphk_step_sort_bits(const sph_solver* s, bool* compact);         // key bits the fused step sorts (compacted keys or the real ones)
 int sphk_hash_for_step(sph_solver* s, int* sortBits, bool* compact);  // fused step: hash with compacted keys where that saves a pass
-int sphk_sort_post_rekey(sph_solver* s);               // the gather after a sort of compacted keys (puts the real cell ids back)
-int sphk_sort_post(sph_solver* s);        // gather + backIndex (K3)
+// bandFlags (both gathers): also write the first stage of the step's search bands — flags, ballots, counts (sph_band_flags.h) — into
+// bandBuf, which the caller has grown; sphk_build_bands does the rest
+int sphk_sort_post_rekey(sph_solver* s, bool bandFlags = false);  // the gather after a sort of compacted keys (puts the real cell ids back)
+int sphk_sort_post(sph_solver* s, bool bandFlags = false);        // gather + backIndex (K3)
 int sphk_index_raw(sph_solver* s);        // K4 table with -1 for empty cells
 int sphk_index_fixed(sph_solver* s);      // H2 table (cellStart)
-int sphk_sort_post_and_index(sph_solver* s);  // fused K3 + K4 + H2
+int sphk_sort_post_and_index(sph_solver* s, bool bandFlags = false);  // fused K3 + K4 + H2
 int sphk_hash_sort_post_slab(sph_solver* s);  // slab mode: K2 + sort + K3 with compacted sort keys (2 radix passes)
 // sph_neighbors.hip
 int sphk_clear_neighbors(sph_solver* s);
@@ -393,7 +395,7 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1, int idxLo = 0, int i
 size_t sphk_bands_bytes(const sph_solver* s, SphBands* out);  // bytes of bandBuf for the solver's capacity and grid; *out: the arrays in it
 SphBandGeom sph_band_geom(const sph_solver* s);
 float sph_band_radius(const SphDev& d, float filterR2);       // Rb from the search filter's radius^2 (binU[63])
-int sphk_build_bands(sph_solver* s);                          // flags, scan, scatter, start tables; on s->stream behind the cell table
+int sphk_build_bands(sph_solver* s);  // scan, scatter, start tables from the flags the gather left (bandFlags); on s->stream behind the cell table
 // sph_pcisph.hip
 int sphk_density(sph_solver* s, int ghostDepth = -1);
 // density and the record pack of chunk c of the partition that enqueue_search_overlapped (sph_api.hip) keeps in s->chunkEdges

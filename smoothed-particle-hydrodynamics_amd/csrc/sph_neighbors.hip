@@ -225,10 +225,13 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
   if (lane == 0) g.nbr16[nbr_index(id, 0)] = (uint16_t)SPH_N16_WIDE;  // no 16-bit copy of this row: readers take the 32-bit ids
 }
 
-// The lane pair (2p, 2p+1) serves particle p. Lane A (even) walks the cells k = 0,5,6,7 of the reference's order and lane B (odd)
-// the cells 1,2,3,4, each cell whole, in sorted-index order. The merged traversal order is therefore
-//   A0 | B1 B2 B3 B4 | A5 A6 A7
+// The lane pair (2p, 2p+1) serves particle p. Lane A (even) walks the cells k = 0,4,5,7 of the reference's order and lane B (odd)
+// the cells 1,2,3,6, each cell whole, in sorted-index order. The merged traversal order is therefore
+//   A0 | B1 B2 B3 | A4 A5 | B6 | A7
 // and four per-cell hit counts per lane (one packed word, one DPP move) place every neighbour in the reference's slot.
+// The two lanes walk their pieces in lockstep (the loop over the pieces is unrolled, the loop inside it is wave-level), so piece i
+// costs the longer of the two. Piece i therefore takes the same y and z steps in both lanes — no step, y, z, yz — and the lanes
+// differ in the x step alone: with bands both lanes walk full, y face, z face, yz edge (tools/fn_walk_model.py prices an assignment).
 // Lane A gets 54 % of the hits (own cell ~42 %, edges 5 % each, corner 2 %), lane B 46 % (faces ~14 % each, one edge).
 //
 // Synchronisation: ONE workgroup barrier per batch, between the staging of the candidates and their use. Everything before it
@@ -405,10 +408,12 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     const int dz = ((pz - cfz) < d.h) ? -1 : 1;
     const int sy = dy * d.gx, sz = dz * d.gx * d.gy;
     const int ry = dy + 1, rz = dz + 1;  // staged-row ids: row = (y step + 1) + 3 * (z step + 1)
-    // lane A: cells 0 (own), 5 (xz), 6 (yz), 7 (xyz); lane B: cells 1 (x), 2 (y), 3 (z), 4 (xy)
-    const bool stepX[4] = {laneB != 0, laneB == 0, false, true};
-    const bool stepY[4] = {false, laneB != 0, laneB == 0, true};
-    const bool stepZ[4] = {false, laneB == 0, true, laneB == 0};
+    // lane A: cells 0 (own), 4 (xy), 5 (xz), 7 (xyz); lane B: cells 1 (x), 2 (y), 3 (z), 6 (yz). Piece i takes the same y and z
+    // steps in both lanes — the same staged row, with bands the same kind of piece (full, y face, z face, yz edge) — and the two
+    // lanes differ in the x step alone.
+    const bool stepX[4] = {laneB != 0, laneB == 0, laneB == 0, laneB == 0};
+    const bool stepY[4] = {false, true, false, true};
+    const bool stepZ[4] = {false, false, true, true};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int xs = stepX[i] ? dx : 0;
@@ -464,7 +469,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     const int zB = laneB ? zLoMine : zOther;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const bool zf = laneB ? (i == 2) : (i != 0);
+      const bool zf = i >= 2;  // cells one z layer away: 5, 7 in lane A, 3, 6 in lane B
       const int rel = SPH_N16_BIAS - (zf ? zB : idNow);
       if (trueHi[i] > trueLo[i] && (trueLo[i] + rel < 0 || trueHi[i] - 1 + rel > SPH_N16_MAX)) wideB = 1;
     }
@@ -686,29 +691,29 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   // (the wave's list area is free from here on: every lane has its slots in slotPk, and LDS operations of a wave retire in order)
   if (!slow) {
     const int c0b = cellTot & 255, c1b = (cellTot >> 8) & 255, c2b = (cellTot >> 16) & 255, c3b = (cellTot >> 24) & 255;
-    const int o0b = otherTot & 255;
-    const int sumOther = o0b + ((otherTot >> 8) & 255) + ((otherTot >> 16) & 255) + ((otherTot >> 24) & 255);
-    const int run = min(c0b + c1b + c2b + c3b + sumOther, SPH_MAXN);
-    // lane A (cells 0 | 5 6 7): cell 0 starts at 0, cells 5.. after cell 0 and all of lane B's;
-    // lane B (cells 1 2 3 4): starts after cell 0 (= lane A's first cell)
-    const int first = laneB ? o0b : 0, afterFirst = laneB ? 0 : sumOther;
+    const int o0b = otherTot & 255, o1b = (otherTot >> 8) & 255, o2b = (otherTot >> 16) & 255, o3b = (otherTot >> 24) & 255;
+    const int run = min(c0b + c1b + c2b + c3b + o0b + o1b + o2b + o3b, SPH_MAXN);
+    // merged order A0 | B1 B2 B3 | A4 A5 | B6 | A7, with a_i, b_i the counts of the lanes' pieces:
+    // lane A (cells 0 4 5 7): 0;  a0 + b0 + b1 + b2;  that + a1;  a0 + a1 + a2 + b0 + b1 + b2 + b3
+    // lane B (cells 1 2 3 6): a0;  a0 + b0;  a0 + b0 + b1;  a0 + a1 + a2 + b0 + b1 + b2
+    const int front = c0b + o0b + (laneB ? c1b + c2b : o1b + o2b);  // a0 + b0 + b1 + b2
     int start[4];
-    start[0] = first;
-    start[1] = first + c0b + afterFirst;
-    start[2] = first + c0b + afterFirst + c1b;
-    start[3] = first + c0b + afterFirst + c1b + c2b;
+    start[0] = laneB ? o0b : 0;
+    start[1] = laneB ? o0b + c0b : front;
+    start[2] = laneB ? o0b + c0b + c1b : front + c1b;
+    start[3] = laneB ? front + o1b + o2b : front + c1b + c2b + o3b;
     // Ids go straight to the tiled map (4-byte stores); the d^2 of the accepted neighbours go to the wave's staging area
     // [particle][slot], from which each lane of the pair then takes 16 consecutive slots: 16 square roots per lane instead of
     // one per list entry, and the distances leave as four 16-byte stores per lane (which also write the -1 of the unused slots).
     // The 16-bit copy of the row (sph_common.h, SPH_N16_*): offsets from the particle itself, or — cells one z layer away: lane A's
-    // 5 6 7, lane B's 3 — from the first particle of the z-neighbour cell. A piece's entries are its LDS slots + one constant, so
+    // 5 7, lane B's 3 6 — from the first particle of the z-neighbour cell. A piece's entries are its LDS slots + one constant, so
     // the range check is two comparisons per piece, not one per entry.
     const int zBase = laneB ? zLoMine : zLoOther;
     int rel16[4];
     int wide = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const bool zf = laneB ? (i == 2) : (i != 0);
+      const bool zf = i >= 2;
       rel16[i] = absDelta[i] - (zf ? zBase : idNow) + SPH_N16_BIAS;
       if (pHi[i] > pLo[i] && (pLo[i] + rel16[i] < 0 || pHi[i] - 1 + rel16[i] > SPH_N16_MAX)) wide = 1;
     }

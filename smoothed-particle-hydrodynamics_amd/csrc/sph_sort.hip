@@ -2,6 +2,7 @@
 // owOpenCLSolver.cpp:255-261), gather into sorted order (K3) and the cell-start table (K4 + the host fix-up loop,
 // owOpenCLSolver.cpp:305-319). No device->host round trip, unlike the reference.
 #include "sph_common.h"
+#include "sph_band_flags.h"
 
 // ------------------------------------------------------------------ K2 hashParticles (sphFluid.cl:187-201,332-383)
 // The step's first kernel: the gate counts of the predict-correct loop and the neighbourhood bytes of its stages start at zero
@@ -45,16 +46,25 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_hash_compact(SphDev d, CompactKey
   d.vals[id] = (uint32_t)id;
 }
 
-__global__ __launch_bounds__(SPH_BLOCK) void k_sort_post_rekey(SphDev d) {
+// FLAGS (both gather kernels; the fused non-slab step where its search reads bands): the kernel also leaves the first stage of the
+// search bands — the particle's flag byte and the wave's eight ballots and counts (sph_band_flags.h) — from the record and the key
+// it stores. The ballots are wave-level, so the lanes past N stay to the end and contribute zero.
+template <bool FLAGS>
+__global__ __launch_bounds__(SPH_BLOCK) void k_sort_post_rekey(SphDev d, SphBandGeom g, SphBands b) {
   const int i = blockIdx.x * SPH_BLOCK + threadIdx.x;
-  if (i >= d.N) return;
-  const uint32_t src = d.vals[i];
-  const float4 p = d.posOrig[src];
-  d.sortedPos[i] = p;
-  d.sortedVel[i] = d.velOrig[src];
-  d.backIndex[src] = (uint32_t)i;
-  const int cx = (int)(p.x * d.cellSizeInv), cy = (int)(p.y * d.cellSizeInv), cz = (int)(p.z * d.cellSizeInv);
-  d.keys[i] = (uint32_t)(cx + cy * d.gx + cz * d.gx * d.gy) & d.cellMask;  // the real cell id, as k_hash computes it
+  uint32_t f = 0u;
+  if (i < d.N) {
+    const uint32_t src = d.vals[i];
+    const float4 p = d.posOrig[src];
+    d.sortedPos[i] = p;
+    d.sortedVel[i] = d.velOrig[src];
+    d.backIndex[src] = (uint32_t)i;
+    const int cx = (int)(p.x * d.cellSizeInv), cy = (int)(p.y * d.cellSizeInv), cz = (int)(p.z * d.cellSizeInv);
+    const uint32_t key = (uint32_t)(cx + cy * d.gx + cz * d.gx * d.gy) & d.cellMask;  // the real cell id, as k_hash computes it
+    d.keys[i] = key;
+    if (FLAGS) f = band_flags(g, p, key);
+  }
+  if (FLAGS) band_flags_store(g, b, i, f);
 }
 
 static int bits_for(long long n) { int b = 1; while ((1LL << b) < n) b++; return b; }
@@ -100,8 +110,19 @@ int sphk_hash_for_step(sph_solver* s, int* sortBits, bool* compact) {
   return SPH_OK;
 }
 
-int sphk_sort_post_rekey(sph_solver* s) {
-  hipLaunchKernelGGL(k_sort_post_rekey, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d);
+// The band arguments of a gather launch: the step's arrays and geometry where it writes the flags, unused otherwise.
+static void gather_band_args(const sph_solver* s, bool bandFlags, SphBandGeom* g, SphBands* b) {
+  *g = SphBandGeom{};
+  *b = SphBands{};
+  if (bandFlags) { sphk_bands_bytes(s, b); *g = sph_band_geom(s); }
+}
+
+int sphk_sort_post_rekey(sph_solver* s, bool bandFlags) {
+  SphBandGeom g;
+  SphBands b;
+  gather_band_args(s, bandFlags, &g, &b);
+  hipLaunchKernelGGL(bandFlags ? k_sort_post_rekey<true> : k_sort_post_rekey<false>, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream,
+                     s->d, g, b);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
@@ -277,13 +298,19 @@ int sphk_sort_pairs(sph_solver* s, int n, int bits) {
 }
 
 // ------------------------------------------------------------------ K3 sortPostPass (sphFluid.cl:441-466)
-__global__ __launch_bounds__(SPH_BLOCK) void k_sort_post(SphDev d) {
+template <bool FLAGS>  // (see k_sort_post_rekey; the key is the sorted one the radix sort left in keys[])
+__global__ __launch_bounds__(SPH_BLOCK) void k_sort_post(SphDev d, SphBandGeom g, SphBands b) {
   const int i = blockIdx.x * SPH_BLOCK + threadIdx.x;
-  if (i >= d.N) return;
-  const uint32_t src = d.vals[i];
-  d.sortedPos[i] = d.posOrig[src];  // .w stays the particle type; the cell id lives in keys[]
-  d.sortedVel[i] = d.velOrig[src];
-  d.backIndex[src] = (uint32_t)i;
+  uint32_t f = 0u;
+  if (i < d.N) {
+    const uint32_t src = d.vals[i];
+    const float4 p = d.posOrig[src];
+    d.sortedPos[i] = p;  // .w stays the particle type; the cell id lives in keys[]
+    d.sortedVel[i] = d.velOrig[src];
+    d.backIndex[src] = (uint32_t)i;
+    if (FLAGS) f = band_flags(g, p, d.keys[i]);
+  }
+  if (FLAGS) band_flags_store(g, b, i, f);
 }
 
 // K4 indexx (sphFluid.cl:385-439) + the host fix-up loop (owOpenCLSolver.cpp:305-319) in one kernel, one lane per cell:
@@ -314,8 +341,11 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cell_start(SphDev d, int first, i
     for (int i = 0; i < SPH_GATE_SLOTS; i++) d.skipGate[i] = 1u;
 }
 
-int sphk_sort_post(sph_solver* s) {
-  hipLaunchKernelGGL(k_sort_post, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d);
+int sphk_sort_post(sph_solver* s, bool bandFlags) {
+  SphBandGeom g;
+  SphBands b;
+  gather_band_args(s, bandFlags, &g, &b);
+  hipLaunchKernelGGL(bandFlags ? k_sort_post<true> : k_sort_post<false>, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d, g, b);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
@@ -343,8 +373,8 @@ int sphk_index_fixed(sph_solver* s) {
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
-int sphk_sort_post_and_index(sph_solver* s) {
-  int rc = sphk_sort_post(s);
+int sphk_sort_post_and_index(sph_solver* s, bool bandFlags) {
+  int rc = sphk_sort_post(s, bandFlags);
   return rc == SPH_OK ? sphk_index_fixed(s) : rc;
 }
 
