@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "sph_api_internal.h"
+#include "sph_tree.h"  // tree_chunks, tree_scratch_doubles, terms_bytes
 
 // ---------------------------------------------------------------------------------------------- field sampling
 // Reads the sorted state the last step's density and pressure loop ran on (sph_sample.hip); enqueued on s->stream and waited
@@ -273,7 +274,7 @@ static int diag_fill_regions(sph_solver* s, DiagArgs* a, const float* regions6, 
 
 // the records of a.count selections: through the diagnostics scratch to `out`, then the check every blocking call ends with
 static int diag_records(sph_solver* s, const DiagArgs& a, double* out) {
-  int rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_diag_scratch_doubles(s->d.N, a.count));
+  int rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * tree_scratch_doubles(s->d.N, a.count, SPH_DIAG_WORDS));
   if (rc != SPH_OK) return rc;
   double* records = nullptr;
   rc = sphk_diagnostics(s, a, (double*)s->diagBuf.p, &records);
@@ -622,6 +623,41 @@ static int force_check(sph_solver* s, uint32_t typeMask, const char* what) {
   return SPH_OK;
 }
 
+// The two piece loops of the force decomposition and the wall loads.
+// n particles, or the selection list, in pieces of whole blocks through the sampling scratch: records(first, m, list, dst)
+// enqueues the records of `words` floats of a piece, which are then copied out
+template <class Records>
+static int measure_records(sph_solver* s, size_t n, const int32_t* list, size_t words, float* out, Records records) {
+  const size_t rec = sizeof(float) * words;
+  const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
+  int rc = sph_grow_scratch(s, s->sampleBuf, piece * rec);
+  if (rc != SPH_OK) return rc;
+  for (size_t first = 0; first < n; first += piece) {
+    const size_t m = std::min(piece, n - first);
+    rc = records((int)first, (int)m, list ? list + first : nullptr, (float*)s->sampleBuf.p);
+    if (rc != SPH_OK) return rc;
+    rc = sph_d2h(s, out + first * words, s->sampleBuf.p, rec * m);
+    if (rc != SPH_OK) return rc;
+  }
+  return sph_check_finite_state(s);
+}
+
+// Region totals: the `terms` per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the
+// diagnostics scratch; run(terms, pieceChunks, scratch, &records) enqueues the call, whose count x words doubles are copied out
+template <class Run>
+static int region_totals(sph_solver* s, int terms, int words, int32_t count, double* out, Run run) {
+  const int pieceChunks = (int)std::min<size_t>((size_t)tree_chunks(s->d.N), kSampleScratchBytes / terms_bytes(terms, 1));
+  int rc = sph_grow_scratch(s, s->sampleBuf, terms_bytes(terms, pieceChunks));
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * tree_scratch_doubles(s->d.N, count, words));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = run((float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, records, sizeof(double) * (size_t)words * (size_t)count);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
 extern "C" int sph_force_measure(sph_solver* s, int32_t fromSelection, float* out) {
   ENTER(s);
   if (fromSelection != 0 && fromSelection != 1) { sph_set_error("sph_force_measure: fromSelection %d is not 0 or 1", fromSelection); return SPH_ERR_INVALID; }
@@ -637,18 +673,8 @@ extern "C" int sph_force_measure(sph_solver* s, int32_t fromSelection, float* ou
   if (rc != SPH_OK) return rc;
   if (n == 0) return sph_check_finite_state(s);
   if (!out) { sph_set_error("sph_force_measure: null pointer"); return SPH_ERR_INVALID; }
-  const size_t rec = sizeof(float) * SPH_FORCE_WORDS;
-  const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
-  rc = sph_grow_scratch(s, s->sampleBuf, piece * rec);
-  if (rc != SPH_OK) return rc;
-  for (size_t first = 0; first < n; first += piece) {
-    const size_t m = std::min(piece, n - first);
-    rc = sphk_force_records(s, (int)first, (int)m, list ? list + first : nullptr, (float*)s->sampleBuf.p);
-    if (rc != SPH_OK) return rc;
-    rc = sph_d2h(s, out + first * SPH_FORCE_WORDS, s->sampleBuf.p, rec * m);
-    if (rc != SPH_OK) return rc;
-  }
-  return sph_check_finite_state(s);
+  return measure_records(s, n, list, SPH_FORCE_WORDS, out,
+                         [&](int first, int m, const int32_t* l, float* dst) { return sphk_force_records(s, first, m, l, dst); });
 }
 
 extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
@@ -660,18 +686,9 @@ extern "C" int sph_force_diagnostics(sph_solver* s, const float* regions6, int32
   DiagArgs a = {};
   rc = diag_fill_regions(s, &a, regions6, count, typeMask, "sph_force_diagnostics");
   if (rc != SPH_OK) return rc;
-  // the per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the diagnostics scratch
-  const int chunks = s->d.N > 0 ? (s->d.N + 1023) / 1024 : 1;
-  const int pieceChunks = (int)std::min<size_t>((size_t)chunks, kSampleScratchBytes / sphk_force_terms_bytes(1));
-  rc = sph_grow_scratch(s, s->sampleBuf, sphk_force_terms_bytes(pieceChunks));
-  if (rc != SPH_OK) return rc;
-  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_force_diag_scratch_doubles(s->d.N, count));
-  if (rc != SPH_OK) return rc;
-  double* records = nullptr;
-  rc = sphk_force_diagnostics(s, a, (float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
-  if (rc != SPH_OK) return rc;
-  rc = sph_d2h(s, out, records, sizeof(double) * SPH_FORCE_DIAG_WORDS * (size_t)count);
-  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+  return region_totals(s, FM_TERMS, SPH_FORCE_DIAG_WORDS, count, out, [&](float* terms, int pieceChunks, double* scratch, double** records) {
+    return sphk_force_diagnostics(s, a, terms, pieceChunks, scratch, records);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- wall loads
@@ -722,18 +739,9 @@ extern "C" int sph_wall_measure(sph_solver* s, int32_t slot, int32_t fromSelecti
   bool inverted = false;
   rc = wall_set(s, slot, &mask, &inverted);
   if (rc != SPH_OK) return rc;
-  const size_t rec = sizeof(float) * SPH_WALL_WORDS;
-  const size_t piece = std::min((n + SPH_BLOCK - 1) / SPH_BLOCK * SPH_BLOCK, kSampleScratchBytes / rec / SPH_BLOCK * SPH_BLOCK);
-  rc = sph_grow_scratch(s, s->sampleBuf, piece * rec);
-  if (rc != SPH_OK) return rc;
-  for (size_t first = 0; first < n; first += piece) {
-    const size_t m = std::min(piece, n - first);
-    rc = sphk_wall_records(s, mask, inverted, (int)first, (int)m, list ? list + first : nullptr, (float*)s->sampleBuf.p);
-    if (rc != SPH_OK) return rc;
-    rc = sph_d2h(s, out + first * SPH_WALL_WORDS, s->sampleBuf.p, rec * m);
-    if (rc != SPH_OK) return rc;
-  }
-  return sph_check_finite_state(s);
+  return measure_records(s, n, list, SPH_WALL_WORDS, out, [&](int first, int m, const int32_t* l, float* dst) {
+    return sphk_wall_records(s, mask, inverted, first, m, l, dst);
+  });
 }
 
 extern "C" int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* regions6, int32_t count, uint32_t typeMask, double* out) {
@@ -749,18 +757,9 @@ extern "C" int sph_wall_diagnostics(sph_solver* s, int32_t slot, const float* re
   bool inverted = false;
   rc = wall_set(s, slot, &mask, &inverted);
   if (rc != SPH_OK) return rc;
-  // the per-particle terms of a piece of whole chunks in the sampling scratch, the tree's partials in the diagnostics scratch
-  const int chunks = s->d.N > 0 ? (s->d.N + 1023) / 1024 : 1;
-  const int pieceChunks = (int)std::min<size_t>((size_t)chunks, kSampleScratchBytes / sphk_wall_terms_bytes(1));
-  rc = sph_grow_scratch(s, s->sampleBuf, sphk_wall_terms_bytes(pieceChunks));
-  if (rc != SPH_OK) return rc;
-  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_wall_diag_scratch_doubles(s->d.N, count));
-  if (rc != SPH_OK) return rc;
-  double* records = nullptr;
-  rc = sphk_wall_diagnostics(s, mask, inverted, a, (float*)s->sampleBuf.p, pieceChunks, (double*)s->diagBuf.p, &records);
-  if (rc != SPH_OK) return rc;
-  rc = sph_d2h(s, out, records, sizeof(double) * SPH_WALL_DIAG_WORDS * (size_t)count);
-  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+  return region_totals(s, WL_TERMS, SPH_WALL_DIAG_WORDS, count, out, [&](float* terms, int pieceChunks, double* scratch, double** records) {
+    return sphk_wall_diagnostics(s, mask, inverted, a, terms, pieceChunks, scratch, records);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- free bodies

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "sph_api_internal.h"
+#include "sph_tree.h"  // tree_scratch_doubles
 
 // ---------------------------------------------------------------------------------------------- carried fields
 // What every field call checks first: no slab solver, a slot number in range (SPH_ERR_INVALID). Whether the slot exists is
@@ -186,7 +187,7 @@ extern "C" int sph_field_diagnostics(sph_solver* s, int32_t slot, const float* r
     std::copy(one.box, one.box + 6, a.box[r]);
   }
   a.count = count; a.typeMask = typeMask; a.rho0 = s->d.rho0;
-  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * sphk_field_diag_scratch_doubles(s->d.N, count));
+  rc = sph_grow_scratch(s, s->diagBuf, sizeof(double) * tree_scratch_doubles(s->d.N, count, SPH_FIELD_DIAG_WORDS));
   if (rc != SPH_OK) return rc;
   double* records = nullptr;
   rc = sphk_field_diagnostics(s, field_of(s, slot), a, (double*)s->diagBuf.p, &records);

@@ -11,7 +11,7 @@
 //                     mask per element, found by walking the set bits of bndMask once); a block without a lane that touches
 //                     body b writes +0.0 partials for it and does no tree. Slot 16 of the partials is no body: its word 0 counts
 //                     the particles in contact with any wall (word 1 of the diagnostics record).
-//   k_bdyn_upper      the upper levels of the tree, k_wall_upper's shape with the body in place of the region
+//   (sph_tree.hip)    the upper levels of the tree, the rows of the dynamic bodies and word 0 of the count row only
 //   k_bdyn_integrate  one thread per slot: the contract's doubles; the new state goes to a staging record, the pose as floats
 //   k_bdyn_pose<C>    validate (C = false) and commit (C = true) of all dynamic bodies in one launch each (blockIdx.y = slot),
 //                     through body_pose_member (sph_body_pose.h), the function k_body_pose runs; the commit is predicated on the
@@ -31,9 +31,7 @@
 #define BD_SLOTS (SPH_MAX_BODIES + 1)  // the bodies, then the contact count of all walls
 #define BD_ALL SPH_MAX_BODIES
 
-__device__ __host__ __forceinline__ size_t bd_at(int body, int word, int chunks, int chunk) {
-  return ((size_t)(body * BD_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
+// (the rows of the tree are the BD_SLOTS slots, BD_WORDS words each; the last row holds word 0 only)
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_map(SphDev d, BodyDynSet set, uint8_t* __restrict__ bodyOf) {
   const int b = blockIdx.y, r = blockIdx.x * SPH_BLOCK + threadIdx.x;
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_leaf(SphDev d, const uint8_t
                                                          double* __restrict__ part, int chunks) {
   __shared__ double sh[BD_GROUP][SPH_BLOCK];
   __shared__ uint32_t shPres;
-  const int t = threadIdx.x, chunk = blockIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, chunk = blockIdx.x;
   // per element: the boundary-slot mask of a selected non-boundary particle (0 otherwise) and the bodies in its row
   uint32_t bnd[4], pres[4];
   uint32_t mine = 0u;
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_leaf(SphDev d, const uint8_t
     if (!((wanted >> b) & 1u)) continue;
     const int nW = b == BD_ALL ? 1 : BD_WORDS;
     if (!((blockPres >> b) & 1u)) {  // every term of this chunk is zero: +0.0, which is what the tree would produce from +0.0 terms
-      if (t < nW) part[bd_at(b, t, chunks, chunk)] = 0.0;
+      if (t < nW) part[tree_at(BD_WORDS, b, t, chunks, chunk)] = 0.0;
       continue;
     }
     const WallBodySet ws = {bodyOf, b};
@@ -156,30 +154,11 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_leaf(SphDev d, const uint8_t
       for (int k = 0; k < BD_GROUP; k++)
         if (g * BD_GROUP + k < BD_WORDS) sh[k][t] = acc[g * BD_GROUP + k];
       __syncthreads();
-      if (t < 128) {
-#pragma unroll
-        for (int k = 0; k < BD_GROUP; k++) sh[k][t] = sh[k][t] + sh[k][t + 128];
-      }
-      __syncthreads();
-      for (int k = wave; k < BD_GROUP; k += 4) {
-        const int w = g * BD_GROUP + k;
-        if (w >= nW) continue;  // (wave-uniform)
-        const double x = diag_wave_sum(sh[k][lane] + sh[k][lane + 64]);
-        if (lane == 0) part[bd_at(b, w, chunks, chunk)] = x;
-      }
+      tree_group_sums<BD_GROUP>(sh, min(BD_GROUP, nW - g * BD_GROUP),
+                                [&](int k, double x) { part[tree_at(BD_WORDS, b, g * BD_GROUP + k, chunks, chunk)] = x; });
       __syncthreads();  // sh is reused by the next group and the next body
     }
   }
-}
-
-// Upper levels: `nIn` partials per word and body -> ceil(nIn / 1024), the same tree. One block per output chunk, body and word.
-__global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut,
-                                                          uint32_t dynMask) {
-  __shared__ double sh[SPH_BLOCK];
-  const int chunk = blockIdx.x, b = blockIdx.y, w = blockIdx.z;
-  if (!(((dynMask | (1u << BD_ALL)) >> b) & 1u) || (b == BD_ALL && w > 0)) return;  // (block-uniform)
-  const double x = diag_block_reduce<DIAG_OP_SUM>(in + bd_at(b, w, nIn, 0), nIn, chunk, 0.0, sh);
-  if (threadIdx.x == 0) out[bd_at(b, w, nOut, chunk)] = x;
 }
 
 // R(q), row-major, the contract's expressions
@@ -202,7 +181,7 @@ __global__ void k_bdyn_integrate(BodyDynDev* __restrict__ D, const double* __res
   if (!((set.dynMask >> b) & 1u)) { rec[0] = -1.0; return; }
   const BodyDynSlot live = D->live[b];
   const sph_body_dynamics& p = live.p;
-  const double* S = top + bd_at(b, 0, 1, 0);
+  const double* S = top + tree_at(BD_WORDS, b, 0, 1, 0);
   double Fl[3], T0[3], Tl[3], V[3], X[3], L[3], om[3], q[4];
   for (int c = 0; c < 3; c++) {
     const double C = S[1 + c], H = (S[4 + c] + S[10 + c]) + S[7 + c], TC = S[13 + c], TH = S[16 + c];
@@ -270,7 +249,7 @@ __global__ void k_bdyn_integrate(BodyDynDev* __restrict__ D, const double* __res
     rec[4 + c] = X[c]; rec[11 + c] = V[c]; rec[14 + c] = L[c]; rec[17 + c] = om[c]; rec[20 + c] = Fl[c]; rec[23 + c] = Tl[c];
   }
   for (int c = 0; c < 4; c++) rec[7 + c] = q[c];
-  rec[26] = top[bd_at(BD_ALL, 0, 1, 0)];
+  rec[26] = top[tree_at(BD_WORDS, BD_ALL, 0, 1, 0)];
   rec[27] = S[0];
 }
 
@@ -325,17 +304,9 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_bdyn_overlap_count(const uint32_t
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-static int bd_chunks(int n) { return n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1; }
 static size_t bd_map_bytes(int N) { return ((size_t)std::max(N, 1) + 255) & ~(size_t)255; }
 
-size_t sphk_bdyn_scratch_bytes(int N) {
-  size_t total = 0;
-  for (int c = bd_chunks(N);; c = bd_chunks(c)) {
-    total += (size_t)c;
-    if (c == 1) break;
-  }
-  return bd_map_bytes(N) + sizeof(double) * total * BD_SLOTS * BD_WORDS;
-}
+size_t sphk_bdyn_scratch_bytes(int N) { return bd_map_bytes(N) + sizeof(double) * tree_level_chunks(N) * BD_SLOTS * BD_WORDS; }
 
 int sphk_bdyn_overlap(sph_solver* s, const BodyDynSet& set, int slot, unsigned long long* seen, BodyDynDev* D) {
   const int N = s->d.N;
@@ -369,23 +340,21 @@ int sphk_bdyn_advance(sph_solver* s, const BodyDynSet& set, const BodyPose& box,
   SPH_HIP(hipMemsetAsync(bodyOf, 0xff, bd_map_bytes(N), s->stream));
   hipLaunchKernelGGL(k_bdyn_map, members, dim3(SPH_BLOCK), 0, s->stream, s->d, set, bodyOf);
   SPH_HIP(hipGetLastError());
-  int chunks = bd_chunks(N);
+  const int chunks = tree_chunks(N);
   hipLaunchKernelGGL(k_bdyn_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, (const uint8_t*)bodyOf, set.dynMask, cur, chunks);
   SPH_HIP(hipGetLastError());
-  while (chunks > 1) {
-    const int nOut = bd_chunks(chunks);
-    double* next = cur + (size_t)BD_SLOTS * BD_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_bdyn_upper, dim3(nOut, BD_SLOTS, BD_WORDS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut,
-                       set.dynMask);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  hipLaunchKernelGGL(k_bdyn_integrate, dim3(1), dim3(64), 0, s->stream, D, (const double*)cur, set, box, (double)s->d.dt,
+  // the rows of non-dynamic bodies and words 1..18 of the count row are unwritten at every level: not reduced, never read
+  TreeShape S = tree_shape(BD_WORDS, BD_WORDS, set.dynMask | (1u << BD_ALL));
+  S.shortRow = BD_ALL; S.shortWords = 1;
+  double *top = nullptr, *end = nullptr;
+  int rc = sphk_tree_upper(s, S, BD_SLOTS, cur, chunks, &top, &end);
+  if (rc != SPH_OK) return rc;
+  hipLaunchKernelGGL(k_bdyn_integrate, dim3(1), dim3(64), 0, s->stream, D, (const double*)top, set, box, (double)s->d.dt,
                      (double)s->d.posTimeStep, (double)s->cfg.mass);
   SPH_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_bdyn_pose<false>, members, dim3(SPH_BLOCK), 0, s->stream, D, set, N, s->d.posOrig, s->d.velOrig);
   SPH_HIP(hipGetLastError());
-  const int rc = sph_guard_position_write(s);  // an asynchronous read-back of posOrig finishes its device copy first
+  rc = sph_guard_position_write(s);  // an asynchronous read-back of posOrig finishes its device copy first
   if (rc != SPH_OK) return rc;
   hipLaunchKernelGGL(k_bdyn_pose<true>, members, dim3(SPH_BLOCK), 0, s->stream, D, set, N, s->d.posOrig, s->d.velOrig);
   SPH_HIP(hipGetLastError());

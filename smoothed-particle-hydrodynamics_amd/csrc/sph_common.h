@@ -484,8 +484,8 @@ struct HistArgs {
   int field, bins;
   float lo, hi, scale;  // scale = (float)bins / (hi - lo)
 };
-size_t sphk_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_DIAG_WORDS records
-int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records);  // *records: where the records land
+// scratch: tree_scratch_doubles(N, a.count, SPH_DIAG_WORDS) (sph_tree.h); *records: where the records land (in scratch)
+int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records);
 int sphk_histogram(sph_solver* s, const HistArgs& a, uint32_t* out);  // out: bins + 2 device words
 // sph_components.hip (connected components of the neighbour graph; read-only on every solver array)
 size_t sphk_components_scratch_bytes(int N);             // parent and labels (4 B per particle each), the scan's block totals
@@ -615,7 +615,7 @@ int sphk_field_paint_region(sph_solver* s, float* field, const SphSelector& a, f
 int sphk_field_paint_list(sph_solver* s, float* field, const int32_t* list, int n, float value);  // field[vals[list[r]]] = value
 int sphk_field_compact(sph_solver* s, const float* in, const int32_t* map, int nOld, float* out);  // out[map[o]] = in[o], map[o] >= 0
 int sphk_field_fill(sph_solver* s, float* field, int first, int n, float value);
-size_t sphk_field_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_FIELD_DIAG_WORDS records
+// scratch: tree_scratch_doubles(N, a.count, SPH_FIELD_DIAG_WORDS) (sph_tree.h); *records: where the records land (in scratch)
 int sphk_field_diagnostics(sph_solver* s, const float* field, const DiagArgs& a, double* scratch, double** records);
 // sph_elastic_measure.hip (spring strain, muscle groups, membrane areas; read-only on every solver array)
 // per elastic particle, device pointers, any of the four may be null; *bad: one device word of error flags (ids out of range)
@@ -660,9 +660,9 @@ int sphk_render_mesh(sph_solver* s, const RenderMeshArgs& a, const float* verts,
 // solver array). Device pointers.
 // records (SPH_FORCE_WORDS floats each, 16-byte aligned) of the sorted particles first .. first + n, or of list[0..n) if given
 int sphk_force_records(sph_solver* s, int first, int n, const int32_t* list, float* out);
-size_t sphk_force_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_FORCE_DIAG_WORDS records
-size_t sphk_force_terms_bytes(int chunks);                   // the staged per-particle terms of `chunks` chunks of 1024 particles
-// the particles go through `terms` in pieces of pieceChunks chunks; *records: where the records land (in scratch)
+#define FM_TERMS 48  // words 1..48 of a region record (word 0 counts the particles)
+// the particles go through `terms` (terms_bytes(FM_TERMS, pieceChunks), sph_tree.h) in pieces of pieceChunks chunks; scratch:
+// tree_scratch_doubles(N, a.count, SPH_FORCE_DIAG_WORDS); *records: where the records land (in scratch)
 int sphk_force_diagnostics(sph_solver* s, const DiagArgs& a, float* terms, int pieceChunks, double* scratch, double** records);
 // sph_wall.hip (what a set of boundary particles did to each particle in integrate, K7 and K12; read-only on every
 // solver array). Device pointers. mask: 1 bit per SORTED particle (sphk_wall_mask_bytes), null = every boundary particle;
@@ -672,8 +672,8 @@ int sphk_wall_mask_clear(sph_solver* s, uint32_t* mask);
 int sphk_wall_mask_add(sph_solver* s, const uint32_t* origIds, int count, uint32_t* mask);  // or-s the bits of backIndex[origIds[..]]
 // records (SPH_WALL_WORDS floats each, 16-byte aligned) of the sorted particles first .. first + n, or of list[0..n) if given
 int sphk_wall_records(sph_solver* s, const uint32_t* mask, bool inverted, int first, int n, const int32_t* list, float* out);
-size_t sphk_wall_diag_scratch_doubles(int N, int regions);  // partials of every tree level, then regions x SPH_WALL_DIAG_WORDS records
-size_t sphk_wall_terms_bytes(int chunks);                   // the staged per-particle terms of `chunks` chunks of 1024 particles
+#define WL_TERMS 26  // words 1..26 of a region record (word 0 counts the particles)
+// as sphk_force_diagnostics, with WL_TERMS and SPH_WALL_DIAG_WORDS
 int sphk_wall_diagnostics(sph_solver* s, const uint32_t* mask, bool inverted, const DiagArgs& a, float* terms, int pieceChunks,
                           double* scratch, double** records);
 // sph_surface.hip (marching cubes over a scalar lattice of P = dims[0]*dims[1]*dims[2] <= 2^31-1 points)

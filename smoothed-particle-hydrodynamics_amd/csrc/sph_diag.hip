@@ -12,16 +12,11 @@
 // (larger v2, then lower index)) and travel through the levels as exactly widened doubles.
 #include "sph_common.h"
 #include "sph_selector.h"  // the selection rule and the histogram's quantity
-#include "sph_tree.h"  // DIAG_CHUNK, diag_wave_sum, diag_block_reduce: shared with the elastic-matter reductions
+#include "sph_tree.h"  // the tree's layout (rows: the regions), the leaf's tail and the upper levels
 
 #include <algorithm>
 
 #define DIAG_SUMS 14  // record words 0..13
-
-// Partials of a level: part[(region * SPH_DIAG_WORDS + word) * chunks + chunk], so that the next level reads them coalesced.
-__device__ __forceinline__ size_t diag_at(int region, int word, int chunks, int chunk) {
-  return ((size_t)(region * SPH_DIAG_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
 
 // the 10 plain extremes of a record, in this order: words 16, 18, 23, 24, 25 (minima), then 17, 19, 26, 27, 28 (maxima)
 __device__ static const int kDiagMinWord[5] = {16, 18, 23, 24, 25};
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
           if (t == kDiagMinWord[k]) { x = (double)INFINITY; used = true; }
           if (t == kDiagMaxWord[k]) { x = -(double)INFINITY; used = true; }
         }
-        if (used) part[diag_at(r, t, chunks, chunk)] = x;
+        if (used) part[tree_at(SPH_DIAG_WORDS, r, t, chunks, chunk)] = x;
       }
       continue;
     }
@@ -134,113 +129,54 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
       shv[wave] = bestV; shi[wave] = bestI;
     }
     __syncthreads();
-    // stride 128
-    if (t < 128) {
-#pragma unroll
-      for (int w = 0; w < DIAG_SUMS; w++) sh[w][t] = sh[w][t] + sh[w][t + 128];
-    }
-    __syncthreads();
-    // stride 64 and the in-wave strides: the 14 words are shared out among the four waves
-    for (int w = wave; w < DIAG_SUMS; w += 4) {
-      const double x = diag_wave_sum(sh[w][lane] + sh[w][lane + 64]);
-      if (lane == 0) part[diag_at(r, w, chunks, chunk)] = x;
-    }
+    // strides 128, 64 and the in-wave strides: the 14 words are shared out among the four waves
+    tree_group_sums<DIAG_SUMS>(sh, DIAG_SUMS, [&](int w, double x) { part[tree_at(SPH_DIAG_WORDS, r, w, chunks, chunk)] = x; });
     if (t < 10) {
       float x = shx[0][t];
       for (int q = 1; q < 4; q++) { const float o = shx[q][t]; x = t < 5 ? (o < x ? o : x) : (o > x ? o : x); }
-      part[diag_at(r, t < 5 ? kDiagMinWord[t] : kDiagMaxWord[t - 5], chunks, chunk)] = (double)x;
+      part[tree_at(SPH_DIAG_WORDS, r, t < 5 ? kDiagMinWord[t] : kDiagMaxWord[t - 5], chunks, chunk)] = (double)x;
     } else if (t == 10) {
       float bv = shv[0]; int bi = shi[0];
       for (int q = 1; q < 4; q++) if (shv[q] > bv || (shv[q] == bv && shi[q] < bi)) { bv = shv[q]; bi = shi[q]; }
-      part[diag_at(r, 20, chunks, chunk)] = (double)bv;
-      part[diag_at(r, 21, chunks, chunk)] = (double)bi;
+      part[tree_at(SPH_DIAG_WORDS, r, 20, chunks, chunk)] = (double)bv;
+      part[tree_at(SPH_DIAG_WORDS, r, 21, chunks, chunk)] = (double)bi;
     }
     __syncthreads();  // sh / shx are reused by the next region
-  }
-}
-
-// ---- upper levels: `nIn` partials per word and region -> ceil(nIn / 1024); the same tree (tiny launches) ------------------------
-// One block per output chunk, region and job: jobs 0..13 the sums, 14..18 the minima, 19..23 the maxima, 24 the pair.
-#define DIAG_UPPER_JOBS 25
-__global__ __launch_bounds__(SPH_BLOCK) void k_diag_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {
-  __shared__ double sh[SPH_BLOCK];
-  __shared__ double shI[SPH_BLOCK];
-  const int t = threadIdx.x, chunk = blockIdx.x, r = blockIdx.y, job = blockIdx.z;
-  if (job < DIAG_SUMS) {
-    const double x = diag_block_reduce<DIAG_OP_SUM>(in + diag_at(r, job, nIn, 0), nIn, chunk, 0.0, sh);
-    if (t == 0) out[diag_at(r, job, nOut, chunk)] = x;
-  } else if (job < DIAG_SUMS + 5) {
-    const int w = kDiagMinWord[job - DIAG_SUMS];
-    const double x = diag_block_reduce<DIAG_OP_MIN>(in + diag_at(r, w, nIn, 0), nIn, chunk, (double)INFINITY, sh);
-    if (t == 0) out[diag_at(r, w, nOut, chunk)] = x;
-  } else if (job < DIAG_SUMS + 10) {
-    const int w = kDiagMaxWord[job - DIAG_SUMS - 5];
-    const double x = diag_block_reduce<DIAG_OP_MAX>(in + diag_at(r, w, nIn, 0), nIn, chunk, -(double)INFINITY, sh);
-    if (t == 0) out[diag_at(r, w, nOut, chunk)] = x;
-  } else {  // the pair (max v2, lowest index that attains it)
-    double bv = -(double)INFINITY, bi = 2147483647.0;
-    for (int k = 0; k < 4; k++) {
-      const int i = chunk * DIAG_CHUNK + k * SPH_BLOCK + t;
-      if (i >= nIn) continue;
-      const double ov = in[diag_at(r, 20, nIn, i)], oi = in[diag_at(r, 21, nIn, i)];
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    sh[t] = bv; shI[t] = bi;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-      if (t < s && (sh[t + s] > sh[t] || (sh[t + s] == sh[t] && shI[t + s] < shI[t]))) { sh[t] = sh[t + s]; shI[t] = shI[t + s]; }
-      __syncthreads();
-    }
-    if (t == 0) { out[diag_at(r, 20, nOut, chunk)] = sh[0]; out[diag_at(r, 21, nOut, chunk)] = shI[0]; }
   }
 }
 
 // ---- the records: canonical extremes (+ 0.0f), the empty-selection rule, the original id of the fastest particle ------------
 __global__ void k_diag_final(SphDev d, const double* __restrict__ top /* one chunk per word */, double* __restrict__ out) {
   const int r = blockIdx.x, w = threadIdx.x;  // SPH_DIAG_WORDS threads
-  const double n = top[diag_at(r, 0, 1, 0)];
+  const double n = top[tree_at(SPH_DIAG_WORDS, r, 0, 1, 0)];
   double x = 0.0;
-  if (w < DIAG_SUMS) x = top[diag_at(r, w, 1, 0)];
+  if (w < DIAG_SUMS) x = top[tree_at(SPH_DIAG_WORDS, r, w, 1, 0)];
   else if (w == 21 || w == 22) {
     x = -1.0;
     if (n > 0.0) {
-      const int idx = (int)top[diag_at(r, 21, 1, 0)];
+      const int idx = (int)top[tree_at(SPH_DIAG_WORDS, r, 21, 1, 0)];
       if (idx < d.N) x = w == 21 ? (double)idx : (double)d.vals[idx];  // (no index when every selected v2 is NaN)
     }
   } else if ((w >= 16 && w <= 20) || (w >= 23 && w <= 28)) {
-    if (n > 0.0) x = (double)((float)top[diag_at(r, w, 1, 0)] + 0.0f);
+    if (n > 0.0) x = (double)((float)top[tree_at(SPH_DIAG_WORDS, r, w, 1, 0)] + 0.0f);
   }
   out[r * SPH_DIAG_WORDS + w] = x;
 }
 
-size_t sphk_diag_scratch_doubles(int N, int regions) {
-  size_t total = 0;
-  for (int n = N;;) {
-    const int c = n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1;
-    total += (size_t)c;
-    if (c == 1) break;
-    n = c;
-  }
-  return (total + 1) * (size_t)regions * SPH_DIAG_WORDS;  // the levels' partials, then the records
-}
-
 int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records) {
-  const int R = a.count;
-  int n = s->d.N;
-  int chunks = n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1;
-  double* cur = scratch;
-  if (a.labels) hipLaunchKernelGGL(k_diag_leaf<true>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
-  else hipLaunchKernelGGL(k_diag_leaf<false>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, cur, chunks);
+  const int R = a.count, chunks = tree_chunks(s->d.N);
+  if (a.labels) hipLaunchKernelGGL(k_diag_leaf<true>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, scratch, chunks);
+  else hipLaunchKernelGGL(k_diag_leaf<false>, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, scratch, chunks);
   SPH_HIP(hipGetLastError());
-  while (chunks > 1) {
-    const int nOut = (chunks + DIAG_CHUNK - 1) / DIAG_CHUNK;
-    double* next = cur + (size_t)R * SPH_DIAG_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_diag_upper, dim3(nOut, R, DIAG_UPPER_JOBS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  double* out = cur + (size_t)R * SPH_DIAG_WORDS;
-  hipLaunchKernelGGL(k_diag_final, dim3(R), dim3(SPH_DIAG_WORDS), 0, s->stream, s->d, (const double*)cur, out);
+  // upper levels: the sums, the minima and the maxima (kDiagMinWord, kDiagMaxWord), the pair (max v2, lowest index) in words 20, 21
+  TreeShape S = tree_shape(SPH_DIAG_WORDS, DIAG_SUMS);
+  for (int w : {16, 18, 23, 24, 25}) tree_shape_add(S, w, DIAG_OP_MIN);
+  for (int w : {17, 19, 26, 27, 28}) tree_shape_add(S, w, DIAG_OP_MAX);
+  tree_shape_add(S, 20, DIAG_OP_PAIR);
+  double *top = nullptr, *out = nullptr;
+  const int rc = sphk_tree_upper(s, S, R, scratch, chunks, &top, &out);
+  if (rc != SPH_OK) return rc;
+  hipLaunchKernelGGL(k_diag_final, dim3(R), dim3(SPH_DIAG_WORDS), 0, s->stream, s->d, (const double*)top, out);
   SPH_HIP(hipGetLastError());
   *records = out;
   return SPH_OK;

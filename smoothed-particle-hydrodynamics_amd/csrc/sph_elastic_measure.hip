@@ -17,15 +17,11 @@
 
 #define EM_ROWS (SPH_BLOCK / 32)  // rows of the connection table per block
 #define EM_SUMS 12
-#define EM_JOBS (EM_SUMS + 2)     // the sums, then the minimum and the maximum
 
 // record words that are tree sums, in the order of the leaf's LDS rows; words 7 and 8 are the extremes, 1 and 15 are constants
 __device__ static const int kEmSumWord[EM_SUMS] = {0, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 14};
 
-// partials of a level: part[(group * SPH_MUSCLE_WORDS + word) * chunks + chunk], read coalesced by the next level
-__device__ __forceinline__ size_t em_at(int group, int word, int chunks, int chunk) {
-  return ((size_t)(group * SPH_MUSCLE_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
+// (the rows of the tree are the groups, SPH_MUSCLE_WORDS words each)
 
 // One slot of the connection table as the contract defines it. v = (x_i - x_j) * simScale; r, dr, e in float, in k_elastic's
 // order; m = 0 for "no muscle group".
@@ -202,85 +198,46 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_muscle_leaf(SphDev d, double* __r
       }
       if (lane == 0) { shx[wave][0] = mn; shx[wave][1] = mx; }
       __syncthreads();
-      if (t < 128) {
-#pragma unroll
-        for (int w = 0; w < EM_SUMS; w++) sh[w][t] = sh[w][t] + sh[w][t + 128];
-      }
-      __syncthreads();
-      for (int w = wave; w < EM_SUMS; w += 4) {
-        const double x = diag_wave_sum(sh[w][lane] + sh[w][lane + 64]);
-        if (lane == 0) part[em_at(g, kEmSumWord[w], chunks, chunk)] = x;
-      }
+      tree_group_sums<EM_SUMS>(sh, EM_SUMS, [&](int w, double x) { part[tree_at(SPH_MUSCLE_WORDS, g, kEmSumWord[w], chunks, chunk)] = x; });
       if (t < 2) {
         float x = shx[0][t];
         for (int q = 1; q < 4; q++) { const float o = shx[q][t]; x = t == 0 ? (o < x ? o : x) : (o > x ? o : x); }
-        part[em_at(g, 7 + t, chunks, chunk)] = (double)x;
+        part[tree_at(SPH_MUSCLE_WORDS, g, 7 + t, chunks, chunk)] = (double)x;
       }
       __syncthreads();  // sh / shx are reused by the next group
     }
   }
 }
 
-// Upper levels: `nIn` partials per group and word -> ceil(nIn / 1024), the same tree. One block per output chunk, group and job.
-__global__ __launch_bounds__(SPH_BLOCK) void k_muscle_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {
-  __shared__ double sh[SPH_BLOCK];
-  const int chunk = blockIdx.x, g = blockIdx.y, job = blockIdx.z;
-  double x;
-  int w;
-  if (job < EM_SUMS) { w = kEmSumWord[job]; x = diag_block_reduce<DIAG_OP_SUM>(in + em_at(g, w, nIn, 0), nIn, chunk, 0.0, sh); }
-  else if (job == EM_SUMS) { w = 7; x = diag_block_reduce<DIAG_OP_MIN>(in + em_at(g, w, nIn, 0), nIn, chunk, (double)INFINITY, sh); }
-  else { w = 8; x = diag_block_reduce<DIAG_OP_MAX>(in + em_at(g, w, nIn, 0), nIn, chunk, -(double)INFINITY, sh); }
-  if (threadIdx.x == 0) out[em_at(g, w, nOut, chunk)] = x;
-}
-
 // The records: the signal, canonical extremes (+ 0.0f), the empty-group rule; the error flags ride behind the last record.
 __global__ void k_muscle_final(SphDev d, const double* __restrict__ top /* one chunk per word */, const uint32_t* __restrict__ bad,
                                double* __restrict__ out) {
   const int g = blockIdx.x, w = threadIdx.x;  // SPH_MUSCLE_WORDS threads
-  const double n = top[em_at(g, 0, 1, 0)];
+  const double n = top[tree_at(SPH_MUSCLE_WORDS, g, 0, 1, 0)];
   double x = 0.0;
   if (w == 1) x = g > 0 ? (double)d.muscle[g - 1] : 0.0;
-  else if (w == 7 || w == 8) { if (n > 0.0) x = (double)((float)top[em_at(g, w, 1, 0)] + 0.0f); }
-  else if (w != 15) x = top[em_at(g, w, 1, 0)];
+  else if (w == 7 || w == 8) { if (n > 0.0) x = (double)((float)top[tree_at(SPH_MUSCLE_WORDS, g, w, 1, 0)] + 0.0f); }
+  else if (w != 15) x = top[tree_at(SPH_MUSCLE_WORDS, g, w, 1, 0)];
   out[(size_t)g * SPH_MUSCLE_WORDS + w] = x;
   if (g == 0 && w == 0) out[(size_t)gridDim.x * SPH_MUSCLE_WORDS] = (double)*bad;
 }
 
-static int em_chunks(long long terms) { return terms > 0 ? (int)((terms + DIAG_CHUNK - 1) / DIAG_CHUNK) : 1; }
+// doubles of the scratch of a call: the levels, the records with the copy of the error flags behind them, the flags' own cell
+size_t sphk_group_tree_doubles(long long terms, int groups) { return tree_scratch_doubles(terms, groups, SPH_MUSCLE_WORDS) + 2; }
 
-// doubles of every level of a tree over `terms` terms for `groups` groups
-static size_t em_level_doubles(long long terms, int groups) {
-  size_t total = 0;
-  for (int c = em_chunks(terms);; c = em_chunks(c)) {
-    total += (size_t)c;
-    if (c == 1) break;
-  }
-  return total * (size_t)groups * SPH_MUSCLE_WORDS;
-}
-
-// ... and of the scratch of a call: the levels, the records with the copy of the error flags behind them, the flags' own cell
-size_t sphk_group_tree_doubles(long long terms, int groups) {
-  return em_level_doubles(terms, groups) + (size_t)groups * SPH_MUSCLE_WORDS + 2;
-}
-
-// levels above `cur` (chunks partials per group and word) until one chunk is left; *top: where that level lies, *end: behind it
+// levels above `cur` (chunks partials per group and word) until one chunk is left: the sums of kEmSumWord, the minimum in word 7
+// and the maximum in word 8; *top: where that level lies, *end: behind it
 static int em_upper_levels(sph_solver* s, int groups, double* cur, int chunks, double** top, double** end) {
-  while (chunks > 1) {
-    const int nOut = em_chunks(chunks);
-    double* next = cur + (size_t)groups * SPH_MUSCLE_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_muscle_upper, dim3(nOut, groups, EM_JOBS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  *top = cur;
-  *end = cur + (size_t)groups * SPH_MUSCLE_WORDS;
-  return SPH_OK;
+  TreeShape S = tree_shape(SPH_MUSCLE_WORDS, 0);
+  for (int w = 0; w < 15; w++)
+    if (w != 1) tree_shape_add(S, w, w == 7 ? DIAG_OP_MIN : w == 8 ? DIAG_OP_MAX : DIAG_OP_SUM);
+  return sphk_tree_upper(s, S, groups, cur, chunks, top, end);
 }
 
 int sphk_muscle_diagnostics(sph_solver* s, double* scratch, double** records) {
   const int groups = s->d.muscleCount + 1;
   const long long terms = (long long)s->d.numElastic * SPH_MAXN;
-  const int chunks = em_chunks(terms);
+  const int chunks = tree_chunks(terms);
   uint32_t* bad = (uint32_t*)(scratch + sphk_group_tree_doubles(terms, groups) - 1);
   SPH_HIP(hipMemsetAsync(bad, 0, sizeof(double), s->stream));
   const size_t total = (size_t)groups * SPH_MUSCLE_WORDS * (size_t)chunks;
@@ -346,25 +303,21 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_membrane_measure(SphDev d, float4
   }
   if (lane == 0) { shx[wave][0] = mn; shx[wave][1] = mx; }
   __syncthreads();
-  if (t < 128) { sh[0][t] = sh[0][t] + sh[0][t + 128]; sh[1][t] = sh[1][t] + sh[1][t + 128]; }
-  __syncthreads();
-  if (wave < 2) {
-    const double x = diag_wave_sum(sh[wave][lane] + sh[wave][lane + 64]);
-    if (lane == 0) part[em_at(0, wave == 0 ? 0 : 2, chunks, chunk)] = x;
-  } else if (wave == 2 && lane < 2) {
+  tree_group_sums<2>(sh, 2, [&](int k, double x) { part[tree_at(SPH_MUSCLE_WORDS, 0, k == 0 ? 0 : 2, chunks, chunk)] = x; });  // waves 0, 1
+  if (wave == 2 && lane < 2) {
     float x = shx[0][lane];
     for (int k = 1; k < 4; k++) { const float o = shx[k][lane]; x = lane == 0 ? (o < x ? o : x) : (o > x ? o : x); }
-    part[em_at(0, 7 + lane, chunks, chunk)] = (double)x;
+    part[tree_at(SPH_MUSCLE_WORDS, 0, 7 + lane, chunks, chunk)] = (double)x;
   } else if (wave == 3 && lane < SPH_MUSCLE_WORDS && lane != 0 && lane != 2 && lane != 7 && lane != 8) {
-    part[em_at(0, lane, chunks, chunk)] = 0.0;  // the sum words the shared upper level reads and this table does not use
+    part[tree_at(SPH_MUSCLE_WORDS, 0, lane, chunks, chunk)] = 0.0;  // the sum words the shared upper level reads and this table does not use
   }
 }
 
 // *top: 16 doubles (word 0 count, 2 area sum, 7 min, 8 max), directly followed by one 8-byte cell whose low word holds the error
 // flags, so that one copy brings both to the host
 int sphk_membrane_measure(sph_solver* s, float* out, double* scratch, double** top) {
-  const int chunks = em_chunks(s->d.numMembranes);
-  uint32_t* bad = (uint32_t*)(scratch + em_level_doubles(s->d.numMembranes, 1));
+  const int chunks = tree_chunks(s->d.numMembranes);
+  uint32_t* bad = (uint32_t*)(scratch + tree_level_chunks(s->d.numMembranes) * SPH_MUSCLE_WORDS);  // behind the levels of one group
   SPH_HIP(hipMemsetAsync(bad, 0, sizeof(double), s->stream));
   hipLaunchKernelGGL(k_membrane_measure, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, (float4*)out, scratch, chunks, bad);
   SPH_HIP(hipGetLastError());

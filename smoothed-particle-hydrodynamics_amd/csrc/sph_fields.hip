@@ -213,11 +213,7 @@ int sphk_field_fill(sph_solver* s, float* field, int first, int n, float value) 
 }
 
 // ---- region records -------------------------------------------------------------------------------------------------------------
-// Partials of a level: part[(region * SPH_FIELD_DIAG_WORDS + word) * chunks + chunk], read coalesced by the next level.
-__device__ __forceinline__ size_t fd_at(int region, int word, int chunks, int chunk) {
-  return ((size_t)(region * SPH_FIELD_DIAG_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
-
+// The rows of the tree (sph_tree.h) are the regions, SPH_FIELD_DIAG_WORDS words each.
 // Level 0, one block per chunk of 1024 particles in k_diag_leaf's layout: thread t holds elements t, t + 256, t + 512, t + 768
 // (strides 512 and 256 in registers), 128 and 64 through LDS, 32 ... 1 inside a wave. Words: 0 n, 1 sum c, 2 sum c*c (the product
 // in double), 3 min, 4 max (float compares, travelling as exactly widened doubles), 5 the selected particles with c != 0.
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_field_leaf(SphDev d, DiagArgs a, 
     for (int e = 0; e < 4; e++) sel[e] = ok[e] && sph_box_holds(x0, y0, z0, x1, y1, z1, px[e], py[e], pz[e]);
     // no particle of this chunk in the region: every sum of +0.0 terms is +0.0 and every extreme keeps its identity
     if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
-      if (t < FIELD_SUMS) part[fd_at(r, t, chunks, chunk)] = t == 3 ? (double)INFINITY : t == 4 ? -(double)INFINITY : 0.0;
+      if (t < FIELD_SUMS) part[tree_at(SPH_FIELD_DIAG_WORDS, r, t, chunks, chunk)] = t == 3 ? (double)INFINITY : t == 4 ? -(double)INFINITY : 0.0;
       continue;
     }
     double q[4][4];
@@ -272,72 +268,39 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_field_leaf(SphDev d, DiagArgs a, 
     }
     if (lane == 0) { shx[wave][0] = mn; shx[wave][1] = mx; }
     __syncthreads();
-    if (t < 128) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) sh[k][t] = sh[k][t] + sh[k][t + 128];
-    }
-    __syncthreads();
-    {  // stride 64 and the in-wave strides: one word per wave
-      const double x = diag_wave_sum(sh[wave][lane] + sh[wave][lane + 64]);
-      if (lane == 0) part[fd_at(r, wave < 3 ? wave : 5, chunks, chunk)] = x;
-    }
+    // strides 128, 64 and the in-wave strides: one word per wave
+    tree_group_sums<4>(sh, 4, [&](int k, double x) { part[tree_at(SPH_FIELD_DIAG_WORDS, r, k < 3 ? k : 5, chunks, chunk)] = x; });
     if (t < 2) {
       float x = shx[0][t];
       for (int w = 1; w < 4; w++) { const float o = shx[w][t]; x = t == 0 ? (o < x ? o : x) : (o > x ? o : x); }
-      part[fd_at(r, 3 + t, chunks, chunk)] = (double)x;
+      part[tree_at(SPH_FIELD_DIAG_WORDS, r, 3 + t, chunks, chunk)] = (double)x;
     }
     __syncthreads();  // sh / shx are reused by the next region
   }
 }
 
-// Upper levels: `nIn` partials per word and region -> ceil(nIn / 1024), the same tree. One block per output chunk, region and word.
-__global__ __launch_bounds__(SPH_BLOCK) void k_field_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {
-  __shared__ double sh[SPH_BLOCK];
-  const int chunk = blockIdx.x, r = blockIdx.y, w = blockIdx.z;
-  const double* src = in + fd_at(r, w, nIn, 0);
-  double x;
-  if (w == 3) x = diag_block_reduce<DIAG_OP_MIN>(src, nIn, chunk, (double)INFINITY, sh);
-  else if (w == 4) x = diag_block_reduce<DIAG_OP_MAX>(src, nIn, chunk, -(double)INFINITY, sh);
-  else x = diag_block_reduce<DIAG_OP_SUM>(src, nIn, chunk, 0.0, sh);
-  if (threadIdx.x == 0) out[fd_at(r, w, nOut, chunk)] = x;
-}
-
 // the records: canonical extremes (+ 0.0f) and the empty-selection rule
 __global__ void k_field_final(const double* __restrict__ top /* one chunk per word */, double* __restrict__ out) {
   const int r = blockIdx.x, w = threadIdx.x;  // SPH_FIELD_DIAG_WORDS threads
-  const double n = top[fd_at(r, 0, 1, 0)];
+  const double n = top[tree_at(SPH_FIELD_DIAG_WORDS, r, 0, 1, 0)];
   double x = 0.0;
-  if (w < 3 || w == 5) x = top[fd_at(r, w, 1, 0)];
-  else if (w < 5 && n > 0.0) x = (double)((float)top[fd_at(r, w, 1, 0)] + 0.0f);
+  if (w < 3 || w == 5) x = top[tree_at(SPH_FIELD_DIAG_WORDS, r, w, 1, 0)];
+  else if (w < 5 && n > 0.0) x = (double)((float)top[tree_at(SPH_FIELD_DIAG_WORDS, r, w, 1, 0)] + 0.0f);
   out[r * SPH_FIELD_DIAG_WORDS + w] = x;
 }
 
-static int fd_chunks(int n) { return n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1; }
-
-size_t sphk_field_diag_scratch_doubles(int N, int regions) {
-  size_t total = 0;
-  for (int c = fd_chunks(N);; c = fd_chunks(c)) {
-    total += (size_t)c;
-    if (c == 1) break;
-  }
-  return (total + 1) * (size_t)regions * SPH_FIELD_DIAG_WORDS;  // the levels' partials, then the records
-}
-
 int sphk_field_diagnostics(sph_solver* s, const float* field, const DiagArgs& a, double* scratch, double** records) {
-  const int R = a.count;
-  int chunks = fd_chunks(s->d.N);
-  double* cur = scratch;
-  hipLaunchKernelGGL(k_field_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, field, cur, chunks);
+  const int R = a.count, chunks = tree_chunks(s->d.N);
+  hipLaunchKernelGGL(k_field_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, a, field, scratch, chunks);
   SPH_HIP(hipGetLastError());
-  while (chunks > 1) {
-    const int nOut = fd_chunks(chunks);
-    double* next = cur + (size_t)R * SPH_FIELD_DIAG_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_field_upper, dim3(nOut, R, FIELD_SUMS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  double* out = cur + (size_t)R * SPH_FIELD_DIAG_WORDS;
-  hipLaunchKernelGGL(k_field_final, dim3(R), dim3(SPH_FIELD_DIAG_WORDS), 0, s->stream, (const double*)cur, out);
+  TreeShape S = tree_shape(SPH_FIELD_DIAG_WORDS, 3);  // words 0..2 sums, then 3 min, 4 max, 5 a sum
+  tree_shape_add(S, 3, DIAG_OP_MIN);
+  tree_shape_add(S, 4, DIAG_OP_MAX);
+  tree_shape_add(S, 5, DIAG_OP_SUM);
+  double *top = nullptr, *out = nullptr;
+  const int rc = sphk_tree_upper(s, S, R, scratch, chunks, &top, &out);
+  if (rc != SPH_OK) return rc;
+  hipLaunchKernelGGL(k_field_final, dim3(R), dim3(SPH_FIELD_DIAG_WORDS), 0, s->stream, (const double*)top, out);
   SPH_HIP(hipGetLastError());
   *records = out;
   return SPH_OK;

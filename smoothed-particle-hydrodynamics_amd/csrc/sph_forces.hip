@@ -17,16 +17,11 @@
 // tree of sph_tree.h. No floating-point atomics.
 #include "sph_common.h"
 #include "sph_row_batch.h"  // FmRow: a row in groups of four slots
-#include "sph_selector.h"  // the selection rule of the region totals
-#include "sph_tree.h"
-
-#include <algorithm>
+#include "sph_terms.h"  // the records' way out through LDS; leaf, tree and final of the region totals
 
 #define FM_BATCH 8
-#define FM_LDS_STRIDE (SPH_FORCE_WORDS + 1)  // 41 words: lane-strided ds_write_b32 without bank conflicts
-#define FM_TERMS 48                          // words 1..48 of a region record (word 0 counts the particles)
-#define FM_SUMS (FM_TERMS + 1)
-#define FM_GROUP 7                           // record words reduced together by the leaf: 49 = 7 x 7
+#define FM_SUMS (FM_TERMS + 1)  // word 0 counts the particles, words 1..48 are the terms
+#define FM_GROUP 7              // record words reduced together by the leaf: 49 = 7 x 7
 
 enum { FM_RECORDS = 0, FM_TERMS_OUT = 1 };
 
@@ -141,9 +136,8 @@ __device__ __forceinline__ void fm_record(const SphDev& d, int id, float (&rec)[
 template <int OUT, bool LIST>
 __global__ __launch_bounds__(SPH_BLOCK) void k_force_records(SphDev d, int first, int n, const int32_t* __restrict__ list,
                                                              float* __restrict__ out, size_t stride) {
-  __shared__ float sm[OUT == FM_RECORDS ? SPH_BLOCK * FM_LDS_STRIDE : 1];
-  const int t = threadIdx.x;
-  const int r = blockIdx.x * SPH_BLOCK + t;
+  __shared__ float sm[OUT == FM_RECORDS ? SPH_BLOCK * (SPH_FORCE_WORDS + 1) : 1];
+  const int r = blockIdx.x * SPH_BLOCK + threadIdx.x;
   int id = -1;
   if (r < n) id = LIST ? list[r] : first + r;
   const bool active = id >= 0 && id < d.N;  // (a list entry outside 0..N-1 would be a defect of the selection: never followed)
@@ -154,18 +148,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_force_records(SphDev d, int first
 #pragma unroll
     for (int w = 0; w < SPH_FORCE_WORDS; w++) rec[w] = 0.f;
   }
-  if (OUT == FM_RECORDS) {
-#pragma unroll
-    for (int w = 0; w < SPH_FORCE_WORDS; w++) sm[t * FM_LDS_STRIDE + w] = rec[w];
-    __syncthreads();
-    const int rows = min(SPH_BLOCK, n - blockIdx.x * SPH_BLOCK);  // records of this block
-    float4* dst = reinterpret_cast<float4*>(out + (size_t)blockIdx.x * SPH_BLOCK * SPH_FORCE_WORDS);
-    const int quads = rows * (SPH_FORCE_WORDS / 4);
-    for (int q = t; q < quads; q += SPH_BLOCK) {
-      const float* src = sm + (q / (SPH_FORCE_WORDS / 4)) * FM_LDS_STRIDE + 4 * (q % (SPH_FORCE_WORDS / 4));
-      dst[q] = make_float4(src[0], src[1], src[2], src[3]);
-    }
-  } else {
+  if (OUT == FM_RECORDS) records_through_lds(rec, sm, n, out);
+  else {
     if (r >= n) return;
     float* o = out + (size_t)r;
 #pragma unroll
@@ -194,126 +178,11 @@ int sphk_force_records(sph_solver* s, int first, int n, const int32_t* list, flo
   return SPH_OK;
 }
 
-// ---- region totals ----------------------------------------------------------------------------------------------------------
-// Partials of a level: part[(region * SPH_FORCE_DIAG_WORDS + word) * chunks + chunk], read coalesced by the next level.
-__device__ __forceinline__ size_t fm_at(int region, int word, int chunks, int chunk) {
-  return ((size_t)(region * SPH_FORCE_DIAG_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
-
-// Level 0 for the chunks [firstChunk, firstChunk + gridDim.x) whose terms lie at `terms` (word-major, `stride` particles per
-// word, particle firstChunk * 1024 first). One block per chunk of 1024 particles in k_diag_leaf's layout: thread t holds
-// elements t, t + 256, t + 512, t + 768 (strides 512 and 256 in registers), 128 and 64 through LDS, 32 ... 1 inside a wave.
-// The words go through in groups of FM_GROUP, so that a term is read once whatever the number of regions.
-__global__ __launch_bounds__(SPH_BLOCK) void k_force_leaf(SphDev d, DiagArgs a, const float* __restrict__ terms, size_t stride,
-                                                          int firstChunk, double* __restrict__ part, int chunks) {
-  __shared__ double sh[FM_GROUP][SPH_BLOCK];
-  const int t = threadIdx.x, chunk = firstChunk + blockIdx.x, lane = t & 63, wave = t >> 6;
-  float px[4], py[4], pz[4];
-  bool ok[4];
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    const int j = chunk * DIAG_CHUNK + e * SPH_BLOCK + t;
-    ok[e] = false;
-    px[e] = py[e] = pz[e] = 0.f;
-    if (j < d.N) {
-      const float4 p = d.sortedPos[j];
-      ok[e] = sph_type_key_selected(d, a.typeMask, j, p);
-      px[e] = p.x; py[e] = p.y; pz[e] = p.z;
-    }
-  }
-  for (int g = 0; g < FM_SUMS / FM_GROUP; g++) {
-    float f[4][FM_GROUP];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const int j = chunk * DIAG_CHUNK + e * SPH_BLOCK + t;
-      const size_t at = (size_t)(blockIdx.x * DIAG_CHUNK + e * SPH_BLOCK + t);
-#pragma unroll
-      for (int k = 0; k < FM_GROUP; k++) {
-        const int w = g * FM_GROUP + k;  // record word; word 0 counts
-        f[e][k] = w == 0 ? 1.0f : (j < d.N ? terms[(size_t)(w - 1) * stride + at] : 0.f);
-      }
-    }
-    for (int r = 0; r < a.count; r++) {
-      const float x0 = a.box[r][0], y0 = a.box[r][1], z0 = a.box[r][2], x1 = a.box[r][3], y1 = a.box[r][4], z1 = a.box[r][5];
-      bool sel[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) sel[e] = ok[e] && sph_box_holds(x0, y0, z0, x1, y1, z1, px[e], py[e], pz[e]);
-      // no particle of this chunk in the region: every sum of +0.0 terms is +0.0, which is what the tree below would produce
-      if (!__syncthreads_or(sel[0] || sel[1] || sel[2] || sel[3])) {
-        if (t < FM_GROUP) part[fm_at(r, g * FM_GROUP + t, chunks, chunk)] = 0.0;
-        continue;
-      }
-#pragma unroll
-      for (int k = 0; k < FM_GROUP; k++) {
-        double q[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) q[e] = sel[e] ? (double)f[e][k] : 0.0;
-        sh[k][t] = (q[0] + q[2]) + (q[1] + q[3]);
-      }
-      __syncthreads();
-      if (t < 128) {
-#pragma unroll
-        for (int k = 0; k < FM_GROUP; k++) sh[k][t] = sh[k][t] + sh[k][t + 128];
-      }
-      __syncthreads();
-      for (int k = wave; k < FM_GROUP; k += 4) {
-        const double x = diag_wave_sum(sh[k][lane] + sh[k][lane + 64]);
-        if (lane == 0) part[fm_at(r, g * FM_GROUP + k, chunks, chunk)] = x;
-      }
-      __syncthreads();  // sh is reused by the next region
-    }
-  }
-}
-
-// Upper levels: `nIn` partials per word and region -> ceil(nIn / 1024), the same tree. One block per output chunk, region and word.
-__global__ __launch_bounds__(SPH_BLOCK) void k_force_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut) {
-  __shared__ double sh[SPH_BLOCK];
-  const int chunk = blockIdx.x, r = blockIdx.y, w = blockIdx.z;
-  const double x = diag_block_reduce<DIAG_OP_SUM>(in + fm_at(r, w, nIn, 0), nIn, chunk, 0.0, sh);
-  if (threadIdx.x == 0) out[fm_at(r, w, nOut, chunk)] = x;
-}
-
-__global__ void k_force_final(const double* __restrict__ top /* one chunk per word */, double* __restrict__ out) {
-  const int r = blockIdx.x, w = threadIdx.x;  // SPH_FORCE_DIAG_WORDS threads
-  out[r * SPH_FORCE_DIAG_WORDS + w] = w < FM_SUMS ? top[fm_at(r, w, 1, 0)] : 0.0;
-}
-
-static int fm_chunks(int n) { return n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1; }
-
-size_t sphk_force_diag_scratch_doubles(int N, int regions) {
-  size_t total = 0;
-  for (int c = fm_chunks(N);; c = fm_chunks(c)) {
-    total += (size_t)c;
-    if (c == 1) break;
-  }
-  return (total + 1) * (size_t)regions * SPH_FORCE_DIAG_WORDS;  // the levels' partials, then the records
-}
-
-size_t sphk_force_terms_bytes(int chunks) { return sizeof(float) * FM_TERMS * DIAG_CHUNK * (size_t)chunks; }
-
+// ---- region totals: 49 sums in seven groups of seven (sph_terms.h) ---------------------------------------------------------------
 int sphk_force_diagnostics(sph_solver* s, const DiagArgs& a, float* terms, int pieceChunks, double* scratch, double** records) {
-  const int R = a.count, N = s->d.N;
-  int chunks = fm_chunks(N);
-  double* cur = scratch;
-  const size_t stride = (size_t)pieceChunks * DIAG_CHUNK;
-  for (int c0 = 0; c0 < chunks; c0 += pieceChunks) {
-    const int nC = std::min(pieceChunks, chunks - c0);
-    const int first = c0 * DIAG_CHUNK, n = std::min(nC * DIAG_CHUNK, N - first);
-    if (n > 0) hipLaunchKernelGGL((k_force_records<FM_TERMS_OUT, false>), dim3(sph_blocks(n)), dim3(SPH_BLOCK), 0, s->stream, s->d, first, n,
-                                  (const int32_t*)nullptr, terms, stride);
-    hipLaunchKernelGGL(k_force_leaf, dim3(nC), dim3(SPH_BLOCK), 0, s->stream, s->d, a, (const float*)terms, stride, c0, cur, chunks);
-    SPH_HIP(hipGetLastError());
-  }
-  while (chunks > 1) {
-    const int nOut = fm_chunks(chunks);
-    double* next = cur + (size_t)R * SPH_FORCE_DIAG_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_force_upper, dim3(nOut, R, FM_SUMS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next, nOut);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  double* out = cur + (size_t)R * SPH_FORCE_DIAG_WORDS;
-  hipLaunchKernelGGL(k_force_final, dim3(R), dim3(SPH_FORCE_DIAG_WORDS), 0, s->stream, (const double*)cur, out);
-  SPH_HIP(hipGetLastError());
-  *records = out;
-  return SPH_OK;
+  return sphk_terms_diagnostics<SPH_FORCE_DIAG_WORDS, FM_SUMS, FM_GROUP>(
+      s, a, terms, pieceChunks, scratch, records, [&](int first, int n, float* out, size_t stride) {
+        hipLaunchKernelGGL((k_force_records<FM_TERMS_OUT, false>), dim3(sph_blocks(n)), dim3(SPH_BLOCK), 0, s->stream, s->d, first, n,
+                           (const int32_t*)nullptr, out, stride);
+      });
 }

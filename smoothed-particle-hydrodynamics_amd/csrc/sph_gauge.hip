@@ -10,7 +10,7 @@
 //                   LDS word and reduces, in the fixed tree of sph_tree.h from registers through LDS, only the (gauge, direction)
 //                   pairs present: velocity and field are gathered, and t, alpha, beta computed again, only by the lanes that
 //                   contribute to the pair. An absent pair gets +0.0 partials, which is what the tree makes of +0.0 terms.
-//   k_gauge_upper   the upper levels of the tree, k_wall_upper's shape with the gauge in place of the region
+//   (sph_tree.hip)  the upper levels of the tree, the rows of the defined gauges only
 //   k_gauge_final   one thread per (gauge, word): the record, total = total + record, the call words 16..19, the history row
 //   k_gauge_clear   the totals of the slots in a mask
 //   k_gauge_mark    the crossing list of one gauge: the ballot of each wave and the count of each block, in the layout of the
@@ -27,10 +27,7 @@
 #define GA_HALF (SPH_GAUGE_WORDS / 2)  // the terms of one direction: reduced together through LDS
 #define GA_WAVES (SPH_BLOCK / 64)
 
-// Partials of a level: part[(gauge * 16 + word) * chunks + chunk], read coalesced by the next level.
-__device__ __host__ __forceinline__ size_t ga_at(int gauge, int word, int chunks, int chunk) {
-  return ((size_t)(gauge * GA_WORDS + word)) * (size_t)chunks + (size_t)chunk;
-}
+// (the rows of the tree are the gauges, GA_WORDS words each)
 
 __device__ __forceinline__ double ga_side(const GaugeOne& G, double px, double py, double pz) {
   return (G.n[0] * (px - G.o[0]) + G.n[1] * (py - G.o[1])) + G.n[2] * (pz - G.o[2]);
@@ -62,7 +59,7 @@ __device__ __forceinline__ bool ga_hit(const GaugeOne& G, const float4& a, const
 __global__ __launch_bounds__(SPH_BLOCK) void k_gauge_leaf(SphDev d, GaugeSet set, double* __restrict__ part, int chunks) {
   __shared__ double sh[GA_HALF][SPH_BLOCK];
   __shared__ uint32_t shPres;
-  const int t = threadIdx.x, chunk = blockIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, chunk = blockIdx.x;
   float4 a[4], b[4];
   uint32_t id[4], word[4];
 #pragma unroll
@@ -108,7 +105,7 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_gauge_leaf(SphDev d, GaugeSet set
     for (int dir = 0; dir < 2; dir++) {
       const int bit = 2 * g + dir;
       if (!((blockPres >> bit) & 1u)) {  // every term of this chunk is +0.0: so is every sum of the tree
-        if (t < GA_HALF) part[ga_at(g, dir * GA_HALF + t, chunks, chunk)] = 0.0;
+        if (t < GA_HALF) part[tree_at(GA_WORDS, g, dir * GA_HALF + t, chunks, chunk)] = 0.0;
         continue;
       }
       double acc[GA_HALF], prev[GA_HALF];
@@ -145,28 +142,10 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_gauge_leaf(SphDev d, GaugeSet set
 #pragma unroll
       for (int k = 0; k < GA_HALF; k++) sh[k][t] = acc[k];
       __syncthreads();
-      if (t < 128) {
-#pragma unroll
-        for (int k = 0; k < GA_HALF; k++) sh[k][t] = sh[k][t] + sh[k][t + 128];
-      }
-      __syncthreads();
-      for (int k = wave; k < GA_HALF; k += GA_WAVES) {
-        const double x = diag_wave_sum(sh[k][lane] + sh[k][lane + 64]);
-        if (lane == 0) part[ga_at(g, dir * GA_HALF + k, chunks, chunk)] = x;
-      }
+      tree_group_sums<GA_HALF>(sh, GA_HALF, [&](int k, double x) { part[tree_at(GA_WORDS, g, dir * GA_HALF + k, chunks, chunk)] = x; });
       __syncthreads();  // sh is reused by the next pair
     }
   }
-}
-
-// Upper levels: `nIn` partials per word and gauge -> ceil(nIn / 1024), the same tree. One block per output chunk, gauge and word.
-__global__ __launch_bounds__(SPH_BLOCK) void k_gauge_upper(const double* __restrict__ in, int nIn, double* __restrict__ out, int nOut,
-                                                           uint32_t defMask) {
-  __shared__ double sh[SPH_BLOCK];
-  const int chunk = blockIdx.x, g = blockIdx.y, w = blockIdx.z;
-  if (!((defMask >> g) & 1u)) return;  // (block-uniform)
-  const double x = diag_block_reduce<DIAG_OP_SUM>(in + ga_at(g, w, nIn, 0), nIn, chunk, 0.0, sh);
-  if (threadIdx.x == 0) out[ga_at(g, w, nOut, chunk)] = x;
 }
 
 // top: the tree's last level, one partial per gauge and word. One thread per (gauge, word).
@@ -175,14 +154,14 @@ __global__ __launch_bounds__(SPH_MAX_GAUGES * GA_WORDS) void k_gauge_final(const
                                                                            int rows, long long call) {
   const int g = threadIdx.x / GA_WORDS, w = threadIdx.x % GA_WORDS;
   const bool defined = ((defMask >> g) & 1u) != 0u;
-  const double rec = defined ? top[ga_at(g, w, 1, 0)] : 0.0;
+  const double rec = defined ? top[tree_at(GA_WORDS, g, w, 1, 0)] : 0.0;
   D->record[g][w] = rec;
   if (hist) hist[(size_t)(call % rows) * (SPH_MAX_GAUGES * GA_WORDS) + threadIdx.x] = rec;
   if (!defined) return;
   double* T = D->totals[g];
   T[w] = T[w] + rec;
   if (w == 0) {  // (this thread alone touches words 16..19 of the gauge)
-    const double plus = rec, minus = top[ga_at(g, GA_HALF, 1, 0)];
+    const double plus = rec, minus = top[tree_at(GA_WORDS, g, GA_HALF, 1, 0)];
     T[16] = T[16] + 1.0;
     if (plus > 0.0 && T[17] < 0.0) T[17] = (double)call;
     if (minus > 0.0 && T[18] < 0.0) T[18] = (double)call;
@@ -242,16 +221,8 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_gauge_list(SphDev d, GaugeOne G, 
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
 static_assert(GA_WAVES == 4, "k_gauge_mark writes the four ballots per block that k_select_scatter reads");
-static int ga_chunks(int n) { return n > 0 ? (n + DIAG_CHUNK - 1) / DIAG_CHUNK : 1; }
 
-size_t sphk_gauge_tree_bytes(int N) {
-  size_t total = 0;
-  for (int c = ga_chunks(N);; c = ga_chunks(c)) {
-    total += (size_t)c;
-    if (c == 1) break;
-  }
-  return sizeof(double) * total * SPH_MAX_GAUGES * GA_WORDS;
-}
+size_t sphk_gauge_tree_bytes(int N) { return sizeof(double) * tree_level_chunks(N) * SPH_MAX_GAUGES * GA_WORDS; }
 
 int sphk_gauge_clear(sph_solver* s, GaugeDev* D, uint32_t slots) {
   hipLaunchKernelGGL(k_gauge_clear, dim3(1), dim3(SPH_MAX_GAUGES * 32), 0, s->stream, D, slots);
@@ -260,19 +231,13 @@ int sphk_gauge_clear(sph_solver* s, GaugeDev* D, uint32_t slots) {
 }
 
 int sphk_gauges_accumulate(sph_solver* s, const GaugeSet& set, double* tree, GaugeDev* D, double* hist, int rows, int64_t call) {
-  double* cur = tree;
-  int chunks = ga_chunks(s->d.N);
-  hipLaunchKernelGGL(k_gauge_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, set, cur, chunks);
+  const int chunks = tree_chunks(s->d.N);
+  hipLaunchKernelGGL(k_gauge_leaf, dim3(chunks), dim3(SPH_BLOCK), 0, s->stream, s->d, set, tree, chunks);
   SPH_HIP(hipGetLastError());
-  while (chunks > 1) {
-    const int nOut = ga_chunks(chunks);
-    double* next = cur + (size_t)SPH_MAX_GAUGES * GA_WORDS * (size_t)chunks;
-    hipLaunchKernelGGL(k_gauge_upper, dim3(nOut, SPH_MAX_GAUGES, GA_WORDS), dim3(SPH_BLOCK), 0, s->stream, (const double*)cur, chunks, next,
-                       nOut, set.defMask);
-    SPH_HIP(hipGetLastError());
-    cur = next; chunks = nOut;
-  }
-  hipLaunchKernelGGL(k_gauge_final, dim3(1), dim3(SPH_MAX_GAUGES * GA_WORDS), 0, s->stream, (const double*)cur, set.defMask, D, hist,
+  double *top = nullptr, *end = nullptr;  // the rows of undefined gauges are unwritten at every level: masked out, never read
+  const int rc = sphk_tree_upper(s, tree_shape(GA_WORDS, GA_WORDS, set.defMask), SPH_MAX_GAUGES, tree, chunks, &top, &end);
+  if (rc != SPH_OK) return rc;
+  hipLaunchKernelGGL(k_gauge_final, dim3(1), dim3(SPH_MAX_GAUGES * GA_WORDS), 0, s->stream, (const double*)top, set.defMask, D, hist,
                      rows > 0 ? rows : 1, (long long)call);
   SPH_HIP(hipGetLastError());
   return SPH_OK;

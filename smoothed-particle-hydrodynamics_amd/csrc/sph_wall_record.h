@@ -164,9 +164,8 @@ __device__ __forceinline__ void wl_record(const SphDev& d, const Set& ws, int id
   rec[27] = reflected ? 1.f : 0.f;
 }
 
-#define WL_TERMS 26  // words 1..26 of a region record (word 0 counts the particles)
-
 // the 26 per-particle terms of a region record (include/sphmi.h: sph_wall_diagnostics, words 1..26) from the particle's record
+// (WL_TERMS: sph_common.h, beside sphk_wall_diagnostics, because the entry point sizes the terms' scratch with it)
 __device__ __forceinline__ void wl_terms(const float (&rec)[SPH_WALL_WORDS], const float4& xi, float (&term)[WL_TERMS]) {
   const float* q = rec + 10;
   // h_S = (visc + pres) + tens; the cross products written like Lx, Ly, Lz of the diagnostics

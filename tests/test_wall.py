@@ -420,8 +420,8 @@ def test_slab_solver_is_invalid():
 
 def test_three_tree_levels_and_several_pieces_on_more_than_a_million_particles():
     """More than 1024^2 particles: the third level of the tree runs and the records travel in several pieces (the piece loop is
-    a copy of sph_force_measure's, not shared code). The 1.3 M box of test_forces.py with half of its floor, a body, lifted 2.4 r0
-    into the liquid before the first step."""
+    the one sph_force_measure runs, with this call's launch and record width). The 1.3 M box of test_forces.py with half of its
+    floor, a body, lifted 2.4 r0 into the liquid before the first step."""
     sc = scenes.liquid_box((60.0, 40.0, 60.0), (125, 85, 125), spacing_in_r0=0.85, mask=0xffffffff)
     cfg = sc["cfg"]
     assert cfg.particleCount > 1024 * 1024

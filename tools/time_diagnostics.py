@@ -2,8 +2,8 @@
 neighbour count), on the 1M cube of config #2 or on config #4 (16.5 M particles), beside what the same answer costs without
 them: read_position_buffer + read_velocity_buffer + read_density_buffer and the numpy reductions on the host. Prints, per scene,
 the wall times of the blocking calls. The kernel times alone: run under
-`rocprofv3 --kernel-trace --stats -- python tools/time_diagnostics.py ...` and read k_diag_leaf, k_diag_upper and k_histogram in
-the stats (the calls come in the order 1 region, 16 z-slab regions, 16 whole-scene regions, density, neighbours, each
+`rocprofv3 --kernel-trace --stats -- python tools/time_diagnostics.py ...` and read k_diag_leaf, k_tree_upper (the upper levels of every tree share
+this kernel; this tool runs no other tree) and k_histogram in the stats (the calls come in the order 1 region, 16 z-slab regions, 16 whole-scene regions, density, neighbours, each
 reps + 1 times).
 
     python tools/time_diagnostics.py [1M|16M|both] [reps] [--no-host]"""

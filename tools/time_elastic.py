@@ -4,7 +4,7 @@ muscles, 66,120 triangles: a three-level group tree), beside the route they repl
 positions and particleIndexBack through sph_read_buffer) and the numpy restatement of tests/elastic_ref.py on the host. Prints,
 per scene, the wall times of the blocking calls and the bytes each copies to the host. The kernel times alone: run under
 `rocprofv3 --kernel-trace --stats -- python tools/time_elastic.py ... --no-host` and read k_elastic_terms, k_muscle_fill,
-k_muscle_leaf, k_muscle_upper, k_muscle_final and k_membrane_measure beside the step's k_elastic in the trace.
+k_muscle_leaf, k_tree_upper (the upper levels of the group tree and of the area tree), k_muscle_final and k_membrane_measure beside the step's k_elastic in the trace.
 
     python tools/time_elastic.py [worm|sheets|both] [reps] [--no-host]"""
 import json

@@ -6,7 +6,8 @@ tests/forces_ref.py. Prints one JSON line per scene: the wall times of the block
 and the algorithmic bytes the full-record pass streams (400 B per particle: 240 read -- position, velocity, rho, (rho*, p), the
 16-bit ids and their base, the stored distances -- and 160 written; its 32 x 40 B of neighbour gathers are not counted). The
 kernel times alone: run under `rocprofv3 --kernel-trace --stats -- python tools/time_forces.py ...` and read k_force_records,
-k_force_leaf, k_force_upper and k_force_final beside k_forces and k_pressure_force in the stats.
+k_terms_leaf<64, 49, 7>, k_tree_upper (one row for every tree of the run: here the force totals' and the diagnostics') and
+k_terms_final<64, 49> beside k_forces and k_pressure_force in the stats.
 
     python tools/time_forces.py [config4|config2|worm|all] [reps] [--host]"""
 import json

@@ -7,8 +7,8 @@ gauge_cases.gauges_of: planes, rectangles, tilted parallelograms):
   (d) sph_diagnostics with one region on the same state: the yardstick, a pass that streams at least as many bytes through a wider
       tree. With a library that has no gauges (SPHMI_LIB=<the parent commit's build>) only (d) and the step are timed.
 Prints one JSON line per scene. The leaf streams 36 B per particle (sortedPos 16, vals 4, the gather of posOrig 16). The kernel
-times alone: run under `rocprofv3 --kernel-trace --stats -- python tools/time_gauges.py` and read k_gauge_leaf, k_gauge_upper and
-k_gauge_final in the stats. The method and its caveats are those of tools/time_wall.py: wall clock from Python, the first call a
+times alone: run under `rocprofv3 --kernel-trace --stats -- python tools/time_gauges.py` and read k_gauge_leaf, k_gauge_final and
+k_tree_upper (shared by every tree: this tool's diagnostics_1 calls are in the same row) in the stats. The method and its caveats are those of tools/time_wall.py: wall clock from Python, the first call a
 warm-up.
 
     python tools/time_gauges.py [config2|config4|both] [reps] [--host]"""

@@ -6,7 +6,8 @@ the wall times of the blocking calls, the bytes each copies to the host, the par
 and the algorithmic bytes the full-record pass streams (216 B per particle: 88 read -- position, velocity, both accelerations,
 the boundary mask, rho, (rho*, p) -- and 128 written; the rows and gathers of the particles next to a wall are not counted).
 The kernel times alone: run under `rocprofv3 --kernel-trace --stats -- python tools/time_wall.py` and read k_wall_records,
-k_wall_leaf, k_wall_upper, k_wall_final and k_wall_mask in the stats. The method and its caveats are those of
+k_terms_leaf<32, 27, 9>, k_terms_final<32, 27>, k_wall_mask and k_tree_upper (one row for every tree of the run: the wall totals',
+and those of this tool's force_diagnostics_1 calls) in the stats. The method and its caveats are those of
 tools/time_forces.py: wall clock from Python, the first call a warm-up.
 
     python tools/time_wall.py [reps] [--host]"""
