@@ -7,7 +7,8 @@
 //
 // MI355X design. The reference walks ~640 candidates twice per particle and does the expensive part
 // (sqrt, IEEE divide, histogram / store) under a branch that ~7 % of the lanes take but ~99 % of the waves execute.
-// Here a 256-thread workgroup owns 128 consecutive sorted particles, TWO lanes per particle (four were measured: slower),
+// Here a 256-thread workgroup owns 128 consecutive sorted particles — 256 with search bands, served as two halves of 128 from
+// one staged copy —, TWO lanes per particle (four were measured: slower),
 // stages the <= 9 contiguous runs of sorted particles that can contain their candidates (cells are contiguous along x in the
 // sorted order) into LDS once as SoA x/y/z, and each lane
 //   1. walks four of the particle's 8 cells ONCE (~280 candidates), four candidates per trip (16-byte aligned LDS reads,
@@ -69,9 +70,14 @@ __device__ __forceinline__ int wrap_cell(int c, int G) {  // searchCell, sphFlui
   return c;
 }
 
-#define FN_PART 128               // particles per workgroup: two workgroups of 256 threads per CU (one of 512 is slower)
-#define FN_THREADS (2 * FN_PART)  // two lanes per particle
-#define FN_PER_WAVE 32            // particles per wave
+#define FN_HALF 128               // particles a workgroup serves at a time: two workgroups of 256 threads per CU (one of 512 is slower)
+#define FN_THREADS (2 * FN_HALF)  // two lanes per particle
+// Particles per workgroup (its tile). With search bands the nine runs of 256 consecutive particles fit the candidate area,
+// so the workgroup stages them ONCE and each lane pair serves two particles in turn from that copy, p0 + p and p0 + FN_HALF + p;
+// without bands they do not (about half of such tiles of the headline's lattice exceed the capacity), and the tile is one half.
+#define FN_PART(BANDS) ((BANDS) ? 2 * FN_HALF : FN_HALF)
+static_assert(SPH_CHUNK_ALIGN % FN_PART(true) == 0 && SPH_CHUNK_ALIGN % FN_PART(false) == 0, "tiles stay whole inside chunk launches");
+#define FN_PER_WAVE 32            // particles per wave and half
 #define FN_WAVES (FN_THREADS / 64)
 #define FN_CAND_CAP 4096          // staged candidates per workgroup (SoA x/y/z: 48 KB; + lists 24 KB -> two workgroups per CU)
 #define FN_STAGE_PER 8            // candidate records per thread and staging round, all loads of a round in flight together
@@ -236,7 +242,8 @@ __device__ __forceinline__ void fn_exact_walk(const FnParams& d, const FnArrays&
 //
 // Synchronisation: ONE workgroup barrier per batch, between the staging of the candidates and their use. Everything before it
 // (batch bounds, the 9 candidate runs, their LDS layout) is computed redundantly by every wave from loads with workgroup-uniform
-// addresses, everything after it is private to a wave (its lists, its d^2 staging area, the exact walks of its own particles).
+// addresses, everything after it is private to a wave (its lists, its d^2 staging area, the exact walks of its own particles) —
+// so the two halves of a 256-particle tile follow each other in a wave without a barrier between them.
 //
 // BANDS: the eight rows other than the own x-row are staged from the search bands of the step — bandPos[slot of the
 // row], with bandStart[slot] read where cellStart is read for the own row — so a piece of those rows holds only the candidates within
@@ -259,9 +266,10 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   // all particles, or fewer ghost layers; of those, the launch's chunk (idxLo is a multiple of SPH_BLOCK, so map tiles stay whole)
   const int rangeBegin = max((int)cellStart[d.rangeLo], d.idxLo), rangeEnd = min((int)cellStart[d.rangeHi], d.idxHi);
   // (an XCD-aware tile order — each XCD one contiguous eighth of the tiles — was measured: 0.441 vs 0.430 ms on config #2, no change at 16.5 M)
-  const int p0 = rangeBegin + blockIdx.x * FN_PART;
+  constexpr int PART = FN_PART(BANDS), HALVES = PART / FN_HALF;
+  const int p0 = rangeBegin + blockIdx.x * PART;
   if (p0 >= rangeEnd) return;  // uniform
-  const int id = p0 + p;
+  const int id = p0 + p;  // the pair's particle of the first half; that of the second half is id + FN_HALF
   const bool alive = id < rangeEnd;
   FnArrays g;
   g.sortedPos = sortedPos; g.keys = keys; g.cellStart = cellStart; g.nbrId = nbrId; g.nbrDist = nbrDist; g.nbr16 = nbr16;
@@ -274,22 +282,33 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
 
   // ---- stage the candidate runs. Cells of a batch of particles lie in [cLo, cHi]; row r = (sy+1) + 3*(sz+1) holds the
   // cells [cLo - 1, cHi + 1] shifted by sy*gx + sz*gx*gy, which is one contiguous run of sorted particles. Normally the
-  // batch is the whole workgroup (128 particles). Where those runs would not fit the LDS budget — the workgroup straddles
+  // batch is the workgroup's whole tile. Where those runs would not fit the LDS budget — the workgroup straddles
   // two x-rows of cells (the runs then span whole rows) or sits in very dense cells — it serves its particles in smaller
-  // batches instead: at most 32 particles, never across an x-row boundary.
-  const int blockHi = min(p0 + FN_PART, rangeEnd);
-  // own record and cell: issued now, needed only after the staging
-  const float4 myPos = alive ? sortedPos[id] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const int myCell = alive ? (int)keys[id] : 0;
-  int batchLo = p0, retry = 0;  // uniform. retry 1: batches end at x-row boundaries; retry 2: and hold at most 32 particles
+  // batches instead, rung by rung: the aligned halves of a two-half tile, then batches that never cross an x-row boundary
+  // (at most FN_HALF particles; such a batch may straddle the two halves), then at most 32 particles.
+  const int blockHi = min(p0 + PART, rangeEnd);
+  // own records and cells, one per half: issued now, needed only after the staging
+  float4 myPos[HALVES];
+  int myCell[HALVES];
+#pragma unroll
+  for (int hf = 0; hf < HALVES; hf++) {
+    const bool aliveH = hf ? id + hf * FN_HALF < rangeEnd : alive;
+    myPos[hf] = aliveH ? sortedPos[id + hf * FN_HALF] : make_float4(0.f, 0.f, 0.f, 0.f);
+    myCell[hf] = aliveH ? (int)keys[id + hf * FN_HALF] : 0;
+  }
+  // uniform. retry 1: batches end at x-row boundaries; retry 2: and hold at most 32 particles. halves (two-half tiles): the rung
+  // in front of those, the batches are the tile's aligned halves
+  int batchLo = p0, retry = 0;
+  bool halves = false;
   while (batchLo < blockHi) {
   int batchHi = blockHi;
+  if (HALVES > 1 && halves && !retry) batchHi = min(p0 + ((batchLo - p0) / FN_HALF + 1) * FN_HALF, blockHi);
   if (retry) {  // every wave finds the end of the batch itself (same data, same answer)
     const unsigned row0 = keys[batchLo] / (unsigned)d.gx;
-    // the workgroup's <= FN_PART particles, 64 per round: the first one that must not join ends the batch
-    int firstStop = FN_PART;
+    // the next <= FN_HALF particles, 64 per round: the first one that must not join ends the batch
+    int firstStop = FN_HALF;
 #pragma unroll
-    for (int q = FN_PART / 64 - 1; q >= 0; q--) {
+    for (int q = FN_HALF / 64 - 1; q >= 0; q--) {
       const int iq = batchLo + 64 * q + lane;
       const bool stopq = (iq >= blockHi) || (keys[min(iq, blockHi - 1)] / (unsigned)d.gx != row0) || (retry == 2 && (q > 0 || lane >= 32));
       const unsigned long long mq = __ballot(stopq);
@@ -324,7 +343,8 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   }
   if (total > FN_CAND_CAP) {
     // redo in smaller batches (nothing was written to LDS yet): first one batch per x-row of cells — a workgroup that straddles two
-    // rows has runs that span whole rows —, then batches of at most 32 particles (very dense cells)
+    // rows has runs that span whole rows —, then batches of at most 32 particles (very dense cells); a two-half tile tries its halves first
+    if (HALVES > 1 && !halves) { halves = true; continue; }
     if (retry < 2) { retry++; continue; }
     total = 0;  // a small batch that still does not fit (very dense cells): drop runs (rare; their particles take the exact walk)
 #pragma unroll
@@ -385,14 +405,23 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   }
   __syncthreads();
   FN_STAMP(3)
-  const bool mine_now = alive && id >= batchLo && id < batchHi;  // this lane's particle belongs to the current batch
+  // The lane pair serves its particle of each half in turn from the one staged copy. No barrier between the halves: the lists and
+  // the store staging are private to a wave, and the candidate area is only read after the barrier above.
+  // (a do-while: under a `for` of one trip hipcc allocates k_find_neighbors<false> differently, 202 VGPRs for 199)
+  int hf = 0;
+#pragma unroll 1
+  do {
+  const int idH = id + hf * FN_HALF;
+  const bool mine_now = (hf ? idH < rangeEnd : alive) && idH >= batchLo && idH < batchHi;  // this lane's particle of the half belongs to the current batch
+  if (HALVES > 1 && !__any(mine_now)) continue;  // (wave-uniform) no particle of the wave's in this half of the batch
   bool slow = false;
 
   if (mine_now) {  // (whole pairs: the two lanes of a particle agree)
   // (opaque to the optimiser: everything derived from the particle's record is otherwise hoisted out of the batch loop,
   // which runs once for almost every workgroup, and then spilled)
-  float4 me = myPos;
-  int myCellNow = myCell, idNow = id;
+  float4 me = myPos[0];
+  int myCellNow = myCell[0], idNow = idH;
+  if (HALVES > 1 && hf) { me = myPos[HALVES - 1]; myCellNow = myCell[HALVES - 1]; }
   asm volatile("" : "+v"(me.x), "+v"(me.y), "+v"(me.z), "+v"(myCellNow), "+v"(idNow));
   int pLo[4], pHi[4], absDelta[4];  // this lane's four pieces as LDS slot ranges; sorted index = LDS slot + absDelta
   int selfSlot = -1;
@@ -814,10 +843,11 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     while (todo != 0ull) {
       const int b = __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
-      fn_exact_walk<BANDS>(d, g, sh, p0 + wave * FN_PER_WAVE + (b >> 1), wave, lane);
+      fn_exact_walk<BANDS>(d, g, sh, p0 + hf * FN_HALF + wave * FN_PER_WAVE + (b >> 1), wave, lane);
     }
   }
   FN_STAMP(9)
+  } while (HALVES > 1 && ++hf < HALVES);  // halves
   batchLo = batchHi;
   if (batchLo < blockHi) __syncthreads();  // (uniform) the next batch overwrites the staging area
   }  // batches
@@ -825,7 +855,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   __syncthreads();
   if (tid < 16) atomicAdd(&dbg[16 + tid], sh.stamps[tid] >> 6);
   if (tid == 0) {  // residency trace: when and where this workgroup ran (row = the workgroup's tile among those of all chunk launches)
-    const size_t row = 4 * ((size_t)(d.idxLo / FN_PART) + blockIdx.x);
+    const size_t row = 4 * ((size_t)(d.idxLo / PART) + blockIdx.x);
     trace[row + 0] = (uint32_t)wgStart_;
     trace[row + 1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
     trace[row + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID
@@ -859,7 +889,8 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth, int idxLo, int idxHi, hip
   a.xmin = r.xmin; a.ymin = r.ymin; a.zmin = r.zmin;
   SphBands b = {};
   if (bands) sphk_bands_bytes(s, &b);
-  hipLaunchKernelGGL(bands ? k_find_neighbors<true> : k_find_neighbors<false>, dim3(sph_blocks(idxHi - idxLo, FN_PART)), dim3(FN_THREADS),
+  hipLaunchKernelGGL(bands ? k_find_neighbors<true> : k_find_neighbors<false>,
+                     dim3(sph_blocks(idxHi - idxLo, bands ? FN_PART(true) : FN_PART(false))), dim3(FN_THREADS),
                      sizeof(FnShared), stream ? stream : s->stream, a,
                      (const float4*)r.sortedPos, (const uint32_t*)r.keys, (const uint32_t*)r.cellStart, r.binU, r.nbrId, r.nbrDist, r.nbr16,
                      r.nbrBase, r.dbg,
