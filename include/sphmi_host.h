@@ -97,6 +97,12 @@ int sphmi_step_chunk_edges(int64_t n, int32_t chunks, int64_t* edges);
 int sphmi_step_pipeline_schedule(int32_t chunks, int32_t depth, int32_t maxIteration, int32_t hasElastic, int32_t* stage,
                                  int32_t* chunk, int32_t cap, int32_t* depthOut);
 
+/* The first chunk whose band records the overlapped step scatters beside the first search launches instead of in front of them
+ * (sphBandDeferFirst, sphmi_chunks.h): the prelude scatters chunks [0, result), search chunks 0 .. result - 2 start at
+ * the fork and every later one behind the deferred scatter. `chunks` itself where nothing is deferred; negative SPH_ERR_* for
+ * chunks < 1. */
+int sphmi_step_band_defer_first(int32_t chunks);
+
 /* The halo check the pipelined step runs on the device every step, restated on the host: 1 if for every chunk c of the partition
  * edges[0 .. chunks] every particle the search can give a particle of chunk c as a neighbour lies in chunks c - 1 .. c + 1,
  * judged from the sorted cell ids keys[0 .. n) and the cell table cellStart[0 .. G] of a gx x gy x (G / (gx gy)) grid alone;

@@ -210,6 +210,7 @@ sph_solver::~sph_solver() {
   if (copyStream) hipStreamDestroy(copyStream);
   for (hipEvent_t e : evChunk) if (e) hipEventDestroy(e);
   if (evChunkJoin) hipEventDestroy(evChunkJoin);
+  if (evDeferred) hipEventDestroy(evDeferred);
   if (chunkStream) hipStreamDestroy(chunkStream);
   if (evSearchFork) hipEventDestroy(evSearchFork);
   if (searchStream) hipStreamDestroy(searchStream);
@@ -357,6 +358,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   SPH_HIP(hipEventCreateWithFlags(&s->evSearchFork, hipEventDisableTiming));
   for (hipEvent_t& e : s->evChunk) SPH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   SPH_HIP(hipEventCreateWithFlags(&s->evChunkJoin, hipEventDisableTiming));
+  SPH_HIP(hipEventCreateWithFlags(&s->evDeferred, hipEventDisableTiming));
   SphDev& d = s->d;
   d.N = N; d.G = cfg->gridCellCount; d.gx = cfg->gridCellsX; d.gy = cfg->gridCellsY; d.gz = cfg->gridCellsZ;
   d.cellMask = cfg->cellIdMask;
@@ -414,7 +416,7 @@ extern "C" int sph_create(const sph_config* cfg, const float* position, const fl
   d.nbStride = (int)waves4; d.nbOut = d.nbIn = d.nbhd; d.gatePolicy = 1; d.cellTable = d.cellStart;
   A(s->blockHist, (size_t)SPH_SORT_MAX_DIGITS * s->maxSortBlocks + SPH_SORT_MAX_DIGITS);  // block histograms + digit totals
   A(d.gid, n); A(d.owned, n); A(s->slabCounts, SPH_SLAB_COUNT_WORDS);
-  A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1); A(s->pipeTable, SPH_STEP_CHUNKS_MAX + 3);
+  A(d.dbg, SPH_DBG_WORDS); A(s->chunkEdges, SPH_STEP_CHUNKS_MAX + 1); A(s->pipeTable, SPH_PIPE_TABLE_WORDS);
   float* binU = nullptr;
   A(binU, 64);
   d.binU = binU;
@@ -641,10 +643,11 @@ static int step_pipeline(const sph_solver* s) {
 }
 
 // The halo check of the pipelined step, one lane per chunk (sphChunkHaloOk, sphmi_chunks.h: every table index is clamped there).
-// table: the pipeline table (the edges, or zeros), then the serial table {0, passed ? 0 : N}. dbg[9] counts the steps that took
-// the serial table, dbg[10] those that ran chunk by chunk.
-__global__ void k_halo_check(const uint32_t* keys, const uint32_t* cellStart, int G, int gx, int gy, int N, int chunks, ChunkEdges v,
-                             uint32_t* table, uint32_t* dbg) {
+// table: the pipeline table (the edges, or zeros), then the serial table {0, passed ? 0 : N}, then the serial table of the deferred
+// band scatter {passed ? 0 : edge[deferFirst], passed ? 0 : N} (deferFirst == chunks: nothing is deferred, both
+// empty). dbg[9] counts the steps that took the serial tables, dbg[10] those that ran chunk by chunk.
+__global__ void k_halo_check(const uint32_t* keys, const uint32_t* cellStart, int G, int gx, int gy, int N, int chunks, int deferFirst,
+                             ChunkEdges v, uint32_t* table, uint32_t* dbg) {
   const int c = threadIdx.x;  // one wave
   int ok = 1;
   if (c < chunks) {
@@ -656,12 +659,58 @@ __global__ void k_halo_check(const uint32_t* keys, const uint32_t* cellStart, in
   if (c == 0) {
     table[SPH_STEP_CHUNKS_MAX + 1] = 0u;
     table[SPH_STEP_CHUNKS_MAX + 2] = passed ? 0u : (uint32_t)N;
+    table[SPH_STEP_CHUNKS_MAX + 3] = passed ? 0u : v.e[min(max(deferFirst, 0), SPH_STEP_CHUNKS_MAX)];
+    table[SPH_STEP_CHUNKS_MAX + 4] = passed ? 0u : (uint32_t)N;
     atomicAdd(&dbg[passed ? 10 : 9], 1u);
   }
 }
 
+// ---- the prelude under the first search chunks. Two parts of the serial prelude produce nothing that the search
+// launches starting at the fork read, and run beside them:
+//  * The velocity half of the gather (k_sort_post_vel: sortedVel, backIndex), first thing on chunkStream, which is otherwise idle
+//    until evChunk[0]. k_find_neighbors reads neither. Their readers in stream
+//    order — the record pack and the forces kernel, the stages on the serial table, k_elastic, the membrane kernels, every later
+//    call — are on chunkStream behind it or on s->stream behind evChunkJoin. Write after read: it reads vals and velOrig, which are
+//    next written by k_pressure_force<2> (integrate; on chunkStream behind it or behind the join) and by the next step's hash and
+//    sort (s->stream, behind the join); it overwrites sortedVel and backIndex, whose readers of the step before were all joined into
+//    s->stream in front of evSearchFork.
+//  * The band records of the chunks from deferFirst = sphBandDeferFirst(chunks) on. Under the premise of k_halo_check findNeighbors
+//    of chunk c reads records only of chunks c - 1 .. c + 1 (its runs lie between bandStart of the cells keys[lo] - S and
+//    keys[hi - 1] + S + 1, and bandStart counts the entries in front of cellStart of the same cell). The prelude scatters chunks
+//    [0, deferFirst); the search of a chunk c with c + 1 < deferFirst starts at the fork; every later search launch is behind the
+//    deferred scatter: on searchStream in stream order (the scatter is enqueued there in front of chunk 1), on s->stream by a wait
+//    for evDeferred. The check's verdict is on the device only, so the rest is enqueued twice, as the stages of the pipelined step
+//    are: on s->stream in front of the fork by the serial table (empty if the check passed), and behind the fork by the pipeline
+//    table (empty if it failed). Every particle is scattered once either way; the scan and k_band_start read no records
+//    (sph_bands.hip).
+// With two chunks in the prelude chunk 1 starts late, behind the scatter, and the two streaming kernels run beside chunk 0 alone;
+// that measured faster than three chunks in the prelude and the scatter on chunkStream beside chunks 0 and 1, which the streams
+// slow down by more (profiles/r39/README.md). The compile-time switches select that placement (-DSPH_BAND_PRELUDE_CHUNKS=3
+// -DSPH_PRELUDE_DEFER_ON_SEARCH=0) or one part alone (make variant EXTRA=...); results do not depend on them.
+#ifndef SPH_PRELUDE_SPLIT_VEL
+#define SPH_PRELUDE_SPLIT_VEL 1
+#endif
+#ifndef SPH_PRELUDE_DEFER_BANDS
+#define SPH_PRELUDE_DEFER_BANDS 1
+#endif
+#ifndef SPH_PRELUDE_DEFER_ON_SEARCH
+#define SPH_PRELUDE_DEFER_ON_SEARCH 1
+#endif
+struct PreludeSplit {
+  bool vel;        // the gather left sortedVel and backIndex to k_sort_post_vel
+  int deferFirst;  // the band records of the chunks from here on are not scattered yet (== chunks: all are)
+};
+static PreludeSplit prelude_split(const sph_solver* s, int chunks, bool bands) {
+  PreludeSplit p;
+  p.vel = chunks > 1 && SPH_PRELUDE_SPLIT_VEL;
+  p.deferFirst = (chunks > 1 && bands && SPH_PRELUDE_DEFER_BANDS) ? sphBandDeferFirst(chunks) : chunks;
+  // (more chunks than blocks: the deferred chunks may all be empty)
+  if (sphChunkEdge(s->d.N, chunks, p.deferFirst) >= s->d.N) p.deferFirst = chunks;
+  return p;
+}
+
 // depth: stages 1 .. depth run here as well (clamped by the caller), by the schedule of sphPipelineSchedule.
-static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth) {
+static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth, PreludeSplit split) {
   const int N = s->d.N;
   ChunkEdges v;
   for (int i = 0; i <= SPH_STEP_CHUNKS_MAX; i++) v.e[i] = (uint32_t)sphChunkEdge(N, chunks, i);
@@ -670,19 +719,40 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth) {
     SPH_HIP(hipGetLastError());
     s->chunkEdgesN = N; s->chunkEdgesC = chunks;
   }
-  if (depth > 0) {  // behind the sort and the cell table, in front of everything that reads the tables
-    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(64), 0, s->stream, s->d.keys, s->d.cellStart, s->d.G, s->d.gx, s->d.gy, N, chunks, v,
-                       s->pipeTable, s->d.dbg);
+  const bool deferred = split.deferFirst < chunks;
+  const int deferLo = (int)v.e[split.deferFirst], deferCount = N - deferLo;
+  int rc = SPH_OK;
+  if (depth > 0 || deferred) {  // behind the sort and the cell table, in front of everything that reads the tables
+    hipLaunchKernelGGL(k_halo_check, dim3(1), dim3(64), 0, s->stream, s->d.keys, s->d.cellStart, s->d.G, s->d.gx, s->d.gy, N, chunks,
+                       split.deferFirst, v, s->pipeTable, s->d.dbg);
     SPH_HIP(hipGetLastError());
   }
+  // the deferred band records where the check failed: here, in front of every search launch
+  if (deferred) rc = sphk_band_scatter(s, s->pipeTable, SPH_STEP_CHUNKS_MAX + 3, SPH_STEP_CHUNKS_MAX + 4, deferCount, true, s->stream);
   // searchStream starts where s->stream stands now: behind the sort and the cell table
   SPH_HIP(hipEventRecord(s->evSearchFork, s->stream));
   SPH_HIP(hipStreamWaitEvent(s->searchStream, s->evSearchFork, 0));
-  auto launch = [s, N, chunks](int stage, int c) -> int {
+  bool waited[2] = {!deferred, !deferred};  // per search stream: it has waited for evDeferred
+  if (split.vel || deferred) {  // chunkStream too: what the searches at the fork do not read
+    SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evSearchFork, 0));
+    if (split.vel && rc == SPH_OK) rc = sphk_sort_post_vel(s, s->chunkStream);
+    if (deferred) {
+      // on searchStream in front of its first search launch, which then needs no wait (0: on chunkStream behind k_sort_post_vel)
+      hipStream_t ds = SPH_PRELUDE_DEFER_ON_SEARCH ? s->searchStream : s->chunkStream;
+      if (rc == SPH_OK) rc = sphk_band_scatter(s, s->pipeTable, split.deferFirst, chunks, deferCount, false, ds);
+      SPH_HIP(hipEventRecord(s->evDeferred, ds));
+      if (SPH_PRELUDE_DEFER_ON_SEARCH) waited[1] = true;
+    }
+  }
+  auto launch = [s, N, chunks, split, &waited](int stage, int c) -> int {
     const int lo = (int)sphChunkEdge(N, chunks, c), hi = (int)sphChunkEdge(N, chunks, c + 1);
     if (hi <= lo) return SPH_OK;  // more chunks than blocks of 256 particles
     if (stage > 0) return sphk_pipeline_stage(s, stage, c, lo, hi, s->chunkStream);
     hipStream_t fnStream = (c & 1) ? s->searchStream : s->stream;
+    if (c + 1 >= split.deferFirst && !waited[c & 1]) {  // the chunk may read deferred band records
+      SPH_HIP(hipStreamWaitEvent(fnStream, s->evDeferred, 0));
+      waited[c & 1] = true;
+    }
     int rc = sphk_find_neighbors(s, -1, lo, hi, fnStream, s->bandsStep);
     if (rc != SPH_OK) return rc;
     SPH_HIP(hipEventRecord(s->evChunk[c], fnStream));
@@ -693,10 +763,10 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth) {
   // The issue order is the schedule's (depth 0: stage 0 of every chunk, the overlapped search alone), never derived here.
   int32_t stage[SPH_PIPELINE_ITEMS_MAX(SPH_STEP_CHUNKS_MAX)], chunk[SPH_PIPELINE_ITEMS_MAX(SPH_STEP_CHUNKS_MAX)];
   const int items = sphPipelineSchedule(chunks, depth, s->cfg.maxIteration, s->d.hasElastic ? 1 : 0, stage, chunk);
-  int rc = SPH_OK;
   for (int i = 0; i < items && rc == SPH_OK; i++) rc = launch(stage[i], chunk[i]);
   // The join, on the device, also after a failed launch. Every findNeighbors launch, on either stream, has a density launch behind
   // it on chunkStream, so chunkStream's last event covers searchStream too.
+  if (SPH_PRELUDE_DEFER_ON_SEARCH && deferred) SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evDeferred, 0));  // (no odd chunk may have followed it)
   SPH_HIP(hipEventRecord(s->evChunkJoin, s->chunkStream));
   SPH_HIP(hipStreamWaitEvent(s->stream, s->evChunkJoin, 0));
   // The same stages again over all particles, by the serial table: empty launches unless the halo check failed.
@@ -717,6 +787,10 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   int rc;
   sph_state_changes(s);
 #define RUN(stage, call) do { StageTimer t_(s, stage); rc = (call); if (rc != SPH_OK) return rc; } while (0)
+  // Host state only, so decided in front of the gather: where the search runs in chunks, the gather and the band scatter leave to
+  // chunkStream what the first search launches do not read (prelude_split; everywhere else both do all of their work here).
+  const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
+  PreludeSplit split = {false, chunks};
   if (s->hasSlab) {
     s->bandsStep = false;  // (sph_bands_apply: never in slab mode)
     RUN(SPH_ST_SORT, sphk_hash_sort_post_slab(s));
@@ -728,17 +802,18 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
       rc = sph_grow_scratch(s, s->bandBuf, sphk_bands_bytes(s, nullptr));  // (the first such step allocates)
       if (rc != SPH_OK) { s->bandsStep = false; return rc; }
     }
+    split = prelude_split(s, chunks, s->bandsStep);
     int bits = s->sortBits;
     bool compact = false;  // wide cell ids: only ~1/8 of the declared index space is reachable, which can save a radix pass
     RUN(SPH_ST_HASH, sphk_hash_for_step(s, &bits, &compact));
     RUN(SPH_ST_SORT, sphk_sort_pairs(s, s->d.N, bits));
     if (compact) {
       StageTimer t_(s, SPH_ST_SORT_POST);
-      rc = sphk_sort_post_rekey(s, s->bandsStep);
+      rc = sphk_sort_post_rekey(s, s->bandsStep, !split.vel);
       if (rc == SPH_OK) rc = sphk_index_fixed(s);
       if (rc != SPH_OK) return rc;
     } else {
-      RUN(SPH_ST_SORT_POST, sphk_sort_post_and_index(s, s->bandsStep));
+      RUN(SPH_ST_SORT_POST, sphk_sort_post_and_index(s, s->bandsStep, !split.vel));
     }
   }
   // Slab mode: a stage runs only on the ghost layers its results are needed on (owned layers + depth layers per side).
@@ -749,9 +824,9 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   const bool slab = s->hasSlab;
   const int M = s->cfg.maxIteration;
   // The rest of the search bands (scan, scatter, start tables), behind the cell table and in front of everything that forks off this stream.
-  if (s->bandsStep) RUN(SPH_ST_BANDS, sphk_build_bands(s));
+  // (the records of the chunks from split.deferFirst on: enqueue_search_overlapped)
+  if (s->bandsStep) RUN(SPH_ST_BANDS, sphk_build_bands(s, split.deferFirst < chunks ? (int)sphChunkEdge(s->d.N, chunks, split.deferFirst) : INT32_MAX));
   auto layersFor = [&](int hops) { return slab ? min((hops * 31 + 59) / 60, s->slab.ghostLayers) : -1; };
-  const int chunks = step_chunks(s);  // > 1: no stage timers (the path is not taken with timing on)
   const int piped = chunks > 1 ? step_pipeline(s) : 0;  // stages 1 .. piped are enqueued with the search
   // The per-wave flags of the predict-correct loop need launch ranges that start at multiples of SPH_BLOCK, so that a
   // wave is one id >> 6, and every writer of a flag finished before its first reader starts: the serial step, the chunked search
@@ -759,7 +834,7 @@ int enqueue_step(sph_solver* s, const StepTail* tail) {
   // The neighbourhood bytes invert the search's cell relation with one cell per offset, which needs a grid larger than an offset.
   s->waveSkip = !slab && piped <= 1 && s->waveSkipMode != 2 && (long long)s->d.G > (long long)s->d.gx * s->d.gy + s->d.gx + 1;
   if (chunks > 1) {
-    rc = enqueue_search_overlapped(s, chunks, piped);
+    rc = enqueue_search_overlapped(s, chunks, piped, split);
     if (rc != SPH_OK) return rc;
   } else {
     RUN(SPH_ST_FIND_NEIGHBORS, sphk_find_neighbors(s, layersFor(2 * (M - 1) + 1), 0, INT32_MAX, nullptr, s->bandsStep));

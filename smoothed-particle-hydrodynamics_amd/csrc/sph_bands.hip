@@ -17,6 +17,9 @@
 //   k_band_scatter  records (x, y, z, sorted index) to band[s][offset of the wave + rank inside the ballot]: stable
 //   k_band_start    bandStart[s][c] = band-s entries in front of cellStart[c], c = 0 .. G
 // No atomics: every word has one writer.
+// The scan and k_band_start read counts, ballots and cellStart, never the records, so the scatter may come later for the particles
+// whose records the first search launches do not read: the overlapped step scatters a prefix here and the rest beside the first
+// search chunks (sphk_band_scatter by a device table; sph_api.hip).
 #include "sph_common.h"
 
 #define BAND_SUPER 1024  // wave entries per block of the scan
@@ -81,9 +84,20 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_band_offsets(SphBandGeom g, SphBa
   }
 }
 
-__global__ __launch_bounds__(SPH_BLOCK) void k_band_scatter(SphBandGeom g, SphBands b, const float4* __restrict__ sortedPos) {
-  const int i = blockIdx.x * SPH_BLOCK + threadIdx.x, lane = threadIdx.x & 63, w = i >> 6;
-  const uint32_t f = i < g.N ? b.flags[i] : 0u;
+// The sorted particles [begin, end) of a scatter launch: entries a and b of a small device table (the pipeline table or one of the
+// serial tables that k_halo_check leaves every step, sph_api.hip), or a and b themselves where there is no table. begin is a
+// multiple of SPH_BLOCK (a chunk edge, sphmi_chunks.h), so a wave of the launch is a wave of the gather's ballots.
+struct BandRange { const uint32_t* table; int a, b; };
+__device__ __forceinline__ void band_range(const BandRange& r, int N, int& begin, int& end) {
+  begin = r.table ? (int)r.table[r.a] : r.a;
+  end = min(r.table ? (int)r.table[r.b] : r.b, N);
+}
+
+// block `blk` of 256 of the range's particles; whole waves (the ballots), the lanes from `end` on contribute nothing
+__device__ __forceinline__ void band_scatter_block(const SphBandGeom& g, const SphBands& b, const float4* __restrict__ sortedPos, int begin,
+                                                   int end, int blk) {
+  const int i = begin + blk * SPH_BLOCK + threadIdx.x, lane = threadIdx.x & 63, w = i >> 6;
+  const uint32_t f = i < end ? b.flags[i] : 0u;
   float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
   if (f) { rec = sortedPos[i]; rec.w = __int_as_float(i); }
   const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -95,6 +109,21 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_band_scatter(SphBandGeom g, SphBa
       if (dst < (uint32_t)b.cap) b.pos[(size_t)s * b.cap + dst] = rec;
     }
   }
+}
+
+// One block per 256 particles of the range the host sized the grid for; the blocks past the range's end leave.
+__global__ __launch_bounds__(SPH_BLOCK) void k_band_scatter(SphBandGeom g, SphBands b, const float4* __restrict__ sortedPos, BandRange r) {
+  int begin, end;
+  band_range(r, g.N, begin, end);
+  if (begin + (int)blockIdx.x * SPH_BLOCK >= end) return;  // uniform
+  band_scatter_block(g, b, sortedPos, begin, end, blockIdx.x);
+}
+// The same over a fixed grid (SPH_SERIAL_GRID): for the launch that is empty on every step whose halo check passed.
+__global__ __launch_bounds__(SPH_BLOCK) void k_band_scatter_strided(SphBandGeom g, SphBands b, const float4* __restrict__ sortedPos, BandRange r) {
+  int begin, end;
+  band_range(r, g.N, begin, end);
+  const int active = end > begin ? (end - begin + SPH_BLOCK - 1) / SPH_BLOCK : 0;
+  for (int blk = blockIdx.x; blk < active; blk += gridDim.x) band_scatter_block(g, b, sortedPos, begin, end, blk);
 }
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_band_start(SphBandGeom g, SphBands b, const uint32_t* __restrict__ cellStart) {
@@ -155,14 +184,29 @@ SphBandGeom sph_band_geom(const sph_solver* s) {
   return g;
 }
 
-int sphk_build_bands(sph_solver* s) {
+int sphk_band_scatter(sph_solver* s, const uint32_t* table, int a, int b, int count, bool strided, hipStream_t stream) {
+  if (count <= 0) return SPH_OK;
+  SphBands bands;
+  sphk_bands_bytes(s, &bands);
+  const SphBandGeom g = sph_band_geom(s);
+  const BandRange r{table, a, b};
+  const int nb = sph_blocks(count);
+  if (strided) hipLaunchKernelGGL(k_band_scatter_strided, dim3(min(nb, SPH_SERIAL_GRID)), dim3(SPH_BLOCK), 0, stream, g, bands, (const float4*)s->d.sortedPos, r);
+  else hipLaunchKernelGGL(k_band_scatter, dim3(nb), dim3(SPH_BLOCK), 0, stream, g, bands, (const float4*)s->d.sortedPos, r);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
+int sphk_build_bands(sph_solver* s, int scatterEnd) {
   SphBands b;
   sphk_bands_bytes(s, &b);
   const SphBandGeom g = sph_band_geom(s);
   const int supers = (g.waves + 1 + BAND_SUPER - 1) / BAND_SUPER;  // (<= superStride: waves + 1 <= waveStride)
   hipLaunchKernelGGL(k_band_super, dim3(supers), dim3(SPH_BLOCK), 0, s->stream, g, b);
   hipLaunchKernelGGL(k_band_offsets, dim3(supers, 8), dim3(SPH_BLOCK), 0, s->stream, g, b);
-  hipLaunchKernelGGL(k_band_scatter, dim3(sph_blocks(g.N)), dim3(SPH_BLOCK), 0, s->stream, g, b, (const float4*)s->d.sortedPos);
+  const int end = min(max(scatterEnd, 0), g.N);
+  const int rc = sphk_band_scatter(s, nullptr, 0, end, end, false, s->stream);
+  if (rc != SPH_OK) return rc;
   hipLaunchKernelGGL(k_band_start, dim3(sph_blocks(g.G + 1)), dim3(SPH_BLOCK), 0, s->stream, g, b, (const uint32_t*)s->d.cellStart);
   SPH_HIP(hipGetLastError());
   return SPH_OK;

@@ -30,6 +30,9 @@
 #define SPH_SORT_MAX_DIGITS 512   // radix digits per pass: 256 (8 bits) or 512 (9 bits)
 #define SPH_GATE_SLOTS 16         // words of SphDev::skipGate: one per stage of the predict-correct loop (stage & 15)
 #define SPH_STEP_CHUNKS_MAX 16    // most chunks the overlapped step takes (sph_set_step_chunks)
+#define SPH_SERIAL_GRID 2048      // blocks of the grid-stride entry points (sphk_pipeline_stage, sphk_band_scatter); a multiple of 8, the XCD count
+// words of sph_solver::pipeTable: the pipeline table, the serial table of the stages and the serial table of the deferred band scatter
+#define SPH_PIPE_TABLE_WORDS (SPH_STEP_CHUNKS_MAX + 5)
 static_assert(SPH_CHUNK_ALIGN == SPH_BLOCK, "chunk edges are launch-block edges of the density and pack passes");
 
 struct SphDev {  // what the kernels see; passed by value
@@ -189,12 +192,16 @@ struct sph_solver {
   // evChunkJoin before the rest of the step, so nothing is pending on either stream when enqueue_step returns. Created by sph_create, destroyed with the solver.
   hipStream_t chunkStream = nullptr, searchStream = nullptr;
   hipEvent_t evChunk[SPH_STEP_CHUNKS_MAX] = {}, evChunkJoin = nullptr, evSearchFork = nullptr;
+  // recorded on searchStream behind the deferred band scatter; s->stream waits for it in front of its first search launch that may
+  // read those records, chunkStream in front of the join
+  hipEvent_t evDeferred = nullptr;
   int stepChunks = 0;                  // sph_set_step_chunks: 0 = automatic, 1 = serial, else that many chunks
   uint32_t* chunkEdges = nullptr;      // device, SPH_STEP_CHUNKS_MAX + 1 words: the partition chunkEdgesN / chunkEdgesC was made for
   int chunkEdgesN = -1, chunkEdgesC = -1;
   // pipelined step (sph_api.hip): up to stepPipeline stages behind the search run on chunkStream chunk by chunk.
   // pipeTable, device, written every step by k_halo_check: [0 .. SPH_STEP_CHUNKS_MAX] the pipeline table (the chunk edges if the
-  // halo check passed, zeros if not), then the two words of the serial table {0, passed ? 0 : N}
+  // halo check passed, zeros if not), then the two words of the serial table {0, passed ? 0 : N}, then the two of the deferred band
+  // scatter's serial table {passed ? 0 : edge[sphBandDeferFirst], passed ? 0 : N} (SPH_PIPE_TABLE_WORDS in all)
   int stepPipeline = -1;               // sph_set_step_pipeline: -1 = the built-in depth, else that many stages
   bool waveSkip = false;               // set by enqueue_step: the fused kernels of this step write and consult the per-wave flags
                                        // (SphDev::pBlk ...); the launchers of sph_pcisph.hip hand every other launch null pointers
@@ -378,11 +385,13 @@ int sphk_step_sort_bits(const sph_solver* s, bool* compact);         // key bits
 int sphk_hash_for_step(sph_solver* s, int* sortBits, bool* compact);  // fused step: hash with compacted keys where that saves a pass
 // bandFlags (both gathers): also write the first stage of the step's search bands — flags, ballots, counts (sph_band_flags.h) — into
 // bandBuf, which the caller has grown; sphk_build_bands does the rest
-int sphk_sort_post_rekey(sph_solver* s, bool bandFlags = false);  // the gather after a sort of compacted keys (puts the real cell ids back)
-int sphk_sort_post(sph_solver* s, bool bandFlags = false);        // gather + backIndex (K3)
+// vel (both gathers): false leaves out sortedVel and backIndex; the caller launches sphk_sort_post_vel for them
+int sphk_sort_post_rekey(sph_solver* s, bool bandFlags = false, bool vel = true);  // the gather after a sort of compacted keys (puts the real cell ids back)
+int sphk_sort_post(sph_solver* s, bool bandFlags = false, bool vel = true);        // gather + backIndex (K3)
+int sphk_sort_post_vel(sph_solver* s, hipStream_t stream);  // sortedVel and backIndex of every particle, from vals and velOrig, on `stream`
 int sphk_index_raw(sph_solver* s);        // K4 table with -1 for empty cells
 int sphk_index_fixed(sph_solver* s);      // H2 table (cellStart)
-int sphk_sort_post_and_index(sph_solver* s, bool bandFlags = false);  // fused K3 + K4 + H2
+int sphk_sort_post_and_index(sph_solver* s, bool bandFlags = false, bool vel = true);  // fused K3 + K4 + H2
 int sphk_hash_sort_post_slab(sph_solver* s);  // slab mode: K2 + sort + K3 with compacted sort keys (2 radix passes)
 // sph_neighbors.hip
 int sphk_clear_neighbors(sph_solver* s);
@@ -395,7 +404,13 @@ int sphk_find_neighbors(sph_solver* s, int ghostDepth = -1, int idxLo = 0, int i
 size_t sphk_bands_bytes(const sph_solver* s, SphBands* out);  // bytes of bandBuf for the solver's capacity and grid; *out: the arrays in it
 SphBandGeom sph_band_geom(const sph_solver* s);
 float sph_band_radius(const SphDev& d, float filterR2);       // Rb from the search filter's radius^2 (binU[63])
-int sphk_build_bands(sph_solver* s);  // scan, scatter, start tables from the flags the gather left (bandFlags); on s->stream behind the cell table
+// scan, scatter, start tables from the flags the gather left (bandFlags); on s->stream behind the cell table. scatterEnd: the
+// records of the sorted particles [0, scatterEnd) only (a chunk edge); the caller scatters the rest with sphk_band_scatter
+int sphk_build_bands(sph_solver* s, int scatterEnd = INT32_MAX);
+// The records of the sorted particles [table[a], table[b]) — table == nullptr: [a, b) — on `stream`, behind the scan. count: the
+// most particles the range can hold (sizes the grid). strided: a grid-stride launch on SPH_SERIAL_GRID blocks, for a range that is
+// empty on most steps.
+int sphk_band_scatter(sph_solver* s, const uint32_t* table, int a, int b, int count, bool strided, hipStream_t stream);
 // sph_pcisph.hip
 int sphk_density(sph_solver* s, int ghostDepth = -1);
 // density and the record pack of chunk c of the partition that enqueue_search_overlapped (sph_api.hip) keeps in s->chunkEdges

@@ -31,7 +31,6 @@ __device__ __forceinline__ void store_pred(const SphDev& d, int id, const float4
 #define FC_BATCH 8   // forces: two 16-B gathers per neighbour
 #define PF_BATCH 8   // pressure force: 16 B + 4 B per neighbour
 #define PD_BATCH 16  // predicted density: 16 B per neighbour
-#define SPH_SERIAL_GRID 2048  // blocks of the grid-stride entry points (sphk_pipeline_stage); a multiple of 8, the XCD count
 
 // index into SphDev::gatherRec: groups of four particles, [4 x part 0][4 x part 1] (one 128-byte line; see k_pack_gather_records)
 __device__ __forceinline__ size_t rec_index(int j, int part) { return ((size_t)(j >> 2) << 3) + (size_t)(part << 2) + (size_t)(j & 3); }

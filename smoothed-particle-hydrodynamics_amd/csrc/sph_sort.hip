@@ -49,7 +49,10 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_hash_compact(SphDev d, CompactKey
 // FLAGS (both gather kernels; the fused non-slab step where its search reads bands): the kernel also leaves the first stage of the
 // search bands — the particle's flag byte and the wave's eight ballots and counts (sph_band_flags.h) — from the record and the key
 // it stores. The ballots are wave-level, so the lanes past N stay to the end and contribute zero.
-template <bool FLAGS>
+// VEL (both gather kernels): the kernel also gathers the velocity and writes backIndex. The overlapped step (sph_api.hip, DESIGN.md
+// 44) launches the instance without and leaves that half to k_sort_post_vel, which runs beside the first search chunks: the search
+// reads neither array.
+template <bool FLAGS, bool VEL>
 __global__ __launch_bounds__(SPH_BLOCK) void k_sort_post_rekey(SphDev d, SphBandGeom g, SphBands b) {
   const int i = blockIdx.x * SPH_BLOCK + threadIdx.x;
   uint32_t f = 0u;
@@ -57,8 +60,10 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_sort_post_rekey(SphDev d, SphBand
     const uint32_t src = d.vals[i];
     const float4 p = d.posOrig[src];
     d.sortedPos[i] = p;
-    d.sortedVel[i] = d.velOrig[src];
-    d.backIndex[src] = (uint32_t)i;
+    if (VEL) {
+      d.sortedVel[i] = d.velOrig[src];
+      d.backIndex[src] = (uint32_t)i;
+    }
     const int cx = (int)(p.x * d.cellSizeInv), cy = (int)(p.y * d.cellSizeInv), cz = (int)(p.z * d.cellSizeInv);
     const uint32_t key = (uint32_t)(cx + cy * d.gx + cz * d.gx * d.gy) & d.cellMask;  // the real cell id, as k_hash computes it
     d.keys[i] = key;
@@ -117,12 +122,13 @@ static void gather_band_args(const sph_solver* s, bool bandFlags, SphBandGeom* g
   if (bandFlags) { sphk_bands_bytes(s, b); *g = sph_band_geom(s); }
 }
 
-int sphk_sort_post_rekey(sph_solver* s, bool bandFlags) {
+int sphk_sort_post_rekey(sph_solver* s, bool bandFlags, bool vel) {
   SphBandGeom g;
   SphBands b;
   gather_band_args(s, bandFlags, &g, &b);
-  hipLaunchKernelGGL(bandFlags ? k_sort_post_rekey<true> : k_sort_post_rekey<false>, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream,
-                     s->d, g, b);
+  auto* const k = vel ? (bandFlags ? k_sort_post_rekey<true, true> : k_sort_post_rekey<false, true>)
+                      : (bandFlags ? k_sort_post_rekey<true, false> : k_sort_post_rekey<false, false>);
+  hipLaunchKernelGGL(k, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d, g, b);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
@@ -298,7 +304,7 @@ int sphk_sort_pairs(sph_solver* s, int n, int bits) {
 }
 
 // ------------------------------------------------------------------ K3 sortPostPass (sphFluid.cl:441-466)
-template <bool FLAGS>  // (see k_sort_post_rekey; the key is the sorted one the radix sort left in keys[])
+template <bool FLAGS, bool VEL>  // (see k_sort_post_rekey; the key is the sorted one the radix sort left in keys[])
 __global__ __launch_bounds__(SPH_BLOCK) void k_sort_post(SphDev d, SphBandGeom g, SphBands b) {
   const int i = blockIdx.x * SPH_BLOCK + threadIdx.x;
   uint32_t f = 0u;
@@ -306,11 +312,29 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_sort_post(SphDev d, SphBandGeom g
     const uint32_t src = d.vals[i];
     const float4 p = d.posOrig[src];
     d.sortedPos[i] = p;  // .w stays the particle type; the cell id lives in keys[]
-    d.sortedVel[i] = d.velOrig[src];
-    d.backIndex[src] = (uint32_t)i;
+    if (VEL) {
+      d.sortedVel[i] = d.velOrig[src];
+      d.backIndex[src] = (uint32_t)i;
+    }
     if (FLAGS) f = band_flags(g, p, d.keys[i]);
   }
   if (FLAGS) band_flags_store(g, b, i, f);
+}
+
+// The half that the gather instances without VEL leave out, for every sorted particle: the same two expressions from the same
+// inputs (vals is what the sort left and both gathers read; velOrig is the state).
+__global__ __launch_bounds__(SPH_BLOCK) void k_sort_post_vel(SphDev d) {
+  const int i = blockIdx.x * SPH_BLOCK + threadIdx.x;
+  if (i >= d.N) return;
+  const uint32_t src = d.vals[i];
+  d.sortedVel[i] = d.velOrig[src];
+  d.backIndex[src] = (uint32_t)i;
+}
+
+int sphk_sort_post_vel(sph_solver* s, hipStream_t stream) {
+  hipLaunchKernelGGL(k_sort_post_vel, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, stream, s->d);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
 }
 
 // K4 indexx (sphFluid.cl:385-439) + the host fix-up loop (owOpenCLSolver.cpp:305-319) in one kernel, one lane per cell:
@@ -341,11 +365,13 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cell_start(SphDev d, int first, i
     for (int i = 0; i < SPH_GATE_SLOTS; i++) d.skipGate[i] = 1u;
 }
 
-int sphk_sort_post(sph_solver* s, bool bandFlags) {
+int sphk_sort_post(sph_solver* s, bool bandFlags, bool vel) {
   SphBandGeom g;
   SphBands b;
   gather_band_args(s, bandFlags, &g, &b);
-  hipLaunchKernelGGL(bandFlags ? k_sort_post<true> : k_sort_post<false>, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d, g, b);
+  auto* const k = vel ? (bandFlags ? k_sort_post<true, true> : k_sort_post<false, true>)
+                      : (bandFlags ? k_sort_post<true, false> : k_sort_post<false, false>);
+  hipLaunchKernelGGL(k, dim3(sph_blocks(s->d.N)), dim3(SPH_BLOCK), 0, s->stream, s->d, g, b);
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
@@ -373,8 +399,8 @@ int sphk_index_fixed(sph_solver* s) {
   SPH_HIP(hipGetLastError());
   return SPH_OK;
 }
-int sphk_sort_post_and_index(sph_solver* s, bool bandFlags) {
-  int rc = sphk_sort_post(s, bandFlags);
+int sphk_sort_post_and_index(sph_solver* s, bool bandFlags, bool vel) {
+  int rc = sphk_sort_post(s, bandFlags, vel);
   return rc == SPH_OK ? sphk_index_fixed(s) : rc;
 }
 

@@ -462,6 +462,11 @@ int sphmi_step_pipeline_schedule(int32_t chunks, int32_t depth, int32_t maxItera
   return sphPipelineSchedule(chunks, depth, maxIteration, hasElastic, stage, chunk);
 }
 
+int sphmi_step_band_defer_first(int32_t chunks) {
+  if (chunks < 1) return SPH_ERR_INVALID;
+  return sphBandDeferFirst(chunks);
+}
+
 int sphmi_step_halo_check(const uint32_t* keys, int64_t n, const uint32_t* cellStart, int64_t G, const int64_t* edges, int32_t chunks,
                           int32_t gx, int32_t gy) {
   if (!keys || !cellStart || !edges || n < 0 || G < 1 || chunks < 1 || gx < 1 || gy < 1) return SPH_ERR_INVALID;

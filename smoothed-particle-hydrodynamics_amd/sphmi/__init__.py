@@ -159,6 +159,7 @@ def host_lib():
         L.sphmi_step_chunk_edges.argtypes = [C.c_int64, C.c_int32, C.c_void_p]
         L.sphmi_step_pipeline_schedule.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.sphmi_step_halo_check.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.sphmi_step_band_defer_first.argtypes = [C.c_int32]
         L.sphmi_trajectory_info.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 4
         L.sphmi_trajectory_frame.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
         L.sphmi_trajectory_connections.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
@@ -200,7 +201,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_read_gauge_crossings"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
-                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_save_configuration", "sphmi_worm_counts",
+                         "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_step_band_defer_first", "sphmi_save_configuration", "sphmi_worm_counts",
                          "sphmi_generate_worm", "sphmi_trajectory_info", "sphmi_trajectory_frame", "sphmi_trajectory_connections",
                          "sphmi_trajectory_membranes"]
 
@@ -555,6 +556,16 @@ def step_pipeline_schedule(chunks, depth, max_iteration=3, has_elastic=False):
     if n < 0:
         raise SphError("sphmi_step_pipeline_schedule failed: %d" % n)
     return clamped.value, [(int(a), int(b)) for a, b in zip(stage[:n], chunk[:n])]
+
+
+def step_band_defer_first(chunks):
+    """The first chunk whose search-band records the overlapped step scatters beside the first search launches (host library, no
+    GPU): the prelude scatters chunks [0, result), search chunks 0 .. result - 2 start at the fork, every later one behind the
+    deferred scatter. `chunks` where nothing is deferred."""
+    rc = host_lib().sphmi_step_band_defer_first(int(chunks))
+    if rc < 0:
+        raise SphError("sphmi_step_band_defer_first failed: %d" % rc)
+    return rc
 
 
 def step_halo_check(keys, cell_start, edges, gx, gy):
