@@ -1051,6 +1051,67 @@ int sph_gauges_read_history(sph_solver* s, int64_t firstCall, int32_t count, dou
 int sph_gauge_crossings(sph_solver* s, int32_t slot, int64_t* count); /* blocking */
 int sph_read_gauge_crossings(sph_solver* s, int32_t* sortedIndex, uint32_t* origId, int32_t* direction, float* tab3 /* t, alpha, beta */);
 
+/* ---- Probes: point samples and water levels on lines, with history (no reference counterpart) --------------------
+ * The instruments of a run: a field at a fixed point over time, and the level of a surface along a fixed line over time. The
+ * definitions are kept by the solver, one call after a step enqueues every record, and a history ring lives on the device; nothing
+ * waits for the host unless asked. State, selected set, order of the sums, denormals and the all-zero record of a non-finite point
+ * are those of sph_sample_points: the sorted state of the last completed step. Every call is read-only on every solver array and
+ * is not a stage. Probes belong to the solver, as tracers do: steps, stages and edits leave them alone. A slab solver is
+ * SPH_ERR_INVALID for every call.
+ * POINT PROBE. Its record is the SPH_SAMPLE_WORDS record sph_sample_points returns at that point with the set's typeMask, bit for
+ * bit.
+ * LEVEL PROBE, a line of `count` points: q_k = origin + (float)k * step per component (one float multiply, one float add: the
+ * lattice expression of sph_sample_grid), k = 0 .. count-1. f_k is word `field` (0..5, as sph_extract_surface) of the sample record
+ * at q_k with the line's typeMask. Point k is INSIDE when f_k >= iso (float compare; NaN is outside). The line is searched from its
+ * far end, k = count-1. Record (SPH_PROBE_LEVEL_WORDS floats):
+ *   SPH_PROBE_SUBMERGED  point count-1 is inside:           { q_{count-1}.xyz, (float)(count-1), 2, (float)(count-1), f_{count-1}, 0 }
+ *   SPH_PROBE_FOUND      K = the largest k with k inside and k+1 outside:
+ *                                                           { x, y, z, (float)K + t, 0, (float)K, f_K, f_{K+1} }
+ *                        t = (iso - f_K)/(f_{K+1} - f_K), x = q_K.x + t*(q_{K+1}.x - q_K.x), likewise y and z
+ *   SPH_PROBE_DRY        there is no such k:                { q_0.xyz, 0, 1, -1, 0, 0 }
+ * all in float, in the written order, no contraction, IEEE division: the vertex expression of sph_extract_surface. t may be 0; a NaN
+ * f_{K+1} gives NaN coordinates. To find a lower face or the bed, orient the line the other way. A line's record depends on the
+ * state and the line alone: not on the other lines, their order or number, nor on how far the search went.
+ * DEFINITIONS. sph_probes_set_points replaces the point set (at most SPH_PROBE_MAX_POINTS; points may be non-finite, as for
+ * sampling), sph_probes_set_lines the lines (at most SPH_PROBE_MAX_LINES); count == 0 releases the set. Both validate all or
+ * nothing: on SPH_ERR_INVALID the set keeps what it held. Invalid: a count above the maximum or below 0, a bad typeMask (as
+ * sampling; per line for lines), a non-finite word of a line's origin or step, a non-finite iso, a line's count outside
+ * 2..SPH_PROBE_LINE_MAX, a field outside 0..5, null pointers with count > 0, and a set whose row no longer fits the existing
+ * ring's byte cap. Both set calls copy the caller's array before they return (blocking). sph_probes_count gives {points, lines}.
+ * RECORDING. sph_probes_record computes every point and line record, writes them to row index % rows of the ring if there is one,
+ * and increments the call INDEX, counted from 0 per solver and never reset. With both pointers NULL everything is enqueued on the
+ * solver's stream and the call returns without a host wait; otherwise it waits once and copies what was asked for (points: P x 8
+ * floats, levels: L x 8 floats). It is SPH_ERR_ORDER with neither points nor lines set; in every other state it returns exactly
+ * what sph_sample_points returns there. A failed call consumes no index.
+ * HISTORY. sph_probes_history(rows) gives the solver a device ring of `rows` rows of P + L records, points first (rows == 0
+ * releases it; SPH_ERR_INVALID for rows outside 0..SPH_PROBE_HISTORY_MAX and for rows * row bytes > 1 << 28). A new ring and a new
+ * set both restart the ring empty. sph_probes_read_history (blocking) copies the records of calls firstCall .. firstCall + count - 1
+ * (points: count x P x 8, levels: count x L x 8; either may be NULL) and *callsWritten (may be NULL) the number of calls so far. It
+ * is SPH_ERR_ORDER without a ring and SPH_ERR_INVALID unless every asked call was made since the ring (re)started and is among the
+ * last `rows` calls.
+ * SCOPE. Straight, fixed lines; the first crossing from the far end only (counting all crossings would forbid the early stop). */
+#define SPH_PROBE_MAX_POINTS 65536
+#define SPH_PROBE_MAX_LINES 65536
+#define SPH_PROBE_LINE_MAX 1024      /* points of one line */
+#define SPH_PROBE_LEVEL_WORDS 8
+#define SPH_PROBE_HISTORY_MAX 16384  /* rows; and rows * row bytes <= 1 << 28 */
+#define SPH_PROBE_FOUND 0
+#define SPH_PROBE_DRY 1
+#define SPH_PROBE_SUBMERGED 2
+typedef struct sph_probe_line {      /* 40 bytes */
+  float origin[3], step[3];
+  int32_t count;      /* 2..SPH_PROBE_LINE_MAX */
+  int32_t field;      /* 0..5, as sph_extract_surface */
+  float iso;
+  uint32_t typeMask;  /* as sampling, per line */
+} sph_probe_line;
+int sph_probes_set_points(sph_solver* s, const float* points4 /* host, count x (x,y,z,unused) */, int32_t count, uint32_t typeMask); /* 0 releases */
+int sph_probes_set_lines(sph_solver* s, const sph_probe_line* lines /* host */, int32_t count); /* 0 releases */
+int sph_probes_count(sph_solver* s, int32_t counts[2] /* out: points, lines */);
+int sph_probes_record(sph_solver* s, float* points /* host, P x 8, or NULL */, float* levels /* host, L x 8, or NULL */);
+int sph_probes_history(sph_solver* s, int32_t rows /* 0 releases; at most SPH_PROBE_HISTORY_MAX */);
+int sph_probes_read_history(sph_solver* s, int64_t firstCall, int32_t count, float* points, float* levels, int64_t* callsWritten); /* blocking */
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -28,8 +28,8 @@ static int region_fill(float box[6], const float* region6, const char* what) {
   return SPH_OK;
 }
 
-// The argument and order rules every analysis call shares; a != nullptr: the constants of the sampling contract too.
-static int sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleArgs* a = nullptr) {
+// The argument and order rules every analysis call shares (declared in sph_api_internal.h, where the probes find them too).
+int sph_sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleArgs* a) {
   if (s->hasSlab) { sph_set_error("%s: sampling a slab solver is not supported", what); return SPH_ERR_INVALID; }
   if (typeMask == 0u || (typeMask & ~0xEu)) { sph_set_error("%s: typeMask must be a non-empty set of bits 1..3", what); return SPH_ERR_INVALID; }
   NEED(s, P_DENSITY | P_PRESSUREFORCE, what);
@@ -114,7 +114,7 @@ extern "C" int sph_sample_points(sph_solver* s, const float* points4, int32_t co
   ENTER(s);
   if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_points: bad count or null pointer"); return SPH_ERR_INVALID; }
   SampleArgs a;
-  const int rc = sample_check(s, typeMask, "sph_sample_points", &a);
+  const int rc = sph_sample_check(s, typeMask, "sph_sample_points", &a);
   if (rc != SPH_OK || count == 0) return rc;
   return sample_point_runs(s, points4, count, SPH_SAMPLE_WORDS, out,
                            [&](const float* pts, int n, float* records) { return sphk_sample_points(s, a, pts, n, records); });
@@ -128,7 +128,7 @@ extern "C" int sph_sample_grid(sph_solver* s, const float origin[3], const float
     return SPH_ERR_INVALID;
   }
   SampleArgs a;
-  const int rc = sample_check(s, typeMask, "sph_sample_grid", &a);
+  const int rc = sph_sample_check(s, typeMask, "sph_sample_grid", &a);
   if (rc != SPH_OK) return rc;
   return sample_grid_chunks(
       s, dims, SPH_SAMPLE_WORDS,
@@ -156,7 +156,7 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
   const long long P = (long long)dims[0] * (long long)dims[1] * (long long)dims[2];
   if (P > 0x7fffffffLL) { sph_set_error("sph_extract_surface: the lattice has more than 2^31-1 points"); return SPH_ERR_INVALID; }
   SampleArgs a;
-  int rc = sample_check(s, typeMask, "sph_extract_surface", &a);
+  int rc = sph_sample_check(s, typeMask, "sph_extract_surface", &a);
   if (rc != SPH_OK) return rc;
   rc = sph_grow_scratch(s, s->surfBuf, sphk_surface_scratch_bytes(P));
   if (rc != SPH_OK) return rc;
@@ -208,7 +208,7 @@ extern "C" int sph_sample_gradient_points(sph_solver* s, const float* points4, i
   ENTER(s);
   if (count < 0 || (count > 0 && (!points4 || !out))) { sph_set_error("sph_sample_gradient_points: bad count or null pointer"); return SPH_ERR_INVALID; }
   SampleArgs a;
-  const int rc = sample_check(s, typeMask, "sph_sample_gradient_points", &a);
+  const int rc = sph_sample_check(s, typeMask, "sph_sample_gradient_points", &a);
   if (rc != SPH_OK || count == 0) return rc;
   const float K = gradient_scale(s);
   return sample_point_runs(s, points4, count, SPH_GRADIENT_WORDS, out,
@@ -223,7 +223,7 @@ extern "C" int sph_sample_gradient_grid(sph_solver* s, const float origin[3], co
     return SPH_ERR_INVALID;
   }
   SampleArgs a;
-  const int rc = sample_check(s, typeMask, "sph_sample_gradient_grid", &a);
+  const int rc = sph_sample_check(s, typeMask, "sph_sample_gradient_grid", &a);
   if (rc != SPH_OK) return rc;
   const float K = gradient_scale(s);
   return sample_grid_chunks(
@@ -243,7 +243,7 @@ extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
   const int64_t V = s->meshCounts[0];
   if (V > 0 && !normals) { sph_set_error("sph_surface_normals: null pointer"); return SPH_ERR_INVALID; }
   SampleArgs a;
-  rc = sample_check(s, s->meshTypeMask, "sph_surface_normals", &a);
+  rc = sph_sample_check(s, s->meshTypeMask, "sph_surface_normals", &a);
   if (rc != SPH_OK || V == 0) return rc;
   const size_t rec = sizeof(float) * 3;
   const int piece = (int)std::min<size_t>((size_t)V, kSampleScratchBytes / rec);
@@ -262,7 +262,7 @@ extern "C" int sph_surface_normals(sph_solver* s, float* normals) {
 
 // ---------------------------------------------------------------------------------------------- flow diagnostics
 // Reductions and histograms over the same state as sampling (sph_diag.hip); blocking, read-only, no stage timing.
-// the `count` regions (6 floats each) and the types of a region-list call into its arguments (sample_check has checked the mask)
+// the `count` regions (6 floats each) and the types of a region-list call into its arguments (sph_sample_check has checked the mask)
 static int diag_fill_regions(sph_solver* s, DiagArgs* a, const float* regions6, int count, uint32_t typeMask, const char* what) {
   for (int r = 0; r < count; r++) {
     const int rc = region_fill(a->box[r], regions6 + 6 * r, what);
@@ -287,7 +287,7 @@ extern "C" int sph_diagnostics(sph_solver* s, const float* regions6, int32_t cou
   ENTER(s);
   if (!regions6 || !out) { sph_set_error("sph_diagnostics: null pointer"); return SPH_ERR_INVALID; }
   if (count < 1 || count > SPH_DIAG_MAX_REGIONS) { sph_set_error("sph_diagnostics: count %d is not in 1..%d", count, SPH_DIAG_MAX_REGIONS); return SPH_ERR_INVALID; }
-  int rc = sample_check(s, typeMask, "sph_diagnostics");
+  int rc = sph_sample_check(s, typeMask, "sph_diagnostics");
   if (rc != SPH_OK) return rc;
   DiagArgs a = {};
   rc = diag_fill_regions(s, &a, regions6, count, typeMask, "sph_diagnostics");
@@ -301,7 +301,7 @@ extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, i
   if (field < 0 || field > 6) { sph_set_error("sph_histogram: field %d is not in 0..6", field); return SPH_ERR_INVALID; }
   if (bins < 1 || bins > SPH_HIST_MAX_BINS) { sph_set_error("sph_histogram: bins %d is not in 1..%d", bins, SPH_HIST_MAX_BINS); return SPH_ERR_INVALID; }
   if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) { sph_set_error("sph_histogram: lo and hi must be finite with lo < hi"); return SPH_ERR_INVALID; }
-  int rc = sample_check(s, typeMask, "sph_histogram");
+  int rc = sph_sample_check(s, typeMask, "sph_histogram");
   if (rc != SPH_OK) return rc;
   HistArgs a = {};
   rc = sph_fill_selector(&a.sel, region6, typeMask, "sph_histogram");
@@ -327,7 +327,7 @@ extern "C" int sph_label_components(sph_solver* s, float linkRadius, uint32_t ty
   if (counts) counts[0] = counts[1] = 0;
   if (!counts) { sph_set_error("sph_label_components: null pointer"); return SPH_ERR_INVALID; }
   if (std::isnan(linkRadius) || !(linkRadius > 0.f)) { sph_set_error("sph_label_components: linkRadius must be > 0"); return SPH_ERR_INVALID; }
-  int rc = sample_check(s, typeMask, "sph_label_components");
+  int rc = sph_sample_check(s, typeMask, "sph_label_components");
   if (rc != SPH_OK) return rc;
   NEED(s, P_FIND, "sph_label_components");
   const bool finite = !std::isinf(linkRadius);
@@ -402,7 +402,7 @@ extern "C" int sph_component_diagnostics(sph_solver* s, const int32_t* component
 // sorted index, and the records are gathered from the live state when they are asked for (an SphDerived record, like the mesh and the labelling).
 static int select_check(sph_solver* s, uint32_t typeMask, const char* what, float* ss2) {
   SampleArgs a;
-  const int rc = sample_check(s, typeMask, what, &a);
+  const int rc = sph_sample_check(s, typeMask, what, &a);
   if (rc != SPH_OK) return rc;
   NEED(s, P_FIND, what);
   *ss2 = a.ss2;
@@ -617,7 +617,7 @@ extern "C" int sph_membrane_measure(sph_solver* s, float* out, double totals[4])
 // The K7 and K12 accelerations by the class of the neighbour that exerted them (sph_forces.hip): per particle in pieces through
 // the sampling scratch, and as region totals through the diagnostics scratch. Blocking, read-only, no stage timing.
 static int force_check(sph_solver* s, uint32_t typeMask, const char* what) {
-  const int rc = sample_check(s, typeMask, what);
+  const int rc = sph_sample_check(s, typeMask, what);
   if (rc != SPH_OK) return rc;
   NEED(s, P_FIND | P_FORCES, what);  // the rows, and the gather records K7 packs
   return SPH_OK;
@@ -790,7 +790,7 @@ extern "C" int sph_bodies_advance(sph_solver* s, double* out) {
 static int trace_check(sph_solver* s, uint32_t typeMask, const sph_trace_params* p, const float* region6, bool curves,
                        const char* what, SampleArgs* a, TraceArgs* t) {
   if (!p) { sph_set_error("%s: null params", what); return SPH_ERR_INVALID; }
-  const int rc = sample_check(s, typeMask, what, a);
+  const int rc = sph_sample_check(s, typeMask, what, a);
   if (rc != SPH_OK) return rc;
   if (!std::isfinite(p->step) || p->step == 0.f) { sph_set_error("%s: step must be finite and not 0", what); return SPH_ERR_INVALID; }
   if (!(p->minSpeed >= 0.f)) { sph_set_error("%s: minSpeed must be >= 0", what); return SPH_ERR_INVALID; }
@@ -948,7 +948,7 @@ extern "C" int sph_render_particles(sph_solver* s, const sph_render_view* view, 
   s->renderHasMesh = false;
   if (counts) counts[0] = counts[1] = 0;
   if (!view || !counts) { sph_set_error("sph_render_particles: null pointer"); return SPH_ERR_INVALID; }
-  int rc = sample_check(s, typeMask, "sph_render_particles");
+  int rc = sph_sample_check(s, typeMask, "sph_render_particles");
   if (rc != SPH_OK) return rc;
   if (!render_view_ok(*view)) return SPH_ERR_INVALID;
   RenderArgs a = {};
@@ -1018,7 +1018,7 @@ extern "C" int sph_render_mesh(sph_solver* s, const sph_render_view* view, const
     sph_derived_drop(s->render);
     s->renderHasMesh = false;
   }
-  int rc = sample_check(s, 0xEu, what);
+  int rc = sph_sample_check(s, 0xEu, what);
   if (rc != SPH_OK) return rc;
   if (!render_view_ok(*view)) return SPH_ERR_INVALID;
   if (y.source != 0 && y.source != 1) { sph_set_error("%s: source %d is not 0 or 1", what, y.source); return SPH_ERR_INVALID; }
@@ -1082,7 +1082,7 @@ extern "C" int sph_render_mesh(sph_solver* s, const sph_render_view* view, const
     tris = (const int32_t*)((const char*)s->meshBuf.p + surf_bytes_align(sizeof(float) * 3 * (size_t)V));
     if ((normals || samples) && V > 0) {
       SampleArgs sa;
-      rc = sample_check(s, s->meshTypeMask, what, &sa);
+      rc = sph_sample_check(s, s->meshTypeMask, what, &sa);
       if (rc != SPH_OK) return rc;
       if (normals) rc = sphk_surface_normals(s, sa, gradient_scale(s), s->meshField, verts, (int)V, (float*)(base + L.normals));
       if (rc != SPH_OK) return rc;

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (sph_api.hip: errors, timing, solver lifetime, stages, the fused step; sph_api_read.hip:
 // read-back and reference-layout export; sph_api_slab.hip: the slab protocol; sph_api_analysis.hip: sampling, surfaces, gradients,
-// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields; sph_api_body.hip: kinematic bodies; sph_api_gauge.hip: flow gauges): the order contract and the entry checks,
+// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields; sph_api_body.hip: kinematic bodies; sph_api_gauge.hip: flow gauges; sph_api_probe.hip: probes): the order contract and the entry checks,
 // the one rule for "the state has changed" and for results derived from it, and the per-particle input checks of sph_create
 // and the adding calls.
 #pragma once
@@ -72,6 +72,9 @@ int sph_check_finite_state(sph_solver* s);                             // synchr
 int sph_slab_finish(sph_solver* s, int32_t counts[4]);
 // (bodies in sph_api_analysis.hip)
 int sph_grow_scratch(sph_solver* s, SphScratch& b, size_t bytes);  // device buffer b grown to at least `bytes`
+// The argument and order rules every analysis call shares (sph_sample_points' own); a != nullptr: the constants of the sampling
+// contract too.
+int sph_sample_check(sph_solver* s, uint32_t typeMask, const char* what, SampleArgs* a = nullptr);
 // The selection arguments every call that takes them shares: typeMask must be a non-empty set of bits 1..3; region6 (x0, y0, z0,
 // x1, y1, z1) may be null (everything: -inf .. +inf) and must not hold a NaN. SPH_ERR_INVALID with "<what>: ..." otherwise.
 int sph_fill_selector(SphSelector* sel, const float* region6 /* may be null */, uint32_t typeMask, const char* what);

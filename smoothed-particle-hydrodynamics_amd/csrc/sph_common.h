@@ -295,6 +295,15 @@ struct sph_solver {
   SphScratch gaugeBuf, gaugeTree, gaugeHist, gaugeScan, gaugeList;
   SphDerived gaugeCross;              // the last successful sph_gauge_crossings
   int64_t gaugeCrossCount = 0;        // ... its length
+  // probes (sph_probes_*, sph_probe.hip): the point set (float4 each) and the lines as given, on the device;
+  // probeCur: the records of the last call, points first, then lines; probeHist: the ring of probeHistRows rows of that layout,
+  // written for the calls from probeHistFirst on. Independent of the particle state, like the tracers.
+  SphScratch probePts, probeLines, probeCur, probeHist;
+  int probePointCount = 0, probeLineCount = 0;
+  uint32_t probeTypeMask = 0;         // of the point set
+  int64_t probeCalls = 0;             // successful sph_probes_record calls so far: the index of the next one
+  int probeHistRows = 0;
+  int64_t probeHistFirst = 0;
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -620,6 +629,11 @@ int sphk_gauges_accumulate(sph_solver* s, const GaugeSet& set, double* tree, Gau
 int sphk_gauge_mark(sph_solver* s, const GaugeOne& g, void* scratch, uint32_t** totals);
 // after sphk_gauge_mark and sphk_select_scatter: original id, direction and (t, alpha, beta) of list[0..n)
 int sphk_gauge_list(sph_solver* s, const GaugeOne& g, const int32_t* list, int n, uint32_t* origId, int32_t* direction, float* tab3);
+// sph_probe.hip (probes: point samples and water levels on lines; read-only on every solver array). Device pointers;
+// cur / row: where the launch's first record goes in the current-record buffer and in the ring's row (row may be null). `a` as for
+// sphk_sample_points; the level kernel takes each line's own typeMask.
+int sphk_probe_points(sph_solver* s, const SampleArgs& a, const float* pts4, int count, float* cur, float* row);
+int sphk_probe_levels(sph_solver* s, const SampleArgs& a, const sph_probe_line* lines, int count, float* cur, float* row);
 // sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
 // values in original-id order (device). Read-only on every solver array.
 size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word

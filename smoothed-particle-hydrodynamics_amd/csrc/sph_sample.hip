@@ -9,21 +9,6 @@
 // its cell box in ascending order.
 #include "sph_sample_walk.h"
 
-__device__ __forceinline__ void sample_hit(const SphDev& d, const SampleArgs& a, SampleAcc& acc, float px, float py, float pz,
-                                           float4 xj, float4 vj /* vel.xyz, pressure */, float invRho) {
-  const float dx = px - xj.x, dy = py - xj.y, dz = pz - xj.z;
-  const float r2 = dx * dx + dy * dy + dz * dz;
-  if (r2 < a.hh) {
-    const float t = d.hs2 - r2 * a.ss2;
-    const float w = t * t * t;
-    const float v = w * invRho;
-    acc.W += w; acc.S += v;
-    acc.Ux += v * vj.x; acc.Uy += v * vj.y; acc.Uz += v * vj.z;
-    acc.P += v * vj.w;
-    acc.n++;
-  }
-}
-
 // One point through the point walk (sph_sample_walk.h): zero sums, a hit per selected particle, the record.
 __device__ void sample_one(const SphDev& d, const SampleArgs& a, float px, float py, float pz, float* out) {
   SampleAcc acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};

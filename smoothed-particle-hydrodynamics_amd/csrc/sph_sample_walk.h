@@ -47,6 +47,22 @@ struct SampleAcc {
   int n;
 };
 
+// One selected candidate into the sums: the arithmetic of the sampling contract (sph_sample.hip), in its order.
+__device__ __forceinline__ void sample_hit(const SphDev& d, const SampleArgs& a, SampleAcc& acc, float px, float py, float pz,
+                                           float4 xj, float4 vj /* vel.xyz, pressure */, float invRho) {
+  const float dx = px - xj.x, dy = py - xj.y, dz = pz - xj.z;
+  const float r2 = dx * dx + dy * dy + dz * dz;
+  if (r2 < a.hh) {
+    const float t = d.hs2 - r2 * a.ss2;
+    const float w = t * t * t;
+    const float v = w * invRho;
+    acc.W += w; acc.S += v;
+    acc.Ux += v * vj.x; acc.Uy += v * vj.y; acc.Uz += v * vj.z;
+    acc.P += v * vj.w;
+    acc.n++;
+  }
+}
+
 __device__ __forceinline__ bool sample_type_ok(const SampleArgs& a, float w) {
   const int t = (int)w;
   return t >= 1 && t <= 3 && ((1u << t) & a.typeMask);

@@ -308,6 +308,23 @@ class owHIPSolver {
     check(sph_read_gauge_crossings(s_, sortedIndex, origId, direction, tab3), "readGaugeCrossings");
   }
 
+  // beyond the reference: probes. Point probes (the sph_sample_points record at fixed points) and level probes (the first crossing
+  // of a field's iso value along a fixed line, searched from its far end) kept by the solver; after a completed step probesRecord
+  // computes every record, writes it to the history ring on the device if there is one (probesHistory) and, with both pointers
+  // null, returns without a host wait. probesSetPoints / probesSetLines with count 0 release a set; probesReadHistory copies the
+  // records of calls firstCall .. firstCall + count - 1 (either pointer may be null) and returns the number of calls so far
+  // (include/sphmi.h, sph_probes_*)
+  void probesSetPoints(const float* points4, int count, uint32_t typeMask) { check(sph_probes_set_points(s_, points4, count, typeMask), "probesSetPoints"); }
+  void probesSetLines(const sph_probe_line* lines, int count) { check(sph_probes_set_lines(s_, lines, count), "probesSetLines"); }
+  void probesCount(int32_t counts[2]) { check(sph_probes_count(s_, counts), "probesCount"); }
+  void probesRecord(float* points = nullptr, float* levels = nullptr) { check(sph_probes_record(s_, points, levels), "probesRecord"); }
+  void probesHistory(int rows) { check(sph_probes_history(s_, rows), "probesHistory"); }
+  int64_t probesReadHistory(int64_t firstCall, int count, float* points, float* levels) {
+    int64_t calls = 0;
+    check(sph_probes_read_history(s_, firstCall, count, points, levels, &calls), "probesReadHistory");
+    return calls;
+  }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

@@ -99,6 +99,14 @@
 //        the totals: `_gauge: step S gauge G plus P minus M net N calls C first F last L  mean velocity plus X Y Z minus X Y Z
 //        field plus A minus B` (counts %.0f; F: the first call, counted from 0, with a crossing in either direction, -1: none yet;
 //        mean velocities and field sums %.9e, the velocity sums over the counts, 0 without a crossing)
+//   ... --probe X Y Z ... --level-line OX OY OZ SX SY SZ N ... --level-grid OX OY OZ SX SY SZ NX NY NZ --probe-every K --probe-out FILE
+//        probes (sph_probes_*): every --probe adds a point probe (the sample record over liquid and elastic matter),
+//        every --level-line a level probe of N points OX.. + k * SX.. (the Shepard sum of the liquid against 0.5, searched from the
+//        far end), --level-grid one such line per (x, y) column of the lattice, along +z, x fastest. After every K-th step all
+//        records go to a history ring on the device without a wait; the ring is read ONCE, at the end, and written to FILE: the text
+//        line `sphmi probes calls C points P lines L every K`, then C x (P + L) x 8 raw float32 words, a call's point records in
+//        front of its line records (frames.read_probes). One line is printed: `_probes: calls C points P lines L`. The ring's limits
+//        (SPH_PROBE_HISTORY_MAX calls, 2^28 bytes) bound steps / K.
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -273,6 +281,8 @@ int main(int argc, char** argv) {
   int forEvery = 0; bool forSeen = false;
   int wallEvery = 0; bool wallSeen = false;
   std::vector<sph_gauge> gaugeDefs; int gaugeEvery = 0; bool gaugeSeen = false, gaugeOk = true;
+  std::vector<float> probePoints; std::vector<sph_probe_line> probeLines; int probeEvery = 0; bool probeSeen = false, probeOk = true;
+  const char* probeFile = nullptr;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -359,6 +369,30 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--gauge-plane")) { if (gaugeDefs.empty()) gaugeOk = false; else gaugeDefs.back().flags |= SPH_GAUGE_PLANE; gaugeSeen = true; }
     else if (!strcmp(argv[i], "--gauge-field") && i + 1 < argc) { if (gaugeDefs.empty()) { gaugeOk = false; ++i; } else gaugeDefs.back().fieldSlot = atoi(argv[++i]); gaugeSeen = true; }
     else if (!strcmp(argv[i], "--gauge-every") && i + 1 < argc) { gaugeEvery = atoi(argv[++i]); gaugeSeen = true; }
+    else if (!strcmp(argv[i], "--probe") && i + 3 < argc) {
+      for (int k = 0; k < 3; k++) probePoints.push_back((float)atof(argv[++i]));
+      probePoints.push_back(0.f); probeSeen = true;
+    }
+    else if ((!strcmp(argv[i], "--level-line") && i + 7 < argc) || (!strcmp(argv[i], "--level-grid") && i + 9 < argc)) {
+      const bool grid = !strcmp(argv[i], "--level-grid");
+      float w[6];
+      for (int k = 0; k < 6; k++) w[k] = (float)atof(argv[++i]);
+      int n[3] = {1, 1, 0};
+      if (grid) { n[0] = atoi(argv[++i]); n[1] = atoi(argv[++i]); }
+      n[2] = atoi(argv[++i]);
+      probeOk = probeOk && n[0] > 0 && n[1] > 0 && (long long)n[0] * n[1] + (long long)probeLines.size() <= SPH_PROBE_MAX_LINES;
+      for (int j = 0; probeOk && j < n[1]; j++)
+        for (int ii = 0; ii < n[0]; ii++) {
+          sph_probe_line l = {};
+          for (int k = 0; k < 3; k++) { l.origin[k] = w[k]; l.step[k] = grid ? 0.f : w[3 + k]; }
+          if (grid) { l.origin[0] = w[0] + (float)ii * w[3]; l.origin[1] = w[1] + (float)j * w[4]; l.step[2] = w[5]; }
+          l.count = n[2]; l.field = 1; l.iso = 0.5f; l.typeMask = 1u << SPH_LIQUID_PARTICLE;
+          probeLines.push_back(l);
+        }
+      probeSeen = true;
+    }
+    else if (!strcmp(argv[i], "--probe-every") && i + 1 < argc) { probeEvery = atoi(argv[++i]); probeSeen = true; }
+    else if (!strcmp(argv[i], "--probe-out") && i + 1 < argc) { probeFile = argv[++i]; probeSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -500,6 +534,12 @@ int main(int argc, char** argv) {
   if (gaugeSeen && (!gaugeOk || gaugeDefs.empty() || gaugeEvery <= 0)) {
     fprintf(stderr, "--gauge \"OX OY OZ UX UY UZ VX VY VZ\" (nine numbers in one argument, at most %d gauges) and --gauge-every K (> 0) go "
                     "together; --gauge-plane and --gauge-field SLOT follow the gauge they belong to\n", SPH_MAX_GAUGES);
+    return 2;
+  }
+  if (probeSeen && (!probeOk || (probePoints.empty() && probeLines.empty()) || probeEvery <= 0 || !probeFile ||
+                    probePoints.size() / 4 > SPH_PROBE_MAX_POINTS)) {
+    fprintf(stderr, "--probe X Y Z, --level-line OX OY OZ SX SY SZ N and --level-grid OX OY OZ SX SY SZ NX NY NZ (at most %d points and %d "
+                    "lines) go with --probe-every K (> 0) and --probe-out FILE\n", SPH_PROBE_MAX_POINTS, SPH_PROBE_MAX_LINES);
     return 2;
   }
   if (renSeen && (renEvery <= 0 || !renDir)) {
@@ -713,6 +753,11 @@ int main(int argc, char** argv) {
       if (dyeRegionSeen) ocl_solver->fieldSetRegion(0, 1.0f, dyeRegion, dyeMask);
     }
     for (size_t g = 0; g < gaugeDefs.size(); g++) ocl_solver->gaugeDefine((int)g, &gaugeDefs[g]);  // (behind the dye: a gauge may sum field 0)
+    if (probeSeen) {
+      ocl_solver->probesSetPoints(probePoints.data(), (int)(probePoints.size() / 4), (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE));
+      ocl_solver->probesSetLines(probeLines.data(), (int)probeLines.size());
+      if (steps / probeEvery > 0) ocl_solver->probesHistory(steps / probeEvery);  // every call of the run stays in the ring
+    }
     int64_t bodyMembers = 0;
     if (moving) {
       bodyMembers = ocl_solver->bodyDefineRegion(0, bodyRegion);
@@ -1041,6 +1086,10 @@ int main(int argc, char** argv) {
         }
         helper.report("_gauge: \t\t%9.3f ms\n");
       }
+      if (probeSeen && (iterationCount + 1) % probeEvery == 0) {
+        ocl_solver->probesRecord();  // no wait: the ring is read after the run
+        helper.report("_probes: \t\t%9.3f ms\n");
+      }
       if (bodyFree && ocl_solver->bodyCount(0) > 0) {  // the load of the step just done moves the body (a drain may have taken it)
         std::vector<double> rec((size_t)SPH_MAX_BODIES * SPH_BODY_STATE_WORDS);
         ocl_solver->bodiesAdvance(rec.data());
@@ -1092,6 +1141,19 @@ int main(int argc, char** argv) {
       FILE* f = fopen(outFile, "wb");
       if (!f || fwrite(position_cpp.data(), sizeof(float), position_cpp.size(), f) != position_cpp.size()) throw std::runtime_error("cannot write --out file");
       fclose(f);
+    }
+    if (probeSeen) {
+      const size_t P = probePoints.size() / 4, L = probeLines.size(), words = SPH_PROBE_LEVEL_WORDS;
+      const int calls = steps / probeEvery;
+      std::vector<float> pts((size_t)calls * P * words), lev((size_t)calls * L * words);
+      if (calls > 0) ocl_solver->probesReadHistory(0, calls, pts.data(), lev.data());
+      FILE* f = fopen(probeFile, "wb");
+      bool ok = f && fprintf(f, "sphmi probes calls %d points %zu lines %zu every %d\n", calls, P, L, probeEvery) > 0;
+      for (int c = 0; ok && c < calls; c++)
+        ok = fwrite(pts.data() + (size_t)c * P * words, sizeof(float), P * words, f) == P * words &&
+             fwrite(lev.data() + (size_t)c * L * words, sizeof(float), L * words, f) == L * words;
+      if (!ok || fclose(f) != 0) throw std::runtime_error(std::string("cannot write ") + probeFile);
+      printf("_probes: calls %d points %zu lines %zu\n", calls, P, L);
     }
     if (diagCsv && fclose(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
     if (compCsv && fclose(compCsv) != 0) throw std::runtime_error(std::string("cannot write ") + compFile);

@@ -39,6 +39,13 @@ GAUGE_WORDS = 16  # sph_gauges_accumulate record per gauge (frames.GAUGE_FIELDS)
 GAUGE_TOTAL_WORDS = 20  # sph_gauges_read totals per gauge (frames.GAUGE_TOTAL_FIELDS)
 GAUGE_HISTORY_MAX = 16384
 GAUGE_PLANE = 1  # sph_gauge.flags
+PROBE_MAX_POINTS = 65536  # SPH_PROBE_MAX_POINTS
+PROBE_MAX_LINES = 65536  # SPH_PROBE_MAX_LINES
+PROBE_LINE_MAX = 1024  # points of one line
+PROBE_LEVEL_WORDS = 8  # sph_probes_record record per line (frames.LEVEL_FIELDS); a point record is a sample record
+PROBE_HISTORY_MAX = 16384
+PROBE_HISTORY_BYTES = 1 << 28  # rows * row bytes of the ring
+PROBE_FOUND, PROBE_DRY, PROBE_SUBMERGED = 0, 1, 2  # word 4 of a level record
 # word ranges of that record (include/sphmi.h): name -> (first word, count)
 BODY_STATE_FIELDS = {"status": (0, 1), "members": (1, 1), "advances": (2, 1), "max_move": (3, 1), "position": (4, 3),
                      "orientation": (7, 4), "velocity": (11, 3), "angular_momentum": (14, 3), "omega": (17, 3), "load_force": (20, 3),
@@ -127,6 +134,17 @@ class SphGauge(C.Structure):
                 ("fieldSlot", C.c_int32), ("flags", C.c_uint32)]
 
 
+class SphProbeLine(C.Structure):
+    """sph_probe_line of include/sphmi.h (frames.level_columns builds arrays of PROBE_LINE_DTYPE, the same 40 bytes)."""
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float * 3), ("count", C.c_int32), ("field", C.c_int32), ("iso", C.c_float),
+                ("typeMask", C.c_uint32)]
+
+
+# the same record as a numpy dtype: what probes_set_lines reads and probe_lines returns
+PROBE_LINE_DTYPE = np.dtype([("origin", np.float32, 3), ("step", np.float32, 3), ("count", np.int32), ("field", np.int32),
+                             ("iso", np.float32), ("typeMask", np.uint32)])
+
+
 class SphError(RuntimeError):
     pass
 
@@ -198,7 +216,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_body_read", "sph_body_set_pose", "sph_wall_measure", "sph_wall_diagnostics", "sph_body_set_dynamics",
                     "sph_body_get_dynamics", "sph_bodies_advance", "sph_gauge_define", "sph_gauge_get", "sph_gauges_accumulate",
                     "sph_gauges_read", "sph_gauges_reset", "sph_gauges_history", "sph_gauges_read_history", "sph_gauge_crossings",
-                    "sph_read_gauge_crossings"] + _STAGE_FUNCS
+                    "sph_read_gauge_crossings", "sph_probes_set_points", "sph_probes_set_lines", "sph_probes_count", "sph_probes_record",
+                    "sph_probes_history", "sph_probes_read_history"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_step_band_defer_first", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -350,6 +369,13 @@ def device_lib():
             L.sph_gauges_read_history.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
             L.sph_gauge_crossings.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
             L.sph_read_gauge_crossings.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_probes_record"):  # (optional: an A/B library built from an older csrc/ has no probes)
+            L.sph_probes_set_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32]
+            L.sph_probes_set_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            L.sph_probes_count.argtypes = [C.c_void_p, C.c_void_p]
+            L.sph_probes_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sph_probes_history.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_probes_read_history.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -649,6 +675,38 @@ def _field_index(field, names, what):
             raise SphError("%s: field must be one of %s" % (what, names))
         field = names.index(field)
     return int(field)
+
+
+def probe_lines(lines):
+    """Level-probe lines as the contiguous PROBE_LINE_DTYPE array probes_set_lines reads: an array of that dtype (any shape is
+    refused but [L]), a SphProbeLine, or a sequence of SphProbeLine or of dicts (origin, step, count, field = name or 0..5, iso,
+    types or typeMask). None or nothing: no lines."""
+    from . import frames
+    if lines is None:
+        return np.zeros(0, PROBE_LINE_DTYPE)
+    if isinstance(lines, np.ndarray):
+        if lines.dtype != PROBE_LINE_DTYPE or lines.ndim != 1:
+            raise SphError("probes_set_lines: a line array must be [L] of PROBE_LINE_DTYPE (40 bytes a line)")
+        return np.ascontiguousarray(lines)
+    if isinstance(lines, (SphProbeLine, dict)):
+        lines = [lines]
+    out = np.zeros(len(lines), PROBE_LINE_DTYPE)
+    for i, ln in enumerate(lines):
+        if isinstance(ln, SphProbeLine):
+            out[i] = (tuple(ln.origin), tuple(ln.step), ln.count, ln.field, ln.iso, ln.typeMask)
+            continue
+        if not isinstance(ln, dict):
+            raise SphError("probes_set_lines: line %d is neither a SphProbeLine nor a dict" % i)
+        for name in ("origin", "step"):
+            a = np.asarray(ln[name], np.float32).reshape(-1)
+            if a.size != 3:
+                raise SphError("probes_set_lines: line %d: %s must hold 3 floats" % (i, name))
+            out[i][name] = a
+        out[i]["count"] = int(ln["count"])
+        out[i]["field"] = _field_index(ln.get("field", "shepard"), frames.GRID_FIELDS[:SURFACE_FIELDS], "probes_set_lines")
+        out[i]["iso"] = np.float32(ln.get("iso", 0.5))
+        out[i]["typeMask"] = int(ln["typeMask"]) if "typeMask" in ln else type_mask(ln.get("types", (1,)))
+    return out
 
 
 def build_info():
@@ -1321,6 +1379,50 @@ class owHIPSolver:
         tab = np.zeros((max(n, 1), 3), np.float32)
         self._chk(self._L.sph_read_gauge_crossings(self._h, _ptr(idx), _ptr(ids), _ptr(way), _ptr(tab)))
         return idx[:n], ids[:n], way[:n], tab[:n]
+
+    # --- probes (sph_probes_*): point samples and water levels on lines, recorded per call, with a history ring on the device ---
+    def probes_set_points(self, points, types=(1, 2, 3)):
+        """Replace the point probes by `points` ([P, 3] or [P, 4]; None or nothing releases them), sampled over `types`."""
+        p4 = _points4(points, "probes_set_points") if points is not None and np.size(points) else np.zeros((0, 4), np.float32)
+        self._chk(self._L.sph_probes_set_points(self._h, _ptr(p4) if p4.size else None, p4.shape[0], type_mask(types)))
+
+    def probes_set_lines(self, lines):
+        """Replace the level probes by `lines` (see probe_lines; frames.level_columns builds them; None or nothing releases them)."""
+        ln = probe_lines(lines)
+        self._chk(self._L.sph_probes_set_lines(self._h, _ptr(ln) if ln.size else None, ln.shape[0]))
+
+    def probes_count(self):
+        """(point probes, level probes) the solver holds."""
+        c = np.zeros(2, np.int32)
+        self._chk(self._L.sph_probes_count(self._h, _ptr(c)))
+        return int(c[0]), int(c[1])
+
+    def probes_record(self, read=True):
+        """Every probe's record of the last completed step, written to the history ring on the device. read=True waits once and
+        returns (points float32[P, 8], the sample_points records; levels float32[L, 8], frames.LEVEL_FIELDS); read=False enqueues
+        everything and returns None without a wait."""
+        if not read:
+            self._chk(self._L.sph_probes_record(self._h, None, None))
+            return None
+        P, L = self.probes_count()
+        pts, lev = np.zeros((P, SAMPLE_WORDS), np.float32), np.zeros((L, PROBE_LEVEL_WORDS), np.float32)
+        one = np.zeros(PROBE_LEVEL_WORDS, np.float32)  # (a non-NULL pointer even with nothing to copy: this call waits)
+        self._chk(self._L.sph_probes_record(self._h, _ptr(pts) if P else _ptr(one), _ptr(lev) if L else _ptr(one)))
+        return pts, lev
+
+    def probes_history(self, rows):
+        """Keep the records of the last `rows` probes_record calls in a ring on the device (0 releases it)."""
+        self._chk(self._L.sph_probes_history(self._h, int(rows)))
+
+    def probe_history(self, first, count):
+        """(points float32[count, P, 8], levels float32[count, L, 8]): the records of probes_record calls first .. first + count - 1,
+        while the ring holds them."""
+        P, L = self.probes_count()
+        n = max(int(count), 0)
+        pts, lev = np.zeros((n, P, SAMPLE_WORDS), np.float32), np.zeros((n, L, PROBE_LEVEL_WORDS), np.float32)
+        self._chk(self._L.sph_probes_read_history(self._h, int(first), int(count), _ptr(pts) if pts.size else None,
+                                                  _ptr(lev) if lev.size else None, None))
+        return pts, lev
 
     # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
     def _field_values(self, values, what):

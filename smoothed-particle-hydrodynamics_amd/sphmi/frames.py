@@ -47,6 +47,10 @@ format `sphmi_run --stream-out` writes.
 Kinematic bodies (owHIPSolver.body_set_pose): `pose_identity`, `pose_translate`, `pose_rotate` and `pose_compose` build the
 float32[3, 4] pose (R | t) in float64 and narrow it once; `piston` and `spin` return the pose of a wave-maker or a blade for a
 step number, always relative to the body's reference placement.
+
+Probes (owHIPSolver.probes_set_lines / probes_record / probe_history, level records named by LEVEL_FIELDS): `level_columns` makes one
+level-probe line per column of a lattice, `level_heights` turns level records into the height map `free_surface_height` gives from
+a whole grid, `probe_series` takes one word out of a history, `read_probes` loads the file `sphmi_run --probe-out` writes.
 """
 import math
 import struct
@@ -1185,3 +1189,76 @@ def gauge_summary(record_or_total, cfg, calls=1):
             out["centroid_" + name] = h[6:8] / h[0]
     out["field_flux"] = p[5] - m[5]
     return out
+
+
+# the 8 words of a level-probe record (include/sphmi.h, sph_probes_record): where the level is, the fractional point index,
+# PROBE_FOUND / PROBE_DRY / PROBE_SUBMERGED, the index K of the inside point (-1: none) and the field at K and at K + 1
+LEVEL_FIELDS = ("x", "y", "z", "index", "status", "k", "f_inside", "f_outside")
+
+
+def level_columns(origin, spacing, dims, axis=2, field="shepard", iso=0.5, types=(1,)):
+    """One level-probe line per column of the lattice origin + (float)i * spacing, i < dims, along `axis`, with the far end up: a
+    line starts at the column's lowest lattice point, steps by spacing[axis] and has dims[axis] points, so its points are the
+    lattice's own, bit for bit. The columns come in the lattice's order over the other two axes, the lower axis fastest (axis 2: a
+    [ny, nx] map). An array of PROBE_LINE_DTYPE for owHIPSolver.probes_set_lines."""
+    from . import PROBE_LINE_DTYPE, SURFACE_FIELDS, _field_index, type_mask
+    o = np.asarray(origin, np.float32).reshape(3)
+    sp = np.asarray(spacing, np.float32).reshape(3)
+    dm = [int(v) for v in np.asarray(dims).reshape(3)]
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError("level_columns: axis must be 0, 1 or 2")
+    a, b = [c for c in range(3) if c != axis]  # a runs fastest
+    lines = np.zeros(dm[a] * dm[b], PROBE_LINE_DTYPE)
+    ia, ib = np.meshgrid(np.arange(dm[a]), np.arange(dm[b]))  # [nb, na]
+    org = np.empty((dm[b], dm[a], 3), np.float32)
+    org[..., a] = o[a] + ia.astype(np.float32) * sp[a]
+    org[..., b] = o[b] + ib.astype(np.float32) * sp[b]
+    org[..., axis] = o[axis]
+    lines["origin"] = org.reshape(-1, 3)
+    lines["step"][:, axis] = sp[axis]
+    lines["count"] = dm[axis]
+    lines["field"] = _field_index(field, GRID_FIELDS[:SURFACE_FIELDS], "level_columns")
+    lines["iso"] = np.float32(iso)
+    lines["typeMask"] = type_mask(types)
+    return lines
+
+
+def level_heights(records, axis=2):
+    """The level along `axis` of level-probe records [..., 8]: the crossing's coordinate, the far end's where the line is
+    submerged, NaN where it is dry — the convention of free_surface_height. float64 [...]."""
+    r = np.asarray(records, np.float32)
+    if r.shape[-1] != len(LEVEL_FIELDS):
+        raise ValueError("level_heights: records of %d words" % len(LEVEL_FIELDS))
+    out = r[..., int(axis)].astype(np.float64)
+    out[r[..., 4] == 1.0] = np.nan
+    return out
+
+
+def probe_series(history, word):
+    """One word of every record over a history's calls: history [calls, n, 8] (owHIPSolver.probe_history, either half) and a word
+    number or name (GRID_FIELDS for point records, LEVEL_FIELDS for level records) -> float32 [calls, n]."""
+    h = np.asarray(history, np.float32)
+    if h.ndim != 3 or h.shape[-1] != len(LEVEL_FIELDS):
+        raise ValueError("probe_series: a history is [calls, n, 8]")
+    if isinstance(word, str):
+        names = LEVEL_FIELDS if word in LEVEL_FIELDS else GRID_FIELDS
+        if word not in names:
+            raise ValueError("probe_series: word must be one of %s or %s" % (GRID_FIELDS, LEVEL_FIELDS))
+        word = names.index(word)
+    return np.ascontiguousarray(h[:, :, int(word)])
+
+
+def read_probes(path):
+    """A `sphmi_run --probe-out` file: (points float32[calls, P, 8], levels float32[calls, L, 8], every), the history of the run's
+    probes_record calls, one after every `every` steps."""
+    with open(path, "rb") as f:
+        head = f.readline().split()
+        if head[:2] != [b"sphmi", b"probes"] or head[2::2] != [b"calls", b"points", b"lines", b"every"]:
+            raise ValueError("read_probes: not a probe history")
+        calls, P, L, every = (int(v) for v in head[3::2])
+        data = np.frombuffer(f.read(), np.float32)
+    if data.size != calls * (P + L) * 8:
+        raise ValueError("read_probes: %d words for %d calls of %d points and %d lines" % (data.size, calls, P, L))
+    rows = data.reshape(calls, P + L, 8)
+    return np.ascontiguousarray(rows[:, :P]), np.ascontiguousarray(rows[:, P:]), every
