@@ -1112,6 +1112,76 @@ int sph_probes_record(sph_solver* s, float* points /* host, P x 8, or NULL */, f
 int sph_probes_history(sph_solver* s, int32_t rows /* 0 releases; at most SPH_PROBE_HISTORY_MAX */);
 int sph_probes_read_history(sph_solver* s, int64_t firstCall, int32_t count, float* points, float* levels, int64_t* callsWritten); /* blocking */
 
+/* ---- Time statistics on a lattice: means, covariances, extremes (no reference counterpart) ------------------------
+ * What a flow is reported by: at every node of a fixed lattice, the sums over time of the sampled field, the fraction of time the
+ * node is wet, the call at which matter first arrived, the peak pressure and the call it occurred at. The solver keeps up to
+ * SPH_MAX_STATS lattices (slots); one call after a step folds every node's record into accumulators that stay on the device; no
+ * record is written and nothing waits for the host until the accumulators are read.
+ * RECORD. Everything is a function of the SPH_SAMPLE_WORDS record r that sph_sample_grid(origin, spacing, dims, typeMask) would
+ * return at the node, bit for bit. State, selected set, order of the sums, denormals and the all-zero record of a non-finite point
+ * are those of sph_sample_points: the sorted state of the last completed step. A lattice point may overflow to a non-finite value:
+ * it gives the all-zero record and is simply dry. Every call is read-only on every solver array and is not a stage. Statistics belong
+ * to the solver, as probes do: steps, stages, edits and poses leave the numbers alone, and the lattice is fixed in space.
+ * SLOTS. sph_stats_define gives slot 0..SPH_MAX_STATS-1 the lattice *g and SPH_STATS_WORDS doubles per node, node-major, x fastest
+ * (node = (k * dims[1] + j) * dims[0] + i, as the records of sph_sample_grid), all empty, with calls = 0; g == NULL releases the
+ * slot. SPH_ERR_INVALID, with the slot's old definition and numbers untouched: a slot outside the range, a non-finite word of
+ * origin or spacing, any dims <= 0, a typeMask of 0 or with bits outside 1..3, accumulators above SPH_STATS_BYTES_MAX bytes
+ * (nodes * SPH_STATS_WORDS * 8), a slab solver (every call). sph_stats_get reports a slot: *defined (0 or 1), *out (left alone when
+ * not defined) and *calls; any out pointer may be NULL.
+ * THE FOLD of record r at the slot's call index c (0-based, counted per slot). D(x) = (double)x; rho, vx, vy, vz, p, n are words
+ * 0, 2, 3, 4, 5, 6 of r. If n > 0 (the node is WET in this call), with A the node's words:
+ *   0       A0 += 1                                      wet calls
+ *   1, 2    if (A1 < 0) A1 = c;  A2 = c                  first and last wet call
+ *   3, 4    A3 += D(rho);  A4 += D(rho)*D(rho)
+ *   5..7    += D(vx), D(vy), D(vz)
+ *   8..13   += D(a)*D(b) for ab = xx, yy, zz, xy, xz, yz
+ *   14, 15  A14 += D(p);  A15 += D(p)*D(p)
+ *   16, 17  if (D(rho) > A16) { A16 = D(rho); A17 = c; }
+ *   18, 19  q = (D(vx)*D(vx) + D(vy)*D(vy)) + D(vz)*D(vz);  if (q > A18) { A18 = q; A19 = c; }
+ *   20, 21  if (D(p) > A20) { A20 = D(p); A21 = c; }     peak pressure and its call
+ *   22, 23  if (D(p) < A22) { A22 = D(p); A23 = c; }
+ * A dry call leaves the node's words untouched (n == 0 implies rho == 0, so A3 / calls is still the mean density over all calls).
+ * EMPTY: the sums and word 0 are +0; words 1, 2, 17, 19, 21, 23 are -1; words 16, 18, 20 are -inf; word 22 is +inf. The strict
+ * compares keep the first call of a tie and ignore a NaN; the sums propagate it. Every product above is of two floats widened to
+ * double and therefore exact: contraction cannot change a bit. One node, one lane: no atomics, a fixed order.
+ * ACCUMULATING. sph_stats_accumulate(slot) folds the slot's lattice and increments its call count; slot -1 means every defined
+ * slot, in ascending order. Everything is enqueued on the solver's stream; the call never waits for the host. It is SPH_ERR_ORDER
+ * with nothing defined (the slot, or with -1 any slot) and SPH_ERR_INVALID for a slot outside -1..SPH_MAX_STATS-1; in every other
+ * state it returns exactly what sph_sample_points returns there. A failed call changes no slot and consumes no index.
+ * sph_stats_reset(slot; -1: every defined slot) makes numbers and calls empty again and keeps the definition; SPH_ERR_ORDER for
+ * a slot that is not defined (with -1: never).
+ * READING. sph_stats_read (blocking) copies the SPH_STATS_WORDS doubles of nodes firstNode .. firstNode + count - 1 and *calls (may
+ * be NULL). SPH_ERR_INVALID unless 0 <= firstNode, 0 <= count and firstNode + count <= nodes, and for a null `out` with count > 0;
+ * SPH_ERR_ORDER for a slot that is not defined. sph_stats_read_moments (blocking, the same window rule) computes
+ * SPH_STATS_MOMENT_WORDS floats per node on the device, in double, one rounded operation at a time in the written order, each value
+ * then cast to float; C = calls, n = A0:
+ *   0       n/C                                          wet fraction
+ *   1       A3/C                                         mean density over all calls
+ *   2       A4/C - (A3/C)*(A3/C)
+ *   3..5    m_a = A(5+a)/n                               mean velocity over the wet calls
+ *   6..11   A(8+i)/n - m_a*m_b for ab = xx, yy, zz, xy, xz, yz      velocity covariances (Reynolds stresses / density)
+ *   12      mp = A14/n
+ *   13      A15/n - mp*mp
+ *   14      A1                                           arrival call
+ *   15      A20                                          peak pressure
+ * With n == 0, words 3..13 and 15 are +0 and word 14 is -1. It is SPH_ERR_ORDER while calls == 0.
+ * SCOPE. Unweighted calls; no gradient quantities; no history of the accumulators; no lattice that moves with a body. */
+#define SPH_MAX_STATS 4
+#define SPH_STATS_WORDS 24
+#define SPH_STATS_MOMENT_WORDS 16
+#define SPH_STATS_BYTES_MAX ((int64_t)1 << 31) /* accumulators of one slot */
+typedef struct sph_stats_lattice { /* 40 bytes */
+  float origin[3], spacing[3];
+  int32_t dims[3];    /* nx, ny, nz */
+  uint32_t typeMask;  /* as sampling */
+} sph_stats_lattice;
+int sph_stats_define(sph_solver* s, int32_t slot, const sph_stats_lattice* g /* NULL releases the slot */);
+int sph_stats_get(sph_solver* s, int32_t slot, sph_stats_lattice* out, int32_t* defined, int64_t* calls);
+int sph_stats_accumulate(sph_solver* s, int32_t slot /* -1: every defined slot */); /* no host wait */
+int sph_stats_reset(sph_solver* s, int32_t slot /* -1: all */);
+int sph_stats_read(sph_solver* s, int32_t slot, int64_t firstNode, int64_t count, double* out /* host, count x 24 */, int64_t* calls); /* blocking */
+int sph_stats_read_moments(sph_solver* s, int32_t slot, int64_t firstNode, int64_t count, float* out /* host, count x 16 */, int64_t* calls); /* blocking */
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (sph_api.hip: errors, timing, solver lifetime, stages, the fused step; sph_api_read.hip:
 // read-back and reference-layout export; sph_api_slab.hip: the slab protocol; sph_api_analysis.hip: sampling, surfaces, gradients,
-// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields; sph_api_body.hip: kinematic bodies; sph_api_gauge.hip: flow gauges; sph_api_probe.hip: probes): the order contract and the entry checks,
+// diagnostics, components, selection, integral curves, rendering; sph_api_edit.hip: particle editing; sph_api_fields.hip: carried fields; sph_api_body.hip: kinematic bodies; sph_api_gauge.hip: flow gauges; sph_api_probe.hip: probes; sph_api_stats.hip: time statistics on a lattice): the order contract and the entry checks,
 // the one rule for "the state has changed" and for results derived from it, and the per-particle input checks of sph_create
 // and the adding calls.
 #pragma once

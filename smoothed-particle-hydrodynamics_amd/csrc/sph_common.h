@@ -304,6 +304,12 @@ struct sph_solver {
   int64_t probeCalls = 0;             // successful sph_probes_record calls so far: the index of the next one
   int probeHistRows = 0;
   int64_t probeHistFirst = 0;
+  // time statistics (sph_stats_*, sph_stats.hip): per slot the lattice as given, its accumulators on the device
+  // (SPH_STATS_WORDS doubles per node; the buffer exists exactly while the slot is defined) and the index of the next call.
+  // statsOut: the bounded scratch sph_stats_read_moments goes through. Independent of the particle state, like the probes.
+  sph_stats_lattice statsLattice[SPH_MAX_STATS] = {};
+  SphScratch statsAcc[SPH_MAX_STATS], statsOut;
+  int64_t statsCalls[SPH_MAX_STATS] = {};
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -634,6 +640,12 @@ int sphk_gauge_list(sph_solver* s, const GaugeOne& g, const int32_t* list, int n
 // sphk_sample_points; the level kernel takes each line's own typeMask.
 int sphk_probe_points(sph_solver* s, const SampleArgs& a, const float* pts4, int count, float* cur, float* row);
 int sphk_probe_levels(sph_solver* s, const SampleArgs& a, const sph_probe_line* lines, int count, float* cur, float* row);
+// sph_stats.hip (time statistics on a lattice; read-only on every solver array). Device pointers. acc: the slot's
+// SPH_STATS_WORDS doubles per node; `a` as for sphk_sample_points with the lattice's typeMask; call: the slot's call index.
+int sphk_stats_accumulate(sph_solver* s, const SampleArgs& a, const sph_stats_lattice& g, int64_t call, double* acc);
+int sphk_stats_init(sph_solver* s, double* acc, int64_t nodes);  // the empty values
+// the SPH_STATS_MOMENT_WORDS floats of `count` nodes from `node` on, after `calls` calls
+int sphk_stats_moments(sph_solver* s, const double* node, int64_t count, int64_t calls, float* out);
 // sph_fields.hip (carried particle fields: paint, diffuse along the neighbour rows, reduce). `field`: a slot's
 // values in original-id order (device). Read-only on every solver array.
 size_t sphk_field_scratch_bytes(int N);  // two float2 records per particle (ping-pong) and the stability word

@@ -325,6 +325,31 @@ class owHIPSolver {
     return calls;
   }
 
+  // beyond the reference: time statistics on a lattice. Up to SPH_MAX_STATS lattices kept by the solver; after a completed step
+  // statsAccumulate folds the sample record at every node of a slot (-1: of every defined slot) into SPH_STATS_WORDS doubles per
+  // node that stay on the device, without a host wait. statsRead copies the accumulators of nodes firstNode .. firstNode + count - 1
+  // (node-major, x fastest), statsReadMoments the SPH_STATS_MOMENT_WORDS floats computed from them on the device; both return the
+  // slot's calls. statsDefine with a null lattice (statsRelease) frees the slot (include/sphmi.h, sph_stats_*)
+  void statsDefine(int slot, const sph_stats_lattice* g) { check(sph_stats_define(s_, slot, g), "statsDefine"); }
+  void statsRelease(int slot) { check(sph_stats_define(s_, slot, nullptr), "statsRelease"); }
+  bool statsGet(int slot, sph_stats_lattice* out, int64_t* calls = nullptr) {
+    int32_t defined = 0;
+    check(sph_stats_get(s_, slot, out, &defined, calls), "statsGet");
+    return defined != 0;
+  }
+  void statsAccumulate(int slot = -1) { check(sph_stats_accumulate(s_, slot), "statsAccumulate"); }
+  void statsReset(int slot = -1) { check(sph_stats_reset(s_, slot), "statsReset"); }
+  int64_t statsRead(int slot, int64_t firstNode, int64_t count, double* out) {
+    int64_t calls = 0;
+    check(sph_stats_read(s_, slot, firstNode, count, out, &calls), "statsRead");
+    return calls;
+  }
+  int64_t statsReadMoments(int slot, int64_t firstNode, int64_t count, float* out) {
+    int64_t calls = 0;
+    check(sph_stats_read_moments(s_, slot, firstNode, count, out, &calls), "statsReadMoments");
+    return calls;
+  }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

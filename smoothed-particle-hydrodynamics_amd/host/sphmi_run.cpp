@@ -107,6 +107,13 @@
 //        line `sphmi probes calls C points P lines L every K`, then C x (P + L) x 8 raw float32 words, a call's point records in
 //        front of its line records (frames.read_probes). One line is printed: `_probes: calls C points P lines L`. The ring's limits
 //        (SPH_PROBE_HISTORY_MAX calls, 2^28 bytes) bound steps / K.
+//   ... --stats-grid OX OY OZ SX SY SZ NX NY NZ [--stats-types "T ..."] [--stats-from S] [--stats-every K] --stats-out FILE
+//        time statistics (sph_stats_*) on the lattice OX.. + i * SX.., i < NX NY NZ, over the particle types T
+//        (1 liquid, 2 elastic, 3 boundary; default: liquid). After step S + 1 (default S = 0: the first step) and every K-th step
+//        behind it (default 1) the lattice is folded into accumulators on the device without a wait; they are read ONCE, at the
+//        end, and written to FILE: the text line `sphmi stats calls C from S every K nx NX ny NY nz NZ`, the 40 bytes of the
+//        sph_stats_lattice, then NX x NY x NZ x 24 raw float64 words, x fastest (frames.read_stats). One line is printed:
+//        `_stats: calls C nodes N`.
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -283,6 +290,8 @@ int main(int argc, char** argv) {
   std::vector<sph_gauge> gaugeDefs; int gaugeEvery = 0; bool gaugeSeen = false, gaugeOk = true;
   std::vector<float> probePoints; std::vector<sph_probe_line> probeLines; int probeEvery = 0; bool probeSeen = false, probeOk = true;
   const char* probeFile = nullptr;
+  sph_stats_lattice statsGrid = {}; int statsFrom = 0, statsEvery = 1, statsCalls = 0; bool statsSeen = false, statsGridSeen = false;
+  const char* statsFile = nullptr;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -393,6 +402,22 @@ int main(int argc, char** argv) {
     }
     else if (!strcmp(argv[i], "--probe-every") && i + 1 < argc) { probeEvery = atoi(argv[++i]); probeSeen = true; }
     else if (!strcmp(argv[i], "--probe-out") && i + 1 < argc) { probeFile = argv[++i]; probeSeen = true; }
+    else if (!strcmp(argv[i], "--stats-grid") && i + 9 < argc) {
+      for (int k = 0; k < 3; k++) statsGrid.origin[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) statsGrid.spacing[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) statsGrid.dims[k] = atoi(argv[++i]);
+      if (!statsGrid.typeMask) statsGrid.typeMask = 1u << SPH_LIQUID_PARTICLE;
+      statsSeen = statsGridSeen = true;
+    }
+    else if (!strcmp(argv[i], "--stats-types") && i + 1 < argc) {
+      statsGrid.typeMask = 0u;
+      for (const char* p = argv[++i]; *p; p++)
+        if (*p >= '0' && *p <= '9') statsGrid.typeMask |= 1u << (*p - '0');
+      statsSeen = true;
+    }
+    else if (!strcmp(argv[i], "--stats-from") && i + 1 < argc) { statsFrom = atoi(argv[++i]); statsSeen = true; }
+    else if (!strcmp(argv[i], "--stats-every") && i + 1 < argc) { statsEvery = atoi(argv[++i]); statsSeen = true; }
+    else if (!strcmp(argv[i], "--stats-out") && i + 1 < argc) { statsFile = argv[++i]; statsSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -540,6 +565,11 @@ int main(int argc, char** argv) {
                     probePoints.size() / 4 > SPH_PROBE_MAX_POINTS)) {
     fprintf(stderr, "--probe X Y Z, --level-line OX OY OZ SX SY SZ N and --level-grid OX OY OZ SX SY SZ NX NY NZ (at most %d points and %d "
                     "lines) go with --probe-every K (> 0) and --probe-out FILE\n", SPH_PROBE_MAX_POINTS, SPH_PROBE_MAX_LINES);
+    return 2;
+  }
+  if (statsSeen && (!statsGridSeen || statsFrom < 0 || statsEvery <= 0 || !statsFile)) {
+    fprintf(stderr, "--stats-grid OX OY OZ SX SY SZ NX NY NZ goes with --stats-out FILE; --stats-types \"T ...\", --stats-from S (>= 0) and "
+                    "--stats-every K (> 0) need both\n");
     return 2;
   }
   if (renSeen && (renEvery <= 0 || !renDir)) {
@@ -758,6 +788,7 @@ int main(int argc, char** argv) {
       ocl_solver->probesSetLines(probeLines.data(), (int)probeLines.size());
       if (steps / probeEvery > 0) ocl_solver->probesHistory(steps / probeEvery);  // every call of the run stays in the ring
     }
+    if (statsSeen) ocl_solver->statsDefine(0, &statsGrid);
     int64_t bodyMembers = 0;
     if (moving) {
       bodyMembers = ocl_solver->bodyDefineRegion(0, bodyRegion);
@@ -1090,6 +1121,11 @@ int main(int argc, char** argv) {
         ocl_solver->probesRecord();  // no wait: the ring is read after the run
         helper.report("_probes: \t\t%9.3f ms\n");
       }
+      if (statsSeen && iterationCount >= statsFrom && (iterationCount - statsFrom) % statsEvery == 0) {
+        ocl_solver->statsAccumulate(0);  // no wait: the accumulators are read after the run
+        statsCalls++;
+        helper.report("_stats: \t\t%9.3f ms\n");
+      }
       if (bodyFree && ocl_solver->bodyCount(0) > 0) {  // the load of the step just done moves the body (a drain may have taken it)
         std::vector<double> rec((size_t)SPH_MAX_BODIES * SPH_BODY_STATE_WORDS);
         ocl_solver->bodiesAdvance(rec.data());
@@ -1154,6 +1190,18 @@ int main(int argc, char** argv) {
              fwrite(lev.data() + (size_t)c * L * words, sizeof(float), L * words, f) == L * words;
       if (!ok || fclose(f) != 0) throw std::runtime_error(std::string("cannot write ") + probeFile);
       printf("_probes: calls %d points %zu lines %zu\n", calls, P, L);
+    }
+    if (statsSeen) {
+      const size_t nodes = (size_t)statsGrid.dims[0] * statsGrid.dims[1] * statsGrid.dims[2], words = nodes * SPH_STATS_WORDS;
+      std::vector<double> acc(words);
+      const int64_t calls = ocl_solver->statsRead(0, 0, (int64_t)nodes, acc.data());
+      if (calls != statsCalls) throw std::runtime_error("statistics: the slot's calls differ from the calls made");
+      FILE* f = fopen(statsFile, "wb");
+      const bool ok = f && fprintf(f, "sphmi stats calls %lld from %d every %d nx %d ny %d nz %d\n", (long long)calls, statsFrom, statsEvery,
+                                   statsGrid.dims[0], statsGrid.dims[1], statsGrid.dims[2]) > 0 &&
+                      fwrite(&statsGrid, sizeof(statsGrid), 1, f) == 1 && fwrite(acc.data(), sizeof(double), words, f) == words;
+      if (!ok || fclose(f) != 0) throw std::runtime_error(std::string("cannot write ") + statsFile);
+      printf("_stats: calls %lld nodes %zu\n", (long long)calls, nodes);
     }
     if (diagCsv && fclose(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
     if (compCsv && fclose(compCsv) != 0) throw std::runtime_error(std::string("cannot write ") + compFile);

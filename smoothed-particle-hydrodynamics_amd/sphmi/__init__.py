@@ -46,6 +46,16 @@ PROBE_LEVEL_WORDS = 8  # sph_probes_record record per line (frames.LEVEL_FIELDS)
 PROBE_HISTORY_MAX = 16384
 PROBE_HISTORY_BYTES = 1 << 28  # rows * row bytes of the ring
 PROBE_FOUND, PROBE_DRY, PROBE_SUBMERGED = 0, 1, 2  # word 4 of a level record
+MAX_STATS = 4  # SPH_MAX_STATS: time-statistics slots per solver
+STATS_WORDS = 24  # float64 accumulators per lattice node (STATS_FIELDS)
+STATS_MOMENT_WORDS = 16  # sph_stats_read_moments floats per node (STATS_MOMENT_FIELDS)
+STATS_BYTES_MAX = 1 << 31  # accumulators of one slot
+# the accumulators of a node (include/sphmi.h, sph_stats_*): sums over the wet calls, call indices, extremes
+STATS_FIELDS = ("wet_calls", "first_wet_call", "last_wet_call", "sum_rho", "sum_rho2", "sum_vx", "sum_vy", "sum_vz", "sum_vxvx",
+                "sum_vyvy", "sum_vzvz", "sum_vxvy", "sum_vxvz", "sum_vyvz", "sum_p", "sum_p2", "max_rho", "max_rho_call",
+                "max_speed2", "max_speed2_call", "max_p", "max_p_call", "min_p", "min_p_call")
+STATS_MOMENT_FIELDS = ("wet_fraction", "mean_rho", "var_rho", "mean_vx", "mean_vy", "mean_vz", "cov_xx", "cov_yy", "cov_zz", "cov_xy",
+                       "cov_xz", "cov_yz", "mean_p", "var_p", "arrival_call", "peak_p")
 # word ranges of that record (include/sphmi.h): name -> (first word, count)
 BODY_STATE_FIELDS = {"status": (0, 1), "members": (1, 1), "advances": (2, 1), "max_move": (3, 1), "position": (4, 3),
                      "orientation": (7, 4), "velocity": (11, 3), "angular_momentum": (14, 3), "omega": (17, 3), "load_force": (20, 3),
@@ -145,6 +155,14 @@ PROBE_LINE_DTYPE = np.dtype([("origin", np.float32, 3), ("step", np.float32, 3),
                              ("iso", np.float32), ("typeMask", np.uint32)])
 
 
+class SphStatsLattice(C.Structure):
+    """sph_stats_lattice of include/sphmi.h (STATS_LATTICE_DTYPE is the same 40 bytes)."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_int32 * 3), ("typeMask", C.c_uint32)]
+
+
+STATS_LATTICE_DTYPE = np.dtype([("origin", np.float32, 3), ("spacing", np.float32, 3), ("dims", np.int32, 3), ("typeMask", np.uint32)])
+
+
 class SphError(RuntimeError):
     pass
 
@@ -217,7 +235,8 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_body_get_dynamics", "sph_bodies_advance", "sph_gauge_define", "sph_gauge_get", "sph_gauges_accumulate",
                     "sph_gauges_read", "sph_gauges_reset", "sph_gauges_history", "sph_gauges_read_history", "sph_gauge_crossings",
                     "sph_read_gauge_crossings", "sph_probes_set_points", "sph_probes_set_lines", "sph_probes_count", "sph_probes_record",
-                    "sph_probes_history", "sph_probes_read_history"] + _STAGE_FUNCS
+                    "sph_probes_history", "sph_probes_read_history", "sph_stats_define", "sph_stats_get", "sph_stats_accumulate",
+                    "sph_stats_reset", "sph_stats_read", "sph_stats_read_moments"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_step_band_defer_first", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -376,6 +395,13 @@ def device_lib():
             L.sph_probes_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
             L.sph_probes_history.argtypes = [C.c_void_p, C.c_int32]
             L.sph_probes_read_history.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_stats_accumulate"):  # (optional: an A/B library built from an older csrc/ has no time statistics)
+            L.sph_stats_define.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            L.sph_stats_get.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sph_stats_accumulate.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_stats_reset.argtypes = [C.c_void_p, C.c_int32]
+            L.sph_stats_read.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+            L.sph_stats_read_moments.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -675,6 +701,21 @@ def _field_index(field, names, what):
             raise SphError("%s: field must be one of %s" % (what, names))
         field = names.index(field)
     return int(field)
+
+
+def stats_lattice(origin, spacing, dims, types=(1,)):
+    """A statistics lattice as the one-element STATS_LATTICE_DTYPE array stats_define reads: origin and spacing of 3 floats, dims
+    (nx, ny, nz) of 3 ints (anything else is refused here), the types as a mask for the library to judge."""
+    o, sp, dm = np.asarray(origin, np.float32), np.asarray(spacing, np.float32), np.asarray(dims)
+    if o.size != 3 or sp.size != 3 or dm.size != 3:
+        raise SphError("stats_define: origin, spacing and dims must hold 3 values each")
+    if dm.dtype.kind not in "iu":
+        raise SphError("stats_define: dims must be integers")
+    if (np.abs(dm.astype(np.int64)) > 0x7fffffff).any():
+        raise SphError("stats_define: dims do not fit 32 bits")
+    g = np.zeros(1, STATS_LATTICE_DTYPE)
+    g["origin"], g["spacing"], g["dims"], g["typeMask"] = o.reshape(3), sp.reshape(3), dm.reshape(3), type_mask(types)
+    return g
 
 
 def probe_lines(lines):
@@ -1423,6 +1464,61 @@ class owHIPSolver:
         self._chk(self._L.sph_probes_read_history(self._h, int(first), int(count), _ptr(pts) if pts.size else None,
                                                   _ptr(lev) if lev.size else None, None))
         return pts, lev
+
+    # --- time statistics on a lattice (sph_stats_*): per-node sums, call indices and extremes that stay on the device ---
+    def stats_define(self, slot, origin, spacing, dims, types=(1,)):
+        """Give statistics slot `slot` (0..3) the lattice origin + (float)i * spacing, i < dims = (nx, ny, nz), sampled over `types`
+        as sample_grid samples it; its accumulators start empty, with no call made."""
+        g = stats_lattice(origin, spacing, dims, types)
+        self._chk(self._L.sph_stats_define(self._h, int(slot), _ptr(g)))
+
+    def stats_release(self, slot):
+        self._chk(self._L.sph_stats_define(self._h, int(slot), None))
+
+    def stats_get(self, slot):
+        """(lattice, calls): the slot's definition as a dict (origin, spacing, dims, typeMask), or None while it has none, and
+        the accumulate calls it has taken."""
+        g, has, calls = np.zeros(1, STATS_LATTICE_DTYPE), np.zeros(1, np.int32), np.zeros(1, np.int64)
+        self._chk(self._L.sph_stats_get(self._h, int(slot), _ptr(g), _ptr(has), _ptr(calls)))
+        if not has[0]:
+            return None, int(calls[0])
+        return {"origin": g["origin"][0].copy(), "spacing": g["spacing"][0].copy(), "dims": tuple(int(v) for v in g["dims"][0]),
+                "typeMask": int(g["typeMask"][0])}, int(calls[0])
+
+    def stats_accumulate(self, slot=-1):
+        """Fold the sample record of the last completed step at every node of slot `slot` (-1: every defined slot) into its
+        accumulators. Enqueued; never waits for the host. Once per step: a second call counts the step again."""
+        self._chk(self._L.sph_stats_accumulate(self._h, int(slot)))
+
+    def stats_reset(self, slot=-1):
+        """Empty the numbers and the call count of slot `slot`, or of every defined slot; the definitions stay."""
+        self._chk(self._L.sph_stats_reset(self._h, int(slot)))
+
+    def _stats_window(self, slot, first, count, what):
+        g, calls = self.stats_get(slot)
+        if g is None:
+            raise SphError("%s: slot %d is not defined" % (what, int(slot)))
+        nx, ny, nz = g["dims"]
+        nodes = nx * ny * nz
+        whole = first is None and count is None
+        first = 0 if first is None else int(first)
+        count = nodes - first if count is None else int(count)
+        return first, count, ((nz, ny, nx) if whole else (max(count, 0),))  # (the library judges the window)
+
+    def stats(self, slot, first=None, count=None):
+        """(float64[nz, ny, nx, 24] named by STATS_FIELDS, calls). With first / count: the nodes first .. first + count - 1 of the
+        node-major order (x fastest), float64[count, 24]. Blocking."""
+        first, count, shape = self._stats_window(slot, first, count, "stats")
+        out, calls = np.zeros(shape + (STATS_WORDS,), np.float64), np.zeros(1, np.int64)
+        self._chk(self._L.sph_stats_read(self._h, int(slot), first, count, _ptr(out) if count else None, _ptr(calls)))
+        return out, int(calls[0])
+
+    def stats_moments(self, slot, first=None, count=None):
+        """(float32[nz, ny, nx, 16] named by STATS_MOMENT_FIELDS, calls), computed on the device; windows as stats(). Blocking."""
+        first, count, shape = self._stats_window(slot, first, count, "stats_moments")
+        out, calls = np.zeros(shape + (STATS_MOMENT_WORDS,), np.float32), np.zeros(1, np.int64)
+        self._chk(self._L.sph_stats_read_moments(self._h, int(slot), first, count, _ptr(out) if count else None, _ptr(calls)))
+        return out, int(calls[0])
 
     # --- carried particle fields (sph_field_*): a scalar of the user's own per particle, in original-id order ---
     def _field_values(self, values, what):

@@ -51,6 +51,11 @@ step number, always relative to the body's reference placement.
 Probes (owHIPSolver.probes_set_lines / probes_record / probe_history, level records named by LEVEL_FIELDS): `level_columns` makes one
 level-probe line per column of a lattice, `level_heights` turns level records into the height map `free_surface_height` gives from
 a whole grid, `probe_series` takes one word out of a history, `read_probes` loads the file `sphmi_run --probe-out` writes.
+
+Time statistics (owHIPSolver.stats_define / stats_accumulate / stats, accumulators named by sphmi.STATS_FIELDS): `stats_moments`
+restates the device's moment words in float64, `stats_summary` names what a flow is reported by (wet fraction, mean velocity,
+stress tensor, TKE, pressure mean and rms, arrival call, peak pressure and its call), `write_vtk_stats` writes that as a VTK lattice,
+`read_stats` loads the file `sphmi_run --stats-out` writes.
 """
 import math
 import struct
@@ -1247,6 +1252,107 @@ def probe_series(history, word):
             raise ValueError("probe_series: word must be one of %s or %s" % (GRID_FIELDS, LEVEL_FIELDS))
         word = names.index(word)
     return np.ascontiguousarray(h[:, :, int(word)])
+
+
+def stats_moments(acc, calls):
+    """The 16 moment words of sph_stats_read_moments (sphmi.STATS_MOMENT_FIELDS) from accumulators [..., 24]
+    (owHIPSolver.stats), in float64 before the narrowing to float: the same operations in the same order, so
+    stats_moments(acc, calls).astype(float32) is what owHIPSolver.stats_moments returns, bit for bit. calls >= 1."""
+    from . import STATS_MOMENT_WORDS, STATS_WORDS
+    a = np.asarray(acc, np.float64)
+    if a.shape[-1] != STATS_WORDS:
+        raise ValueError("stats_moments: accumulators of %d words" % STATS_WORDS)
+    if int(calls) < 1:
+        raise ValueError("stats_moments: no call has been made")
+    C = np.float64(int(calls))
+    n = a[..., 0]
+    wet = n > 0
+    out = np.zeros(a.shape[:-1] + (STATS_MOMENT_WORDS,), np.float64)
+    with np.errstate(all="ignore"):
+        out[..., 0] = n / C
+        mr = a[..., 3] / C
+        out[..., 1] = mr
+        out[..., 2] = a[..., 4] / C - mr * mr
+        nn = np.where(wet, n, 1.0)
+        m = [a[..., 5 + k] / nn for k in range(3)]
+        for k in range(3):
+            out[..., 3 + k] = m[k]
+        for w, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            out[..., 6 + w] = a[..., 8 + w] / nn - m[i] * m[j]
+        mp = a[..., 14] / nn
+        out[..., 12] = mp
+        out[..., 13] = a[..., 15] / nn - mp * mp
+    out[..., 14] = a[..., 1]
+    out[..., 15] = a[..., 20]
+    out[..., 3:14][~wet] = 0.0
+    out[..., 15][~wet] = 0.0
+    out[..., 14][~wet] = -1.0
+    return out
+
+
+def stats_summary(acc, calls):
+    """What a flow is reported by, from accumulators [..., 24] (owHIPSolver.stats) after `calls` calls, float64: `wet_fraction`,
+    `mean_velocity` [..., 3], `stress` [..., 3, 3] (the symmetric velocity covariance <u_a' u_b'>: times the density, the Reynolds
+    stresses), `tke` = (xx + yy + zz) / 2, `mean_pressure`, `rms_pressure` (the root of the variance, which rounding may leave a
+    little below 0: clamped there), `arrival_call` (-1: never wet), `peak_pressure` and `peak_pressure_call` (-1). The moments are
+    stats_moments', so a node that was never wet has zeros."""
+    a = np.asarray(acc, np.float64)
+    m = stats_moments(a, calls)
+    stress = np.empty(m.shape[:-1] + (3, 3), np.float64)
+    for w, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+        stress[..., i, j] = m[..., 6 + w]
+        stress[..., j, i] = m[..., 6 + w]
+    return {"wet_fraction": m[..., 0], "mean_velocity": m[..., 3:6], "stress": stress,
+            "tke": 0.5 * ((m[..., 6] + m[..., 7]) + m[..., 8]), "mean_pressure": m[..., 12],
+            "rms_pressure": np.sqrt(np.maximum(m[..., 13], 0.0)), "arrival_call": m[..., 14], "peak_pressure": m[..., 15],
+            "peak_pressure_call": a[..., 21]}
+
+
+def write_vtk_stats(path, origin, spacing, acc, calls):
+    """Legacy-VTK STRUCTURED_POINTS (binary, big-endian like write_vtk_grid) of the statistics `acc` [nz, ny, nx, 24] after `calls`
+    calls: scalars `wet_fraction`, `tke`, `mean_pressure`, `rms_pressure`, `arrival_call`, `peak_pressure`, `peak_pressure_call`,
+    vectors `mean_velocity` and the six `stress_ab` scalars. Returns the node count."""
+    a = np.asarray(acc, np.float64)
+    if a.ndim != 4:
+        raise ValueError("write_vtk_stats: accumulators must be [nz, ny, nx, 24]")
+    s = stats_summary(a, calls)
+    nz, ny, nx = a.shape[:3]
+    n = nx * ny * nz
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi statistics\nBINARY\nDATASET STRUCTURED_POINTS\n")
+        f.write(("DIMENSIONS %d %d %d\n" % (nx, ny, nz)).encode())
+        f.write(("ORIGIN %.9g %.9g %.9g\n" % tuple(float(np.float32(v)) for v in origin)).encode())
+        f.write(("SPACING %.9g %.9g %.9g\n" % tuple(float(np.float32(v)) for v in spacing)).encode())
+        f.write(("POINT_DATA %d\n" % n).encode())
+        scalars = [(k, s[k]) for k in ("wet_fraction", "tke", "mean_pressure", "rms_pressure", "arrival_call", "peak_pressure",
+                                       "peak_pressure_call")]
+        scalars += [("stress_%s%s" % ("xyz"[i], "xyz"[j]), s["stress"][..., i, j]) for i, j in
+                    ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))]
+        for name, v in scalars:
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(v).astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(b"VECTORS mean_velocity float\n")
+        f.write(np.ascontiguousarray(s["mean_velocity"]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return n
+
+
+def read_stats(path):
+    """A `sphmi_run --stats-out` file: (lattice dict of origin, spacing, dims, typeMask; acc float64[nz, ny, nx, 24]; calls; first
+    step; every), the accumulators as the run left them after one stats_accumulate behind every `every`-th step from `first` on."""
+    with open(path, "rb") as f:
+        head = f.readline().split()
+        if head[:2] != [b"sphmi", b"stats"] or head[2::2] != [b"calls", b"from", b"every", b"nx", b"ny", b"nz"]:
+            raise ValueError("read_stats: not a statistics file")
+        calls, first, every, nx, ny, nz = (int(v) for v in head[3::2])
+        g = np.frombuffer(f.read(40), np.dtype([("origin", np.float32, 3), ("spacing", np.float32, 3), ("dims", np.int32, 3),
+                                                ("typeMask", np.uint32)]))
+        data = np.frombuffer(f.read(), np.float64)
+    if g.size != 1 or tuple(int(v) for v in g["dims"][0]) != (nx, ny, nz) or data.size != nx * ny * nz * 24:
+        raise ValueError("read_stats: %d words for a lattice of %d x %d x %d nodes" % (data.size, nx, ny, nz))
+    lattice = {"origin": g["origin"][0].copy(), "spacing": g["spacing"][0].copy(), "dims": (nx, ny, nz), "typeMask": int(g["typeMask"][0])}
+    return lattice, data.reshape(nz, ny, nx, 24).copy(), calls, first, every
 
 
 def read_probes(path):
