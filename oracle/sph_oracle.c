@@ -217,6 +217,11 @@ static void st_find(sph_oracle* s) {
       for (int k = 0; k < 8; k++) {
         int c = (k == 0) ? myCell
                          : search_cell(myCell, order[k][0] * dx, order[k][1] * dy, order[k][2] * dz, gx, gy, G);
+        /* A key from G on (reference mode takes a particle outside the declared grid) is no entry of the cell table: the
+         * reference reads gridCellIndexFixedUp[myCell] beyond its buffer there, which defines nothing. The restatement takes the
+         * cell the HIP search takes: wrapped like a neighbour cell, then clamped into the table. No-op for a key below G. */
+        if (c >= G) c -= G;
+        c = c < 0 ? 0 : (c > G - 1 ? G - 1 : c);
         found += scan_cell(s, c, me, id, MAXN - found, mode, hist, r_thr);
       }
       if (mode == 0) {
