@@ -59,11 +59,8 @@ static inline int32_t sphPipelineSchedule(int32_t chunks, int32_t depth, int32_t
  * search launches of the chunks c with c + 1 < sphBandDeferFirst need no others and start at the fork; the records of the chunks
  * from sphBandDeferFirst on are scattered beside them, and every later search launch is issued behind that scatter. With three
  * chunks or fewer nothing is deferred and the function returns `chunks`.
- * SPH_BAND_PRELUDE_CHUNKS = 2: chunk 0 alone starts at the fork (measured against 3, profiles/r39/README.md). */
-#ifndef SPH_BAND_PRELUDE_CHUNKS
-#define SPH_BAND_PRELUDE_CHUNKS 2
-#endif
-static inline int32_t sphBandDeferFirst(int32_t chunks) { return chunks > 3 ? SPH_BAND_PRELUDE_CHUNKS : chunks; }
+ * 2: chunk 0 alone starts at the fork (measured against 3, profiles/r39/README.md). */
+static inline int32_t sphBandDeferFirst(int32_t chunks) { return chunks > 3 ? 2 : chunks; }
 
 /* The halo check of chunk [lo, hi) of the sorted particles: 1 only if every particle that findNeighbors can give a particle of
  * the chunk as a neighbour has its sorted index in [below, above) (the pipelined step: below = edge c - 1, above = edge c + 2).

@@ -571,12 +571,8 @@ static_assert(SPH_OVERLAP_CHUNKS >= 1 && SPH_OVERLAP_CHUNKS <= SPH_STEP_CHUNKS_M
 // chunk c lie in chunks c - 1 .. c + 1 the one in-order stream orders every read after its write and every overwrite after its
 // last read, and no array needs a second copy. k_halo_check tests that premise on the device every step and either way leaves two
 // tables by which each stage runs exactly once per particle: chunk by chunk, or over all particles behind the join.
-// The depth the step takes when sph_set_step_pipeline left it automatic: the forces kernel alone. Deeper pipelines were measured
-// and are slower, the whole loop (6) slower than none (profiles/r24/README.md).
-#ifndef SPH_PIPELINE_DEPTH
-#define SPH_PIPELINE_DEPTH 1
-#endif
-static_assert(SPH_PIPELINE_DEPTH >= 0 && SPH_PIPELINE_DEPTH <= SPH_PIPELINE_STAGES_MAX, "pipeline depth");
+// The depth the step takes when sph_set_step_pipeline left it automatic is 1: the forces kernel alone. Deeper pipelines were
+// measured and are slower, the whole loop (6) slower than none (profiles/r24/README.md).
 
 extern "C" int sph_set_step_chunks(sph_solver* s, int32_t chunks) {
   ENTER(s);
@@ -639,7 +635,7 @@ __global__ void k_chunk_edges(uint32_t* edges, ChunkEdges v) {
 
 // Stages of the chunked step that follow the search chunk by chunk (0: none; only asked where the search runs in chunks)
 static int step_pipeline(const sph_solver* s) {
-  return sphPipelineDepth(s->stepPipeline >= 0 ? s->stepPipeline : SPH_PIPELINE_DEPTH, s->cfg.maxIteration, s->d.hasElastic ? 1 : 0);
+  return sphPipelineDepth(s->stepPipeline >= 0 ? s->stepPipeline : 1, s->cfg.maxIteration, s->d.hasElastic ? 1 : 0);
 }
 
 // The halo check of the pipelined step, one lane per chunk (sphChunkHaloOk, sphmi_chunks.h: every table index is clamped there).
@@ -685,25 +681,15 @@ __global__ void k_halo_check(const uint32_t* keys, const uint32_t* cellStart, in
 //    (sph_bands.hip).
 // With two chunks in the prelude chunk 1 starts late, behind the scatter, and the two streaming kernels run beside chunk 0 alone;
 // that measured faster than three chunks in the prelude and the scatter on chunkStream beside chunks 0 and 1, which the streams
-// slow down by more (profiles/r39/README.md). The compile-time switches select that placement (-DSPH_BAND_PRELUDE_CHUNKS=3
-// -DSPH_PRELUDE_DEFER_ON_SEARCH=0) or one part alone (make variant EXTRA=...); results do not depend on them.
-#ifndef SPH_PRELUDE_SPLIT_VEL
-#define SPH_PRELUDE_SPLIT_VEL 1
-#endif
-#ifndef SPH_PRELUDE_DEFER_BANDS
-#define SPH_PRELUDE_DEFER_BANDS 1
-#endif
-#ifndef SPH_PRELUDE_DEFER_ON_SEARCH
-#define SPH_PRELUDE_DEFER_ON_SEARCH 1
-#endif
+// slow down by more, and faster than either part alone (profiles/r39/README.md). Results do not depend on the placement.
 struct PreludeSplit {
   bool vel;        // the gather left sortedVel and backIndex to k_sort_post_vel
   int deferFirst;  // the band records of the chunks from here on are not scattered yet (== chunks: all are)
 };
 static PreludeSplit prelude_split(const sph_solver* s, int chunks, bool bands) {
   PreludeSplit p;
-  p.vel = chunks > 1 && SPH_PRELUDE_SPLIT_VEL;
-  p.deferFirst = (chunks > 1 && bands && SPH_PRELUDE_DEFER_BANDS) ? sphBandDeferFirst(chunks) : chunks;
+  p.vel = chunks > 1;
+  p.deferFirst = (chunks > 1 && bands) ? sphBandDeferFirst(chunks) : chunks;
   // (more chunks than blocks: the deferred chunks may all be empty)
   if (sphChunkEdge(s->d.N, chunks, p.deferFirst) >= s->d.N) p.deferFirst = chunks;
   return p;
@@ -736,12 +722,10 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth, Prelu
   if (split.vel || deferred) {  // chunkStream too: what the searches at the fork do not read
     SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evSearchFork, 0));
     if (split.vel && rc == SPH_OK) rc = sphk_sort_post_vel(s, s->chunkStream);
-    if (deferred) {
-      // on searchStream in front of its first search launch, which then needs no wait (0: on chunkStream behind k_sort_post_vel)
-      hipStream_t ds = SPH_PRELUDE_DEFER_ON_SEARCH ? s->searchStream : s->chunkStream;
-      if (rc == SPH_OK) rc = sphk_band_scatter(s, s->pipeTable, split.deferFirst, chunks, deferCount, false, ds);
-      SPH_HIP(hipEventRecord(s->evDeferred, ds));
-      if (SPH_PRELUDE_DEFER_ON_SEARCH) waited[1] = true;
+    if (deferred) {  // on searchStream in front of its first search launch, which then needs no wait
+      if (rc == SPH_OK) rc = sphk_band_scatter(s, s->pipeTable, split.deferFirst, chunks, deferCount, false, s->searchStream);
+      SPH_HIP(hipEventRecord(s->evDeferred, s->searchStream));
+      waited[1] = true;
     }
   }
   auto launch = [s, N, chunks, split, &waited](int stage, int c) -> int {
@@ -766,7 +750,7 @@ static int enqueue_search_overlapped(sph_solver* s, int chunks, int depth, Prelu
   for (int i = 0; i < items && rc == SPH_OK; i++) rc = launch(stage[i], chunk[i]);
   // The join, on the device, also after a failed launch. Every findNeighbors launch, on either stream, has a density launch behind
   // it on chunkStream, so chunkStream's last event covers searchStream too.
-  if (SPH_PRELUDE_DEFER_ON_SEARCH && deferred) SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evDeferred, 0));  // (no odd chunk may have followed it)
+  if (deferred) SPH_HIP(hipStreamWaitEvent(s->chunkStream, s->evDeferred, 0));  // (no odd chunk may have followed it)
   SPH_HIP(hipEventRecord(s->evChunkJoin, s->chunkStream));
   SPH_HIP(hipStreamWaitEvent(s->stream, s->evChunkJoin, 0));
   // The same stages again over all particles, by the serial table: empty launches unless the halo check failed.
