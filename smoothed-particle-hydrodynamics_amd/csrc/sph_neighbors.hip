@@ -618,10 +618,12 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   }
 
   // ---- 2. replay of the reference's two passes over the short lists, entirely in registers: the list (<= 24 LDS slots
-  // per lane) is expanded once into d2v[] with static indices, 8 entries at a time with a wave-uniform skip. The slots are
+  // per lane) is expanded once into d2p[] with static indices, 8 entries at a time with a wave-uniform skip. The slots are
   // kept (two per register): the list area is about to be reused.
   const int total = segEnd[3];
-  float d2v[FN_LIST_CAP];
+  // d^2 of the entries, two per register pair: the counting loops below subtract two at a time (v_pk_add_f32)
+  f32x2 d2p[FN_LIST_CAP / 2];
+#define FN_D2(e) d2p[(e) >> 1][(e) & 1]
   uint32_t slotPk[FN_LIST_CAP / 2];  // (not with BANDS)
   int idxv[FN_LIST_CAP];  // BANDS only: the entries' sorted indices — own-row entries slot + delta, the others from their records
 #pragma unroll
@@ -649,7 +651,12 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
         const int sl = slotv[u];
         const float ex = me.x - sh.x[sl], ey = me.y - sh.y[sl], ez = me.z - sh.z[sl];
         const float v = ex * ex + ey * ey + ez * ez;
-        d2v[c0 + u] = (c0 + u < total) ? v : __builtin_inff();  // +inf never passes a `<` / `<=` test below
+        // The counting loops below read SIGN BITS of differences, so a NaN (a non-finite candidate record: it hashes to cell 0 and
+        // is staged like any other) must not reach them: as bit patterns both NaN signs lie above +inf — d^2 is a sum of squares,
+        // never negative — and one unsigned minimum turns them into +inf, which is never counted. (Not a float min: what that
+        // does with a signalling NaN depends on the kernel's IEEE mode.)
+        const float vc = __uint_as_float(min(__float_as_uint(v), 0x7f800000u));
+        FN_D2(c0 + u) = (c0 + u < total) ? vc : __builtin_inff();  // +inf is never counted and never accepted below
       }
       if (!BANDS) {
 #pragma unroll
@@ -657,7 +664,7 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
       }
     } else {
 #pragma unroll
-      for (int u = 0; u < FN_CHUNK; u++) d2v[c0 + u] = __builtin_inff();
+      for (int u = 0; u < FN_CHUNK; u++) FN_D2(c0 + u) = __builtin_inff();
       if (BANDS) {
 #pragma unroll
         for (int u = 0; u < FN_CHUNK; u++) idxv[c0 + u] = 0;
@@ -679,14 +686,27 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   for (int it = 0; it < 5; it++) {
     const int mid = (lo + hi) >> 1;  // lo == hi on converged lanes: harmless re-evaluation
     const float U = sh.binU[min(mid, SPH_RSEG - 1)];
-    int c = 0;
+    // d^2 < U  <=>  the sign bit of d^2 - U is set. The build keeps f32 denormals (-fno-gpu-flush-denormals-to-zero), so under
+    // round-to-nearest x != y gives x - y != 0 with the sign of the exact difference; x == y gives +0; a +inf padding entry gives
+    // +inf (U is finite); NaN was turned into +inf at the expansion. Two entries per packed subtraction, one v_alignbit per entry
+    // into a mask word as in the walk, one v_bcnt per word.
+    const f32x2 U2 = {U, U};
+    uint32_t w0 = 0u, w1 = 0u;
 #pragma unroll
     for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {
       if (c0 < liveEnd) {
+        f32x2 df[FN_CHUNK / 2];
 #pragma unroll
-        for (int u = 0; u < FN_CHUNK; u++) c += (d2v[c0 + u] < U) ? 1 : 0;
+        for (int u = 0; u < FN_CHUNK / 2; u++) df[u] = d2p[(c0 >> 1) + u] - U2;  // (the subtractions of a chunk first: their results are not used at once)
+        uint32_t& w = (c0 < 32) ? w0 : w1;
+#pragma unroll
+        for (int u = 0; u < FN_CHUNK / 2; u++) {
+          w = __builtin_amdgcn_alignbit(w, __float_as_uint(df[u].x), 31);
+          w = __builtin_amdgcn_alignbit(w, __float_as_uint(df[u].y), 31);
+        }
       }
     }
+    int c = __popc(w0) + __popc(w1);
     c += pair_other(c);
     if (lo < hi) {
       if (c >= SPH_MAXN) { hi = mid; cAtHi = c; } else lo = mid + 1;
@@ -699,13 +719,30 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
   // ---- 2b. pass 1: hits with d^2 <= r_thr^2 as a bit mask; per-piece counts by popcount, exchanged inside the pair as one
   // packed word; every hit goes to (hits in earlier pieces of the merged order) + (rank inside its piece). Slots >= 32
   // are dropped, which is what the reference's `break` / `spaceLeft` logic amounts to (sphFluid.cl:145,168-169).
-  fn_mask_t acc = 0;
+  //
+  // d^2 <= r2  <=>  the sign bit of r2 - d^2 is clear (equal values give +0, a +inf entry gives -inf; see the bisection). The entries
+  // are shifted in LAST FIRST, so that entry e ends up in bit e of its word whatever liveEnd is, over a word of ones: the entries
+  // never shifted in — those past liveEnd, +inf in every lane — read "rejected" like the sign bits do, and one v_not per word
+  // turns the lot into the mask of the accepted.
+  fn_mask_t acc;
+  {
+    const f32x2 R2 = {r2, r2};
+    uint32_t rj0 = ~0u, rj1 = ~0u;
 #pragma unroll
-  for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {
-    if (c0 < liveEnd) {
+    for (int c0 = FN_LIST_CAP - FN_CHUNK; c0 >= 0; c0 -= FN_CHUNK) {
+      if (c0 < liveEnd) {
+        f32x2 df[FN_CHUNK / 2];
 #pragma unroll
-      for (int u = 0; u < FN_CHUNK; u++) acc |= (d2v[c0 + u] <= r2) ? ((fn_mask_t)1 << (c0 + u)) : (fn_mask_t)0;
+        for (int u = 0; u < FN_CHUNK / 2; u++) df[u] = R2 - d2p[(c0 >> 1) + u];
+        uint32_t& w = (c0 < 32) ? rj0 : rj1;
+#pragma unroll
+        for (int u = FN_CHUNK / 2 - 1; u >= 0; u--) {
+          w = __builtin_amdgcn_alignbit(w, __float_as_uint(df[u].y), 31);
+          w = __builtin_amdgcn_alignbit(w, __float_as_uint(df[u].x), 31);
+        }
+      }
     }
+    acc = ((fn_mask_t)(~rj1) << 32) | (fn_mask_t)(~rj0);
   }
   fn_mask_t below[4];  // bits of the entries before the end of piece i
 #pragma unroll
@@ -722,15 +759,16 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     const int c0b = cellTot & 255, c1b = (cellTot >> 8) & 255, c2b = (cellTot >> 16) & 255, c3b = (cellTot >> 24) & 255;
     const int o0b = otherTot & 255, o1b = (otherTot >> 8) & 255, o2b = (otherTot >> 16) & 255, o3b = (otherTot >> 24) & 255;
     const int run = min(c0b + c1b + c2b + c3b + o0b + o1b + o2b + o3b, SPH_MAXN);
-    // merged order A0 | B1 B2 B3 | A4 A5 | B6 | A7, with a_i, b_i the counts of the lanes' pieces:
-    // lane A (cells 0 4 5 7): 0;  a0 + b0 + b1 + b2;  that + a1;  a0 + a1 + a2 + b0 + b1 + b2 + b3
-    // lane B (cells 1 2 3 6): a0;  a0 + b0;  a0 + b0 + b1;  a0 + a1 + a2 + b0 + b1 + b2
-    const int front = c0b + o0b + (laneB ? c1b + c2b : o1b + o2b);  // a0 + b0 + b1 + b2
-    int start[4];
-    start[0] = laneB ? o0b : 0;
-    start[1] = laneB ? o0b + c0b : front;
-    start[2] = laneB ? o0b + c0b + c1b : front + c1b;
-    start[3] = laneB ? front + o1b + o2b : front + c1b + c2b + o3b;
+    // merged order A0 | B1 B2 B3 | A4 A5 | B6 | A7, with a_i, b_i the counts of the lanes' pieces. Entry e goes to slot
+    // popc(acc & bits below e) + (the partner lane's accepted entries in front of e's piece), and the partner's part changes only
+    // where a piece of the partner's lies between two of this lane's:
+    // lane A (cells 0 4 5 7): 0 | b0 + b1 + b2 (cells 4, 5) | that + b3 (cell 7)
+    // lane B (cells 1 2 3 6): a0 (cells 1, 2, 3) | a0 + a1 + a2 (cell 6)
+    // — two boundaries, segEnd[0] and segEnd[2], and one carried value (tests/test_fn_replay_host.py proves it against a direct merge).
+    const int oFront = o0b + o1b + o2b;
+    const int base0 = laneB ? o0b : 0, base1 = laneB ? o0b : oFront, base2 = laneB ? oFront : oFront + o3b;
+    const uint32_t accLo = (uint32_t)acc, accHi = (uint32_t)(acc >> 32);
+    const int cntLo = __popc(accLo);
     // Ids go straight to the tiled map (4-byte stores); the d^2 of the accepted neighbours go to the wave's staging area
     // [particle][slot], from which each lane of the pair then takes 16 consecutive slots: 16 square roots per lane instead of
     // one per list entry, and the distances leave as four 16-byte stores per lane (which also write the -1 of the unused slots).
@@ -762,52 +800,48 @@ __global__ __launch_bounds__(FN_THREADS, 2) void k_find_neighbors(FnParams d, co
     for (int v = 0; v < FN_SLOTS_PER_LANE / 8; v++)
       *reinterpret_cast<uint4*>(idRow + FN_SLOTS_PER_LANE * laneB + 8 * v) = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
     const uint32_t mapBase = ((uint32_t)(idNow >> 6) * (8u * 64u) + (uint32_t)(idNow & 63)) << 2;  // element index of slot 0 (< 2^32: N <= 2^27)
-    // walk the entries in list order with a running (piece start, index delta, rank inside the piece)
-    int curStart = start[0], curDelta = absDelta[0], rank = 0;
-#pragma unroll
-    for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {
-      if (!__any(c0 < total)) continue;  // wave-uniform skip of empty chunks
-#pragma unroll
-      for (int u = 0; u < FN_CHUNK; u++) {
-        const int e = c0 + u;
-        if (e == segEnd[0]) { curStart = start[1]; curDelta = absDelta[1]; rank = 0; }  // (empty pieces cascade in order)
-        if (e == segEnd[1]) { curStart = start[2]; curDelta = absDelta[2]; rank = 0; }
-        if (e == segEnd[2]) { curStart = start[3]; curDelta = absDelta[3]; rank = 0; }
-        if ((acc >> e) & 1) {
-          const int pos = curStart + rank;
-          rank++;
-          if (pos < SPH_MAXN) {
-            const int jn = BANDS ? idxv[e] : (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
-            const int o16 = jn + own16;
-            idRow[pos] = (uint16_t)((uint32_t)o16 <= (uint32_t)SPH_N16_MAX ? o16 : jn + far16);
-            dstRow[pos] = d2v[e];
-          }
-        }
-      }
+    // Walk the entries in list order: BODY sees the accepted entry e, its slot pos < 32 and its sorted index jn. The bits below e
+    // are a compile-time mask; from entry 32 on the carried value includes the count of the low word. With bands the index comes
+    // from idxv[], without them from the slot and the piece's delta (carried: three boundaries).
+    const int base1h = base1 + cntLo, base2h = base2 + cntLo;
+#define FN_ROW_WALK(...)                                                                                         \
+  {                                                                                                              \
+    int base = base0, curDelta = absDelta[0];                                                                    \
+    _Pragma("unroll") for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {                                       \
+      if (!__any(c0 < total)) continue; /* wave-uniform skip of empty chunks */                                  \
+      _Pragma("unroll") for (int u = 0; u < FN_CHUNK; u++) {                                                     \
+        const int e = c0 + u;                                                                                    \
+        if (e == 32) base += cntLo;                                                                              \
+        if (e == segEnd[0]) base = (e >= 32) ? base1h : base1; /* (empty pieces cascade in order) */             \
+        if (e == segEnd[2]) base = (e >= 32) ? base2h : base2;                                                   \
+        if (!BANDS) {                                                                                            \
+          if (e == segEnd[0]) curDelta = absDelta[1];                                                            \
+          if (e == segEnd[1]) curDelta = absDelta[2];                                                            \
+          if (e == segEnd[2]) curDelta = absDelta[3];                                                            \
+        }                                                                                                        \
+        const uint32_t word = (e < 32) ? accLo : accHi;                                                          \
+        if ((word >> (e & 31)) & 1u) {                                                                           \
+          const int pos = base + __popc(word & ((1u << (e & 31)) - 1u));                                         \
+          if (pos < SPH_MAXN) {                                                                                  \
+            const int jn = BANDS ? idxv[e] : (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;     \
+            __VA_ARGS__                                                                                          \
+          }                                                                                                      \
+        }                                                                                                        \
+      }                                                                                                          \
+    }                                                                                                            \
+  }
+    FN_ROW_WALK({
+      const int o16 = jn + own16;
+      idRow[pos] = (uint16_t)((uint32_t)o16 <= (uint32_t)SPH_N16_MAX ? o16 : jn + far16);
+      dstRow[pos] = FN_D2(e);
+    })
+    if (__any(wide != 0)) {  // (rare) rows without a 16-bit copy: the same walk once more, for the 32-bit ids
+      FN_ROW_WALK({
+        if (wide) nbrId[mapBase + (uint32_t)(((pos >> 2) << 8) + (pos & 3))] = jn;  // tiled map: group stride 64 lanes * 4 slots
+      })
     }
-    if (__any(wide != 0)) {
-    // (rare) rows without a 16-bit copy: the same walk once more, for the 32-bit ids
-    int curStart = start[0], curDelta = absDelta[0], rank = 0;
-#pragma unroll
-    for (int c0 = 0; c0 < FN_LIST_CAP; c0 += FN_CHUNK) {
-      if (!__any(c0 < total)) continue;  // wave-uniform skip of empty chunks
-#pragma unroll
-      for (int u = 0; u < FN_CHUNK; u++) {
-        const int e = c0 + u;
-        if (e == segEnd[0]) { curStart = start[1]; curDelta = absDelta[1]; rank = 0; }  // (empty pieces cascade in order)
-        if (e == segEnd[1]) { curStart = start[2]; curDelta = absDelta[2]; rank = 0; }
-        if (e == segEnd[2]) { curStart = start[3]; curDelta = absDelta[3]; rank = 0; }
-        if ((acc >> e) & 1) {
-          const int pos = curStart + rank;
-          rank++;
-          if (pos < SPH_MAXN) {
-            const int jn = BANDS ? idxv[e] : (int)((slotPk[e >> 1] >> ((e & 1) * 16)) & 0xffffu) + curDelta;
-            if (wide) nbrId[mapBase + (uint32_t)(((pos >> 2) << 8) + (pos & 3))] = jn;  // tiled map: group stride 64 lanes * 4 slots
-          }
-        }
-      }
-    }
-    }
+#undef FN_ROW_WALK
+#undef FN_D2
     if (wide) {  // K1 folded in: unused slots of the 32-bit row (the 16-bit ones are pre-filled)
       for (int k = run + laneB; k < SPH_MAXN; k += 2) nbrId[mapBase + (uint32_t)(((k >> 2) << 8) + (k & 3))] = -1;
     }
