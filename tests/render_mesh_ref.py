@@ -156,7 +156,8 @@ def render_mesh(view, pos, tris, shading=0, normals=None, colour=(0.8, 0.8, 0.8)
     rgba), None for a fresh image. Extra keys: `cover` (how many drawn triangles cover each pixel centre, whether or not their
     fragment exists), `winners` (distinct winning triangles), `queued` (drawn triangles whose clipped box is above 8 pixels a
     side), `partly_outside` (drawn triangles whose box crosses the image border and still meets the image), `unusable` and
-    `degenerate` (the two reasons for a skip), `ties` (pixels whose winning depth bits came from more than one triangle)."""
+    `degenerate` (the two reasons for a skip), `ties` (pixels whose winning depth bits came from more than one triangle),
+    `boxes` (the drawn triangles t and their clipped boxes)."""
     W, H = int(view.width), int(view.height)
     pos = np.asarray(pos, np.float32).reshape(-1, 3)
     S = Setup(view, pos, tris)
@@ -226,7 +227,7 @@ def render_mesh(view, pos, tris, shading=0, normals=None, colour=(0.8, 0.8, 0.8)
                 triangle=triangle.reshape(H, W), counts=(int(S.t.size), int(S.count - S.t.size), int(cp.size), covered_any),
                 cover=cover.reshape(H, W), winners=int(np.unique(win_t).size), queued=int((inside & (sides > LARGE_BOX)).sum()),
                 partly_outside=int(crosses.sum()), unusable=S.unusable, degenerate=S.degenerate, ties=int(np.unique(pix[tie]).size),
-                fragments=int(pix.size))
+                fragments=int(pix.size), boxes=dict(t=S.t, x0=S.x0, x1=S.x1, y0=S.y0, y1=S.y1))
 
 
 def surface_scalar(records, field):

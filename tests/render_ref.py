@@ -13,6 +13,7 @@ from sphmi import frames
 f32 = np.float32
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 SMALL = 16
+LARGE_BOX = 8  # the kernels queue a splat whose clipped search box is above LARGE_BOX pixels a side
 LIMIT = f32(1048576.0)
 
 
@@ -146,7 +147,8 @@ def fragments(view, j, u, v, R, R2, cz, all_pixels=False):
 def render(state, view, region=None, types=(1, 2), thickness=False, rho0=None, labels=None, nbr_counts=None, all_pixels=False):
     """The five images and the counts of one render, plus what the tests assert about it: `ties` (pixels whose winning depth bits
     came from more than one particle), `winners` (distinct winning particles), `fragments`, `max_box` (the largest side of a
-    clipped search box) and `candidates`."""
+    clipped search box), `candidates`, `boxes` (the drawn particles j and their clipped search boxes) and `queued` (drawn
+    particles whose box meets the image and is above 8 pixels a side)."""
     W, H = int(view.width), int(view.height)
     pos = np.asarray(state["pos"], np.float32)
     sel = diag_ref.selected(state, diag_ref.EVERYTHING if region is None else region, types)
@@ -189,8 +191,11 @@ def render(state, view, region=None, types=(1, 2), thickness=False, rho0=None, l
     tie = (key >> np.uint64(32) == keys[pix] >> np.uint64(32)) & (key != keys[pix])
     x0, x1, y0, y1 = search_box(view, u, v, R)
     sides = np.maximum(x1 - x0 + 1, y1 - y0 + 1)
-    sides = sides[(x1 >= x0) & (y1 >= y0)]
+    inside = (x1 >= x0) & (y1 >= y0)
+    queued = int((inside & (sides > LARGE_BOX)).sum())
+    sides = sides[inside]
     return dict(depth=out_depth.reshape(H, W), index=out_index.reshape(H, W), orig_id=out_id.reshape(H, W), rgba=rgba.reshape(H, W, 4),
                 thickness=saturate(sums).reshape(H, W) if thickness else None, sums=sums.reshape(H, W), drawn=int(j.size),
                 covered=int(cp.size), ties=int(np.unique(pix[tie]).size), winners=int(np.unique(win).size),
-                fragments=int(pix.size), max_box=int(sides.max()) if sides.size else 0, candidates=int(sel.sum()))
+                fragments=int(pix.size), max_box=int(sides.max()) if sides.size else 0, candidates=int(sel.sum()),
+                boxes=dict(j=j, x0=x0, x1=x1, y0=y0, y1=y1), queued=queued)

@@ -78,14 +78,15 @@ def bounds_of(mesh, field):
     return lo, (hi if hi > lo else lo + 1.0)
 
 
-def check_mesh(hip, mesh, view, what, shading="flat", field=None, compose=None):
-    """One sph_render_mesh against the restatement, word for word; compose: (particle view, types) of the render drawn over.
-    Returns (the restatement's result, the device's images)."""
+def check_mesh(hip, mesh, view, what, shading="flat", field=None, compose=None, bounds=None):
+    """One sph_render_mesh against the restatement, word for word; compose: (particle view, types) of the render drawn over;
+    bounds: (lo, hi) of the ramp, by default the extremes of the vertex scalar. Returns (the restatement's result, the device's
+    images)."""
     base = None
     if compose is not None:
         hip.render(compose[0], None, compose[1])
         base = hip.rendered()  # (test_render compares these with their own restatement)
-    lo, hi = bounds_of(mesh, field) if field is not None else (0.0, 1.0)
+    lo, hi = (0.0, 1.0) if field is None else bounds_of(mesh, field) if bounds is None else bounds
     want = mr.render_mesh(view, mesh.verts, mesh.tris, 1 if shading == "smooth" else 0, mesh.normals() if shading == "smooth" else None, COLOUR,
                           None if field is None else mesh.scalar(field), lo, hi, base)
     counts = hip.render_mesh(view, mesh.source, shading, COLOUR, field, lo, hi, compose is not None)
