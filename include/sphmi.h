@@ -1182,6 +1182,37 @@ int sph_stats_reset(sph_solver* s, int32_t slot /* -1: all */);
 int sph_stats_read(sph_solver* s, int32_t slot, int64_t firstNode, int64_t count, double* out /* host, count x 24 */, int64_t* calls); /* blocking */
 int sph_stats_read_moments(sph_solver* s, int32_t slot, int64_t firstNode, int64_t count, float* out /* host, count x 16 */, int64_t* calls); /* blocking */
 
+/* ---- Binned diagnostics: the sph_diagnostics record of every bin of a lattice (no reference counterpart) ---------
+ * Maps and profiles of particle SUMS (water depth over a plan view, u(z) across a channel, mass and momentum per block): a bin's
+ * record is a share of the particles, unlike a node value of sph_sample_grid, the probes or the time statistics.
+ * EDGES. Edge i of axis a is e_a(i) = origin[a] + (float)i * spacing[a]: one float multiply, one float add, no contraction (the
+ * expression of sph_sample_grid). Bin (i, j, k), i < nx, j < ny, k < nz, is the box [e_x(i), e_x(i+1)) x [e_y(j), e_y(j+1)) x
+ * [e_z(k), e_z(k+1)); its record is record b = (k * ny + j) * nx + i. Neighbouring bins share the same float edge, so every
+ * particle lies in at most one bin and a particle exactly on an edge belongs to the upper bin; where the origin is so large
+ * against the spacing that consecutive edges coincide, the bins between them are empty and no particle is lost. An axis with
+ * dims[a] == 1 and spacing[a] == 0 is the whole axis (-inf, +inf).
+ * RECORD. out[b] is, word for word as 64-bit patterns, the record sph_diagnostics returns for that one box with the same typeMask
+ * in the same state: the 14 sums in the positional fixed tree over all N terms, the extremes, the (max v2, lowest index, original
+ * id) triple and the empty-record rule. Hence a record depends on the state and its own box only (not on the rest of the lattice),
+ * and the counts over all bins add up exactly to the count of sph_diagnostics over the lattice's outer box.
+ * sph_bin_index returns the bin b of every sorted particle under the same rule, -1 for a particle that is unselected by type or
+ * key or lies in no bin: the tiling itself.
+ * Errors: as sph_diagnostics (SPH_ERR_ORDER before a step's density and pressure-force stages have run; SPH_ERR_INVALID for a
+ * slab solver, a typeMask of 0 or with bits outside 1..3, null pointers; a blown-up state is reported as by every blocking call),
+ * and SPH_ERR_INVALID for a non-finite origin or spacing, a negative spacing, a spacing of 0 on an axis with dims != 1, dims <= 0,
+ * nx * ny * nz > SPH_BIN_MAX_BINS. Blocking, on the solver's stream, read-only on every solver array, not a stage.
+ * Device scratch, grown on demand and freed by sph_destroy, for B bins, N particles and E (chunk of 1024 particles, bin) pairs
+ * with at least one member (E <= N; for a spatially sorted state about the chunks times the bins a chunk touches):
+ *   264 * B + 4 * N + 4 bytes of tables, and 212 * E bytes of partials (sph_bin_index: the tables only). */
+typedef struct sph_bin_lattice { /* 40 bytes, laid out like sph_stats_lattice */
+  float origin[3], spacing[3];
+  int32_t dims[3];    /* nx, ny, nz */
+  uint32_t typeMask;  /* as sph_diagnostics */
+} sph_bin_lattice;
+#define SPH_BIN_MAX_BINS (1 << 18)
+int sph_bin_diagnostics(sph_solver* s, const sph_bin_lattice* g, double* out /* host, bins x SPH_DIAG_WORDS */);
+int sph_bin_index(sph_solver* s, const sph_bin_lattice* g, int32_t* binOfSorted /* host, N, sorted order; -1 = in no bin */);
+
 /* ---- Integral curves: streamlines and tracers (no reference counterpart) ---------------------------------------
  * Curves that follow the sampled velocity field. State, selected set, order of the sums, argument rules and errors are those of
  * sph_sample_points: the sorted state of the last completed step (one integration step behind sph_read_position), SPH_ERR_ORDER

@@ -317,6 +317,66 @@ extern "C" int sph_histogram(sph_solver* s, int32_t field, float lo, float hi, i
   return rc != SPH_OK ? rc : sph_check_finite_state(s);
 }
 
+// ---------------------------------------------------------------------------------------------- binned diagnostics
+// The diagnostics record of every bin of a lattice (sph_bins.hip): same state, order and mask rules as sph_diagnostics, plus the
+// lattice's own. Blocks once for the number of (chunk, bin) entries, which sizes the pool.
+static int bin_check(sph_solver* s, const sph_bin_lattice* g, const void* out, const char* what, BinArgs* a, int* bins) {
+  if (!g || !out) { sph_set_error("%s: null pointer", what); return SPH_ERR_INVALID; }
+  const int rc = sph_sample_check(s, g->typeMask, what);
+  if (rc != SPH_OK) return rc;
+  long long B = 1;
+  for (int k = 0; k < 3; k++) {
+    if (!std::isfinite(g->origin[k]) || !std::isfinite(g->spacing[k])) { sph_set_error("%s: origin and spacing must be finite", what); return SPH_ERR_INVALID; }
+    if (g->dims[k] <= 0) { sph_set_error("%s: dims must be > 0", what); return SPH_ERR_INVALID; }
+    if (g->spacing[k] < 0.f || (g->spacing[k] == 0.f && g->dims[k] != 1)) {
+      sph_set_error("%s: spacing must be > 0 (0 with dims 1: the whole axis)", what);
+      return SPH_ERR_INVALID;
+    }
+    B *= g->dims[k];
+    if (B > SPH_BIN_MAX_BINS) { sph_set_error("%s: more than %d bins", what, SPH_BIN_MAX_BINS); return SPH_ERR_INVALID; }
+    a->o[k] = g->origin[k]; a->s[k] = g->spacing[k]; a->n[k] = g->dims[k];
+  }
+  a->typeMask = g->typeMask; a->rho0 = s->d.rho0;
+  *bins = (int)B;
+  return SPH_OK;
+}
+
+extern "C" int sph_bin_diagnostics(sph_solver* s, const sph_bin_lattice* g, double* out) {
+  ENTER(s);
+  BinArgs a = {};
+  int B = 0;
+  int rc = bin_check(s, g, out, "sph_bin_diagnostics", &a, &B);
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->binBuf, sphk_bin_scratch_bytes(s->d.N, B));
+  if (rc != SPH_OK) return rc;
+  uint32_t *dTotal = nullptr, entries = 0;
+  rc = sphk_bin_index(s, a, B, s->binBuf.p, true, &dTotal);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, &entries, dTotal, sizeof(entries));
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->binPool, sphk_bin_pool_bytes(entries));
+  if (rc != SPH_OK) return rc;
+  double* records = nullptr;
+  rc = sphk_bin_records(s, a, B, s->binBuf.p, s->binPool.p, entries, &records);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, out, records, sizeof(double) * SPH_DIAG_WORDS * (size_t)B);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
+extern "C" int sph_bin_index(sph_solver* s, const sph_bin_lattice* g, int32_t* binOfSorted) {
+  ENTER(s);
+  BinArgs a = {};
+  int B = 0;
+  int rc = bin_check(s, g, binOfSorted, "sph_bin_index", &a, &B);
+  if (rc != SPH_OK) return rc;
+  rc = sph_grow_scratch(s, s->binBuf, sphk_bin_scratch_bytes(s->d.N, B));
+  if (rc != SPH_OK) return rc;
+  rc = sphk_bin_index(s, a, B, s->binBuf.p, false, nullptr);
+  if (rc != SPH_OK) return rc;
+  rc = sph_d2h(s, binOfSorted, sphk_bin_ids(s->binBuf.p, B), sizeof(int32_t) * (size_t)s->d.N);
+  return rc != SPH_OK ? rc : sph_check_finite_state(s);
+}
+
 // ---------------------------------------------------------------------------------------------- connected components
 // The pieces the matter is in: components of the graph of the last step's neighbour rows (sph_components.hip). The labelling
 // lives in ccBuf / ccTable until the next one; the per-component records reuse the diagnostics tree with the labels as selection.

@@ -310,6 +310,9 @@ struct sph_solver {
   sph_stats_lattice statsLattice[SPH_MAX_STATS] = {};
   SphScratch statsAcc[SPH_MAX_STATS], statsOut;
   int64_t statsCalls[SPH_MAX_STATS] = {};
+  // binned diagnostics (sph_bin_diagnostics / sph_bin_index, sph_bins.hip): binBuf: the records, the bin tables and
+  // the bin of every particle; binPool: the leaf's (chunk, bin) entries. Both grown on demand.
+  SphScratch binBuf, binPool;
   // a stage-by-stage step is half done: set by every stage entry point, cleared by the stage that leaves posOrig / velOrig final
   // (integrate, or membranes-finalize with elastic matter), by sph_step and by an edit that changes the set
   bool stepOpen = false;
@@ -517,6 +520,21 @@ struct HistArgs {
 // scratch: tree_scratch_doubles(N, a.count, SPH_DIAG_WORDS) (sph_tree.h); *records: where the records land (in scratch)
 int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records);
 int sphk_histogram(sph_solver* s, const HistArgs& a, uint32_t* out);  // out: bins + 2 device words
+// sph_bins.hip (the diagnostics record of every bin of a lattice; read-only on every solver array)
+struct BinArgs {
+  float o[3], s[3];  // edge i of axis a: o[a] + (float)i * s[a]
+  int n[3];
+  uint32_t typeMask;
+  float rho0;
+};
+size_t sphk_bin_scratch_bytes(int N, int B);     // records, bin tables and the N bin ids of a call over B bins
+size_t sphk_bin_pool_bytes(uint32_t entries);    // the (chunk, bin) entries of the leaf
+int32_t* sphk_bin_ids(void* scratch, int B);     // where the N bin ids lie in that scratch
+// the bin of every sorted particle; count: also the entries per bin and their prefix sums, *total = the device word that holds
+// their number
+int sphk_bin_index(sph_solver* s, const BinArgs& a, int B, void* scratch, bool count, uint32_t** total);
+// after sphk_bin_index(count) on the same scratch, with a pool of sphk_bin_pool_bytes(entries): *records = B records (in scratch)
+int sphk_bin_records(sph_solver* s, const BinArgs& a, int B, void* scratch, void* pool, uint32_t entries, double** records);
 // sph_components.hip (connected components of the neighbour graph; read-only on every solver array)
 size_t sphk_components_scratch_bytes(int N);             // parent and labels (4 B per particle each), the scan's block totals
 int32_t* sphk_components_labels(void* scratch, int N);   // where the N labels lie in that scratch

@@ -13,28 +13,20 @@
 #include "sph_common.h"
 #include "sph_selector.h"  // the selection rule and the histogram's quantity
 #include "sph_tree.h"  // the tree's layout (rows: the regions), the leaf's tail and the upper levels
+#include "sph_diag_leaf.h"  // the reduction of one chunk for one selection, and a record's words from the top of its tree
 
 #include <algorithm>
 
-#define DIAG_SUMS 14  // record words 0..13
-
-// the 10 plain extremes of a record, in this order: words 16, 18, 23, 24, 25 (minima), then 17, 19, 26, 27, 28 (maxima)
-__device__ static const int kDiagMinWord[5] = {16, 18, 23, 24, 25};
-__device__ static const int kDiagMaxWord[5] = {17, 19, 26, 27, 28};
-
 // ---- level 0: particles -> one partial per chunk, word and region ---------------------------------------------------------
 // Every array is read once, whatever the number of regions: the per-particle terms stay in registers and the region loop only
-// selects among them.
+// selects among them; the reduction of one selection is diag_leaf_reduce (sph_diag_leaf.h).
 // COMP: the selection of record r is labels[j] == comp[r] (sph_component_diagnostics) instead of type, key and box; everything
 // after the selection is the same code.
 template <bool COMP>
 __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, double* __restrict__ part, int chunks) {
-  __shared__ double sh[DIAG_SUMS][SPH_BLOCK];
-  __shared__ float shx[4][10];
-  __shared__ float shv[4];
-  __shared__ int shi[4];
-  const int t = threadIdx.x, chunk = blockIdx.x, lane = t & 63, wave = t >> 6;
-  float f[4][13];  // x y z, vx vy vz, Lx Ly Lz, v2, rho, e2, p: record words 1..13
+  __shared__ DiagLeafLds L;
+  const int t = threadIdx.x, chunk = blockIdx.x;
+  float f[4][DIAG_TERMS];
   bool ok[4];
   int lab[4];
 #pragma unroll
@@ -43,24 +35,12 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
     ok[e] = false;
     lab[e] = -1;
 #pragma unroll
-    for (int w = 0; w < 13; w++) f[e][w] = 0.f;
+    for (int w = 0; w < DIAG_TERMS; w++) f[e][w] = 0.f;
     if (j < d.N) {
       const float4 p = d.sortedPos[j];
-      const float4 v = d.sortedVel[j];
-      const float rho = d.rho[j];
-      const float pr = d.rp[j].y;
+      diag_leaf_load(d, a.rho0, j, p, f[e]);
       if (COMP) { lab[e] = a.labels[j]; ok[e] = lab[e] >= 0; }
       else ok[e] = sph_type_key_selected(d, a.typeMask, j, p);
-      f[e][0] = p.x; f[e][1] = p.y; f[e][2] = p.z;
-      f[e][3] = v.x; f[e][4] = v.y; f[e][5] = v.z;
-      f[e][6] = p.y * v.z - p.z * v.y;
-      f[e][7] = p.z * v.x - p.x * v.z;
-      f[e][8] = p.x * v.y - p.y * v.x;
-      f[e][9] = v.x * v.x + v.y * v.y + v.z * v.z;
-      f[e][10] = rho;
-      const float er = rho - a.rho0;
-      f[e][11] = er * er;
-      f[e][12] = pr;
     }
   }
   for (int r = 0; r < a.count; r++) {
@@ -86,81 +66,14 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_diag_leaf(SphDev d, DiagArgs a, d
       }
       continue;
     }
-    // sums: strides 512 and 256 in registers, one word at a time (the 14 doubles are never live together)
-#pragma unroll
-    for (int w = 0; w < DIAG_SUMS; w++) {
-      double q[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        float x = w == 0 ? 1.0f : f[e][w == 0 ? 0 : w - 1];
-        asm volatile("" : "+v"(x));  // widen here, per region: hoisted out of the loop, the 52 doubles cost 104 VGPRs
-        q[e] = sel[e] ? (double)x : 0.0;
-      }
-      sh[w][t] = (q[0] + q[2]) + (q[1] + q[3]);
-    }
-    // extremes of this thread's four elements, then of its wave
-    float mn[5], mx[5], bestV = -INFINITY;
-    int bestI = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < 5; k++) { mn[k] = INFINITY; mx[k] = -INFINITY; }
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      if (!sel[e]) continue;
-      const float q[5] = {f[e][10], f[e][12], f[e][0], f[e][1], f[e][2]};
-#pragma unroll
-      for (int k = 0; k < 5; k++) { mn[k] = q[k] < mn[k] ? q[k] : mn[k]; mx[k] = q[k] > mx[k] ? q[k] : mx[k]; }
-      if (f[e][9] > bestV) { bestV = f[e][9]; bestI = chunk * DIAG_CHUNK + e * SPH_BLOCK + t; }  // ascending index: the first wins
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-      for (int k = 0; k < 5; k++) {
-        const float om = __shfl_down(mn[k], s, 64), ox = __shfl_down(mx[k], s, 64);
-        mn[k] = om < mn[k] ? om : mn[k];
-        mx[k] = ox > mx[k] ? ox : mx[k];
-      }
-      const float ov = __shfl_down(bestV, s, 64);
-      const int oi = __shfl_down(bestI, s, 64);
-      if (ov > bestV || (ov == bestV && oi < bestI)) { bestV = ov; bestI = oi; }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 5; k++) { shx[wave][k] = mn[k]; shx[wave][5 + k] = mx[k]; }
-      shv[wave] = bestV; shi[wave] = bestI;
-    }
-    __syncthreads();
-    // strides 128, 64 and the in-wave strides: the 14 words are shared out among the four waves
-    tree_group_sums<DIAG_SUMS>(sh, DIAG_SUMS, [&](int w, double x) { part[tree_at(SPH_DIAG_WORDS, r, w, chunks, chunk)] = x; });
-    if (t < 10) {
-      float x = shx[0][t];
-      for (int q = 1; q < 4; q++) { const float o = shx[q][t]; x = t < 5 ? (o < x ? o : x) : (o > x ? o : x); }
-      part[tree_at(SPH_DIAG_WORDS, r, t < 5 ? kDiagMinWord[t] : kDiagMaxWord[t - 5], chunks, chunk)] = (double)x;
-    } else if (t == 10) {
-      float bv = shv[0]; int bi = shi[0];
-      for (int q = 1; q < 4; q++) if (shv[q] > bv || (shv[q] == bv && shi[q] < bi)) { bv = shv[q]; bi = shi[q]; }
-      part[tree_at(SPH_DIAG_WORDS, r, 20, chunks, chunk)] = (double)bv;
-      part[tree_at(SPH_DIAG_WORDS, r, 21, chunks, chunk)] = (double)bi;
-    }
-    __syncthreads();  // sh / shx are reused by the next region
+    diag_leaf_reduce(L, f, sel, chunk, [&](int w, double x) { part[tree_at(SPH_DIAG_WORDS, r, w, chunks, chunk)] = x; });
   }
 }
 
 // ---- the records: canonical extremes (+ 0.0f), the empty-selection rule, the original id of the fastest particle ------------
 __global__ void k_diag_final(SphDev d, const double* __restrict__ top /* one chunk per word */, double* __restrict__ out) {
   const int r = blockIdx.x, w = threadIdx.x;  // SPH_DIAG_WORDS threads
-  const double n = top[tree_at(SPH_DIAG_WORDS, r, 0, 1, 0)];
-  double x = 0.0;
-  if (w < DIAG_SUMS) x = top[tree_at(SPH_DIAG_WORDS, r, w, 1, 0)];
-  else if (w == 21 || w == 22) {
-    x = -1.0;
-    if (n > 0.0) {
-      const int idx = (int)top[tree_at(SPH_DIAG_WORDS, r, 21, 1, 0)];
-      if (idx < d.N) x = w == 21 ? (double)idx : (double)d.vals[idx];  // (no index when every selected v2 is NaN)
-    }
-  } else if ((w >= 16 && w <= 20) || (w >= 23 && w <= 28)) {
-    if (n > 0.0) x = (double)((float)top[tree_at(SPH_DIAG_WORDS, r, w, 1, 0)] + 0.0f);
-  }
-  out[r * SPH_DIAG_WORDS + w] = x;
+  out[r * SPH_DIAG_WORDS + w] = diag_record_word(d, w, [&](int word) { return top[tree_at(SPH_DIAG_WORDS, r, word, 1, 0)]; });
 }
 
 int sphk_diagnostics(sph_solver* s, const DiagArgs& a, double* scratch, double** records) {

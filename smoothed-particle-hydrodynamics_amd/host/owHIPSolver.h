@@ -350,6 +350,13 @@ class owHIPSolver {
     return calls;
   }
 
+  // beyond the reference: binned diagnostics. binDiagnostics writes the diagnostics() record of every bin of the lattice (edge i of
+  // axis a: origin[a] + (float)i * spacing[a]; dims 1 with spacing 0: the whole axis), nx * ny * nz x SPH_DIAG_WORDS doubles, bin
+  // (i, j, k) at (k * ny + j) * nx + i, each word for word what diagnostics() returns for the bin's box; binIndex the bin of every
+  // sorted particle, -1 = in none (include/sphmi.h, sph_bin_diagnostics / sph_bin_index)
+  void binDiagnostics(const sph_bin_lattice* g, double* out) { check(sph_bin_diagnostics(s_, g, out), "binDiagnostics"); }
+  void binIndex(const sph_bin_lattice* g, int32_t* binOfSorted) { check(sph_bin_index(s_, g, binOfSorted), "binIndex"); }
+
   // beyond the reference: a scalar of the user's own that travels with the particles (a dye, a temperature). Up to
   // SPH_FIELD_SLOTS fields of one float per particle in original-id order (read_position_buffer's); a step never touches them,
   // the edits above carry them along (new particles get `inflow`). fieldSetRegion paints the particles removeRegion would

@@ -114,6 +114,11 @@
 //        end, and written to FILE: the text line `sphmi stats calls C from S every K nx NX ny NY nz NZ`, the 40 bytes of the
 //        sph_stats_lattice, then NX x NY x NZ x 24 raw float64 words, x fastest (frames.read_stats). One line is printed:
 //        `_stats: calls C nodes N`.
+//   ... --bin-grid OX OY OZ SX SY SZ NX NY NZ [--bin-types "T ..."] [--bin-every K] --bin-out FILE
+//        binned diagnostics (sph_bin_diagnostics): the diagnostics record of every bin of the lattice whose edges are
+//        OX.. + i * SX.., i <= NX NY NZ (N 1 with S 0: the whole axis), over the particle types T (default: liquid and elastic).
+//        After every K-th step (default 1) the records are appended to the CSV FILE, one row per bin: `step,bin,` and the 32 words
+//        as %.17g (frames.read_bins). One line is printed per call: `_bins: step S bins B n N`.
 //   ... --dye-region X0 Y0 Z0 X1 Y1 Z1 [--dye-inflow V] [--dye-diffusivity D] [--dye-every K]
 //        a dye carried by the liquid (sph_field_*): carried field 0 starts at 1 on the liquid inside the region
 //        ("inf" / "-inf" are accepted as bounds) and at 0 elsewhere; the emitter's liquid carries V (default 0; --dye-inflow alone
@@ -270,6 +275,12 @@ static void body_pose(const double spin[7], const double vel[3], double k, float
   }
 }
 
+// the 32 words of a diagnostics record as the CSV tables name them (frames.DIAG_FIELDS): --diagnostics-out and --bin-out
+static const char kDiagCsvFields[] =
+    "n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
+    "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
+    "reserved31\n";
+
 int main(int argc, char** argv) {
   const char *posFile = nullptr, *velFile = nullptr, *outFile = nullptr;
   int steps = 10; bool staged = false, wide = false, quiet = false, muscles = false, worm = false, blockingRead = false;
@@ -292,6 +303,7 @@ int main(int argc, char** argv) {
   const char* probeFile = nullptr;
   sph_stats_lattice statsGrid = {}; int statsFrom = 0, statsEvery = 1, statsCalls = 0; bool statsSeen = false, statsGridSeen = false;
   const char* statsFile = nullptr;
+  sph_bin_lattice binGrid = {}; int binEvery = 1; bool binSeen = false, binGridSeen = false; const char* binFile = nullptr;
   int renEvery = 0, renSize[2] = {640, 480}; bool renSeen = false, renEyeSeen = false, renTargetSeen = false, renThickness = false;
   const char* renDir = nullptr; const char* renColour = "density";
   double renEye[3] = {0, 0, 0}, renTarget[3] = {0, 0, 0}, renUp[3] = {0, 1, 0};
@@ -418,6 +430,21 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--stats-from") && i + 1 < argc) { statsFrom = atoi(argv[++i]); statsSeen = true; }
     else if (!strcmp(argv[i], "--stats-every") && i + 1 < argc) { statsEvery = atoi(argv[++i]); statsSeen = true; }
     else if (!strcmp(argv[i], "--stats-out") && i + 1 < argc) { statsFile = argv[++i]; statsSeen = true; }
+    else if (!strcmp(argv[i], "--bin-grid") && i + 9 < argc) {
+      for (int k = 0; k < 3; k++) binGrid.origin[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) binGrid.spacing[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) binGrid.dims[k] = atoi(argv[++i]);
+      if (!binGrid.typeMask) binGrid.typeMask = (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE);
+      binSeen = binGridSeen = true;
+    }
+    else if (!strcmp(argv[i], "--bin-types") && i + 1 < argc) {
+      binGrid.typeMask = 0u;
+      for (const char* p = argv[++i]; *p; p++)
+        if (*p >= '0' && *p <= '9') binGrid.typeMask |= 1u << (*p - '0');
+      binSeen = true;
+    }
+    else if (!strcmp(argv[i], "--bin-every") && i + 1 < argc) { binEvery = atoi(argv[++i]); binSeen = true; }
+    else if (!strcmp(argv[i], "--bin-out") && i + 1 < argc) { binFile = argv[++i]; binSeen = true; }
     else if (!strcmp(argv[i], "--render-every") && i + 1 < argc) { renEvery = atoi(argv[++i]); renSeen = true; }
     else if (!strcmp(argv[i], "--render-out") && i + 1 < argc) { renDir = argv[++i]; renSeen = true; }
     else if (!strcmp(argv[i], "--render-size") && i + 2 < argc) { renSize[0] = atoi(argv[++i]); renSize[1] = atoi(argv[++i]); renSeen = true; }
@@ -572,6 +599,12 @@ int main(int argc, char** argv) {
                     "--stats-every K (> 0) need both\n");
     return 2;
   }
+  if (binSeen && (!binGridSeen || binEvery <= 0 || !binFile || binGrid.dims[0] <= 0 || binGrid.dims[1] <= 0 || binGrid.dims[2] <= 0 ||
+                  (long long)binGrid.dims[0] * binGrid.dims[1] * binGrid.dims[2] > SPH_BIN_MAX_BINS)) {
+    fprintf(stderr, "--bin-grid OX OY OZ SX SY SZ NX NY NZ (NX, NY, NZ > 0, at most %d bins) goes with --bin-out FILE; --bin-types \"T ...\" and "
+                    "--bin-every K (> 0) need both\n", SPH_BIN_MAX_BINS);
+    return 2;
+  }
   if (renSeen && (renEvery <= 0 || !renDir)) {
     fprintf(stderr, "--render-every K (> 0) and --render-out DIR go together (the other --render options need both)\n");
     return 2;
@@ -713,9 +746,16 @@ int main(int argc, char** argv) {
     if (diagnosing) {
       diagCsv = fopen(diagFile, "w");
       if (!diagCsv) throw std::runtime_error(std::string("cannot write ") + diagFile);
-      fputs("step,region,n,sum_x,sum_y,sum_z,sum_vx,sum_vy,sum_vz,sum_lx,sum_ly,sum_lz,sum_v2,sum_rho,sum_e2,sum_p,reserved14,reserved15,"
-            "min_rho,max_rho,min_p,max_p,max_v2,max_v2_index,max_v2_id,min_x,min_y,min_z,max_x,max_y,max_z,reserved29,reserved30,"
-            "reserved31\n", diagCsv);
+      fputs("step,region,", diagCsv);
+      fputs(kDiagCsvFields, diagCsv);
+    }
+    std::vector<double> binRecords(binSeen ? (size_t)binGrid.dims[0] * binGrid.dims[1] * binGrid.dims[2] * SPH_DIAG_WORDS : 0);
+    FILE* binCsv = nullptr;
+    if (binSeen) {
+      binCsv = fopen(binFile, "w");
+      if (!binCsv) throw std::runtime_error(std::string("cannot write ") + binFile);
+      fputs("step,bin,", binCsv);
+      fputs(kDiagCsvFields, binCsv);
     }
     FILE* compCsv = nullptr;
     std::vector<int32_t> compRootCount, compIds;
@@ -928,6 +968,20 @@ int main(int argc, char** argv) {
         write_ply(std::string(surfDir) + "/surface_" + std::to_string(iterationCount + 1) + ".ply", meshVerts, meshTris,
                   surfNormals ? &meshNormals : nullptr);
         helper.report("_extractSurface: \t%9.3f ms\n");
+      }
+      if (binSeen && (iterationCount + 1) % binEvery == 0) {
+        ocl_solver->binDiagnostics(&binGrid, binRecords.data());
+        const size_t bins = binRecords.size() / SPH_DIAG_WORDS;
+        double n = 0.0;
+        for (size_t b = 0; b < bins; b++) {
+          fprintf(binCsv, "%d,%zu", iterationCount + 1, b);
+          for (int w = 0; w < SPH_DIAG_WORDS; w++) fprintf(binCsv, ",%.17g", binRecords[b * SPH_DIAG_WORDS + w]);
+          fputc('\n', binCsv);
+          n += binRecords[b * SPH_DIAG_WORDS];
+        }
+        if (fflush(binCsv) != 0) throw std::runtime_error(std::string("cannot write ") + binFile);
+        if (!quiet) printf("_bins: step %d bins %zu n %.0f\n", iterationCount + 1, bins, n);
+        helper.report("_binDiagnostics: \t%9.3f ms\n");
       }
       if (diagnosing && (iterationCount + 1) % diagEvery == 0) {
         ocl_solver->diagnostics(diagRegions.data(), diagCount, (1u << SPH_LIQUID_PARTICLE) | (1u << SPH_ELASTIC_PARTICLE), diagRecords.data());
@@ -1204,6 +1258,7 @@ int main(int argc, char** argv) {
       printf("_stats: calls %lld nodes %zu\n", (long long)calls, nodes);
     }
     if (diagCsv && fclose(diagCsv) != 0) throw std::runtime_error(std::string("cannot write ") + diagFile);
+    if (binCsv && fclose(binCsv) != 0) throw std::runtime_error(std::string("cannot write ") + binFile);
     if (compCsv && fclose(compCsv) != 0) throw std::runtime_error(std::string("cannot write ") + compFile);
     delete ocl_solver;
   } catch (std::exception& e) {  // owPhysicsFluidSimulator.cpp:73-76,144-148

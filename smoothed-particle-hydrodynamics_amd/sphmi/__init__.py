@@ -21,6 +21,7 @@ SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
 DIAG_WORDS = 32  # sph_diagnostics record (frames.DIAG_FIELDS)
 DIAG_MAX_REGIONS = 16
 HIST_MAX_BINS = 4096
+BIN_MAX_BINS = 1 << 18  # SPH_BIN_MAX_BINS: bins of one bin_diagnostics / bin_index lattice
 HIST_FIELDS = ("density", "speed", "pressure", "neighbors", "x", "y", "z")  # sph_histogram field numbers 0..6
 SELECT_WORDS = 12  # sph_read_selection record: x, y, z, type, vx, vy, vz, rho, p, neighbour count, surface measure, 0 (frames.SELECT_FIELDS)
 SELECT_MAX_TERMS = 4
@@ -236,7 +237,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_gauges_read", "sph_gauges_reset", "sph_gauges_history", "sph_gauges_read_history", "sph_gauge_crossings",
                     "sph_read_gauge_crossings", "sph_probes_set_points", "sph_probes_set_lines", "sph_probes_count", "sph_probes_record",
                     "sph_probes_history", "sph_probes_read_history", "sph_stats_define", "sph_stats_get", "sph_stats_accumulate",
-                    "sph_stats_reset", "sph_stats_read", "sph_stats_read_moments"] + _STAGE_FUNCS
+                    "sph_stats_reset", "sph_stats_read", "sph_stats_read_moments", "sph_bin_diagnostics", "sph_bin_index"] + _STAGE_FUNCS
 HOST_EXPORTED_SYMBOLS = ["sphmi_default_config", "sphmi_config_set_box", "sphmi_count_particles",
                          "sphmi_load_configuration", "sphmi_load_elastic_connections", "sphmi_box_counts",
                          "sphmi_generate_box", "sphmi_box_layer_histogram", "sphmi_generate_box_slice", "sphmi_muscle_signal", "sphmi_step_chunk_edges", "sphmi_step_pipeline_schedule", "sphmi_step_halo_check", "sphmi_step_band_defer_first", "sphmi_save_configuration", "sphmi_worm_counts",
@@ -402,6 +403,9 @@ def device_lib():
             L.sph_stats_reset.argtypes = [C.c_void_p, C.c_int32]
             L.sph_stats_read.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
             L.sph_stats_read_moments.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sph_bin_diagnostics"):  # (optional: an A/B library built from an older csrc/ has no binned diagnostics)
+            L.sph_bin_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sph_bin_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _dev = L
     return _dev
 
@@ -718,6 +722,30 @@ def stats_lattice(origin, spacing, dims, types=(1,)):
     return g
 
 
+def bin_lattice(origin, spacing, dims, types=(1, 2)):
+    """A lattice of bins as the one-element STATS_LATTICE_DTYPE array bin_diagnostics and bin_index read (sph_bin_lattice has the
+    layout of sph_stats_lattice): edge i of axis a is origin[a] + (float32)i * spacing[a], bin (i, j, k) is the half-open box
+    between consecutive edges, dims = (nx, ny, nz). dims 1 with spacing 0 is the whole axis. Shapes and integer dims are checked
+    here, everything else by the library. frames.bin_edges / bin_boxes give the edges and the boxes."""
+    o, sp, dm = np.asarray(origin, np.float32), np.asarray(spacing, np.float32), np.asarray(dims)
+    if o.size != 3 or sp.size != 3 or dm.size != 3:
+        raise SphError("bin_lattice: origin, spacing and dims must hold 3 values each")
+    if dm.dtype.kind not in "iu":
+        raise SphError("bin_lattice: dims must be integers")
+    if (np.abs(dm.astype(np.int64)) > 0x7fffffff).any():
+        raise SphError("bin_lattice: dims do not fit 32 bits")
+    g = np.zeros(1, STATS_LATTICE_DTYPE)
+    g["origin"], g["spacing"], g["dims"], g["typeMask"] = o.reshape(3), sp.reshape(3), dm.reshape(3), type_mask(types)
+    return g
+
+
+def _bin_lattice(lattice, what):
+    g = np.ascontiguousarray(lattice)
+    if g.dtype != STATS_LATTICE_DTYPE or g.size != 1:
+        raise SphError("%s: the lattice must be what bin_lattice() returns" % what)
+    return g.reshape(1)
+
+
 def probe_lines(lines):
     """Level-probe lines as the contiguous PROBE_LINE_DTYPE array probes_set_lines reads: an array of that dtype (any shape is
     refused but [L]), a SphProbeLine, or a sequence of SphProbeLine or of dicts (origin, step, count, field = name or 0..5, iso,
@@ -937,6 +965,27 @@ class owHIPSolver:
         self._chk(self._L.sph_histogram(self._h, field, float(np.float32(lo)), float(np.float32(hi)), int(bins), _ptr(rg),
                                         type_mask(types), _ptr(out)))
         return out
+
+    # --- binned diagnostics (sph_bin_diagnostics / sph_bin_index): maps and profiles of particle sums ---
+    def bin_diagnostics(self, lattice):
+        """float64[nz, ny, nx, 32]: the diagnostics() record of every bin of `lattice` (bin_lattice()), each bit for bit the record
+        diagnostics() returns for the bin's box (frames.bin_boxes) with the lattice's types, in one call and without a pass over
+        the particles per bin. A particle on an edge belongs to the upper bin; the counts add up to the count over the outer box.
+        frames.bin_profile / bin_column_depth turn the records into means and depths."""
+        g = _bin_lattice(lattice, "bin_diagnostics")
+        nx, ny, nz = (int(x) for x in g["dims"][0])
+        bins = nx * ny * nz if min(nx, ny, nz) > 0 and nx * ny * nz <= BIN_MAX_BINS else 0
+        out = np.zeros((nz, ny, nx, DIAG_WORDS) if bins else (1, DIAG_WORDS), np.float64)
+        self._chk(self._L.sph_bin_diagnostics(self._h, _ptr(g), _ptr(out)))
+        return out
+
+    def bin_index(self, lattice):
+        """int32[N], sorted order: the flat bin (k * ny + j) * nx + i of every particle under bin_diagnostics' rule, -1 for a
+        particle that is unselected by type or key or lies in no bin."""
+        g = _bin_lattice(lattice, "bin_index")
+        out = np.empty(max(self.N, 1), np.int32)
+        self._chk(self._L.sph_bin_index(self._h, _ptr(g), _ptr(out)))
+        return out[:self.N]
 
     # --- connected components (sph_label_components / sph_read_components / sph_component_diagnostics) ---
     def label_components(self, link_radius=np.inf, types=(1, 2)):

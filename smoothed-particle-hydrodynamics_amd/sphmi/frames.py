@@ -56,6 +56,11 @@ Time statistics (owHIPSolver.stats_define / stats_accumulate / stats, accumulato
 restates the device's moment words in float64, `stats_summary` names what a flow is reported by (wet fraction, mean velocity,
 stress tensor, TKE, pressure mean and rms, arrival call, peak pressure and its call), `write_vtk_stats` writes that as a VTK lattice,
 `read_stats` loads the file `sphmi_run --stats-out` writes.
+
+Binned diagnostics (owHIPSolver.bin_diagnostics / bin_index over a sphmi.bin_lattice, records named by DIAG_FIELDS): `bin_edges`
+and `bin_boxes` restate the lattice's float32 edges and the bins' boxes (usable as diagnostics() regions), `bin_profile` gives
+mass, mean velocity and mean density per bin, `bin_column_depth` the water depth of a plan-view map, `write_bins_csv` /
+`read_bins` write and read the table `sphmi_run --bin-out` writes, `write_vtk_bins` writes the profile as VTK cell data.
 """
 import math
 import struct
@@ -1353,6 +1358,127 @@ def read_stats(path):
         raise ValueError("read_stats: %d words for a lattice of %d x %d x %d nodes" % (data.size, nx, ny, nz))
     lattice = {"origin": g["origin"][0].copy(), "spacing": g["spacing"][0].copy(), "dims": (nx, ny, nz), "typeMask": int(g["typeMask"][0])}
     return lattice, data.reshape(nz, ny, nx, 24).copy(), calls, first, every
+
+
+# ---- binned diagnostics (owHIPSolver.bin_diagnostics / bin_index; include/sphmi.h, sph_bin_diagnostics) ----
+def _bin_lattice(lattice):
+    g = np.asarray(lattice)
+    if g.dtype.names is None or g.size != 1 or set(g.dtype.names) != {"origin", "spacing", "dims", "typeMask"}:
+        raise ValueError("a bin lattice is what sphmi.bin_lattice() returns")
+    g = g.reshape(1)
+    return g["origin"][0].astype(np.float32), g["spacing"][0].astype(np.float32), tuple(int(v) for v in g["dims"][0])
+
+
+def bin_edges(lattice):
+    """(ex, ey, ez): the float32 edges of the lattice's bins per axis, dims[a] + 1 each, by the contract's expression origin[a] +
+    (float32)i * spacing[a] (one rounded multiply, one rounded add); (-inf, +inf) for a whole axis (dims 1, spacing 0)."""
+    o, sp, dims = _bin_lattice(lattice)
+    out = []
+    for a in range(3):
+        if dims[a] == 1 and sp[a] == 0:
+            out.append(np.array([-np.inf, np.inf], np.float32))
+        else:
+            i = np.arange(dims[a] + 1).astype(np.float32)
+            out.append((o[a] + (i * sp[a]).astype(np.float32)).astype(np.float32))
+    return tuple(out)
+
+
+def bin_boxes(lattice):
+    """float32[bins, 6]: the box (x0, y0, z0, x1, y1, z1) of every bin, bin (i, j, k) at row (k * ny + j) * nx + i, usable as
+    diagnostics() regions (16 at a time): bin_diagnostics' record b is the diagnostics record of row b."""
+    ex, ey, ez = bin_edges(lattice)
+    nx, ny, nz = ex.size - 1, ey.size - 1, ez.size - 1
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    i, j, k = i.reshape(-1), j.reshape(-1), k.reshape(-1)
+    return np.stack([ex[i], ey[j], ez[k], ex[i + 1], ey[j + 1], ez[k + 1]], axis=1).astype(np.float32)
+
+
+def bin_profile(records, cfg):
+    """Per bin, from records [..., 32] (float64, computed in double): `n`, `mass` = n * cfg.mass, `mean_velocity` [..., 3],
+    `mean_position` [..., 3], `mean_density`, `mean_pressure`. An empty bin has zeros everywhere (no NaN, no warning)."""
+    r = np.asarray(records, np.float64)
+    if r.shape[-1] != len(DIAG_FIELDS):
+        raise ValueError("bin_profile: a record has %d words" % len(DIAG_FIELDS))
+    n = r[..., 0]
+    inv = np.zeros_like(n)
+    np.divide(1.0, n, out=inv, where=n > 0)
+    return {"n": n, "mass": n * float(cfg.mass), "mean_position": r[..., 1:4] * inv[..., None],
+            "mean_velocity": r[..., 4:7] * inv[..., None], "mean_density": r[..., 11] * inv, "mean_pressure": r[..., 13] * inv}
+
+
+def bin_column_depth(records, cfg, lattice):
+    """The water depth of a plan-view map, scene units: a lattice with exactly one whole axis (dims 1, spacing 0), records
+    [nz, ny, nx, 32] (or any shape of nx * ny * nz records). Each particle stands for the volume cfg.mass / cfg.rho0 (cubic
+    metres; scene units are metres / cfg.simulationScale), so depth = n * volume / bin area. Returns float64 of the records'
+    leading shape."""
+    _, sp, dims = _bin_lattice(lattice)
+    whole = [a for a in range(3) if dims[a] == 1 and sp[a] == 0]
+    if len(whole) != 1:
+        raise ValueError("bin_column_depth: the lattice must have exactly one whole axis (dims 1, spacing 0)")
+    r = np.asarray(records, np.float64)
+    if r.shape[-1] != len(DIAG_FIELDS) or r[..., 0].size != dims[0] * dims[1] * dims[2]:
+        raise ValueError("bin_column_depth: records do not fit the lattice")
+    area = float(np.prod([float(sp[a]) for a in range(3) if a != whole[0]]))
+    volume = float(cfg.mass) / float(cfg.rho0) / float(cfg.simulationScale) ** 3
+    return r[..., 0] * (volume / area)
+
+
+def write_bins_csv(path, steps, records):
+    """One row per step and bin: `step,bin,` then the 32 record words as %.17g (a round trip keeps every bit), under a header naming
+    them. `steps`: S step numbers; `records`: float64[S, ..., 32], the bins of a step in flat order (k * ny + j) * nx + i."""
+    rec = np.asarray(records, np.float64)
+    if rec.ndim < 2 or rec.shape[-1] != len(DIAG_FIELDS) or rec.shape[0] != len(steps):
+        raise ValueError("write_bins_csv: records must be [len(steps), ..., %d]" % len(DIAG_FIELDS))
+    rec = rec.reshape(len(steps), -1, len(DIAG_FIELDS))
+    with open(path, "w") as f:
+        f.write("step,bin," + ",".join(DIAG_FIELDS) + "\n")
+        for s, block in zip(steps, rec):
+            for b, row in enumerate(block):
+                f.write("%d,%d," % (int(s), b) + ",".join("%.17g" % float(x) for x in row) + "\n")
+
+
+def read_bins(path):
+    """(steps int64[S], records float64[S, bins, 32]) of a file written by write_bins_csv or `sphmi_run --bin-out`."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        if header != ["step", "bin"] + list(DIAG_FIELDS):
+            raise ValueError("%s: not a table of binned diagnostics" % path)
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    if not rows:
+        return np.zeros(0, np.int64), np.zeros((0, 0, len(DIAG_FIELDS)), np.float64)
+    steps, bins = [int(r[0]) for r in rows], [int(r[1]) for r in rows]
+    B = max(bins) + 1
+    if len(rows) % B or bins != list(range(B)) * (len(rows) // B):
+        raise ValueError("%s: rows are not grouped as one block of bins per step" % path)
+    rec = np.array([[float(x) for x in r[2:]] for r in rows], np.float64).reshape(-1, B, len(DIAG_FIELDS))
+    return np.array(steps[::B], np.int64), rec
+
+
+def write_vtk_bins(path, lattice, records, cfg):
+    """Legacy-VTK STRUCTURED_POINTS (binary, big-endian like write_vtk_stats) whose CELLS are the bins: cell scalars `n`, `mass`,
+    `mean_density`, `mean_pressure` and cell vectors `mean_velocity` of bin_profile(records [nz, ny, nx, 32]). A whole axis is
+    drawn as one cell from 0 to 1. Returns the bin count."""
+    o, sp, dims = _bin_lattice(lattice)
+    r = np.asarray(records, np.float64)
+    nx, ny, nz = dims
+    if r.shape != (nz, ny, nx, len(DIAG_FIELDS)):
+        raise ValueError("write_vtk_bins: records must be [nz, ny, nx, %d]" % len(DIAG_FIELDS))
+    prof = bin_profile(r, cfg)
+    whole = [dims[a] == 1 and sp[a] == 0 for a in range(3)]
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\nsphmi binned diagnostics\nBINARY\nDATASET STRUCTURED_POINTS\n")
+        f.write(("DIMENSIONS %d %d %d\n" % (nx + 1, ny + 1, nz + 1)).encode())
+        f.write(("ORIGIN %.9g %.9g %.9g\n" % tuple(0.0 if whole[a] else float(o[a]) for a in range(3))).encode())
+        f.write(("SPACING %.9g %.9g %.9g\n" % tuple(1.0 if whole[a] else float(sp[a]) for a in range(3))).encode())
+        f.write(("CELL_DATA %d\n" % (nx * ny * nz)).encode())
+        for name in ("n", "mass", "mean_density", "mean_pressure"):
+            f.write(("SCALARS %s float 1\nLOOKUP_TABLE default\n" % name).encode())
+            f.write(np.ascontiguousarray(prof[name]).astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(b"VECTORS mean_velocity float\n")
+        f.write(np.ascontiguousarray(prof["mean_velocity"]).astype(">f4").tobytes())
+        f.write(b"\n")
+    return nx * ny * nz
 
 
 def read_probes(path):
