@@ -243,6 +243,59 @@ int sph_sample_gradient_grid(sph_solver* s, const float origin[3], const float s
  * counts[0] > 0. */
 int sph_surface_normals(sph_solver* s, float* normals /* host, counts[0] x 3 */);
 
+/* ---- Surface measures (shells, area and enclosed volume of the extracted mesh; no reference counterpart) -------
+ * Input: the mesh of the last successful sph_extract_surface (V vertices as packed float3, T triangles as int32 x 3) and the
+ * lattice (origin, spacing, dims) it was cut on. The result is a function of these alone.
+ * Shells: a shell is a connected component of the graph whose nodes are the vertex ids and whose edges are the three sides of
+ * every triangle. A shell's ROOT is its lowest vertex id; shells are numbered 0 .. S-1 in ascending order of their roots;
+ * vertexShell[v] is the shell number of vertex v; a triangle belongs to the shell of its first vertex. Coincident vertices (t == 0)
+ * have different ids and are not merged.
+ * Open sides: a directed side (a, b) of a triangle is open when no triangle has the side (b, a); it is counted in the shell of
+ * a. A shell is CLOSED when it has no open side. On these meshes open sides occur only where the lattice border cuts the surface.
+ * Euler characteristic of a shell: chi = V_s - (3*T_s + open_s)/2 + T_s.
+ * Per-triangle terms, ALL IN DOUBLE, in the written order, no contraction, IEEE sqrt; v0, v1, v2 the triangle's vertices:
+ *   p_i = (double)v_i - (double)origin, per component;   e1 = p1 - p0, e2 = p2 - p0
+ *   n = e1 x e2: nx = e1y*e2z - e1z*e2y, ny = e1z*e2x - e1x*e2z, nz = e1x*e2y - e1y*e2x
+ *   a2 = sqrt((nx*nx + ny*ny) + nz*nz)             twice the area
+ *   d6 = (p0x*nx + p0y*ny) + p0z*nz                six times the signed volume of the tetrahedron to the lattice origin: positive
+ *                                                  for a drop, negative for a cavity (the normals point toward lower f)
+ *   m_c = a2 * ((p0_c + p1_c) + p2_c), c = x, y, z six times the area moment
+ * Sums are EXACT INTEGERS, so they do not depend on any order. Each term x is quantised once, q = llrint(ldexp(x, k)) (round to
+ * nearest, ties to even), and added as int64. The exponents are a function of the lattice and of T, computed on the host in
+ * double:
+ *   bT = ceil(log2(T + 1))
+ *   eL = 1 + E,  frexp(max_a (dims_a - 1) * |spacing_a|) = (., E);     eS = 1 + E',  frexp(max_a |spacing_a|) = (., E')
+ *   (E = 0 for an argument that is 0 or not finite)
+ *   kA = 60 - bT - 2*eS (for a2),   kV = 59 - bT - eL - 2*eS (for d6),   kM = 58 - bT - eL - 2*eS (for m_c)
+ * No partial sum can overflow. With sigma = 2^eS and Lambda = 2^eL: a triangle's sides lie inside one cell, so
+ * |e| <= sqrt(3) * max spacing < sqrt(3)*sigma/2, and |p| < Lambda; hence a2 < 4 sigma^2, |d6| < 8 Lambda sigma^2 and
+ * |m_c| < 16 Lambda sigma^2, every scaled term is below 2^(62 - bT), and there are at most 2^bT triangles, so every sum stays
+ * below 2^62. The bound is also enforced: a triangle with ANY scaled term ldexp(x, k) that is not below 2^(62 - bT) in magnitude
+ * (a non-finite a2 or d6 among them) adds nothing to the five sums and counts as a BAD triangle.
+ * A value is ldexp((double)sum, -k): area = value/2, volume = value/6, the centroid of the area = m / (3 * a2 sum), measured
+ * from the lattice origin.
+ * Table, one row of SPH_SHELL_WORDS int64 per shell: root, vertices, triangles, open sides, bad triangles, sum q(a2), sum q(d6),
+ * sum q(mx), q(my), q(mz). Beside it a float bounding box of six words per shell, min x, y, z, max x, y, z of the shell's
+ * vertices (float compares, canonicalised by + 0.0f as the components' boxes).
+ * counts = {shells, closed shells, open sides, bad triangles}; exps = {kA, kV, kM}.
+ * Rules: both calls are blocking, on the solver's stream, not stages (no stage timing), and do not count as a change of state.
+ * Both are read-only on every solver array and on the mesh: normals, renders, labellings and selections stay valid. The measure
+ * depends on the mesh only, so unlike sph_surface_normals it remains legal after further steps. It lives in device memory owned
+ * by the solver until the next sph_extract_surface (successful or not) or sph_destroy.
+ * Errors: SPH_ERR_ORDER before any successful extraction, and for sph_read_shells before a successful measure; SPH_ERR_INVALID
+ * for a slab solver and for null counts / exps; SPH_ERR_SIZE for more than 2^31-4097 vertices or triangles. An empty mesh is
+ * legal: all counts are 0 and exps is computed with T = 0. A pointer walk that exceeds its bound of V steps, or a triangle that
+ * names no vertex (never, unless memory is corrupted), is reported as SPH_ERR_HIP rather than followed. A failed measure leaves
+ * none behind.
+ * Device memory: 16 bytes per vertex (the union-find parents, the shell numbers and the int64 side sums that find the open
+ * sides), 104 bytes per shell, 12 bytes per 256 vertices for the scan; grown on demand and freed by sph_destroy. */
+#define SPH_SHELL_WORDS 10
+int sph_measure_surface(sph_solver* s, int64_t counts[4] /* out: shells, closed shells, open sides, bad triangles */,
+                        int32_t exps[3] /* out: kA, kV, kM */);
+/* Any pointer may be NULL. */
+int sph_read_shells(sph_solver* s, int32_t* vertexShell /* host, V */, int64_t* table /* host, S x SPH_SHELL_WORDS */,
+                    float* bbox /* host, S x 6 */);
+
 /* ---- Flow diagnostics (reductions and histograms over the particles; no reference counterpart) ------------------------------
  * State: the sorted state of the last completed step, exactly the one sph_sample_* describes (one integration step behind
  * sph_read_position). Sorted particle j is SELECTED for the region (x0,y0,z0,x1,y1,z1) when its type t = (int)position.w is

@@ -147,6 +147,7 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
                                    uint32_t typeMask, int32_t field, float iso, int64_t counts[2]) {
   ENTER(s);
   sph_derived_drop(s->mesh);
+  sph_derived_drop(s->shells);  // a measure is of the mesh it was made on
   s->meshCounts[0] = s->meshCounts[1] = 0;
   if (counts) counts[0] = counts[1] = 0;
   if (!origin || !spacing || !dims || !counts) { sph_set_error("sph_extract_surface: null pointer"); return SPH_ERR_INVALID; }
@@ -182,6 +183,7 @@ extern "C" int sph_extract_surface(sph_solver* s, const float origin[3], const f
   s->meshCounts[1] = (int64_t)totals[1];
   s->meshTypeMask = typeMask;
   s->meshField = field;
+  for (int k = 0; k < 3; k++) { s->meshOrigin[k] = origin[k]; s->meshSpacing[k] = spacing[k]; s->meshDims[k] = dims[k]; }
   sph_derived_stamp(s, s->mesh);
   counts[0] = s->meshCounts[0];
   counts[1] = s->meshCounts[1];
@@ -197,6 +199,87 @@ extern "C" int sph_read_surface(sph_solver* s, float* vertices, int32_t* triangl
   if (rc != SPH_OK) return rc;
   const size_t tBytes = sizeof(int32_t) * 3 * (size_t)s->meshCounts[1];
   if (triangles && tBytes) rc = sph_d2h(s, triangles, (char*)s->meshBuf.p + surf_bytes_align(vBytes), tBytes);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- surface measures
+// Shells, open sides, area, volume and area moments of the mesh in meshBuf (sph_shells.hip). A function of the mesh alone: the
+// measure stays valid across steps and is dropped by the next extraction. Blocks twice: for the shell count, and for the totals.
+// frexp's exponent of x, 0 for a zero or non-finite x
+static int shell_exponent(double x) {
+  int e = 0;
+  if (std::isfinite(x) && x != 0.0) frexp(x, &e);
+  return e;
+}
+
+extern "C" int sph_measure_surface(sph_solver* s, int64_t counts[4], int32_t exps[3]) {
+  ENTER(s);
+  const char* what = "sph_measure_surface";
+  sph_derived_drop(s->shells);
+  for (int k = 0; k < 4; k++) { s->shellCounts[k] = 0; if (counts) counts[k] = 0; }
+  if (!counts || !exps) { sph_set_error("%s: null pointer", what); return SPH_ERR_INVALID; }
+  if (s->hasSlab) { sph_set_error("%s: measuring a slab solver is not supported", what); return SPH_ERR_INVALID; }
+  int rc = sph_derived_check(s, s->mesh, what, "no surface has been extracted", nullptr);
+  if (rc != SPH_OK) return rc;
+  const int64_t V = s->meshCounts[0], T = s->meshCounts[1];
+  if (V > 0x7fffffffLL - 4096 || T > 0x7fffffffLL - 4096) { sph_set_error("%s: %lld vertices or %lld triangles exceed the int32 indices", what, (long long)V, (long long)T); return SPH_ERR_SIZE; }
+  // the exponents: a function of the lattice and of T (include/sphmi.h)
+  double extent = 0.0, widest = 0.0;
+  for (int k = 0; k < 3; k++) {
+    const double sp = fabs((double)s->meshSpacing[k]);
+    extent = std::max(extent, (double)(s->meshDims[k] - 1) * sp);
+    widest = std::max(widest, sp);
+  }
+  int bT = 0;
+  while (((int64_t)1 << bT) < T + 1) bT++;
+  const int eL = 1 + shell_exponent(extent), eS = 1 + shell_exponent(widest);
+  ShellArgs a = {};
+  a.V = (int)V; a.T = (int)T;
+  a.verts = (const float*)s->meshBuf.p;
+  a.tris = (const int32_t*)((const char*)s->meshBuf.p + surf_bytes_align(sizeof(float) * 3 * (size_t)V));
+  for (int k = 0; k < 3; k++) a.origin[k] = (double)s->meshOrigin[k];
+  a.kA = 60 - bT - 2 * eS; a.kV = 59 - bT - eL - 2 * eS; a.kM = 58 - bT - eL - 2 * eS;
+  a.limit = ldexp(1.0, 62 - bT);
+  exps[0] = a.kA; exps[1] = a.kV; exps[2] = a.kM;
+  int S = 0;
+  if (V > 0) {
+    rc = sph_grow_scratch(s, s->shellBuf, sphk_shells_scratch_bytes(a.V));
+    if (rc != SPH_OK) return rc;
+    uint32_t* dTotals = nullptr;
+    rc = sphk_shells_link(s, a, s->shellBuf.p, &dTotals);
+    if (rc != SPH_OK) return rc;
+    uint32_t totals[3] = {0, 0, 0};
+    rc = sph_d2h(s, totals, dTotals, sizeof(totals));  // the first wait: the table's size
+    if (rc != SPH_OK) return rc;
+    if (totals[2]) {
+      sph_set_error("%s: a parent walk or hook retry ran past its bound of V steps, or a triangle names no vertex (flags 0x%x)", what, totals[2]);
+      return SPH_ERR_HIP;
+    }
+    S = (int)totals[1];
+    rc = sph_grow_scratch(s, s->shellTable, sphk_shells_table_bytes(S));
+    if (rc != SPH_OK) return rc;
+    rc = sphk_shells_number(s, a, s->shellBuf.p, S, s->shellTable.p);
+    if (rc != SPH_OK) return rc;
+    int64_t sums[3] = {0, 0, 0};
+    rc = sph_d2h(s, sums, sphk_shells_totals(s->shellTable.p, S), sizeof(sums));  // the second: closed shells, open sides, bad triangles
+    if (rc != SPH_OK) return rc;
+    s->shellCounts[0] = S; s->shellCounts[1] = sums[0]; s->shellCounts[2] = sums[1]; s->shellCounts[3] = sums[2];
+  }
+  sph_derived_stamp(s, s->shells);
+  for (int k = 0; k < 4; k++) counts[k] = s->shellCounts[k];
+  return SPH_OK;
+}
+
+extern "C" int sph_read_shells(sph_solver* s, int32_t* vertexShell, int64_t* table, float* bbox) {
+  ENTER(s);
+  int rc = sph_derived_check(s, s->shells, "sph_read_shells", "no surface has been measured (sph_measure_surface)", nullptr);
+  if (rc != SPH_OK) return rc;
+  const size_t V = (size_t)s->meshCounts[0], S = (size_t)s->shellCounts[0];
+  if (vertexShell && V) rc = sph_d2h(s, vertexShell, sphk_shells_labels(s->shellBuf.p, (int)V), sizeof(int32_t) * V);
+  if (rc != SPH_OK) return rc;
+  if (table && S) rc = sph_d2h(s, table, s->shellTable.p, sizeof(int64_t) * SPH_SHELL_WORDS * S);
+  if (rc != SPH_OK) return rc;
+  if (bbox && S) rc = sph_d2h(s, bbox, sphk_shells_bbox(s->shellTable.p, (int)S), sizeof(float) * 6 * S);
   return rc;
 }
 

@@ -230,6 +230,12 @@ struct sph_solver {
   SphDerived mesh;                            // the last successful extraction (sph_surface_normals needs it current)
   int64_t meshCounts[2] = {};                 // ... its vertices, triangles
   uint32_t meshTypeMask = 0; int meshField = 0;  // ... and its arguments (sph_surface_normals)
+  float meshOrigin[3] = {}, meshSpacing[3] = {}; int32_t meshDims[3] = {};  // ... and the lattice it was cut on (sph_measure_surface)
+  // surface measures (sph_measure_surface / sph_read_shells): the union-find scratch with the vertices' shell numbers, and the
+  // shells' table (S x SPH_SHELL_WORDS int64, then S x 6 box words, then the call's totals)
+  SphScratch shellBuf, shellTable;
+  SphDerived shells;                  // the last successful measure: of the mesh alone, so steps do not stale it; an extraction drops it
+  int64_t shellCounts[4] = {};        // ... its shells, closed shells, open sides, bad triangles
   // connected components (sph_label_components / sph_read_components): the labelling's scratch and table, grown on demand
   SphScratch ccBuf, ccTable;
   SphDerived cc;                      // the last successful labelling (sph_component_diagnostics needs it current)
@@ -542,6 +548,32 @@ int32_t* sphk_components_labels(void* scratch, int N);   // where the N labels l
 int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float link2, void* scratch, uint32_t** totals);
 // after sphk_components_link on the same scratch: labels, and the table of C rows of 8 words (root, n, bbox as floats)
 int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table);
+// The steps of that sequence that do not depend on what the nodes and edges are (sph_shells.hip runs them on the mesh's vertices).
+// N nodes, parent[x] < 0: not a node. compress: pointer jumping on a forest no hook is running on. flatten_count: parent[x] = root
+// of x, then totals = {nodes, roots, err[0]} and off[b] = roots in the 256-node blocks before b (blockTot: 8 B per block).
+// label: labels[x] = labels[parent[x]] for the non-roots (the roots' labels are the caller's), -1 for a non-node.
+int sphk_uf_compress(sph_solver* s, int N, int32_t* parent, uint32_t* err);
+int sphk_uf_flatten_count(sph_solver* s, int N, int32_t* parent, void* blockTot, uint32_t* off, uint32_t* err, uint32_t* totals);
+int sphk_uf_label(sph_solver* s, int N, const int32_t* parent, int32_t* labels);
+
+// sph_shells.hip (shells, open sides, area, volume and area moments of the extracted mesh; read-only on the mesh)
+struct ShellArgs {
+  int V, T;
+  const float* verts;    // V x 3
+  const int32_t* tris;   // T x 3
+  double origin[3];      // (double) of the lattice origin
+  int kA, kV, kM;        // the quantisation exponents
+  double limit;          // 2^(62 - bT): a triangle with a scaled term not below it in magnitude is bad
+};
+size_t sphk_shells_scratch_bytes(int V);                // parent, labels (4 B per vertex each), the side sums (8 B), the scan's block words
+int32_t* sphk_shells_labels(void* scratch, int V);      // where the V shell numbers lie in that scratch
+size_t sphk_shells_table_bytes(int S);                  // S x (SPH_SHELL_WORDS x 8 + 24) B and the totals
+float* sphk_shells_bbox(void* table, int S);            // where the S x 6 box words lie in the table allocation
+int64_t* sphk_shells_totals(void* table, int S);        // {closed shells, open sides, bad triangles} after sphk_shells_number
+// parents of the vertices under the triangles' sides, flattened; *totals (device) = {V, shells, error flags}
+int sphk_shells_link(sph_solver* s, const ShellArgs& a, void* scratch, uint32_t** totals);
+// after sphk_shells_link on the same scratch: the shell numbers, the table's S rows and boxes, the totals
+int sphk_shells_number(sph_solver* s, const ShellArgs& a, void* scratch, int S, void* table);
 // sph_select.hip (particle selection, surface measure and compact read-back; read-only on every solver array)
 struct SelectArgs {
   SphSelector sel;

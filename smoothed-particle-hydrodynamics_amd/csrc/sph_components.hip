@@ -24,51 +24,17 @@
 #include "sph_common.h"
 #include "sph_row_walk.h"
 #include "sph_selector.h"  // the type and key pieces of the selection rule
+#include "sph_union_find.h"  // cc_load, cc_find, cc_union, cc_block_exclusive, cc_ordered: shared with sph_shells.hip
 
 #include <algorithm>
 
-#define CC_WAVE 64
-#define CC_WAVES (SPH_BLOCK / CC_WAVE)
 #define CC_SCAN_THREADS 1024
 #define CC_TABLE_WORDS 8  // root, n, then min x, y, z, max x, y, z
-
-__device__ __forceinline__ int cc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_init(SphDev d, uint32_t typeMask, int32_t* __restrict__ parent) {
   const int j = blockIdx.x * SPH_BLOCK + threadIdx.x;
   if (j >= d.N) return;
   parent[j] = sph_type_key_selected(d, typeMask, j, d.sortedPos[j]) ? j : -1;
-}
-
-// Root of x's tree as far as this lane can see it (a value that was a root when it was read). Path halving: parent[x] moves to
-// its grandparent by an atomic minimum, so that a slower lane's older value never moves it back up.
-__device__ __forceinline__ int cc_find(int32_t* parent, int x, int limit, uint32_t* err) {
-  int steps = 0;
-  int p = cc_load(parent + x);
-  while (p != x) {
-    const int g = cc_load(parent + p);
-    if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-    p = g;
-    if (++steps > limit) { atomicOr(err, 1u); break; }
-  }
-  return x;
-}
-
-// Joins the sets of a and b; returns the root the pair ended under (a member of both sets, not larger than either root seen).
-__device__ __forceinline__ int cc_union(int32_t* parent, int i, int j, int limit, uint32_t* err) {
-  int a = cc_find(parent, i, limit, err), b = cc_find(parent, j, limit, err);
-  int tries = 0;
-  while (a != b) {
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    int seen = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return lo;
-    // hi has been hooked by another lane meanwhile: go on from where it points now (a smaller member of its set)
-    a = cc_find(parent, seen, limit, err);
-    b = lo;
-    if (++tries > limit) { atomicOr(err, 2u); return lo; }
-  }
-  return a;
 }
 
 // fn(j) for every entry j of selected particle i's row that is an edge of the contract (j selected, j != i, r2 < link2 if FINITE)
@@ -145,29 +111,6 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_flatten(int N, int32_t* parent
   __hip_atomic_store(parent + j, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Exclusive prefix of v over the block's lanes (lane order = sorted order) and the block total.
-__device__ __forceinline__ uint32_t cc_block_exclusive(uint32_t v, uint32_t& total) {
-  __shared__ uint32_t waveSum[CC_WAVES];
-  const int lane = threadIdx.x & (CC_WAVE - 1), wave = threadIdx.x / CC_WAVE;
-  uint32_t inc = v;
-  for (int o = 1; o < CC_WAVE; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o, CC_WAVE);
-    if (lane >= o) inc += u;
-  }
-  if (lane == CC_WAVE - 1) waveSum[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < CC_WAVES; w++) {
-    const uint32_t s = waveSum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  total = all;
-  __syncthreads();  // waveSum is reused by a second call
-  return before + inc - v;
-}
-
 __global__ __launch_bounds__(SPH_BLOCK) void k_cc_flags(int N, const int32_t* __restrict__ parent, uint2* __restrict__ blockTot) {
   const int j = blockIdx.x * SPH_BLOCK + threadIdx.x;
   const int p = j < N ? parent[j] : -1;
@@ -222,10 +165,6 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_label(int N, const int32_t* __
   if (p == j) return;  // a root: k_cc_rank has written its label, and only roots' labels are read here
   labels[j] = p < 0 ? -1 : labels[p];
 }
-
-// order-preserving integer image of a float (signed compare) and back
-__device__ __forceinline__ int cc_ordered(float f) { const int i = __float_as_int(f); return i ^ ((i >> 31) & 0x7fffffff); }
-__device__ __forceinline__ float cc_unordered(int i) { return __int_as_float(i ^ ((i >> 31) & 0x7fffffff)); }
 
 struct CcAcc {  // per lane: members and box of the lane's particles in the current run
   int n, mn[3], mx[3];
@@ -340,6 +279,34 @@ __global__ __launch_bounds__(SPH_BLOCK) void k_cc_table_fin(int C, int32_t* tabl
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
+// The steps that do not depend on what the nodes and edges are, for sph_shells.hip too (N nodes, N >= 0; parent[x] < 0: no node).
+int sphk_uf_compress(sph_solver* s, int N, int32_t* parent, uint32_t* err) {
+  if (N <= 0) return SPH_OK;
+  hipLaunchKernelGGL(k_cc_compress, dim3(sph_blocks(N)), dim3(SPH_BLOCK), 0, s->stream, N, parent, err);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
+int sphk_uf_flatten_count(sph_solver* s, int N, int32_t* parent, void* blockTot, uint32_t* off, uint32_t* err, uint32_t* totals) {
+  const int nb = N > 0 ? sph_blocks(N) : 1;
+  if (N > 0) {
+    hipLaunchKernelGGL(k_cc_flatten, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, err);
+    SPH_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cc_flags, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, (const int32_t*)parent, (uint2*)blockTot);
+  SPH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(CC_SCAN_THREADS), 0, s->stream, (const uint2*)blockTot, nb, off, (const uint32_t*)err, totals);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
+int sphk_uf_label(sph_solver* s, int N, const int32_t* parent, int32_t* labels) {
+  if (N <= 0) return SPH_OK;
+  hipLaunchKernelGGL(k_cc_label, dim3(sph_blocks(N)), dim3(SPH_BLOCK), 0, s->stream, N, parent, labels);
+  SPH_HIP(hipGetLastError());
+  return SPH_OK;
+}
+
 static size_t cc_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // scratch layout: parent[N] | labels[N] | blockTot[nb] (uint2) | off[nb] | {err, pad} | totals[4]
@@ -378,21 +345,14 @@ int sphk_components_link(sph_solver* s, uint32_t typeMask, bool finite, float li
     if (finite) hipLaunchKernelGGL(k_cc_prelink<true>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent);
     else hipLaunchKernelGGL(k_cc_prelink<false>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent);
     SPH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cc_compress, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, err);
-    SPH_HIP(hipGetLastError());
+    const int rc = sphk_uf_compress(s, N, parent, err);
+    if (rc != SPH_OK) return rc;
     if (finite) hipLaunchKernelGGL(k_cc_hook<true>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent, err);
     else hipLaunchKernelGGL(k_cc_hook<false>, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, s->d, link2, parent, err);
     SPH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cc_flatten, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, err);
-    SPH_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_cc_flags, dim3(nb), dim3(SPH_BLOCK), 0, s->stream, N, (const int32_t*)parent, (uint2*)(base + L.blockTot));
-  SPH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(CC_SCAN_THREADS), 0, s->stream, (const uint2*)(base + L.blockTot), nb,
-                     (uint32_t*)(base + L.off), (const uint32_t*)err, (uint32_t*)(base + L.totals));
-  SPH_HIP(hipGetLastError());
   *totals = (uint32_t*)(base + L.totals);
-  return SPH_OK;
+  return sphk_uf_flatten_count(s, N, parent, base + L.blockTot, (uint32_t*)(base + L.off), err, *totals);
 }
 
 int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table) {
@@ -404,8 +364,8 @@ int sphk_components_number(sph_solver* s, void* scratch, int C, int32_t* table) 
   int32_t* labels = (int32_t*)(base + L.labels);
   hipLaunchKernelGGL(k_cc_rank, dim3(L.nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, (const uint32_t*)(base + L.off), labels, table);
   SPH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cc_label, dim3(L.nb), dim3(SPH_BLOCK), 0, s->stream, N, parent, labels);
-  SPH_HIP(hipGetLastError());
+  const int rc = sphk_uf_label(s, N, parent, labels);
+  if (rc != SPH_OK) return rc;
   if (C <= 0) return SPH_OK;
   // 4096 particles per wave where there are enough of them to fill the device, never less than one wave step
   int perWave = 4096;

@@ -108,6 +108,11 @@ class owHIPSolver {
     check(sph_sample_gradient_grid(s_, origin, spacing, dims, typeMask, out), "sampleGradientGrid");
   }
   void surfaceNormals(float* normals) { check(sph_surface_normals(s_, normals), "surfaceNormals"); }
+  // beyond the reference: shells, open sides and exact sums of area, volume and area moment of the last extractSurface mesh
+  // (include/sphmi.h, sph_measure_surface); counts = {shells, closed shells, open sides, bad triangles}, exps = {kA, kV, kM};
+  // readShells copies the shell number per vertex, the table (shells x SPH_SHELL_WORDS) and the boxes (shells x 6); any may be null
+  void measureSurface(int64_t counts[4], int32_t exps[3]) { check(sph_measure_surface(s_, counts, exps), "measureSurface"); }
+  void readShells(int32_t* vertexShell, int64_t* table, float* bbox) { check(sph_read_shells(s_, vertexShell, table, bbox), "readShells"); }
   // beyond the reference: reductions over the particles inside `count` (1..16) regions (x0,y0,z0,x1,y1,z1), SPH_DIAG_WORDS doubles
   // each, and the distribution of one per-particle quantity in bins + 2 counters (include/sphmi.h, sph_diagnostics / sph_histogram)
   void diagnostics(const float* regions6, int count, unsigned int typeMask, double* out) {

@@ -16,6 +16,9 @@
 //   ... --sample-gradients      with --sample-grid: also write DIR/gradients_<steps done>.bin, sph_sample_gradient_grid's
 //        32-word records on the same lattice (NZ x NY x NX x 32; sphmi.frames.read_gradients)
 //   ... --surface-normals       with --surface-grid: the PLY files carry unit vertex normals (sph_surface_normals) as nx ny nz
+//   ... --surface-shells        with --surface-grid: measure each extracted mesh on the device (sph_measure_surface) and write
+//        DIR/shells_<steps done>.csv beside the PLY file: one row per shell with its ten exact int64 words and its bounding box
+//        (sphmi.frames.read_shells / shell_summary)
 //   ... --diagnostics-every K --diagnostics-out FILE.csv [--diagnostics-region X0 Y0 Z0 X1 Y1 Z1]...
 //        after every K-th step, sph_diagnostics of the liquid and elastic particles over the whole scene (region 0) and up to 15
 //        further regions ("inf" / "-inf" are accepted as bounds): one CSV row per report and region (step, region, the 32 record
@@ -163,6 +166,20 @@ struct Watch {  // owHelper::refreshTime / watch_report (owHelper.cpp:44-57,1806
   double elapsed() const { return t1 - t0; }
 };
 
+// the table of sph_read_shells as text (sphmi.frames.write_shells_csv writes the same file)
+static void write_shells_csv(const std::string& path, const std::vector<int64_t>& table, const std::vector<float>& boxes, const int32_t exps[3]) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) throw std::runtime_error("cannot write " + path);
+  fprintf(f, "# exps %d %d %d\nshell,root,vertices,triangles,open,bad,a2,d6,mx,my,mz,min_x,min_y,min_z,max_x,max_y,max_z\n", exps[0], exps[1], exps[2]);
+  for (size_t r = 0; r < table.size() / SPH_SHELL_WORDS; r++) {
+    fprintf(f, "%zu", r);
+    for (int w = 0; w < SPH_SHELL_WORDS; w++) fprintf(f, ",%lld", (long long)table[r * SPH_SHELL_WORDS + w]);
+    for (int w = 0; w < 6; w++) fprintf(f, ",%.9g", (double)boxes[r * 6 + w]);
+    fputc('\n', f);
+  }
+  if (fclose(f) != 0) throw std::runtime_error("cannot write " + path);
+}
+
 // binary little-endian PLY: float x y z (and nx ny nz when normals are given) per vertex, list uchar int vertex_indices per
 // face (sphmi.frames.write_ply)
 static void write_ply(const std::string& path, const std::vector<float>& verts, const std::vector<int32_t>& tris,
@@ -287,7 +304,7 @@ int main(int argc, char** argv) {
   double box[3] = {0, 0, 0}; int lat[3] = {0, 0, 0};
   int sampleDims[3] = {0, 0, 0}, sampleEvery = 0; const char* sampleDir = nullptr;
   int surfDims[3] = {0, 0, 0}, surfEvery = 0; const char* surfDir = nullptr; float surfIso = 0.5f;
-  bool sampleGradients = false, surfNormals = false;
+  bool sampleGradients = false, surfNormals = false, surfShells = false;
   int diagEvery = 0; bool diagEverySeen = false; const char* diagFile = nullptr;
   std::vector<float> diagRegions = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};  // region 0: everything
   int compEvery = 0, compTop = SPH_DIAG_MAX_REGIONS; bool compSeen = false, compTypesSeen = false; const char* compFile = nullptr;
@@ -520,6 +537,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--diagnostics-out") && i + 1 < argc) diagFile = argv[++i];
     else if (!strcmp(argv[i], "--diagnostics-region") && i + 6 < argc) { for (int k = 0; k < 6; k++) diagRegions.push_back((float)atof(argv[++i])); }
     else if (!strcmp(argv[i], "--surface-normals")) surfNormals = true;
+    else if (!strcmp(argv[i], "--surface-shells")) surfShells = true;
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool sampling = sampleDims[0] > 0 || sampleEvery > 0 || sampleDir;
@@ -545,6 +563,7 @@ int main(int argc, char** argv) {
   }
   if (sampleGradients && !sampling) { fprintf(stderr, "--sample-gradients needs --sample-grid\n"); return 2; }
   if (surfNormals && !surfacing) { fprintf(stderr, "--surface-normals needs --surface-grid\n"); return 2; }
+  if (surfShells && !surfacing) { fprintf(stderr, "--surface-shells needs --surface-grid\n"); return 2; }
   const int diagCount = (int)(diagRegions.size() / 6);
   const bool diagnosing = diagEverySeen || diagFile || diagCount > 1;
   if (diagnosing && (diagEvery <= 0 || !diagFile)) {
@@ -968,6 +987,16 @@ int main(int argc, char** argv) {
         write_ply(std::string(surfDir) + "/surface_" + std::to_string(iterationCount + 1) + ".ply", meshVerts, meshTris,
                   surfNormals ? &meshNormals : nullptr);
         helper.report("_extractSurface: \t%9.3f ms\n");
+        if (surfShells) {
+          int64_t shellCounts[4];
+          int32_t exps[3];
+          ocl_solver->measureSurface(shellCounts, exps);
+          std::vector<int64_t> table((size_t)shellCounts[0] * SPH_SHELL_WORDS);
+          std::vector<float> boxes((size_t)shellCounts[0] * 6);
+          ocl_solver->readShells(nullptr, table.data(), boxes.data());
+          write_shells_csv(std::string(surfDir) + "/shells_" + std::to_string(iterationCount + 1) + ".csv", table, boxes, exps);
+          helper.report("_measureSurface: \t%9.3f ms\n");
+        }
       }
       if (binSeen && (iterationCount + 1) % binEvery == 0) {
         ocl_solver->binDiagnostics(&binGrid, binRecords.data());

@@ -18,6 +18,8 @@ ABI_VERSION = 2
 MAX_BODIES = 16  # SPH_MAX_BODIES: kinematic-body slots per solver
 SAMPLE_WORDS = 8  # sph_sample_* record: density, shepard, vx, vy, vz, pressure, count, 0
 SURFACE_FIELDS = 6  # sph_extract_surface: record words 0..5
+SHELL_WORDS = 10  # SPH_SHELL_WORDS: int64 words of one row of sph_read_shells' table
+SHELL_FIELDS = ("root", "vertices", "triangles", "open", "bad", "a2", "d6", "mx", "my", "mz")  # ... and their names
 DIAG_WORDS = 32  # sph_diagnostics record (frames.DIAG_FIELDS)
 DIAG_MAX_REGIONS = 16
 HIST_MAX_BINS = 4096
@@ -224,7 +226,7 @@ EXPORTED_SYMBOLS = ["sph_create", "sph_destroy", "sph_run_pcisph_integrate", "sp
                     "sph_slab_rebuild", "sph_particle_count", "sph_slab_read", "sph_slab_rebuild_framed", "sph_slab_rebuild_finish",
                     "sph_slab_liquid_signature", "sph_slab_set_record_format", "sph_stream_wait_event", "sph_sample_points",
                     "sph_sample_grid", "sph_extract_surface", "sph_read_surface", "sph_sample_gradient_points",
-                    "sph_sample_gradient_grid", "sph_surface_normals", "sph_diagnostics", "sph_histogram", "sph_label_components",
+                    "sph_sample_gradient_grid", "sph_surface_normals", "sph_measure_surface", "sph_read_shells", "sph_diagnostics", "sph_histogram", "sph_label_components",
                     "sph_read_components", "sph_component_diagnostics", "sph_particle_measure", "sph_select_particles",
                     "sph_read_selection", "sph_elastic_measure", "sph_muscle_diagnostics", "sph_membrane_measure",
                     "sph_render_particles", "sph_read_render", "sph_render_mesh", "sph_read_render_triangles", "sph_force_measure", "sph_force_diagnostics", "sph_remove_region",
@@ -329,6 +331,8 @@ def device_lib():
         L.sph_sample_gradient_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_sample_gradient_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.sph_surface_normals.argtypes = [C.c_void_p, C.c_void_p]
+        L.sph_measure_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sph_read_shells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sph_diagnostics.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.sph_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.sph_label_components.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
@@ -908,6 +912,7 @@ class owHIPSolver:
         o, sp, dm = _lattice(origin, spacing, dims)
         counts = np.zeros(2, np.int64)
         self._mesh_vertices = 0  # (a failed extraction leaves no mesh behind)
+        self._shells = 0  # (and any extraction drops the measure of the mesh before)
         self._chk(self._L.sph_extract_surface(self._h, _ptr(o), _ptr(sp), _ptr(dm), type_mask(types), int(field), float(iso),
                                               _ptr(counts)))
         self._mesh_vertices = int(counts[0])
@@ -941,6 +946,32 @@ class owHIPSolver:
         out = np.empty((n, 3), np.float32)
         self._chk(self._L.sph_surface_normals(self._h, _ptr(out) if out.size else None))
         return out
+
+    # --- surface measures (sph_measure_surface / sph_read_shells): shells, area and enclosed volume of the extracted mesh ---
+    def measure_surface(self):
+        """Measure the mesh of the last extract_surface on the device: the shells it consists of (connected pieces: drops,
+        cavities, sheets cut by the lattice border), their open sides, and per shell exact integer sums of area, signed volume
+        and area moment (include/sphmi.h). Returns {"shells", "closed", "open_sides", "bad_triangles", "kA", "kV", "kM"}; the
+        table stays on the device until the next extract_surface (surface_shells()). Legal after further steps: it is a
+        function of the mesh alone. frames.shell_summary turns the table into areas, volumes and centroids."""
+        counts = np.zeros(4, np.int64)
+        exps = np.zeros(3, np.int32)
+        self._shells = 0  # (a failed measure leaves none behind)
+        self._chk(self._L.sph_measure_surface(self._h, _ptr(counts), _ptr(exps)))
+        self._shells = int(counts[0])
+        return {"shells": int(counts[0]), "closed": int(counts[1]), "open_sides": int(counts[2]), "bad_triangles": int(counts[3]),
+                "kA": int(exps[0]), "kV": int(exps[1]), "kM": int(exps[2])}
+
+    def surface_shells(self):
+        """The last measure_surface: (vertexShell int32[V], table int64[S, 10], bbox float32[S, 6]); the table's columns are
+        named by SHELL_FIELDS, bbox is min x, y, z, max x, y, z of each shell's vertices."""
+        n = getattr(self, "_mesh_vertices", 0)
+        c = getattr(self, "_shells", 0)  # 0 without a measure: the library reports SPH_ERR_ORDER
+        vs = np.empty(n, np.int32)
+        table = np.empty((c, SHELL_WORDS), np.int64)
+        bb = np.empty((c, 6), np.float32)
+        self._chk(self._L.sph_read_shells(self._h, _ptr(vs) if n else None, _ptr(table) if c else None, _ptr(bb) if c else None))
+        return vs, table, bb
 
     # --- flow diagnostics (sph_diagnostics / sph_histogram): the sorted state of the last completed step ---
     def diagnostics(self, regions=None, types=(1, 2)):

@@ -446,6 +446,81 @@ def read_components_csv(path):
     return steps, ids, rc, bb, rec
 
 
+# ---- surface measures (owHIPSolver.measure_surface / surface_shells; include/sphmi.h, sph_measure_surface) ----
+SHELL_FIELDS = ("root", "vertices", "triangles", "open", "bad", "a2", "d6", "mx", "my", "mz")
+SHELL_BBOX_FIELDS = COMPONENT_FIELDS[2:]
+SHELL_KINDS = ("drop", "cavity", "open")
+
+
+def _shell_value(total, k):
+    """ldexp((double)sum, -k) of an exact integer sum."""
+    return float(np.ldexp(np.float64(int(total)), -int(k)))
+
+
+def shell_summary(table, exps, origin):
+    """Physical numbers from the table of surface_shells() and the exponents (kA, kV, kM) of measure_surface(); `origin` is the
+    origin of the lattice the mesh was extracted on. Per shell (arrays of length S): area, volume (signed: negative for a
+    cavity; meaningful for closed shells), centroid float64[S, 3] of the area in scene coordinates (NaN for a shell without
+    area), chi (Euler characteristic), genus (closed shells, else -1), closed, kind (an index into SHELL_KINDS: drop, cavity,
+    open) and radius (of the sphere with the shell's |volume|). "totals": the whole mesh from the exact integer column sums
+    (shells, closed, vertices, triangles, open, bad, area, volume, centroid)."""
+    t = np.asarray(table, np.int64).reshape(-1, len(SHELL_FIELDS))
+    kA, kV, kM = (int(x) for x in np.asarray(exps).reshape(3))
+    o = np.asarray(origin, np.float32).astype(np.float64).reshape(3)
+    S = t.shape[0]
+    a2 = np.ldexp(t[:, 5].astype(np.float64), -kA)
+    d6 = np.ldexp(t[:, 6].astype(np.float64), -kV)
+    m = np.ldexp(t[:, 7:10].astype(np.float64), -kM)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        centroid = o[None, :] + m / (3.0 * a2[:, None])
+    closed = t[:, 3] == 0
+    twice_edges = 3 * t[:, 2] + t[:, 3]
+    chi = t[:, 1] - twice_edges // 2 + t[:, 2]
+    genus = np.where(closed & (chi % 2 == 0), (2 - chi) // 2, -1)
+    volume = d6 / 6.0
+    kind = np.where(~closed, 2, np.where(volume < 0, 1, 0)).astype(np.int32)
+    cols = [sum(int(x) for x in t[:, c]) for c in range(len(SHELL_FIELDS))]  # exact, whatever the number of shells
+    ta2 = _shell_value(cols[5], kA)
+    tm = np.array([_shell_value(cols[7 + c], kM) for c in range(3)])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tc = o + tm / (3.0 * ta2)
+    totals = dict(shells=S, closed=int(closed.sum()), vertices=cols[1], triangles=cols[2], open=cols[3], bad=cols[4],
+                  area=ta2 / 2.0, volume=_shell_value(cols[6], kV) / 6.0, centroid=tc)
+    return dict(area=a2 / 2.0, volume=volume, centroid=centroid, chi=chi, genus=genus, closed=closed, kind=kind,
+                radius=np.cbrt(3.0 * np.abs(volume) / (4.0 * np.pi)), totals=totals)
+
+
+def write_shells_csv(path, table, bbox, exps):
+    """The table of surface_shells() as text, lossless: a line `# exps kA kV kM`, a header, then one row per shell: its number,
+    the ten int64 words and the bounding box as %.9g (float32 round trip). `sphmi_run --surface-shells` writes the same file."""
+    t = np.asarray(table, np.int64).reshape(-1, len(SHELL_FIELDS))
+    bb = np.asarray(bbox, np.float32).reshape(-1, 6)
+    if bb.shape[0] != t.shape[0]:
+        raise ValueError("write_shells_csv: table and bbox must have one row per shell")
+    with open(path, "w") as f:
+        f.write("# exps %d %d %d\n" % tuple(int(x) for x in np.asarray(exps).reshape(3)))
+        f.write("shell," + ",".join(SHELL_FIELDS) + "," + ",".join(SHELL_BBOX_FIELDS) + "\n")
+        for r in range(t.shape[0]):
+            f.write("%d," % r + ",".join("%d" % int(x) for x in t[r]) + "," + ",".join("%.9g" % float(x) for x in bb[r]) + "\n")
+
+
+def read_shells(path):
+    """(table int64[S, 10], bbox float32[S, 6], exps int32[3]) of a file written by write_shells_csv or `sphmi_run
+    --surface-shells`."""
+    with open(path) as f:
+        first = f.readline().split()
+        header = f.readline().strip().split(",")
+        if first[:2] != ["#", "exps"] or len(first) != 5 or header != ["shell"] + list(SHELL_FIELDS) + list(SHELL_BBOX_FIELDS):
+            raise ValueError("%s: not a shells table" % path)
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    S = len(rows)
+    if [int(r[0]) for r in rows] != list(range(S)):
+        raise ValueError("%s: shells out of order" % path)
+    table = np.array([[int(x) for x in r[1:11]] for r in rows], np.int64).reshape(S, len(SHELL_FIELDS))
+    bb = np.array([[float(x) for x in r[11:17]] for r in rows], np.float64).astype(np.float32).reshape(S, 6)
+    return table, bb, np.array([int(x) for x in first[2:]], np.int32)
+
+
 # ---- particle selection (owHIPSolver.select / selection; include/sphmi.h, sph_select_particles) ----
 SELECT_FIELDS = ("x", "y", "z", "type", "vx", "vy", "vz", "density", "pressure", "neighbors", "surface", "unused11")
 
